@@ -17,7 +17,12 @@ SURVEY.md 8(d): T = 256 ids (96 reference + 160 target), 6.0 s reference clip (1
 
 N > 1: one process per GPU, rank 0 packs the weights and RCCL-broadcasts the flat buffer over xGMI,
 every rank synthesises its own batch of 32 (weak scaling, no data-path collective).
-Prints ONE JSON line on rank 0.  The CPU oracle is used only for the reported cpu_baseline leg.
+Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds what takes runs of its own: the
+PCIe-inclusive steps (`pcie_inclusive`), the one-lane pass with HIP events per kernel class (`kernel_classes`, `roofline`,
+`other_rooflines`, `vocoder_stages`, `lanes`), the GroupNorm micro-measurement and the CPU oracle's rate (`cpu_baseline`, the only
+use of the oracle here).  `--dump-outputs DIR` writes what the timed call returned in the last timed step (rank 0) as .npy files.
 """
 import argparse
 import json
@@ -42,6 +47,7 @@ GEN_FRAMES = 1037
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense, MI355X_MICROARCH.md
 MFMA_F32_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this many bytes of .npy data in all
 
 
 def synth_reference_clip(i: int, n: int = REF_SAMPLES) -> torch.Tensor:
@@ -251,6 +257,40 @@ def serve(a):
                                              f"max_requests={a.batch}, max_wait_ms={a.max_wait_ms}", "spec": a.spec}, **out}), flush=True)
 
 
+def dump_outputs(dirname: str, outs, budget: int = DUMP_BUDGET_BYTES):
+    """--dump-outputs: what `synthesize_batch` (or the captured graph) handed its caller in one step, per batch: the final mel state
+    `mel` [B, N, n_mel], the int16 PCM `pcm` [B, samples] and its lengths `pcm_len` [B], as float32 (mel, pcm: exact) and float64
+    (pcm_len) .npy files; with several batches every name gets a `_b<i>` suffix.  Over `budget` bytes in all, the same fixed, seeded
+    sample of batch items is written for every array of a batch, and its item indices as `items[_b<i>].npy`.  Returns the names."""
+    import numpy as np
+    sfx = [("" if len(outs) == 1 else f"_b{i}") for i in range(len(outs))]
+    rows = [{"mel": o[0].float(), "pcm": o[1].float(), "pcm_len": o[2].double()} for o in outs]
+    total = sum(t.numel() * t.element_size() for r in rows for t in r.values())
+    sel = [None] * len(rows)
+    if total > budget:
+        g = torch.Generator().manual_seed(SEED)
+        room = budget - 2 ** 20                     # headroom for the item indices and the .npy headers
+        for i, r in enumerate(rows):
+            B = r["pcm_len"].shape[0]
+            keep = min(B, B * room // total)        # the same fraction of every batch: sum of kept bytes <= room
+            sel[i] = torch.randperm(B, generator=g)[:keep].sort().values
+    os.makedirs(dirname, exist_ok=True)
+    names, written = [], 0
+    for i, r in enumerate(rows):
+        arrays = {k: (t if sel[i] is None else t.index_select(0, sel[i].to(t.device))) for k, t in r.items()}
+        if sel[i] is not None:
+            arrays["items"] = sel[i].double()
+        for k, t in arrays.items():
+            a = t.detach().cpu().numpy()
+            assert a.dtype in (np.float32, np.float64)
+            path = os.path.join(dirname, k + sfx[i] + ".npy")
+            np.save(path, a)
+            names.append(k + sfx[i])
+            written += os.path.getsize(path)
+    assert written <= budget, (written, budget)
+    return names
+
+
 def cpu_baseline(spec, weights, nfe_step):
     """Oracle (kind 'port') on the host cores, bounded sample, rank 0 only."""
     from oracle.vv_oracle import Oracle
@@ -310,7 +350,13 @@ def main():
                     help="batch32 = the headline metric (BASELINE configs[2]); mixed256 = configs[3] (32 ragged units per GPU); "
                          "longform = configs[4] (4k-char text through TTSEngine, 8 chunks in flight, hipGraph vocoder); "
                          "serve = the batching front end under 16 client threads next to serial TTSEngine.synthesize calls")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the PCIe-inclusive steps, the per-kernel-class pass with its "
+                    "rooflines, the GroupNorm micro-measurement and the CPU baseline (off by default: a plain run times the K steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed call returned in the last one "
+                    "(mel, pcm, pcm_len; rank 0) to DIR/<name>.npy as float32 / float64, at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.workload == "longform":
         return longform(a)
     if a.workload == "serve":
@@ -418,7 +464,7 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    if a.warmup and a.pcie_steps and not a.pcie:
+    if a.full and a.warmup and a.pcie_steps and not a.pcie:
         step(pcie=True)                                   # allocates the pinned landing buffers outside every timed region
     torch.cuda.synchronize()
     if dist is not None:
@@ -439,10 +485,13 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert abs(sum(float(o[2].sum().item()) for o in out) / spec.sample_rate - audio_s_rank) < 1e-3
+    if a.dump_outputs and rank == 0:
+        names = dump_outputs(a.dump_outputs, out)
+        print(f"bench: wrote {', '.join(names)} to {a.dump_outputs}", file=sys.stderr, flush=True)
     pcie_inclusive = None
     if a.pcie:                                            # what landed on the host is the PCM the device produced
         assert all(torch.equal(h[1], o[2].cpu()) and int(h[0].abs().max()) > 0 for h, o in zip(pcm_host, out))
-    elif a.pcie_steps > 0 and dist is None:
+    elif a.full and a.pcie_steps > 0 and dist is None:
         # the same step with its PCIe legs (pinned host int16 clips / ids / noise -> H2D, int16 PCM -> D2H to pinned memory): reported
         # beside `value`, never as `value` (the contract: inputs resident in HBM when the timed region starts)
         step(pcie=True)
@@ -476,99 +525,100 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- per-kernel-class timing with HIP events on the launch stream (one extra, untimed pass)
-    # The timed steps run the Euler loop as two half batches on two streams (option "lanes": one lane's kernel tails are filled by the
-    # other's kernels).  A kernel's own rate is measured with the chip to itself: the profiled pass runs ONE lane, so the class times
-    # below are each kernel alone and their sum exceeds the two-lane step time by what the overlap recovers.
-    eng.prof_enable(True)
-    was_graph, a.graph_steps = a.graph_steps, False       # events cannot be recorded inside a replayed graph: the profiled pass runs eagerly
-    eng.set_option("lanes", 1)
-    torch.cuda.synchronize()
-    t_cls = time.perf_counter()
-    step()
-    class_pass_ms = (time.perf_counter() - t_cls) * 1e3
-    eng.set_option("lanes", lanes_opt)
-    a.graph_steps = was_graph
-    prof = eng.prof_collect()
-    eng.prof_enable(False)
-    gm = prof["gemm"]
-    peak = MFMA_BF16_PEAK_TFLOPS if a.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS
-    ach = gm["flops"] / (gm["ms"] * 1e-3) / 1e12 if gm["ms"] > 0 else 0.0
-    # HBM-side bytes per launch: PMC counters cannot be read from inside the process, so the figure comes from the committed
-    # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.py).  Passes over THIS command die inside the profiler
-    # (profiles/r02/gemm_notes.md, stack + maps committed), so the file is taken over tools/gemm_ab.py at the block's four shapes; the
-    # file names the program it was taken over ("how_short"), and that string is what traffic_source reports.
-    traffic, traffic_src = None, None
-    here = os.path.dirname(os.path.abspath(__file__))
-    for rel in ("profiles/r05/gemm_pmc_traffic.json", "profiles/r04/gemm_pmc_traffic.json", "profiles/r03/gemm_pmc_traffic.json", "profiles/r02/gemm_pmc_traffic.json", "profiles/r01/gemm_pmc_traffic.json"):
-        tf = os.path.join(here, rel)
-        if a.dtype == "bf16" and a.workload == "batch32" and a.batch == 32 and a.spec == "full" and os.path.exists(tf):
-            with open(tf) as fh:
-                tj = json.load(fh)
-            traffic, traffic_src = tj["traffic_bytes_per_launch"], rel + " (" + tj.get("how_short", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 x2 read correction") + ")"
-            break
-    kname = "gemm_pp_kernel (K6, persistent 256x256x64 ping-pong, bf16 MFMA 16x16x32)" if a.dtype == "bf16" else "gemm_kernel (K6, f32 MFMA 32x32x2)"
-    roofline = {"bound": "mfma", "kernel": kname, "achieved": round(ach, 2), "peak": peak,
-                "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "launches": gm["launches"], "avg_launch_ms": round(gm["ms"] / max(gm["launches"], 1), 4)}
-    if a.dtype == "bf16":
-        # peak is the nominal 2.4 GHz figure; measured with the stamp build on one box (not in this run): the chip holds this loop at 1.8-1.9 GHz on
-        # random operands and at 2.23-2.35 GHz on all-zero operands (same cycles, 19 % less time)
-        roofline["clock_note"] = "power-limited clock: profiles/r03/gemm_notes.md (power probe)"
-    def _rf(name, bound, peak):
-        v = prof[name]
-        if not v["launches"] or v["ms"] <= 0:
-            return None
-        ach = (v["flops"] / 1e12 if bound == "mfma" else v["bytes"] / 1e9) / (v["ms"] * 1e-3)
-        return {"bound": bound, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-                "frac": round(ach / peak, 4), "launches": v["launches"]}
-    other_rooflines = {"attention (K8, bf16 MFMA)": _rf("attention", "mfma", peak),
-                       "layernorm+residual (K4)": _rf("norm", "hbm", HBM_PEAK_GBS),
-                       "pos-conv (K3, bf16 MFMA)": _rf("posconv", "mfma", peak),
-                       # x3: six bf16 piece products per fp32 product, so the matrix roof for ALGORITHMIC flops is the bf16 peak / 6
-                       ("vocoder convs (K11x: fp32 products as six bf16 MFMA terms; roof = bf16 peak / 6)" if voc_x3 else "vocoder convs (K11/K12, f32 MFMA)"):
-                           _rf("voc_conv", "mfma", round(MFMA_BF16_PEAK_TFLOPS / 6, 1) if voc_x3 else MFMA_F32_PEAK_TFLOPS),
-                       "vocoder convs, HBM side (algorithmic bytes per launch)": _rf("voc_conv", "hbm", HBM_PEAK_GBS),
-                       "vocoder conv_post+tanh+int16 (K13)": _rf("voc_post", "hbm", HBM_PEAK_GBS)}
-    # ---- the vocoder convs by stage: one entry per upsampler / MRF stack against the roof SURVEY 8(a) names for it
-    # (K11 stages 0-1 and K12: matrix; K11 stages 2-3: HBM), with the other side beside it
-    voc_peak = round(MFMA_BF16_PEAK_TFLOPS / 6, 1) if voc_x3 else MFMA_F32_PEAK_TFLOPS
-    voc_stages = {}
-    for name, bound in (("voc_pre", "hbm"), ("voc_up0", "mfma"), ("voc_up1", "mfma"), ("voc_up2", "hbm"), ("voc_up3", "hbm"),
-                        ("voc_mrf0", "mfma"), ("voc_mrf1", "mfma"), ("voc_mrf2", "mfma"), ("voc_mrf3", "mfma")):
-        v = prof.get(name)
-        if not v or not v["launches"] or v["ms"] <= 0:
-            continue
-        tf, gb = v["flops"] / 1e12 / (v["ms"] * 1e-3), v["bytes"] / 1e9 / (v["ms"] * 1e-3)
-        voc_stages[name] = {"bound": bound, "ms": round(v["ms"], 3), "launches": v["launches"], "TFLOP/s": round(tf, 2), "frac_mfma": round(tf / voc_peak, 4),
-                            "GB/s": round(gb, 1), "frac_hbm": round(gb / HBM_PEAK_GBS, 4), "flop_per_byte": round(v["flops"] / max(v["bytes"], 1.0), 1)}
-        if bound == "hbm" and name != "voc_pre":
-            other_rooflines[f"vocoder upsample stage {name[-1]} (K11, HBM-bound by SURVEY 8a)"] = {
-                "bound": "hbm", "achieved": round(gb, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gb / HBM_PEAK_GBS, 4), "launches": v["launches"]}
-    # ---- K5 GroupNorm: not on the synthesis path of this architecture (the survey lists it "as used"); one micro-measurement so that it has a number
-    if a.spec == "full":
-        gB, gC, gT, gG = a.batch, 512, GEN_FRAMES, 32
-        gx = torch.randn(gB, gC, gT, device=device)
-        gy, gg, gb_ = torch.empty_like(gx), torch.ones(gC, device=device), torch.zeros(gC, device=device)
-        st_ = torch.cuda.current_stream(device)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for it in range(25):
-            if it == 5:
-                e0.record(st_)
-            eng._check(eng.lib.vv_groupnorm(eng.ctx, gx.data_ptr(), gy.data_ptr(), gg.data_ptr(), gb_.data_ptr(), gB, gC, gT, gG, 1e-5, 0, st_.cuda_stream))
-        e1.record(st_)
+    if a.full:
+        # ---- per-kernel-class timing with HIP events on the launch stream (one extra, untimed pass)
+        # The timed steps run the Euler loop as two half batches on two streams (option "lanes": one lane's kernel tails are filled by the
+        # other's kernels).  A kernel's own rate is measured with the chip to itself: the profiled pass runs ONE lane, so the class times
+        # below are each kernel alone and their sum exceeds the two-lane step time by what the overlap recovers.
+        eng.prof_enable(True)
+        was_graph, a.graph_steps = a.graph_steps, False       # events cannot be recorded inside a replayed graph: the profiled pass runs eagerly
+        eng.set_option("lanes", 1)
         torch.cuda.synchronize()
-        g_ms = e0.elapsed_time(e1) / 20
-        g_gbs = 8.0 * gx.numel() / 1e9 / (g_ms * 1e-3)
-        other_rooflines["groupnorm (K5; off the synthesis path, micro-measured)"] = {
-            "bound": "hbm", "achieved": round(g_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(g_gbs / HBM_PEAK_GBS, 4), "launches": 20,
-            "shape": f"[{gB}, {gC}, {gT}] f32, {gG} groups; algorithmic bytes = one read + one write"}
-    classes = {}
-    for k, v in prof.items():
-        if v["launches"] and not (k.startswith("voc_") and k not in ("voc_conv", "voc_post")):      # the stage classes repeat voc_conv: `vocoder_stages`
-            classes[k] = {"ms": round(v["ms"], 2), "launches": v["launches"],
-                          "TFLOP/s": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None,
-                          "GB/s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
+        t_cls = time.perf_counter()
+        step()
+        class_pass_ms = (time.perf_counter() - t_cls) * 1e3
+        eng.set_option("lanes", lanes_opt)
+        a.graph_steps = was_graph
+        prof = eng.prof_collect()
+        eng.prof_enable(False)
+        gm = prof["gemm"]
+        peak = MFMA_BF16_PEAK_TFLOPS if a.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS
+        ach = gm["flops"] / (gm["ms"] * 1e-3) / 1e12 if gm["ms"] > 0 else 0.0
+        # HBM-side bytes per launch: PMC counters cannot be read from inside the process, so the figure comes from the committed
+        # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.py).  Passes over THIS command die inside the profiler
+        # (profiles/r02/gemm_notes.md, stack + maps committed), so the file is taken over tools/gemm_ab.py at the block's four shapes; the
+        # file names the program it was taken over ("how_short"), and that string is what traffic_source reports.
+        traffic, traffic_src = None, None
+        here = os.path.dirname(os.path.abspath(__file__))
+        for rel in ("profiles/r05/gemm_pmc_traffic.json", "profiles/r04/gemm_pmc_traffic.json", "profiles/r03/gemm_pmc_traffic.json", "profiles/r02/gemm_pmc_traffic.json", "profiles/r01/gemm_pmc_traffic.json"):
+            tf = os.path.join(here, rel)
+            if a.dtype == "bf16" and a.workload == "batch32" and a.batch == 32 and a.spec == "full" and os.path.exists(tf):
+                with open(tf) as fh:
+                    tj = json.load(fh)
+                traffic, traffic_src = tj["traffic_bytes_per_launch"], rel + " (" + tj.get("how_short", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, gfx950 x2 read correction") + ")"
+                break
+        kname = "gemm_pp_kernel (K6, persistent 256x256x64 ping-pong, bf16 MFMA 16x16x32)" if a.dtype == "bf16" else "gemm_kernel (K6, f32 MFMA 32x32x2)"
+        roofline = {"bound": "mfma", "kernel": kname, "achieved": round(ach, 2), "peak": peak,
+                    "unit": "TFLOP/s", "frac": round(ach / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "launches": gm["launches"], "avg_launch_ms": round(gm["ms"] / max(gm["launches"], 1), 4)}
+        if a.dtype == "bf16":
+            # peak is the nominal 2.4 GHz figure; measured with the stamp build on one box (not in this run): the chip holds this loop at 1.8-1.9 GHz on
+            # random operands and at 2.23-2.35 GHz on all-zero operands (same cycles, 19 % less time)
+            roofline["clock_note"] = "power-limited clock: profiles/r03/gemm_notes.md (power probe)"
+        def _rf(name, bound, peak):
+            v = prof[name]
+            if not v["launches"] or v["ms"] <= 0:
+                return None
+            ach = (v["flops"] / 1e12 if bound == "mfma" else v["bytes"] / 1e9) / (v["ms"] * 1e-3)
+            return {"bound": bound, "achieved": round(ach, 2), "peak": peak, "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                    "frac": round(ach / peak, 4), "launches": v["launches"]}
+        other_rooflines = {"attention (K8, bf16 MFMA)": _rf("attention", "mfma", peak),
+                           "layernorm+residual (K4)": _rf("norm", "hbm", HBM_PEAK_GBS),
+                           "pos-conv (K3, bf16 MFMA)": _rf("posconv", "mfma", peak),
+                           # x3: six bf16 piece products per fp32 product, so the matrix roof for ALGORITHMIC flops is the bf16 peak / 6
+                           ("vocoder convs (K11x: fp32 products as six bf16 MFMA terms; roof = bf16 peak / 6)" if voc_x3 else "vocoder convs (K11/K12, f32 MFMA)"):
+                               _rf("voc_conv", "mfma", round(MFMA_BF16_PEAK_TFLOPS / 6, 1) if voc_x3 else MFMA_F32_PEAK_TFLOPS),
+                           "vocoder convs, HBM side (algorithmic bytes per launch)": _rf("voc_conv", "hbm", HBM_PEAK_GBS),
+                           "vocoder conv_post+tanh+int16 (K13)": _rf("voc_post", "hbm", HBM_PEAK_GBS)}
+        # ---- the vocoder convs by stage: one entry per upsampler / MRF stack against the roof SURVEY 8(a) names for it
+        # (K11 stages 0-1 and K12: matrix; K11 stages 2-3: HBM), with the other side beside it
+        voc_peak = round(MFMA_BF16_PEAK_TFLOPS / 6, 1) if voc_x3 else MFMA_F32_PEAK_TFLOPS
+        voc_stages = {}
+        for name, bound in (("voc_pre", "hbm"), ("voc_up0", "mfma"), ("voc_up1", "mfma"), ("voc_up2", "hbm"), ("voc_up3", "hbm"),
+                            ("voc_mrf0", "mfma"), ("voc_mrf1", "mfma"), ("voc_mrf2", "mfma"), ("voc_mrf3", "mfma")):
+            v = prof.get(name)
+            if not v or not v["launches"] or v["ms"] <= 0:
+                continue
+            tf, gb = v["flops"] / 1e12 / (v["ms"] * 1e-3), v["bytes"] / 1e9 / (v["ms"] * 1e-3)
+            voc_stages[name] = {"bound": bound, "ms": round(v["ms"], 3), "launches": v["launches"], "TFLOP/s": round(tf, 2), "frac_mfma": round(tf / voc_peak, 4),
+                                "GB/s": round(gb, 1), "frac_hbm": round(gb / HBM_PEAK_GBS, 4), "flop_per_byte": round(v["flops"] / max(v["bytes"], 1.0), 1)}
+            if bound == "hbm" and name != "voc_pre":
+                other_rooflines[f"vocoder upsample stage {name[-1]} (K11, HBM-bound by SURVEY 8a)"] = {
+                    "bound": "hbm", "achieved": round(gb, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(gb / HBM_PEAK_GBS, 4), "launches": v["launches"]}
+        # ---- K5 GroupNorm: not on the synthesis path of this architecture (the survey lists it "as used"); one micro-measurement so that it has a number
+        if a.spec == "full":
+            gB, gC, gT, gG = a.batch, 512, GEN_FRAMES, 32
+            gx = torch.randn(gB, gC, gT, device=device)
+            gy, gg, gb_ = torch.empty_like(gx), torch.ones(gC, device=device), torch.zeros(gC, device=device)
+            st_ = torch.cuda.current_stream(device)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for it in range(25):
+                if it == 5:
+                    e0.record(st_)
+                eng._check(eng.lib.vv_groupnorm(eng.ctx, gx.data_ptr(), gy.data_ptr(), gg.data_ptr(), gb_.data_ptr(), gB, gC, gT, gG, 1e-5, 0, st_.cuda_stream))
+            e1.record(st_)
+            torch.cuda.synchronize()
+            g_ms = e0.elapsed_time(e1) / 20
+            g_gbs = 8.0 * gx.numel() / 1e9 / (g_ms * 1e-3)
+            other_rooflines["groupnorm (K5; off the synthesis path, micro-measured)"] = {
+                "bound": "hbm", "achieved": round(g_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(g_gbs / HBM_PEAK_GBS, 4), "launches": 20,
+                "shape": f"[{gB}, {gC}, {gT}] f32, {gG} groups; algorithmic bytes = one read + one write"}
+        classes = {}
+        for k, v in prof.items():
+            if v["launches"] and not (k.startswith("voc_") and k not in ("voc_conv", "voc_post")):      # the stage classes repeat voc_conv: `vocoder_stages`
+                classes[k] = {"ms": round(v["ms"], 2), "launches": v["launches"],
+                              "TFLOP/s": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] > 0 else None,
+                              "GB/s": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
     total_audio = audio_s_all * a.steps
     res = {
         "metric": "audio-seconds/sec (24 kHz) at batch 32, 256-token utterances; RTF",
@@ -579,11 +629,7 @@ def main():
         "rtf": round(elapsed / total_audio, 6),
         "timed_region": ("host (pinned) int16 clips / ids / noise -> H2D -> preprocess + Euler steps + vocoder -> int16 PCM D2H to pinned host memory (--pcie; SURVEY 8d)"
                          if a.pcie else "inputs (int16 clips, ids, noise) and int16 PCM resident in HBM: preprocess + Euler steps + vocoder; the PCIe-inclusive "
-                                        "rate of the same step is in `pcie_inclusive`"),
-        "hbm_target_note": "north_star's '>= 40 % of HBM roofline on the vocoder kernel': met by the kernels SURVEY 8(a) puts on the HBM roof that are "
-                           "memory-bound in practice -- K13 conv_post+tanh+int16 (0.70-0.75) and the x2 up-sampler of stage 3 (0.41-0.44, round 5); stage 2 "
-                           "(arithmetic intensity 64 flop/B, above the ~52 ridge of the six-term bf16 form) and every MRF conv (43-450 flop/B) are reported "
-                           "against their matrix roof with the HBM side beside it: `vocoder_stages` (SURVEY 7 / 8d)",
+                                        "rate of the same step is in `pcie_inclusive` (--full)"),
         "vocoder_arith": ("fp32 in / out / accumulate; every product a*w taken as the six bf16 piece products >= 2^-16 |a w| of exact 3-way splits a = h+m+l, "
                           "w = h+m+l (v_mfma_f32_32x32x16_bf16, vv_vocoder_x3.hip): fp32 fidelity -- waveform max |err| vs the float64 oracle 7.6e-7 against "
                           "7.4e-7 for v_mfma_f32_32x32x2_f32 (tests/test_fullsize_gpu.py)") if voc_x3 else "fp32 (v_mfma_f32_32x32x2_f32)",
@@ -593,16 +639,21 @@ def main():
                                 f"{len(batches)} length-bucketed batches {[b[0]['seq_len'].numel() for b in batches]} (row fill {fill:.3f}), ")
                                + f"{a.dtype} acoustic + fp32 vocoder, nfe_step={a.nfe} ({a.nfe - 1} Euler steps x 2 CFG branches)",
                    "spec": a.spec, "global_batch": world * a.batch, "parallelism": f"dp{world} (independent utterances, weight broadcast only)"},
-        "roofline": roofline, "other_rooflines": other_rooflines, "kernel_classes": classes, "vocoder_stages": voc_stages,
         "value_definition": "whole-job audio-seconds per wall second with the inputs resident in HBM when the timed region starts (the bench contract); "
                             "SURVEY 8(d)'s host-to-host wording of the same metric is `pcie_inclusive` (rounds 1-3 reported that one as `value`: "
                             "about 0.25 % lower)",
     }
-    res["lanes"] = {"option": lanes_opt, "class_pass_ms": round(class_pass_ms, 2),
-                    "what": "timed steps: the Euler steps run as two lanes (half batches, or the two CFG branches of a single item) on two HIP streams, "
-                            "bit-identical to one lane (tests/test_e2e_gpu.py::test_two_lanes_equal_one_lane_bit_for_bit).  kernel_classes / rooflines: ONE extra "
-                            "untimed pass on one lane with HIP events around every launch (class_pass_ms: its wall time, which the class ms add up to) -- each "
-                            "kernel with the chip to itself; the two-lane step is shorter than that sum by the kernel tails the other lane fills"}
+    if a.full:
+        res["hbm_target_note"] = ("north_star's '>= 40 % of HBM roofline on the vocoder kernel': met by the kernels SURVEY 8(a) puts on the HBM roof that are "
+                                  "memory-bound in practice -- K13 conv_post+tanh+int16 (0.70-0.75) and the x2 up-sampler of stage 3 (0.41-0.44, round 5); stage 2 "
+                                  "(arithmetic intensity 64 flop/B, above the ~52 ridge of the six-term bf16 form) and every MRF conv (43-450 flop/B) are reported "
+                                  "against their matrix roof with the HBM side beside it: `vocoder_stages` (SURVEY 7 / 8d)")
+        res.update(roofline=roofline, other_rooflines=other_rooflines, kernel_classes=classes, vocoder_stages=voc_stages)
+        res["lanes"] = {"option": lanes_opt, "class_pass_ms": round(class_pass_ms, 2),
+                        "what": "timed steps: the Euler steps run as two lanes (half batches, or the two CFG branches of a single item) on two HIP streams, "
+                                "bit-identical to one lane (tests/test_e2e_gpu.py::test_two_lanes_equal_one_lane_bit_for_bit).  kernel_classes / rooflines: ONE extra "
+                                "untimed pass on one lane with HIP events around every launch (class_pass_ms: its wall time, which the class ms add up to) -- each "
+                                "kernel with the chip to itself; the two-lane step is shorter than that sum by the kernel tails the other lane fills"}
     if pcie_inclusive is not None:
         res["pcie_inclusive"] = pcie_inclusive
     res["devices"] = devices
@@ -619,7 +670,7 @@ def main():
     if bcast_ms is not None:
         res["weight_pack_and_broadcast_ms"] = round(bcast_ms, 2)
         res["dist_backend"] = "nccl (RCCL)" if backend == "nccl" else backend + " (rehearsal: ranks may share a card)"
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(spec, weights, a.nfe)
     print(json.dumps(res), flush=True)
     if dist is not None:

@@ -351,10 +351,10 @@ def test_engine_from_reference_layout_onnx_archive(tmp_path):
 
 
 def test_bench_json_contract():
-    """bench.py prints ONE JSON line with the contract's keys (tiny model, 1 step: this checks the plumbing, not speed)."""
+    """bench.py --full prints ONE JSON line with the contract's keys (tiny model, 1 step: this checks the plumbing, not speed)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--spec", "tiny", "--steps", "1", "--warmup", "0", "--batch", "4"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--spec", "tiny", "--steps", "1", "--warmup", "0", "--batch", "4", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -379,6 +379,33 @@ def test_bench_json_contract():
     assert sum(v["launches"] for v in vs.values()) == d["kernel_classes"]["voc_conv"]["launches"]
     assert abs(sum(v["ms"] for v in vs.values()) - d["kernel_classes"]["voc_conv"]["ms"]) <= 0.02 * d["kernel_classes"]["voc_conv"]["ms"] + 0.05
     assert "resident in HBM" in d["value_definition"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps, prints the headline keys only, and --dump-outputs writes what the timed
+    call returned in its last step: the mel state, the PCM and its lengths, float32 / float64, within 64 MB."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--spec", "tiny", "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "audio-seconds/sec" and d["dtype"] == "bf16" and d["metric"].startswith("audio-seconds/sec")
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 4 * 1037 * 256 / 24000.0) < 0.01 * 4 * 1037 * 256 / 24000.0
+    for k in ("cpu_baseline", "pcie_inclusive", "roofline", "kernel_classes", "vocoder_stages", "lanes"):
+        assert k not in d, k
+    files = sorted(os.listdir(out))
+    assert files == ["mel.npy", "pcm.npy", "pcm_len.npy"], files
+    a = {f[:-4]: np.load(out / f) for f in files}
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+    assert a["mel"].dtype == np.float32 and a["mel"].shape == (4, 1600, 100) and np.isfinite(a["mel"]).all()
+    assert a["pcm"].dtype == np.float32 and a["pcm"].shape == (4, 1037 * 256) and np.abs(a["pcm"]).max() > 0
+    assert np.array_equal(a["pcm"], np.round(a["pcm"])) and np.abs(a["pcm"]).max() <= 32768
+    assert a["pcm_len"].dtype == np.float64 and a["pcm_len"].tolist() == [1037 * 256] * 4
 
 
 def test_bench_serve_workload_contract():
