@@ -99,6 +99,29 @@ VV_API int vv_preprocess_h(vv_ctx* ctx, int B, int N, const int16_t* audio, int 
                     const int32_t* text_len, const int32_t* seq_len, float* cat_mel_text, float* cat_mel_text_drop,
                     int32_t* ref_signal_len, void* stream);
 
+/* ---- N5 speech editing: regenerate chosen spans of an existing clip (F5-TTS's edit_mask), the rest conditioned frame by frame.
+ * The host plans the edit on the hop grid (vietvoice-tts_amd/speech_edit.py); these three calls run it with the stages above:
+ *   vv_edit_splice -> vv_preprocess_edit -> vv_transformer_steps_h -> vv_edit_restore -> vv_decode (ref_signal_len = 0).
+ *
+ * Splice: out [B][ld_out] int16 (8-byte aligned, ld_out % 4 == 0) from source clips in HBM.  desc = n_rows x 4 int64 (device)
+ * {item, src_off, dst_off, n}: out[item][dst_off + k] = src[src_off + k] for k < n.  Every output sample is written exactly once:
+ * copied where a row covers it, 0 elsewhere (the spans to regenerate and everything past the clip).  The rows live in device
+ * memory, so the library cannot check them: the CALLER validates them before the call (0 <= item < B, src_off + n <= n_src,
+ * dst_off + n <= ld_out, the rows of one item disjoint on the output; runtime.HipSynth.edit_splice does). */
+VV_API int vv_edit_splice(vv_ctx* ctx, const int16_t* src, int64_t n_src, const int64_t* desc, int n_rows, int B, int16_t* out,
+                          int ld_out, void* stream);
+/* The preprocess stage of an edit: the arguments of vv_preprocess_h plus keep [B][ld_keep] uint8 (device, ld_keep >= N).
+ * cat_mel_text[b][t] = [mel(audio_b)[t] where keep[b][t] and t < audio_len[b] / hop + 1, else 0 | text(b)] -- the frame mask in place
+ * of the reference prefix; cat_mel_text_drop exactly as vv_preprocess builds it; ref_signal_len[b] = 0. */
+VV_API int vv_preprocess_edit(vv_ctx* ctx, int B, int N, const int16_t* audio, int ld_audio, int max_audio_len,
+                              const int32_t* audio_len, const int32_t* audio_len_host, const int32_t* text_ids, int ld_text,
+                              const int32_t* text_len, const int32_t* seq_len, float* cat_mel_text, float* cat_mel_text_drop,
+                              int32_t* ref_signal_len, const uint8_t* keep, int ld_keep, void* stream);
+/* After the last Euler step: x[b][t][0:n_mel] = cat_mel_text[b][t][0:n_mel] wherever keep[b][t] and t < seq_len[b], bit for bit
+ * (x [B][N][n_mel], cat_mel_text [B][N][n_mel + text_dim], both 16-byte aligned; keep as above). */
+VV_API int vv_edit_restore(vv_ctx* ctx, int B, int N, float* x, const float* cat_mel_text, const uint8_t* keep, int ld_keep,
+                           const int32_t* seq_len, void* stream);
+
 /* replaces the loop over sessions['transformer'].run, core/tts_engine.py:148-174: n_steps Euler
  * steps of the flow ODE starting at step index step0, state x [B][N][n_mel] f32 updated in HBM.
  * rope tables are [>=N][head_dim] f32 (q tables carry the softmax scale). */

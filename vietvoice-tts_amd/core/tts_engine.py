@@ -285,6 +285,54 @@ class TTSEngine:
         except Exception as e:
             raise RuntimeError(f"Speech synthesis failed: {str(e)}")
 
+    def edit_speech(self, audio, text: str, parts_to_edit, fix_duration=None, seed: Optional[int] = None,
+                    output_path: Optional[str] = None) -> Tuple[np.ndarray, float]:
+        """Speech editing (F5-TTS speech_edit.py): regenerate the spans ``parts_to_edit`` = [(start, end)] seconds of
+        ``audio`` (a path or WAV bytes, taken in like a reference clip, or an int16 array at ``config.sample_rate``) so that the clip
+        says ``text`` (the corrected FULL transcript); ``fix_duration`` = the new length of each span in seconds (default: unchanged).
+        Only the spans are drawn from noise; every other frame conditions the model and is put back after the last step, and the
+        whole clip is rendered again by the vocoder.  Noise: the manager's seeded stream, or ``torch.Generator().manual_seed(seed)``.
+        Returns (int16 PCM of the spliced length, seconds).  Validation errors propagate as ValueError; device failures become
+        RuntimeError("Speech editing failed: ...")."""
+        import torch
+        from ..pack import MAX_POS
+        from ..speech_edit import plan_edit
+        start = time.time()
+        m = self.model_session_manager
+        eng = m.engine
+        if eng is None:
+            raise RuntimeError("Speech editing runs on the HIP engine only: the session IO of the reference graphs has no frame mask")
+        cfg = self.config
+        sr, hop = cfg.sample_rate, cfg.hop_length
+        if not isinstance(audio, (str, bytes, bytearray)):
+            audio = self.audio_processor.to_wav_bytes(np.asarray(audio, dtype=np.int16), sr)
+        clean = self.text_processor.clean_text(text)
+        if not clean.strip(" .,?!"):                  # clean_text ends every text with a punctuation mark
+            raise ValueError("the transcript of the edited clip is empty")
+        with self._lock:
+            entry = self.voice_bank.get(bytes(audio) if isinstance(audio, bytearray) else audio)
+            plan = plan_edit(entry.n_samples, parts_to_edit, fix_duration, sr, hop, m.spec.n_fft, MAX_POS)
+            if plan.spliced_len / sr > cfg.max_chunk_duration:
+                raise ValueError(f"the edited clip would last {plan.spliced_len / sr:.2f}s, more than max_chunk_duration "
+                                 f"({cfg.max_chunk_duration}s)")
+            gen = m.noise_gen if seed is None else torch.Generator().manual_seed(int(seed))
+            noise = torch.randn((plan.n_frames, m.spec.n_mel), generator=gen, dtype=torch.float32)
+            ids = self.text_processor.text_to_indices([list(clean)])
+            try:
+                dev = eng.device
+                eng.set_nfe(cfg.nfe_step)
+                _x, pcm, _len = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
+                                               torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
+                                               torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
+                                               torch.from_numpy(plan.keep.reshape(1, -1)).to(dev), noise.unsqueeze(0).to(dev))
+                wave = pcm[0, : plan.spliced_len].cpu().numpy()
+            except Exception as e:
+                raise RuntimeError(f"Speech editing failed: {str(e)}") from e
+        if output_path:
+            self.audio_processor.save_audio(wave, output_path, sr)
+            logger.info("Audio saved to: %s", output_path)
+        return wave, time.time() - start
+
     def validate_configuration(self, reference_audio: Optional[str] = None) -> bool:
         if reference_audio is None:
             return True          # built-in voice samples are used

@@ -10,7 +10,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.1 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.2 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -371,7 +371,9 @@ int vv_set_time_grid(vv_ctx* c, const float* sinus_host, const float* dt_host, i
 // --------------------------------------------------------------------------------- preprocess
 static int preprocess_impl(vv_ctx* c, int B, int N, const int16_t* audio, int ld_audio, int max_audio_len, const int32_t* audio_len,
                            const int32_t* audio_len_host, const int32_t* text_ids, int ld_text, const int32_t* text_len, const int32_t* seq_len,
-                           float* cat, float* cat_drop, int32_t* ref_len, void* stream) {
+                           float* cat, float* cat_drop, int32_t* ref_len, void* stream, const uint8_t* keep = nullptr, int ld_keep = 0) {
+    // keep != nullptr (vv_preprocess_edit): the mel conditioning is masked by keep[b][t] on top of t < audio_len / hop + 1, and
+    // ref_signal_len is 0 (the whole clip is decoded)
     if (!c) return -22;
     if (!c->finalized) return c->fail(-1, "vv_preprocess: weights not finalized");
     if (B < 1 || N < 1 || !audio || !audio_len || !text_ids || !text_len || !seq_len || !cat || !cat_drop || !ref_len)
@@ -433,9 +435,10 @@ static int preprocess_impl(vv_ctx* c, int B, int N, const int16_t* audio, int ld
         if (int r = gemm(c, c->dt, VV_DTYPE_F32, VV_EPI_GATE_RES, VV_ACT_NONE_, tm, C2, (p + ".pwconv2.weight").c_str(), C2, (p + ".pwconv2.bias").c_str(), tx, Dt, (int)R2, Dt, C2, st)) return r;
     }
     {
-        Prof p(c, VV_PROF_ELEMWISE, 0, 12.0 * B * N * (M + Dt), st);
-        KCHK(c, vvk_build_cat(mel, F_max, ref_len, tx, cat, cat_drop, B, N, M, Dt, st, &m__));
+        Prof p(c, VV_PROF_ELEMWISE, 0, 12.0 * B * N * (M + Dt) + (keep ? (double)B * N : 0.0), st);
+        KCHK(c, vvk_build_cat(mel, F_max, ref_len, tx, cat, cat_drop, B, N, M, Dt, st, &m__, keep, ld_keep));
     }
+    if (keep) HIPCHK(c, hipMemsetAsync(ref_len, 0, sizeof(int32_t) * B, st));     // the frame bound of the build above, now the decode start
     return 0;
 }
 
@@ -452,6 +455,40 @@ int vv_preprocess_h(vv_ctx* c, int B, int N, const int16_t* audio, int ld_audio,
                     float* cat, float* cat_drop, int32_t* ref_len, void* stream) {
     if (c && !audio_len_host) return c->fail(-22, "vv_preprocess_h: host lengths missing");
     return preprocess_impl(c, B, N, audio, ld_audio, max_audio_len, audio_len, audio_len_host, text_ids, ld_text, text_len, seq_len, cat, cat_drop, ref_len, stream);
+}
+
+// Speech editing (N5): the conditioning as a frame mask keep [B][ld_keep] (device, ld_keep >= N) instead of the clip's prefix.
+int vv_preprocess_edit(vv_ctx* c, int B, int N, const int16_t* audio, int ld_audio, int max_audio_len, const int32_t* audio_len,
+                       const int32_t* audio_len_host, const int32_t* text_ids, int ld_text, const int32_t* text_len, const int32_t* seq_len,
+                       float* cat, float* cat_drop, int32_t* ref_len, const uint8_t* keep, int ld_keep, void* stream) {
+    if (!c) return -22;
+    if (!audio_len_host) return c->fail(-22, "vv_preprocess_edit: host lengths missing");
+    if (!keep || ld_keep < N) return c->fail(-22, "vv_preprocess_edit: keep must be a device array [B][ld_keep] with ld_keep >= N");
+    return preprocess_impl(c, B, N, audio, ld_audio, max_audio_len, audio_len, audio_len_host, text_ids, ld_text, text_len, seq_len, cat, cat_drop,
+                           ref_len, stream, keep, ld_keep);
+}
+
+int vv_edit_splice(vv_ctx* c, const int16_t* src, int64_t n_src, const int64_t* desc, int n_rows, int B, int16_t* out, int ld_out, void* stream) {
+    if (!c) return -22;
+    if (B < 1 || n_rows < 0 || n_src < 0 || !out || ld_out < 4 || ld_out % 4 || (uintptr_t)out % 8 || (n_rows > 0 && (!src || !desc)))
+        return c->fail(-22, "vv_edit_splice: bad arguments (out [B][ld_out] 8-byte aligned with ld_out %% 4 == 0; src and desc for n_rows > 0)");
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * B * ld_out + 32.0 * n_rows, st);
+    KCHK(c, vvk_edit_splice(src, (long long)n_src, (const long long*)desc, n_rows, B, out, ld_out, st, &m__));
+    return 0;
+}
+
+int vv_edit_restore(vv_ctx* c, int B, int N, float* x, const float* cat, const uint8_t* keep, int ld_keep, const int32_t* seq_len, void* stream) {
+    if (!c) return -22;
+    const int M = c->cfg.n_mel, cd = c->cfg.n_mel + c->cfg.text_dim;
+    if (B < 1 || N < 1 || !x || !cat || !keep || !seq_len || ld_keep < N || (uintptr_t)x % 16 || (uintptr_t)cat % 16)
+        return c->fail(-22, "vv_edit_restore: bad arguments (x, cat 16-byte aligned; keep [B][ld_keep] with ld_keep >= N)");
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    Prof p(c, VV_PROF_ELEMWISE, 0, (double)B * N * (1 + 8.0 * M), st);
+    KCHK(c, vvk_edit_restore(x, cat, keep, ld_keep, seq_len, B, N, M, cd, st, &m__));
+    return 0;
 }
 
 // --------------------------------------------------------------------------- transformer steps

@@ -281,10 +281,12 @@ __global__ __launch_bounds__(256) void grn_apply_kernel(T* __restrict__ x, const
 }
 
 // conditioning: cat[b][t] = [mel (t < ref_len) | text(b)], cat_drop[b][t] = [0 | text(B+b)]
+// MASKED (speech editing, vv_edit.hip): the mel only where keep[b][t] as well -- a frame mask in place of the prefix
+template <bool MASKED>
 __global__ __launch_bounds__(256) void build_cat_kernel(const float* __restrict__ mel, int F_max,
                                                         const int* __restrict__ ref_len, const float* __restrict__ text,
                                                         float* __restrict__ cat, float* __restrict__ cat_drop, int B, int N,
-                                                        int n_mel, int Dt) {
+                                                        int n_mel, int Dt, const uint8_t* __restrict__ keep, int ld_keep) {
     const int cd = n_mel + Dt;
     const int c4 = cd >> 2;
     const size_t total = (size_t)B * N * c4;
@@ -295,7 +297,7 @@ __global__ __launch_bounds__(256) void build_cat_kernel(const float* __restrict_
         const int b = (int)(row / N);
         float4 v, vd;
         if (c < n_mel) {
-            v = (t < ref_len[b] && t < F_max) ? *(const float4*)(mel + ((size_t)b * F_max + t) * n_mel + c)
+            v = (t < ref_len[b] && t < F_max && (!MASKED || keep[(size_t)b * ld_keep + t])) ? *(const float4*)(mel + ((size_t)b * F_max + t) * n_mel + c)
                                                : make_float4(0.f, 0.f, 0.f, 0.f);
             vd = make_float4(0.f, 0.f, 0.f, 0.f);
         } else {
@@ -528,9 +530,14 @@ int vvk_grn(int dtype, void* x, float* sumsq, const float* gamma, const float* b
 }
 
 int vvk_build_cat(const float* mel, int F_max, const int* ref_len, const float* text, float* cat, float* cat_drop, int B, int N,
-                  int n_mel, int Dt, hipStream_t st, const char** err) {
+                  int n_mel, int Dt, hipStream_t st, const char** err, const uint8_t* keep, int ld_keep) {
     if (n_mel % 4 || Dt % 4) { *err = "build_cat: widths % 4"; return -22; }
-    build_cat_kernel<<<grid_for((size_t)B * N * (n_mel + Dt) / 4), 256, 0, st>>>(mel, F_max, ref_len, text, cat, cat_drop, B, N, n_mel, Dt);
+    if (keep && ld_keep < N) { *err = "build_cat: ld_keep < N"; return -22; }
+    const int grid = grid_for((size_t)B * N * (n_mel + Dt) / 4);
+    if (keep)
+        build_cat_kernel<true><<<grid, 256, 0, st>>>(mel, F_max, ref_len, text, cat, cat_drop, B, N, n_mel, Dt, keep, ld_keep);
+    else
+        build_cat_kernel<false><<<grid, 256, 0, st>>>(mel, F_max, ref_len, text, cat, cat_drop, B, N, n_mel, Dt, nullptr, 0);
     VVK_CHECK_LAUNCH();
     return 0;
 }

@@ -35,8 +35,9 @@ int vvk_dwconv(const float* in, float* out, const float* w, const float* bias, c
                int KW, hipStream_t st, const char** err);
 int vvk_grn(int dtype, void* x, float* sumsq, const float* gamma, const float* beta, const int* seq_len, int B, int n_seq, int N,
             int C, hipStream_t st, const char** err);
+// keep (optional, [B][ld_keep] device, ld_keep >= N): speech editing's frame mask -- the mel only where keep[b][t] as well
 int vvk_build_cat(const float* mel, int F_max, const int* ref_len, const float* text, float* cat, float* cat_drop, int B, int N,
-                  int n_mel, int Dt, hipStream_t st, const char** err);
+                  int n_mel, int Dt, hipStream_t st, const char** err, const uint8_t* keep = nullptr, int ld_keep = 0);
 int vvk_ref_len(const int* audio_len, int* ref_len, int B, int hop, hipStream_t st, const char** err);
 int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, hipStream_t st,
                    const char** err);
@@ -54,3 +55,8 @@ int vvk_rope_compact(const float* c, const float* s, float* out, int n, hipStrea
 int vvk_rope_rows(const float* cs, const int* pos, float* out, int rows, hipStream_t st, const char** err);
 int vvk_groupnorm(const float* x, float* y, const float* gamma, const float* beta, int B, int C, int T, int G, float eps, int act,
                   hipStream_t st, const char** err);
+// N5 speech editing (vv_edit.hip).  Splice rows are {item, src_off, dst_off, n} (n_rows x 4 int64, device), validated by the caller.
+int vvk_edit_splice(const int16_t* src, long long n_src, const long long* desc, int n_rows, int B, int16_t* out, int ld_out,
+                    hipStream_t st, const char** err);
+int vvk_edit_restore(float* x, const float* cat, const uint8_t* keep, int ld_keep, const int* seq_len, int B, int N, int n_mel, int cd,
+                     hipStream_t st, const char** err);

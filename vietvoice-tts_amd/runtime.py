@@ -142,6 +142,10 @@ EXPORTS = {
     "vv_ingest_pcm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "vv_normalize_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "vv_normalize_clips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vv_edit_splice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_preprocess_edit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_edit_restore": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
@@ -303,6 +307,9 @@ class HipSynth:
                 self._check(self.lib.vv_preprocess(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(),
                                                    text_ids.data_ptr(), text_ids.shape[1], text_len.data_ptr(), seq_len.data_ptr(),
                                                    cat.data_ptr(), cat_drop.data_ptr(), ref_len.data_ptr(), self._stream()))
+        return self._pre_dict(cat, cat_drop, ref_len, seq_len, N, seq_len_host)
+
+    def _pre_dict(self, cat, cat_drop, ref_len, seq_len, N, seq_len_host):
         return {"cat_mel_text": cat, "cat_mel_text_drop": cat_drop, "ref_signal_len": ref_len, "seq_len": seq_len,
                 "seq_len_host": None if seq_len_host is None else [int(v) for v in seq_len_host],
                 "rope_cos_q": self.rope[0][:N], "rope_sin_q": self.rope[1][:N], "rope_cos_k": self.rope[2][:N],
@@ -381,6 +388,88 @@ class HipSynth:
         else:
             pcm, pcm_len = self.decode(x, pre, t_gen_max)
         return x, pcm, pcm_len, pre
+
+    # ------------------------------------------------------------------ speech editing (N5)
+    def edit_splice(self, src: torch.Tensor, rows, B: int, ld_out: int) -> torch.Tensor:
+        """src int16 [n] on the device (source clips back to back) and rows = HOST rows {item, src_off, dst_off, n} -> int16 [B, ld_out]:
+        out[item][dst_off + k] = src[src_off + k], 0 wherever no row writes (ld_out % 4 == 0).  The rows are validated here, on the host,
+        before anything is launched: the kernel indexes both buffers by them."""
+        assert src.is_cuda and src.dtype == torch.int16 and src.is_contiguous()
+        rows = [[int(v) for v in r] for r in rows]
+        n_src = src.numel()
+        per_item = {}
+        for r in rows:
+            if len(r) != 4:
+                raise ValueError("edit_splice: a descriptor row has 4 entries")
+            item, so, do, n = r
+            if not (0 <= item < B) or so < 0 or do < 0 or n < 0 or so + n > n_src or do + n > ld_out:
+                raise ValueError(f"edit_splice: descriptor row {r} does not fit the buffers ({n_src} source samples, [{B}, {ld_out}] out)")
+            per_item.setdefault(item, []).append((do, do + n))
+        for spans in per_item.values():
+            spans.sort()
+            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+                raise ValueError("edit_splice: the rows of one item overlap on the output")
+        out = torch.empty((B, ld_out), dtype=torch.int16, device=self.device)
+        d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4).to(self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_edit_splice(self.ctx, src.data_ptr(), n_src, d.data_ptr(), len(rows), B, out.data_ptr(), ld_out,
+                                                self._stream()))
+        return out
+
+    def preprocess_edit(self, audio: torch.Tensor, audio_len: torch.Tensor, text_ids: torch.Tensor, text_len: torch.Tensor,
+                        seq_len: torch.Tensor, N: int, keep: torch.Tensor, audio_len_host, max_audio_len: Optional[int] = None,
+                        seq_len_host=None) -> Dict[str, torch.Tensor]:
+        """preprocess with the mel conditioning masked by keep (uint8 [B, >= N] on the device): the same ``pre`` dict, ref_signal_len 0."""
+        B = audio.shape[0]
+        for t, d in ((audio, torch.int16), (audio_len, torch.int32), (text_ids, torch.int32), (text_len, torch.int32), (seq_len, torch.int32),
+                     (keep, torch.uint8)):
+            assert t.is_cuda and t.dtype == d and t.is_contiguous(), "preprocess_edit inputs must be contiguous device tensors"
+        assert keep.dim() == 2 and keep.shape[0] == B
+        cat = torch.empty((B, N, self.spec.cond_dim), dtype=torch.float32, device=self.device)
+        cat_drop = torch.empty_like(cat)
+        ref_len = torch.empty((B,), dtype=torch.int32, device=self.device)
+        mal = int(max_audio_len if max_audio_len is not None else audio.shape[1])
+        host = (C.c_int32 * B)(*[int(v) for v in audio_len_host])
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_preprocess_edit(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(), host,
+                                                    text_ids.data_ptr(), text_ids.shape[1], text_len.data_ptr(), seq_len.data_ptr(),
+                                                    cat.data_ptr(), cat_drop.data_ptr(), ref_len.data_ptr(), keep.data_ptr(), keep.shape[1],
+                                                    self._stream()))
+        return self._pre_dict(cat, cat_drop, ref_len, seq_len, N, seq_len_host)
+
+    def edit_restore(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], keep: torch.Tensor) -> torch.Tensor:
+        """x fp32 [B,N,n_mel] in place: the kept frames (keep[b][t], t < seq_len[b]) become the conditioning's mel, bit for bit."""
+        B, N, M = x.shape
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
+        assert keep.is_cuda and keep.dtype == torch.uint8 and keep.is_contiguous() and keep.dim() == 2 and keep.shape[0] == B
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_edit_restore(self.ctx, B, N, x.data_ptr(), pre["cat_mel_text"].data_ptr(), keep.data_ptr(), keep.shape[1],
+                                                 pre["seq_len"].data_ptr(), self._stream()))
+        return x
+
+    def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
+                   noise: torch.Tensor, n_steps: Optional[int] = None):
+        """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
+        src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
+        list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
+        transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device).
+        Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = L_b samples."""
+        s = self.spec
+        hop = s.hop_length
+        L = [int(v) for v in spliced_len]
+        B = len(L)
+        frames = [v // hop + 1 for v in L]
+        N = max(frames)
+        assert noise.shape == (B, N, s.n_mel) and noise.is_cuda and noise.dtype == torch.float32
+        mal = max(max(L), s.n_fft)                  # the audio plane is at least n_fft wide (vv_preprocess's contract)
+        audio = self.edit_splice(src, rows, B, (mal + 3) // 4 * 4)
+        i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
+        pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
+        x = noise.clone()
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps)
+        self.edit_restore(x, pre, keep)
+        pcm, _ = self.decode(x, pre, N)
+        return x, pcm, i32(L)
 
     # ------------------------------------------------------------------ hipGraph-captured vocoder step (config 5)
     def capture_decode(self, B: int, N: int, t_gen_max: int) -> "GraphedDecode":
