@@ -62,6 +62,15 @@ typedef struct vv_model_cfg {
     int32_t max_pos; /* rows of the rope / text position tables */
 } vv_model_cfg;
 
+/* N6: the Vocos decoder (ConvNeXt backbone + ISTFT head) in place of the HiFi-GAN generator.  vv_model_cfg is ABI and
+ * stays as it is; a context is switched to Vocos with vv_set_vocos between vv_create and vv_finalize_weights. */
+typedef struct vv_vocos_cfg {
+    int32_t dim, intermediate, layers;   /* backbone width (% 128, <= 1024), ConvNeXt intermediate width (% 128), block count */
+    int32_t embed_k, dw_k;               /* odd kernel sizes of the embed conv and of the depthwise convs */
+    float ln_eps;                        /* every LayerNorm of the backbone */
+    int32_t n_fft, win_length, hop_length;   /* the ISTFT: n_fft == win_length == the model's n_fft (% 128), hop == the model's hop */
+} vv_vocos_cfg;
+
 /* ---- context ------------------------------------------------------------------------------ */
 /* replaces onnxruntime.InferenceSession creation, core/model.py:96-102 */
 VV_API int vv_create(vv_ctx** out, int device, const vv_model_cfg* cfg, int acoustic_dtype);
@@ -73,6 +82,13 @@ VV_API const char* vv_version(void);
 VV_API int vv_bind_weight(vv_ctx* ctx, const char* name, const void* device_ptr, uint64_t bytes);
 /* Verify every tensor the three stages need is bound (names listed in the error if not). */
 VV_API int vv_finalize_weights(vv_ctx* ctx);
+
+/* Select the Vocos decoder for this context (fp32 whatever the acoustic dtype).  Only between vv_create and the first
+ * vv_finalize_weights, which then checks the Vocos tensor names (voc.embed / voc.norm / voc.blocks.{i}.* / voc.final_norm / voc.head,
+ * const.istft_basis; layouts DESIGN.md 3) instead of the HiFi-GAN ones.  -22 otherwise, and for a cfg the kernels cannot run.
+ * vv_decode / vv_decode_into / vv_decode_ws_bytes then run Vocos: pcm_len[b] = hop * max(T_b - 1, 0) (centred ISTFT) where the
+ * HiFi-GAN gives hop * T_b; samples from pcm_len[b] up to t_gen_max * hop are written as zeros. */
+VV_API int vv_set_vocos(vv_ctx* ctx, const vv_vocos_cfg* cfg);
 
 /* ODE time grid: sinus[n_steps][time_freq_dim] (host), dt[n_steps] (host).  Runs the time MLP and
  * every block's AdaLN projection once on the GPU and keeps the modulation tables in HBM. */
@@ -201,8 +217,8 @@ VV_API int vv_set_option(vv_ctx* ctx, const char* name, int value);
 #define VV_PROF_NORM 2
 #define VV_PROF_POSCONV 3
 #define VV_PROF_ELEMWISE 4
-#define VV_PROF_VOC_CONV 5
-#define VV_PROF_VOC_POST 6
+#define VV_PROF_VOC_CONV 5      /* Vocos context: the backbone (embed, ConvNeXt blocks, final norm) */
+#define VV_PROF_VOC_POST 6      /* Vocos context: the ISTFT head (head GEMM, spectrum, inverse-DFT GEMM, overlap-add) */
 #define VV_PROF_MEL 7
 #define VV_PROF_TEXT 8
 /* the vocoder convs once more, by stage (each launch is counted in VV_PROF_VOC_CONV and in exactly one of these): conv_pre, the four
@@ -341,6 +357,16 @@ typedef struct vv_mrf_args {
 } vv_mrf_args;
 VV_API int vv_mrf_resblock(vv_ctx* ctx, const vv_mrf_args* args, void* stream);
 
+/* N6 single-kernel entries (unit parity).  vv_vocos_im2col: the embed conv's operand, out [B * T_max][ld_out] f32 (16-byte aligned,
+ * ld_out >= embed_k * n_mel, % 4): out[b * T_max + t][j * n_mel + m] = x[b][ref_len[b] + t + j - embed_k / 2][m] inside the item's
+ * generated frames [0, min(min(seq_len[b], N) - ref_len[b], T_max)), 0 elsewhere and in the columns past embed_k * n_mel.
+ * vv_istft_head (finalized Vocos context): head [B][T_max][ld_head] f32 (the head GEMM's output, ld_head >= n_fft + 2), n_frames[B]
+ * valid frames per item (device) -> pcm [B][ld_pcm] int16, pcm_len[B] = hop * max(T_b - 1, 0), optional wave_f32 [B][T_max * hop];
+ * ld_pcm >= T_max * hop.  Reads only each item's valid frames; uses the context arena. */
+VV_API int vv_vocos_im2col(vv_ctx* ctx, const float* x, int B, int N, const int32_t* ref_signal_len, const int32_t* seq_len, int T_max,
+                           float* out, int ld_out, void* stream);
+VV_API int vv_istft_head(vv_ctx* ctx, int B, int T_max, const float* head, int ld_head, const int32_t* n_frames, int16_t* pcm, int ld_pcm,
+                         int32_t* pcm_len, float* wave_f32, void* stream);
 VV_API int vv_conv_post(vv_ctx* ctx, const float* in, const float* w, float bias, int16_t* pcm, int ld_pcm, float* wave_f32,
                  int B, int C, int T, int KW, float pre_slope, const int32_t* len_in, void* stream);
 VV_API int vv_mel(vv_ctx* ctx, const int16_t* audio, int ld_audio, const int32_t* audio_len, float* mel, int B, int F_max,

@@ -56,7 +56,7 @@ class ModelConfig:
     device: str = "cuda:0"
     acoustic_dtype: str = "bf16"            # "bf16" (throughput) or "fp32" (numerics configuration)
     synthetic_model: bool = False           # build a seeded synthetic model pack when none is cached
-    model_spec: str = "full"                # architecture preset of a synthetic pack: full | small | tiny
+    model_spec: str = "full"                # architecture preset of a synthetic pack: full | small | tiny (+ "-vocos")
     max_batch_chunks: int = 32              # chunks of one long text synthesised per GPU batch
     use_hip_graph: bool = False             # replay the vocoder step from a captured hipGraph (fixed frame buckets)
     decode_graph_cache_entries: int = 8     # captured decode graphs kept per engine (least recently used beyond that)

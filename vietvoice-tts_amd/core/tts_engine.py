@@ -292,7 +292,7 @@ class TTSEngine:
         says ``text`` (the corrected FULL transcript); ``fix_duration`` = the new length of each span in seconds (default: unchanged).
         Only the spans are drawn from noise; every other frame conditions the model and is put back after the last step, and the
         whole clip is rendered again by the vocoder.  Noise: the manager's seeded stream, or ``torch.Generator().manual_seed(seed)``.
-        Returns (int16 PCM of the spliced length, seconds).  Validation errors propagate as ValueError; device failures become
+        Returns (int16 PCM of the spliced length -- hop * (N - 1) samples of it with the Vocos decoder --, seconds).  Validation errors propagate as ValueError; device failures become
         RuntimeError("Speech editing failed: ...")."""
         import torch
         from ..pack import MAX_POS
@@ -321,11 +321,11 @@ class TTSEngine:
             try:
                 dev = eng.device
                 eng.set_nfe(cfg.nfe_step)
-                _x, pcm, _len = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
+                _x, pcm, n_out = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
                                                torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
                                                torch.from_numpy(plan.keep.reshape(1, -1)).to(dev), noise.unsqueeze(0).to(dev))
-                wave = pcm[0, : plan.spliced_len].cpu().numpy()
+                wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:
                 raise RuntimeError(f"Speech editing failed: {str(e)}") from e
         if output_path:

@@ -30,6 +30,9 @@ struct vv_ctx {
     std::string err;
     std::map<std::string, Bound> w;
     bool finalized = false;
+    bool ever_finalized = false;        // vv_set_vocos is refused once the weights have been finalized
+    bool vocos = false;                 // N6: the Vocos decoder instead of the HiFi-GAN generator (vv_set_vocos)
+    vv_vocos_cfg vcfg{};
     float post_bias = 0.f;
     // time grid tables
     int n_steps = 0;
@@ -286,6 +289,25 @@ int vv_finalize_weights(vv_ctx* c) {
     }
     need("final.adaln.weight", 4ull * 2 * D * D); need("final.adaln.bias", 4ull * 2 * D);
     need("final.proj.weight", (uint64_t)es * MP * D); need("final.proj.bias", 4ull * MP);
+    if (c->vocos) {                                        // N6: the Vocos tensors instead of the HiFi-GAN ones (all fp32)
+        const vv_vocos_cfg& v = c->vcfg;
+        const uint64_t V = v.dim, I = v.intermediate, KE = pad_to(v.embed_k * g.n_mel, 32), HP = pad_to(v.n_fft + 2, 128);
+        need("const.istft_basis", 4ull * v.n_fft * v.n_fft);
+        need("voc.embed.weight", 4 * V * KE); need("voc.embed.bias", 4 * V);
+        for (const char* n : {"voc.norm", "voc.final_norm"}) { need(std::string(n) + ".weight", 4 * V); need(std::string(n) + ".bias", 4 * V); }
+        for (int i = 0; i < v.layers; ++i) {
+            const std::string p = "voc.blocks." + std::to_string(i);
+            need(p + ".dwconv.weight", 4 * V * v.dw_k); need(p + ".dwconv.bias", 4 * V);
+            need(p + ".norm.weight", 4 * V); need(p + ".norm.bias", 4 * V);
+            need(p + ".pwconv1.weight", 4 * I * V); need(p + ".pwconv1.bias", 4 * I);
+            need(p + ".pwconv2.weight", 4 * V * I); need(p + ".pwconv2.bias", 4 * V);
+            need(p + ".gamma", 4 * V);
+        }
+        need("voc.head.weight", 4 * HP * V); need("voc.head.bias", 4 * HP);
+        if (!missing.empty()) return c->fail(-2, "missing or short weights: %s", missing.c_str());
+        c->finalized = c->ever_finalized = true;
+        return 0;
+    }
     int ch = g.voc_pre_ch;
     struct ConvW { std::string name; int cin_pad, kw, rows_pad; };
     std::vector<ConvW> convs;                              // every vocoder conv slab [cin_pad][kw][rows_pad]: split for the x3 kernels below
@@ -331,7 +353,26 @@ int vv_finalize_weights(vv_ctx* c) {
     for (int s = 0; s < g.voc_n_up; ++s) mult[s + 1] = mult[s] * g.voc_up_rates[s];
     if (!c->d_mult) HIPCHK(c, hipMalloc((void**)&c->d_mult, sizeof(int) * (VV_MAX_UP + 1)));
     HIPCHK(c, hipMemcpy(c->d_mult, mult.data(), sizeof(int) * mult.size(), hipMemcpyHostToDevice));
-    c->finalized = true;
+    c->finalized = c->ever_finalized = true;
+    return 0;
+}
+
+int vv_set_vocos(vv_ctx* c, const vv_vocos_cfg* v) {
+    if (!c) return -22;
+    if (!v) return c->fail(-22, "vv_set_vocos: null cfg");
+    if (c->ever_finalized) return c->fail(-22, "vv_set_vocos: only between vv_create and vv_finalize_weights");
+    const vv_model_cfg& g = c->cfg;
+    if (v->dim < 128 || v->dim > 1024 || v->dim % 128 || v->intermediate < 128 || v->intermediate > 16384 || v->intermediate % 128)
+        return c->fail(-22, "vv_set_vocos: dim must be a multiple of 128 in [128, 1024], intermediate a multiple of 128 (fp32 GEMM tiles)");
+    if (v->layers < 1 || v->layers > 64 || v->embed_k < 1 || v->embed_k > 31 || v->embed_k % 2 == 0 || v->dw_k < 1 || v->dw_k > 31 || v->dw_k % 2 == 0 ||
+        !(v->ln_eps > 0.f))
+        return c->fail(-22, "vv_set_vocos: 1..64 layers, odd kernel sizes up to 31, ln_eps > 0");
+    if (v->n_fft != v->win_length || v->n_fft != g.n_fft || g.win_length != g.n_fft || v->hop_length != g.hop_length || v->n_fft % 128 ||
+        v->hop_length < 1 || v->n_fft % v->hop_length || v->n_fft / v->hop_length > 16)
+        return c->fail(-22, "vv_set_vocos: the ISTFT needs n_fft == win_length == the model's n_fft (a multiple of 128) and the model's hop "
+                            "(dividing n_fft, at most 16 frames per sample)");
+    c->vcfg = *v;
+    c->vocos = true;
     return 0;
 }
 
@@ -835,7 +876,22 @@ int vv_transformer_steps_into(vv_ctx* c, int B, int N, const int32_t* seq_len, c
 }
 
 // --------------------------------------------------------------------------------------- decode
+// N6 Vocos: lens[B], three [B * T_max][dim] planes (residual stream, conv / norm outputs), one plane as wide as the widest GEMM
+// operand (im2col, intermediate, head, frames), the spectrum operand [B * T_max][n_fft]
+static int vocos_wide(const vv_ctx* c) {
+    const vv_vocos_cfg& v = c->vcfg;
+    return std::max(std::max(pad_to(v.embed_k * c->cfg.n_mel, 32), v.intermediate), pad_to(v.n_fft + 2, 128));
+}
+static size_t vocos_need(const vv_ctx* c, int B, int t_gen_max) {
+    const size_t R = (size_t)B * t_gen_max;
+    Need nd; nd.add(4ull * B);
+    for (int i = 0; i < 3; ++i) nd.add(4ull * R * c->vcfg.dim);
+    nd.add(4ull * R * vocos_wide(c)); nd.add(4ull * R * c->vcfg.n_fft);
+    return nd.b;
+}
+
 static size_t decode_need(const vv_ctx* c, int B, int t_gen_max) {
+    if (c->vocos) return vocos_need(c, B, t_gen_max);
     const vv_model_cfg& g = c->cfg;
     const int nu = g.voc_n_up;
     size_t big = (size_t)g.voc_pre_ch * t_gen_max, T = t_gen_max;
@@ -855,6 +911,85 @@ int vv_decode_ws_bytes(vv_ctx* c, int B, int t_gen_max, uint64_t* bytes) {
 
 uint64_t vv_ws_generation(const vv_ctx* c) { return c ? c->ws_generation : 0; }
 
+// ---- N6 Vocos.  Every GEMM is fp32 on the pinned 128 x 128 tiling: a row's arithmetic is then the same whatever
+// the batch (M) it shares a launch with.
+static int vocos_gemm(vv_ctx* c, int mode, int act, const float* A, int lda, const std::string& wn, const char* bn, float* C, int ldc, int M,
+                      int N, int K, const float* gate, int n_store, int cls, hipStream_t st) {
+    vv_gemm_args g{};
+    g.dtype = VV_DTYPE_F32; g.out_dtype = VV_DTYPE_F32; g.mode = mode; g.act = act;
+    g.A = A; g.lda = lda; g.W = c->W(wn); g.ldw = K; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    g.bias = bn ? c->Wf(bn) : nullptr; g.gate = gate; g.n_store = n_store; g.tile = 128; g.chip_share = 1;
+    if (!g.W || (bn && !g.bias)) return c->fail(-2, "weight '%s' is not bound", wn.c_str());
+    Prof p(c, cls, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (mode == VV_EPI_GATE_RES ? 2 : 1)), st);
+    const char* m = "";
+    if (int r = vvk_gemm(&g, st, &m)) return c->fail(r, "%s (weight %s, M=%d N=%d K=%d)", m, wn.c_str(), M, N, K);
+    return 0;
+}
+
+static int vocos_ln(vv_ctx* c, const float* x, float* y, int R, const std::string& n, hipStream_t st) {
+    vv_ln_args a{};
+    a.out_dtype = VV_DTYPE_F32; a.x = x; a.ldx = c->vcfg.dim; a.y = y; a.ldy = c->vcfg.dim; a.R = R; a.D = c->vcfg.dim;
+    a.w = c->Wf(n + ".weight"); a.b = c->Wf(n + ".bias"); a.add_one = 0; a.eps = c->vcfg.ln_eps;
+    Prof p(c, VV_PROF_VOC_CONV, 0, 8.0 * R * c->vcfg.dim, st);
+    KCHK(c, vvk_ln_mod(&a, st, &m__));
+    return 0;
+}
+
+// The ISTFT head after the head GEMM: head [B * T_max][ld_head] -> spectrum operand -> windowed frames (one K = n_fft GEMM against
+// const.istft_basis) -> overlap-add / envelope / trim / int16.  spec and frames: [B * T_max][n_fft] scratch.
+static int vocos_istft(vv_ctx* c, int B, int T_max, const float* head, int ld_head, const int* lens, int16_t* pcm, int ld_pcm, int32_t* pcm_len,
+                       float* wave, float* spec, float* frames, hipStream_t st) {
+    const int n = c->vcfg.n_fft, hop = c->vcfg.hop_length, R = B * T_max;
+    {
+        Prof p(c, VV_PROF_VOC_POST, 0, 4.0 * R * ((double)n + 2 + n), st);
+        KCHK(c, vvk_vocos_spectrum(head, ld_head, R, n, spec, st, &m__));
+    }
+    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, spec, n, "const.istft_basis", nullptr, frames, n, R, n, n, nullptr, 0, VV_PROF_VOC_POST, st)) return r;
+    Prof p(c, VV_PROF_VOC_POST, 0, 4.0 * R * (double)n + 6.0 * B * (double)T_max * hop, st);
+    KCHK(c, vvk_vocos_ola(frames, n, B, T_max, lens, c->Wf("const.window"), n, hop, pcm, ld_pcm, pcm_len, wave, T_max * hop, st, &m__));
+    return 0;
+}
+
+static int decode_vocos(vv_ctx* c, int B, int N, const float* x, const int32_t* ref_len, const int32_t* seq_len, int T_max, int16_t* pcm,
+                        int ld_pcm, int32_t* pcm_len, float* wave_f32, void* ext_ws, uint64_t ext_bytes, hipStream_t st) {
+    const vv_vocos_cfg& v = c->vcfg;
+    const int M = c->cfg.n_mel, V = v.dim, I = v.intermediate, KE = pad_to(v.embed_k * M, 32), HP = pad_to(v.n_fft + 2, 128);
+    if ((size_t)B * T_max * vocos_wide(c) * 4 >= ((size_t)1 << 31)) return c->fail(-22, "vv_decode: a Vocos plane of 2 GiB or more (split the batch)");
+    const int R = B * T_max;
+    const size_t need = vocos_need(c, B, T_max);
+    if (ext_ws) { if (int r = use_ws(c, ext_ws, (size_t)ext_bytes, need)) return r; }
+    else if (int r = ensure_ws(c, need)) return r;
+    int* lens = carve<int>(c, B);
+    float* res = carve<float>(c, (size_t)R * V);
+    float* t = carve<float>(c, (size_t)R * V);
+    float* hn = carve<float>(c, (size_t)R * V);
+    float* big = carve<float>(c, (size_t)R * vocos_wide(c));
+    float* spec = carve<float>(c, (size_t)R * v.n_fft);
+    KCHK(c, vvk_vocos_lens(seq_len, ref_len, lens, B, N, T_max, st, &m__));
+    {
+        Prof p(c, VV_PROF_VOC_CONV, 0, 4.0 * R * ((double)M + KE), st);
+        KCHK(c, vvk_vocos_im2col(x, B, N, M, ref_len, seq_len, T_max, v.embed_k, big, KE, st, &m__));
+    }
+    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, big, KE, "voc.embed.weight", "voc.embed.bias", t, V, R, V, KE, nullptr, 0, VV_PROF_VOC_CONV, st)) return r;
+    if (int r = vocos_ln(c, t, res, R, "voc.norm", st)) return r;
+    for (int i = 0; i < v.layers; ++i) {
+        const std::string p = "voc.blocks." + std::to_string(i);
+        {
+            Prof pr(c, VV_PROF_VOC_CONV, 2.0 * R * (double)V * v.dw_k, 8.0 * R * V, st);
+            KCHK(c, vvk_dwconv(res, t, c->Wf(p + ".dwconv.weight"), c->Wf(p + ".dwconv.bias"), lens, B, B, T_max, V, v.dw_k, st, &m__));
+        }
+        if (int r = vocos_ln(c, t, hn, R, p + ".norm", st)) return r;
+        if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_GELU_ERF_, hn, V, p + ".pwconv1.weight", (p + ".pwconv1.bias").c_str(), big, I, R, I, V,
+                               nullptr, 0, VV_PROF_VOC_CONV, st)) return r;
+        if (int r = vocos_gemm(c, VV_EPI_GATE_RES, VV_ACT_NONE_, big, I, p + ".pwconv2.weight", (p + ".pwconv2.bias").c_str(), res, V, R, V, I,
+                               c->Wf(p + ".gamma"), 0, VV_PROF_VOC_CONV, st)) return r;
+    }
+    if (int r = vocos_ln(c, res, hn, R, "voc.final_norm", st)) return r;
+    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, hn, V, "voc.head.weight", "voc.head.bias", big, HP, R, HP, V, nullptr, v.n_fft + 2,
+                           VV_PROF_VOC_POST, st)) return r;
+    return vocos_istft(c, B, T_max, big, HP, lens, pcm, ld_pcm, pcm_len, wave_f32, spec, big, st);
+}
+
 static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* ref_len, const int32_t* seq_len, int t_gen_max, int16_t* pcm,
                        int ld_pcm, int32_t* pcm_len, float* wave_f32, void* ext_ws, uint64_t ext_bytes, void* stream) {
     if (!c) return -22;
@@ -865,6 +1000,7 @@ static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* r
     if (ld_pcm < t_gen_max * g.hop_length) return c->fail(-22, "vv_decode: ld_pcm too small");
     hipSetDevice(c->device);
     hipStream_t st = (hipStream_t)stream;
+    if (c->vocos) return decode_vocos(c, B, N, x, ref_len, seq_len, t_gen_max, pcm, ld_pcm, pcm_len, wave_f32, ext_ws, ext_bytes, st);
     const int M = g.n_mel, nu = g.voc_n_up;
     // buffer plan
     std::vector<int> Ts(nu + 1), Cs(nu + 1);
@@ -1101,6 +1237,26 @@ int vv_ingest_pcm(vv_ctx* c, const void* pcm, const int64_t* desc, int n_clips, 
 size_t vv_normalize_scratch_bytes(int n_clips, int64_t total_len) { return vvk_normalize_scratch_bytes(n_clips, (long long)total_len); }
 int vv_normalize_clips(vv_ctx* c, const float* x, const int64_t* offsets, int n_clips, int64_t max_len, void* scratch, int16_t* out, void* st) {
     SINGLE(c, vvk_normalize_clips(x, (const long long*)offsets, n_clips, (long long)max_len, scratch, out, (hipStream_t)st, &m__));
+}
+int vv_vocos_im2col(vv_ctx* c, const float* x, int B, int N, const int32_t* ref_len, const int32_t* seq_len, int T_max, float* out, int ld_out,
+                    void* st) {
+    if (c && !c->vocos) return c->fail(-22, "vv_vocos_im2col: not a Vocos context (vv_set_vocos)");
+    SINGLE(c, vvk_vocos_im2col(x, B, N, c->cfg.n_mel, ref_len, seq_len, T_max, c->vcfg.embed_k, out, ld_out, (hipStream_t)st, &m__));
+}
+int vv_istft_head(vv_ctx* c, int B, int T_max, const float* head, int ld_head, const int32_t* n_frames, int16_t* pcm, int ld_pcm, int32_t* pcm_len,
+                  float* wave_f32, void* stream) {
+    if (!c) return -22;
+    if (!c->vocos || !c->finalized) return c->fail(-22, "vv_istft_head: needs a finalized Vocos context");
+    if (B < 1 || T_max < 1 || !head || !n_frames || !pcm || ld_head < c->vcfg.n_fft + 2 || ld_pcm < T_max * c->vcfg.hop_length)
+        return c->fail(-22, "vv_istft_head: bad arguments (ld_head >= n_fft + 2, ld_pcm >= T_max * hop)");
+    if ((size_t)B * T_max * c->vcfg.n_fft * 4 >= ((size_t)1 << 31)) return c->fail(-22, "vv_istft_head: a plane of 2 GiB or more");
+    hipSetDevice(c->device);
+    const size_t R = (size_t)B * T_max;
+    Need nd; nd.add(4 * R * c->vcfg.n_fft); nd.add(4 * R * c->vcfg.n_fft);
+    if (int r = ensure_ws(c, nd.b)) return r;
+    float* spec = carve<float>(c, R * c->vcfg.n_fft);
+    float* frames = carve<float>(c, R * c->vcfg.n_fft);
+    return vocos_istft(c, B, T_max, head, ld_head, n_frames, pcm, ld_pcm, pcm_len, wave_f32, spec, frames, (hipStream_t)stream);
 }
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));

@@ -60,3 +60,10 @@ int vvk_edit_splice(const int16_t* src, long long n_src, const long long* desc, 
                     hipStream_t st, const char** err);
 int vvk_edit_restore(float* x, const float* cat, const uint8_t* keep, int ld_keep, const int* seq_len, int B, int N, int n_mel, int cd,
                      hipStream_t st, const char** err);
+// N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
+int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
+int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,
+                     hipStream_t st, const char** err);
+int vvk_vocos_spectrum(const float* head, int ld_head, int R, int n_fft, float* out, hipStream_t st, const char** err);
+int vvk_vocos_ola(const float* frames, int ld_f, int B, int T_max, const int* lens, const float* window, int n_fft, int hop, int16_t* pcm,
+                  int ld_pcm, int32_t* pcm_len, float* wave, int ld_wave, hipStream_t st, const char** err);

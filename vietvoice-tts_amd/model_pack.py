@@ -38,7 +38,8 @@ _SYMBOLS = (" " + "abcdefghijklmnopqrstuvwxyz" + "Ã Ã¡áº£Ã£áº¡Äƒáº±áº¯áº³áºµáº·Ã
 
 
 def spec_by_name(name: str) -> ModelSpec:
-    return {"full": ModelSpec.full, "small": ModelSpec.small, "tiny": ModelSpec.tiny}[name]()
+    return {"full": ModelSpec.full, "small": ModelSpec.small, "tiny": ModelSpec.tiny,
+            "full-vocos": ModelSpec.full_vocos, "small-vocos": ModelSpec.small_vocos, "tiny-vocos": ModelSpec.tiny_vocos}[name]()
 
 
 def synthetic_voice(seed: int, seconds: float, sample_rate: int = 24000) -> np.ndarray:

@@ -56,6 +56,14 @@ class ModelSpec:
     voc_res_kernels: Tuple[int, ...] = (3, 7, 11)
     voc_res_dilations: Tuple[int, ...] = (1, 3, 5)
     voc_lrelu: float = 0.1
+    # vocoder kind: "hifigan" (the voc_* generator above, default) or "vocos" (ConvNeXt backbone + ISTFT head)
+    vocoder: str = "hifigan"
+    vocos_dim: int = 512
+    vocos_intermediate: int = 1536
+    vocos_layers: int = 8
+    vocos_embed_k: int = 7
+    vocos_dw_k: int = 7
+    vocos_ln_eps: float = 1e-6
 
     def __post_init__(self):
         assert self.heads * self.head_dim == self.dim
@@ -67,6 +75,19 @@ class ModelSpec:
             prod *= r
         assert prod == self.hop_length
         assert self.n_mel == 100 or self.n_mel % 4 == 0
+        assert self.vocoder in ("hifigan", "vocos"), self.vocoder
+        if self.vocoder == "vocos":
+            # the fp32 GEMMs of the backbone and the inverse DFT need N % 128 == 0 and K % 32 == 0
+            assert self.vocos_dim % 128 == 0 and 0 < self.vocos_dim <= 1024 and self.vocos_intermediate % 128 == 0
+            assert self.vocos_layers >= 1 and self.vocos_embed_k % 2 == 1 and self.vocos_dw_k % 2 == 1
+            assert self.win_length == self.n_fft and self.n_fft % 128 == 0 and self.n_fft % self.hop_length == 0
+            assert self.n_fft // self.hop_length <= 8
+
+    def pcm_samples(self, frames: int) -> int:
+        """Output samples the vocoder makes of ``frames`` mel frames: hop * T (HiFi-GAN), hop * (T - 1) (Vocos, centred ISTFT)."""
+        if self.vocoder == "vocos":
+            return self.hop_length * max(int(frames) - 1, 0)
+        return self.hop_length * max(int(frames), 0)
 
     @property
     def cat_dim(self) -> int:
@@ -89,7 +110,7 @@ class ModelSpec:
     def from_json(cls, s: str) -> "ModelSpec":
         d = json.loads(s)
         for k in ("voc_up_rates", "voc_up_kernels", "voc_res_kernels", "voc_res_dilations"):
-            d[k] = tuple(d[k])
+            d[k] = tuple(d[k])                  # (files written before the vocoder kind existed load as HiFi-GAN specs)
         return cls(**d)
 
     @classmethod
@@ -107,6 +128,23 @@ class ModelSpec:
         """Mid-size config (all tile paths exercised, oracle still seconds)."""
         return cls(dim=256, depth=3, heads=4, text_dim=128, text_layers=2, vocab_size=64,
                    pos_conv_groups=4, voc_pre_ch=128)
+
+    def with_vocos(self, dim: int = 512, intermediate: int = 1536, layers: int = 8) -> "ModelSpec":
+        from dataclasses import replace
+        return replace(self, vocoder="vocos", vocos_dim=dim, vocos_intermediate=intermediate, vocos_layers=layers)
+
+    @classmethod
+    def full_vocos(cls) -> "ModelSpec":
+        """The full model with the Vocos decoder of charactr/vocos-mel-24khz (512 / 1536 / 8 layers, k 7)."""
+        return cls.full().with_vocos()
+
+    @classmethod
+    def small_vocos(cls) -> "ModelSpec":
+        return cls.small().with_vocos(256, 768, 4)
+
+    @classmethod
+    def tiny_vocos(cls) -> "ModelSpec":
+        return cls.tiny().with_vocos(128, 384, 2)
 
 
 def time_grid(nfe_step: int, sway_coef: float) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -179,6 +217,27 @@ def weight_shapes(spec: ModelSpec) -> Dict[str, Tuple[Tuple[int, ...], float]]:
         lin(p + ".ff2", D, D * spec.ff_mult, gain=0.7)
     lin("final.adaln", 2 * D, D, gain=0.6, bias_std=0.05)
     lin("final.proj", M, D, gain=1.0)
+    if spec.vocoder == "vocos":
+        # ---- Vocos decoder, after every acoustic tensor (the per-tensor seed index of the acoustic weights is that of the HiFi-GAN
+        # spec).  Scaled so that a seeded N(0, 1) mel state gives a waveform peak of a few tenths: log-magnitudes ~ N(1.6, 0.3^2)
+        V, I, n_out = spec.vocos_dim, spec.vocos_intermediate, spec.n_fft + 2
+        sh["voc.embed.weight"] = ((V, M, spec.vocos_embed_k), 1.0 / math.sqrt(M * spec.vocos_embed_k))
+        sh["voc.embed.bias"] = ((V,), 0.02)
+        sh["voc.norm.weight"] = ((V,), -1.0)
+        sh["voc.norm.bias"] = ((V,), 0.02)
+        for i in range(spec.vocos_layers):
+            p = f"voc.blocks.{i}"
+            sh[p + ".dwconv.weight"] = ((V, 1, spec.vocos_dw_k), 1.0 / math.sqrt(spec.vocos_dw_k))
+            sh[p + ".dwconv.bias"] = ((V,), 0.02)
+            sh[p + ".norm.weight"] = ((V,), -1.0)
+            sh[p + ".norm.bias"] = ((V,), 0.02)
+            lin(p + ".pwconv1", I, V, gain=1.4)
+            lin(p + ".pwconv2", V, I, gain=0.7)
+            sh[p + ".gamma"] = ((V,), -1.0 / spec.vocos_layers)
+        sh["voc.final_norm.weight"] = ((V,), -1.0)
+        sh["voc.final_norm.bias"] = ((V,), 0.02)
+        lin("voc.head", n_out, V, gain=0.3, bias_std=-1.6)
+        return sh
     # ---- vocoder
     ch = spec.voc_channels()
     sh["voc.pre.weight"] = ((ch[0], M, spec.voc_pre_k), 1.0 / math.sqrt(M * spec.voc_pre_k) / 3.0)

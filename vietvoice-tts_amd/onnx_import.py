@@ -16,9 +16,12 @@ The reader is checked against protobuf bytes assembled BY HAND from the public o
 (tests/test_onnx_import_cpu.py::test_reader_on_hand_assembled_protobuf) and against graphs written by the fixture
 writer, which is test infrastructure and lives in tests/onnx_fixture_writer.py (it was part of this module up to round 4).
 
-PARITY UNPINNED: the real archive cannot be fetched here, so NAME_RULES follows the public F5-TTS / HiFi-GAN
-module naming and is exercised only on graphs written by that fixture writer.  A graph that does not match
-(for instance a vocoder without ConvTranspose nodes) raises UnsupportedGraph naming what was found.
+PARITY UNPINNED: the real archive cannot be fetched here, so NAME_RULES follows the public F5-TTS / HiFi-GAN / Vocos
+module naming and is exercised only on graphs written by that fixture writer.  The decode graph is read as a Vocos decoder
+(``vocoder="vocos"``) when its initializers carry the public Vocos names (``backbone.embed.*``,
+``backbone.convnext.{i}.*``, ``head.out.*``; the community F5-TTS export wraps charactr/vocos-mel-24khz), otherwise as a
+HiFi-GAN generator.  A graph that matches neither (a vocoder with no ConvTranspose nodes and no Vocos initializers, or a Vocos
+head that is not n_fft + 2 wide) raises UnsupportedGraph naming what was found.
 """
 from __future__ import annotations
 
@@ -338,6 +341,13 @@ NAME_RULES: List[Tuple[str, str]] = [
     (r"voc\.pre\.(weight|bias)", "conv_pre.{0}"),
     (r"voc\.up\.(\d+)\.(weight|bias)", "ups.{0}.{1}"),
     (r"voc\.post\.(weight|bias)", "conv_post.{0}"),
+    # Vocos (public charactr/vocos module naming)
+    (r"voc\.embed\.(weight|bias)", "backbone.embed.{0}"),
+    (r"voc\.norm\.(weight|bias)", "backbone.norm.{0}"),
+    (r"voc\.blocks\.(\d+)\.(dwconv|norm|pwconv1|pwconv2)\.(weight|bias)", "backbone.convnext.{0}.{1}.{2}"),
+    (r"voc\.blocks\.(\d+)\.gamma", "backbone.convnext.{0}.gamma"),
+    (r"voc\.final_norm\.(weight|bias)", "backbone.final_layer_norm.{0}"),
+    (r"voc\.head\.(weight|bias)", "head.out.{0}"),
 ]
 _QKV = re.compile(r"blocks\.(\d+)\.attn\.qkv\.(weight|bias)")
 _RES = re.compile(r"voc\.res\.(\d+)\.(\d+)\.(\d+)\.conv([12])\.(weight|bias)")
@@ -383,6 +393,32 @@ def infer_spec(named: Dict[str, np.ndarray], decode_nodes: List[OnnxNode], base=
     depth = count("transformer.transformer_blocks.{}.attn.to_q.weight")
     text_layers = count("transformer.text_embed.text_blocks.{}.dwconv.weight")
     pos = need("transformer.input_embed.conv_pos_embed.conv1d.0.weight")
+    head_dim = base.head_dim if dim % base.head_dim == 0 else dim
+    ff1 = need("transformer.transformer_blocks.0.ff.ff.0.0.weight")
+    t1 = need("transformer.time_embed.time_mlp.0.weight")
+    pw1 = need("transformer.text_embed.text_blocks.0.pwconv1.weight") if text_layers else None
+    from dataclasses import replace
+    acoustic = dict(n_mel=int(n_mel), dim=int(dim), depth=depth, heads=dim // head_dim, head_dim=head_dim,
+                    ff_mult=int(ff1.shape[0] // dim), text_dim=int(emb.shape[1]), text_layers=text_layers,
+                    text_conv_k=int(g["transformer.text_embed.text_blocks.0.dwconv.weight"].shape[2]) if text_layers else base.text_conv_k,
+                    text_ff_mult=int(pw1.shape[0] // emb.shape[1]) if text_layers else base.text_ff_mult,
+                    vocab_size=int(emb.shape[0]) - 1, pos_conv_k=int(pos.shape[2]), pos_conv_groups=int(dim // pos.shape[1]),
+                    time_freq_dim=int(t1.shape[1]))
+    if "backbone.embed.weight" in g:                     # Vocos decoder (N6)
+        ew = g["backbone.embed.weight"]
+        if ew.ndim != 3 or ew.shape[1] != n_mel:
+            raise UnsupportedGraph(f"Vocos embed conv {tuple(ew.shape)} does not read the {n_mel} mel channels")
+        layers = count("backbone.convnext.{}.dwconv.weight")
+        if not layers:
+            raise UnsupportedGraph("Vocos decode graph without backbone.convnext.{i} blocks")
+        vdim, inter = int(ew.shape[0]), int(need("backbone.convnext.0.pwconv1.weight").shape[0])
+        rows = int(need("head.out.weight").shape[0])
+        if rows != base.n_fft + 2:
+            raise UnsupportedGraph(f"Vocos head has {rows} output rows; the ISTFT head of n_fft {base.n_fft} needs n_fft + 2 = {base.n_fft + 2}")
+        if vdim % 128 or vdim > 1024 or inter % 128:
+            raise UnsupportedGraph(f"Vocos widths {vdim} / {inter}: the fp32 GEMMs need multiples of 128 (width <= 1024)")
+        return replace(base, **acoustic, vocoder="vocos", vocos_dim=vdim, vocos_intermediate=inter, vocos_layers=layers,
+                       vocos_embed_k=int(ew.shape[2]), vocos_dw_k=int(need("backbone.convnext.0.dwconv.weight").shape[2]))
     ups = [n for n in decode_nodes if n.op_type == "ConvTranspose"]
     if not ups:
         ops = sorted({n.op_type for n in decode_nodes})
@@ -399,17 +435,7 @@ def infer_spec(named: Dict[str, np.ndarray], decode_nodes: List[OnnxNode], base=
     n_d = count("resblocks.0.convs1.{}.weight")
     by_weight = {n.inputs[1]: n for n in decode_nodes if n.op_type == "Conv" and len(n.inputs) > 1}
     dil = tuple(int(by_weight[f"resblocks.0.convs1.{k}.weight"].attrs.get("dilations", [1])[0]) for k in range(n_d))
-    head_dim = base.head_dim if dim % base.head_dim == 0 else dim
-    ff1 = need("transformer.transformer_blocks.0.ff.ff.0.0.weight")
-    t1 = need("transformer.time_embed.time_mlp.0.weight")
-    pw1 = need("transformer.text_embed.text_blocks.0.pwconv1.weight") if text_layers else None
-    from dataclasses import replace
-    return replace(base, n_mel=int(n_mel), dim=int(dim), depth=depth, heads=dim // head_dim, head_dim=head_dim,
-                   ff_mult=int(ff1.shape[0] // dim), text_dim=int(emb.shape[1]), text_layers=text_layers,
-                   text_conv_k=int(g["transformer.text_embed.text_blocks.0.dwconv.weight"].shape[2]) if text_layers else base.text_conv_k,
-                   text_ff_mult=int(pw1.shape[0] // emb.shape[1]) if text_layers else base.text_ff_mult,
-                   vocab_size=int(emb.shape[0]) - 1, pos_conv_k=int(pos.shape[2]), pos_conv_groups=int(dim // pos.shape[1]),
-                   time_freq_dim=int(t1.shape[1]), voc_pre_ch=int(need("conv_pre.weight").shape[0]),
+    return replace(base, **acoustic, vocoder="hifigan", voc_pre_ch=int(need("conv_pre.weight").shape[0]),
                    voc_pre_k=int(g["conv_pre.weight"].shape[2]), voc_post_k=int(need("conv_post.weight").shape[2]),
                    voc_up_rates=rates, voc_up_kernels=kernels, voc_res_kernels=res_k, voc_res_dilations=dil)
 

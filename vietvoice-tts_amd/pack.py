@@ -12,6 +12,9 @@ Layouts:
   * vocoder conv: fp32 [Cin_pad8][KW][Cout_pad64]; ConvTranspose (stride u, kernel 2u) in polyphase
     form fp32 [Cin_pad8][2][(Cout*u)_pad64] with row = co*u + phase, tap j -> kernel index phase + j*u.
   * constant tables (Hann window, DFT twiddles, mel filterbank, text position table) fp32.
+  * Vocos decoder (spec.vocoder == "vocos", fp32 whatever the acoustic dtype): the embed conv as an im2col GEMM weight
+    [dim][pad32(k * n_mel)] with column k * n_mel + m = W[o][m][k]; depthwise convs [dim][k]; Linear layers [N_pad128][K];
+    the head [pad128(n_fft + 2)][dim] (zero rows); const.istft_basis [n_fft][n_fft], the window-folded inverse real DFT.
 """
 from __future__ import annotations
 
@@ -134,6 +137,9 @@ def entries(spec: ModelSpec, acoustic_dtype: torch.dtype) -> List[Entry]:
         lin(p + ".ff2", D, FF)
     lin("final.adaln", 2 * D, D, kp=D, dtype=torch.float32)
     lin("final.proj", M, D, np_=MP)
+    if spec.vocoder == "vocos":
+        _vocos_entries(spec, f32, lambda name, n, k: lin(name, n, k, kp=k, dtype=torch.float32))
+        return es
     # ---- vocoder (fp32)
     ch = spec.voc_channels()
 
@@ -167,6 +173,49 @@ def entries(spec: ModelSpec, acoustic_dtype: torch.dtype) -> List[Entry]:
     f32("voc.post.weight", (ch[-1], spec.voc_post_k), lambda w: w["voc.post.weight"].reshape(ch[-1], spec.voc_post_k))
     f32("voc.post.bias", (1,), lambda w: w["voc.post.bias"])
     return es
+
+
+def istft_basis(spec: ModelSpec) -> torch.Tensor:
+    """[n_fft samples][n_fft inputs] fp32, built in float64: frame = basis @ [Re 0..n/2 | Im 1..n/2-1] is w * irfft(S) (norm
+    "backward"; the imaginary parts of bins 0 and n/2 drop out of a real inverse DFT, so they are not inputs)."""
+    n = spec.n_fft
+    h = n // 2
+    t = torch.arange(n, dtype=torch.float64)
+    k = torch.arange(h + 1, dtype=torch.float64)
+    ang = 2.0 * math.pi * torch.outer(t, k) / n                      # [n][h+1]
+    c = torch.full((h + 1,), 2.0, dtype=torch.float64)
+    c[0] = c[h] = 1.0
+    win = torch.hann_window(spec.win_length, periodic=True, dtype=torch.float64)[:, None]
+    re = ang.cos() * c / n
+    im = -ang[:, 1:h].sin() * 2.0 / n
+    return (torch.cat([re, im], dim=1) * win).to(torch.float32).contiguous()
+
+
+def vocos_embed_k(spec: ModelSpec) -> int:
+    """K of the embed conv's im2col GEMM: k * n_mel taps padded to the fp32 GEMM's 32."""
+    return _pad_to(spec.vocos_embed_k * spec.n_mel, 32)
+
+
+def _vocos_entries(spec: ModelSpec, f32, lin32) -> None:
+    V, I, M, KE = spec.vocos_dim, spec.vocos_intermediate, spec.n_mel, vocos_embed_k(spec)
+    k, kd = spec.vocos_embed_k, spec.vocos_dw_k
+    f32("const.istft_basis", (spec.n_fft, spec.n_fft), lambda w: istft_basis(spec))
+    # im2col order: column j = tap * n_mel + mel channel
+    f32("voc.embed.weight", (V, KE), lambda w: _pad2(w["voc.embed.weight"].permute(0, 2, 1).reshape(V, k * M), V, KE))
+    f32("voc.embed.bias", (V,), lambda w: w["voc.embed.bias"])
+    for n in ("voc.norm", "voc.final_norm"):
+        f32(n + ".weight", (V,), lambda w, n=n: w[n + ".weight"])
+        f32(n + ".bias", (V,), lambda w, n=n: w[n + ".bias"])
+    for i in range(spec.vocos_layers):
+        p = f"voc.blocks.{i}"
+        f32(p + ".dwconv.weight", (V, kd), lambda w, p=p: w[p + ".dwconv.weight"].reshape(V, kd))
+        f32(p + ".dwconv.bias", (V,), lambda w, p=p: w[p + ".dwconv.bias"])
+        f32(p + ".norm.weight", (V,), lambda w, p=p: w[p + ".norm.weight"])
+        f32(p + ".norm.bias", (V,), lambda w, p=p: w[p + ".norm.bias"])
+        lin32(p + ".pwconv1", I, V)
+        lin32(p + ".pwconv2", V, I)
+        f32(p + ".gamma", (V,), lambda w, p=p: w[p + ".gamma"])
+    lin32("voc.head", spec.n_fft + 2, V)                        # rows padded to 128 with zeros (n_store = n_fft + 2)
 
 
 def _nbytes(dtype: torch.dtype, shape) -> int:

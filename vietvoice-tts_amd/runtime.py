@@ -45,6 +45,11 @@ class vv_model_cfg(C.Structure):
     ]
 
 
+class vv_vocos_cfg(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("intermediate", C.c_int32), ("layers", C.c_int32), ("embed_k", C.c_int32), ("dw_k", C.c_int32),
+                ("ln_eps", C.c_float), ("n_fft", C.c_int32), ("win_length", C.c_int32), ("hop_length", C.c_int32)]
+
+
 class vv_gemm_args(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("out_dtype", C.c_int32), ("mode", C.c_int32), ("act", C.c_int32),
                 ("A", C.c_void_p), ("lda", C.c_int32), ("W", C.c_void_p), ("ldw", C.c_int32), ("C", C.c_void_p), ("ldc", C.c_int32),
@@ -146,6 +151,10 @@ EXPORTS = {
     "vv_preprocess_edit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_edit_restore": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
+    "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
 }
 
 _lib = None
@@ -194,6 +203,14 @@ def cfg_from_spec(spec: ModelSpec) -> vv_model_cfg:
     return c
 
 
+def vocos_cfg_from_spec(spec: ModelSpec) -> vv_vocos_cfg:
+    v = vv_vocos_cfg()
+    v.dim, v.intermediate, v.layers = spec.vocos_dim, spec.vocos_intermediate, spec.vocos_layers
+    v.embed_k, v.dw_k, v.ln_eps = spec.vocos_embed_k, spec.vocos_dw_k, spec.vocos_ln_eps
+    v.n_fft, v.win_length, v.hop_length = spec.n_fft, spec.win_length, spec.hop_length
+    return v
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -228,6 +245,8 @@ class HipSynth:
         rc = self.lib.vv_create(C.byref(self.ctx), idx, C.byref(cfg), self.dt_code)
         if rc != 0:
             raise HipUnavailable(f"vv_create failed ({rc}): {self.lib.vv_last_error(None).decode()}")
+        if spec.vocoder == "vocos":                  # N6: before any weight is bound (vv_finalize_weights then checks the Vocos names)
+            self._check(self.lib.vv_set_vocos(self.ctx, C.byref(vocos_cfg_from_spec(spec))))
         table, total = pack.plan(spec, self.dt_torch)
         if flat_weights is None:
             if weights is None:
@@ -453,7 +472,8 @@ class HipSynth:
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
         transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device).
-        Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = L_b samples."""
+        Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = min(L_b, the vocoder's
+        output of N_b frames) samples -- L_b with the HiFi-GAN (hop * N_b >= L_b), hop * (N_b - 1) with Vocos (the rest is zeros)."""
         s = self.spec
         hop = s.hop_length
         L = [int(v) for v in spliced_len]
@@ -469,7 +489,7 @@ class HipSynth:
         self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
-        return x, pcm, i32(L)
+        return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
 
     # ------------------------------------------------------------------ hipGraph-captured vocoder step (config 5)
     def capture_decode(self, B: int, N: int, t_gen_max: int) -> "GraphedDecode":
