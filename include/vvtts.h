@@ -94,6 +94,16 @@ VV_API int vv_set_vocos(vv_ctx* ctx, const vv_vocos_cfg* cfg);
  * every block's AdaLN projection once on the GPU and keeps the modulation tables in HBM. */
 VV_API int vv_set_time_grid(vv_ctx* ctx, const float* sinus_host, const float* dt_host, int n_steps, void* stream);
 
+/* N7 ODE plan: vv_set_time_grid generalised to an explicit Runge-Kutta method with s <= 4 stages.  a [s * s] row-major
+ * and strictly lower triangular, b [s]; sinus [n_steps * s][time_freq_dim] holds one row per EVALUATION (step n, stage i at row
+ * n * s + i: the embedding of t_n + c_i h_n, c_i = sum_j a[i][j]), dt [n_steps] the step sizes h_n (all host).  n_steps * s <= 512.
+ * -22 for a tableau that is not strictly lower triangular, not finite, or whose weights do not sum to 1 (|sum b - 1| < 1e-6), for
+ * s outside [1, 4] and for too many evaluations; the plan in force then stays as it was.  vv_set_time_grid is the s = 1 case.
+ * vv_transformer_steps* keep counting ODE steps; each runs s evaluations, and with s > 1 vv_transformer_ws_bytes grows by the stage
+ * state and up to s - 1 slope buffers ([rows][n_mel] fp32 each). */
+VV_API int vv_set_ode_plan(vv_ctx* ctx, const float* sinus_host, const float* dt_host, int n_steps, int s, const double* a,
+                           const double* b, void* stream);
+
 /* ---- the three stages (device-resident, batched) ------------------------------------------ */
 /* replaces sessions['preprocess'].run, core/tts_engine.py:133-146.
  * audio [B][ld_audio] int16, audio_len[B], text_ids [B][ld_text] int32, text_len[B], seq_len[B]
@@ -140,7 +150,9 @@ VV_API int vv_edit_restore(vv_ctx* ctx, int B, int N, float* x, const float* cat
 
 /* replaces the loop over sessions['transformer'].run, core/tts_engine.py:148-174: n_steps Euler
  * steps of the flow ODE starting at step index step0, state x [B][N][n_mel] f32 updated in HBM.
- * rope tables are [>=N][head_dim] f32 (q tables carry the softmax scale). */
+ * rope tables are [>=N][head_dim] f32 (q tables carry the softmax scale).
+ * Under a plan of more than one stage (vv_set_ode_plan) a step is one Runge-Kutta step of s evaluations; step0 and n_steps of
+ * every form below keep counting ODE steps, and a step is never split between calls. */
 VV_API int vv_transformer_steps(vv_ctx* ctx, int B, int N, const int32_t* seq_len, float* x, const float* cat_mel_text,
                          const float* cat_mel_text_drop, const float* rope_cos_q, const float* rope_sin_q,
                          const float* rope_cos_k, const float* rope_sin_k, int step0, int n_steps, void* stream);
@@ -168,6 +180,24 @@ VV_API int vv_transformer_steps_into(vv_ctx* ctx, int B, int N, const int32_t* s
                               const float* cat_mel_text, const float* cat_mel_text_drop, const float* rope_cos_q,
                               const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k, int step0,
                               int n_steps, void* ws, uint64_t ws_bytes, void* stream);
+
+/* One struct-argument entry for the transformer stage: every argument of vv_transformer_steps_into plus a guidance strength PER
+ * ITEM.  seq_len_host NULL = the lengths are read back (vv_transformer_steps); ws NULL = the context arena (a ws needs the host
+ * lengths); cfg_item NULL = vv_model_cfg.cfg_strength for every item, else a device array [B] of fp32 strengths (item b's slope is
+ * p_c + (p_c - p_u) * cfg_item[b]).  A zero-initialised struct plus the fields of the positional entries behaves as they do. */
+typedef struct vv_steps_args {
+    int32_t B, N;
+    const int32_t* seq_len;           /* device [B] */
+    const int32_t* seq_len_host;      /* host [B], optional */
+    float* x;                         /* [B][N][n_mel] f32, updated in place */
+    const float* cat_mel_text;
+    const float* cat_mel_text_drop;
+    const float* rope_cos_q; const float* rope_sin_q; const float* rope_cos_k; const float* rope_sin_k;
+    int32_t step0, n_steps;           /* ODE steps of the plan in force (vv_set_ode_plan / vv_set_time_grid) */
+    void* ws; uint64_t ws_bytes;      /* optional caller-owned workspace (>= vv_transformer_ws_bytes, 256-byte aligned) */
+    const float* cfg_item;            /* optional device [B] */
+} vv_steps_args;
+VV_API int vv_transformer_steps_ex(vv_ctx* ctx, const vv_steps_args* args, void* stream);
 
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
@@ -378,6 +408,19 @@ VV_API int vv_groupnorm(vv_ctx* ctx, const float* x, float* y, const float* gamm
 VV_API int vv_rope_compact(vv_ctx* ctx, const float* cos_t, const float* sin_t, float* out, int n, void* stream);
 /* out[r][0..63] = compact[pos[r]][0..63]: the compact table gathered once per call for every packed row */
 VV_API int vv_rope_rows(vv_ctx* ctx, const float* compact, const int32_t* pos, float* out, int rows, void* stream);
+/* N7: one stage i of an explicit Runge-Kutta step.  k_i = p_c + (p_c - p_u) * g from pred (conditional rows [0, Rc), unconditional
+ * [Rc, 2 Rc), ld ldp), g = g_item[row / seq_n] when g_item is given (row = row_src[r] or r), else the scalar; k_i is stored to k_out
+ * when that is not NULL.  acc = x[row] + sum_{j < n_prev, coef[j] != 0} coef[j] * k_prev[j][r] + coef[n_prev] * k_i (ascending j, a zero
+ * coefficient is skipped and its buffer may be NULL).  x_out != NULL: x_out[r] = acc (packed rows [Rc][n_mel], the next stage's
+ * state); x_out == NULL: x[row] = acc in place (the step's last stage).  The coefficients are h * a[i+1][j] (h * b[j] on the last
+ * stage).  All buffers fp32, 16-byte aligned. */
+typedef struct vv_ode_stage_args {
+    float* x; const float* pred; int32_t ldp, Rc, n_mel, n_prev;
+    const float* k_prev[3]; float coef[4];
+    float* k_out; float* x_out;
+    float g; const float* g_item; int32_t seq_n; const int32_t* row_src;
+} vv_ode_stage_args;
+VV_API int vv_ode_stage(vv_ctx* ctx, const vv_ode_stage_args* args, void* stream);
 VV_API int vv_cfg_euler(vv_ctx* ctx, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* stream);
 
 /* ---- reference-clip ingest on the device (a8 + SURVEY 8(f) N3).  Together they replace the arithmetic of

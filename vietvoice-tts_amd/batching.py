@@ -33,10 +33,10 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "cfgs", "t0", "n_req")
 
     def __init__(self):
-        self.plans, self.flat, self.blocks, self.t0, self.n_req = [], [], [], time.time(), 0
+        self.plans, self.flat, self.blocks, self.cfgs, self.t0, self.n_req = [], [], [], [], time.time(), 0
 
 
 class BatchingFrontend:
@@ -67,10 +67,17 @@ class BatchingFrontend:
         for t in self._threads:
             t.start()
 
-    def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, **voice) -> Future:
+    def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
+               **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
-        ``serial`` fixes the request's noise stream (default: arrival counter)."""
+        ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
+        (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours."""
         fut: Future = Future()
+        if cfg_strength is not None:
+            cfg_strength = float(cfg_strength)
+            if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
+                fut.set_exception(ValueError("cfg_strength must be a finite number or None"))
+                return fut
         with self._serial_lock:           # close() raises `_closed` under the same lock: a request is either queued in front of the
             if self._closed or self._stage_down:      # sentinel (and served) or refused here -- never orphaned behind it
                 fut.set_exception(RuntimeError("Speech synthesis failed: the batching front end is closed"))
@@ -78,7 +85,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -111,7 +118,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut = req
+        serial, text, speed, voice, fut, cfg_strength = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -134,6 +141,7 @@ class BatchingFrontend:
         batch.plans.append((fut, len(inputs)))
         batch.flat.extend(inputs)
         batch.blocks.extend(blocks)
+        batch.cfgs.extend([cfg_strength] * len(inputs))
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -240,7 +248,7 @@ class BatchingFrontend:
         t0 = time.perf_counter()
         with eng._lock:
             if eng.model_session_manager.engine is not None:
-                waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks)
+                waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0

@@ -61,6 +61,9 @@ class ModelConfig:
     use_hip_graph: bool = False             # replay the vocoder step from a captured hipGraph (fixed frame buckets)
     decode_graph_cache_entries: int = 8     # captured decode graphs kept per engine (least recently used beyond that)
     decode_graph_cache_bytes: int = 16 << 30   # HBM the cache may pin (shared workspace + per-graph I/O buffers)
+    ode_method: str = "euler"               # flow-ODE solver: euler | midpoint | heun2 | heun3 | rk4 (model_spec.ODE_METHODS); nfe_step stays
+                                            # the number of grid points, the DiT runs stages x (nfe_step - 1) times
+    cfg_strength: Optional[float] = None    # classifier-free guidance strength of every synthesis of this engine; None = the model's
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -69,6 +72,13 @@ class ModelConfig:
             raise ValueError("NFE step must be between 1 and 100")
         if self.acoustic_dtype not in ("bf16", "fp32"):
             raise ValueError("acoustic_dtype must be 'bf16' or 'fp32'")
+        from ..model_spec import ODE_METHODS
+        if self.ode_method not in ODE_METHODS:
+            raise ValueError(f"ode_method must be one of {sorted(ODE_METHODS)}")
+        if self.cfg_strength is not None:
+            self.cfg_strength = float(self.cfg_strength)
+            if self.cfg_strength != self.cfg_strength or abs(self.cfg_strength) == float("inf"):
+                raise ValueError("cfg_strength must be a finite number or None")
         self.validate_paths()
 
     @property

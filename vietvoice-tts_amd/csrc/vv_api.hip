@@ -2,6 +2,7 @@
 // transformer-steps / decode launch sequences, and HIP-event profiling per kernel class.
 // No torch types, no exceptions across the ABI, no device allocation inside the step loop.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -35,10 +36,15 @@ struct vv_ctx {
     vv_vocos_cfg vcfg{};
     float post_bias = 0.f;
     // time grid tables
-    int n_steps = 0;
+    int n_steps = 0;                    // ODE steps of the plan in force
     std::vector<float> dt_host;
-    float* modtab = nullptr;            // [depth][n_steps][6D]
-    float* fintab = nullptr;            // [n_steps][2D]
+    float* modtab = nullptr;            // [depth][n_steps * ode_s][6D]: one row per evaluation (step n, stage i at n * ode_s + i)
+    float* fintab = nullptr;            // [n_steps * ode_s][2D]
+    // N7: explicit Runge-Kutta tableau of the plan (vv_set_ode_plan; vv_set_time_grid = Euler, ode_s 1)
+    int ode_s = 1;
+    double ode_a[16] = {}, ode_b[4] = {1.0, 0, 0, 0};
+    int ode_kslot[4] = {-1, -1, -1, -1};   // slope buffer of k_j, -1 = k_j is consumed by the launch that makes it and never read again
+    int ode_nk = 0;                     // slope buffers a step needs (<= ode_s - 1)
     // workspace arena
     char* ws = nullptr;                 // context-owned arena: may MOVE when a later call needs more bytes (ensure_ws)
     size_t ws_cap = 0;
@@ -376,13 +382,30 @@ int vv_set_vocos(vv_ctx* c, const vv_vocos_cfg* v) {
     return 0;
 }
 
-int vv_set_time_grid(vv_ctx* c, const float* sinus_host, const float* dt_host, int n_steps, void* stream) {
+// The tables of a plan: one modulation row per EVALUATION (n_steps * s of them; s = 1: the Euler time grid).  Everything is validated
+// before the tables in force are touched.
+static int set_plan_impl(vv_ctx* c, const char* who, const float* sinus_host, const float* dt_host, int n_steps, int s, const double* a,
+                         const double* b, void* stream) {
     if (!c) return -22;
-    if (!c->finalized) return c->fail(-1, "vv_set_time_grid: weights not finalized");
-    if (n_steps < 1 || n_steps > 512 || !sinus_host || !dt_host) return c->fail(-22, "vv_set_time_grid: bad arguments");
+    if (!c->finalized) return c->fail(-1, "%s: weights not finalized", who);
+    if (n_steps < 1 || n_steps > 512 || !sinus_host || !dt_host) return c->fail(-22, "%s: bad arguments", who);
+    if (s < 1 || s > 4 || !a || !b) return c->fail(-22, "%s: 1 to 4 stages with their tableau", who);
+    if ((long long)n_steps * s > 512) return c->fail(-22, "%s: %d steps x %d stages exceed 512 evaluations", who, n_steps, s);
+    double sum_b = 0;
+    for (int i = 0; i < s; ++i) {
+        if (!std::isfinite(b[i])) return c->fail(-22, "%s: the tableau must be finite", who);
+        sum_b += b[i];
+        for (int j = 0; j < s; ++j) {
+            if (!std::isfinite(a[i * s + j])) return c->fail(-22, "%s: the tableau must be finite", who);
+            if (j >= i && a[i * s + j] != 0.0) return c->fail(-22, "%s: the tableau must be strictly lower triangular (explicit method)", who);
+        }
+    }
+    if (!(std::fabs(sum_b - 1.0) < 1e-6)) return c->fail(-22, "%s: the weights b must sum to 1", who);
+    for (int n = 0; n < n_steps; ++n)
+        if (!std::isfinite(dt_host[n])) return c->fail(-22, "%s: the step sizes must be finite", who);
     hipSetDevice(c->device);
     hipStream_t st = (hipStream_t)stream;
-    const int D = c->cfg.dim, S = n_steps, TF = c->cfg.time_freq_dim, L = c->cfg.depth;
+    const int D = c->cfg.dim, S = n_steps * s, TF = c->cfg.time_freq_dim, L = c->cfg.depth;
     if (TF % 32) return c->fail(-22, "time_freq_dim must be a multiple of 32");
     if (c->modtab) { hipDeviceSynchronize(); hipFree(c->modtab); hipFree(c->fintab); c->modtab = c->fintab = nullptr; }
     HIPCHK(c, hipMalloc((void**)&c->modtab, sizeof(float) * (size_t)L * S * 6 * D));
@@ -404,9 +427,32 @@ int vv_set_time_grid(vv_ctx* c, const float* sinus_host, const float* dt_host, i
     }
     if (int r = gemm(c, VV_DTYPE_F32, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, t2, D, "final.adaln.weight", D, "final.adaln.bias", c->fintab, 2 * D, S, 2 * D, D, st)) return r;
     HIPCHK(c, hipStreamSynchronize(st));
-    c->n_steps = S;
-    c->dt_host.assign(dt_host, dt_host + S);
+    c->n_steps = n_steps;
+    c->dt_host.assign(dt_host, dt_host + n_steps);
+    c->ode_s = s;
+    std::fill(c->ode_a, c->ode_a + 16, 0.0);
+    std::fill(c->ode_b, c->ode_b + 4, 0.0);
+    for (int i = 0; i < s; ++i) {
+        c->ode_b[i] = b[i];
+        for (int j = 0; j < i; ++j) c->ode_a[i * 4 + j] = a[i * s + j];
+    }
+    // k_j lives in a buffer when a launch after the one that makes it reads it: a later stage state (a[m][j], m > j + 1) or the final sum
+    c->ode_nk = 0;
+    for (int j = 0; j < 4; ++j) {
+        bool later = j < s - 1 && c->ode_b[j] != 0.0;
+        for (int m = j + 2; m < s; ++m) later = later || c->ode_a[m * 4 + j] != 0.0;
+        c->ode_kslot[j] = later ? c->ode_nk++ : -1;
+    }
     return 0;
+}
+
+int vv_set_time_grid(vv_ctx* c, const float* sinus_host, const float* dt_host, int n_steps, void* stream) {
+    const double a = 0.0, b = 1.0;
+    return set_plan_impl(c, "vv_set_time_grid", sinus_host, dt_host, n_steps, 1, &a, &b, stream);
+}
+
+int vv_set_ode_plan(vv_ctx* c, const float* sinus_host, const float* dt_host, int n_steps, int s, const double* a, const double* b, void* stream) {
+    return set_plan_impl(c, "vv_set_ode_plan", sinus_host, dt_host, n_steps, s, a, b, stream);
 }
 
 // --------------------------------------------------------------------------------- preprocess
@@ -560,6 +606,7 @@ struct Lane {
     hipStream_t st = nullptr;
     char *xcat = nullptr, *h = nullptr, *h2 = nullptr, *h3 = nullptr, *qkv = nullptr, *att = nullptr, *ffm = nullptr;
     float *xres = nullptr, *pred = nullptr, *csq = nullptr, *csk = nullptr, *csq_rows = nullptr, *csk_rows = nullptr, *h2_tail = nullptr, *h3_tail = nullptr;
+    float *xs = nullptr, *kbuf[3] = {};     // N7 (more than one stage): the stage state and the stored slopes, [Rc][n_mel] fp32 each
     int *kv_len = nullptr, *tab = nullptr;
     const int *row_start = nullptr, *row_src = nullptr, *row_pos = nullptr, *qkv_pos = nullptr;
 };
@@ -568,7 +615,7 @@ struct Lane {
 static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat,
                                   const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
                                   const float* rope_sin_k, int step0, int n_steps, void* stream, void* ext_ws = nullptr,
-                                  uint64_t ext_bytes = 0, uint64_t* ws_only = nullptr) {
+                                  uint64_t ext_bytes = 0, uint64_t* ws_only = nullptr, const float* cfg_item = nullptr) {
     if (!c) return -22;
     if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
     if (B < 1 || N < 1 || (!ws_only && (!seq_len || !x || !cat || !cat_drop || !rope_cos_q || !rope_sin_q || !rope_cos_k || !rope_sin_k)))
@@ -618,7 +665,8 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
     const bool branch_lanes = n_lanes == 1 && !(c->split_k_tail && c->dt == VV_DTYPE_BF16) &&
                               (c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS));
     Lane lanes[2];
-    const int S = c->n_steps;
+    const int ns = c->ode_s, S = c->n_steps * ns;      // S: rows of the modulation tables (evaluations)
+    const bool rk = ns > 1 || cfg_item != nullptr;       // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     Need nd;
     for (int li = 0; li < n_lanes; ++li) {
         Lane& L = lanes[li];
@@ -640,6 +688,7 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         nd.add(es * R * FF); nd.add(4 * R * MP); nd.add(4 * 2 * L.B); nd.add(4ull * N * 64); nd.add(4ull * N * 64); nd.add(4ull * L.n_tab);
         nd.add(4ull * R * 64); nd.add(4ull * R * 64);
         nd.add(4 * L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0)); nd.add(4 * L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
+        if (ns > 1) for (int k = 0; k < 1 + c->ode_nk; ++k) nd.add(4 * L.Rc * M);
     }
     if (ws_only) { *ws_only = (uint64_t)align_up(nd.b, 256); return 0; }
     if (ext_ws) { if (int r = use_ws(c, ext_ws, (size_t)ext_bytes, nd.b)) return r; }
@@ -672,6 +721,10 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         L.csk_rows = carve<float>(c, R * 64);
         L.h2_tail = carve<float>(c, L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0));     // fp32 [parts][tail_rows][D] K parts of the tail rows' deltas
         L.h3_tail = carve<float>(c, L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
+        if (ns > 1) {
+            L.xs = carve<float>(c, L.Rc * M);
+            for (int k = 0; k < c->ode_nk; ++k) L.kbuf[k] = carve<float>(c, L.Rc * M);
+        }
         L.row_start = L.tab; L.row_src = L.tab + 2 * L.B; L.row_pos = L.row_src + L.Rc;
         L.qkv_pos = L.uniform ? nullptr : L.row_pos;   // every sequence N rows: position = packed row mod N, no table lookup
     }
@@ -695,15 +748,17 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         return 0;
     };
     // input embedding of step s: proj, then conv position embedding (two grouped convs + Mish) + residual
-    auto step_pack = [&](Lane& L, int s) -> int {
+    // stage i > 0 of step s reads the stage state (packed rows, no row map) instead of x
+    auto step_pack = [&](Lane& L, int s, int i) -> int {
         hipStream_t st = L.st;
         const size_t Rc = L.Rc;
-        if (s != step0) {
+        if (s != step0 || i > 0) {
             Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * Rc * M + 2.0 * es * Rc * M, st);
-            KCHK(c, vvk_pack_cat(c->dt, L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, L.row_src, st, &m__));
+            KCHK(c, vvk_pack_cat(c->dt, i ? L.xs : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, i ? nullptr : L.row_src, st, &m__));
         }
         return 0;
     };
+    // (s below: the EVALUATION index step * ns + stage, the row of the modulation tables)
     auto step_head = [&](Lane& L, int s) -> int {
         (void)s;
         hipStream_t st = L.st;
@@ -791,6 +846,25 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         KCHK(c, vvk_cfg_euler(L.x, L.pred, MP, (int)L.Rc, M, g.cfg_strength, c->dt_host[s], L.row_src, st, &m__));
         return 0;
     };
+    // N7: stage i of step s -- CFG combine, slope store, then the next stage's state or (last stage) x in place
+    auto step_stage = [&](Lane& L, int s, int i) -> int {
+        hipStream_t st = L.st;
+        const bool last = i == ns - 1;
+        const double h = (double)c->dt_host[s];
+        vv_ode_stage_args a{};
+        a.x = L.x; a.pred = L.pred; a.ldp = MP; a.Rc = (int)L.Rc; a.n_mel = M; a.n_prev = i;
+        int n_read = 0;
+        for (int j = 0; j <= i; ++j) {
+            a.coef[j] = (float)(h * (last ? c->ode_b[j] : c->ode_a[(i + 1) * 4 + j]));
+            if (j < i && a.coef[j] != 0.f) { a.k_prev[j] = L.kbuf[c->ode_kslot[j]]; ++n_read; }
+        }
+        a.k_out = (!last && c->ode_kslot[i] >= 0) ? L.kbuf[c->ode_kslot[i]] : nullptr;
+        a.x_out = last ? nullptr : L.xs;
+        a.g = g.cfg_strength; a.g_item = cfg_item ? cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0)), st);
+        KCHK(c, vvk_ode_stage(&a, st, &m__));
+        return 0;
+    };
 
     // Launch order: the lanes alternate block by block, so both streams always hold work and neither lane's enqueue waits for the
     // other's queue to drain; the device orders each stream by itself.  Item lanes: lane 1 forks from the caller's stream once (what
@@ -829,17 +903,19 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
     c->chip_share = n_views;
     if (n_lanes > 1) rc = fork();
     for (int li = 0; li < n_lanes && !rc; ++li) rc = setup(lanes[li]);
-    for (int s = step0; s < step0 + n_steps && !rc; ++s) {
-        for (int li = 0; li < n_lanes && !rc; ++li) rc = step_pack(lanes[li], s);
-        if (branch_lanes && !rc) rc = fork();
-        const bool forked = branch_lanes && !rc;
-        for (int v = 0; v < n_views && !rc; ++v) rc = step_head(views[v], s);
-        for (int l = 0; l < g.depth && !rc; ++l)
-            for (int v = 0; v < n_views && !rc; ++v) rc = block(views[v], s, l);
-        for (int v = 0; v < n_views && !rc; ++v) rc = step_tail(views[v], s);
-        if (forked) join();
-        for (int li = 0; li < n_lanes && !rc; ++li) rc = step_euler(lanes[li], s);
-    }
+    for (int s = step0; s < step0 + n_steps && !rc; ++s)
+        for (int i = 0; i < ns && !rc; ++i) {             // the evaluations of one ODE step (one for Euler); branch lanes fork / join around each
+            const int e = s * ns + i;
+            for (int li = 0; li < n_lanes && !rc; ++li) rc = step_pack(lanes[li], s, i);
+            if (branch_lanes && !rc) rc = fork();
+            const bool forked = branch_lanes && !rc;
+            for (int v = 0; v < n_views && !rc; ++v) rc = step_head(views[v], e);
+            for (int l = 0; l < g.depth && !rc; ++l)
+                for (int v = 0; v < n_views && !rc; ++v) rc = block(views[v], e, l);
+            for (int v = 0; v < n_views && !rc; ++v) rc = step_tail(views[v], e);
+            if (forked) join();
+            for (int li = 0; li < n_lanes && !rc; ++li) rc = rk ? step_stage(lanes[li], s, i) : step_euler(lanes[li], s);
+        }
     if (n_lanes > 1) join();
     c->chip_share = 1;
     return rc;
@@ -873,6 +949,17 @@ int vv_transformer_steps_into(vv_ctx* c, int B, int N, const int32_t* seq_len, c
                               const float* rope_sin_k, int step0, int n_steps, void* ws, uint64_t ws_bytes, void* stream) {
     if (c && (!seq_len_host || !ws)) return c->fail(-22, "vv_transformer_steps_into: host lengths and a workspace block are required");
     return transformer_steps_impl(c, B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps, stream, ws, ws_bytes);
+}
+
+// N7: the struct-argument form -- the arguments of the three entries above plus a guidance strength per item
+int vv_transformer_steps_ex(vv_ctx* c, const vv_steps_args* a, void* stream) {
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_ex: null arguments");
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_ex: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_ex: cfg_item must be a float array");
+    return transformer_steps_impl(c, a->B, a->N, a->seq_len, a->seq_len_host, a->x, a->cat_mel_text, a->cat_mel_text_drop, a->rope_cos_q,
+                                  a->rope_sin_q, a->rope_cos_k, a->rope_sin_k, a->step0, a->n_steps, stream, a->ws, a->ws_bytes, nullptr,
+                                  a->cfg_item);
 }
 
 // --------------------------------------------------------------------------------------- decode
@@ -1257,6 +1344,10 @@ int vv_istft_head(vv_ctx* c, int B, int T_max, const float* head, int ld_head, c
     float* spec = carve<float>(c, R * c->vcfg.n_fft);
     float* frames = carve<float>(c, R * c->vcfg.n_fft);
     return vocos_istft(c, B, T_max, head, ld_head, n_frames, pcm, ld_pcm, pcm_len, wave_f32, spec, frames, (hipStream_t)stream);
+}
+int vv_ode_stage(vv_ctx* c, const vv_ode_stage_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_stage: null arguments") : -22;
+    SINGLE(c, vvk_ode_stage(a, (hipStream_t)st, &m__));
 }
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));

@@ -181,6 +181,44 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, c
     }
 }
 
+// ---------------------------------------------------------------- N7: one stage of an explicit Runge-Kutta step
+// k_i = pc + (pc - pu) g (the combine of cfg_euler_kernel, g per item through g_item[row_src[row] / seq_n] when given), stored to
+// k_out when a later stage or the final sum reads it; then acc = x + sum_j c_j k_j over the earlier slopes (j ascending, k_prev[j]
+// NULL = zero coefficient, skipped) and the fresh one (c_new, skipped when 0).  x_out != NULL: acc is the next stage's state (packed
+// rows); x_out == NULL (last stage): x is updated in place through row_src.  The coefficients arrive multiplied by h.
+struct OdeStagePrev { const float* k[3]; float c[3]; };
+__global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
+                                                        const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
+                                                        OdeStagePrev pv, float c_new, float* __restrict__ k_out, float* __restrict__ x_out) {
+    const int c4 = n_mel >> 2;
+    const size_t total = (size_t)BN * c4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % c4) * 4;
+        const size_t row = i / c4;
+        const float4 pc = *(const float4*)(pred + row * ldp + c);
+        const float4 pu = *(const float4*)(pred + (row + BN) * ldp + c);
+        const size_t xr = row_src ? (size_t)row_src[row] : row;
+        const float cfg = g_item ? g_item[xr / (size_t)seq_n] : g;
+        float4 k;
+        k.x = pc.x + (pc.x - pu.x) * cfg;
+        k.y = pc.y + (pc.y - pu.y) * cfg;
+        k.z = pc.z + (pc.z - pu.z) * cfg;
+        k.w = pc.w + (pc.w - pu.w) * cfg;
+        if (k_out) *(float4*)(k_out + row * n_mel + c) = k;
+        float4 xv = *(const float4*)(x + xr * n_mel + c);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (pv.k[j]) {
+                const float4 kj = *(const float4*)(pv.k[j] + row * n_mel + c);
+                xv.x += pv.c[j] * kj.x; xv.y += pv.c[j] * kj.y; xv.z += pv.c[j] * kj.z; xv.w += pv.c[j] * kj.w;
+            }
+        if (c_new != 0.f) {
+            xv.x += c_new * k.x; xv.y += c_new * k.y; xv.z += c_new * k.z; xv.w += c_new * k.w;
+        }
+        *(float4*)(x_out ? x_out + row * n_mel + c : x + xr * n_mel + c) = xv;
+    }
+}
+
 // ---------------------------------------------------------------- text: embed gather + position table
 // Sequence s in [0, 2B): b = s % B, drop branch when s >= B (all filler ids).  Token t of the
 // text is id+1; beyond the text (or the sequence) the filler id 0.
@@ -492,6 +530,28 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
                   const char** err) {
     if (n_mel % 4 || ldp % 4) { *err = "cfg_euler: widths must be multiples of 4"; return -22; }
     cfg_euler_kernel<<<grid_for((size_t)BN * n_mel / 4), 256, 0, st>>>(x, pred, ldp, BN, n_mel, cfg, dt, row_src);
+    VVK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vvk_ode_stage(const vv_ode_stage_args* a, hipStream_t st, const char** err) {
+    if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
+    if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
+    if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
+    uintptr_t al = (uintptr_t)a->x | (uintptr_t)a->pred | (uintptr_t)a->k_out | (uintptr_t)a->x_out;
+    OdeStagePrev pv{};
+    for (int j = 0; j < a->n_prev; ++j) {
+        if (!(a->coef[j] == a->coef[j]) || !(a->coef[a->n_prev] == a->coef[a->n_prev])) { *err = "ode_stage: NaN coefficient"; return -22; }
+        if (a->coef[j] == 0.f) continue;
+        if (!a->k_prev[j]) { *err = "ode_stage: a non-zero coefficient without its slope buffer"; return -22; }
+        pv.k[j] = a->k_prev[j]; pv.c[j] = a->coef[j];
+        al |= (uintptr_t)a->k_prev[j];
+        if (a->k_prev[j] == a->k_out || a->k_prev[j] == a->x_out) { *err = "ode_stage: an output aliases an earlier slope"; return -22; }
+    }
+    if (al % 16) { *err = "ode_stage: buffers must be 16-byte aligned"; return -22; }
+    if (a->x_out && (a->x_out == a->x || a->x_out == a->k_out)) { *err = "ode_stage: x_out must be a buffer of its own"; return -22; }
+    ode_stage_kernel<<<grid_for((size_t)a->Rc * a->n_mel / 4), 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src,
+                                                                             pv, a->coef[a->n_prev], a->k_out, a->x_out);
     VVK_CHECK_LAUNCH();
     return 0;
 }

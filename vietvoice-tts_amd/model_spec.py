@@ -17,7 +17,8 @@ from __future__ import annotations
 import json
 import math
 from dataclasses import asdict, dataclass, field
-from typing import Dict, Tuple
+from fractions import Fraction
+from typing import Dict, NamedTuple, Tuple
 
 import torch
 
@@ -158,6 +159,71 @@ def time_grid(nfe_step: int, sway_coef: float) -> Tuple[torch.Tensor, torch.Tens
     t = t + sway_coef * (torch.cos(math.pi / 2 * t) - 1.0 + t)
     dt = t[1:] - t[:-1]
     return t[:-1].to(torch.float32), dt.to(torch.float32)
+
+
+# Explicit Runge-Kutta methods of the flow-ODE sampler: name -> (a, b), a strictly lower triangular, nodes
+# c_i = sum_j a[i][j].  Exact fractions; "rk4" is the 3/8 rule (torchdiffeq's fixed-grid rk4).
+_F = Fraction
+ODE_METHODS: Dict[str, Tuple[Tuple[Tuple[Fraction, ...], ...], Tuple[Fraction, ...]]] = {
+    "euler": (((_F(0),),), (_F(1),)),
+    "midpoint": (((_F(0), _F(0)), (_F(1, 2), _F(0))), (_F(0), _F(1))),
+    "heun2": (((_F(0), _F(0)), (_F(1), _F(0))), (_F(1, 2), _F(1, 2))),
+    "heun3": (((_F(0), _F(0), _F(0)), (_F(1, 3), _F(0), _F(0)), (_F(0), _F(2, 3), _F(0))), (_F(1, 4), _F(0), _F(3, 4))),
+    "rk4": (((_F(0), _F(0), _F(0), _F(0)), (_F(1, 3), _F(0), _F(0), _F(0)), (_F(-1, 3), _F(1), _F(0), _F(0)), (_F(1), _F(-1), _F(1), _F(0))),
+            (_F(1, 8), _F(3, 8), _F(3, 8), _F(1, 8))),
+}
+ODE_MAX_STAGES = 4
+ODE_MAX_EVALS = 512
+
+
+def ode_tableau(method) -> Tuple[Tuple[Tuple[float, ...], ...], Tuple[float, ...]]:
+    """A method name of ODE_METHODS, or a custom tableau (a, b), as validated float64 rows: 1 to 4 stages, a square and strictly
+    lower triangular, finite, |sum b - 1| < 1e-6.  ValueError otherwise."""
+    if isinstance(method, str):
+        if method not in ODE_METHODS:
+            raise ValueError(f"ode_method must be one of {sorted(ODE_METHODS)} or a tableau (a, b), got {method!r}")
+        a, b = ODE_METHODS[method]
+    else:
+        try:
+            a, b = method
+            a, b = tuple(tuple(r) for r in a), tuple(b)
+        except (TypeError, ValueError):
+            raise ValueError("a custom ode_method is a pair (a, b): a [s][s] strictly lower triangular, b [s]") from None
+    s = len(b)
+    if not 1 <= s <= ODE_MAX_STAGES or len(a) != s or any(len(r) != s for r in a):
+        raise ValueError(f"an ODE tableau has 1 to {ODE_MAX_STAGES} stages, a [s][s] and b [s]")
+    af = tuple(tuple(float(v) for v in r) for r in a)
+    bf = tuple(float(v) for v in b)
+    if not all(math.isfinite(v) for r in af for v in r) or not all(math.isfinite(v) for v in bf):
+        raise ValueError("an ODE tableau must be finite")
+    if any(af[i][j] != 0.0 for i in range(s) for j in range(i, s)):
+        raise ValueError("an ODE tableau must be strictly lower triangular (explicit method)")
+    if not abs(sum(bf) - 1.0) < 1e-6:
+        raise ValueError("the weights b of an ODE tableau must sum to 1")
+    return af, bf
+
+
+class OdePlan(NamedTuple):
+    t: torch.Tensor          # fp32 [n_steps * s]: evaluation times t_n + c_i h_n, step-major (row n * s + i)
+    dt: torch.Tensor         # fp32 [n_steps]: h_n, exactly time_grid's
+    a: Tuple[Tuple[float, ...], ...]
+    b: Tuple[float, ...]
+    s: int
+
+
+def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
+    """The sampler's plan on time_grid's grid: ``nfe_step`` points, ``nfe_step - 1`` ODE steps of ``s`` evaluations each at
+    t_n + c_i h_n (float64, clamped to [0, 1], then fp32 -- like time_grid).  ``ode_plan(n, sway, "euler")`` is time_grid bit for bit."""
+    a, b = ode_tableau(method)
+    s = len(b)
+    t = torch.linspace(0.0, 1.0, nfe_step, dtype=torch.float64)
+    t = t + sway_coef * (torch.cos(math.pi / 2 * t) - 1.0 + t)
+    dt = t[1:] - t[:-1]
+    c = torch.tensor([sum(r) for r in a], dtype=torch.float64)
+    te = t[:-1, None] + c[None, :] * dt[:, None]
+    if s > 1:
+        te = te.clamp(0.0, 1.0)
+    return OdePlan(te.reshape(-1).to(torch.float32), dt.to(torch.float32), a, b, s)
 
 
 def mel_filterbank(spec: ModelSpec) -> torch.Tensor:

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ModelSpec, time_grid
+from .model_spec import ODE_MAX_EVALS, ModelSpec, ode_plan
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VVTTS_LIB") or os.path.join(_HERE, "libvvtts_hip.so")   # VVTTS_LIB: A/B builds in tools/
@@ -96,6 +96,19 @@ class vv_mrf_args(C.Structure):
                 ("accumulate", C.c_int32), ("slope", C.c_float), ("out_scale", C.c_float), ("len_in", C.c_void_p)]
 
 
+class vv_steps_args(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("seq_len", C.c_void_p), ("seq_len_host", C.c_void_p), ("x", C.c_void_p),
+                ("cat_mel_text", C.c_void_p), ("cat_mel_text_drop", C.c_void_p), ("rope_cos_q", C.c_void_p), ("rope_sin_q", C.c_void_p),
+                ("rope_cos_k", C.c_void_p), ("rope_sin_k", C.c_void_p), ("step0", C.c_int32), ("n_steps", C.c_int32),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_uint64), ("cfg_item", C.c_void_p)]
+
+
+class vv_ode_stage_args(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("pred", C.c_void_p), ("ldp", C.c_int32), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("n_prev", C.c_int32),
+                ("k_prev", C.c_void_p * 3), ("coef", C.c_float * 4), ("k_out", C.c_void_p), ("x_out", C.c_void_p),
+                ("g", C.c_float), ("g_item", C.c_void_p), ("seq_n", C.c_int32), ("row_src", C.c_void_p)]
+
+
 EXPORTS = {
     # name: (restype, argtypes)
     "vv_version": (C.c_char_p, []),
@@ -105,6 +118,9 @@ EXPORTS = {
     "vv_bind_weight": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64]),
     "vv_finalize_weights": (C.c_int, [C.c_void_p]),
     "vv_set_time_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_set_ode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vv_transformer_steps_ex": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p]),
+    "vv_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p]),
     "vv_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_preprocess_h": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -231,7 +247,7 @@ class HipSynth:
     """
 
     def __init__(self, spec: ModelSpec, weights: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda:0",
-                 acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None):
+                 acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None, ode_method="euler"):
         self.lib = load_library()
         if not torch.cuda.is_available():
             raise HipUnavailable("no HIP device is visible to torch; the synthesis hot path runs only on the GPU")
@@ -267,7 +283,8 @@ class HipSynth:
         self.grid_generation = 0         # bumped by whatever a captured Euler-step graph has baked in (time grid, rope mode, options)
         self.set_rope_theta(float(spec.rope_theta))
         self.nfe_step = None
-        self.set_nfe(nfe_step)
+        self.ode_method = None           # the solver of the plan in force: a name of model_spec.ODE_METHODS or a custom tableau (a, b)
+        self.set_nfe(nfe_step, ode_method)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -288,19 +305,30 @@ class HipSynth:
         except Exception:
             pass
 
-    def set_nfe(self, nfe_step: int):
-        if nfe_step == self.nfe_step:
+    def set_nfe(self, nfe_step: int, ode_method="euler"):
+        """The sampler's plan (N7): ``nfe_step`` grid points = ``nfe_step - 1`` ODE steps of the explicit Runge-Kutta method
+        ``ode_method`` (a name of model_spec.ODE_METHODS, or a tableau (a, b)); ``n_evals`` = stages x steps DiT evaluations."""
+        if not isinstance(ode_method, str):
+            ode_method = (tuple(tuple(r) for r in ode_method[0]), tuple(ode_method[1]))
+        if (nfe_step, ode_method) == (self.nfe_step, self.ode_method):
             return
         if nfe_step < 2:
             raise ValueError("nfe_step must be >= 2")
-        t, dt = time_grid(nfe_step, self.spec.sway_coef)
-        sinus = pack.time_sinus_table(self.spec, t).contiguous()
-        dtc = dt.contiguous()
+        plan = ode_plan(nfe_step, self.spec.sway_coef, ode_method)
+        n_steps = int(plan.dt.numel())
+        if n_steps * plan.s > ODE_MAX_EVALS:
+            raise ValueError(f"{n_steps} ODE steps of {plan.s} stages exceed {ODE_MAX_EVALS} evaluations")
+        sinus = pack.time_sinus_table(self.spec, plan.t).contiguous()
+        dtc = plan.dt.contiguous()
+        a = (C.c_double * (plan.s * plan.s))(*[v for r in plan.a for v in r])
+        b = (C.c_double * plan.s)(*plan.b)
         with self._lock, torch.cuda.device(self.device):          # under the engine lock: no step call or graph replay runs across the change
-            self._check(self.lib.vv_set_time_grid(self.ctx, sinus.data_ptr(), dtc.data_ptr(), int(t.numel()), self._stream()))
+            self._check(self.lib.vv_set_ode_plan(self.ctx, sinus.data_ptr(), dtc.data_ptr(), n_steps, plan.s, a, b, self._stream()))
             self.nfe_step = nfe_step
-            self.n_steps = int(t.numel())
-            self.grid_generation += 1    # vv_set_time_grid frees and reallocates the tables a captured step graph points into
+            self.ode_method = ode_method
+            self.n_steps = n_steps
+            self.n_evals = n_steps * plan.s
+            self.grid_generation += 1    # vv_set_ode_plan frees and reallocates the tables a captured step graph points into
 
     # ------------------------------------------------------------------ stages
     def preprocess(self, audio: torch.Tensor, audio_len: torch.Tensor, text_ids: torch.Tensor, text_len: torch.Tensor,
@@ -340,13 +368,20 @@ class HipSynth:
         es = 2 if self.dt_torch == torch.bfloat16 else 4
         return ((1 << 31) - 1) // (2 * 3 * self.spec.dim * es)
 
-    def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None) -> torch.Tensor:
+    def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None,
+                          cfg: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x fp32 [B,N,n_mel] updated in place on the device.  seq_len_host (optional list / array of the B lengths, the same
-        values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h)."""
+        values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
+        cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's."""
         B, N, M = x.shape
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
         if seq_len_host is None:
             seq_len_host = pre.get("seq_len_host")
+        if cfg is not None:
+            assert cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,), "cfg: fp32 [B] on the device"
+            host = None if seq_len_host is None else (C.c_int32 * B)(*[int(v) for v in seq_len_host])
+            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg)
+            return x
         with self._lock, torch.cuda.device(self.device):
             tail = (pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr(), pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr(),
                     pre["rope_cos_k"].data_ptr(), pre["rope_sin_k"].data_ptr(), step0, n_steps, self._stream())
@@ -357,6 +392,24 @@ class HipSynth:
             else:
                 self._check(self.lib.vv_transformer_steps(self.ctx, B, N, pre["seq_len"].data_ptr(), x.data_ptr(), *tail))
         return x
+
+    def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
+                             cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> None:
+        """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
+        the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host)."""
+        B, N, _ = x.shape
+        a = vv_steps_args()
+        a.B, a.N, a.seq_len, a.x = B, N, pre["seq_len"].data_ptr(), x.data_ptr()
+        a.seq_len_host = None if host is None else C.cast(host, C.c_void_p)
+        a.cat_mel_text, a.cat_mel_text_drop = pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr()
+        a.rope_cos_q, a.rope_sin_q = pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr()
+        a.rope_cos_k, a.rope_sin_k = pre["rope_cos_k"].data_ptr(), pre["rope_sin_k"].data_ptr()
+        a.step0, a.n_steps = int(step0), int(n_steps)
+        if ws is not None:
+            a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+        a.cfg_item = _ptr(cfg)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_transformer_steps_ex(self.ctx, C.byref(a), self._stream()))
 
     def decode(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], t_gen_max: int, want_wave: bool = False):
         B, N, _ = x.shape
@@ -392,14 +445,15 @@ class HipSynth:
 
     def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: torch.Tensor, t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
-                         audio_len_host=None):
+                         audio_len_host=None, cfg: Optional[torch.Tensor] = None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
         gen_frames (host list, optional): per-item generated frames; lets the vocoder run in length buckets on ragged batches.
-        seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation."""
+        seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
+        cfg (optional fp32 [B] on the device): per-item guidance strength."""
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
         x = noise.clone()
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
             if pcm.shape[1] < t_gen_max * self.spec.hop_length:
@@ -467,7 +521,7 @@ class HipSynth:
         return x
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
-                   noise: torch.Tensor, n_steps: Optional[int] = None):
+                   noise: torch.Tensor, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
@@ -486,7 +540,7 @@ class HipSynth:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
         x = noise.clone()
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
