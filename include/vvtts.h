@@ -303,11 +303,16 @@ VV_API int vv_gemm_tail_plan(vv_ctx* ctx, int32_t M, int32_t N, int32_t K, int32
 typedef struct vv_attn_args {
     int32_t dtype;
     const void* qkv; int32_t ld_qkv;
-    void* out; int32_t ld_out;
+    void* out; int32_t ld_out; /* qkv, out and ld_qkv rows 16-byte aligned; ld_out a multiple of 4 elements (the width of a store) */
     int32_t n_seq, seq_n, heads, dim;
-    const int32_t* kv_len;
+    const int32_t* kv_len;     /* optional [n_seq]: keys [0, kv_len[s]) of sequence s are attended, clamped to seq_n.  Padded layout: a
+                                  length <= 0 is taken as 1 (the sequence still has its seq_n output rows).  Packed layout: a sequence
+                                  with kv_len[s] <= 0 owns no row -- nothing of it is read or written */
     const int32_t* row_start;  /* optional [n_seq]: packed ragged rows -- sequence s owns rows [row_start[s], +kv_len[s]);
-                                  default s * seq_n (padded layout, rows beyond kv_len are computed and ignored) */
+                                  default s * seq_n (padded layout, rows beyond kv_len are computed and ignored).
+                                  EVERY row inside the qkv buffer must hold FINITE values, masked ones included (rows >= kv_len[s] of a
+                                  padded sequence, a packed neighbour's rows, rows no sequence owns): a masked key gets the weight 0, and a
+                                  non-finite V there reaches the output as 0 x nan */
     int32_t total_rows;        /* rows in the qkv / out buffers (bounds the K/V buffer resource; reads past it return zero).
                                   Required (> 0) with row_start; 0 = n_seq * seq_n in the padded layout */
     float q_scale;             /* bf16 kernel: factor applied to q while it is loaded (the softmax scale when the projection did not carry

@@ -114,6 +114,13 @@ def test_abi_argument_errors_are_codes_not_aborts(hip_tiny, tiny_setup):
     pcm = torch.zeros(1, 64, dtype=torch.int16, device=DEV)
     assert eng.lib.vv_conv_post(eng.ctx, A.data_ptr(), A.data_ptr(), 0.0, pcm.data_ptr(), 64, None, 1, 8, 64, 5, 0.01, None, gu.stream()) == -22
     assert b"k=7" in eng.lib.vv_last_error(eng.ctx)
+    # attention: a row of out is stored 4 elements at a time -- 16 bytes in fp32, 8 in bf16 -- and ld_out must keep every row aligned to it
+    for dt, ld_bad, ld_ok in ((torch.float32, 64 + 2, 64 + 4), (torch.bfloat16, 64 + 2, 64 + 4)):
+        qkv = torch.zeros(8, 192, dtype=dt, device=DEV)
+        rc, msg = gu.attention(eng, qkv, n_seq=1, seq_n=8, heads=1, ld_out=ld_bad, expect_error=True)
+        assert rc == -22 and b"aligned" in msg, (dt, rc, msg)
+        out = gu.attention(eng, qkv, n_seq=1, seq_n=8, heads=1, ld_out=ld_ok, fill=3.0)
+        assert bool((out[:, :64] == 0).all()) and bool((out[:, 64:] == 3.0).all())
     # the context is still usable
     y = gu.gemm(eng, torch.ones(64, 64, device=DEV), torch.ones(128, 64, device=DEV))
     assert float(y.min()) == float(y.max()) == 64.0
@@ -187,6 +194,47 @@ def test_device_lengths_shorter_than_host_lengths_leave_no_stray_index(hip_tiny,
     torch.cuda.synchronize()
     assert bool(torch.isfinite(x_bad).all())
     assert torch.equal(x_bad[0, : seq_host[0]], x_ok[0, : seq_host[0]])            # item 0 is untouched by item 1's mismatch
+
+
+@pytest.mark.parametrize("which", ["last_longer", "middle_longer", "one_zero"])
+@pytest.mark.parametrize("acoustic", ["f32", "bf16"])
+def test_device_lengths_longer_than_host_lengths_write_no_row_beyond_the_buffers(hip_tiny, tiny_setup, acoustic, which):
+    """The mirror of the test above: a device array that claims MORE rows than the host copy the buffers were sized from (or a zero).
+    row_tables_kernel clamps every length to [0, N] and to the Rc rows that exist, and attention / posconv run on those clamped lengths
+    (both branches), so no kernel addresses a packed row >= R; an item left with no row is skipped.  Checked: the call returns, the
+    state is finite, every item whose lengths agree AFTER the clamp equals the matched run bit for bit, and a guard region right
+    after x keeps its pattern.  The guard sees a stray store through x only; the stores the clamp prevents went into the engine's own
+    qkv / attention workspace, which no test can fence -- there the evidence is indirect: the agreeing items equal the matched run bit
+    for bit, and row_tables_kernel can hand no kernel a row >= R."""
+    spec, w, _ = tiny_setup
+    eng = hip_tiny[acoustic]
+    g = torch.Generator().manual_seed(22)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)
+    la, lt, gen = [256 * 8, 256 * 6, 256 * 7], [10, 7, 9], [9, 7, 5]
+    B = 3
+    seq_host = [la[b] // spec.hop_length + 1 + gen[b] for b in range(B)]
+    N = max(seq_host) + 3                                    # every claimed length stays inside [0, N]: the clamp to Rc is what is tested
+    audio = torch.zeros(B, max(la), dtype=torch.int16)
+    for b in range(B):
+        audio[b, : la[b]] = (torch.randn(la[b], generator=g) * 3000).to(torch.int16)
+    ids = torch.randint(1, spec.vocab_size, (B, max(lt)), generator=g, dtype=torch.int32)
+    noise = torch.randn(B, N, spec.n_mel, generator=g)
+    seq_dev, same = {"last_longer": ([seq_host[0], seq_host[1], seq_host[2] + 3], [0, 1, 2]),      # clamped back to the host's rows: all agree
+                     "middle_longer": ([seq_host[0], seq_host[1] + 3, seq_host[2]], [0]),           # the last item loses 3 rows
+                     "one_zero": ([seq_host[0], 0, seq_host[2]], [0])}[which]                       # item 1 owns no row, item 2 moves up
+    pre = eng.preprocess(audio.to(DEV), i32(la), ids.to(DEV), i32(lt), i32(seq_host), N, seq_len_host=seq_host)
+    x_ok = noise.to(DEV).clone()
+    eng.transformer_steps(x_ok, pre, 0, 2, seq_len_host=seq_host)
+    n, guard = B * N * spec.n_mel, 4096
+    buf = torch.full((n + guard,), 12345.0, device=DEV)
+    x_bad = buf[:n].view(B, N, spec.n_mel)
+    x_bad.copy_(noise.to(DEV))
+    eng.transformer_steps(x_bad, dict(pre, seq_len=i32(seq_dev)), 0, 2, seq_len_host=seq_host)
+    torch.cuda.synchronize()
+    assert bool((buf[n:] == 12345.0).all()), "the guard region after x was written"
+    assert bool(torch.isfinite(x_bad).all())
+    for b in same:
+        assert torch.equal(x_bad[b, : seq_host[b]], x_ok[b, : seq_host[b]]), (which, b)
 
 
 def test_conv_post_negative_length_is_an_empty_row(hip_tiny):

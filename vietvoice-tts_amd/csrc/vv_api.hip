@@ -735,14 +735,14 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
 
     auto setup = [&](Lane& L) -> int {
         hipStream_t st = L.st;
-        KCHK(c, vvk_row_tables(L.seq_len, L.B, N, (int)L.Rc, L.tab, L.tab + 2 * L.B, L.tab + 2 * L.B + L.Rc, st, &m__));
+        // kv_len: the clamped lengths of the tables, both branches -- what attention and posconv run on (never the raw device lengths)
+        KCHK(c, vvk_row_tables(L.seq_len, L.B, N, (int)L.Rc, L.tab, L.tab + 2 * L.B, L.tab + 2 * L.B + L.Rc, L.kv_len, st, &m__));
         KCHK(c, vvk_rope_compact(rope_cos_q, rope_sin_q, L.csq, N, st, &m__));
         KCHK(c, vvk_rope_compact(rope_cos_k, rope_sin_k, L.csk, N, st, &m__));
         if (c->rope_rows) {
             KCHK(c, vvk_rope_rows(L.csq, L.row_pos, L.csq_rows, (int)L.R, st, &m__));
             KCHK(c, vvk_rope_rows(L.csk, L.row_pos, L.csk_rows, (int)L.R, st, &m__));
         }
-        KCHK(c, vvk_dup_len(L.seq_len, L.kv_len, L.B, st, &m__));
         Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.R * (M + CD) / 2 + (double)es * L.R * KP, st);
         KCHK(c, vvk_pack_cat(c->dt, L.x, L.cat, L.cat_drop, L.xcat, KP, (int)L.Rc, M, CD, 0, L.row_src, st, &m__));
         return 0;

@@ -109,9 +109,12 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r32 = lane & 31, h = lane >> 5;
     int kv_len = kv_len_arr ? kv_len_arr[seq] : seq_n;
-    kv_len = max(1, min(kv_len, seq_n));
     // packed rows (row_start given): sequence `seq` owns rows [row_start[seq], +kv_len) only -- the rows after them are the
-    // next sequence's, so queries stop at kv_len and every row index is clamped inside the sequence.
+    // next sequence's, so queries stop at kv_len and every row index is clamped inside the sequence.  A sequence of length <= 0
+    // owns NO row: nothing of it is loaded or stored (row_start[seq] is then its successor's first row, or total_rows).  The padded
+    // layout has seq_n rows per sequence whatever the length: there a length <= 0 is taken as 1 (every query sees key 0).
+    if (row_start && kv_len <= 0) return;
+    kv_len = max(1, min(kv_len, seq_n));
     const size_t row0 = row_start ? (size_t)row_start[seq] : (size_t)seq * seq_n;
     const int q_lim = row_start ? kv_len : seq_n;
     if (qblock * 128 >= q_lim) return;
@@ -388,8 +391,9 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const float* __restric
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r32 = lane & 31, h = lane >> 5;
     int kv_len = kv_len_arr ? kv_len_arr[seq] : seq_n;
+    if (row_start && kv_len <= 0) return;                                                // packed rows: see the bf16 kernel
     kv_len = max(1, min(kv_len, seq_n));
-    const size_t row0 = row_start ? (size_t)row_start[seq] : (size_t)seq * seq_n;       // packed rows: see the bf16 kernel
+    const size_t row0 = row_start ? (size_t)row_start[seq] : (size_t)seq * seq_n;
     const int q_lim = row_start ? kv_len : seq_n;
     if (qblock * 128 >= q_lim) return;
 
@@ -518,8 +522,9 @@ int vvk_attention(const vv_attn_args* a, hipStream_t st, const char** err) {
     if (a->n_seq <= 0 || a->seq_n <= 0 || a->heads <= 0) { *err = "attention: empty shape"; return -22; }
     if (a->dim != a->heads * 64) { *err = "attention: head_dim must be 64"; return -22; }
     const int esz = a->dtype == VV_BF16 ? 2 : 4;
-    if (((size_t)a->ld_qkv * esz) % 16 || ((size_t)a->ld_out * esz) % 8 || ((uintptr_t)a->qkv % 16) || ((uintptr_t)a->out % 16)) {
-        *err = "attention: qkv/out must be 16-byte aligned"; return -22;
+    // rows of qkv are read 16 bytes at a time; a row of out is stored 4 elements at a time: 8 bytes in bf16, 16 bytes in fp32
+    if (((size_t)a->ld_qkv * esz) % 16 || ((size_t)a->ld_out * esz) % (4 * esz) || ((uintptr_t)a->qkv % 16) || ((uintptr_t)a->out % 16)) {
+        *err = "attention: qkv/out must be 16-byte aligned (ld_out: 4 elements)"; return -22;
     }
     if (a->ld_qkv < 3 * a->dim || a->ld_out < a->dim) { *err = "attention: leading dimensions too small"; return -22; }
     if (a->row_start && !a->kv_len) { *err = "attention: packed rows need kv_len"; return -22; }

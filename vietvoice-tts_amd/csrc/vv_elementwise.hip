@@ -360,18 +360,17 @@ __global__ void decode_len_kernel(const int* __restrict__ seq_len, const int* __
     const int tg = max(seq_len[b] - ref_len[b], 0);
     for (int l = 0; l < n_levels; ++l) lens[l * B + b] = tg * mult[l];
 }
-__global__ void dup_len_kernel(const int* __restrict__ seq_len, int* __restrict__ out, int B) {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b < B) { out[b] = seq_len[b]; out[B + b] = seq_len[b]; }
-}
 
 // Packed-row tables of one vv_transformer_steps call, built on the device from the per-item lengths (one workgroup per item):
 //   row_start[2B] (conditional branch first), row_src[Rc] = b * N + t, row_pos[2 Rc] = t.
+//   kv_len[2B]: the lengths attention and posconv run on, both branches -- the SAME clamped lengths the tables are built from.
 __global__ __launch_bounds__(256) void row_tables_kernel(const int* __restrict__ seq_len, int B, int N, int Rc, int* __restrict__ row_start,
-                                                         int* __restrict__ row_src, int* __restrict__ row_pos) {
+                                                         int* __restrict__ row_src, int* __restrict__ row_pos, int* __restrict__ kv_len) {
     // The table sizes (Rc, 2 Rc) and every launch shape come from the HOST copy of the lengths; the device copy is clamped to
     // [0, N] and to the Rc rows that exist, so a device array that disagrees with the host one (stale tensor, wrong batch) cannot
-    // write past the tables -- it produces wrong audio for that call, never a stray store: when the device lengths sum to FEWER
+    // write past the tables -- it produces wrong audio for that call, never a stray store.  When the device lengths sum to MORE
+    // rows than Rc, the items past the Rc-th row get a shorter or a zero length (kv_len carries the clamped value, so every row
+    // [row_start, +kv_len) the block kernels address lies below Rc in its branch; a zero-length item owns no row).  When they sum to FEWER
     // rows than the host's Rc, the last workgroup maps the rows nobody owns onto the PADDING rows of the last item (the rows of
     // x / cat right after its device length, clamped to N - 1), so the gathers and the read-modify-write of cfg_euler through
     // row_src never see an unwritten index and never touch a valid row of any item.
@@ -380,7 +379,7 @@ __global__ __launch_bounds__(256) void row_tables_kernel(const int* __restrict__
     for (int i = 0; i < b; ++i) r0 += min(max(seq_len[i], 0), N);   // B is at most a few hundred: a serial prefix per workgroup is cheaper than a scan
     r0 = min(r0, Rc);
     const int len = min(min(max(seq_len[b], 0), N), Rc - r0);
-    if (threadIdx.x == 0) { row_start[b] = r0; row_start[B + b] = Rc + r0; }
+    if (threadIdx.x == 0) { row_start[b] = r0; row_start[B + b] = Rc + r0; kv_len[b] = len; kv_len[B + b] = len; }
     for (int t = threadIdx.x; t < len; t += 256) {
         row_src[r0 + t] = b * N + t;
         row_pos[r0 + t] = t;
@@ -612,19 +611,14 @@ int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int
     VVK_CHECK_LAUNCH();
     return 0;
 }
-int vvk_row_tables(const int* seq_len, int B, int N, int Rc, int* row_start, int* row_src, int* row_pos, hipStream_t st, const char** err) {
+int vvk_row_tables(const int* seq_len, int B, int N, int Rc, int* row_start, int* row_src, int* row_pos, int* kv_len, hipStream_t st, const char** err) {
     if (B <= 0 || N <= 0 || Rc <= 0) { *err = "row_tables: empty"; return -22; }
-    row_tables_kernel<<<B, 256, 0, st>>>(seq_len, B, N, Rc, row_start, row_src, row_pos);
+    row_tables_kernel<<<B, 256, 0, st>>>(seq_len, B, N, Rc, row_start, row_src, row_pos, kv_len);
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
 
-int vvk_dup_len(const int* seq_len, int* out, int B, hipStream_t st, const char** err) {
-    dup_len_kernel<<<(B + 63) / 64, 64, 0, st>>>(seq_len, out, B);
-    VVK_CHECK_LAUNCH();
-    return 0;
-}
 int vvk_groupnorm(const float* x, float* y, const float* gamma, const float* beta, int B, int C, int T, int G, float eps, int act,
                   hipStream_t st, const char** err) {
     if (B <= 0 || C <= 0 || T <= 0 || G <= 0 || C % G) { *err = "groupnorm: C must be a multiple of G"; return -22; }
