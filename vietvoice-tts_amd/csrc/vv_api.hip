@@ -45,11 +45,9 @@ struct vv_ctx {
     double ode_a[16] = {}, ode_b[4] = {1.0, 0, 0, 0};
     int ode_kslot[4] = {-1, -1, -1, -1};   // slope buffer of k_j, -1 = k_j is consumed by the launch that makes it and never read again
     int ode_nk = 0;                     // slope buffers a step needs (<= ode_s - 1)
-    // workspace arena
-    char* ws = nullptr;                 // context-owned arena: may MOVE when a later call needs more bytes (ensure_ws)
+    // workspace block
+    char* ws = nullptr;                 // context-owned block: may MOVE when a later call needs more bytes (ensure_ws)
     size_t ws_cap = 0;
-    char* ar = nullptr;                 // active arena of the current call: ws, or a caller-owned block (vv_decode_into)
-    size_t ar_cap = 0, ar_off = 0;
     uint64_t ws_generation = 0;         // bumped whenever ws is reallocated
     int* d_mult = nullptr;              // decode length multipliers
     int rope_rows = 0;                  // 1: the QKV rope epilogue reads row-gathered tables (vv_rope_rows).  Off by default: 11 % faster in a
@@ -140,59 +138,69 @@ struct Prof {
     ~Prof() { if (idx >= 0) hipEventRecord(c->recs[idx].b, st); }
 };
 
-int ensure_ws(vv_ctx* c, size_t bytes) {
+// The workspace of ONE call.  A stage names its buffers in one function that takes them from an arena, and runs it twice (plan_ws):
+// on a null-based arena for the byte count, then on the block for the pointers.  A zero-length take still aligns.
+struct Arena {
+    char* base = nullptr; size_t cap = 0, off = 0;
+    template <typename T> T* take(size_t n) { off = align_up(off, 256); T* p = base ? (T*)(base + off) : nullptr; off += n * sizeof(T); return p; }
+};
+template <typename F> size_t plan_bytes(F&& plan) { Arena dry; plan(dry); return dry.off; }
+// The context's own block, grown to `bytes` (it may move: nothing a captured hipGraph points into).
+int ensure_ws(vv_ctx* c, size_t bytes, Arena* a) {
     if (bytes > c->ws_cap) {
         if (c->ws) { hipDeviceSynchronize(); hipFree(c->ws); c->ws = nullptr; c->ws_cap = 0; }
         const size_t want = align_up(bytes + bytes / 16, 1 << 20);
         hipError_t e = hipMalloc((void**)&c->ws, want);
         if (e != hipSuccess) return c->fail(-12, "workspace hipMalloc(%zu MiB): %s", want >> 20, hipGetErrorString(e));
-        c->ws_cap = want;
-        ++c->ws_generation;
+        c->ws_cap = want; ++c->ws_generation;
     }
-    c->ar = c->ws; c->ar_cap = c->ws_cap; c->ar_off = 0;
+    *a = Arena{c->ws, c->ws_cap, 0};
     return 0;
 }
 // A caller-owned block as the arena of one call (memory that can never move: what a captured hipGraph must point into).
-int use_ws(vv_ctx* c, void* block, size_t have, size_t need) {
+int use_ws(vv_ctx* c, void* block, size_t have, size_t need, Arena* a) {
     if ((uintptr_t)block % 256) return c->fail(-22, "workspace block must be 256-byte aligned");
     if (have < need) return c->fail(-22, "workspace block too small: %zu < %zu bytes", have, need);
-    c->ar = (char*)block; c->ar_cap = have; c->ar_off = 0;
+    *a = Arena{(char*)block, have, 0};
     return 0;
 }
-template <typename T> T* carve(vv_ctx* c, size_t n) {
-    c->ar_off = align_up(c->ar_off, 256);
-    T* p = (T*)(c->ar + c->ar_off);
-    c->ar_off += n * sizeof(T);
-    return p;
+// plan(Arena&) twice: the bytes, then the pointers into `block` (caller-owned) or, block == nullptr, the context's block.
+template <typename F> int plan_ws(vv_ctx* c, void* block, size_t have, F&& plan) {
+    const size_t need = plan_bytes(plan);
+    Arena a;
+    if (int r = block ? use_ws(c, block, have, need, &a) : ensure_ws(c, need, &a)) return r;
+    plan(a);
+    if (a.off > a.cap) return c->fail(-14, "workspace plan took %zu bytes of a %zu-byte block", a.off, a.cap);
+    return 0;
 }
-struct Need { size_t b = 0; void add(size_t bytes) { b = align_up(b, 256) + bytes; } };
 
-// ---- GEMM helper over bound weights -------------------------------------------------------
-int gemm(vv_ctx* c, int dtype, int out_dtype, int mode, int act, const void* A, int lda, const char* wname, int ldw, const char* bname,
-         void* C, int ldc, int M, int N, int K, hipStream_t st, const float* gate = nullptr, int n_store = 0,
-         const float* const* rope = nullptr, int seq_n = 0, int rope_dim = 0, double alg_flops = -1, const int* rope_pos = nullptr,
-         int rope_by_row = 0, void* c_tail = nullptr, int tail_row0 = 0, int tail_parts = 0, int rope_skip_q = 0, float rope_theta = 0.f) {
-    // (c->chip_share: 2 while vv_transformer_steps runs two lanes -- set around its launch loop)
-    // rope: [cos_q, sin_q, cos_k, sin_k, compact_q, compact_k]
-    vv_gemm_args g{};
+// ---- GEMM launches over bound weights -----------------------------------------------------
+// gemm_args fills what every launch has; the call site sets everything optional by field name and hands the launch to launch_gemm.
+struct Gemm : vv_gemm_args { const char* wname; };
+Gemm gemm_args(const vv_ctx* c, int dtype, int out_dtype, int mode, int act, const void* A, int lda, const char* wname, int ldw,
+               const char* bname, void* C, int ldc, int M, int N, int K) {
+    Gemm g{};
     g.dtype = dtype; g.out_dtype = out_dtype; g.mode = mode; g.act = act;
     g.A = A; g.lda = lda; g.W = c->W(wname); g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.bias = bname ? c->Wf(bname) : nullptr; g.gate = gate; g.n_store = n_store; g.seq_n = seq_n; g.rope_dim = rope_dim;
-    if (rope) { g.cos_q = rope[0]; g.sin_q = rope[1]; g.cos_k = rope[2]; g.sin_k = rope[3]; g.rope_cs_q = rope[4]; g.rope_cs_k = rope[5]; }
-    g.rope_pos = rope_pos; g.rope_by_row = rope_by_row;
-    g.C_tail = c_tail; g.tail_row0 = tail_row0; g.tail_parts = tail_parts; g.rope_skip_q = rope_skip_q; g.rope_theta = rope_theta;
-    g.chip_share = c->chip_share;
-    if (!g.W) return c->fail(-2, "weight '%s' is not bound", wname);
-    if (c->pp_min_tiles >= 0 && dtype == VV_DTYPE_BF16 && N % 256 == 0)
+    g.bias = bname ? c->Wf(bname) : nullptr; g.wname = wname;
+    if (bname && !g.bias) g.W = nullptr;          // a named bias that is not bound: refused by launch_gemm like an unbound weight
+    return g;
+}
+// The context's tile rules and chip_share where the call site pinned neither, the profiling record under class `cls`, the launch.
+// alg_flops >= 0: the flops of the un-padded product, where N or K is padded.
+int launch_gemm(vv_ctx* c, Gemm g, int cls, hipStream_t st, double alg_flops = -1) {
+    if (!g.W) return c->fail(-2, "weight '%s' is not bound", g.wname);
+    const int M = g.M, N = g.N, K = g.K, bf16 = g.dtype == VV_DTYPE_BF16;
+    if (!g.chip_share) g.chip_share = c->chip_share;
+    if (g.tile == 0 && c->pp_min_tiles >= 0 && bf16 && N % 256 == 0)
         g.tile = (M >= 4096 && (long long)((M + 255) / 256) * (N / 256) >= c->pp_min_tiles) ? 256 : 128;
-    if (c->ring_tiles && g.tile == 0 && dtype == VV_DTYPE_BF16 && N <= 1024 && N % 64 == 0 && (long long)((M + 63) / 64) * (N / 128) <= c->ring_tiles_max)
+    if (c->ring_tiles && g.tile == 0 && bf16 && N <= 1024 && N % 64 == 0 && (long long)((M + 63) / 64) * (N / 128) <= c->ring_tiles_max)
         g.tile = 6464;
-    const int esz = dtype == VV_DTYPE_BF16 ? 2 : 4, osz = out_dtype == VV_DTYPE_BF16 ? 2 : 4;
+    const int esz = bf16 ? 2 : 4, osz = g.out_dtype == VV_DTYPE_BF16 ? 2 : 4;
     const double fl = alg_flops >= 0 ? alg_flops : 2.0 * M * (double)N * K;
-    Prof p(c, VV_PROF_GEMM, fl, (double)M * K * esz + (double)N * K * esz + (double)M * N * osz * (mode == VV_EPI_GATE_RES ? 2 : 1), st);
+    Prof p(c, cls, fl, (double)M * K * esz + (double)N * K * esz + (double)M * N * osz * (g.mode == VV_EPI_GATE_RES ? 2 : 1), st);
     const char* m = "";
-    int r = vvk_gemm(&g, st, &m);
-    if (r) return c->fail(r, "%s (weight %s, M=%d N=%d K=%d)", m, wname, M, N, K);
+    if (int r = vvk_gemm(&g, st, &m)) return c->fail(r, "%s (weight %s, M=%d N=%d K=%d)", m, g.wname, M, N, K);
     return 0;
 }
 
@@ -410,22 +418,20 @@ static int set_plan_impl(vv_ctx* c, const char* who, const float* sinus_host, co
     if (c->modtab) { hipDeviceSynchronize(); hipFree(c->modtab); hipFree(c->fintab); c->modtab = c->fintab = nullptr; }
     HIPCHK(c, hipMalloc((void**)&c->modtab, sizeof(float) * (size_t)L * S * 6 * D));
     HIPCHK(c, hipMalloc((void**)&c->fintab, sizeof(float) * (size_t)S * 2 * D));
-    Need nd; nd.add(4ull * S * TF); nd.add(4ull * S * D); nd.add(4ull * S * D);
-    if (int r = ensure_ws(c, nd.b)) return r;
-    float* sin_d = carve<float>(c, (size_t)S * TF);
-    float* t1 = carve<float>(c, (size_t)S * D);
-    float* t2 = carve<float>(c, (size_t)S * D);
+    float *sin_d, *t1, *t2;                  // the sinusoids of every evaluation and the two MLP outputs
+    auto bufs = [&](Arena& a) { sin_d = a.take<float>((size_t)S * TF); t1 = a.take<float>((size_t)S * D); t2 = a.take<float>((size_t)S * D); };
+    if (int r = plan_ws(c, nullptr, 0, bufs)) return r;
     HIPCHK(c, hipMemcpyAsync(sin_d, sinus_host, 4ull * S * TF, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));     // host buffer may be pageable; keep its lifetime simple
-    if (int r = gemm(c, VV_DTYPE_F32, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_SILU_, sin_d, TF, "time.mlp1.weight", TF, "time.mlp1.bias", t1, D, S, D, TF, st)) return r;
-    if (int r = gemm(c, VV_DTYPE_F32, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_SILU_, t1, D, "time.mlp2.weight", D, "time.mlp2.bias", t2, D, S, D, D, st)) return r;
+    const int f32 = VV_DTYPE_F32, store = VV_EPI_STORE;
+    if (int r = launch_gemm(c, gemm_args(c, f32, f32, store, VV_ACT_SILU_, sin_d, TF, "time.mlp1.weight", TF, "time.mlp1.bias", t1, D, S, D, TF), VV_PROF_GEMM, st)) return r;
+    if (int r = launch_gemm(c, gemm_args(c, f32, f32, store, VV_ACT_SILU_, t1, D, "time.mlp2.weight", D, "time.mlp2.bias", t2, D, S, D, D), VV_PROF_GEMM, st)) return r;
     // t2 = SiLU(t_emb): every AdaLN consumes the embedding through SiLU only
     for (int l = 0; l < L; ++l) {
         const std::string wn = blk(l, ".adaln.weight"), bn = blk(l, ".adaln.bias");
-        if (int r = gemm(c, VV_DTYPE_F32, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, t2, D, wn.c_str(), D, bn.c_str(),
-                         c->modtab + (size_t)l * S * 6 * D, 6 * D, S, 6 * D, D, st)) return r;
+        if (int r = launch_gemm(c, gemm_args(c, f32, f32, store, VV_ACT_NONE_, t2, D, wn.c_str(), D, bn.c_str(), c->modtab + (size_t)l * S * 6 * D, 6 * D, S, 6 * D, D), VV_PROF_GEMM, st)) return r;
     }
-    if (int r = gemm(c, VV_DTYPE_F32, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, t2, D, "final.adaln.weight", D, "final.adaln.bias", c->fintab, 2 * D, S, 2 * D, D, st)) return r;
+    if (int r = launch_gemm(c, gemm_args(c, f32, f32, store, VV_ACT_NONE_, t2, D, "final.adaln.weight", D, "final.adaln.bias", c->fintab, 2 * D, S, 2 * D, D), VV_PROF_GEMM, st)) return r;
     HIPCHK(c, hipStreamSynchronize(st));
     c->n_steps = n_steps;
     c->dt_host.assign(dt_host, dt_host + n_steps);
@@ -481,16 +487,15 @@ static int preprocess_impl(vv_ctx* c, int B, int N, const int16_t* audio, int ld
     const int Dt = g.text_dim, C2 = Dt * g.text_ff_mult, M = g.n_mel, es = c->esz();
     const int F_max = max_audio_len / g.hop_length + 1;
     const size_t R2 = (size_t)2 * B * N;
-    Need nd;
-    nd.add(4ull * B * F_max * M); nd.add(4ull * R2 * Dt); nd.add(4ull * R2 * Dt); nd.add((size_t)es * R2 * Dt);
-    nd.add((size_t)es * R2 * C2); nd.add(4ull * 2 * B * C2);
-    if (int r = ensure_ws(c, nd.b)) return r;
-    float* mel = carve<float>(c, (size_t)B * F_max * M);
-    float* tx = carve<float>(c, R2 * Dt);
-    float* ty = carve<float>(c, R2 * Dt);
-    char* th = carve<char>(c, (size_t)es * R2 * Dt);
-    char* tm = carve<char>(c, (size_t)es * R2 * C2);
-    float* sumsq = carve<float>(c, (size_t)2 * B * C2);
+    float *mel, *tx, *ty, *sumsq;            // the reference mels, the text stream and its conv output (fp32), the GRN sums
+    char *th, *tm;                           // operand dtype: the norm output and the MLP plane
+    auto bufs = [&](Arena& a) {
+        mel = a.take<float>((size_t)B * F_max * M);
+        tx = a.take<float>(R2 * Dt); ty = a.take<float>(R2 * Dt);
+        th = a.take<char>((size_t)es * R2 * Dt); tm = a.take<char>((size_t)es * R2 * C2);
+        sumsq = a.take<float>((size_t)2 * B * C2);
+    };
+    if (int r = plan_ws(c, nullptr, 0, bufs)) return r;
 
     KCHK(c, vvk_ref_len(audio_len, ref_len, B, g.hop_length, st, &m__));
     {
@@ -514,12 +519,13 @@ static int preprocess_impl(vv_ctx* c, int B, int N, const int16_t* audio, int ld
             Prof pr(c, VV_PROF_NORM, 0, (4.0 + es) * R2 * Dt, st);
             KCHK(c, vvk_ln_mod(&a, st, &m__));
         }
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_ERF_, th, Dt, (p + ".pwconv1.weight").c_str(), Dt, (p + ".pwconv1.bias").c_str(), tm, C2, (int)R2, C2, Dt, st)) return r;
+        const std::string w1 = p + ".pwconv1.weight", b1 = p + ".pwconv1.bias", w2 = p + ".pwconv2.weight", b2 = p + ".pwconv2.bias";
+        if (int r = launch_gemm(c, gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_ERF_, th, Dt, w1.c_str(), Dt, b1.c_str(), tm, C2, (int)R2, C2, Dt), VV_PROF_GEMM, st)) return r;
         {
             Prof pr(c, VV_PROF_TEXT, 0, 3.0 * es * R2 * C2, st);
             KCHK(c, vvk_grn(c->dt, tm, sumsq, c->Wf(p + ".grn.gamma"), c->Wf(p + ".grn.beta"), seq_len, B, 2 * B, N, C2, st, &m__));
         }
-        if (int r = gemm(c, c->dt, VV_DTYPE_F32, VV_EPI_GATE_RES, VV_ACT_NONE_, tm, C2, (p + ".pwconv2.weight").c_str(), C2, (p + ".pwconv2.bias").c_str(), tx, Dt, (int)R2, Dt, C2, st)) return r;
+        if (int r = launch_gemm(c, gemm_args(c, c->dt, VV_DTYPE_F32, VV_EPI_GATE_RES, VV_ACT_NONE_, tm, C2, w2.c_str(), C2, b2.c_str(), tx, Dt, (int)R2, Dt, C2), VV_PROF_GEMM, st)) return r;
     }
     {
         Prof p(c, VV_PROF_ELEMWISE, 0, 12.0 * B * N * (M + Dt) + (keep ? (double)B * N : 0.0), st);
@@ -579,8 +585,8 @@ int vv_edit_restore(vv_ctx* c, int B, int N, float* x, const float* cat, const u
 }
 
 // --------------------------------------------------------------------------- transformer steps
-// ws_only != nullptr: only compute the workspace bytes the call would carve (nothing is launched; the data pointers may be null).
-// ext_ws != nullptr: carve from that caller-owned block instead of the context arena (what a captured hipGraph must point into).
+// ws_only != nullptr: only compute the workspace bytes the call would take (nothing is launched; the data pointers may be null).
+// args.ws != nullptr: take them from that caller-owned block instead of the context's (what a captured hipGraph must point into).
 //
 // LANES (round 4): a batch of independent items may run as TWO half batches ("lanes") on two HIP streams at once -- lane 0 on the
 // caller's stream, lane 1 on a context-owned side stream forked from it and joined back before the call returns.  Every kernel of
@@ -610,13 +616,37 @@ struct Lane {
     int *kv_len = nullptr, *tab = nullptr;
     const int *row_start = nullptr, *row_src = nullptr, *row_pos = nullptr, *qkv_pos = nullptr;
 };
+
+// workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
+// zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N) {
+    const vv_model_cfg& g = c->cfg;
+    const size_t R = L.R, es = c->esz(), D = g.dim, FF = D * g.ff_mult, M = g.n_mel;
+    const size_t KP = pad_to(2 * g.n_mel + g.text_dim, 64), MP = pad_to(g.n_mel, 128);
+    L.xcat = a.take<char>(es * R * KP);
+    L.h = a.take<char>(es * R * D); L.h2 = a.take<char>(es * R * D); L.h3 = a.take<char>(es * R * D);
+    L.xres = a.take<float>(R * D);
+    L.qkv = a.take<char>(es * R * 3 * D); L.att = a.take<char>(es * R * D); L.ffm = a.take<char>(es * R * FF);
+    L.pred = a.take<float>(R * MP); L.kv_len = a.take<int>(2 * L.B);
+    L.csq = a.take<float>((size_t)N * 64); L.csk = a.take<float>((size_t)N * 64);
+    L.tab = a.take<int>(L.n_tab);                  // row_start[2B] | row_src[Rc] | row_pos[R]
+    L.csq_rows = a.take<float>(R * 64); L.csk_rows = a.take<float>(R * 64);     // compact rope tables gathered per packed row, once per call
+    L.h2_tail = a.take<float>(L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0));     // fp32 [parts][tail_rows][D] K parts of the tail rows' deltas
+    L.h3_tail = a.take<float>(L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
+    if (c->ode_s > 1) {                            // N7: the stage state and the stored slopes
+        L.xs = a.take<float>(L.Rc * M);
+        for (int k = 0; k < c->ode_nk; ++k) L.kbuf[k] = a.take<float>(L.Rc * M);
+    }
+}
 }  // namespace
 
-static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat,
-                                  const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
-                                  const float* rope_sin_k, int step0, int n_steps, void* stream, void* ext_ws = nullptr,
-                                  uint64_t ext_bytes = 0, uint64_t* ws_only = nullptr, const float* cfg_item = nullptr) {
+static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t* ws_only, void* stream) {
     if (!c) return -22;
+    const int B = args.B, N = args.N, step0 = args.step0, n_steps = args.n_steps;
+    const int32_t *seq_len = args.seq_len, *seq_len_host = args.seq_len_host;
+    float* x = args.x;
+    const float *cat = args.cat_mel_text, *cat_drop = args.cat_mel_text_drop, *cfg_item = args.cfg_item, *rope_cos_q = args.rope_cos_q,
+                *rope_sin_q = args.rope_sin_q, *rope_cos_k = args.rope_cos_k, *rope_sin_k = args.rope_sin_k;
     if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
     if (B < 1 || N < 1 || (!ws_only && (!seq_len || !x || !cat || !cat_drop || !rope_cos_q || !rope_sin_q || !rope_cos_k || !rope_sin_k)))
         return c->fail(-22, "vv_transformer_steps: bad arguments");
@@ -667,7 +697,6 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
     Lane lanes[2];
     const int ns = c->ode_s, S = c->n_steps * ns;      // S: rows of the modulation tables (evaluations)
     const bool rk = ns > 1 || cfg_item != nullptr;       // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
-    Need nd;
     for (int li = 0; li < n_lanes; ++li) {
         Lane& L = lanes[li];
         L.b0 = cuts[li]; L.B = cuts[li + 1] - cuts[li];
@@ -683,16 +712,10 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         }
         L.tail_rows = (L.tp_o || L.tp_f) ? L.R - L.tail_row0 : 0;
         L.n_tab = 2 * (size_t)L.B + L.Rc + L.R;          // row_start[2B] | row_src[Rc] | row_pos[R]
-        const size_t R = L.R;
-        nd.add(es * R * KP); nd.add(es * R * D); nd.add(es * R * D); nd.add(es * R * D); nd.add(4 * R * D); nd.add(es * R * 3 * D); nd.add(es * R * D);
-        nd.add(es * R * FF); nd.add(4 * R * MP); nd.add(4 * 2 * L.B); nd.add(4ull * N * 64); nd.add(4ull * N * 64); nd.add(4ull * L.n_tab);
-        nd.add(4ull * R * 64); nd.add(4ull * R * 64);
-        nd.add(4 * L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0)); nd.add(4 * L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
-        if (ns > 1) for (int k = 0; k < 1 + c->ode_nk; ++k) nd.add(4 * L.Rc * M);
     }
-    if (ws_only) { *ws_only = (uint64_t)align_up(nd.b, 256); return 0; }
-    if (ext_ws) { if (int r = use_ws(c, ext_ws, (size_t)ext_bytes, nd.b)) return r; }
-    else if (int r = ensure_ws(c, nd.b)) return r;
+    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N); };
+    if (ws_only) { *ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
+    if (int r = plan_ws(c, args.ws, (size_t)args.ws_bytes, bufs)) return r;
     for (int li = 1; li < (branch_lanes ? 2 : n_lanes); ++li)
         if (!c->side_stream[li - 1]) {
             HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream[li - 1], hipStreamNonBlocking));
@@ -701,30 +724,8 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
     if ((n_lanes > 1 || branch_lanes) && !c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
     for (int li = 0; li < n_lanes; ++li) {
         Lane& L = lanes[li];
-        const size_t R = L.R;
         L.seq_len = seq_len + L.b0; L.x = x + (size_t)L.b0 * N * M; L.cat = cat + (size_t)L.b0 * N * CD; L.cat_drop = cat_drop + (size_t)L.b0 * N * CD;
         L.st = li == 0 ? st : c->side_stream[li - 1];
-        L.xcat = carve<char>(c, es * R * KP);
-        L.h = carve<char>(c, es * R * D);
-        L.h2 = carve<char>(c, es * R * D);
-        L.h3 = carve<char>(c, es * R * D);
-        L.xres = carve<float>(c, R * D);
-        L.qkv = carve<char>(c, es * R * 3 * D);
-        L.att = carve<char>(c, es * R * D);
-        L.ffm = carve<char>(c, es * R * FF);
-        L.pred = carve<float>(c, R * MP);
-        L.kv_len = carve<int>(c, 2 * L.B);
-        L.csq = carve<float>(c, (size_t)N * 64);
-        L.csk = carve<float>(c, (size_t)N * 64);
-        L.tab = carve<int>(c, L.n_tab);
-        L.csq_rows = carve<float>(c, R * 64);          // compact rope tables gathered per packed row, once per call
-        L.csk_rows = carve<float>(c, R * 64);
-        L.h2_tail = carve<float>(c, L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0));     // fp32 [parts][tail_rows][D] K parts of the tail rows' deltas
-        L.h3_tail = carve<float>(c, L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
-        if (ns > 1) {
-            L.xs = carve<float>(c, L.Rc * M);
-            for (int k = 0; k < c->ode_nk; ++k) L.kbuf[k] = carve<float>(c, L.Rc * M);
-        }
         L.row_start = L.tab; L.row_src = L.tab + 2 * L.B; L.row_pos = L.row_src + L.Rc;
         L.qkv_pos = L.uniform ? nullptr : L.row_pos;   // every sequence N rows: position = packed row mod N, no table lookup
     }
@@ -763,8 +764,8 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         (void)s;
         hipStream_t st = L.st;
         const size_t R = L.R;
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_NONE_, L.xcat, KP, "input.proj.weight", KP, "input.proj.bias", L.h, D, (int)R, D, KP, st,
-                         nullptr, 0, nullptr, 0, 0, 2.0 * R * D * (M + CD))) return r;
+        Gemm proj = gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_NONE_, L.xcat, KP, "input.proj.weight", KP, "input.proj.bias", L.h, D, (int)R, D, KP);
+        if (int r = launch_gemm(c, proj, VV_PROF_GEMM, st, 2.0 * R * D * (M + CD))) return r;
         for (int j = 1; j <= 2; ++j) {
             vv_posconv_args a{};
             a.dtype = c->dt; a.out_dtype = (j == 1) ? c->dt : VV_DTYPE_F32;
@@ -788,7 +789,6 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         hipStream_t st = L.st;
         const size_t R = L.R;
         const bool pending = L.pending;
-        const float* rope[6] = {rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, c->rope_rows ? L.csq_rows : L.csq, c->rope_rows ? L.csk_rows : L.csk};
         const float* mod = c->modtab + ((size_t)l * S + s) * 6 * D;
         const std::string qkvw = blk(l, ".attn.qkv.weight"), qkvb = blk(l, ".attn.qkv.bias"), ow = blk(l, ".attn.out.weight"),
                           ob = blk(l, ".attn.out.bias"), f1w = blk(l, ".ff1.weight"), f1b = blk(l, ".ff1.bias"),
@@ -800,8 +800,11 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
         a.w = mod + D; a.b = mod;                       // scale_msa, shift_msa
         a.delta = pending ? L.h2 : nullptr; a.delta2 = pending ? L.h3 : nullptr; a.keep_x = 0;
         { Prof p(c, VV_PROF_NORM, 0, (4.0 + es) * R * D + (pending ? (4.0 + 2.0 * es) * R * D : 0), st); KCHK(c, vvk_ln_mod(&a, st, &m__)); }
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_QKV_ROPE, VV_ACT_NONE_, L.h, D, qkvw.c_str(), D, qkvb.c_str(), L.qkv, 3 * D, (int)R, 3 * D, D, st, nullptr, 0, rope, N, D, -1, L.qkv_pos, c->rope_rows,
-                         nullptr, 0, 0, q_rope_attn, rope_theta)) return r;
+        Gemm qkv = gemm_args(c, c->dt, c->dt, VV_EPI_QKV_ROPE, VV_ACT_NONE_, L.h, D, qkvw.c_str(), D, qkvb.c_str(), L.qkv, 3 * D, (int)R, 3 * D, D);
+        qkv.cos_q = rope_cos_q; qkv.sin_q = rope_sin_q; qkv.cos_k = rope_cos_k; qkv.sin_k = rope_sin_k;
+        qkv.rope_cs_q = c->rope_rows ? L.csq_rows : L.csq; qkv.rope_cs_k = c->rope_rows ? L.csk_rows : L.csk; qkv.rope_by_row = c->rope_rows;
+        qkv.seq_n = N; qkv.rope_dim = D; qkv.rope_pos = L.qkv_pos; qkv.rope_skip_q = q_rope_attn; qkv.rope_theta = rope_theta;
+        if (int r = launch_gemm(c, qkv, VV_PROF_GEMM, st)) return r;
         {
             vv_attn_args t{}; t.dtype = c->dt; t.qkv = L.qkv; t.ld_qkv = 3 * D; t.out = L.att; t.ld_out = D; t.n_seq = L.n_seq; t.seq_n = N;
             t.heads = g.heads; t.dim = D; t.kv_len = L.kv_len; t.row_start = L.row_start; t.total_rows = (int)R;
@@ -810,14 +813,18 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
             Prof p(c, VV_PROF_ATTN, 4.0 * g.heads * L.sum_sq * 64, (double)es * R * 4 * D, st);
             KCHK(c, vvk_attention(&t, st, &m__));
         }
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.att, D, ow.c_str(), D, ob.c_str(), L.h2, D, (int)R, D, D, st, mod + 2 * D,
-                         0, nullptr, 0, 0, -1, nullptr, 0, L.tp_o ? L.h2_tail : nullptr, L.tp_o ? L.tail_row0 : 0, L.tp_o)) return r;
+        Gemm out = gemm_args(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.att, D, ow.c_str(), D, ob.c_str(), L.h2, D, (int)R, D, D);
+        out.gate = mod + 2 * D;                         // gate_msa
+        if (L.tp_o) { out.C_tail = L.h2_tail; out.tail_row0 = L.tail_row0; out.tail_parts = L.tp_o; }
+        if (int r = launch_gemm(c, out, VV_PROF_GEMM, st)) return r;
         a.w = mod + 4 * D; a.b = mod + 3 * D;           // scale_mlp, shift_mlp
         a.delta = L.h2; a.delta2 = nullptr; a.keep_x = 1; a.delta_tail_parts = L.tp_o; a.delta2_tail_parts = 0;
         { Prof p(c, VV_PROF_NORM, 0, (4.0 + 2.0 * es) * R * D, st); KCHK(c, vvk_ln_mod(&a, st, &m__)); }
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_TANH_, L.h, D, f1w.c_str(), D, f1b.c_str(), L.ffm, FF, (int)R, FF, D, st)) return r;
-        if (int r = gemm(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.ffm, FF, f2w.c_str(), FF, f2b.c_str(), L.h3, D, (int)R, D, FF, st, mod + 5 * D,
-                         0, nullptr, 0, 0, -1, nullptr, 0, L.tp_f ? L.h3_tail : nullptr, L.tp_f ? L.tail_row0 : 0, L.tp_f)) return r;
+        if (int r = launch_gemm(c, gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_TANH_, L.h, D, f1w.c_str(), D, f1b.c_str(), L.ffm, FF, (int)R, FF, D), VV_PROF_GEMM, st)) return r;
+        Gemm ff2 = gemm_args(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.ffm, FF, f2w.c_str(), FF, f2b.c_str(), L.h3, D, (int)R, D, FF);
+        ff2.gate = mod + 5 * D;                         // gate_mlp
+        if (L.tp_f) { ff2.C_tail = L.h3_tail; ff2.tail_row0 = L.tail_row0; ff2.tail_parts = L.tp_f; }
+        if (int r = launch_gemm(c, ff2, VV_PROF_GEMM, st)) return r;
         L.pending = true;
         return 0;
     };
@@ -836,9 +843,9 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
             Prof p(c, VV_PROF_NORM, 0, es * R * D + (pending ? (4.0 + 2.0 * es) * R * D : 4.0 * R * D), st);
             KCHK(c, vvk_ln_mod(&a, st, &m__));
         }
-        if (int r = gemm(c, c->dt, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, L.h, D, "final.proj.weight", D, "final.proj.bias", L.pred, MP, (int)R, MP, D, st,
-                         nullptr, M, nullptr, 0, 0, 2.0 * R * D * M)) return r;
-        return 0;
+        Gemm proj = gemm_args(c, c->dt, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, L.h, D, "final.proj.weight", D, "final.proj.bias", L.pred, MP, (int)R, MP, D);
+        proj.n_store = M;
+        return launch_gemm(c, proj, VV_PROF_GEMM, st, 2.0 * R * D * M);
     };
     auto step_euler = [&](Lane& L, int s) -> int {
         hipStream_t st = L.st;
@@ -921,10 +928,19 @@ static int transformer_steps_impl(vv_ctx* c, int B, int N, const int32_t* seq_le
     return rc;
 }
 
+// the arguments of the positional entries as the struct the stage runs on
+static vv_steps_args steps_args(int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat, const float* cat_drop,
+                                const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k, int step0, int n_steps) {
+    vv_steps_args a{};
+    a.B = B; a.N = N; a.seq_len = seq_len; a.seq_len_host = seq_len_host; a.x = x; a.cat_mel_text = cat; a.cat_mel_text_drop = cat_drop;
+    a.rope_cos_q = rope_cos_q; a.rope_sin_q = rope_sin_q; a.rope_cos_k = rope_cos_k; a.rope_sin_k = rope_sin_k; a.step0 = step0; a.n_steps = n_steps;
+    return a;
+}
+
 int vv_transformer_steps(vv_ctx* c, int B, int N, const int32_t* seq_len, float* x, const float* cat, const float* cat_drop,
                          const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k,
                          int step0, int n_steps, void* stream) {
-    return transformer_steps_impl(c, B, N, seq_len, nullptr, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps, stream);
+    return transformer_steps_impl(c, steps_args(B, N, seq_len, nullptr, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), nullptr, stream);
 }
 
 // Same, with the per-item lengths ALSO given on the host (they must equal the device array): no read-back, no stream
@@ -933,22 +949,26 @@ int vv_transformer_steps_h(vv_ctx* c, int B, int N, const int32_t* seq_len, cons
                            const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
                            const float* rope_sin_k, int step0, int n_steps, void* stream) {
     if (c && !seq_len_host) return c->fail(-22, "vv_transformer_steps_h: host lengths missing");
-    return transformer_steps_impl(c, B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps, stream);
+    return transformer_steps_impl(c, steps_args(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), nullptr, stream);
 }
 
-// The same call with every intermediate carved from a CALLER-OWNED block (>= vv_transformer_ws_bytes for the same B, N and host
+// The same call with every intermediate taken from a CALLER-OWNED block (>= vv_transformer_ws_bytes for the same B, N and host
 // lengths, 256-byte aligned): no allocation and no synchronisation anywhere in the call, and nothing it points at can move -- the
 // form to capture into a hipGraph (all Euler steps of an utterance + vv_decode_into = one graph launch).
 int vv_transformer_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
     if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_ws_bytes: bad arguments");
-    return transformer_steps_impl(c, B, N, nullptr, seq_len_host, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, bytes);
+    vv_steps_args a{};                                    // nothing is launched: no device pointer is needed
+    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
+    return transformer_steps_impl(c, a, bytes, nullptr);
 }
 
 int vv_transformer_steps_into(vv_ctx* c, int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat,
                               const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
                               const float* rope_sin_k, int step0, int n_steps, void* ws, uint64_t ws_bytes, void* stream) {
     if (c && (!seq_len_host || !ws)) return c->fail(-22, "vv_transformer_steps_into: host lengths and a workspace block are required");
-    return transformer_steps_impl(c, B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps, stream, ws, ws_bytes);
+    vv_steps_args a = steps_args(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps);
+    a.ws = ws; a.ws_bytes = ws_bytes;
+    return transformer_steps_impl(c, a, nullptr, stream);
 }
 
 // N7: the struct-argument form -- the arguments of the three entries above plus a guidance strength per item
@@ -957,42 +977,47 @@ int vv_transformer_steps_ex(vv_ctx* c, const vv_steps_args* a, void* stream) {
     if (!a) return c->fail(-22, "vv_transformer_steps_ex: null arguments");
     if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_ex: a workspace block needs the host lengths");
     if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_ex: cfg_item must be a float array");
-    return transformer_steps_impl(c, a->B, a->N, a->seq_len, a->seq_len_host, a->x, a->cat_mel_text, a->cat_mel_text_drop, a->rope_cos_q,
-                                  a->rope_sin_q, a->rope_cos_k, a->rope_sin_k, a->step0, a->n_steps, stream, a->ws, a->ws_bytes, nullptr,
-                                  a->cfg_item);
+    return transformer_steps_impl(c, *a, nullptr, stream);
 }
 
 // --------------------------------------------------------------------------------------- decode
-// N6 Vocos: lens[B], three [B * T_max][dim] planes (residual stream, conv / norm outputs), one plane as wide as the widest GEMM
-// operand (im2col, intermediate, head, frames), the spectrum operand [B * T_max][n_fft]
 static int vocos_wide(const vv_ctx* c) {
     const vv_vocos_cfg& v = c->vcfg;
     return std::max(std::max(pad_to(v.embed_k * c->cfg.n_mel, 32), v.intermediate), pad_to(v.n_fft + 2, 128));
 }
-static size_t vocos_need(const vv_ctx* c, int B, int t_gen_max) {
-    const size_t R = (size_t)B * t_gen_max;
-    Need nd; nd.add(4ull * B);
-    for (int i = 0; i < 3; ++i) nd.add(4ull * R * c->vcfg.dim);
-    nd.add(4ull * R * vocos_wide(c)); nd.add(4ull * R * c->vcfg.n_fft);
-    return nd.b;
+// N6 Vocos: lens[B], three [B * T_max][dim] planes (residual stream, conv / norm outputs), one plane as wide as the widest GEMM
+// operand (im2col, intermediate, head, frames), the spectrum operand [B * T_max][n_fft]
+struct VocosBufs { int* lens; float *res, *t, *hn, *big, *spec; };
+static VocosBufs vocos_bufs(Arena& a, const vv_ctx* c, int B, int T_max) {
+    const size_t R = (size_t)B * T_max, V = c->vcfg.dim;
+    VocosBufs w;
+    w.lens = a.take<int>(B);
+    w.res = a.take<float>(R * V); w.t = a.take<float>(R * V); w.hn = a.take<float>(R * V);
+    w.big = a.take<float>(R * vocos_wide(c)); w.spec = a.take<float>(R * c->vcfg.n_fft);
+    return w;
 }
-
-static size_t decode_need(const vv_ctx* c, int B, int t_gen_max) {
-    if (c->vocos) return vocos_need(c, B, t_gen_max);
-    const vv_model_cfg& g = c->cfg;
-    const int nu = g.voc_n_up;
-    size_t big = (size_t)g.voc_pre_ch * t_gen_max, T = t_gen_max;
-    int ch = g.voc_pre_ch;
-    for (int s = 0; s < nu; ++s) { T *= g.voc_up_rates[s]; ch /= 2; big = std::max(big, (size_t)ch * T); }
-    Need nd; nd.add(4ull * B * g.n_mel * t_gen_max);
-    for (int i = 0; i < 5; ++i) nd.add(4ull * B * big);
-    nd.add(4ull * (nu + 1) * B);
-    return nd.b;
+// HiFi-GAN: frames and channels per level (0 = conv_pre's output, s + 1 = after upsampler s) and the largest [C][T] plane
+struct HifiPlan { int Ts[VV_MAX_UP + 1], Cs[VV_MAX_UP + 1]; size_t big; };
+static HifiPlan hifi_plan(const vv_model_cfg& g, int t_gen_max) {
+    HifiPlan p;
+    p.Ts[0] = t_gen_max; p.Cs[0] = g.voc_pre_ch; p.big = (size_t)p.Cs[0] * p.Ts[0];
+    for (int s = 0; s < g.voc_n_up; ++s) { p.Ts[s + 1] = p.Ts[s] * g.voc_up_rates[s]; p.Cs[s + 1] = p.Cs[s] / 2; p.big = std::max(p.big, (size_t)p.Cs[s + 1] * p.Ts[s + 1]); }
+    return p;
+}
+// the mel slice, five rotating [B][big] planes, the lengths of every level
+struct HifiBufs { float *v0, *buf[5]; int* lens; };
+static HifiBufs hifi_bufs(Arena& a, const vv_model_cfg& g, const HifiPlan& p, int B) {
+    HifiBufs w{a.take<float>((size_t)B * g.n_mel * p.Ts[0])};
+    for (float*& b : w.buf) b = a.take<float>((size_t)B * p.big);
+    w.lens = a.take<int>((size_t)(g.voc_n_up + 1) * B);
+    return w;
 }
 
 int vv_decode_ws_bytes(vv_ctx* c, int B, int t_gen_max, uint64_t* bytes) {
     if (!c || !bytes || B < 1 || t_gen_max < 1) return c ? c->fail(-22, "vv_decode_ws_bytes: bad arguments") : -22;
-    *bytes = (uint64_t)align_up(decode_need(c, B, t_gen_max), 256);
+    Arena dry;
+    if (c->vocos) vocos_bufs(dry, c, B, t_gen_max); else hifi_bufs(dry, c->cfg, hifi_plan(c->cfg, t_gen_max), B);
+    *bytes = (uint64_t)align_up(dry.off, 256);
     return 0;
 }
 
@@ -1000,17 +1025,10 @@ uint64_t vv_ws_generation(const vv_ctx* c) { return c ? c->ws_generation : 0; }
 
 // ---- N6 Vocos.  Every GEMM is fp32 on the pinned 128 x 128 tiling: a row's arithmetic is then the same whatever
 // the batch (M) it shares a launch with.
-static int vocos_gemm(vv_ctx* c, int mode, int act, const float* A, int lda, const std::string& wn, const char* bn, float* C, int ldc, int M,
-                      int N, int K, const float* gate, int n_store, int cls, hipStream_t st) {
-    vv_gemm_args g{};
-    g.dtype = VV_DTYPE_F32; g.out_dtype = VV_DTYPE_F32; g.mode = mode; g.act = act;
-    g.A = A; g.lda = lda; g.W = c->W(wn); g.ldw = K; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.bias = bn ? c->Wf(bn) : nullptr; g.gate = gate; g.n_store = n_store; g.tile = 128; g.chip_share = 1;
-    if (!g.W || (bn && !g.bias)) return c->fail(-2, "weight '%s' is not bound", wn.c_str());
-    Prof p(c, cls, 2.0 * M * (double)N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N * (mode == VV_EPI_GATE_RES ? 2 : 1)), st);
-    const char* m = "";
-    if (int r = vvk_gemm(&g, st, &m)) return c->fail(r, "%s (weight %s, M=%d N=%d K=%d)", m, wn.c_str(), M, N, K);
-    return 0;
+static Gemm vocos_gemm(const vv_ctx* c, int mode, int act, const float* A, int lda, const char* wn, const char* bn, float* C, int ldc, int M, int N, int K) {
+    Gemm g = gemm_args(c, VV_DTYPE_F32, VV_DTYPE_F32, mode, act, A, lda, wn, K, bn, C, ldc, M, N, K);
+    g.tile = 128; g.chip_share = 1;
+    return g;
 }
 
 static int vocos_ln(vv_ctx* c, const float* x, float* y, int R, const std::string& n, hipStream_t st) {
@@ -1031,7 +1049,7 @@ static int vocos_istft(vv_ctx* c, int B, int T_max, const float* head, int ld_he
         Prof p(c, VV_PROF_VOC_POST, 0, 4.0 * R * ((double)n + 2 + n), st);
         KCHK(c, vvk_vocos_spectrum(head, ld_head, R, n, spec, st, &m__));
     }
-    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, spec, n, "const.istft_basis", nullptr, frames, n, R, n, n, nullptr, 0, VV_PROF_VOC_POST, st)) return r;
+    if (int r = launch_gemm(c, vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, spec, n, "const.istft_basis", nullptr, frames, n, R, n, n), VV_PROF_VOC_POST, st)) return r;
     Prof p(c, VV_PROF_VOC_POST, 0, 4.0 * R * (double)n + 6.0 * B * (double)T_max * hop, st);
     KCHK(c, vvk_vocos_ola(frames, n, B, T_max, lens, c->Wf("const.window"), n, hop, pcm, ld_pcm, pcm_len, wave, T_max * hop, st, &m__));
     return 0;
@@ -1043,21 +1061,15 @@ static int decode_vocos(vv_ctx* c, int B, int N, const float* x, const int32_t* 
     const int M = c->cfg.n_mel, V = v.dim, I = v.intermediate, KE = pad_to(v.embed_k * M, 32), HP = pad_to(v.n_fft + 2, 128);
     if ((size_t)B * T_max * vocos_wide(c) * 4 >= ((size_t)1 << 31)) return c->fail(-22, "vv_decode: a Vocos plane of 2 GiB or more (split the batch)");
     const int R = B * T_max;
-    const size_t need = vocos_need(c, B, T_max);
-    if (ext_ws) { if (int r = use_ws(c, ext_ws, (size_t)ext_bytes, need)) return r; }
-    else if (int r = ensure_ws(c, need)) return r;
-    int* lens = carve<int>(c, B);
-    float* res = carve<float>(c, (size_t)R * V);
-    float* t = carve<float>(c, (size_t)R * V);
-    float* hn = carve<float>(c, (size_t)R * V);
-    float* big = carve<float>(c, (size_t)R * vocos_wide(c));
-    float* spec = carve<float>(c, (size_t)R * v.n_fft);
+    VocosBufs w;
+    if (int r = plan_ws(c, ext_ws, (size_t)ext_bytes, [&](Arena& a) { w = vocos_bufs(a, c, B, T_max); })) return r;
+    auto [lens, res, t, hn, big, spec] = w;
     KCHK(c, vvk_vocos_lens(seq_len, ref_len, lens, B, N, T_max, st, &m__));
     {
         Prof p(c, VV_PROF_VOC_CONV, 0, 4.0 * R * ((double)M + KE), st);
         KCHK(c, vvk_vocos_im2col(x, B, N, M, ref_len, seq_len, T_max, v.embed_k, big, KE, st, &m__));
     }
-    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, big, KE, "voc.embed.weight", "voc.embed.bias", t, V, R, V, KE, nullptr, 0, VV_PROF_VOC_CONV, st)) return r;
+    if (int r = launch_gemm(c, vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, big, KE, "voc.embed.weight", "voc.embed.bias", t, V, R, V, KE), VV_PROF_VOC_CONV, st)) return r;
     if (int r = vocos_ln(c, t, res, R, "voc.norm", st)) return r;
     for (int i = 0; i < v.layers; ++i) {
         const std::string p = "voc.blocks." + std::to_string(i);
@@ -1066,14 +1078,16 @@ static int decode_vocos(vv_ctx* c, int B, int N, const float* x, const int32_t* 
             KCHK(c, vvk_dwconv(res, t, c->Wf(p + ".dwconv.weight"), c->Wf(p + ".dwconv.bias"), lens, B, B, T_max, V, v.dw_k, st, &m__));
         }
         if (int r = vocos_ln(c, t, hn, R, p + ".norm", st)) return r;
-        if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_GELU_ERF_, hn, V, p + ".pwconv1.weight", (p + ".pwconv1.bias").c_str(), big, I, R, I, V,
-                               nullptr, 0, VV_PROF_VOC_CONV, st)) return r;
-        if (int r = vocos_gemm(c, VV_EPI_GATE_RES, VV_ACT_NONE_, big, I, p + ".pwconv2.weight", (p + ".pwconv2.bias").c_str(), res, V, R, V, I,
-                               c->Wf(p + ".gamma"), 0, VV_PROF_VOC_CONV, st)) return r;
+        const std::string w1 = p + ".pwconv1.weight", b1 = p + ".pwconv1.bias", w2 = p + ".pwconv2.weight", b2 = p + ".pwconv2.bias";
+        if (int r = launch_gemm(c, vocos_gemm(c, VV_EPI_STORE, VV_ACT_GELU_ERF_, hn, V, w1.c_str(), b1.c_str(), big, I, R, I, V), VV_PROF_VOC_CONV, st)) return r;
+        Gemm g2 = vocos_gemm(c, VV_EPI_GATE_RES, VV_ACT_NONE_, big, I, w2.c_str(), b2.c_str(), res, V, R, V, I);
+        g2.gate = c->Wf(p + ".gamma");
+        if (int r = launch_gemm(c, g2, VV_PROF_VOC_CONV, st)) return r;
     }
     if (int r = vocos_ln(c, res, hn, R, "voc.final_norm", st)) return r;
-    if (int r = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, hn, V, "voc.head.weight", "voc.head.bias", big, HP, R, HP, V, nullptr, v.n_fft + 2,
-                           VV_PROF_VOC_POST, st)) return r;
+    Gemm head = vocos_gemm(c, VV_EPI_STORE, VV_ACT_NONE_, hn, V, "voc.head.weight", "voc.head.bias", big, HP, R, HP, V);
+    head.n_store = v.n_fft + 2;
+    if (int r = launch_gemm(c, head, VV_PROF_VOC_POST, st)) return r;
     return vocos_istft(c, B, T_max, big, HP, lens, pcm, ld_pcm, pcm_len, wave_f32, spec, big, st);
 }
 
@@ -1089,19 +1103,11 @@ static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* r
     hipStream_t st = (hipStream_t)stream;
     if (c->vocos) return decode_vocos(c, B, N, x, ref_len, seq_len, t_gen_max, pcm, ld_pcm, pcm_len, wave_f32, ext_ws, ext_bytes, st);
     const int M = g.n_mel, nu = g.voc_n_up;
-    // buffer plan
-    std::vector<int> Ts(nu + 1), Cs(nu + 1);
-    Ts[0] = t_gen_max; Cs[0] = g.voc_pre_ch;
-    size_t big = 0;
-    for (int s = 0; s < nu; ++s) { Ts[s + 1] = Ts[s] * g.voc_up_rates[s]; Cs[s + 1] = Cs[s] / 2; big = std::max(big, (size_t)Cs[s + 1] * Ts[s + 1]); }
-    big = std::max(big, (size_t)Cs[0] * Ts[0]);
-    const size_t need = decode_need(c, B, t_gen_max);
-    if (ext_ws) { if (int r = use_ws(c, ext_ws, (size_t)ext_bytes, need)) return r; }
-    else if (int r = ensure_ws(c, need)) return r;
-    float* v0 = carve<float>(c, (size_t)B * M * Ts[0]);
-    float* buf[5];
-    for (int i = 0; i < 5; ++i) buf[i] = carve<float>(c, (size_t)B * big);
-    int* lens = carve<int>(c, (size_t)(nu + 1) * B);
+    const HifiPlan plan = hifi_plan(g, t_gen_max);
+    const int *Ts = plan.Ts, *Cs = plan.Cs;
+    HifiBufs w;
+    if (int r = plan_ws(c, ext_ws, (size_t)ext_bytes, [&](Arena& a) { w = hifi_bufs(a, g, plan, B); })) return r;
+    auto [v0, buf, lens] = w;
 
     KCHK(c, vvk_decode_len(seq_len, ref_len, lens, B, nu + 1, c->d_mult, st, &m__));
     HIPCHK(c, hipMemcpyAsync(pcm_len, lens + (size_t)nu * B, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
@@ -1139,7 +1145,7 @@ static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* r
         if (int r = conv(cur, "voc.up." + std::to_string(s), up_out, nullptr, Cs[s], C, Ts[s], T, 2, 1, g.voc_up_rates[s], g.voc_lrelu, 1.0f, 0, lens + (size_t)s * B,
                          s < 4 ? VV_PROF_VOC_UP0 + s : -1)) return r;
         // MRF: acc = (1/n_res) * sum_a resblock_a(up_out)
-        float* acc = cur;                                   // previous stage input is dead now
+        float* acc = cur;                                   // the previous stage's input is dead now: the sum lands there and is the next stage's input
         float* t1 = (up_out == buf[1]) ? buf[2] : buf[1];
         float* ya = buf[3];
         float* yb = buf[4];
@@ -1169,11 +1175,6 @@ static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* r
                 y = dst;
             }
         }
-        // rotate: acc becomes the next stage input; up_out buffer is free
-        float* old_up = up_out;
-        cur = acc;
-        up_out = old_up;
-        // make sure next up_out differs from cur (it does: acc was the previous cur)
     }
     {
         const int C = Cs[nu], T = Ts[nu];
@@ -1339,10 +1340,8 @@ int vv_istft_head(vv_ctx* c, int B, int T_max, const float* head, int ld_head, c
     if ((size_t)B * T_max * c->vcfg.n_fft * 4 >= ((size_t)1 << 31)) return c->fail(-22, "vv_istft_head: a plane of 2 GiB or more");
     hipSetDevice(c->device);
     const size_t R = (size_t)B * T_max;
-    Need nd; nd.add(4 * R * c->vcfg.n_fft); nd.add(4 * R * c->vcfg.n_fft);
-    if (int r = ensure_ws(c, nd.b)) return r;
-    float* spec = carve<float>(c, R * c->vcfg.n_fft);
-    float* frames = carve<float>(c, R * c->vcfg.n_fft);
+    float *spec, *frames;                                // the spectrum operand and the windowed frames, [B * T_max][n_fft] each
+    if (int r = plan_ws(c, nullptr, 0, [&](Arena& a) { spec = a.take<float>(R * c->vcfg.n_fft); frames = a.take<float>(R * c->vcfg.n_fft); })) return r;
     return vocos_istft(c, B, T_max, head, ld_head, n_frames, pcm, ld_pcm, pcm_len, wave_f32, spec, frames, (hipStream_t)stream);
 }
 int vv_ode_stage(vv_ctx* c, const vv_ode_stage_args* a, void* st) {

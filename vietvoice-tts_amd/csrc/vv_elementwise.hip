@@ -464,21 +464,6 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(const float* __restrict_
     *(float4*)(out + r * 64 + q * 4) = *(const float4*)(cs + (size_t)pos[r] * 64 + q * 4);
 }
 
-__global__ __launch_bounds__(256) void silu_kernel(float* __restrict__ x, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const float v = x[i];
-        x[i] = v / (1.0f + expf(-v));
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ in, T* __restrict__ out, size_t n4) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-        const float4 v = *(const float4*)(in + i * 4);
-        store4<T>(out + i * 4, v.x, v.y, v.z, v.w);
-    }
-}
-
 inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 8); }
 
 }  // namespace
@@ -638,18 +623,6 @@ int vvk_rope_rows(const float* cs, const int* pos, float* out, int rows, hipStre
 int vvk_rope_compact(const float* c, const float* s, float* out, int n, hipStream_t st, const char** err) {
     if (n <= 0) { *err = "rope_compact: empty"; return -22; }
     rope_compact_kernel<<<(n * 32 + 255) / 256, 256, 0, st>>>(c, s, out, n);
-    VVK_CHECK_LAUNCH();
-    return 0;
-}
-int vvk_silu(float* x, size_t n, hipStream_t st, const char** err) {
-    silu_kernel<<<grid_for(n), 256, 0, st>>>(x, n);
-    VVK_CHECK_LAUNCH();
-    return 0;
-}
-int vvk_cast(int dtype, const float* in, void* out, size_t n, hipStream_t st, const char** err) {
-    if (n % 4) { *err = "cast: n % 4"; return -22; }
-    if (dtype == VV_BF16) cast_kernel<bf16><<<grid_for(n / 4), 256, 0, st>>>(in, (bf16*)out, n / 4);
-    else cast_kernel<float><<<grid_for(n / 4), 256, 0, st>>>(in, (float*)out, n / 4);
     VVK_CHECK_LAUNCH();
     return 0;
 }

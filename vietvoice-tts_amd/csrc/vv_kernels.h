@@ -1,4 +1,4 @@
-// Internal launcher interface between the kernel translation units and vv_api.cpp.
+// Internal launcher interface between the kernel translation units and vv_api.hip.
 // Every launcher validates operand shapes on the host BEFORE launching (a faulting kernel can
 // reset the whole box) and returns 0 / negative errno with a static message in *err.
 #pragma once
@@ -43,14 +43,12 @@ int vvk_ref_len(const int* audio_len, int* ref_len, int B, int hop, hipStream_t 
 int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, hipStream_t st,
                    const char** err);
 int vvk_row_tables(const int* seq_len, int B, int N, int Rc, int* row_start, int* row_src, int* row_pos, int* kv_len, hipStream_t st, const char** err);
-int vvk_silu(float* x, size_t n, hipStream_t st, const char** err);
 int vvk_resample_poly(const float* x, int n_in, const double* h, int n_taps, int up, int down, int skip, float* y, int n_out,
                       hipStream_t st, const char** err);
 int vvk_ingest_pcm(const void* pcm, const long long* desc, int n_clips, long long max_out, float* out, hipStream_t st, const char** err);
 size_t vvk_normalize_scratch_bytes(int n_clips, long long total_len);
 int vvk_normalize_clips(const float* x, const long long* off, int n_clips, long long max_len, void* scratch, int16_t* out,
                         hipStream_t st, const char** err);
-int vvk_cast(int dtype, const float* in, void* out, size_t n, hipStream_t st, const char** err);
 int vvk_rope_compact(const float* c, const float* s, float* out, int n, hipStream_t st, const char** err);
 int vvk_rope_rows(const float* cs, const int* pos, float* out, int rows, hipStream_t st, const char** err);
 int vvk_groupnorm(const float* x, float* y, const float* gamma, const float* beta, int B, int C, int T, int G, float eps, int act,
