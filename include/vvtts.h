@@ -199,6 +199,20 @@ typedef struct vv_steps_args {
 } vv_steps_args;
 VV_API int vv_transformer_steps_ex(vv_ctx* ctx, const vv_steps_args* args, void* stream);
 
+/* N8 guidance interval: vv_transformer_steps_ex with a guidance MASK.  guide_host is a HOST array
+ * [evaluations of the plan in force][ld_guide] of uint8, ld_guide >= B: row e = step * s + stage (the plan's ABSOLUTE evaluation index, so
+ * calls split by step0 / n_steps read the same table), column b != 0 = item b is guided at evaluation e.  A guided item's slope is
+ * p_c + (p_c - p_u) * g_b as in every other entry; an item that is not guided has the slope p_c and NO unconditional rows at that
+ * evaluation: per lane the conditional rows stay at [0, Rc) and the unconditional rows of the guided items alone are packed behind them,
+ * so an evaluation costs Rc + Ru_e rows instead of 2 Rc (nothing is launched on zero rows).  Every other row's arithmetic is that of the
+ * unmasked call, bit for bit.  guide_host NULL = every item guided everywhere: the call IS vv_transformer_steps_ex.  The mask is read
+ * during the call only (it reaches the device as kernel arguments): with host lengths the call never synchronises and can be captured
+ * into a hipGraph.  A caller-owned ws holds vv_transformer_guided_ws_bytes bytes: vv_transformer_ws_bytes plus the row tables of the
+ * subsets, the same figure whatever the mask.  -22 for ld_guide < B, for more than 1024 items, and for a mask while option
+ * "split_k_tail" is on (its tail plan depends on the row count); a refused call launches nothing and leaves the context usable. */
+VV_API int vv_transformer_steps_guided(vv_ctx* ctx, const vv_steps_args* args, const uint8_t* guide_host, int ld_guide, void* stream);
+VV_API int vv_transformer_guided_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, uint64_t* bytes);
+
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
  * that needs more bytes (vv_ws_generation counts those moves); a launch sequence captured into a hipGraph
@@ -426,6 +440,11 @@ typedef struct vv_ode_stage_args {
     float g; const float* g_item; int32_t seq_n; const int32_t* row_src;
 } vv_ode_stage_args;
 VV_API int vv_ode_stage(vv_ctx* ctx, const vv_ode_stage_args* args, void* stream);
+/* N8: the same stage where only some rows have an unconditional prediction.  u_row [Rc] int32 (device): u_row[r] >= 0 = the ROW OF pred
+ * that holds p_u of packed row r (the guided rows compacted behind the conditional ones: values in [Rc, Rc + Ru)); u_row[r] < 0 = row r
+ * is not guided, k_i = p_c.  u_row[r] = Rc + r for every r is vv_ode_stage bit for bit, and so is u_row NULL.  The caller keeps the
+ * entries inside pred. */
+VV_API int vv_ode_stage_guided(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, void* stream);
 VV_API int vv_cfg_euler(vv_ctx* ctx, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* stream);
 
 /* ---- reference-clip ingest on the device (a8 + SURVEY 8(f) N3).  Together they replace the arithmetic of

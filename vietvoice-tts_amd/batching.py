@@ -33,10 +33,10 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "cfgs", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "cfgs", "ivals", "t0", "n_req")
 
     def __init__(self):
-        self.plans, self.flat, self.blocks, self.cfgs, self.t0, self.n_req = [], [], [], [], time.time(), 0
+        self.plans, self.flat, self.blocks, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], time.time(), 0
 
 
 class BatchingFrontend:
@@ -68,11 +68,18 @@ class BatchingFrontend:
             t.start()
 
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
-               **voice) -> Future:
+               cfg_interval: Optional[Tuple[float, float]] = None, **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
-        (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours."""
+        (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
+        ``cfg_interval``: this request's guidance interval (lo, hi), 0 <= lo <= hi <= 1 (None = the engine's), per item in the same way."""
         fut: Future = Future()
+        try:
+            from .model_spec import check_cfg_interval
+            cfg_interval = check_cfg_interval(cfg_interval)
+        except ValueError as e:
+            fut.set_exception(e)
+            return fut
         if cfg_strength is not None:
             cfg_strength = float(cfg_strength)
             if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
@@ -85,7 +92,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -118,7 +125,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength = req
+        serial, text, speed, voice, fut, cfg_strength, cfg_interval = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -142,6 +149,7 @@ class BatchingFrontend:
         batch.flat.extend(inputs)
         batch.blocks.extend(blocks)
         batch.cfgs.extend([cfg_strength] * len(inputs))
+        batch.ivals.extend([cfg_interval] * len(inputs))
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -248,7 +256,7 @@ class BatchingFrontend:
         t0 = time.perf_counter()
         with eng._lock:
             if eng.model_session_manager.engine is not None:
-                waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs)
+                waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0

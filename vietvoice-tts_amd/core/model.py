@@ -47,9 +47,10 @@ class HipSession:
     """One stage of the HIP engine with onnxruntime.InferenceSession's call shape (batch 1, host
     numpy in and out -- the reference's contract, including its host round trips)."""
 
-    def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None):
+    def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None):
         self.engine, self.kind, self.noise_gen, self.fuse_nfe = engine, kind, noise_gen, max(1, int(fuse_nfe))
         self.cfg_strength = cfg_strength          # None = the model's guidance strength (ModelConfig.cfg_strength)
+        self.cfg_interval = cfg_interval          # None = guidance at every evaluation (ModelConfig.cfg_interval)
         self._in, self._out = SESSION_IO[kind]
 
     def get_inputs(self):
@@ -96,14 +97,15 @@ class HipSession:
             step = int(np.asarray(vals[7]).reshape(-1)[0])
             k = min(self.fuse_nfe, eng.n_steps - step)          # ODE steps, whatever the solver: a step is never split between calls
             cfg = None if self.cfg_strength is None else torch.full((1,), float(self.cfg_strength), dtype=torch.float32, device=dev)
+            guide = eng.guidance_mask(self.cfg_interval, [self.cfg_strength])      # absolute evaluation rows: the split calls read one table
             if same:
-                eng.transformer_steps(x, pre, step, k, cfg=cfg)
+                eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide)
             else:
                 if not getattr(self, "_rope_warned", False):
                     logger.warning("transformer session: non-standard rope tables fed; the tables are read instead of computed")
                     self._rope_warned = True
                 with eng.reading_rope_tables():
-                    eng.transformer_steps(x, pre, step, k, cfg=cfg)
+                    eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide)
             return [x.cpu().numpy(), np.array([step + k], dtype=np.int32)]
         x = torch.from_numpy(np.ascontiguousarray(vals[0], dtype=np.float32)).to(dev)
         n = x.shape[1]
@@ -161,7 +163,8 @@ class ModelSessionManager:
                 from ..runtime import HipSynth
                 self.engine = HipSynth(spec, weights, device=self.config.device, acoustic_dtype=self.config.acoustic_dtype,
                                        nfe_step=self.config.nfe_step, ode_method=self.config.ode_method)
-                made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength) for k in SESSION_IO}
+                made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval)
+                        for k in SESSION_IO}
             for name in ("preprocess", "transformer", "decode"):
                 sess = made[name]
                 self.sessions[name] = sess

@@ -17,7 +17,7 @@ import logging
 import os
 from dataclasses import dataclass, fields
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Tuple
 
 logger = logging.getLogger("vietvoicetts")
 
@@ -64,6 +64,8 @@ class ModelConfig:
     ode_method: str = "euler"               # flow-ODE solver: euler | midpoint | heun2 | heun3 | rk4 (model_spec.ODE_METHODS); nfe_step stays
                                             # the number of grid points, the DiT runs stages x (nfe_step - 1) times
     cfg_strength: Optional[float] = None    # classifier-free guidance strength of every synthesis of this engine; None = the model's
+    cfg_interval: Optional[Tuple[float, float]] = None   # guidance only at the evaluations with lo <= t <= hi (limited-interval guidance);
+                                            # outside it the unconditional branch is not computed.  None = guidance everywhere
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -79,6 +81,8 @@ class ModelConfig:
             self.cfg_strength = float(self.cfg_strength)
             if self.cfg_strength != self.cfg_strength or abs(self.cfg_strength) == float("inf"):
                 raise ValueError("cfg_strength must be a finite number or None")
+        from ..model_spec import check_cfg_interval
+        self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         self.validate_paths()
 
     @property

@@ -146,12 +146,14 @@ class TTSEngine:
         return waves
 
     # ------------------------------------------------------------------ device-resident batched path
-    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None) -> List[np.ndarray]:
+    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None) -> List[np.ndarray]:
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
         clips may differ per item (cross-request batches).  One ragged GPU batch per ``max_batch_chunks`` items.
         noise_blocks: optional pre-drawn (N_i, n_mel) fp32 tensors, one per item (the batching front end draws them from
         per-request generators); default = the manager's seeded stream, in item order, like the session path.
-        cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model)."""
+        cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model).
+        cfg_intervals: optional guidance interval (lo, hi) per item (None entries = ``config.cfg_interval``).  An item is guided at the
+        evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed."""
         import torch
         m = self.model_session_manager
         eng, spec = m.engine, m.spec
@@ -160,6 +162,8 @@ class TTSEngine:
         hop = self.config.hop_length
         g_all = [self.config.cfg_strength] * len(inputs_list) if cfg_strengths is None else \
             [self.config.cfg_strength if v is None else float(v) for v in cfg_strengths]
+        iv_all = [self.config.cfg_interval] * len(inputs_list) if cfg_intervals is None else \
+            [self.config.cfg_interval if v is None else v for v in cfg_intervals]
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
@@ -217,17 +221,18 @@ class TTSEngine:
             cfg = None                                   # per-item guidance strength: only when some item asks for one
             if any(g_all[j] is not None for j in idx):
                 cfg = torch.tensor([float(spec.cfg_strength) if g_all[j] is None else g_all[j] for j in idx], dtype=torch.float32).to(dev)
+            guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx])     # None: every item guided everywhere
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
                 x = noise.to(dev)
-                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg)
+                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide)
                 if self._decode_graphs is None:
                     self._decode_graphs = DecodeGraphCache(eng, self.config.decode_graph_cache_entries, self.config.decode_graph_cache_bytes)
                 pcm, pcm_len = self._decode_graphs.get(B, N, t_gen)(x, pre["ref_signal_len"], pre["seq_len"])
             else:
                 _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
-                                                              audio_len_host=lens_a, cfg=cfg)
+                                                              audio_len_host=lens_a, cfg=cfg, guide=guide)
             pcm, pcm_len = pcm.cpu().numpy(), pcm_len.cpu().numpy()
             for i, j in enumerate(idx):
                 waves[j] = pcm[i, : pcm_len[i]].reshape(1, 1, -1)
@@ -331,7 +336,8 @@ class TTSEngine:
                 _x, pcm, n_out = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
                                                torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
-                                               torch.from_numpy(plan.keep.reshape(1, -1)).to(dev), noise.unsqueeze(0).to(dev), cfg=g_item)
+                                               torch.from_numpy(plan.keep.reshape(1, -1)).to(dev), noise.unsqueeze(0).to(dev), cfg=g_item,
+                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]))
                 wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:
                 raise RuntimeError(f"Speech editing failed: {str(e)}") from e

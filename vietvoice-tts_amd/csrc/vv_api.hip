@@ -615,11 +615,20 @@ struct Lane {
     float *xs = nullptr, *kbuf[3] = {};     // N7 (more than one stage): the stage state and the stored slopes, [Rc][n_mel] fp32 each
     int *kv_len = nullptr, *tab = nullptr;
     const int *row_start = nullptr, *row_src = nullptr, *row_pos = nullptr, *qkv_pos = nullptr;
+    // N8 (a call with a guidance mask): the tables of the evaluation's guided subset, rebuilt when the subset changes (guided_tables_kernel)
+    int *g_row_start = nullptr, *g_rs_rel = nullptr, *g_kv_len = nullptr, *g_row_pos = nullptr, *u_src = nullptr, *u_crow = nullptr, *u_row = nullptr;
+};
+// N8: what the host knows of a lane's guided subset at the evaluation in hand
+struct GuideState {
+    std::vector<uint8_t> flags;        // [B] of the lane; empty = no tables built yet in this call
+    size_t Ru = 0;                     // unconditional rows: the guided items' lengths
+    int Bu = 0;                        // guided items
+    double sum_sq = 0;                 // sum of len^2 over them
 };
 
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N) {
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided) {
     const vv_model_cfg& g = c->cfg;
     const size_t R = L.R, es = c->esz(), D = g.dim, FF = D * g.ff_mult, M = g.n_mel;
     const size_t KP = pad_to(2 * g.n_mel + g.text_dim, 64), MP = pad_to(g.n_mel, 128);
@@ -637,11 +646,21 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N) {
         L.xs = a.take<float>(L.Rc * M);
         for (int k = 0; k < c->ode_nk; ++k) L.kbuf[k] = a.take<float>(L.Rc * M);
     }
+    if (guided) {                                  // N8: row_start[2B] | rs_rel[B] | kv_len[2B] | row_pos[2 Rc] | u_src[Rc] | u_crow[Rc] | u_row[Rc]
+        int* t = a.take<int>(5 * (size_t)L.B + 5 * L.Rc);
+        L.g_row_start = t; L.g_rs_rel = t + 2 * L.B; L.g_kv_len = t + 3 * L.B; L.g_row_pos = t + 5 * L.B;
+        L.u_src = L.g_row_pos + 2 * L.Rc; L.u_crow = L.u_src + L.Rc; L.u_row = L.u_crow + L.Rc;
+    }
 }
 }  // namespace
 
-static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t* ws_only, void* stream) {
+// guide != nullptr (N8, vv_transformer_steps_guided): HOST flags [evaluations of the plan][ld_guide], guided(b, e) at guide[e * ld_guide + b];
+// an item that is not guided at an evaluation has no unconditional rows there.  guided_ws: the workspace of such a call (the tables of
+// the subsets on top of the plain call's bytes), whatever the mask.
+static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t* ws_only, void* stream, const uint8_t* guide = nullptr,
+                                  int ld_guide = 0, bool guided_ws = false) {
     if (!c) return -22;
+    const bool guided = guide != nullptr || guided_ws;
     const int B = args.B, N = args.N, step0 = args.step0, n_steps = args.n_steps;
     const int32_t *seq_len = args.seq_len, *seq_len_host = args.seq_len_host;
     float* x = args.x;
@@ -651,6 +670,9 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
     if (B < 1 || N < 1 || (!ws_only && (!seq_len || !x || !cat || !cat_drop || !rope_cos_q || !rope_sin_q || !rope_cos_k || !rope_sin_k)))
         return c->fail(-22, "vv_transformer_steps: bad arguments");
     if (step0 < 0 || n_steps < 0 || step0 + n_steps > c->n_steps) return c->fail(-22, "vv_transformer_steps: steps [%d,%d) outside the time grid (%d)", step0, step0 + n_steps, c->n_steps);
+    if (guide && ld_guide < B) return c->fail(-22, "vv_transformer_steps_guided: ld_guide = %d < B = %d", ld_guide, B);
+    if (guide && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_guided: a guidance mask cannot be combined with option split_k_tail (its tail plan depends on the row count)");
+    if (guided && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_guided: at most %d items per call", VVK_GUIDE_MAX_ITEMS);
     const vv_model_cfg& g = c->cfg;
     hipSetDevice(c->device);
     hipStream_t st = (hipStream_t)stream;
@@ -696,7 +718,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
                               (c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS));
     Lane lanes[2];
     const int ns = c->ode_s, S = c->n_steps * ns;      // S: rows of the modulation tables (evaluations)
-    const bool rk = ns > 1 || cfg_item != nullptr;       // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
+    const bool rk = ns > 1 || cfg_item != nullptr || guide != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     for (int li = 0; li < n_lanes; ++li) {
         Lane& L = lanes[li];
         L.b0 = cuts[li]; L.B = cuts[li + 1] - cuts[li];
@@ -713,7 +735,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         L.tail_rows = (L.tp_o || L.tp_f) ? L.R - L.tail_row0 : 0;
         L.n_tab = 2 * (size_t)L.B + L.Rc + L.R;          // row_start[2B] | row_src[Rc] | row_pos[R]
     }
-    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N); };
+    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N, guided); };
     if (ws_only) { *ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
     if (int r = plan_ws(c, args.ws, (size_t)args.ws_bytes, bufs)) return r;
     for (int li = 1; li < (branch_lanes ? 2 : n_lanes); ++li)
@@ -740,6 +762,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         KCHK(c, vvk_row_tables(L.seq_len, L.B, N, (int)L.Rc, L.tab, L.tab + 2 * L.B, L.tab + 2 * L.B + L.Rc, L.kv_len, st, &m__));
         KCHK(c, vvk_rope_compact(rope_cos_q, rope_sin_q, L.csq, N, st, &m__));
         KCHK(c, vvk_rope_compact(rope_cos_k, rope_sin_k, L.csk, N, st, &m__));
+        if (guide) return 0;                             // N8: the row-gathered rope tables and the pack follow the evaluation's subset (guide_eval)
         if (c->rope_rows) {
             KCHK(c, vvk_rope_rows(L.csq, L.row_pos, L.csq_rows, (int)L.R, st, &m__));
             KCHK(c, vvk_rope_rows(L.csk, L.row_pos, L.csk_rows, (int)L.R, st, &m__));
@@ -758,6 +781,40 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
             KCHK(c, vvk_pack_cat(c->dt, i ? L.xs : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, i ? nullptr : L.row_src, st, &m__));
         }
         return 0;
+    };
+    // N8: evaluation e of a call with a mask -- the lane's guided subset, its tables when the subset differs from the previous evaluation's
+    // (always at the call's first), and the pack: every column of the rows whose content moved (all rows at the call's first evaluation,
+    // the unconditional rows after a change of subset), else the n_mel state columns alone, as step_pack
+    auto guide_eval = [&](Lane& L, GuideState& G, int i, int e) -> int {
+        hipStream_t st = L.st;
+        const uint8_t* row = guide + (size_t)e * ld_guide + L.b0;
+        std::vector<uint8_t> f(L.B);
+        size_t Ru = 0; int Bu = 0; double sq = 0;
+        for (int b = 0; b < L.B; ++b) {
+            f[b] = row[b] ? 1 : 0;
+            if (f[b]) { Ru += hlen[L.b0 + b]; ++Bu; sq += (double)hlen[L.b0 + b] * hlen[L.b0 + b]; }
+        }
+        const bool first = G.flags.empty(), changed = first || f != G.flags;
+        if (changed) {
+            KCHK(c, vvk_guided_tables(L.seq_len, f.data(), L.B, N, (int)L.Rc, (int)Ru, L.g_row_start, L.g_rs_rel, L.g_kv_len, L.g_row_pos, L.u_src,
+                                      L.u_crow, L.u_row, st, &m__));
+            if (c->rope_rows) {
+                KCHK(c, vvk_rope_rows(L.csq, L.g_row_pos, L.csq_rows, (int)(L.Rc + Ru), st, &m__));
+                KCHK(c, vvk_rope_rows(L.csk, L.g_row_pos, L.csk_rows, (int)(L.Rc + Ru), st, &m__));
+            }
+            G.flags = f; G.Ru = Ru; G.Bu = Bu; G.sum_sq = sq;
+        }
+        const float* xin = i ? L.xs : L.x;
+        const int Rc = (int)L.Rc, R = (int)(L.Rc + Ru);
+        auto pack = [&](int row0, int n_rows, int only_x) -> int {
+            Prof p(c, VV_PROF_ELEMWISE, 0, only_x ? (4.0 + es) * n_rows * M : 4.0 * n_rows * (M + CD) + (double)es * n_rows * KP, st);
+            KCHK(c, vvk_pack_cat_guided(c->dt, xin, L.cat, L.cat_drop, L.xcat, KP, Rc, row0, n_rows, M, CD, only_x, i ? 1 : 0, L.row_src, L.u_src,
+                                        L.u_crow, st, &m__));
+            return 0;
+        };
+        if (first || !changed) return pack(0, R, first ? 0 : 1);
+        if (int r = pack(0, Rc, 1)) return r;
+        return Ru ? pack(Rc, (int)Ru, 0) : 0;
     };
     // (s below: the EVALUATION index step * ns + stage, the row of the modulation tables)
     auto step_head = [&](Lane& L, int s) -> int {
@@ -869,7 +926,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         a.x_out = last ? nullptr : L.xs;
         a.g = g.cfg_strength; a.g_item = cfg_item ? cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
         Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0)), st);
-        KCHK(c, vvk_ode_stage(&a, st, &m__));
+        KCHK(c, vvk_ode_stage(&a, guide ? L.u_row : nullptr, st, &m__));
         return 0;
     };
 
@@ -879,24 +936,49 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
     // lanes).  Branch lanes: the same fork / join once per STEP, between the conditioning pack and the CFG combine.
     Lane views[2];                                        // what the block-level kernels run on
     int n_views = n_lanes;
+    auto branch_view = [&](const Lane& L, int v) {
+        Lane V = L;
+        const size_t r0 = v ? L.Rc : 0;                 // the unconditional branch's rows follow the conditional branch's
+        V.st = v ? c->side_stream[0] : st;
+        V.R = L.Rc; V.n_seq = L.B; V.sum_sq = L.sum_sq / 2;
+        V.xcat += r0 * KP * es; V.h += r0 * D * es; V.h2 += r0 * D * es; V.h3 += r0 * D * es; V.att += r0 * D * es;
+        V.qkv += r0 * 3 * D * es; V.ffm += r0 * FF * es; V.xres += r0 * D; V.pred += r0 * MP;
+        V.csq_rows += r0 * 64; V.csk_rows += r0 * 64;
+        // row_start / kv_len: the conditional branch's entries serve both views (same lengths, rows relative to the view's base);
+        // row_pos: the first Rc entries (a row's position does not depend on its branch)
+        return V;
+    };
     if (branch_lanes) {
-        const Lane& L = lanes[0];
         n_views = 2;
-        for (int v = 0; v < 2; ++v) {
-            Lane& V = views[v];
-            V = L;
-            const size_t r0 = v ? L.Rc : 0;             // the unconditional branch's rows follow the conditional branch's
-            V.st = v ? c->side_stream[0] : st;
-            V.R = L.Rc; V.n_seq = L.B; V.sum_sq = L.sum_sq / 2;
-            V.xcat += r0 * KP * es; V.h += r0 * D * es; V.h2 += r0 * D * es; V.h3 += r0 * D * es; V.att += r0 * D * es;
-            V.qkv += r0 * 3 * D * es; V.ffm += r0 * FF * es; V.xres += r0 * D; V.pred += r0 * MP;
-            V.csq_rows += r0 * 64; V.csk_rows += r0 * 64;
-            // row_start / kv_len: the conditional branch's entries serve both views (same lengths, rows relative to the view's base);
-            // row_pos: the first Rc entries (a row's position does not depend on its branch)
-        }
+        for (int v = 0; v < 2; ++v) views[v] = branch_view(lanes[0], v);
     } else {
         for (int li = 0; li < n_lanes; ++li) views[li] = lanes[li];
     }
+    // N8: the views of one evaluation under a mask -- Rc + Ru rows and B + Bu sequences on the subset's tables.  Branch lanes: the side
+    // stream's view is the Ru compacted rows (sequence starts relative to the unconditional half); there is none when Ru = 0.
+    GuideState gstate[2];
+    auto guided_views = [&]() {
+        if (branch_lanes) {
+            const Lane& L = lanes[0];
+            const GuideState& G = gstate[0];
+            n_views = G.Ru ? 2 : 1;
+            for (int v = 0; v < n_views; ++v) {
+                Lane& V = views[v];
+                V = branch_view(L, v);
+                V.row_start = v ? L.g_rs_rel : L.g_row_start; V.kv_len = v ? L.g_kv_len + L.B : L.g_kv_len;
+                V.qkv_pos = L.uniform ? nullptr : (v ? L.g_row_pos + L.Rc : L.g_row_pos);
+                if (v) { V.R = G.Ru; V.n_seq = G.Bu; V.sum_sq = G.sum_sq; }
+            }
+            return;
+        }
+        for (int li = 0; li < n_lanes; ++li) {
+            Lane& V = views[li];
+            const GuideState& G = gstate[li];
+            V = lanes[li];
+            V.R = V.Rc + G.Ru; V.n_seq = V.B + G.Bu; V.sum_sq = V.sum_sq / 2 + G.sum_sq;
+            V.row_start = V.g_row_start; V.kv_len = V.g_kv_len; V.qkv_pos = V.uniform ? nullptr : V.g_row_pos;
+        }
+    };
     auto fork = [&]() -> int {
         HIPCHK(c, hipEventRecord(c->ev_fork, st));
         HIPCHK(c, hipStreamWaitEvent(c->side_stream[0], c->ev_fork, 0));
@@ -913,9 +995,16 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
     for (int s = step0; s < step0 + n_steps && !rc; ++s)
         for (int i = 0; i < ns && !rc; ++i) {             // the evaluations of one ODE step (one for Euler); branch lanes fork / join around each
             const int e = s * ns + i;
-            for (int li = 0; li < n_lanes && !rc; ++li) rc = step_pack(lanes[li], s, i);
-            if (branch_lanes && !rc) rc = fork();
-            const bool forked = branch_lanes && !rc;
+            if (guide) {
+                for (int li = 0; li < n_lanes && !rc; ++li) rc = guide_eval(lanes[li], gstate[li], i, e);
+                guided_views();
+                c->chip_share = n_views;
+            } else {
+                for (int li = 0; li < n_lanes && !rc; ++li) rc = step_pack(lanes[li], s, i);
+            }
+            const bool want_fork = branch_lanes && n_views == 2;   // N8: an evaluation without unconditional rows neither forks nor joins
+            if (want_fork && !rc) rc = fork();
+            const bool forked = want_fork && !rc;
             for (int v = 0; v < n_views && !rc; ++v) rc = step_head(views[v], e);
             for (int l = 0; l < g.depth && !rc; ++l)
                 for (int v = 0; v < n_views && !rc; ++v) rc = block(views[v], e, l);
@@ -978,6 +1067,23 @@ int vv_transformer_steps_ex(vv_ctx* c, const vv_steps_args* a, void* stream) {
     if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_ex: a workspace block needs the host lengths");
     if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_ex: cfg_item must be a float array");
     return transformer_steps_impl(c, *a, nullptr, stream);
+}
+
+// N8: a guidance mask on top of vv_transformer_steps_ex (include/vvtts.h)
+int vv_transformer_steps_guided(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, void* stream) {
+    if (!guide_host) return vv_transformer_steps_ex(c, a, stream);
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_guided: null arguments");
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_guided: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_guided: cfg_item must be a float array");
+    return transformer_steps_impl(c, *a, nullptr, stream, guide_host, ld_guide, false);
+}
+
+int vv_transformer_guided_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
+    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_guided_ws_bytes: bad arguments");
+    vv_steps_args a{};
+    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
+    return transformer_steps_impl(c, a, bytes, nullptr, nullptr, 0, true);
 }
 
 // --------------------------------------------------------------------------------------- decode
@@ -1346,7 +1452,12 @@ int vv_istft_head(vv_ctx* c, int B, int T_max, const float* head, int ld_head, c
 }
 int vv_ode_stage(vv_ctx* c, const vv_ode_stage_args* a, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage: null arguments") : -22;
-    SINGLE(c, vvk_ode_stage(a, (hipStream_t)st, &m__));
+    SINGLE(c, vvk_ode_stage(a, nullptr, (hipStream_t)st, &m__));
+}
+int vv_ode_stage_guided(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_guided: null arguments") : -22;
+    if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_guided: u_row must be an int32 array");
+    SINGLE(c, vvk_ode_stage(a, u_row, (hipStream_t)st, &m__));
 }
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));

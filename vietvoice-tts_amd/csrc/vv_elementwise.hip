@@ -161,6 +161,30 @@ __global__ __launch_bounds__(256) void pack_cat_kernel(const float* __restrict__
     }
 }
 
+// N8: the same pack for a guided SUBSET, rows [row0, row0 + n_rows) of the packed buffer.  Conditional rows [0, Rc) read cat through
+// row_src; unconditional row Rc + u exists only for a guided item and gathers cat_drop through u_src[u] (its padded [B][N] row).
+// x_packed: x is the stage state [Rc][n_mel] (packed conditional rows): row r reads x[r], unconditional row u reads x[u_crow[u]].
+template <typename T>
+__global__ __launch_bounds__(256) void pack_cat_guided_kernel(const float* __restrict__ x, const float* __restrict__ cat,
+                                                              const float* __restrict__ cat_drop, T* __restrict__ out, int ldo, int Rc,
+                                                              int row0, int n_rows, int n_mel, int cond_dim, int only_x, int x_packed,
+                                                              const int* __restrict__ row_src, const int* __restrict__ u_src,
+                                                              const int* __restrict__ u_crow) {
+    const int cols4 = (only_x ? n_mel : ldo) >> 2;
+    const size_t total = (size_t)n_rows * cols4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int c = (int)(i % cols4) * 4;
+        const size_t row = (size_t)row0 + i / cols4;
+        const bool unc = row >= (size_t)Rc;
+        const size_t bt = unc ? (size_t)u_src[row - Rc] : (size_t)row_src[row];
+        float4 v;
+        if (c < n_mel) v = *(const float4*)(x + (x_packed ? (unc ? (size_t)u_crow[row - Rc] : row) : bt) * n_mel + c);
+        else if (c < n_mel + cond_dim) v = *(const float4*)((unc ? cat_drop : cat) + bt * cond_dim + (c - n_mel));
+        else v = make_float4(0.f, 0.f, 0.f, 0.f);
+        store4<T>(out + row * ldo + c, v.x, v.y, v.z, v.w);
+    }
+}
+
 // ---------------------------------------------------------------- K9: x += dt * (pc + cfg (pc - pu))
 __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, const float* __restrict__ pred, int ldp,
                                                         int BN, int n_mel, float cfg, float dt, const int* __restrict__ row_src) {
@@ -186,24 +210,32 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, c
 // k_out when a later stage or the final sum reads it; then acc = x + sum_j c_j k_j over the earlier slopes (j ascending, k_prev[j]
 // NULL = zero coefficient, skipped) and the fresh one (c_new, skipped when 0).  x_out != NULL: acc is the next stage's state (packed
 // rows); x_out == NULL (last stage): x is updated in place through row_src.  The coefficients arrive multiplied by h.
+// GUIDED (N8): the unconditional row of packed row r is pred row u_row[r] (an absolute row of pred, inside [BN, BN + Ru)); u_row[r] < 0:
+// the item is not guided at this evaluation, it has no unconditional row and k_i = pc.  One body, so a mapped row runs the very
+// arithmetic of the plain kernel.
 struct OdeStagePrev { const float* k[3]; float c[3]; };
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
                                                         const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
-                                                        OdeStagePrev pv, float c_new, float* __restrict__ k_out, float* __restrict__ x_out) {
+                                                        OdeStagePrev pv, float c_new, float* __restrict__ k_out, float* __restrict__ x_out,
+                                                        const int* __restrict__ u_row) {
     const int c4 = n_mel >> 2;
     const size_t total = (size_t)BN * c4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int c = (int)(i % c4) * 4;
         const size_t row = i / c4;
         const float4 pc = *(const float4*)(pred + row * ldp + c);
-        const float4 pu = *(const float4*)(pred + (row + BN) * ldp + c);
         const size_t xr = row_src ? (size_t)row_src[row] : row;
         const float cfg = g_item ? g_item[xr / (size_t)seq_n] : g;
-        float4 k;
-        k.x = pc.x + (pc.x - pu.x) * cfg;
-        k.y = pc.y + (pc.y - pu.y) * cfg;
-        k.z = pc.z + (pc.z - pu.z) * cfg;
-        k.w = pc.w + (pc.w - pu.w) * cfg;
+        const int ur = GUIDED ? u_row[row] : 0;
+        float4 k = pc;
+        if (!GUIDED || ur >= 0) {
+            const float4 pu = *(const float4*)(pred + (GUIDED ? (size_t)ur : row + BN) * ldp + c);
+            k.x = pc.x + (pc.x - pu.x) * cfg;
+            k.y = pc.y + (pc.y - pu.y) * cfg;
+            k.z = pc.z + (pc.z - pu.z) * cfg;
+            k.w = pc.w + (pc.w - pu.w) * cfg;
+        }
         if (k_out) *(float4*)(k_out + row * n_mel + c) = k;
         float4 xv = *(const float4*)(x + xr * n_mel + c);
 #pragma unroll
@@ -394,6 +426,58 @@ __global__ __launch_bounds__(256) void row_tables_kernel(const int* __restrict__
         }
 }
 
+// N8: the tables of one evaluation whose unconditional half covers only the GUIDED items (bit b of `flags`), one workgroup per item.
+// Conditional entries are row_tables_kernel's; the unconditional rows of the guided items are compacted to [Rc, Rc + Ru) in item order
+// and their sequences to entries [B, B + Bu):
+//   row_start[B + j] = Rc + u0, rs_rel[j] = u0 (the same, relative to the unconditional half), kv_len[B + j], row_pos[Rc + u],
+//   u_src[Ru]: unconditional row -> padded [B][N] row, u_crow[Ru]: -> its conditional packed row,
+//   u_row[Rc]: conditional packed row -> its unconditional packed row Rc + u, or -1.
+// Rc and Ru come from the HOST lengths and flags; the device lengths are clamped as in row_tables_kernel and once more to the Ru rows
+// that exist, so device lengths that disagree with the host's never index past a table: a guided item past the Ru-th row gets a shorter
+// or empty unconditional sequence (its remaining rows are unguided, u_row -1), and rows of either half that nobody owns map onto the
+// padding rows of the last item.
+struct GuideFlags { unsigned w[32]; };
+__global__ __launch_bounds__(256) void guided_tables_kernel(const int* __restrict__ seq_len, GuideFlags flags, int B, int N, int Rc, int Ru,
+                                                            int* __restrict__ row_start, int* __restrict__ rs_rel, int* __restrict__ kv_len,
+                                                            int* __restrict__ row_pos, int* __restrict__ u_src, int* __restrict__ u_crow,
+                                                            int* __restrict__ u_row) {
+    const int b = blockIdx.x;
+    int r0 = 0, u0 = 0, j = 0;
+    for (int i = 0; i < b; ++i) {
+        const int li = min(min(max(seq_len[i], 0), N), Rc - r0);
+        r0 += li;
+        if ((flags.w[i >> 5] >> (i & 31)) & 1u) { u0 += min(li, Ru - u0); ++j; }
+    }
+    const int len = min(min(max(seq_len[b], 0), N), Rc - r0);
+    const bool guided = (flags.w[b >> 5] >> (b & 31)) & 1u;
+    const int ulen = guided ? min(len, Ru - u0) : 0;
+    if (threadIdx.x == 0) {
+        row_start[b] = r0; kv_len[b] = len;
+        if (guided) { row_start[B + j] = Rc + u0; rs_rel[j] = u0; kv_len[B + j] = ulen; }
+    }
+    for (int t = threadIdx.x; t < len; t += 256) {
+        row_pos[r0 + t] = t;
+        u_row[r0 + t] = t < ulen ? Rc + u0 + t : -1;
+    }
+    for (int t = threadIdx.x; t < ulen; t += 256) {
+        row_pos[Rc + u0 + t] = t;
+        u_src[u0 + t] = b * N + t;
+        u_crow[u0 + t] = r0 + t;
+    }
+    if (b == B - 1) {
+        for (int t = r0 + len + (int)threadIdx.x; t < Rc; t += 256) {
+            row_pos[t] = min(len + (t - (r0 + len)), N - 1);
+            u_row[t] = -1;
+        }
+        for (int t = u0 + ulen + (int)threadIdx.x; t < Ru; t += 256) {
+            const int p = min(len + (t - (u0 + ulen)), N - 1);
+            row_pos[Rc + t] = p;
+            u_src[t] = b * N + p;
+            u_crow[t] = Rc - 1;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- K5: GroupNorm over channel-major slabs [B][C][T]
 // One workgroup per (group, batch item) slab of (C / G) x T contiguous floats.  Two passes, 2 reads + 1 write per element:
 // (1) sum and sum of squares of (x - p), p = the slab's first element (a shifted one-pass variance: no cancellation for data with
@@ -518,7 +602,7 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
     return 0;
 }
 
-int vvk_ode_stage(const vv_ode_stage_args* a, hipStream_t st, const char** err) {
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, hipStream_t st, const char** err) {
     if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
     if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
     if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
@@ -534,8 +618,40 @@ int vvk_ode_stage(const vv_ode_stage_args* a, hipStream_t st, const char** err) 
     }
     if (al % 16) { *err = "ode_stage: buffers must be 16-byte aligned"; return -22; }
     if (a->x_out && (a->x_out == a->x || a->x_out == a->k_out)) { *err = "ode_stage: x_out must be a buffer of its own"; return -22; }
-    ode_stage_kernel<<<grid_for((size_t)a->Rc * a->n_mel / 4), 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src,
-                                                                             pv, a->coef[a->n_prev], a->k_out, a->x_out);
+    const int grid = grid_for((size_t)a->Rc * a->n_mel / 4);
+    if (u_row)
+        ode_stage_kernel<true><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
+                                                     a->coef[a->n_prev], a->k_out, a->x_out, u_row);
+    else
+        ode_stage_kernel<false><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
+                                                      a->coef[a->n_prev], a->k_out, a->x_out, nullptr);
+    VVK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vvk_pack_cat_guided(int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int Rc, int row0, int n_rows,
+                        int n_mel, int cond_dim, int only_x, int x_packed, const int* row_src, const int* u_src, const int* u_crow,
+                        hipStream_t st, const char** err) {
+    if (n_mel % 4 || cond_dim % 4 || ldo % 4 || ldo < n_mel + cond_dim) { *err = "pack_cat_guided: bad widths"; return -22; }
+    if (Rc < 1 || row0 < 0 || n_rows < 1 || !row_src || !u_src || !u_crow) { *err = "pack_cat_guided: rows and their three tables"; return -22; }
+    const size_t total = (size_t)n_rows * ((only_x ? n_mel : ldo) / 4);
+    if (dtype == VV_BF16)
+        pack_cat_guided_kernel<bf16><<<grid_for(total), 256, 0, st>>>(x, cat, cat_drop, (bf16*)out, ldo, Rc, row0, n_rows, n_mel, cond_dim, only_x,
+                                                                      x_packed, row_src, u_src, u_crow);
+    else
+        pack_cat_guided_kernel<float><<<grid_for(total), 256, 0, st>>>(x, cat, cat_drop, (float*)out, ldo, Rc, row0, n_rows, n_mel, cond_dim, only_x,
+                                                                       x_packed, row_src, u_src, u_crow);
+    VVK_CHECK_LAUNCH();
+    return 0;
+}
+
+int vvk_guided_tables(const int* seq_len, const unsigned char* flags, int B, int N, int Rc, int Ru, int* row_start, int* rs_rel, int* kv_len,
+                      int* row_pos, int* u_src, int* u_crow, int* u_row, hipStream_t st, const char** err) {
+    if (B < 1 || B > VVK_GUIDE_MAX_ITEMS || N < 1 || Rc < 1 || Ru < 0 || Ru > Rc || !flags) { *err = "guided_tables: 1..1024 items, 0 <= Ru <= Rc"; return -22; }
+    GuideFlags f{};
+    for (int b = 0; b < B; ++b)
+        if (flags[b]) f.w[b >> 5] |= 1u << (b & 31);
+    guided_tables_kernel<<<B, 256, 0, st>>>(seq_len, f, B, N, Rc, Ru, row_start, rs_rel, kv_len, row_pos, u_src, u_crow, u_row);
     VVK_CHECK_LAUNCH();
     return 0;
 }

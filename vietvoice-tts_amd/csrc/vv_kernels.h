@@ -29,7 +29,15 @@ int vvk_pack_cat(int dtype, const float* x, const float* cat, const float* cat_d
                  int cond_dim, int only_x, const int* row_src, hipStream_t st, const char** err);
 int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, const int* row_src, hipStream_t st,
                   const char** err);
-int vvk_ode_stage(const vv_ode_stage_args* a, hipStream_t st, const char** err);
+// u_row (N8, optional [Rc] device): conditional packed row -> the row of pred that holds its unconditional prediction, -1 = none (k = pc)
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, hipStream_t st, const char** err);
+// N8 guidance subsets: flags [B] on the HOST (they travel as kernel arguments), at most VVK_GUIDE_MAX_ITEMS items per launch
+#define VVK_GUIDE_MAX_ITEMS 1024
+int vvk_guided_tables(const int* seq_len, const unsigned char* flags, int B, int N, int Rc, int Ru, int* row_start, int* rs_rel, int* kv_len,
+                      int* row_pos, int* u_src, int* u_crow, int* u_row, hipStream_t st, const char** err);
+int vvk_pack_cat_guided(int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int Rc, int row0, int n_rows,
+                        int n_mel, int cond_dim, int only_x, int x_packed, const int* row_src, const int* u_src, const int* u_crow,
+                        hipStream_t st, const char** err);
 int vvk_text_embed(const int* ids, int ld_ids, const int* text_len, const float* emb, const float* pos, float* out, int B, int N,
                    int Dt, int vocab_rows, hipStream_t st, const char** err);
 int vvk_dwconv(const float* in, float* out, const float* w, const float* bias, const int* seq_len, int B, int n_seq, int N, int C,

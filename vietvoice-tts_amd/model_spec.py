@@ -16,9 +16,10 @@ from __future__ import annotations
 
 import json
 import math
+import numbers
 from dataclasses import asdict, dataclass, field
 from fractions import Fraction
-from typing import Dict, NamedTuple, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -224,6 +225,40 @@ def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
     if s > 1:
         te = te.clamp(0.0, 1.0)
     return OdePlan(te.reshape(-1).to(torch.float32), dt.to(torch.float32), a, b, s)
+
+
+def check_cfg_interval(interval) -> Optional[Tuple[float, float]]:
+    """A guidance interval (lo, hi) as two floats with 0 <= lo <= hi <= 1, or None (guidance everywhere); ValueError otherwise."""
+    if interval is None:
+        return None
+    try:
+        lo, hi = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError("cfg_interval must be None or a pair (lo, hi)") from None
+    if not (math.isfinite(lo) and math.isfinite(hi) and 0.0 <= lo <= hi <= 1.0):
+        raise ValueError("cfg_interval must satisfy 0 <= lo <= hi <= 1 (finite)")
+    return lo, hi
+
+
+def guidance_mask(plan: OdePlan, interval, strengths) -> Optional[torch.Tensor]:
+    """N8 limited-interval guidance (Kynkaanniemi et al. 2024): uint8 [n_evals][B], row e = step * s + stage as in ``plan.t``,
+    guided(b, e) = (interval is None or lo <= float(plan.t[e]) <= hi) and strengths[b] != 0 -- both edges inclusive, the fp32 time
+    of the plan compared as a double.  ``interval``: None or one (lo, hi) for every item, or a sequence of B of them, one per item.
+    Returns None when every item is guided at every evaluation (the unmasked call)."""
+    g = [float(v) for v in strengths]
+    B = len(g)
+    one = interval is None or (len(interval) == 2 and all(isinstance(v, numbers.Real) for v in interval))
+    ivals = [check_cfg_interval(interval)] * B if one else [check_cfg_interval(v) for v in interval]
+    if len(ivals) != B:
+        raise ValueError("guidance_mask: one interval per item")
+    t = [float(v) for v in plan.t]
+    mask = torch.zeros((len(t), B), dtype=torch.uint8)
+    for b in range(B):
+        if g[b] == 0.0:
+            continue
+        for e, te in enumerate(t):
+            mask[e, b] = 1 if ivals[b] is None or ivals[b][0] <= te <= ivals[b][1] else 0
+    return None if bool(mask.all()) else mask
 
 
 def mel_filterbank(spec: ModelSpec) -> torch.Tensor:

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ODE_MAX_EVALS, ModelSpec, ode_plan
+from .model_spec import ODE_MAX_EVALS, ModelSpec, guidance_mask, ode_plan
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VVTTS_LIB") or os.path.join(_HERE, "libvvtts_hip.so")   # VVTTS_LIB: A/B builds in tools/
@@ -121,6 +121,9 @@ EXPORTS = {
     "vv_set_ode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_transformer_steps_ex": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p]),
     "vv_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p]),
+    "vv_transformer_steps_guided": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_transformer_guided_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vv_ode_stage_guided": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.c_void_p]),
     "vv_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_preprocess_h": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -328,6 +331,7 @@ class HipSynth:
             self.ode_method = ode_method
             self.n_steps = n_steps
             self.n_evals = n_steps * plan.s
+            self.plan = plan             # the evaluation times a guidance interval is compared with (guidance_mask)
             self.grid_generation += 1    # vv_set_ode_plan frees and reallocates the tables a captured step graph points into
 
     # ------------------------------------------------------------------ stages
@@ -368,19 +372,26 @@ class HipSynth:
         es = 2 if self.dt_torch == torch.bfloat16 else 4
         return ((1 << 31) - 1) // (2 * 3 * self.spec.dim * es)
 
+    def guidance_mask(self, interval, strengths) -> Optional[torch.Tensor]:
+        """model_spec.guidance_mask on the plan in force: the ``guide`` of transformer_steps for a guidance interval (one for every item
+        or one per item) and the B strengths (a None strength = the model's); None = every item guided everywhere."""
+        return guidance_mask(self.plan, interval, [self.spec.cfg_strength if v is None else v for v in strengths])
+
     def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None,
-                          cfg: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x fp32 [B,N,n_mel] updated in place on the device.  seq_len_host (optional list / array of the B lengths, the same
         values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
-        cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's."""
+        cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's.
+        guide (optional uint8 [n_evals, B] on the HOST, N8): guided(b, e) of every evaluation of the plan in force
+        (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere."""
         B, N, M = x.shape
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
         if seq_len_host is None:
             seq_len_host = pre.get("seq_len_host")
-        if cfg is not None:
-            assert cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,), "cfg: fp32 [B] on the device"
+        if cfg is not None or guide is not None:
+            assert cfg is None or (cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,)), "cfg: fp32 [B] on the device"
             host = None if seq_len_host is None else (C.c_int32 * B)(*[int(v) for v in seq_len_host])
-            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg)
+            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide)
             return x
         with self._lock, torch.cuda.device(self.device):
             tail = (pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr(), pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr(),
@@ -393,10 +404,25 @@ class HipSynth:
                 self._check(self.lib.vv_transformer_steps(self.ctx, B, N, pre["seq_len"].data_ptr(), x.data_ptr(), *tail))
         return x
 
+    def guided_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
+        """Bytes of a caller-owned workspace for a call with a guidance mask (vv_transformer_guided_ws_bytes; the same for every mask)."""
+        host = (C.c_int32 * B)(*[int(v) for v in seq_len_host])
+        nb = C.c_uint64()
+        with self._lock:
+            self._check(self.lib.vv_transformer_guided_ws_bytes(self.ctx, int(B), int(N), host, C.byref(nb)))
+        return int(nb.value)
+
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
-                             cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> None:
+                             cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                             guide: Optional[torch.Tensor] = None) -> None:
         """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
-        the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host)."""
+        the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host).  guide: a contiguous uint8
+        HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
+        ld_guide >= B)."""
+        if guide is not None:
+            if not (isinstance(guide, torch.Tensor) and guide.device.type == "cpu" and guide.dtype == torch.uint8 and guide.dim() == 2
+                    and guide.is_contiguous() and guide.shape[0] == self.n_evals):
+                raise ValueError(f"guide must be a contiguous uint8 host tensor [{self.n_evals} evaluations, >= B]")
         B, N, _ = x.shape
         a = vv_steps_args()
         a.B, a.N, a.seq_len, a.x = B, N, pre["seq_len"].data_ptr(), x.data_ptr()
@@ -409,7 +435,10 @@ class HipSynth:
             a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
         a.cfg_item = _ptr(cfg)
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_transformer_steps_ex(self.ctx, C.byref(a), self._stream()))
+            if guide is not None:
+                self._check(self.lib.vv_transformer_steps_guided(self.ctx, C.byref(a), guide.data_ptr(), int(guide.shape[1]), self._stream()))
+            else:
+                self._check(self.lib.vv_transformer_steps_ex(self.ctx, C.byref(a), self._stream()))
 
     def decode(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], t_gen_max: int, want_wave: bool = False):
         B, N, _ = x.shape
@@ -445,15 +474,16 @@ class HipSynth:
 
     def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: torch.Tensor, t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
-                         audio_len_host=None, cfg: Optional[torch.Tensor] = None):
+                         audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
         gen_frames (host list, optional): per-item generated frames; lets the vocoder run in length buckets on ragged batches.
         seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
-        cfg (optional fp32 [B] on the device): per-item guidance strength."""
+        cfg (optional fp32 [B] on the device): per-item guidance strength.  guide (optional uint8 [n_evals, B] on the host): the
+        guidance mask of transformer_steps."""
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
         x = noise.clone()
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
             if pcm.shape[1] < t_gen_max * self.spec.hop_length:
@@ -521,7 +551,8 @@ class HipSynth:
         return x
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
-                   noise: torch.Tensor, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None):
+                   noise: torch.Tensor, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
+                   guide: Optional[torch.Tensor] = None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
@@ -540,7 +571,7 @@ class HipSynth:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
         x = noise.clone()
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
