@@ -362,16 +362,19 @@ typedef struct vv_posconv_args {
     const void* W;            /* bf16: [G][KW][64 co][64 ci]   f32: [G][KW][64 ci][64 co] */
     const float* bias;
     void* out; int32_t ld_out;
-    const void* resid; int32_t ld_resid;   /* optional, operand dtype */
+    const void* resid; int32_t ld_resid;   /* optional, operand dtype; ld_resid >= groups * 64 */
     int32_t n_seq, seq_n, groups, KW, B;
-    const int32_t* seq_len;
+    const int32_t* seq_len;    /* optional [B], indexed seq % B (conditional and unconditional lanes share it): B >= 1 when given */
     const int32_t* row_start;  /* optional [n_seq]: packed ragged rows, as in vv_attn_args */
 } vv_posconv_args;
+/* Refused with -22 (nothing is launched): seq_len with B <= 0; resid with ld_resid < groups * 64; and, on the bf16 kernel, whose epilogue
+ * moves 4 channels at a time: ld_out or ld_resid not a multiple of 4 elements, out not 8-byte (bf16 out) / 16-byte (f32 out) aligned,
+ * resid not 8-byte aligned, bias not 16-byte aligned.  The f32 kernel's epilogue is scalar and has no such precondition. */
 VV_API int vv_posconv(vv_ctx* ctx, const vv_posconv_args* args, void* stream);
 
 typedef struct vv_conv_args {
     const float* in;          /* [B][Cin][T_in]  */
-    const float* W;           /* [Cin_pad8][KW][rows_pad64], rows = co (conv) or co*up + phase (transposed) */
+    const float* W;           /* [Cin_pad8][KW][rows_pad64], rows = co (conv) or co*up + phase (transposed); nothing past Cin_pad8 is read */
     const float* bias;        /* [Cout] */
     float* out;               /* [B][Cout][T_out] */
     const float* resid;       /* optional, like out */

@@ -355,3 +355,565 @@ def attn_case_refs(case, dtype, which):
         return refs, None
     model = attention_model_bf16(flat, **shp, **kw)
     return refs, attention_errs(model, refs, **shp)[0]
+
+
+# ------------------------------------------------------------------------------------ convolutions: wrappers, float64 references, metric
+import torch.nn.functional as F  # noqa: E402
+
+NAN = float("nan")
+CONV_FILL = 7.0                         # what guard bands, padding columns and sentinel rows hold before a launch
+CONV_GUARD = 64                         # guard elements in front of and behind a conv output (a multiple of 4: out stays 16-byte aligned)
+EPS24 = 2.0 ** -24
+X3_DROPPED = 2.0 ** -23                 # m.l + l.m + l.l of the six-product form (top of vv_vocoder_x3.hip), per term, so per A_e
+# Round-to-nearest store of a bf16 output.  bf16 keeps 8 significant bits: the spacing in [2^e, 2^(e+1)) is 2^(e-7), half of it is
+# 2^(e-8) -- 2^-9 of the binade's TOP but up to 2^-8 of an element at its bottom (1.004 stores as 1.0078: off by 2^-8 x 1.004).  The term
+# per element is therefore 2^-8 |ref_e|; 2^-9 |ref_e| is what a float64 value rounded to bf16 already exceeds (the tests print both the
+# device's figure and that store-only model under the 2^-9 term: profiles/conv_parity/notes.md).
+BF16_STORE = 2.0 ** -8
+BF16_STORE_HALF = 2.0 ** -9
+
+
+def pack_conv(w):         # torch [Cout][Cin][KW] -> [Cin_pad8][KW][Cout_pad64]
+    cout, cin, kw = w.shape
+    t = torch.zeros(((cin + 7) // 8 * 8, kw, (cout + 63) // 64 * 64))
+    t[:cin, :, :cout] = w.permute(1, 2, 0)
+    return t
+
+
+def conv_transpose_pack(w, up):
+    """torch ConvTranspose1d weight [Cin][Cout][2 up] -> the polyphase slab [Cin_pad8][2][rows_pad64]: row = co * up + phase, tap j of
+    that row = w[ci][co][phase + j up]  (out time q up + phase - up / 2 reads in[q - j])."""
+    cin, cout, k = w.shape
+    assert k == 2 * up
+    rows = cout * up
+    t = torch.zeros(((cin + 7) // 8 * 8, 2, (rows + 63) // 64 * 64))
+    t[:cin, :, :rows] = w.reshape(cin, cout, 2, up).permute(0, 2, 1, 3).reshape(cin, 2, rows)
+    return t
+
+
+def split_conv_weights(eng, dw):
+    """vv_conv_split_weights on a packed fp32 slab [Cin_pad][KW][rows_pad] (device) -> the x3 slab (device uint16 tensor)."""
+    cin_pad, kw, rows_pad = dw.shape
+    nbytes = int(eng.lib.vv_conv_split_bytes(cin_pad, kw, rows_pad))
+    assert nbytes == (cin_pad + 15) // 16 * kw * 3 * rows_pad * 16 * 2
+    wb = torch.zeros(nbytes // 2, dtype=torch.int16, device=DEV)
+    check(eng, eng.lib.vv_conv_split_weights(eng.ctx, dw.data_ptr(), cin_pad, kw, rows_pad, wb.data_ptr(), stream()))
+    torch.cuda.synchronize()
+    return wb
+
+
+def _guarded(shape, guard, fill, init=None, dtype=torch.float32):
+    """-> (whole flat buffer, view of `shape` that starts `guard` elements in).  The view holds init (or zeros), the bands hold fill."""
+    n = int(math.prod(shape))
+    buf = torch.full((n + 2 * guard,), fill, dtype=dtype, device=DEV)
+    view = buf[guard:guard + n].view(*shape)
+    if init is None:
+        view.zero_()
+    else:
+        view.copy_(init.to(DEV))
+    return buf, view
+
+
+def _bands_intact(buf, guard, fill, what):
+    if guard:
+        assert bool((buf[:guard] == fill).all()), f"{what}: the guard band in front of out was written"
+        assert bool((buf[-guard:] == fill).all()), f"{what}: the guard band behind out was written"
+
+
+def _offset_input(x, in_offset, in_tail):
+    """x on the device, in_offset elements into an allocation whose head and tail (in_tail elements) hold NaN -> (keep-alive, pointer)."""
+    if not in_offset and not in_tail:
+        dx = x.to(DEV).contiguous()
+        return dx, dx.data_ptr()
+    flat = torch.full((in_offset + x.numel() + in_tail,), NAN, dtype=x.dtype, device=DEV)
+    flat[in_offset:in_offset + x.numel()] = x.reshape(-1).to(DEV)
+    return flat, flat.data_ptr() + in_offset * x.element_size()
+
+
+def conv1d(eng, x, wp, bias, cout, T_out, KW, dil, up, resid=None, pre_slope=1.0, scale=1.0, accumulate=0, out0=None, lens=None, x3=False,
+           guard=0, fill=CONV_FILL, in_offset=0, in_tail=0, expect_error=False):
+    """vv_conv1d on x [B][Cin][T_in] (CPU) with the packed slab wp.  up = 0: conv; up >= 2: polyphase ConvTranspose.  x3: False = the f32
+    MFMA kernel; True = x3 with wg_rows 0; an int = x3 with that wg_rows (128: 8-wave workgroups, -1: never the streaming up-sampler).
+    guard: fp32 elements of `fill` in front of and behind out, checked after the launch.  in_offset / in_tail: the input pointer stands
+    that many elements into a larger allocation whose head / tail hold NaN.  Returns out [B][cout][T_out] (device)."""
+    B, cin, T_in = x.shape
+    assert guard % 4 == 0
+    buf, out = _guarded((B, cout, T_out), guard, fill, out0)
+    keep, in_ptr = _offset_input(x, in_offset, in_tail)
+    db = bias.to(DEV)
+    if guard:                           # eight more channels of NaN behind the slab: a chunk that runs past Cin_pad8 would show
+        wflat = torch.full((wp.numel() + 8 * wp.shape[1] * wp.shape[2],), NAN, device=DEV)
+        dw = wflat[:wp.numel()].view(wp.shape)
+        dw.copy_(wp.to(DEV))
+    else:
+        dw = wp.to(DEV)
+    dr = resid.to(DEV) if resid is not None else None
+    dl = torch.tensor(lens, dtype=torch.int32, device=DEV) if lens is not None else None
+    a = rt.vv_conv_args()
+    a.in_, a.W, a.bias, a.out = in_ptr, dw.data_ptr(), db.data_ptr(), out.data_ptr()
+    a.resid = dr.data_ptr() if dr is not None else None
+    a.B, a.Cin, a.Cout, a.T_in, a.T_out, a.KW, a.dil = B, cin, cout, T_in, T_out, KW, dil
+    a.transposed, a.up = (1 if up else 0), up
+    a.rows_total = cout * up if up else cout
+    a.rows_pad = (a.rows_total + 63) // 64 * 64
+    a.accumulate, a.pre_slope, a.out_scale = accumulate, pre_slope, scale
+    a.len_in = dl.data_ptr() if dl is not None else None
+    if x3:
+        wb = split_conv_weights(eng, dw)
+        a.W_x3 = wb.data_ptr()
+        a.wg_rows = x3 if (isinstance(x3, int) and not isinstance(x3, bool)) else 0
+    rc = eng.lib.vv_conv1d(eng.ctx, C.byref(a), stream())
+    torch.cuda.synchronize()
+    if expect_error:
+        return rc, eng.lib.vv_last_error(eng.ctx)
+    check(eng, rc)
+    _bands_intact(buf, guard, fill, "vv_conv1d")
+    del keep
+    return out
+
+
+def mrf_resblock(eng, y, p1, b1, p2, b2, KW, dil, lens=None, slope=0.1, scale=1.0, accumulate=0, out0=None, guard=0, fill=CONV_FILL,
+                 in_offset=0, in_tail=0, expect_error=False):
+    """vv_mrf_resblock on y [B][C][T] (CPU), packed slabs p1 / p2 [C_pad8][KW][64].  Guard band and input offset as in conv1d."""
+    B, C_, T = y.shape
+    assert guard % 4 == 0
+    buf, out = _guarded((B, C_, T), guard, fill, out0)
+    keep, in_ptr = _offset_input(y, in_offset, in_tail)
+    dev = [t.to(DEV) for t in (p1, b1, p2, b2)]
+    dl = torch.tensor(lens, dtype=torch.int32, device=DEV) if lens is not None else None
+    a = rt.vv_mrf_args()
+    a.y = in_ptr
+    a.W1, a.b1, a.W2, a.b2 = [t.data_ptr() for t in dev]
+    a.out = out.data_ptr()
+    a.B, a.C, a.T, a.KW, a.dil, a.rows_pad, a.accumulate, a.slope, a.out_scale = B, C_, T, KW, dil, 64, accumulate, slope, scale
+    a.len_in = dl.data_ptr() if dl is not None else None
+    rc = eng.lib.vv_mrf_resblock(eng.ctx, C.byref(a), stream())
+    torch.cuda.synchronize()
+    if expect_error:
+        return rc, eng.lib.vv_last_error(eng.ctx)
+    check(eng, rc)
+    _bands_intact(buf, guard, fill, "vv_mrf_resblock")
+    del keep
+    return out
+
+
+def _lrelu(x, slope):
+    """LeakyReLU with the slope the kernel is given: the fp32 value of `slope`."""
+    return torch.where(x >= 0, x, x * float(torch.tensor(slope, dtype=torch.float32)))
+
+
+def _zero_outside(x, lens):
+    """x [B][C][T] with columns outside [0, len_b) set to zero (whatever they held: NaN too)."""
+    if lens is None:
+        return x
+    t = torch.arange(x.shape[-1])
+    keep = t[None, :] < torch.tensor([max(0, min(int(L), x.shape[-1])) for L in lens])[:, None]
+    return torch.where(keep[:, None, :], x, torch.zeros((), dtype=x.dtype))
+
+
+def _conv_taps(a, w, dil):
+    """Plain sum over taps: a [B][Cin][T], w [Cout][Cin][KW] -> [B][Cout][T], 'same' padding dil (KW - 1) / 2 (no library convolution)."""
+    KW, T = w.shape[2], a.shape[2]
+    left = dil * (KW - 1) // 2
+    ap = F.pad(a, (left, dil * (KW - 1) - left))
+    y = torch.zeros(a.shape[0], w.shape[0], T, dtype=a.dtype)
+    for k in range(KW):
+        y += torch.einsum("oc,bct->bot", w[:, :, k], ap[:, :, k * dil:k * dil + T])
+    return y
+
+
+def _conv_transpose_taps(a, w, up):
+    """Plain scatter form of ConvTranspose1d (stride up, kernel 2 up, padding up / 2): a [B][Cin][T], w [Cin][Cout][2 up] -> [B][Cout][T up]."""
+    B, _, T = a.shape
+    full = torch.zeros(B, w.shape[1], (T - 1) * up + 2 * up, dtype=a.dtype)
+    for k in range(2 * up):
+        full[:, :, k:k + (T - 1) * up + 1:up] += torch.einsum("co,bct->bot", w[:, :, k], a)
+    return full[:, :, up // 2:up // 2 + T * up]
+
+
+def conv_ref(x, w, bias, *, dil=1, up=0, lens=None, slope=1.0, resid=None, scale=1.0, prev=None, mode="f64"):
+    """out = (conv(lrelu(x zero-filled outside [0, len))) + bias [+ resid as given]) * scale [+ previous out], every column of the output.
+    x [B][Cin][T]; w in torch layout ([Cout][Cin][KW], or [Cin][Cout][2 up] for the transposed form); all operands as the kernel gets them.
+    mode 'f64': the float64 reference (plain tap sums).  'abs': the per-element scale A_e, the same expression with every operand replaced
+    by its absolute value.  'f32': the yardstick, the CPU library in fp32 on the same operands."""
+    if mode == "f32":
+        a = F.leaky_relu(_zero_outside(x.float(), lens), slope)
+        w32, b32 = w.float(), bias.float()
+        y = F.conv_transpose1d(a, w32, b32, stride=up, padding=up // 2) if up else F.conv1d(a, w32, b32, dilation=dil, padding=dil * (w.shape[2] - 1) // 2)
+        if resid is not None:
+            y = y + resid.float()
+        y = y * torch.tensor(scale, dtype=torch.float32)
+        return y + prev.float() if prev is not None else y
+    pos = (lambda t: t.double().abs()) if mode == "abs" else (lambda t: t.double())
+    a = pos(_lrelu(_zero_outside(x.double(), lens), slope))
+    y = _conv_transpose_taps(a, pos(w), up) if up else _conv_taps(a, pos(w), dil)
+    y = y + pos(bias)[None, :, None]
+    if resid is not None:
+        y = y + pos(resid)
+    y = y * pos(torch.tensor(scale, dtype=torch.float32))       # the kernel multiplies by the fp32 scale it is given
+    return y + pos(prev) if prev is not None else y
+
+
+def mrf_ref(y, w1, b1, w2, b2, *, dil, lens=None, slope=0.1, scale=1.0, prev=None, mode="f64"):
+    """conv1 (dilated) + b1, zeroed outside [0, len), LeakyReLU, conv2 (undilated) + b2 + y AS GIVEN, times scale [+ previous out]."""
+    if mode == "f32":
+        t1 = F.conv1d(F.leaky_relu(_zero_outside(y.float(), lens), slope), w1.float(), b1.float(), dilation=dil, padding=dil * (w1.shape[2] - 1) // 2)
+        o = F.conv1d(F.leaky_relu(_zero_outside(t1, lens), slope), w2.float(), b2.float(), padding=(w2.shape[2] - 1) // 2) + y.float()
+        o = o * torch.tensor(scale, dtype=torch.float32)
+        return o + prev.float() if prev is not None else o
+    pos = (lambda t: t.double().abs()) if mode == "abs" else (lambda t: t.double())
+    t1 = _conv_taps(pos(_lrelu(_zero_outside(y.double(), lens), slope)), pos(w1), dil) + pos(b1)[None, :, None]
+    t1 = pos(_lrelu(_zero_outside(t1, lens), slope))
+    o = _conv_taps(t1, pos(w2), 1) + pos(b2)[None, :, None] + pos(y)
+    o = o * pos(torch.tensor(scale, dtype=torch.float32))
+    return o + pos(prev) if prev is not None else o
+
+
+def parity_err(got, ref, A, allow=None):
+    """max_e (|got_e - ref_e| - allow_e) / A_e and the index of the worst element; a non-finite element counts as infinite.  allow: an
+    absolute per-element allowance that is not part of the accumulation error (the bf16 store rounding)."""
+    d = (got.detach().cpu().double() - ref).abs()
+    if allow is not None:
+        d = (d - allow).clamp_min(0.0)
+    e = d / A
+    e = torch.where(torch.isfinite(e), e, torch.full_like(e, float("inf")))
+    i = int(e.argmax())
+    where = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), e.shape)) if e.dim() > 1 else (i,)
+    return float(e.reshape(-1)[i]), where
+
+
+def conv_bound(yardstick, x3=False):
+    """fp32 forms: max(8 x 2^-24, 4 x yardstick).  Floor: one product rounding plus at most four epilogue roundings (bias, residual,
+    scale, accumulate), each <= 2^-24 A_e, with room for the bias add.  4: the kernel sums one fp32 chain of Cin_pad x KW steps per
+    element, the CPU library sums in vector lanes (the project grants 2 between its own two orders).  x3: + 2^-23, the dropped piece
+    products.  Never fitted to a measurement: profiles/conv_parity/notes.md."""
+    return max(8.0 * EPS24, 4.0 * yardstick) + (X3_DROPPED if x3 else 0.0)
+
+
+# ---- posconv
+def posconv_pack(w, groups, dtype):
+    """torch grouped-conv weight [G 64][64][KW] -> bf16: [G][KW][64 co][64 ci]; f32: [G][KW][64 ci][64 co]."""
+    kw = w.shape[2]
+    w4 = w.reshape(groups, 64, 64, kw)
+    return (w4.permute(0, 3, 1, 2) if dtype == torch.bfloat16 else w4.permute(0, 3, 2, 1)).contiguous()
+
+
+def posconv(eng, x, w, bias, *, n_seq, seq_n, groups, resid=None, lens=None, B=None, starts=None, out_dtype=None, pad_in=0, pad_out=0,
+            pad_resid=0, sentinel_rows=0, fill=CONV_FILL, tweak=None, expect_error=False):
+    """vv_posconv on x [rows][groups 64] (CPU, bf16 or f32: picks the kernel) with the torch-layout weight w [D][64][KW] (same dtype).
+    lens: list of B lengths indexed seq % B (B defaults to len(lens)); starts: packed rows.  The leading dimensions are padded by pad_*
+    elements; padding columns of in / resid hold 1e4 (finite, wrong if read), those of out and the sentinel rows hold `fill`.  tweak(a)
+    may edit the argument struct before the call.  Returns the WHOLE out buffer [rows + sentinel_rows][D + pad_out] (device)."""
+    D, rows, dt = groups * 64, x.shape[0], x.dtype
+    odt = dt if out_dtype is None else out_dtype
+    din = torch.full((rows, D + pad_in), 1.0e4, dtype=dt, device=DEV)
+    din[:, :D] = x.to(DEV)
+    out = torch.full((rows + sentinel_rows, D + pad_out), fill, dtype=odt, device=DEV)
+    dw, db = posconv_pack(w, groups, dt).to(DEV), bias.float().to(DEV)
+    dr = None
+    if resid is not None:
+        dr = torch.full((rows, D + pad_resid), 1.0e4, dtype=dt, device=DEV)
+        dr[:, :D] = resid.to(DEV)
+    sl, rs = _i32(lens), _i32(starts)
+    a = rt.vv_posconv_args()
+    a.dtype = rt.VV_BF16 if dt == torch.bfloat16 else rt.VV_F32
+    a.out_dtype = rt.VV_BF16 if odt == torch.bfloat16 else rt.VV_F32
+    a.in_, a.ld_in, a.W, a.bias, a.out, a.ld_out = din.data_ptr(), D + pad_in, dw.data_ptr(), db.data_ptr(), out.data_ptr(), D + pad_out
+    a.resid, a.ld_resid = (None if dr is None else dr.data_ptr()), D + pad_resid
+    a.n_seq, a.seq_n, a.groups, a.KW = n_seq, seq_n, groups, w.shape[2]
+    a.B = (len(lens) if lens is not None else n_seq) if B is None else B
+    a.seq_len = None if sl is None else sl.data_ptr()
+    a.row_start = None if rs is None else rs.data_ptr()
+    if tweak is not None:
+        tweak(a)
+    rc = eng.lib.vv_posconv(eng.ctx, C.byref(a), stream())
+    torch.cuda.synchronize()
+    if expect_error:
+        return rc, eng.lib.vv_last_error(eng.ctx)
+    check(eng, rc)
+    return out
+
+
+def posconv_rows(n_seq, seq_n, lens=None, starts=None):
+    """-> per sequence (first row, rows the kernel writes, valid length): padded layout every row < seq_n; packed rows [0, len) only."""
+    res = []
+    for s in range(n_seq):
+        L = seq_n if lens is None else max(0, min(int(lens[s % len(lens)]), seq_n))
+        res.append((s * seq_n, seq_n, L) if starts is None else (int(starts[s]), L, L))
+    return res
+
+
+def posconv_ref(x, w, bias, resid, *, n_seq, seq_n, groups, lens=None, starts=None, mode="f64"):
+    """mish(conv(x zero-filled outside [0, len)) + bias) + resid on the operands as given, for every row the kernel writes.  Returns a
+    list over sequences of (first row, ref [rows][D]).  Modes as in conv_ref ('f32': F.conv1d + F.mish in fp32)."""
+    D, KW = groups * 64, w.shape[2]
+    pad = KW // 2
+    res = []
+    for r0, n, L in posconv_rows(n_seq, seq_n, lens, starts):
+        if n == 0:
+            res.append((r0, torch.zeros(0, D, dtype=torch.float32 if mode == "f32" else torch.float64)))
+            continue
+        rz = None if resid is None else resid[r0:r0 + n]
+        if mode == "f32":
+            xs = x[r0:r0 + n].float().clone()
+            xs[L:] = 0
+            o = F.mish(F.conv1d(xs.t().unsqueeze(0), w.float(), bias.float(), padding=pad, groups=groups)).squeeze(0).t()
+            res.append((r0, o + rz.float() if rz is not None else o))
+            continue
+        pos = (lambda t: t.double().abs()) if mode == "abs" else (lambda t: t.double())
+        xs = pos(x[r0:r0 + n]).clone()
+        xs[L:] = 0
+        xp = F.pad(xs, (0, 0, pad, pad)).reshape(n + 2 * pad, groups, 64)
+        wg = pos(w).reshape(groups, 64, 64, KW)
+        z = torch.zeros(n, groups, 64, dtype=torch.float64)
+        for k in range(KW):
+            z += torch.einsum("tgc,goc->tgo", xp[k:k + n], wg[:, :, :, k])
+        o = F.mish(z.reshape(n, D) + pos(bias)[None, :])
+        res.append((r0, o + pos(rz) if rz is not None else o))
+    return res
+
+
+# ---- the conv parity grid (tests/test_conv_gpu.py runs it, tests/test_conv_ref_cpu.py checks the claims made here)
+# forms -> the x3 argument of conv1d.  'stream' is x3 with wg_rows 0 on a shape the streaming up-sampler takes, 'generic' its twin.
+CONV_FORMS = {"f32": False, "x3": True, "x3w": 128, "stream": True, "generic": -1}
+# conv_x3_kernel<KW, TR, RT, TG, NWV, OCC> instantiations and the two up2_stream_x3_kernel widths, by the names used in the claims
+NARROW, R64, K11, WIDE = "<KW,1,2,4,3>", "<KW,2,2,4,3>", "<11,2,4,4,2>", "<KW,2,2,8,2>"
+T_NARROW, T_R64, T_WIDE, STREAM4, STREAM8 = "T<2,1,2,4,3>", "T<2,2,2,4,3>", "T<2,2,2,8,2>", "up2_stream<4>", "up2_stream<8>"
+X3_REQUIRED = (NARROW, R64, K11, WIDE, T_R64, T_WIDE, STREAM4, STREAM8)
+MRF_VT2 = {3: 124, 7: 120, 11: 116}     # output columns per mrf_pair_kernel workgroup: 128 - ((KW - 1 + 3) & ~3)
+
+
+class _Ops:
+    pass
+
+
+class ConvCase:
+    """One problem of the conv grid.  kind 'conv' / 'tconv' (polyphase ConvTranspose, T = T_in) / 'mrf' (cin = cout = C).  variants:
+    'plain' = conv + bias; 'conv2' = the decode's second-conv form (resid, out_scale 1/3, accumulate onto a previous out; mrf: scale 1/3 +
+    accumulate).  reach: form -> the x3 instantiation the case claims to reach; claims: form -> (n_win, n_rt) of the 1-D window walk."""
+
+    def __init__(self, name, section, kind, *, B, cin, cout, T, KW=2, dil=1, up=0, lens=None, variants=("plain",), forms=("f32", "x3", "x3w"),
+                 reach=None, claims=None, in_offset=0, fallback=False):
+        self.name, self.section, self.kind = name, section, kind
+        self.B, self.cin, self.cout, self.T, self.KW, self.dil, self.up = B, cin, cout, T, KW, dil, up
+        self.lens, self.variants, self.forms, self.reach, self.claims = lens, variants, forms, reach or {}, claims or {}
+        self.in_offset, self.fallback = in_offset, fallback
+        self.T_out = T * up if up else T
+        self.rows_total = cout * up if up else cout
+        self.rows_pad = (self.rows_total + 63) // 64 * 64
+        self._ops, self._refs = None, {}
+
+    def forms_of(self, variant):
+        """The streaming kernel takes no residual and no accumulate: in the conv2 variant 'stream' would be the generic kernel again."""
+        return tuple(f for f in self.forms if not (variant == "conv2" and f == "stream"))
+
+    def ops(self):
+        if self._ops is None:
+            g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(self.name)) % 100003)
+            o, B, T = _Ops(), self.B, self.T
+            o.x = torch.randn(B, self.cin, T, generator=g)
+            if self.kind == "mrf":
+                o.w = torch.randn(self.cout, self.cin, self.KW, generator=g) * 1.4 / math.sqrt(self.cin * self.KW)
+                o.w2 = torch.randn(self.cout, self.cin, self.KW, generator=g) * 0.45 / math.sqrt(self.cin * self.KW)
+                o.bias2 = torch.randn(self.cout, generator=g) * 0.1
+                o.wp, o.wp2 = pack_conv(o.w), pack_conv(o.w2)
+            elif self.up:
+                o.w = torch.randn(self.cin, self.cout, 2 * self.up, generator=g) / math.sqrt(2 * self.cin)
+                o.wp = conv_transpose_pack(o.w, self.up)
+            else:
+                o.w = torch.randn(self.cout, self.cin, self.KW, generator=g) / math.sqrt(self.cin * self.KW)
+                o.wp = pack_conv(o.w)
+            o.bias = torch.randn(self.cout, generator=g) * 0.1
+            o.resid = torch.randn(B, self.cout, self.T_out, generator=g)
+            o.prev = torch.randn(B, self.cout, self.T_out, generator=g)
+            self._ops = o
+        return self._ops
+
+    def item(self, i):
+        """The operands of item i alone (B = 1), weights shared."""
+        o, s = self.ops(), _Ops()
+        s.__dict__.update(o.__dict__)
+        s.x, s.resid, s.prev = o.x[i:i + 1], o.resid[i:i + 1], o.prev[i:i + 1]
+        return s
+
+    def ref_kw(self, variant, o=None, lens="case"):
+        o = self.ops() if o is None else o
+        lens = self.lens if lens == "case" else lens
+        c2 = variant == "conv2"
+        if self.kind == "mrf":
+            return dict(dil=self.dil, lens=lens, slope=0.1, scale=1.0 / 3.0 if c2 else 1.0, prev=o.prev if c2 else None)
+        return dict(dil=self.dil, up=self.up, lens=lens, slope=0.1, resid=o.resid if c2 else None, scale=1.0 / 3.0 if c2 else 1.0,
+                    prev=o.prev if c2 else None)
+
+    def compute(self, variant, mode, o=None, lens="case"):
+        o = self.ops() if o is None else o
+        kw = self.ref_kw(variant, o, lens)
+        if self.kind == "mrf":
+            return mrf_ref(o.x, o.w, o.bias, o.w2, o.bias2, mode=mode, **kw)
+        return conv_ref(o.x, o.w, o.bias, mode=mode, **kw)
+
+    def refs(self, variant):
+        """-> (float64 reference, A_e, the fp32 CPU yardstick's err in the same metric); computed once per (case, variant)."""
+        if variant not in self._refs:
+            ref, A = self.compute(variant, "f64"), self.compute(variant, "abs")
+            self._refs[variant] = (ref, A, parity_err(self.compute(variant, "f32"), ref, A)[0])
+        return self._refs[variant]
+
+
+def _x3_walk(B, q_total, rows_total, vr):
+    return (B * ((q_total + 255) // 256), (rows_total + vr - 1) // vr)
+
+
+def conv_cases():
+    cs = []
+    # ---- taps: every (kernel, dilation) the ABI takes.  Cout = 64: rows_pad = 64 is no multiple of 128, so wg_rows = 128 falls back to the
+    # 64-row forms -- k = 3 / 7 reach <KW,2,2,4,3>, k = 11 reaches <11,2,4,4,2> in both x3 forms
+    for KW in (3, 7, 11):
+        for d in (1, 2, 3, 4, 5):
+            r = K11 if KW == 11 else R64
+            cs.append(ConvCase(f"taps_k{KW}d{d}", "taps", "conv", B=2, cin=24, cout=64, T=300, KW=KW, dil=d, reach={"x3": r, "x3w": r}))
+            for C_ in (32, 64):
+                cs.append(ConvCase(f"taps_mrf_k{KW}d{d}_c{C_}", "taps", "mrf", B=2, cin=C_, cout=C_, T=300, KW=KW, dil=d, variants=("plain", "conv2"), forms=("mrf",)))
+    # ---- time seams.  conv: Cout = 24 <= 32 rows: <KW,1,2,4,3> for every k (wg_rows is not looked at)
+    for KW, d in ((3, 1), (7, 5), (11, 5)):
+        for T in (1, 2, 3, 255, 256, 257, 513):
+            cs.append(ConvCase(f"seam_k{KW}d{d}_T{T}", "seams", "conv", B=2, cin=20, cout=24, T=T, KW=KW, dil=d, variants=("plain", "conv2"),
+                               reach={"x3": NARROW, "x3w": NARROW}))
+        for i, T in enumerate((1, MRF_VT2[KW] - 1, MRF_VT2[KW], MRF_VT2[KW] + 1, 2 * MRF_VT2[KW] + 1)):
+            C_ = 64 if (i + KW) % 2 else 32
+            cs.append(ConvCase(f"seam_mrf_k{KW}d{d}_T{T}_c{C_}", "seams", "mrf", B=2, cin=C_, cout=C_, T=T, KW=KW, dil=d, variants=("plain", "conv2"), forms=("mrf",)))
+    # transposed: the window walk runs over q in [0, T_in]: T_in = 255 is one full window, 256 opens a second one for a single column.
+    # up 8, 32 -> 16: 128 rows = rows_pad: 64-row T<2,2,2,4,3> by default, wide T<2,2,2,8,2> with wg_rows = 128.  up 2, 64 -> 32: 64 rows:
+    # the streaming kernel up2_stream<4> unless wg_rows = -1, then T<2,2,2,4,3>
+    for T in (1, 255, 256, 257):
+        cs.append(ConvCase(f"seam_up8_T{T}", "seams", "tconv", B=2, cin=32, cout=16, T=T, up=8, reach={"x3": T_R64, "x3w": T_WIDE}))
+        cs.append(ConvCase(f"seam_up2_T{T}", "seams", "tconv", B=2, cin=64, cout=32, T=T, up=2, forms=("f32", "stream", "generic"),
+                           reach={"stream": STREAM4, "generic": T_R64}))
+    # ---- valid lengths on every form, plain and in the conv2 form.  Seam = 256 (window) / VT2 (mrf); T % 4 == 0, so the f32 kernels stage
+    # float4s that straddle a length.  Cout = 65: rows_pad 128: <KW,2,2,4,3> with two row tiles, and the 128-row <KW,2,2,8,2>
+    both = ("plain", "conv2")
+    cl = lambda seam, T: [-3, 0, 1, seam - 1, seam, seam + 1, T]
+    cs.append(ConvCase("len_k7d3", "lengths", "conv", B=7, cin=20, cout=65, T=300, KW=7, dil=3, lens=cl(256, 300), variants=both, reach={"x3": R64, "x3w": WIDE}))
+    cs.append(ConvCase("len_k11d5_narrow", "lengths", "conv", B=7, cin=20, cout=24, T=300, KW=11, dil=5, lens=cl(256, 300), variants=both, forms=("f32", "x3"),
+                       reach={"x3": NARROW}))
+    cs.append(ConvCase("len_k11d3_wide", "lengths", "conv", B=7, cin=20, cout=128, T=300, KW=11, dil=3, lens=cl(256, 300), variants=both, reach={"x3": K11, "x3w": WIDE}))
+    cs.append(ConvCase("len_up8", "lengths", "tconv", B=7, cin=32, cout=16, T=300, up=8, lens=cl(256, 300), variants=both, reach={"x3": T_R64, "x3w": T_WIDE}))
+    cs.append(ConvCase("len_up8_512rows", "lengths", "tconv", B=7, cin=64, cout=64, T=260, up=8, lens=cl(256, 260), variants=both, reach={"x3": T_R64, "x3w": T_WIDE}))
+    cs.append(ConvCase("len_up2_c64", "lengths", "tconv", B=7, cin=64, cout=32, T=300, up=2, lens=cl(256, 300), variants=both, forms=("f32", "stream", "generic"),
+                       reach={"stream": STREAM4, "generic": T_R64}))
+    cs.append(ConvCase("len_up2_c128", "lengths", "tconv", B=7, cin=128, cout=64, T=300, up=2, lens=cl(256, 300), variants=both, forms=("f32", "stream", "generic"),
+                       reach={"stream": STREAM8, "generic": T_R64}))
+    for KW, d, C_ in ((3, 3, 64), (7, 5, 32), (11, 3, 64)):
+        T = MRF_VT2[KW] + 44
+        cs.append(ConvCase(f"len_mrf_k{KW}d{d}_c{C_}", "lengths", "mrf", B=7, cin=C_, cout=C_, T=T, KW=KW, dil=d, lens=cl(MRF_VT2[KW], T), variants=both, forms=("mrf",)))
+    # ---- channels: chunk edges of the f32 kernel (8 channels per chunk at k = 3, 4 at k = 7 / 11) and of x3 (16).  Cout = 33: 64-row forms
+    for cin in (1, 7, 8, 9, 15, 16, 17, 100):
+        cs.append(ConvCase(f"cin{cin}_k3", "channels", "conv", B=2, cin=cin, cout=33, T=70, KW=3, dil=1, forms=("f32", "x3"), reach={"x3": R64}))
+        cs.append(ConvCase(f"cin{cin}_k11", "channels", "conv", B=2, cin=cin, cout=33, T=70, KW=11, dil=2, forms=("f32", "x3"), reach={"x3": K11}))
+    cs.append(ConvCase("cin512_k3", "channels", "conv", B=2, cin=512, cout=64, T=40, KW=3, dil=1, variants=both, reach={"x3": R64, "x3w": R64}))
+    cs.append(ConvCase("cin512_k7_wide", "channels", "conv", B=1, cin=512, cout=128, T=40, KW=7, dil=1, reach={"x3": R64, "x3w": WIDE}))
+    # ---- rows: n_rt 1, 2, 3, 4 of the 64-row forms, pad rows (24, 33, 65), and rows_pad = 192, where wg_rows = 128 must fall back
+    for cout in (24, 32, 33, 64, 65, 128, 192, 256):
+        for KW, d in ((7, 3), (11, 1)):
+            small = NARROW if cout <= 32 else (K11 if KW == 11 else R64)
+            big = WIDE if cout in (65, 128, 256) else small
+            cs.append(ConvCase(f"cout{cout}_k{KW}", "rows", "conv", B=2, cin=20, cout=cout, T=70, KW=KW, dil=d, variants=both, reach={"x3": small, "x3w": big},
+                               fallback=cout == 192))
+    # transposed shapes: (16, 8, 2): 16 rows: T<2,1,2,4,3>; (32, 16, 8): 128 rows; (64, 32, 8): 256 rows; the two x2 up-samplers stream
+    cs.append(ConvCase("t_16_8_up2", "rows", "tconv", B=2, cin=16, cout=8, T=41, up=2, variants=both, reach={"x3": T_NARROW, "x3w": T_NARROW}))
+    cs.append(ConvCase("t_32_16_up8", "rows", "tconv", B=2, cin=32, cout=16, T=41, up=8, variants=both, reach={"x3": T_R64, "x3w": T_WIDE}))
+    cs.append(ConvCase("t_64_32_up8", "rows", "tconv", B=2, cin=64, cout=32, T=41, up=8, variants=both, reach={"x3": T_R64, "x3w": T_WIDE}))
+    cs.append(ConvCase("t_64_32_up2", "rows", "tconv", B=2, cin=64, cout=32, T=41, up=2, variants=both, forms=("f32", "stream", "generic"), reach={"stream": STREAM4, "generic": T_R64}))
+    cs.append(ConvCase("t_128_64_up2", "rows", "tconv", B=2, cin=128, cout=64, T=41, up=2, variants=both, forms=("f32", "stream", "generic"), reach={"stream": STREAM8, "generic": T_R64}))
+    # ---- windows: the 1-D walk win = (jj / n_rt) * 8 + xcd of conv_x3_kernel.  n_win in {1, 7, 8, 9, 12, 17}; Cout 64 / 128 / 256 / 512 gives
+    # n_rt 1 / 2 / 4 / 8 in the 64-row form and 1 / 1 / 2 / 4 in the 128-row form (Cout = 64: rows_pad 64, falls back to 64 rows)
+    for B, T, n_win in ((1, 40, 1), (7, 8, 7), (8, 8, 8), (9, 40, 9), (3, 769, 12), (17, 8, 17)):
+        for cout, rt64, rt128 in ((64, 1, 1), (128, 2, 1), (256, 4, 2), (512, 8, 4)):
+            cs.append(ConvCase(f"win{n_win}_cout{cout}", "windows", "conv", B=B, cin=8, cout=cout, T=T, KW=3, dil=1, forms=("x3", "x3w"),
+                               reach={"x3": R64, "x3w": R64 if cout == 64 else WIDE}, claims={"x3": (n_win, rt64), "x3w": (n_win, rt128)}))
+    cs.append(ConvCase("win9_up8", "windows", "tconv", B=3, cin=16, cout=32, T=513, up=8, forms=("x3", "x3w"), reach={"x3": T_R64, "x3w": T_WIDE},
+                       claims={"x3": (9, 4), "x3w": (9, 2)}))
+    # ---- alignment: T % 4 == 0 with the input pointer one element into its allocation: vec_ok false by address, scalar staging
+    cs.append(ConvCase("off1_k7d3", "alignment", "conv", B=2, cin=20, cout=33, T=300, KW=7, dil=3, variants=both, forms=("f32", "x3"), reach={"x3": R64}, in_offset=1))
+    cs.append(ConvCase("off1_k3d2", "alignment", "conv", B=2, cin=20, cout=33, T=300, KW=3, dil=2, forms=("f32", "x3"), reach={"x3": R64}, in_offset=1))
+    cs.append(ConvCase("off1_up8", "alignment", "tconv", B=2, cin=32, cout=16, T=60, up=8, forms=("f32", "x3"), reach={"x3": T_R64}, in_offset=1))
+    cs.append(ConvCase("off1_up2", "alignment", "tconv", B=2, cin=64, cout=32, T=60, up=2, forms=("f32", "stream", "generic"), reach={"stream": STREAM4, "generic": T_R64}, in_offset=1))
+    cs.append(ConvCase("off1_mrf_k7d3_c32", "alignment", "mrf", B=2, cin=32, cout=32, T=300, KW=7, dil=3, variants=both, forms=("mrf",), in_offset=1))
+    cs.append(ConvCase("off1_mrf_k3d1_c64", "alignment", "mrf", B=2, cin=64, cout=64, T=300, KW=3, dil=1, lens=[300, 123], forms=("mrf",), in_offset=1))
+    cs.append(ConvCase("odd_T301_k7d3", "alignment", "conv", B=2, cin=20, cout=33, T=301, KW=7, dil=3, lens=[301, 130], forms=("f32", "x3"), reach={"x3": R64}))
+    cs.append(ConvCase("odd_T301_mrf_k11d1", "alignment", "mrf", B=2, cin=32, cout=32, T=301, KW=11, dil=1, lens=[301, 130], forms=("mrf",)))
+    # ---- neighbours: the last channel chunk has pad channels (Cin 20 / 100 at 8 and 16 per chunk, 18 at 4 per chunk); in memory they are the
+    # next item's first channels
+    for cin in (18, 20, 100):
+        cs.append(ConvCase(f"nb_cin{cin}_k3", "neighbours", "conv", B=3, cin=cin, cout=33, T=70, KW=3, dil=1, forms=("f32", "x3"), reach={"x3": R64}))
+        cs.append(ConvCase(f"nb_cin{cin}_k7", "neighbours", "conv", B=3, cin=cin, cout=128, T=70, KW=7, dil=1, reach={"x3": R64, "x3w": WIDE}))
+    # transposed: the f32 kernel walks 16 channels per chunk over a slab padded to 8 (Cin 20 -> 24, 8 -> 8: its last chunk ends past the slab)
+    cs.append(ConvCase("nb_cin20_up8", "neighbours", "tconv", B=3, cin=20, cout=16, T=70, up=8, reach={"x3": T_R64, "x3w": T_WIDE}))
+    cs.append(ConvCase("nb_cin8_up2", "neighbours", "tconv", B=3, cin=8, cout=4, T=70, up=2, forms=("f32", "x3"), reach={"x3": T_NARROW}))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+class PosCase:
+    """One posconv problem: n_seq sequences of seq_n rows, lengths lens[seq % B] (None: no length array), KW = 31."""
+
+    def __init__(self, name, seq_n, groups, lens, n_seq=None, resid=True, pad=8):
+        self.name, self.seq_n, self.groups, self.lens, self.resid, self.pad = name, seq_n, groups, lens, resid, pad
+        self.n_seq = n_seq if n_seq is not None else (len(lens) if lens else 2)
+        self.D, self.KW = groups * 64, 31
+        self._ops, self._refs = {}, {}
+
+    def ops(self, dtype):
+        """x [n_seq seq_n][D], w [D][64][KW], resid in dtype (the kernel's operands), bias fp32."""
+        if dtype not in self._ops:
+            g = torch.Generator().manual_seed(5000 + self.seq_n * 17 + self.groups)
+            o = _Ops()
+            o.x = torch.randn(self.n_seq * self.seq_n, self.D, generator=g).to(dtype)
+            o.w = (torch.randn(self.D, 64, self.KW, generator=g) / math.sqrt(64 * self.KW)).to(dtype)
+            o.bias = torch.randn(self.D, generator=g) * 0.1
+            o.resid = torch.randn(self.n_seq * self.seq_n, self.D, generator=g).to(dtype) if self.resid else None
+            self._ops[dtype] = o
+        return self._ops[dtype]
+
+    def packed(self, dtype):
+        """-> (x, resid, starts, total_rows): rows [0, len) of every sequence back to back, s % 3 rows nobody owns behind sequence s (2 at the
+        end; finite values)."""
+        o, rows = self.ops(dtype), posconv_rows(self.n_seq, self.seq_n, self.lens)
+        g = torch.Generator().manual_seed(77)
+        xs, rs, starts, r = [], [], [], 0
+        for s, (r0, _, L) in enumerate(rows):
+            gap = s % 3 if s + 1 < self.n_seq else 2
+            starts.append(r)
+            xs += [o.x[r0:r0 + L], torch.randn(gap, self.D, generator=g).to(dtype)]
+            if o.resid is not None:
+                rs += [o.resid[r0:r0 + L], torch.randn(gap, self.D, generator=g).to(dtype)]
+            r += L + gap
+        return torch.cat(xs, 0), (torch.cat(rs, 0) if rs else None), starts, r
+
+    def refs(self, dtype, layout):
+        """-> (refs, As, yardstick) for the operands of dtype in the padded or packed layout; lists over sequences of (first row, tensor)."""
+        key = (dtype, layout)
+        if key not in self._refs:
+            o = self.ops(dtype)
+            x, resid, starts = o.x, o.resid, None
+            if layout == "packed":
+                x, resid, starts, _ = self.packed(dtype)
+            kw = dict(n_seq=self.n_seq, seq_n=self.seq_n, groups=self.groups, lens=self.lens, starts=starts)
+            ref, A, y32 = (posconv_ref(x, o.w, o.bias, resid, mode=m, **kw) for m in ("f64", "abs", "f32"))
+            yard = max([parity_err(y[1], r[1], a[1])[0] for y, r, a in zip(y32, ref, A) if r[1].numel()] or [0.0])
+            self._refs[key] = (ref, A, yard)
+        return self._refs[key]
+
+
+def posconv_cases():
+    """seq_n at the edges of the f32 kernel's 64-token and the bf16 kernel's 256-token workgroups; lengths 1, seam +- 1 and seq_n, a zero and a
+    negative one; n_seq = 2 B (lengths indexed seq % B) where the case has a length array; 16 groups at seq_n = 257."""
+    cs = []
+    for i, seq_n in enumerate((1, 15, 16, 17, 63, 64, 65, 255, 256, 257, 513)):
+        lens = sorted({L for L in (1, 63, 65, 255, 257, seq_n) if L <= seq_n}) + [0, -2]
+        groups = 16 if seq_n == 257 else (1 if seq_n in (1, 16, 64, 513) else 2)
+        if seq_n == 257:
+            lens = [257, 255, 1, 0]
+        cs.append(PosCase(f"seq_n{seq_n}", seq_n, groups, lens, n_seq=2 * len(lens), resid=i % 2 == 0, pad=0 if i % 4 == 3 else 8))
+    cs.append(PosCase("full_seq_n300", 300, 2, None, n_seq=3, resid=True, pad=8))
+    return cs

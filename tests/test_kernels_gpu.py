@@ -854,47 +854,15 @@ def test_posconv(hip_tiny, dtype):
 
 
 # ------------------------------------------------------------------------------------ vocoder convs
-def _pack_conv(w):        # torch [Cout][Cin][KW] -> [Cin_pad8][KW][Cout_pad64]
-    cout, cin, kw = w.shape
-    t = torch.zeros(((cin + 7) // 8 * 8, kw, (cout + 63) // 64 * 64))
-    t[:cin, :, :cout] = w.permute(1, 2, 0)
-    return t
+from tests.gpu_util import pack_conv as _pack_conv  # noqa: E402  (the conv helpers live in tests/gpu_util.py: pack_conv, split_conv_weights, conv1d)
 
 
 def _split_conv_weights(eng, rt, gu, dw):
-    """vv_conv_split_weights on a packed fp32 slab [Cin_pad][KW][rows_pad] (device) -> the x3 slab (device uint16 tensor)."""
-    cin_pad, kw, rows_pad = dw.shape
-    nbytes = int(eng.lib.vv_conv_split_bytes(cin_pad, kw, rows_pad))
-    assert nbytes == (cin_pad + 15) // 16 * kw * 3 * rows_pad * 16 * 2
-    wb = torch.zeros(nbytes // 2, dtype=torch.int16, device=gu.DEV)
-    gu.check(eng, eng.lib.vv_conv_split_weights(eng.ctx, dw.data_ptr(), cin_pad, kw, rows_pad, wb.data_ptr(), gu.stream()))
-    torch.cuda.synchronize()
-    return wb
+    return gu.split_conv_weights(eng, dw)
 
 
-def _run_conv(eng, rt, gu, x, wp, bias, cout, T_out, KW, dil, up, resid=None, pre_slope=1.0, scale=1.0, accumulate=0, out0=None, lens=None,
-              x3=False):
-    B, cin, T_in = x.shape
-    out = out0.clone().to(gu.DEV) if out0 is not None else torch.zeros(B, cout, T_out, device=gu.DEV)
-    dx, dw, db = x.to(gu.DEV), wp.to(gu.DEV), bias.to(gu.DEV)
-    dr = resid.to(gu.DEV) if resid is not None else None
-    dl = torch.tensor(lens, dtype=torch.int32, device=gu.DEV) if lens is not None else None
-    a = rt.vv_conv_args()
-    a.in_, a.W, a.bias, a.out = dx.data_ptr(), dw.data_ptr(), db.data_ptr(), out.data_ptr()
-    a.resid = dr.data_ptr() if dr is not None else None
-    a.B, a.Cin, a.Cout, a.T_in, a.T_out, a.KW, a.dil = B, cin, cout, T_in, T_out, KW, dil
-    a.transposed, a.up = (1 if up else 0), up
-    a.rows_total = cout * up if up else cout
-    a.rows_pad = (a.rows_total + 63) // 64 * 64
-    a.accumulate, a.pre_slope, a.out_scale = accumulate, pre_slope, scale
-    a.len_in = dl.data_ptr() if dl is not None else None
-    if x3:
-        wb = _split_conv_weights(eng, rt, gu, dw)
-        a.W_x3 = wb.data_ptr()
-        a.wg_rows = x3 if (isinstance(x3, int) and not isinstance(x3, bool)) else 0      # 128: the 8-wave workgroup form; -1: never the streaming up-sampler
-    gu.check(eng, eng.lib.vv_conv1d(eng.ctx, C.byref(a), gu.stream()))
-    torch.cuda.synchronize()
-    return out
+def _run_conv(eng, rt, gu, x, *args, **kw):
+    return gu.conv1d(eng, x, *args, **kw)
 
 
 @pytest.mark.parametrize("x3", [False, True, 128])         # f32 MFMA / x3 (4-wave workgroups) / x3 with 8-wave 128-row workgroups

@@ -171,8 +171,22 @@ int vvk_posconv(const vv_posconv_args* a, hipStream_t st, const char** err) {
     if (a->KW < 1 || a->KW > 63 || !(a->KW & 1)) { *err = "posconv: odd kernel width expected"; return -22; }
     if (a->ld_in < a->groups * 64 || a->ld_out < a->groups * 64) { *err = "posconv: 64 channels per group expected"; return -22; }
     if (a->row_start && !a->seq_len) { *err = "posconv: packed rows need seq_len"; return -22; }
+    // the kernels index seq_len[seq % B] (conditional and unconditional lanes share one length array)
+    if (a->seq_len && a->B <= 0) { *err = "posconv: seq_len needs B >= 1 (lengths are indexed seq % B)"; return -22; }
+    if (a->resid && a->ld_resid < a->groups * 64) { *err = "posconv: ld_resid must cover groups * 64 channels"; return -22; }
     if (a->dtype == VV_BF16) {
         if ((a->ld_in * 2) % 16 || (uintptr_t)a->in % 16 || (uintptr_t)a->W % 16) { *err = "posconv: alignment"; return -22; }
+        // epilogue: a lane owns 4 consecutive channels -- float4 of bias, load4<bf16> of resid (8 bytes), store4 of out (8 bytes
+        // bf16, 16 bytes f32); every row must start on that boundary
+        const int out_bytes = a->out_dtype == VV_BF16 ? 8 : 16;
+        if (a->ld_out % 4 || (uintptr_t)a->out % out_bytes || (uintptr_t)a->bias % 16) {
+            *err = "posconv: bf16 kernel stores 4 channels at a time: ld_out % 4 elements, out 8-byte (bf16) / 16-byte (f32) aligned, bias 16-byte aligned";
+            return -22;
+        }
+        if (a->resid && (a->ld_resid % 4 || (uintptr_t)a->resid % 8)) {
+            *err = "posconv: bf16 kernel loads 4 residual channels at a time: ld_resid % 4 elements, resid 8-byte aligned";
+            return -22;
+        }
         dim3 grid((a->seq_n + PC_TOK - 1) / PC_TOK, a->groups, a->n_seq);
         const size_t lds = (size_t)(PC_TOK + a->KW - 1) * 128 + 2 * 8192;
         if (a->out_dtype == VV_BF16)

@@ -90,10 +90,13 @@ __global__ __launch_bounds__(256, 4) void conv_mfma_kernel(const float* __restri
                 *(float4*)(xs + c * xw_pad + i4 * 4) = v;
             }
         }
-        // ---- stage the weight slab: ws[c][kw][r] = Wt[c0+c][kw][r0+r]   (padded, no masks)
+        // ---- stage the weight slab: ws[c][kw][r] = Wt[c0+c][kw][r0+r]   (padded to 8 channels: no masks while a chunk is <= 8 channels;
+        // the 16-channel chunk of the transposed form ends past a [Cin_pad8] slab when Cin_pad8 is no multiple of 16: zeros there)
         for (int i = threadIdx.x; i < VCI * KW * (VR / 4); i += 256) {
             const int r4 = i % (VR / 4), ck = i / (VR / 4);
-            *(float4*)(ws + ck * VR + r4 * 4) = *(const float4*)(Wt + ((size_t)c0 * KW + ck) * rows_pad + r0 + r4 * 4);
+            float4 wv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (VCI <= 8 || c0 + ck / KW < ((Cin + 7) & ~7)) wv = *(const float4*)(Wt + ((size_t)c0 * KW + ck) * rows_pad + r0 + r4 * 4);
+            *(float4*)(ws + ck * VR + r4 * 4) = wv;
         }
         __syncthreads();
 #pragma unroll
