@@ -109,7 +109,7 @@ VV_API int vv_set_ode_plan(vv_ctx* ctx, const float* sinus_host, const float* dt
  * audio [B][ld_audio] int16, audio_len[B], text_ids [B][ld_text] int32, text_len[B], seq_len[B]
  * (= max_duration per item, frames), N = padded frame count (>= every seq_len).
  * Outputs: cat_mel_text, cat_mel_text_drop [B][N][n_mel+text_dim] f32, ref_signal_len[B] int32.
- * (noise is supplied by the caller; the rope tables are slices of the bound constant tables.) */
+ * (noise is supplied by the caller, or drawn on the device by vv_noise_fill; the rope tables are slices of the bound constant tables.) */
 VV_API int vv_preprocess(vv_ctx* ctx, int B, int N, const int16_t* audio, int ld_audio, int max_audio_len,
                   const int32_t* audio_len, const int32_t* text_ids, int ld_text, const int32_t* text_len,
                   const int32_t* seq_len, float* cat_mel_text, float* cat_mel_text_drop,
@@ -147,6 +147,18 @@ VV_API int vv_preprocess_edit(vv_ctx* ctx, int B, int N, const int16_t* audio, i
  * (x [B][N][n_mel], cat_mel_text [B][N][n_mel + text_dim], both 16-byte aligned; keep as above). */
 VV_API int vv_edit_restore(vv_ctx* ctx, int B, int N, float* x, const float* cat_mel_text, const uint8_t* keep, int ld_keep,
                            const int32_t* seq_len, void* stream);
+
+/* ---- N9 start noise on the device.  The reference's preprocess graph returns `noise` itself (core/tts_engine.py:133-146,
+ * 229-230); this call fills x [B][N][n_mel] f32 (16-byte aligned, n_mel % 4 == 0) with it.  Philox4x32-10: key = the 64-bit seed (low word
+ * k0, high word k1), counter = (q, 0, stream_lo, stream_hi); element e = t * n_mel + m of item b lies in group q = e >> 2 and takes output
+ * word e & 3.  keys = device [B][2] uint64 {seed, stream}: a value is a pure function of (seed, stream, t, m), whatever the batch, N or
+ * the padding, and a captured hipGraph replays with new keys without a new capture.  Word w -> u = ((w >> 9) + 0.5f) * 2^-23 (exact in
+ * fp32, in (0, 1)); kind 0 = normals by Box-Muller on the word pairs (0, 1) and (2, 3): r = sqrtf(-2 logf(u0)), z0 = r cospif(2 u1),
+ * z1 = r sinpif(2 u1); kind 1 = the four uniforms themselves (exact tests).  Rows t >= clamp(seq_len[b], 0, N) are written as +0.0f.
+ * -22, and nothing is launched, for n_mel % 4 != 0, a misaligned x, B < 1, N < 1, a kind outside {0, 1}, a null pointer, or N * n_mel / 4
+ * > 2^32 (the counter word q); the context stays usable. */
+VV_API int vv_noise_fill(vv_ctx* ctx, int B, int N, int n_mel, float* x, const int32_t* seq_len,
+                         const uint64_t* keys /* device [B][2] = {seed, stream} */, int kind /* 0 normal, 1 uniform */, void* stream);
 
 /* replaces the loop over sessions['transformer'].run, core/tts_engine.py:148-174: n_steps Euler
  * steps of the flow ODE starting at step index step0, state x [B][N][n_mel] f32 updated in HBM.

@@ -4,7 +4,8 @@ The reference REST layer pushes each request onto a worker thread against ONE en
 mutates ``engine.config.speed`` around the call (api/tts_engine.py:64-91).  Here every request carries its own speed,
 all chunks of all waiting requests are flattened into ragged GPU batches (different reference clips per item are
 fine: per-item lengths live on the device), and each request gets its own cross-faded PCM back through a Future.
-Noise is drawn from a per-request generator seeded with (config.random_seed, request serial), and every kernel of the
+Noise is drawn from a per-request generator seeded with (config.random_seed, request serial) -- or, with ``noise_source="device"``, in
+HBM from the Philox streams (config.random_seed, request serial, chunk) of model_spec.noise_keys -- and every kernel of the
 path is row- or sequence-local with one arithmetic whatever the launch size (round 4: the split-K tail is off, the two
 GEMM kernels share their epilogue arithmetic), so a request's audio does not depend on which other requests happened to
 share its batch -- bit for bit (tests/test_engine_gpu.py::test_batching_frontend_batch_composition_invariance*).
@@ -33,10 +34,10 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "cfgs", "ivals", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "t0", "n_req")
 
     def __init__(self):
-        self.plans, self.flat, self.blocks, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], time.time(), 0
+        self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
 
 
 class BatchingFrontend:
@@ -139,15 +140,21 @@ class BatchingFrontend:
             fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))
             return
         try:
-            n_mel = eng.model_session_manager.spec.n_mel
-            gen = torch.Generator().manual_seed(eng.config.random_seed * 1000003 + serial)
-            blocks = [torch.randn((int(i[2][0]), n_mel), generator=gen, dtype=torch.float32) for i in inputs]
+            blocks, keys = [], []
+            if eng._device_noise():         # N9: nothing is drawn here -- the request's serial names its Philox streams, chunk by chunk
+                from .model_spec import noise_keys
+                keys = list(noise_keys(eng.config.random_seed, serial, len(inputs)))
+            else:
+                n_mel = eng.model_session_manager.spec.n_mel
+                gen = torch.Generator().manual_seed(eng.config.random_seed * 1000003 + serial)
+                blocks = [torch.randn((int(i[2][0]), n_mel), generator=gen, dtype=torch.float32) for i in inputs]
         except Exception as e:          # noqa: BLE001  (nothing of this request has entered the batch yet)
             fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))
             return
         batch.plans.append((fut, len(inputs)))
         batch.flat.extend(inputs)
         batch.blocks.extend(blocks)
+        batch.keys.extend(keys)
         batch.cfgs.extend([cfg_strength] * len(inputs))
         batch.ivals.extend([cfg_interval] * len(inputs))
         batch.n_req += 1
@@ -256,7 +263,10 @@ class BatchingFrontend:
         t0 = time.perf_counter()
         with eng._lock:
             if eng.model_session_manager.engine is not None:
-                waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
+                if batch.keys:
+                    waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
+                else:
+                    waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0

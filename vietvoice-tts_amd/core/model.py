@@ -47,8 +47,12 @@ class HipSession:
     """One stage of the HIP engine with onnxruntime.InferenceSession's call shape (batch 1, host
     numpy in and out -- the reference's contract, including its host round trips)."""
 
-    def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None):
+    def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None,
+                 noise_keys=None):
         self.engine, self.kind, self.noise_gen, self.fuse_nfe = engine, kind, noise_gen, max(1, int(fuse_nfe))
+        # N9 (ModelConfig.noise_source == "device"): a callable -> the next run's Philox key row {seed, stream}; the preprocess session
+        # then fills the noise in HBM (vv_noise_fill) and returns it, as the reference's graph returns its own.  None = the host generator.
+        self.noise_keys = noise_keys
         self.cfg_strength = cfg_strength          # None = the model's guidance strength (ModelConfig.cfg_strength)
         self.cfg_interval = cfg_interval          # None = guidance at every evaluation (ModelConfig.cfg_interval)
         self._in, self._out = SESSION_IO[kind]
@@ -73,7 +77,10 @@ class HipSession:
             n = int(np.asarray(vals[2]).reshape(-1)[0])
             i32 = lambda v: torch.tensor([v], dtype=torch.int32, device=dev)
             pre = eng.preprocess(audio, i32(n_audio), ids, i32(ids.shape[1]), i32(n), n, audio_len_host=[n_audio])
-            noise = torch.randn((1, n, eng.spec.n_mel), generator=self.noise_gen, dtype=torch.float32)
+            if self.noise_keys is not None:
+                noise = eng.noise(self.noise_keys(), pre["seq_len"], n).cpu()
+            else:
+                noise = torch.randn((1, n, eng.spec.n_mel), generator=self.noise_gen, dtype=torch.float32)
             res = {"noise": noise.numpy(), "ref_signal_len": pre["ref_signal_len"].cpu().numpy().astype(np.int64)}
             for k in ("rope_cos_q", "rope_sin_q", "rope_cos_k", "rope_sin_k"):
                 res[k] = pre[k].cpu().numpy()[None]
@@ -129,12 +136,40 @@ class ModelSessionManager:
         self.vocab_path = None
         self.engine = None           # HipSynth when the HIP sessions are active
         self.noise_gen = None
+        self.noise_serial = 0        # N9: calls served with device noise so far (take_noise_keys)
+        self.edit_serial = 0         # N9: seedless speech edits served with device noise so far (take_edit_keys)
+        self._queued_keys: List = [] # N9: key rows the engine has queued for the preprocess session's next runs
         self.spec = None
         self._clip_cache: Dict[str, bytes] = {}
 
     def _get_optimal_providers(self) -> List[str]:
         """The reference ranks onnxruntime providers (model.py:31-48); this build has exactly one."""
         return ["HIPExecutionProvider"] if self._session_factory is None else ["InjectedSessionProvider"]
+
+    # ------------------------------------------------------------------ N9: Philox keys of the device noise source
+    def take_noise_keys(self, n_chunks: int, seed: Optional[int] = None, edit: bool = False):
+        """The keys of ONE call of ``n_chunks`` chunks (model_spec.noise_keys) under the next call serial, which this advances: call k of
+        a fresh engine draws from the streams a front-end request with serial = k draws from.  The caller holds the engine lock."""
+        from ..model_spec import noise_keys
+        keys = noise_keys(self.config.random_seed if seed is None else seed, self.noise_serial, n_chunks, edit=edit)
+        self.noise_serial += 1
+        return keys
+
+    def take_edit_keys(self):
+        """The key of one seedless speech edit: edits count their own serials, in streams apart from synthesis (bit 63)."""
+        from ..model_spec import noise_keys
+        keys = noise_keys(self.config.random_seed, self.edit_serial, 1, edit=True)
+        self.edit_serial += 1
+        return keys
+
+    def queue_session_keys(self, keys) -> None:
+        """Key rows for the next runs of the preprocess session, one per run, in order (TTSEngine._synthesize_sessions)."""
+        self._queued_keys = [k.reshape(1, 2) for k in keys]
+
+    def _session_key(self):
+        """The preprocess session's next key row: a queued one, else a call of its own with one chunk (a reference-style caller that
+        drives the session directly)."""
+        return self._queued_keys.pop(0) if self._queued_keys else self.take_noise_keys(1)
 
     def _load_models_from_file(self) -> None:
         model_path = self.config.ensure_model_downloaded()
@@ -163,8 +198,9 @@ class ModelSessionManager:
                 from ..runtime import HipSynth
                 self.engine = HipSynth(spec, weights, device=self.config.device, acoustic_dtype=self.config.acoustic_dtype,
                                        nfe_step=self.config.nfe_step, ode_method=self.config.ode_method)
-                made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval)
-                        for k in SESSION_IO}
+                on_device = self._session_key if self.config.noise_source == "device" else None
+                made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval,
+                                      noise_keys=on_device if k == "preprocess" else None) for k in SESSION_IO}
             for name in ("preprocess", "transformer", "decode"):
                 sess = made[name]
                 self.sessions[name] = sess

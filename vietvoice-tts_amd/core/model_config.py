@@ -66,6 +66,8 @@ class ModelConfig:
     cfg_strength: Optional[float] = None    # classifier-free guidance strength of every synthesis of this engine; None = the model's
     cfg_interval: Optional[Tuple[float, float]] = None   # guidance only at the evaluations with lo <= t <= hi (limited-interval guidance);
                                             # outside it the unconditional branch is not computed.  None = guidance everywhere
+    noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
+                                            # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -81,6 +83,9 @@ class ModelConfig:
             self.cfg_strength = float(self.cfg_strength)
             if self.cfg_strength != self.cfg_strength or abs(self.cfg_strength) == float("inf"):
                 raise ValueError("cfg_strength must be a finite number or None")
+        from ..model_spec import NOISE_SOURCES
+        if self.noise_source not in NOISE_SOURCES:
+            raise ValueError(f"noise_source must be one of {list(NOISE_SOURCES)}")
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         self.validate_paths()

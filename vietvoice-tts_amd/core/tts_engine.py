@@ -137,7 +137,15 @@ class TTSEngine:
         names = m.input_names["decode"]
         return m.sessions["decode"].run(m.output_names["decode"], {names[0]: noise, names[1]: ref_signal_len})[0]
 
-    def _synthesize_sessions(self, inputs_list) -> List[np.ndarray]:
+    def _device_noise(self) -> bool:
+        """N9: the start noise is drawn in HBM (config.noise_source == "device"; the HIP engine only -- injected sessions draw their own)."""
+        return self.config.noise_source == "device" and self.model_session_manager.engine is not None
+
+    def _synthesize_sessions(self, inputs_list, noise_keys=None) -> List[np.ndarray]:
+        """noise_keys (device noise source): the chunks' key rows; default = a call of its own (the next call serial)."""
+        if self._device_noise():
+            m = self.model_session_manager
+            m.queue_session_keys(m.take_noise_keys(len(inputs_list)) if noise_keys is None else noise_keys)
         waves = []
         for audio, text_ids, max_duration, time_step in inputs_list:
             pre = self._run_preprocess(audio, text_ids, max_duration)
@@ -146,11 +154,14 @@ class TTSEngine:
         return waves
 
     # ------------------------------------------------------------------ device-resident batched path
-    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None) -> List[np.ndarray]:
+    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None) -> List[np.ndarray]:
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
         clips may differ per item (cross-request batches).  One ragged GPU batch per ``max_batch_chunks`` items.
         noise_blocks: optional pre-drawn (N_i, n_mel) fp32 tensors, one per item (the batching front end draws them from
         per-request generators); default = the manager's seeded stream, in item order, like the session path.
+        noise_keys (N9, ``noise_source="device"``): uint64 [n_items][2] Philox key rows (model_spec.noise_keys), one per item: the noise is
+        drawn in HBM by vv_noise_fill, no host tensor is built and none is uploaded.  Default with that source = a call of its own (the
+        next call serial); explicit noise_blocks still win.
         cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model).
         cfg_intervals: optional guidance interval (lo, hi) per item (None entries = ``config.cfg_interval``).  An item is guided at the
         evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed."""
@@ -167,7 +178,14 @@ class TTSEngine:
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
-        if noise_blocks is None:      # the same seeded stream the session path draws from: one (N_i, n_mel) block per chunk, in item order
+        if noise_blocks is not None:
+            noise_keys = None
+        elif noise_keys is not None or self._device_noise():
+            noise_keys = m.take_noise_keys(n_items) if noise_keys is None else np.asarray(noise_keys, dtype=np.uint64).reshape(-1, 2)
+            if len(noise_keys) != n_items:
+                raise ValueError(f"{len(noise_keys)} noise key rows for {n_items} items")
+        else:                         # the same seeded stream the session path draws from: one (N_i, n_mel) block per chunk, in item order
+            noise_keys = None
             noise_blocks = [torch.randn((n, spec.n_mel), generator=m.noise_gen, dtype=torch.float32) for n in seq_all]
         waves: List[Optional[np.ndarray]] = [None] * n_items
         # the device packs ragged rows, so padding is free for the acoustic stages; sorting by length still puts similar
@@ -214,9 +232,13 @@ class TTSEngine:
                 from ..runtime import DecodeGraphCache
                 Nb = DecodeGraphCache.bucket(N, 0)[0]
                 N, t_gen = DecodeGraphCache.bucket(Nb, Nb - int(ref_frames.min()))      # every chunk group of a text lands on one key
-            noise = torch.zeros((B, N, spec.n_mel), dtype=torch.float32)
-            for i, j in enumerate(idx):
-                noise[i, : seq[i]] = noise_blocks[j]
+            if noise_keys is None:
+                noise = torch.zeros((B, N, spec.n_mel), dtype=torch.float32)
+                for i, j in enumerate(idx):
+                    noise[i, : seq[i]] = noise_blocks[j]
+                keys = None
+            else:
+                noise, keys = None, eng.noise_keys_device(noise_keys[list(idx)])
             t32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
             cfg = None                                   # per-item guidance strength: only when some item asks for one
             if any(g_all[j] is not None for j in idx):
@@ -224,15 +246,16 @@ class TTSEngine:
             guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx])     # None: every item guided everywhere
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
-                x = noise.to(dev)
+                x = noise.to(dev) if keys is None else eng.noise(keys, pre["seq_len"], N)
                 eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide)
                 if self._decode_graphs is None:
                     self._decode_graphs = DecodeGraphCache(eng, self.config.decode_graph_cache_entries, self.config.decode_graph_cache_bytes)
                 pcm, pcm_len = self._decode_graphs.get(B, N, t_gen)(x, pre["ref_signal_len"], pre["seq_len"])
             else:
-                _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, noise.to(dev), t_gen,
+                _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N,
+                                                              None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
-                                                              audio_len_host=lens_a, cfg=cfg, guide=guide)
+                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys)
             pcm, pcm_len = pcm.cpu().numpy(), pcm_len.cpu().numpy()
             for i, j in enumerate(idx):
                 waves[j] = pcm[i, : pcm_len[i]].reshape(1, 1, -1)
@@ -251,7 +274,8 @@ class TTSEngine:
                 inputs_list = self._prepare_inputs(ref_audio, ref_text, text, speed=speed)
                 self._last_plan = [int(i[2][0]) for i in inputs_list]
                 if self.model_session_manager.engine is not None:
-                    waves = self._synthesize_device(inputs_list)
+                    keys = self.model_session_manager.take_noise_keys(len(inputs_list)) if self._device_noise() else None
+                    waves = self._synthesize_device(inputs_list, noise_keys=keys)
                 else:
                     waves = self._synthesize_sessions(inputs_list)
             final_wave = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration,
@@ -279,6 +303,8 @@ class TTSEngine:
         try:
             with self._lock:
                 inputs_list = self._prepare_inputs(ref_audio, ref_text, text, speed=speed)
+                # device noise: ONE call serial for the whole stream, chunk c under it whatever group it is synthesised in
+                keys = self.model_session_manager.take_noise_keys(len(inputs_list)) if self._device_noise() else None
             self._last_plan = [int(i[2][0]) for i in inputs_list]
             from .audio_processor import CrossfadeStream
             joiner = CrossfadeStream(len(inputs_list), self.config.cross_fade_duration, self.config.sample_rate)
@@ -286,7 +312,7 @@ class TTSEngine:
             for lo in range(0, len(inputs_list), step):
                 with self._lock:
                     if self.model_session_manager.engine is not None:
-                        waves = self._synthesize_device(inputs_list[lo: lo + step])
+                        waves = self._synthesize_device(inputs_list[lo: lo + step], noise_keys=None if keys is None else keys[lo: lo + step])
                     else:
                         waves = self._synthesize_sessions(inputs_list[lo: lo + step])
                 blocks = [joiner.push(w) for w in waves]
@@ -302,7 +328,8 @@ class TTSEngine:
         ``audio`` (a path or WAV bytes, taken in like a reference clip, or an int16 array at ``config.sample_rate``) so that the clip
         says ``text`` (the corrected FULL transcript); ``fix_duration`` = the new length of each span in seconds (default: unchanged).
         Only the spans are drawn from noise; every other frame conditions the model and is put back after the last step, and the
-        whole clip is rendered again by the vocoder.  Noise: the manager's seeded stream, or ``torch.Generator().manual_seed(seed)``.
+        whole clip is rendered again by the vocoder.  Noise: the manager's seeded stream, or ``torch.Generator().manual_seed(seed)``; with
+        ``noise_source="device"`` the Philox stream (seed or random_seed, edit serial, edit=True) of model_spec.noise_keys.
         Returns (int16 PCM of the spliced length -- hop * (N - 1) samples of it with the Vocos decoder --, seconds).  Validation errors propagate as ValueError; device failures become
         RuntimeError("Speech editing failed: ...")."""
         import torch
@@ -326,8 +353,12 @@ class TTSEngine:
             if plan.spliced_len / sr > cfg.max_chunk_duration:
                 raise ValueError(f"the edited clip would last {plan.spliced_len / sr:.2f}s, more than max_chunk_duration "
                                  f"({cfg.max_chunk_duration}s)")
-            gen = m.noise_gen if seed is None else torch.Generator().manual_seed(int(seed))
-            noise = torch.randn((plan.n_frames, m.spec.n_mel), generator=gen, dtype=torch.float32)
+            if self._device_noise():      # N9: edits have streams of their own (bit 63); a given seed is serial 0 -- the call is reproducible
+                from ..model_spec import noise_keys
+                noise, keys = None, (m.take_edit_keys() if seed is None else noise_keys(int(seed), 0, 1, edit=True))
+            else:
+                gen = m.noise_gen if seed is None else torch.Generator().manual_seed(int(seed))
+                noise, keys = torch.randn((plan.n_frames, m.spec.n_mel), generator=gen, dtype=torch.float32), None
             ids = self.text_processor.text_to_indices([list(clean)])
             try:
                 dev = eng.device
@@ -336,8 +367,9 @@ class TTSEngine:
                 _x, pcm, n_out = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
                                                torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
-                                               torch.from_numpy(plan.keep.reshape(1, -1)).to(dev), noise.unsqueeze(0).to(dev), cfg=g_item,
-                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]))
+                                               torch.from_numpy(plan.keep.reshape(1, -1)).to(dev),
+                                               None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
+                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys)
                 wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:
                 raise RuntimeError(f"Speech editing failed: {str(e)}") from e

@@ -11,7 +11,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.2 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.3 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -581,6 +581,18 @@ int vv_edit_restore(vv_ctx* c, int B, int N, float* x, const float* cat, const u
     hipStream_t st = (hipStream_t)stream;
     Prof p(c, VV_PROF_ELEMWISE, 0, (double)B * N * (1 + 8.0 * M), st);
     KCHK(c, vvk_edit_restore(x, cat, keep, ld_keep, seq_len, B, N, M, cd, st, &m__));
+    return 0;
+}
+
+// N9: the start noise of the flow ODE, drawn on the device.  Every argument is checked before the launch; a refused call launches nothing.
+int vv_noise_fill(vv_ctx* c, int B, int N, int n_mel, float* x, const int32_t* seq_len, const uint64_t* keys, int kind, void* stream) {
+    if (!c) return -22;
+    if (B < 1 || N < 1 || n_mel < 4 || n_mel % 4 || (kind != 0 && kind != 1) || !x || !seq_len || !keys || (uintptr_t)x % 16 || (uintptr_t)keys % 8)
+        return c->fail(-22, "vv_noise_fill: bad arguments (B, N >= 1; n_mel %% 4 == 0; x 16-byte aligned; keys [B][2] uint64; kind 0 or 1)");
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    Prof p(c, VV_PROF_ELEMWISE, 0, (double)B * (12.0 + 4.0 * N * n_mel), st);
+    KCHK(c, vvk_noise_fill(x, seq_len, (const unsigned long long*)keys, B, N, n_mel, kind, st, &m__));
     return 0;
 }
 

@@ -66,6 +66,9 @@ int vvk_edit_splice(const int16_t* src, long long n_src, const long long* desc, 
                     hipStream_t st, const char** err);
 int vvk_edit_restore(float* x, const float* cat, const uint8_t* keep, int ld_keep, const int* seq_len, int B, int N, int n_mel, int cd,
                      hipStream_t st, const char** err);
+// N9 start noise on the device (vv_noise.hip): Philox4x32-10 keyed per item, keys [B][2] = {seed, stream} in device memory
+int vvk_noise_fill(float* x, const int* seq_len, const unsigned long long* keys, int B, int N, int n_mel, int kind, hipStream_t st,
+                   const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

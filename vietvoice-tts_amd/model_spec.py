@@ -261,6 +261,26 @@ def guidance_mask(plan: OdePlan, interval, strengths) -> Optional[torch.Tensor]:
     return None if bool(mask.all()) else mask
 
 
+NOISE_SOURCES = ("host", "device")      # ModelConfig.noise_source: torch.randn on the host (default) | vv_noise_fill on the device (N9)
+
+
+def noise_keys(seed: int, serial: int, n_chunks: int, edit: bool = False):
+    """N9: the Philox keys of one call's chunks, numpy uint64 [n_chunks][2] = {seed, stream} -- the rows vv_noise_fill reads, and the
+    ONLY place the stream convention lives.  stream = (serial << 16) | chunk, bit 63 set for a speech edit: ``serial`` is the call's
+    (engine) or the request's (front end) serial, 0 <= serial < 2^47, ``chunk`` the chunk's index inside the call, n_chunks <= 65536.
+    ``seed``: any integer, taken modulo 2^64.  ValueError outside those ranges."""
+    import numpy as np
+    seed, serial, n_chunks = int(seed), int(serial), int(n_chunks)
+    if not 0 <= n_chunks <= 65536:
+        raise ValueError(f"noise_keys: {n_chunks} chunks do not fit the 16 chunk bits of a stream id")
+    if not 0 <= serial < (1 << 47):
+        raise ValueError(f"noise_keys: serial {serial} does not fit 47 bits")
+    keys = np.empty((n_chunks, 2), dtype=np.uint64)
+    keys[:, 0] = np.uint64(seed & ((1 << 64) - 1))
+    keys[:, 1] = np.arange(n_chunks, dtype=np.uint64) | np.uint64((serial << 16) | ((1 << 63) if edit else 0))
+    return keys
+
+
 def mel_filterbank(spec: ModelSpec) -> torch.Tensor:
     """HTK-scale triangular mel filterbank, no norm: (n_fft//2+1, n_mel) fp32."""
     n_freqs = spec.n_fft // 2 + 1

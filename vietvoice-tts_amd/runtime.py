@@ -169,6 +169,7 @@ EXPORTS = {
     "vv_edit_splice": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_preprocess_edit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vv_noise_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_edit_restore": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -472,17 +473,55 @@ class HipSynth:
             pcm_len[idx] = n
         return pcm, pcm_len
 
-    def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: torch.Tensor, t_gen_max: int,
+    # ------------------------------------------------------------------ start noise on the device (N9)
+    def noise_keys_device(self, keys) -> torch.Tensor:
+        """Philox keys {seed, stream} as the int64 [B][2] device tensor vv_noise_fill reads: from model_spec.noise_keys' numpy uint64
+        rows (a 16 * B byte upload), or a device tensor already in that form, which is returned as it is."""
+        if isinstance(keys, torch.Tensor):
+            assert keys.is_cuda and keys.dtype == torch.int64 and keys.is_contiguous() and keys.dim() == 2 and keys.shape[1] == 2
+            return keys
+        import numpy as np
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        if k.ndim != 2 or k.shape[1] != 2:
+            raise ValueError("noise keys are uint64 [B][2] = {seed, stream} (model_spec.noise_keys)")
+        return torch.from_numpy(k.view(np.int64)).to(self.device)
+
+    def noise(self, keys, seq_len: torch.Tensor, N: int, kind: int = 0, n_mel: Optional[int] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The start noise of B items, drawn in HBM (vv_noise_fill): fp32 [B, N, n_mel], item b's rows [0, clamp(seq_len[b], 0, N)) from
+        the Philox stream keys[b] = {seed, stream}, +0.0 behind them.  keys: model_spec.noise_keys rows or their device form
+        (noise_keys_device); seq_len int32 [B] on the device; kind 0 = normals, 1 = the uniforms under them (exact tests); n_mel defaults
+        to the model's; out = an existing [B, N, n_mel] buffer to fill (a captured graph's static one).  Raises on a refused call."""
+        kd = self.noise_keys_device(keys)
+        B, M = int(kd.shape[0]), int(self.spec.n_mel if n_mel is None else n_mel)
+        assert seq_len.is_cuda and seq_len.dtype == torch.int32 and seq_len.is_contiguous() and seq_len.shape == (B,)
+        if out is None:
+            out = torch.empty((B, int(N), M), dtype=torch.float32, device=self.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == (B, int(N), M)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_noise_fill(self.ctx, B, int(N), M, out.data_ptr(), seq_len.data_ptr(), kd.data_ptr(), int(kind),
+                                               self._stream()))
+        return out
+
+    @staticmethod
+    def _one_noise(noise, noise_keys):
+        if (noise is None) == (noise_keys is None):
+            raise ValueError("give exactly one of noise (a tensor drawn by the caller) and noise_keys (drawn on the device)")
+
+    def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: Optional[torch.Tensor], t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
-                         audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None):
+                         audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, noise_keys=None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
+        noise fp32 [B, N, n_mel] on the device, or None with noise_keys = (model_spec.noise_keys rows): the noise is then drawn on the
+        device (``noise``) and nothing of it crosses PCIe.  Exactly one of the two.
         gen_frames (host list, optional): per-item generated frames; lets the vocoder run in length buckets on ragged batches.
         seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
         cfg (optional fp32 [B] on the device): per-item guidance strength.  guide (optional uint8 [n_evals, B] on the host): the
         guidance mask of transformer_steps."""
+        self._one_noise(noise, noise_keys)
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
-        x = noise.clone()
+        x = noise.clone() if noise_keys is None else self.noise(noise_keys, seq_len, N)
         self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
@@ -551,12 +590,13 @@ class HipSynth:
         return x
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
-                   noise: torch.Tensor, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
-                   guide: Optional[torch.Tensor] = None):
+                   noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
+                   guide: Optional[torch.Tensor] = None, noise_keys=None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
-        transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device).
+        transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device) or, in its place, noise_keys =
+        model_spec.noise_keys rows (drawn on the device; exactly one of the two).
         Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = min(L_b, the vocoder's
         output of N_b frames) samples -- L_b with the HiFi-GAN (hop * N_b >= L_b), hop * (N_b - 1) with Vocos (the rest is zeros)."""
         s = self.spec
@@ -565,12 +605,13 @@ class HipSynth:
         B = len(L)
         frames = [v // hop + 1 for v in L]
         N = max(frames)
-        assert noise.shape == (B, N, s.n_mel) and noise.is_cuda and noise.dtype == torch.float32
+        self._one_noise(noise, noise_keys)
+        assert noise is None or (noise.shape == (B, N, s.n_mel) and noise.is_cuda and noise.dtype == torch.float32)
         mal = max(max(L), s.n_fft)                  # the audio plane is at least n_fft wide (vv_preprocess's contract)
         audio = self.edit_splice(src, rows, B, (mal + 3) // 4 * 4)
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
-        x = noise.clone()
+        x = noise.clone() if noise_keys is None else self.noise(noise_keys, pre["seq_len"], N)
         self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
@@ -582,9 +623,10 @@ class HipSynth:
         Long-form synthesis replays it per chunk group: ~80 launches become one graph launch."""
         return GraphedDecode(self, B, N, t_gen_max)
 
-    def capture_steps(self, B: int, N: int, seq_len_host, t_gen_max: int) -> "GraphedSteps":
-        """Capture all Euler steps + the decode of one batch shape into ONE hipGraph (single-utterance latency path)."""
-        return GraphedSteps(self, B, N, seq_len_host, t_gen_max)
+    def capture_steps(self, B: int, N: int, seq_len_host, t_gen_max: int, device_noise: bool = False) -> "GraphedSteps":
+        """Capture all Euler steps + the decode of one batch shape into ONE hipGraph (single-utterance latency path).
+        device_noise: the noise fill (vv_noise_fill) is captured in front of the steps and the graph is called with keys."""
+        return GraphedSteps(self, B, N, seq_len_host, t_gen_max, device_noise=device_noise)
 
     # ------------------------------------------------------------------ reference-clip ingest (N3)
     def resample_poly(self, x: torch.Tensor, taps: torch.Tensor, up: int, down: int, skip: int, n_out: int) -> torch.Tensor:
@@ -732,8 +774,12 @@ class GraphedSteps:
     the decode run one after the other on one stream and share it) are owned here.  ``__call__`` copies the inputs in and replays.
     No reference counterpart: the reference pays a host round trip per step (core/tts_engine.py:157-172)."""
 
-    def __init__(self, eng: HipSynth, B: int, N: int, seq_len_host, t_gen_max: int, n_steps: Optional[int] = None):
+    def __init__(self, eng: HipSynth, B: int, N: int, seq_len_host, t_gen_max: int, n_steps: Optional[int] = None, device_noise: bool = False):
+        """device_noise (N9): the graph starts with vv_noise_fill into ``x`` from a static key buffer, and ``__call__`` takes the keys
+        (model_spec.noise_keys rows) in place of a noise tensor: a replay for a new request uploads 16 bytes per item, no noise."""
         self.eng, self.B, self.N, self.t_gen_max = eng, int(B), int(N), int(t_gen_max)
+        self.device_noise = bool(device_noise)
+        self.keys = torch.zeros((int(B), 2), dtype=torch.int64, device=eng.device) if self.device_noise else None
         self.seq_host = [int(v) for v in seq_len_host]
         assert len(self.seq_host) == self.B
         self.n_steps = eng.n_steps if n_steps is None else int(n_steps)
@@ -765,6 +811,9 @@ class GraphedSteps:
     def _launch(self):
         e = self.eng
         with e._lock, torch.cuda.device(e.device):
+            if self.device_noise:
+                e._check(e.lib.vv_noise_fill(e.ctx, self.B, self.N, e.spec.n_mel, self.x.data_ptr(), self.seq_len.data_ptr(), self.keys.data_ptr(),
+                                             0, e._stream()))
             e._check(e.lib.vv_transformer_steps_into(e.ctx, self.B, self.N, self.seq_len.data_ptr(), self._host, self.x.data_ptr(),
                                                      self.cat.data_ptr(), self.cat_drop.data_ptr(), e.rope[0].data_ptr(), e.rope[1].data_ptr(),
                                                      e.rope[2].data_ptr(), e.rope[3].data_ptr(), 0, self.n_steps, self.ws.data_ptr(), self.ws.numel(),
@@ -774,13 +823,16 @@ class GraphedSteps:
                                           self.ws.data_ptr(), self.ws.numel(), e._stream()))
 
     def __call__(self, noise: torch.Tensor, pre: Dict[str, torch.Tensor]):
-        """noise [B,N,n_mel] and ``pre`` (HipSynth.preprocess of the same batch) -> (x, pcm, pcm_len): views of the static buffers,
-        valid until the next call."""
+        """noise [B,N,n_mel] -- with ``device_noise`` the B keys instead -- and ``pre`` (HipSynth.preprocess of the same batch) ->
+        (x, pcm, pcm_len): views of the static buffers, valid until the next call."""
         with self.eng._lock:                             # the setters take the same lock: the check and the replay see one state
             if self.stale():
                 raise RuntimeError("captured Euler-step graph is stale: the engine's time grid, rope mode or an option changed after the "
                                    "capture (set_nfe / set_rope_theta / set_option); capture again with HipSynth.capture_steps")
-            self.x.copy_(noise)
+            if self.device_noise:
+                self.keys.copy_(self.eng.noise_keys_device(noise))
+            else:
+                self.x.copy_(noise)
             self.cat.copy_(pre["cat_mel_text"])
             self.cat_drop.copy_(pre["cat_mel_text_drop"])
             self.ref_len.copy_(pre["ref_signal_len"])
