@@ -482,6 +482,48 @@ VV_API size_t vv_normalize_scratch_bytes(int n_clips, int64_t total_len);
 VV_API int vv_normalize_clips(vv_ctx* ctx, const float* x, const int64_t* offsets, int n_clips, int64_t max_len, void* scratch,
                        int16_t* out, void* stream);
 
+/* ---- N10 the output stage on the device: what the engine did on the host after vv_decode.  No call here synchronises;
+ * descriptor rows live in device memory, so the library cannot check them: the CALLER validates them before the call
+ * (runtime.HipSynth.join_chunks / pcm_resample / pcm_encode do).  The kernels clamp every index all the same. */
+#define VV_JOIN_MAX_N 24576   /* the largest junction: the walk keeps that many joined samples in LDS */
+/* AudioProcessor.concatenate_with_crossfade_improved(waves, cross_fade_duration, sample_rate) (reference core/audio_processor.py:122-192)
+ * for R requests in one call, bit for bit: a request of one chunk is copied untouched; otherwise every raw chunk that holds a 32767 sample
+ * becomes (int16)(x * (26214.0 / 32767)) (float64, truncated), and junction by junction, with n = min(int(cross_fade_duration *
+ * sample_rate), joined so far, len(next)) > 0: rms = sqrtf(mean_f32(x_f32 * x_f32)) of the last n joined samples and of the first n of the
+ * next chunk in numpy's float32 summation order; if both > 100 the WHOLE next chunk becomes (int16)(int32)(x_f32 * clamp(rms_prev /
+ * rms_next, 0.7f, 1.5f)) (low 16 bits kept: a wrap is allowed, as numpy on x86); mixed[k] = (int16)(tail[k] * c[k] + head[k] * s[k]) in
+ * float64.  The host owns every length, so it hands over
+ *   chunk_rows  n_chunks x 8 int64 {src_off, len, pos, n, fin, tab_off, repair, req}: the chunk is pcm[src_off, +len) (a row of vv_decode's
+ *               plane); pos = the position of its first sample in its request's joined signal (joined length before it - n); n = its
+ *               junction size (0 for a request's first chunk and where cross_fade_duration <= 0); fin = its samples are final at positions
+ *               < fin = the smallest pos of the request's later chunks (INT64_MAX for the last); tab_off = offset in doubles of its
+ *               c[n] | s[n] tables in fade; repair = 1 in a request of two or more chunks; req = the index of its request
+ *   req_rows    R x 4 int64 {chunk0, n_chunks, out_off, joined_len}: consecutive chunk rows; the result is out[out_off, +joined_len)
+ *   fade        float64: per distinct n, c = cos(linspace(0, pi / 2, n)) ** 2 then s = sin(..) ** 2, computed by numpy ON THE HOST (the device
+ *               never evaluates cos: a last-bit difference would flip a truncation)
+ *   max_n, max_len   the largest n and len of the rows;  ws = 8 * n_chunks bytes of device scratch (8-byte aligned).
+ * Every output sample of a request is written exactly once, nothing outside its slice, no atomics.  -22, and nothing is launched, for a
+ * null pointer, R < 1, n_chunks < R, out not 16-byte aligned, max_n > VV_JOIN_MAX_N.  chunk_rows_host / req_rows_host (optional, both or
+ * neither) = the same rows in HOST memory: the call then checks them itself and also returns -22 for a row that does not fit a buffer, an
+ * n above max_n, and a chunk of len <= 0 inside a request of two or more chunks (the reference raises on an empty chunk in
+ * fix_clipped_audio). */
+VV_API int vv_join_chunks(vv_ctx* ctx, const int16_t* pcm, int64_t n_pcm, const int64_t* chunk_rows, const int64_t* chunk_rows_host,
+                          int n_chunks, const int64_t* req_rows, const int64_t* req_rows_host, int R, const double* fade, int64_t n_fade,
+                          int max_n, int64_t max_len, int16_t* out, int64_t n_out, void* ws, void* stream);
+/* Output rate: batched int16 -> int16 polyphase FIR, y[m] = clamp(rint(sum_i x[i] * taps[(m + skip) * down - i * up]), -32768, 32767), one
+ * float64 fma chain over ascending i (the arithmetic of vv_resample_poly), rint = ties to even.  taps = host-designed low-pass already scaled
+ * by `up` (f64, device; voice_bank.resample_design).  rows = n_rows x 6 int64 {src_off, n_in, dst_off, n_out, m0, i0}: the row writes outputs
+ * m0 ... m0 + n_out - 1 of a signal whose samples i0 ... i0 + n_in - 1 are x[src_off, +n_in); samples outside that range contribute zero (the
+ * caller guarantees that the filter reaches none of them inside the signal).  A whole clip: m0 = i0 = 0, n_out = ceil(n_in * up / down).
+ * max_out = the largest n_out.  NOT the reference's arithmetic: the reference has no output rate. */
+VV_API int vv_pcm_resample(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_out, const double* taps,
+                           int n_taps, int up, int down, int skip, int16_t* y, int64_t n_y, void* stream);
+/* G.711: int16 -> uint8, kind 1 = mu-law, 2 = A-law, bit-exact to audioop.lin2ulaw(data, 2) / audioop.lin2alaw(data, 2) for all 65,536
+ * inputs (the segment arithmetic of CPython's Modules/audioop.c).  rows = n_rows x 3 int64 {src_off, n, dst_off}; max_n = the largest n;
+ * y 8-byte aligned. */
+VV_API int vv_pcm_encode(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_n, int kind, uint8_t* y,
+                         int64_t n_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

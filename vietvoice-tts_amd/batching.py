@@ -18,7 +18,8 @@ Round 4: the loop is a three-stage pipeline instead of collect -> GPU -> cross-f
              everything that arrived during the previous one: under load the collect window is the GPU time of the batch in
              front, not ``max_wait_ms``.
   gpu        one ragged batch after the other through ``TTSEngine._synthesize_device`` (serialised by the engine lock).
-  finisher   per-request cross-fade (host numpy, audio_processor.py:122-192) and Future completion, off the GPU stage's path.
+  finisher   per-request cross-fade (host numpy, audio_processor.py:122-192; with the device output stage ONE finish_output call joins
+             every request of the batch in HBM) and Future completion, off the GPU stage's path.
 
 ``overlap=False`` keeps the three stages on one thread in the old order (the A/B baseline and the equality test).
 """
@@ -263,10 +264,13 @@ class BatchingFrontend:
         t0 = time.perf_counter()
         with eng._lock:
             if eng.model_session_manager.engine is not None:
+                dev_out = eng._device_output()      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
                 if batch.keys:
-                    waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
+                    waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
+                                                   device_out=dev_out)
                 else:
-                    waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals)
+                    waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
+                                                   device_out=dev_out)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0
@@ -298,11 +302,20 @@ class BatchingFrontend:
                 if not fut.done():
                     fut.set_exception(RuntimeError(f"Speech synthesis failed: {err}"))
             return
+        if isinstance(waves, tuple):          # device output stage: (device PCM, spans) -- one finish_output call for the whole batch
+            try:
+                finals = eng._finish_device(waves, [n for _f, n in batch.plans])
+            except Exception as e:        # noqa: BLE001
+                self._fail(batch, e)
+                return
+            for (fut, _n), final in zip(batch.plans, finals):
+                fut.set_result((final, time.time() - batch.t0))
+                self.requests_done += 1
+            return
         pos = 0
         for fut, n in batch.plans:
             try:
-                final = eng.audio_processor.concatenate_with_crossfade_improved(waves[pos: pos + n], eng.config.cross_fade_duration,
-                                                                                eng.config.sample_rate)
+                final = eng._finish_host(waves[pos: pos + n])
                 fut.set_result((final, time.time() - batch.t0))
             except Exception as e:        # noqa: BLE001
                 fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))

@@ -134,6 +134,94 @@ def _resample_polyphase(x: np.ndarray, src: int, dst: int) -> np.ndarray:
     return resample_poly(x.astype(np.float64), dst // g, src // g).astype(np.float32)
 
 
+OUTPUT_ENCODINGS = ("pcm16", "ulaw", "alaw")      # ModelConfig.output_encoding; G.711 = WAVE format tags 7 (mu-law) / 6 (A-law)
+_WAVE_TAG = {"pcm16": 1, "alaw": 6, "ulaw": 7}
+_DESIGNS = {}
+
+
+def output_design(src: int, dst: int):
+    """(taps f64, up, down, skip) of the output-rate filter: voice_bank.resample_design(src, dst), designed once per rate pair."""
+    key = (int(src), int(dst))
+    if key not in _DESIGNS:
+        from ..voice_bank import resample_design
+        _DESIGNS[key] = resample_design(*key)
+    return _DESIGNS[key]
+
+
+def resample_len(n_in: int, up: int, down: int) -> int:
+    """Samples scipy.signal.resample_poly returns for n_in input samples: ceil(n_in * up / down)."""
+    return -(-int(n_in) * int(up) // int(down))
+
+
+def resample_rows(x: np.ndarray, taps: np.ndarray, up: int, down: int, skip: int, m0: int, i0: int, n_out: int) -> np.ndarray:
+    """Host mirror of vv_pcm_resample for one descriptor row: outputs m0 ... m0 + n_out - 1 of a signal whose samples
+    i0 ... i0 + len(x) - 1 are ``x`` (int16); everything else contributes zero.  y[m] = clamp(rint(sum_i x[i] * taps[(m + skip) * down
+    - i * up])), a float64 sum over ascending i (the kernel's order; it fuses each multiply-add, numpy rounds the product first: only a
+    value on a tie can differ)."""
+    x64 = np.asarray(x).reshape(-1).astype(np.float64)
+    n_in, n_taps = x64.size, int(taps.size)
+    if n_out <= 0:
+        return np.zeros(0, np.int16)
+    pos = (np.arange(m0, m0 + n_out, dtype=np.int64) + skip) * down
+    i_hi = pos // up
+    acc = np.zeros(n_out, np.float64)
+    for k in range((n_taps + up - 1) // up, -1, -1):           # i = i_hi - k: ascending i
+        i = i_hi - k
+        t = pos - i * up
+        ok = (t >= 0) & (t < n_taps) & (i >= i0) & (i < i0 + n_in)
+        if not ok.any():
+            continue
+        xv = x64[np.clip(i - i0, 0, max(n_in - 1, 0))] if n_in else np.zeros(n_out)
+        acc = acc + np.where(ok, xv * taps[np.clip(t, 0, n_taps - 1)], 0.0)
+    return np.clip(np.rint(acc), -32768, 32767).astype(np.int16)
+
+
+def resample_output(x: np.ndarray, src: int, dst: int) -> np.ndarray:
+    """int16 PCM at ``src`` Hz -> int16 at ``dst`` Hz through the band-limited polyphase FIR of the voice bank (Kaiser beta 5, half length
+    10 * max(up, down)): the host mirror of the device output stage.  NOT the reference's arithmetic (it has no output rate)."""
+    x = np.asarray(x).reshape(-1)
+    if int(src) == int(dst) or x.size == 0:
+        return x
+    taps, up, down, skip = output_design(src, dst)
+    return resample_rows(x, taps, up, down, skip, 0, 0, resample_len(x.size, up, down))
+
+
+def lin2ulaw(x: np.ndarray) -> np.ndarray:
+    """int16 -> uint8 G.711 mu-law, audioop.lin2ulaw(data, 2): the segment arithmetic of CPython's Modules/audioop.c on sample >> 2
+    (bias 0x21, clip 8159)."""
+    v = np.asarray(x).reshape(-1).astype(np.int32) >> 2
+    mask = np.where(v < 0, 0x7F, 0xFF)
+    v = np.minimum(np.abs(v), 8159) + 0x21
+    seg = np.zeros_like(v)
+    for k in range(8):
+        seg += v > ((0x40 << k) - 1)                       # seg_uend = 0x3F, 0x7F, ... 0x1FFF
+    code = np.where(seg >= 8, 0x7F, (seg << 4) | ((v >> (np.minimum(seg, 7) + 1)) & 0xF))
+    return (code ^ mask).astype(np.uint8)
+
+
+def lin2alaw(x: np.ndarray) -> np.ndarray:
+    """int16 -> uint8 G.711 A-law, audioop.lin2alaw(data, 2): the same source's st_linear2alaw on sample >> 3."""
+    v = np.asarray(x).reshape(-1).astype(np.int32) >> 3
+    mask = np.where(v >= 0, 0xD5, 0x55)
+    v = np.where(v < 0, -v - 1, v)
+    seg = np.zeros_like(v)
+    for k in range(8):
+        seg += v > ((0x20 << k) - 1)                       # seg_aend = 0x1F, 0x3F, ... 0xFFF
+    s7 = np.minimum(seg, 7)
+    code = np.where(seg >= 8, 0x7F, (seg << 4) | (np.where(seg < 2, v >> 1, v >> s7) & 0xF))
+    return (code ^ mask).astype(np.uint8)
+
+
+def encode_output(x: np.ndarray, encoding: str) -> np.ndarray:
+    if encoding == "pcm16":
+        return x
+    if encoding == "ulaw":
+        return lin2ulaw(x)
+    if encoding == "alaw":
+        return lin2alaw(x)
+    raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+
+
 class AudioProcessor:
     """Static helpers, same names and semantics as the reference class."""
 
@@ -189,11 +277,30 @@ class AudioProcessor:
         return audio
 
     @staticmethod
-    def save_audio(audio: np.ndarray, file_path: str, sample_rate: int) -> None:
+    def _g711_wav(flat: np.ndarray, sample_rate: int, encoding: str) -> bytes:
+        """RIFF/WAVE bytes of G.711 data: format tag 7 (mu-law) / 6 (A-law), 8 bits, an 18-byte fmt chunk and a fact chunk."""
+        payload = np.asarray(flat, dtype=np.uint8).tobytes()
+        pad = b"\0" * (len(payload) & 1)
+        fmt = struct.pack("<HHIIHHH", _WAVE_TAG[encoding], 1, sample_rate, sample_rate, 1, 8, 0)
+        fact = struct.pack("<I", len(payload))
+        body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"fact" + struct.pack("<I", 4) + fact + \
+            b"data" + struct.pack("<I", len(payload)) + payload + pad
+        return b"RIFF" + struct.pack("<I", len(body)) + body
+
+    @staticmethod
+    def save_audio(audio: np.ndarray, file_path: str, sample_rate: int, encoding: str = "pcm16") -> None:
         if audio.size == 0:
             raise ValueError("Cannot save empty audio.")
+        if encoding not in OUTPUT_ENCODINGS:
+            raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
         Path(file_path).parent.mkdir(parents=True, exist_ok=True)
         flat = np.asarray(audio).reshape(-1)
+        if encoding != "pcm16":                      # already companded (uint8) by the output stage
+            if flat.dtype != np.uint8:
+                raise ValueError(f"{encoding} audio must be uint8 G.711 codes")
+            with open(file_path, "wb") as fh:
+                fh.write(AudioProcessor._g711_wav(flat, sample_rate, encoding))
+            return
         if flat.dtype != np.int16:
             if np.issubdtype(flat.dtype, np.floating):
                 flat = np.clip(flat * 32768.0 if np.max(np.abs(flat)) <= 1.0 else flat, -32768, 32767)
@@ -206,7 +313,11 @@ class AudioProcessor:
             fh.write(b"data" + struct.pack("<I", len(payload)) + payload)
 
     @staticmethod
-    def to_wav_bytes(audio: np.ndarray, sample_rate: int) -> bytes:
+    def to_wav_bytes(audio: np.ndarray, sample_rate: int, encoding: str = "pcm16") -> bytes:
+        if encoding != "pcm16":
+            if encoding not in OUTPUT_ENCODINGS:
+                raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+            return AudioProcessor._g711_wav(np.asarray(audio).reshape(-1), sample_rate, encoding)
         buf = io.BytesIO()
         flat = np.asarray(audio).reshape(-1).astype("<i2")
         buf.write(b"RIFF" + struct.pack("<I", 36 + flat.nbytes) + b"WAVEfmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16))
@@ -308,3 +419,56 @@ class CrossfadeStream:
         keep = 0 if last else min(self.cf, len(joined))       # the next junction may rewrite at most the last cf samples
         out, self.held = joined[: len(joined) - keep], joined[len(joined) - keep:]
         return np.ascontiguousarray(out)
+
+
+class OutputStream:
+    """Output rate and encoding for a STREAM of final 24 kHz blocks (``synthesize_stream``): carries the position (m0, i0) and the input
+    history the filter still needs, so that the concatenation of the blocks it returns equals the buffered result bit for bit --
+    every output sample is the same ascending float64 sum over the same input samples, whichever block delivers it.
+
+    ``resample(x, m0, i0, n_out)`` and ``encode(y)`` are the two back ends: the host mirrors above, or the device kernels
+    (HipSynth.output_stream_backends).  ``push`` returns what became final, ``flush`` the rest (inputs past the end are zeros)."""
+
+    def __init__(self, src: int, dst, encoding: str = "pcm16", resample=None, encode=None):
+        self.rate = None if dst is None or int(dst) == int(src) else int(dst)
+        self.encoding = encoding
+        if self.rate is not None:
+            self.taps, self.up, self.down, self.skip = output_design(src, self.rate)
+            self._resample = resample or (lambda x, m0, i0, n: resample_rows(x, self.taps, self.up, self.down, self.skip, m0, i0, n))
+        self._encode = encode or (lambda y: encode_output(y, encoding))
+        self.hist = np.zeros(0, np.int16)     # input samples i0 ... n_seen - 1
+        self.i0 = 0
+        self.n_seen = 0
+        self.m_done = 0
+
+    def _i_lo(self, m: int) -> int:
+        lo = (m + self.skip) * self.down - int(self.taps.size) + 1
+        return 0 if lo <= 0 else -(-lo // self.up)
+
+    def _emit(self, m_end: int) -> np.ndarray:
+        n_out = m_end - self.m_done
+        if n_out <= 0:
+            return np.zeros(0, np.int16)
+        y = self._resample(self.hist, self.m_done, self.i0, n_out)
+        self.m_done = m_end
+        keep_from = min(self._i_lo(self.m_done), self.n_seen)      # the oldest sample the next output reads
+        if keep_from > self.i0:
+            self.hist, self.i0 = self.hist[keep_from - self.i0:], keep_from
+        return y
+
+    def push(self, block: np.ndarray) -> np.ndarray:
+        block = np.asarray(block).reshape(-1)
+        if self.rate is None:
+            return self._encode(block) if self.encoding != "pcm16" else block
+        self.hist = np.concatenate([self.hist, block.astype(np.int16, copy=False)])
+        self.n_seen += block.size
+        # outputs whose newest input is in hand: (m + skip) * down // up <= n_seen - 1
+        m_end = max(self.m_done, resample_len(self.n_seen, self.up, self.down) - self.skip)
+        y = self._emit(m_end)
+        return self._encode(y) if self.encoding != "pcm16" else y
+
+    def flush(self) -> np.ndarray:
+        if self.rate is None:
+            return np.zeros(0, np.uint8 if self.encoding != "pcm16" else np.int16)
+        y = self._emit(resample_len(self.n_seen, self.up, self.down))
+        return self._encode(y) if self.encoding != "pcm16" else y

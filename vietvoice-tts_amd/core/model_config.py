@@ -68,6 +68,11 @@ class ModelConfig:
                                             # outside it the unconditional branch is not computed.  None = guidance everywhere
     noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
                                             # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
+    output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
+                                            # function); "device" = vv_join_chunks in HBM, bit for bit the same samples, one copy of the final bytes
+    output_sample_rate: Optional[int] = None   # None = sample_rate; else the output is rate-converted (band-limited polyphase FIR, vv_pcm_resample)
+    output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode).  A rate or an encoding runs on the
+                                            # device on the HIP engine, through the host mirrors on injected sessions
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -86,6 +91,16 @@ class ModelConfig:
         from ..model_spec import NOISE_SOURCES
         if self.noise_source not in NOISE_SOURCES:
             raise ValueError(f"noise_source must be one of {list(NOISE_SOURCES)}")
+        if self.output_stage not in ("host", "device"):
+            raise ValueError("output_stage must be 'host' or 'device'")
+        if self.output_encoding not in ("pcm16", "ulaw", "alaw"):
+            raise ValueError("output_encoding must be one of ['pcm16', 'ulaw', 'alaw']")
+        if self.output_sample_rate is not None:
+            if isinstance(self.output_sample_rate, bool) or int(self.output_sample_rate) != self.output_sample_rate:
+                raise ValueError("output_sample_rate must be an integer number of Hz or None")
+            self.output_sample_rate = int(self.output_sample_rate)
+            if not 4000 <= self.output_sample_rate <= 192000:
+                raise ValueError("output_sample_rate must be between 4000 and 192000 Hz")
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         self.validate_paths()

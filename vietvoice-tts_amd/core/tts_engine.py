@@ -154,7 +154,44 @@ class TTSEngine:
         return waves
 
     # ------------------------------------------------------------------ device-resident batched path
-    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None) -> List[np.ndarray]:
+    # ------------------------------------------------------------------ the output stage (N10)
+    def _output_options(self) -> Tuple[Optional[int], str]:
+        """(output rate or None when it is the model's own, encoding)."""
+        cfg = self.config
+        rate = cfg.output_sample_rate
+        return (None if rate is None or int(rate) == int(cfg.sample_rate) else int(rate)), cfg.output_encoding
+
+    @property
+    def output_rate(self) -> int:
+        return self._output_options()[0] or self.config.sample_rate
+
+    def _device_output(self) -> bool:
+        """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
+        rate or an encoding is set.  False = today's path: one copy per chunk group, the numpy join."""
+        rate, enc = self._output_options()
+        return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16")
+
+    def _finish_host(self, waves) -> np.ndarray:
+        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of the output rate / encoding."""
+        from .audio_processor import encode_output, resample_output
+        final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
+        rate, enc = self._output_options()
+        if rate is not None:
+            final = resample_output(final, self.config.sample_rate, rate)
+        return encode_output(final, enc) if enc != "pcm16" else final
+
+    def _finish_device(self, dev_pcm, counts) -> List[np.ndarray]:
+        """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
+        one HipSynth.finish_output call (join, rate, encoding in HBM; one device-to-host copy)."""
+        pcm, spans = dev_pcm
+        plans, pos = [], 0
+        for n in counts:
+            plans.append(spans[pos: pos + n])
+            pos += n
+        rate, enc = self._output_options()
+        return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc)
+
+    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False):
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
         clips may differ per item (cross-request batches).  One ragged GPU batch per ``max_batch_chunks`` items.
         noise_blocks: optional pre-drawn (N_i, n_mel) fp32 tensors, one per item (the batching front end draws them from
@@ -164,7 +201,9 @@ class TTSEngine:
         next call serial); explicit noise_blocks still win.
         cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model).
         cfg_intervals: optional guidance interval (lo, hi) per item (None entries = ``config.cfg_interval``).  An item is guided at the
-        evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed."""
+        evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed.
+        device_out (N10): nothing is copied to the host; returns (int16 device tensor, [(offset, samples) per item]) -- the planes of the
+        chunk groups back to back and each item's span in them, the lengths from the host's own frame counts (no readback)."""
         import torch
         m = self.model_session_manager
         eng, spec = m.engine, m.spec
@@ -188,6 +227,7 @@ class TTSEngine:
             noise_keys = None
             noise_blocks = [torch.randn((n, spec.n_mel), generator=m.noise_gen, dtype=torch.float32) for n in seq_all]
         waves: List[Optional[np.ndarray]] = [None] * n_items
+        planes, spans, plane_base = [], [None] * n_items, 0
         # the device packs ragged rows, so padding is free for the acoustic stages; sorting by length still puts similar
         # lengths into the same batch when a text has more chunks than max_batch_chunks (vocoder planes are padded)
         groups = []
@@ -256,9 +296,18 @@ class TTSEngine:
                                                               None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
                                                               audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys)
+            if device_out:
+                pcm = pcm.clone() if self.config.use_hip_graph else pcm.contiguous()      # a captured graph's output buffer is replayed over
+                for i, j in enumerate(idx):
+                    spans[j] = (plane_base + i * pcm.shape[1], spec.pcm_samples(int(seq[i] - ref_frames[i])))
+                planes.append(pcm.reshape(-1))
+                plane_base += pcm.numel()
+                continue
             pcm, pcm_len = pcm.cpu().numpy(), pcm_len.cpu().numpy()
             for i, j in enumerate(idx):
                 waves[j] = pcm[i, : pcm_len[i]].reshape(1, 1, -1)
+        if device_out:
+            return (planes[0] if len(planes) == 1 else torch.cat(planes)), spans
         return waves
 
     # ------------------------------------------------------------------ public API
@@ -275,14 +324,18 @@ class TTSEngine:
                 self._last_plan = [int(i[2][0]) for i in inputs_list]
                 if self.model_session_manager.engine is not None:
                     keys = self.model_session_manager.take_noise_keys(len(inputs_list)) if self._device_noise() else None
-                    waves = self._synthesize_device(inputs_list, noise_keys=keys)
+                    if self._device_output():
+                        dev_pcm = self._synthesize_device(inputs_list, noise_keys=keys, device_out=True)
+                        waves, final_wave = None, self._finish_device(dev_pcm, [len(inputs_list)])[0]
+                    else:
+                        waves = self._synthesize_device(inputs_list, noise_keys=keys)
                 else:
                     waves = self._synthesize_sessions(inputs_list)
-            final_wave = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration,
-                                                                                  self.config.sample_rate)
+            if waves is not None:
+                final_wave = self._finish_host(waves)
             generation_time = time.time() - start
             if output_path:
-                self.audio_processor.save_audio(final_wave, output_path, self.config.sample_rate)
+                self.audio_processor.save_audio(final_wave, output_path, self.output_rate, self.config.output_encoding)
                 logger.info("Audio saved to: %s", output_path)
             return final_wave, generation_time
         except Exception as e:
@@ -291,7 +344,7 @@ class TTSEngine:
     def synthesize_stream(self, text: str, gender: Optional[str] = None, group: Optional[str] = None, area: Optional[str] = None,
                           emotion: Optional[str] = None, sample_iteration: Optional[int] = None,
                           reference_audio: Optional[str] = None, reference_text: Optional[str] = None, chunks_per_step: int = 1):
-        """Generator of int16 PCM blocks: audio is emitted as soon as a group of ``chunks_per_step``
+        """Generator of PCM blocks (int16 at the output rate, or uint8 G.711 codes): audio is emitted as soon as a group of ``chunks_per_step``
         chunks is synthesised instead of after the whole text (the reference buffers everything, api/app.py:59-65).
         Overlap-save: the improved cross-fade only rewrites the last ``cross_fade_duration`` of what has been joined
         so far (audio_processor.py:122-192), so everything before that tail is final and can be yielded.  The joiner
@@ -308,6 +361,15 @@ class TTSEngine:
             self._last_plan = [int(i[2][0]) for i in inputs_list]
             from .audio_processor import CrossfadeStream
             joiner = CrossfadeStream(len(inputs_list), self.config.cross_fade_duration, self.config.sample_rate)
+            # N10: a rate or an encoding is applied to every final block by an OutputStream that carries the filter's position and history
+            # (on the HIP engine through the device kernels, blocks re-uploaded), so that the blocks still add up to synthesize()'s result
+            rate, enc = self._output_options()
+            ostream = None
+            if rate is not None or enc != "pcm16":
+                from .audio_processor import OutputStream
+                eng = self.model_session_manager.engine
+                backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
+                ostream = OutputStream(self.config.sample_rate, rate, enc, *backends)
             step = max(1, int(chunks_per_step))
             for lo in range(0, len(inputs_list), step):
                 with self._lock:
@@ -317,6 +379,12 @@ class TTSEngine:
                         waves = self._synthesize_sessions(inputs_list[lo: lo + step])
                 blocks = [joiner.push(w) for w in waves]
                 block = np.concatenate(blocks) if len(blocks) > 1 else blocks[0]
+                if ostream is not None:
+                    block = ostream.push(block)
+                if block.size:
+                    yield block
+            if ostream is not None:
+                block = ostream.flush()
                 if block.size:
                     yield block
         except Exception as e:
@@ -370,11 +438,15 @@ class TTSEngine:
                                                torch.from_numpy(plan.keep.reshape(1, -1)).to(dev),
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
                                                guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys)
-                wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
+                if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
+                    n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
+                    wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options())[0]
+                else:
+                    wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:
                 raise RuntimeError(f"Speech editing failed: {str(e)}") from e
         if output_path:
-            self.audio_processor.save_audio(wave, output_path, sr)
+            self.audio_processor.save_audio(wave, output_path, self.output_rate, cfg.output_encoding)
             logger.info("Audio saved to: %s", output_path)
         return wave, time.time() - start
 

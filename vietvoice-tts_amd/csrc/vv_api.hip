@@ -11,7 +11,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.3 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.4 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -593,6 +593,63 @@ int vv_noise_fill(vv_ctx* c, int B, int N, int n_mel, float* x, const int32_t* s
     hipStream_t st = (hipStream_t)stream;
     Prof p(c, VV_PROF_ELEMWISE, 0, (double)B * (12.0 + 4.0 * N * n_mel), st);
     KCHK(c, vvk_noise_fill(x, seq_len, (const unsigned long long*)keys, B, N, n_mel, kind, st, &m__));
+    return 0;
+}
+
+// N10: the output stage.  Every argument the host can see is checked before a launch; a refused call launches nothing.
+int vv_join_chunks(vv_ctx* c, const int16_t* pcm, int64_t n_pcm, const int64_t* chunk_rows, const int64_t* chunk_rows_host, int n_chunks,
+                   const int64_t* req_rows, const int64_t* req_rows_host, int R, const double* fade, int64_t n_fade, int max_n, int64_t max_len,
+                   int16_t* out, int64_t n_out, void* ws, void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (R < 1 || n_chunks < R || !pcm || !chunk_rows || !req_rows || !out || !ws || max_n < 0 || max_n > vvk_join_max_n() || (uintptr_t)out % 16)
+        return c->fail(-22, "vv_join_chunks: bad arguments (1 <= R <= n_chunks; pcm, rows, out, ws not null; out 16-byte aligned; max_n <= %d)",
+                       vvk_join_max_n());
+    if ((chunk_rows_host == nullptr) != (req_rows_host == nullptr)) return c->fail(-22, "vv_join_chunks: host rows come as a pair or not at all");
+    if (chunk_rows_host) {               // the same rows on the host: checked here, before anything is launched
+        for (int r = 0; r < R; ++r) {
+            const int64_t* q = req_rows_host + 4 * (size_t)r;
+            if (q[0] < 0 || q[1] < 1 || q[0] + q[1] > n_chunks || q[2] < 0 || q[3] < 0 || q[2] + q[3] > n_out)
+                return c->fail(-22, "vv_join_chunks: request row %d does not fit the chunk rows or the output", r);
+            for (int64_t k = q[0]; k < q[0] + q[1]; ++k) {
+                const int64_t* w = chunk_rows_host + 8 * (size_t)k;
+                if (w[0] < 0 || w[1] < 0 || w[0] + w[1] > n_pcm || w[2] < 0 || w[3] < 0 || w[3] > max_n || w[1] > max_len || w[7] != r ||
+                    (w[3] > 0 && (w[5] < 0 || w[5] + 2 * w[3] > n_fade)))
+                    return c->fail(-22, "vv_join_chunks: chunk row %lld does not fit the buffers", (long long)k);
+                if (q[1] >= 2 && w[1] <= 0)
+                    return c->fail(-22, "vv_join_chunks: chunk %lld is empty inside a request of %lld chunks", (long long)k, (long long)q[1]);
+            }
+        }
+    }
+    Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * (double)n_out + 96.0 * n_chunks, st);
+    KCHK(c, vvk_join_chunks(pcm, (long long)n_pcm, (const long long*)chunk_rows, n_chunks, (const long long*)req_rows, R, fade, (long long)n_fade,
+                            max_n, (long long)max_len, out, (long long)n_out, ws, st, &m__));
+    return 0;
+}
+
+int vv_pcm_resample(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_out, const double* taps, int n_taps,
+                    int up, int down, int skip, int16_t* y, int64_t n_y, void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rows < 1 || !x || !rows || !taps || !y || n_taps < 1 || up < 1 || down < 1 || skip < 0 || max_out < 0)
+        return c->fail(-22, "vv_pcm_resample: bad arguments (n_rows, n_taps, up, down >= 1; skip, max_out >= 0; no null pointer)");
+    Prof p(c, VV_PROF_ELEMWISE, 2.0 * (double)n_y * (n_taps / up + 1), 2.0 * (double)(n_x + n_y), st);
+    KCHK(c, vvk_pcm_resample(x, (long long)n_x, (const long long*)rows, n_rows, (long long)max_out, taps, n_taps, up, down, skip, y, (long long)n_y,
+                             st, &m__));
+    return 0;
+}
+
+int vv_pcm_encode(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_n, int kind, uint8_t* y, int64_t n_y,
+                  void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rows < 1 || !x || !rows || !y || (kind != 1 && kind != 2) || max_n < 0 || (uintptr_t)y % 8)
+        return c->fail(-22, "vv_pcm_encode: bad arguments (n_rows >= 1; kind 1 = mu-law, 2 = A-law; y 8-byte aligned; no null pointer)");
+    Prof p(c, VV_PROF_ELEMWISE, 0, 2.0 * (double)n_x + (double)n_y, st);
+    KCHK(c, vvk_pcm_encode(x, (long long)n_x, (const long long*)rows, n_rows, (long long)max_n, kind, y, (long long)n_y, st, &m__));
     return 0;
 }
 

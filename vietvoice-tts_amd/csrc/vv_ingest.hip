@@ -14,6 +14,7 @@
 // The polyphase FIR resampler of rounds 2-4 (vv_resample_poly) stays as an explicit opt-in; it is NOT the reference's arithmetic.
 #include "vv_common.h"
 #include "vv_kernels.h"
+#include "vv_np_sum.h"
 
 namespace {
 
@@ -81,23 +82,7 @@ __global__ __launch_bounds__(256) void ingest_pcm_kernel(const unsigned char* __
     }
 }
 
-// ---------------------------------------------------------------- np.mean(float32 array): numpy's summation order
-constexpr int NP_BUF = 8192;          // np.getbufsize(): add.reduce hands the inner loop one buffer at a time
-constexpr int NP_LEAF = 128;          // PW_BLOCKSIZE of numpy's pairwise sum
-constexpr int PW_DEPTH = 7;           // a buffer's tree is at most 7 deep: right child <= n / 2 + 8  ->  8192 / 128 + 16 <= 128
-
-// node (k, p) of the pairwise tree over L elements: its length (0 = does not exist: an ancestor already is a leaf) and start
-__device__ __forceinline__ int pw_node(int L, int k, int p, int& start) {
-    int len = L;
-    start = 0;
-    for (int j = 0; j < k; ++j) {
-        if (len <= NP_LEAF) return 0;
-        const int n2 = (len >> 1) & ~7;
-        if ((p >> (k - 1 - j)) & 1) { start += n2; len -= n2; } else len = n2;
-    }
-    return len;
-}
-
+// ---------------------------------------------------------------- np.mean(float32 array): numpy's summation order (vv_np_sum.h)
 __device__ __forceinline__ long long chunk_slot0(const long long* __restrict__ off, int clip) { return off[clip] / NP_BUF + clip; }
 
 // chunk_sum[slot0(clip) + c] = pairwise sum of x[off[clip] + c * 8192 ...), exactly as numpy's FLOAT_pairwise_sum orders it
@@ -107,44 +92,11 @@ __global__ __launch_bounds__(256) void clip_chunk_sum_kernel(const float* __rest
     const long long a = off[clip], n = off[clip + 1] - a;
     const long long n_chunks = (n + NP_BUF - 1) / NP_BUF;
     __shared__ float v[1 << PW_DEPTH];
-    const int lane = threadIdx.x & 7;
     for (long long c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const float* xc = x + a + c * NP_BUF;
         const int L = (int)((n - c * NP_BUF) < NP_BUF ? (n - c * NP_BUF) : NP_BUF);
-        for (int it = 0; it < 4; ++it) {
-            const int slot = it * 32 + (threadIdx.x >> 3);                           // 7 path bits, most significant first
-            int len = L, start = 0, k = 0;
-            for (; k < PW_DEPTH && len > NP_LEAF; ++k) {
-                const int n2 = (len >> 1) & ~7;
-                if ((slot >> (PW_DEPTH - 1 - k)) & 1) { start += n2; len -= n2; } else len = n2;
-            }
-            const bool owner = (slot & ((1 << (PW_DEPTH - k)) - 1)) == 0;            // a leaf at depth k belongs to the slot with zero low bits
-            if (!owner) len = 0;
-            float r = 0.f;
-            const int body = len - (len & 7);
-            if (len >= 8) {                                                          // r[lane] = a[lane] + a[8 + lane] + ...
-                r = xc[start + lane];
-                for (int i = 8; i < body; i += 8) r += xc[start + i + lane];
-            }
-            r += __shfl_xor(r, 1);                                                   // (r0 + r1), (r2 + r3), ...
-            r += __shfl_xor(r, 2);                                                   // ((r0 + r1) + (r2 + r3)), ...
-            r += __shfl_xor(r, 4);
-            if (lane == 0) {
-                for (int i = (len >= 8 ? body : 0); i < len; ++i) r += xc[start + i];   // the tail (or a whole leaf of < 8) in order
-                v[slot] = r;
-            }
-        }
-        __syncthreads();
-        for (int k = PW_DEPTH - 1; k >= 0; --k) {                                    // node = left child + right child, bottom up
-            const int p = threadIdx.x;
-            if (p < (1 << k)) {
-                int st;
-                if (pw_node(L, k, p, st) > NP_LEAF) v[p << (PW_DEPTH - k)] += v[(p << (PW_DEPTH - k)) + (1 << (PW_DEPTH - 1 - k))];
-            }
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) chunk_sum[chunk_slot0(off, clip) + c] = v[0];
-        __syncthreads();
+        const float s = np_buffer_sum([xc](int i) { return xc[i]; }, L, v);
+        if (threadIdx.x == 0) chunk_sum[chunk_slot0(off, clip) + c] = s;
     }
 }
 

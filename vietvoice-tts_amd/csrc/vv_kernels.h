@@ -69,6 +69,15 @@ int vvk_edit_restore(float* x, const float* cat, const uint8_t* keep, int ld_kee
 // N9 start noise on the device (vv_noise.hip): Philox4x32-10 keyed per item, keys [B][2] = {seed, stream} in device memory
 int vvk_noise_fill(float* x, const int* seq_len, const unsigned long long* keys, int B, int N, int n_mel, int kind, hipStream_t st,
                    const char** err);
+// N10 output stage (vv_output.hip): chunk join (rows validated by the caller), int16 polyphase rate conversion, G.711
+int vvk_join_max_n();
+int vvk_join_chunks(const int16_t* pcm, long long n_pcm, const long long* chunk_rows, int n_chunks, const long long* req_rows, int R,
+                    const double* fade, long long n_fade, int max_n, long long max_len, int16_t* out, long long n_out, void* ws,
+                    hipStream_t st, const char** err);
+int vvk_pcm_resample(const int16_t* x, long long n_x, const long long* rows, int n_rows, long long max_out, const double* taps, int n_taps,
+                     int up, int down, int skip, int16_t* y, long long n_y, hipStream_t st, const char** err);
+int vvk_pcm_encode(const int16_t* x, long long n_x, const long long* rows, int n_rows, long long max_n, int kind, uint8_t* y, long long n_y,
+                   hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

@@ -171,6 +171,11 @@ EXPORTS = {
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_noise_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_edit_restore": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "vv_join_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vv_pcm_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vv_pcm_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -241,6 +246,55 @@ def _dt(s) -> Tuple[int, torch.dtype]:
     if s in ("fp32", "f32", "float32", torch.float32, VV_F32):
         return VV_F32, torch.float32
     raise ValueError(f"acoustic dtype must be bf16 or fp32, got {s!r}")
+
+
+JOIN_MAX_N = 24576            # VV_JOIN_MAX_N of include/vvtts.h: the largest junction vv_join_chunks walks
+_I64_MAX = (1 << 63) - 1
+
+
+def plan_join(requests, cross_fade_duration: float, sample_rate: int, align: int = 8):
+    """The host side of vv_join_chunks: every length is known here, so every junction size, position and final owner is too.
+    requests = per request a list of chunks (src_off, len) in joining order.  Returns (chunk rows WITHOUT tab_off resolved: column 5 holds
+    n, request rows, joined lengths, sorted distinct n, total output samples); request r's result starts at an ``align``-sample boundary.
+    Mirrors AudioProcessor.concatenate_with_crossfade_improved: n = min(int(cross_fade_duration * sample_rate), joined so far, len(next));
+    a request of one chunk is copied untouched; an empty chunk inside a longer request is refused (the reference raises on it in
+    fix_clipped_audio), and so is an empty request."""
+    cf = int(cross_fade_duration * sample_rate) if cross_fade_duration > 0 else 0
+    rows, reqs, lens, out_pos = [], [], [], 0
+    for r, chunks in enumerate(requests):
+        chunks = [(int(a), int(b)) for a, b in chunks]
+        if not chunks:
+            raise ValueError("join_chunks: a request without chunks")
+        c0 = len(rows)
+        if len(chunks) == 1:
+            so, ln = chunks[0]
+            if ln < 0:
+                raise ValueError("join_chunks: negative chunk length")
+            rows.append([so, ln, 0, 0, _I64_MAX, 0, 0, r])
+            total = ln
+        else:
+            total, pos_n = 0, []
+            for k, (so, ln) in enumerate(chunks):
+                if ln <= 0:
+                    raise ValueError("join_chunks: an empty chunk inside a request of two or more chunks")
+                n = min(cf, total, ln) if k else 0
+                if n > JOIN_MAX_N:
+                    raise ValueError(f"join_chunks: a junction of {n} samples, more than {JOIN_MAX_N}")
+                pos_n.append((total - n, n))
+                total = total - n + ln
+            fin = _I64_MAX
+            fins = []
+            for P, _n in reversed(pos_n):          # fin_k = the smallest position of a later chunk
+                fins.append(fin)
+                fin = min(fin, P)
+            fins.reverse()
+            for (so, ln), (P, n), f in zip(chunks, pos_n, fins):
+                rows.append([so, ln, P, n, f, n, 1, r])
+        out_pos = -(-out_pos // align) * align
+        reqs.append([c0, len(chunks), out_pos, total])
+        lens.append(total)
+        out_pos += total
+    return rows, reqs, lens, sorted({row[3] for row in rows if row[3] > 0}), out_pos
 
 
 class HipSynth:
@@ -616,6 +670,176 @@ class HipSynth:
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
+
+    # ------------------------------------------------------------------ the output stage (N10): join, output rate, G.711
+    def _fade_tables(self, ns):
+        """c = cos(linspace(0, pi / 2, n)) ** 2 | s = sin(..) ** 2 per distinct n, computed by numpy on the HOST (the expression of the
+        reference's mix) and kept in one float64 device buffer: -> (buffer, {n: offset in doubles})."""
+        import numpy as np
+        cache = self.__dict__.setdefault("_fade_cache", {"off": {}, "host": [], "dev": None, "size": 0})
+        new = [n for n in ns if n not in cache["off"]]
+        if new:
+            if cache["size"] + 2 * sum(new) > (1 << 22):       # 32 MB of tables: start over
+                cache.update(off={}, host=[], dev=None, size=0)
+                new = list(ns)
+            for n in new:
+                theta = np.linspace(0, np.pi / 2, n)
+                cache["off"][n] = cache["size"]
+                cache["host"] += [np.cos(theta) ** 2, np.sin(theta) ** 2]
+                cache["size"] += 2 * n
+            cache["dev"] = torch.from_numpy(np.concatenate(cache["host"])).to(self.device)
+        if cache["dev"] is None:
+            cache["dev"] = torch.zeros(2, dtype=torch.float64, device=self.device)
+        return cache["dev"], cache["off"]
+
+    def join_chunks(self, pcm: torch.Tensor, requests, cross_fade_duration: float, sample_rate: int, out: Optional[torch.Tensor] = None,
+                    out_base: int = 0):
+        """AudioProcessor.concatenate_with_crossfade_improved for R requests in one call (vv_join_chunks), bit for bit.
+        pcm int16 on the device (vv_decode's plane, taken flat); requests = per request the (src_off, len) spans of its chunks in joining
+        order.  -> (out int16 flat, offsets, lengths): request r is out[offsets[r] : offsets[r] + lengths[r]].  out (optional) = an
+        existing flat int16 buffer, the results then start out_base samples into it (out_base % 8 == 0).  The rows are planned and
+        validated here, on the host, before anything is launched; the call never synchronises."""
+        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
+        n_pcm = pcm.numel()
+        rows, reqs, lens, ns, total = plan_join(requests, cross_fade_duration, sample_rate)
+        if out_base < 0 or out_base % 8:
+            raise ValueError("join_chunks: out_base must be a non-negative multiple of 8 samples")
+        for row in rows:
+            if row[0] < 0 or row[0] + row[1] > n_pcm:
+                raise ValueError(f"join_chunks: chunk ({row[0]}, {row[1]}) does not fit the {n_pcm} samples of pcm")
+        if total + out_base >= 1 << 40 or len(rows) > 65535:
+            raise ValueError("join_chunks: too many chunks or samples for one call")
+        if out is None:
+            out = torch.empty((max(total + out_base, 8),), dtype=torch.int16, device=self.device)
+        assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.dim() == 1
+        if out.numel() < total + out_base:
+            raise ValueError(f"join_chunks: out holds {out.numel()} samples, {total + out_base} are needed")
+        fade, off = self._fade_tables(ns)
+        for row in rows:
+            row[5] = off[row[3]] if row[3] > 0 else 0
+        for rq in reqs:
+            rq[2] += out_base
+        rows_h, reqs_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8), torch.tensor(reqs, dtype=torch.int64).reshape(-1, 4)
+        rows_d, reqs_d = rows_h.to(self.device), reqs_h.to(self.device)
+        ws = torch.empty((2 * len(rows),), dtype=torch.int32, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_join_chunks(self.ctx, pcm.data_ptr(), n_pcm, rows_d.data_ptr(), rows_h.data_ptr(), len(rows),
+                                                reqs_d.data_ptr(), reqs_h.data_ptr(), len(reqs), fade.data_ptr(), fade.numel(), max(ns, default=0), max(r[1] for r in rows), out.data_ptr(),
+                                                out.numel(), ws.data_ptr(), self._stream()))
+        return out, [rq[2] for rq in reqs], lens
+
+    def _output_taps(self, src: int, dst: int):
+        from .core.audio_processor import output_design
+        cache = self.__dict__.setdefault("_out_taps", {})
+        if (src, dst) not in cache:
+            taps, up, down, skip = output_design(src, dst)
+            cache[(src, dst)] = (torch.from_numpy(taps).to(self.device), up, down, skip)
+        return cache[(src, dst)]
+
+    def pcm_resample(self, x: torch.Tensor, rows, src: int, dst: int, n_y: Optional[int] = None) -> torch.Tensor:
+        """Output rate (vv_pcm_resample): x int16 flat on the device at ``src`` Hz, rows = HOST rows {src_off, n_in, dst_off, n_out, m0, i0}
+        (include/vvtts.h) -> int16 [n_y] at ``dst`` Hz through voice_bank.resample_design(src, dst).  A whole clip is m0 = i0 = 0 and
+        n_out = ceil(n_in * up / down).  The rows are validated here (in range of both buffers, disjoint on the output)."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous()
+        if int(src) == int(dst):
+            raise ValueError("pcm_resample: equal rates need no launch")
+        taps, up, down, skip = self._output_taps(int(src), int(dst))
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) != 6 for r in rows):
+            raise ValueError("pcm_resample: rows of 6 entries {src_off, n_in, dst_off, n_out, m0, i0}")
+        n_x = x.numel()
+        n_y = max((r[2] + r[3] for r in rows), default=0) if n_y is None else int(n_y)
+        spans = []
+        for so, n_in, do, n_out, m0, i0 in rows:
+            if min(so, n_in, do, n_out, m0, i0) < 0 or so + n_in > n_x or do + n_out > n_y or (m0 + n_out + skip) * down >= 1 << 62:
+                raise ValueError(f"pcm_resample: row {[so, n_in, do, n_out, m0, i0]} does not fit the buffers ({n_x} in, {n_y} out)")
+            spans.append((do, do + n_out))
+        spans.sort()
+        if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+            raise ValueError("pcm_resample: rows overlap on the output")
+        y = torch.empty((max(n_y, 1),), dtype=torch.int16, device=self.device)
+        d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 6).to(self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_pcm_resample(self.ctx, x.data_ptr(), n_x, d.data_ptr(), len(rows), max(r[3] for r in rows), taps.data_ptr(),
+                                                 taps.numel(), up, down, skip, y.data_ptr(), n_y, self._stream()))
+        return y[:n_y]
+
+    def pcm_encode(self, x: torch.Tensor, rows, encoding: str, n_y: Optional[int] = None) -> torch.Tensor:
+        """G.711 (vv_pcm_encode): x int16 flat on the device, rows = HOST rows {src_off, n, dst_off} -> uint8 [n_y]; encoding "ulaw" | "alaw",
+        bit-exact to audioop.lin2ulaw / lin2alaw at width 2.  The rows are validated here."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous()
+        kind = {"ulaw": 1, "alaw": 2}.get(encoding)
+        if kind is None:
+            raise ValueError("pcm_encode: encoding is 'ulaw' or 'alaw'")
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) != 3 for r in rows):
+            raise ValueError("pcm_encode: rows of 3 entries {src_off, n, dst_off}")
+        n_x = x.numel()
+        n_y = max((r[2] + r[1] for r in rows), default=0) if n_y is None else int(n_y)
+        spans = []
+        for so, n, do in rows:
+            if min(so, n, do) < 0 or so + n > n_x or do + n > n_y:
+                raise ValueError(f"pcm_encode: row {[so, n, do]} does not fit the buffers ({n_x} in, {n_y} out)")
+            spans.append((do, do + n))
+        spans.sort()
+        if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+            raise ValueError("pcm_encode: rows overlap on the output")
+        y = torch.empty((max(n_y, 8),), dtype=torch.uint8, device=self.device)
+        d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_pcm_encode(self.ctx, x.data_ptr(), n_x, d.data_ptr(), len(rows), max(r[1] for r in rows), kind,
+                                               y.data_ptr(), n_y, self._stream()))
+        return y[:n_y]
+
+    def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
+                      encoding: str = "pcm16"):
+        """The whole output stage of R requests on the caller's stream: join (-> output rate) (-> G.711), then ONE device-to-host copy of
+        the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.  -> a list of R numpy arrays:
+        int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
+        from .core.audio_processor import resample_len
+        buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
+        if rate is not None and int(rate) != int(sample_rate):
+            _taps, up, down, _skip = self._output_taps(int(sample_rate), int(rate))
+            rows, pos = [], 0
+            for o, n in zip(offs, lens):
+                n_out = resample_len(n, up, down)
+                rows.append([o, n, pos, n_out, 0, 0])
+                pos += n_out
+            buf = self.pcm_resample(buf, rows, sample_rate, rate, n_y=pos) if pos else buf[:0]
+            offs, lens = [r[2] for r in rows], [r[3] for r in rows]
+        if encoding != "pcm16":
+            rows, pos = [], 0
+            for o, n in zip(offs, lens):
+                rows.append([o, n, pos])
+                pos += n
+            buf = self.pcm_encode(buf, rows, encoding, n_y=pos) if pos else torch.empty((0,), dtype=torch.uint8, device=self.device)
+            offs = [r[2] for r in rows]
+        host = buf.cpu().numpy()
+        return [host[o: o + n] for o, n in zip(offs, lens)]
+
+    def output_stream_backends(self, sample_rate: int, rate: Optional[int], encoding: str, max_upload: int = 1 << 18):
+        """(resample, encode) callables for core.audio_processor.OutputStream on this device: host blocks go up in pieces of at most
+        ``max_upload`` samples (0.5 MB), through vv_pcm_resample / vv_pcm_encode, and come back."""
+        import numpy as np
+
+        def up_(x):
+            parts = [torch.from_numpy(np.ascontiguousarray(x[i: i + max_upload])).to(self.device) for i in range(0, x.size, max_upload)]
+            return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+        def resample(x, m0, i0, n_out):
+            x = np.asarray(x, dtype=np.int16).reshape(-1)
+            if n_out <= 0:
+                return np.zeros(0, np.int16)
+            xd = up_(x) if x.size else torch.zeros((8,), dtype=torch.int16, device=self.device)
+            return self.pcm_resample(xd, [[0, x.size, 0, n_out, m0, i0]], sample_rate, rate, n_y=n_out).cpu().numpy()
+
+        def encode(y):
+            y = np.asarray(y, dtype=np.int16).reshape(-1)
+            if y.size == 0:
+                return np.zeros(0, np.uint8)
+            return self.pcm_encode(up_(y), [[0, y.size, 0]], encoding, n_y=y.size).cpu().numpy()
+
+        return (resample if rate is not None and int(rate) != int(sample_rate) else None), (encode if encoding != "pcm16" else None)
 
     # ------------------------------------------------------------------ hipGraph-captured vocoder step (config 5)
     def capture_decode(self, B: int, N: int, t_gen_max: int) -> "GraphedDecode":
