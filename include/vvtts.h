@@ -225,6 +225,27 @@ VV_API int vv_transformer_steps_ex(vv_ctx* ctx, const vv_steps_args* args, void*
 VV_API int vv_transformer_steps_guided(vv_ctx* ctx, const vv_steps_args* args, const uint8_t* guide_host, int ld_guide, void* stream);
 VV_API int vv_transformer_guided_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, uint64_t* bytes);
 
+/* N11 adaptive projected guidance (APG): vv_transformer_steps_guided where the two predictions of a guided item are
+ * combined as k = p_c + A_b D + C_b d, D = p_c - p_u, d = x_e + (1 - t_e) p_c the conditional data estimate at the state x_e the DiT was
+ * evaluated at.  Over the item's valid frames and the n_mel columns: S1 = sum D d, S2 = sum d d, S3 = sum D D, n = frames * n_mel;
+ * s = r_b / ((1 - t_e) sqrt(S3 / n)) where r_b > 0 and that RMS exceeds it, else 1; A_b = g_b s; C_b = g_b s (eta_b - 1) S1 / S2 (0 when
+ * S2 == 0): the part of the difference parallel to d is scaled by eta_b, its data-space RMS capped at r_b.  eta / norm_rms: device [B]
+ * fp32, NULL = 1 / no cap for every item; an item with eta 1 and !(r > 0) gets the bits of the plain rule, an item that is not guided at an
+ * evaluation has k = p_c and nothing is reduced for it.  t_host: HOST [evaluations of the plan in force] fp32, the evaluation times t_e the
+ * plan's sinusoids were made from (row e = step * s + stage; read during the call only).  The sums are float64, deterministic and independent
+ * of the item's place in the batch (no atomics); every evaluation adds two small launches to the stage kernel's.  apg NULL: the call IS
+ * vv_transformer_steps_guided.  A caller-owned ws holds vv_transformer_apg_ws_bytes bytes (the same figure whatever the mask).  -22 for
+ * what vv_transformer_steps_guided refuses and for a missing t_host; no readback, no synchronisation. */
+#define VV_APG_TILE 32   /* frames per partial sum, counted from the item's frame 0 */
+typedef struct vv_apg_args {
+    const float* eta;        /* device [B], optional */
+    const float* norm_rms;   /* device [B], optional */
+    const float* t_host;     /* host [evaluations] */
+} vv_apg_args;
+VV_API int vv_transformer_steps_apg(vv_ctx* ctx, const vv_steps_args* args, const uint8_t* guide_host, int ld_guide, const vv_apg_args* apg,
+                                    void* stream);
+VV_API int vv_transformer_apg_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, uint64_t* bytes);
+
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
  * that needs more bytes (vv_ws_generation counts those moves); a launch sequence captured into a hipGraph
@@ -460,6 +481,27 @@ VV_API int vv_ode_stage(vv_ctx* ctx, const vv_ode_stage_args* args, void* stream
  * is not guided, k_i = p_c.  u_row[r] = Rc + r for every r is vv_ode_stage bit for bit, and so is u_row NULL.  The caller keeps the
  * entries inside pred. */
 VV_API int vv_ode_stage_guided(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, void* stream);
+/* N11 single-kernel entries (unit parity).  vv_apg_coef: the reduction and the coefficients of one evaluation.  Item b owns the packed
+ * conditional rows [row_start[b], + len[b]) of pred (device [B] int32, inside [0, Rc), len[b] <= VV_APG_TILE * n_tiles); p_u of row r is
+ * pred row Rc + r, or u_row[r] when u_row is given (< 0: not guided); x_e of row r is row row_src[r] of x_e, or r when row_src is NULL.
+ * partials [B][n_tiles][3] float64 (scratch: the entries of an item's tiles are written, the rest untouched), coef [B][2] fp32 = {A, C};
+ * {0, 0} for an item without rows or not guided.  g_item / eta / norm_rms: device [B], optional (g, 1, no cap). */
+typedef struct vv_apg_coef_args {
+    const float* pred; int32_t ldp, Rc, n_mel;
+    const int32_t* u_row;
+    const float* x_e; const int32_t* row_src;
+    int32_t B, n_tiles;
+    const int32_t* row_start; const int32_t* len;
+    float t_e, g;
+    const float* g_item; const float* eta; const float* norm_rms;
+    double* partials; float* coef;
+} vv_apg_coef_args;
+VV_API int vv_apg_coef(vv_ctx* ctx, const vv_apg_coef_args* args, void* stream);
+/* vv_ode_stage_guided with the projected combine: the strength of row r's item (row_src[r] / seq_n, or r / seq_n) is coef[item][0], and
+ * where coef[item][1] != 0 the slope also takes coef[item][1] * fmaf(1 - t_e, p_c, x_e) (x_e row r when x_e_packed, else row_src[r]; x_e
+ * must not be an output of the launch).  g and g_item are not read.  apg NULL: the call IS vv_ode_stage_guided. */
+typedef struct vv_apg_stage_args { const float* coef; const float* x_e; int32_t x_e_packed; float t_e; } vv_apg_stage_args;
+VV_API int vv_ode_stage_apg(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, const vv_apg_stage_args* apg, void* stream);
 VV_API int vv_cfg_euler(vv_ctx* ctx, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* stream);
 
 /* ---- reference-clip ingest on the device (a8 + SURVEY 8(f) N3).  Together they replace the arithmetic of

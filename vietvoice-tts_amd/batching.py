@@ -35,10 +35,11 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "t0", "n_req")
 
     def __init__(self):
         self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
+        self.etas, self.norms = [], []
 
 
 class BatchingFrontend:
@@ -70,15 +71,20 @@ class BatchingFrontend:
             t.start()
 
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
-               cfg_interval: Optional[Tuple[float, float]] = None, **voice) -> Future:
+               cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
+               **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
-        ``cfg_interval``: this request's guidance interval (lo, hi), 0 <= lo <= hi <= 1 (None = the engine's), per item in the same way."""
+        ``cfg_interval``: this request's guidance interval (lo, hi), 0 <= lo <= hi <= 1 (None = the engine's), per item in the same way.
+        ``apg_eta`` / ``apg_norm``: this request's projected guidance (model_spec.check_apg; None = the engine's value), per item as well:
+        plain and projected requests share one batch."""
         fut: Future = Future()
         try:
-            from .model_spec import check_cfg_interval
+            from .model_spec import check_apg, check_cfg_interval
             cfg_interval = check_cfg_interval(cfg_interval)
+            check_apg(apg_eta, apg_norm)
+            apg_eta, apg_norm = (None if v is None else float(v) for v in (apg_eta, apg_norm))
         except ValueError as e:
             fut.set_exception(e)
             return fut
@@ -94,7 +100,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -127,7 +133,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength, cfg_interval = req
+        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -158,6 +164,8 @@ class BatchingFrontend:
         batch.keys.extend(keys)
         batch.cfgs.extend([cfg_strength] * len(inputs))
         batch.ivals.extend([cfg_interval] * len(inputs))
+        batch.etas.extend([apg_eta] * len(inputs))
+        batch.norms.extend([apg_norm] * len(inputs))
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -267,10 +275,10 @@ class BatchingFrontend:
                 dev_out = eng._device_output()      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
                 if batch.keys:
                     waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
-                                                   device_out=dev_out)
+                                                   device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
                 else:
                     waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
-                                                   device_out=dev_out)
+                                                   device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0

@@ -48,13 +48,14 @@ class HipSession:
     numpy in and out -- the reference's contract, including its host round trips)."""
 
     def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None,
-                 noise_keys=None):
+                 noise_keys=None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None):
         self.engine, self.kind, self.noise_gen, self.fuse_nfe = engine, kind, noise_gen, max(1, int(fuse_nfe))
         # N9 (ModelConfig.noise_source == "device"): a callable -> the next run's Philox key row {seed, stream}; the preprocess session
         # then fills the noise in HBM (vv_noise_fill) and returns it, as the reference's graph returns its own.  None = the host generator.
         self.noise_keys = noise_keys
         self.cfg_strength = cfg_strength          # None = the model's guidance strength (ModelConfig.cfg_strength)
         self.cfg_interval = cfg_interval          # None = guidance at every evaluation (ModelConfig.cfg_interval)
+        self.apg_eta, self.apg_norm = apg_eta, apg_norm      # both None = the plain combine (ModelConfig.apg_eta / apg_norm)
         self._in, self._out = SESSION_IO[kind]
 
     def get_inputs(self):
@@ -105,14 +106,15 @@ class HipSession:
             k = min(self.fuse_nfe, eng.n_steps - step)          # ODE steps, whatever the solver: a step is never split between calls
             cfg = None if self.cfg_strength is None else torch.full((1,), float(self.cfg_strength), dtype=torch.float32, device=dev)
             guide = eng.guidance_mask(self.cfg_interval, [self.cfg_strength])      # absolute evaluation rows: the split calls read one table
+            apg = eng.apg_tensors([self.apg_eta], [self.apg_norm])                 # N11: stateless between the split calls (no momentum)
             if same:
-                eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide)
+                eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg)
             else:
                 if not getattr(self, "_rope_warned", False):
                     logger.warning("transformer session: non-standard rope tables fed; the tables are read instead of computed")
                     self._rope_warned = True
                 with eng.reading_rope_tables():
-                    eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide)
+                    eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg)
             return [x.cpu().numpy(), np.array([step + k], dtype=np.int32)]
         x = torch.from_numpy(np.ascontiguousarray(vals[0], dtype=np.float32)).to(dev)
         n = x.shape[1]
@@ -200,7 +202,8 @@ class ModelSessionManager:
                                        nfe_step=self.config.nfe_step, ode_method=self.config.ode_method)
                 on_device = self._session_key if self.config.noise_source == "device" else None
                 made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval,
-                                      noise_keys=on_device if k == "preprocess" else None) for k in SESSION_IO}
+                                      noise_keys=on_device if k == "preprocess" else None, apg_eta=self.config.apg_eta,
+                                      apg_norm=self.config.apg_norm) for k in SESSION_IO}
             for name in ("preprocess", "transformer", "decode"):
                 sess = made[name]
                 self.sessions[name] = sess

@@ -66,6 +66,9 @@ class ModelConfig:
     cfg_strength: Optional[float] = None    # classifier-free guidance strength of every synthesis of this engine; None = the model's
     cfg_interval: Optional[Tuple[float, float]] = None   # guidance only at the evaluations with lo <= t <= hi (limited-interval guidance);
                                             # outside it the unconditional branch is not computed.  None = guidance everywhere
+    apg_eta: Optional[float] = None         # adaptive projected guidance (model_spec.check_apg): the factor on the part of the guidance difference
+                                            # parallel to the conditional data estimate (0 removes it, 1 or None = plain CFG)
+    apg_norm: Optional[float] = None        # ... and the cap on the RMS of the data-space guidance difference (None = no cap)
     noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
                                             # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
     output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
@@ -103,6 +106,10 @@ class ModelConfig:
                 raise ValueError("output_sample_rate must be between 4000 and 192000 Hz")
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
+        from ..model_spec import check_apg
+        check_apg(self.apg_eta, self.apg_norm)                          # finite eta, finite norm > 0; both None (or eta 1) = plain CFG
+        self.apg_eta = None if self.apg_eta is None else float(self.apg_eta)
+        self.apg_norm = None if self.apg_norm is None else float(self.apg_norm)
         self.validate_paths()
 
     @property

@@ -191,7 +191,8 @@ class TTSEngine:
         rate, enc = self._output_options()
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc)
 
-    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False):
+    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
+                           apg_etas=None, apg_norms=None):
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
         clips may differ per item (cross-request batches).  One ragged GPU batch per ``max_batch_chunks`` items.
         noise_blocks: optional pre-drawn (N_i, n_mel) fp32 tensors, one per item (the batching front end draws them from
@@ -202,6 +203,8 @@ class TTSEngine:
         cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model).
         cfg_intervals: optional guidance interval (lo, hi) per item (None entries = ``config.cfg_interval``).  An item is guided at the
         evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed.
+        apg_etas / apg_norms: optional projected guidance per item (None entries = ``config.apg_eta`` / ``config.apg_norm``); items with
+        neither keep the plain combine, in the same batch.
         device_out (N10): nothing is copied to the host; returns (int16 device tensor, [(offset, samples) per item]) -- the planes of the
         chunk groups back to back and each item's span in them, the lengths from the host's own frame counts (no readback)."""
         import torch
@@ -214,6 +217,8 @@ class TTSEngine:
             [self.config.cfg_strength if v is None else float(v) for v in cfg_strengths]
         iv_all = [self.config.cfg_interval] * len(inputs_list) if cfg_intervals is None else \
             [self.config.cfg_interval if v is None else v for v in cfg_intervals]
+        eta_all = [self.config.apg_eta] * len(inputs_list) if apg_etas is None else [self.config.apg_eta if v is None else v for v in apg_etas]
+        norm_all = [self.config.apg_norm] * len(inputs_list) if apg_norms is None else [self.config.apg_norm if v is None else v for v in apg_norms]
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
@@ -284,10 +289,11 @@ class TTSEngine:
             if any(g_all[j] is not None for j in idx):
                 cfg = torch.tensor([float(spec.cfg_strength) if g_all[j] is None else g_all[j] for j in idx], dtype=torch.float32).to(dev)
             guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx])     # None: every item guided everywhere
+            apg = eng.apg_tensors([eta_all[j] for j in idx], [norm_all[j] for j in idx])      # None: the plain combine for every item
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
                 x = noise.to(dev) if keys is None else eng.noise(keys, pre["seq_len"], N)
-                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide)
+                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide, apg=apg)
                 if self._decode_graphs is None:
                     self._decode_graphs = DecodeGraphCache(eng, self.config.decode_graph_cache_entries, self.config.decode_graph_cache_bytes)
                 pcm, pcm_len = self._decode_graphs.get(B, N, t_gen)(x, pre["ref_signal_len"], pre["seq_len"])
@@ -295,7 +301,7 @@ class TTSEngine:
                 _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N,
                                                               None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
-                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys)
+                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg)
             if device_out:
                 pcm = pcm.clone() if self.config.use_hip_graph else pcm.contiguous()      # a captured graph's output buffer is replayed over
                 for i, j in enumerate(idx):
@@ -437,7 +443,8 @@ class TTSEngine:
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
                                                torch.from_numpy(plan.keep.reshape(1, -1)).to(dev),
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
-                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys)
+                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys,
+                                               apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]))
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options())[0]

@@ -686,6 +686,10 @@ struct Lane {
     const int *row_start = nullptr, *row_src = nullptr, *row_pos = nullptr, *qkv_pos = nullptr;
     // N8 (a call with a guidance mask): the tables of the evaluation's guided subset, rebuilt when the subset changes (guided_tables_kernel)
     int *g_row_start = nullptr, *g_rs_rel = nullptr, *g_kv_len = nullptr, *g_row_pos = nullptr, *u_src = nullptr, *u_crow = nullptr, *u_row = nullptr;
+    // N11 (a call with APG): the partial sums [B][n_tiles][3] and the coefficients [B][2] of the evaluation in hand, and a second stage state:
+    // stage i reads the state it was evaluated at (x_e) while it writes the next one
+    double* apg_part = nullptr;
+    float *apg_coef = nullptr, *xs2 = nullptr;
 };
 // N8: what the host knows of a lane's guided subset at the evaluation in hand
 struct GuideState {
@@ -697,7 +701,7 @@ struct GuideState {
 
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided) {
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided, bool apg) {
     const vv_model_cfg& g = c->cfg;
     const size_t R = L.R, es = c->esz(), D = g.dim, FF = D * g.ff_mult, M = g.n_mel;
     const size_t KP = pad_to(2 * g.n_mel + g.text_dim, 64), MP = pad_to(g.n_mel, 128);
@@ -720,16 +724,24 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided) {
         L.g_row_start = t; L.g_rs_rel = t + 2 * L.B; L.g_kv_len = t + 3 * L.B; L.g_row_pos = t + 5 * L.B;
         L.u_src = L.g_row_pos + 2 * L.Rc; L.u_crow = L.u_src + L.Rc; L.u_row = L.u_crow + L.Rc;
     }
+    if (apg) {                                     // N11
+        L.apg_part = a.take<double>((size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 3);
+        L.apg_coef = a.take<float>(2 * (size_t)L.B);
+        if (c->ode_s > 1) L.xs2 = a.take<float>(L.Rc * M);
+    }
 }
 }  // namespace
 
 // guide != nullptr (N8, vv_transformer_steps_guided): HOST flags [evaluations of the plan][ld_guide], guided(b, e) at guide[e * ld_guide + b];
 // an item that is not guided at an evaluation has no unconditional rows there.  guided_ws: the workspace of such a call (the tables of
 // the subsets on top of the plain call's bytes), whatever the mask.
+// apg != nullptr (N11, vv_transformer_steps_apg): the projected combine -- per evaluation and lane, apg_reduce_kernel and apg_coef_kernel in
+// front of the stage kernel, on its stream.  apg_ws: the workspace of such a call (with the tables of a mask, whether one is given or not).
 static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t* ws_only, void* stream, const uint8_t* guide = nullptr,
-                                  int ld_guide = 0, bool guided_ws = false) {
+                                  int ld_guide = 0, bool guided_ws = false, const vv_apg_args* apg = nullptr, bool apg_ws = false) {
     if (!c) return -22;
-    const bool guided = guide != nullptr || guided_ws;
+    const bool with_apg = apg != nullptr || apg_ws;
+    const bool guided = guide != nullptr || guided_ws || with_apg;
     const int B = args.B, N = args.N, step0 = args.step0, n_steps = args.n_steps;
     const int32_t *seq_len = args.seq_len, *seq_len_host = args.seq_len_host;
     float* x = args.x;
@@ -787,7 +799,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
                               (c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS));
     Lane lanes[2];
     const int ns = c->ode_s, S = c->n_steps * ns;      // S: rows of the modulation tables (evaluations)
-    const bool rk = ns > 1 || cfg_item != nullptr || guide != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
+    const bool rk = ns > 1 || cfg_item != nullptr || guide != nullptr || apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     for (int li = 0; li < n_lanes; ++li) {
         Lane& L = lanes[li];
         L.b0 = cuts[li]; L.B = cuts[li + 1] - cuts[li];
@@ -804,7 +816,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         L.tail_rows = (L.tp_o || L.tp_f) ? L.R - L.tail_row0 : 0;
         L.n_tab = 2 * (size_t)L.B + L.Rc + L.R;          // row_start[2B] | row_src[Rc] | row_pos[R]
     }
-    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N, guided); };
+    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N, guided, with_apg); };
     if (ws_only) { *ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
     if (int r = plan_ws(c, args.ws, (size_t)args.ws_bytes, bufs)) return r;
     for (int li = 1; li < (branch_lanes ? 2 : n_lanes); ++li)
@@ -842,12 +854,15 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
     };
     // input embedding of step s: proj, then conv position embedding (two grouped convs + Mish) + residual
     // stage i > 0 of step s reads the stage state (packed rows, no row map) instead of x
+    // the state stage i >= 1 is evaluated at: under APG the stages alternate between two buffers (stage i - 1 wrote it, stage i reads it as x_e
+    // while it writes the other one)
+    auto stage_state = [&](const Lane& L, int i) -> float* { return (apg && !(i & 1)) ? L.xs2 : L.xs; };
     auto step_pack = [&](Lane& L, int s, int i) -> int {
         hipStream_t st = L.st;
         const size_t Rc = L.Rc;
         if (s != step0 || i > 0) {
             Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * Rc * M + 2.0 * es * Rc * M, st);
-            KCHK(c, vvk_pack_cat(c->dt, i ? L.xs : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, i ? nullptr : L.row_src, st, &m__));
+            KCHK(c, vvk_pack_cat(c->dt, i ? stage_state(L, i) : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, i ? nullptr : L.row_src, st, &m__));
         }
         return 0;
     };
@@ -873,7 +888,7 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
             }
             G.flags = f; G.Ru = Ru; G.Bu = Bu; G.sum_sq = sq;
         }
-        const float* xin = i ? L.xs : L.x;
+        const float* xin = i ? stage_state(L, i) : L.x;
         const int Rc = (int)L.Rc, R = (int)(L.Rc + Ru);
         auto pack = [&](int row0, int n_rows, int only_x) -> int {
             Prof p(c, VV_PROF_ELEMWISE, 0, only_x ? (4.0 + es) * n_rows * M : 4.0 * n_rows * (M + CD) + (double)es * n_rows * KP, st);
@@ -992,10 +1007,24 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
             if (j < i && a.coef[j] != 0.f) { a.k_prev[j] = L.kbuf[c->ode_kslot[j]]; ++n_read; }
         }
         a.k_out = (!last && c->ode_kslot[i] >= 0) ? L.kbuf[c->ode_kslot[i]] : nullptr;
-        a.x_out = last ? nullptr : L.xs;
+        a.x_out = last ? nullptr : stage_state(L, i + 1);
         a.g = g.cfg_strength; a.g_item = cfg_item ? cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
-        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0)), st);
-        KCHK(c, vvk_ode_stage(&a, guide ? L.u_row : nullptr, st, &m__));
+        const int* u_row = guide ? L.u_row : nullptr;
+        vv_apg_stage_args sa{};
+        if (apg) {                                       // N11: the item sums of this evaluation, then their coefficients
+            vv_apg_coef_args q{};
+            q.pred = L.pred; q.ldp = MP; q.Rc = (int)L.Rc; q.n_mel = M; q.u_row = u_row;
+            q.x_e = i ? stage_state(L, i) : L.x; q.row_src = i ? nullptr : L.row_src;
+            q.B = L.B; q.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; q.row_start = L.row_start; q.len = L.kv_len;
+            q.t_e = apg->t_host[s * ns + i]; q.g = a.g; q.g_item = a.g_item;
+            q.eta = apg->eta ? apg->eta + L.b0 : nullptr; q.norm_rms = apg->norm_rms ? apg->norm_rms + L.b0 : nullptr;
+            q.partials = L.apg_part; q.coef = L.apg_coef;
+            { Prof p(c, VV_PROF_ELEMWISE, 14.0 * L.Rc * M, 12.0 * L.Rc * M, st); KCHK(c, vvk_apg_coef(&q, 1, st, &m__)); }
+            { Prof p(c, VV_PROF_ELEMWISE, 0, 24.0 * L.B * q.n_tiles, st); KCHK(c, vvk_apg_coef(&q, 2, st, &m__)); }
+            sa.coef = L.apg_coef; sa.x_e = q.x_e; sa.x_e_packed = i ? 1 : 0; sa.t_e = q.t_e;
+        }
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0)), st);
+        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, st, &m__));
         return 0;
     };
 
@@ -1153,6 +1182,25 @@ int vv_transformer_guided_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_l
     vv_steps_args a{};
     a.B = B; a.N = N; a.seq_len_host = seq_len_host;
     return transformer_steps_impl(c, a, bytes, nullptr, nullptr, 0, true);
+}
+
+// N11: projected guidance on top of vv_transformer_steps_guided (include/vvtts.h)
+int vv_transformer_steps_apg(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, const vv_apg_args* apg, void* stream) {
+    if (!apg) return vv_transformer_steps_guided(c, a, guide_host, ld_guide, stream);
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_apg: null arguments");
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_apg: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_apg: cfg_item must be a float array");
+    if (!apg->t_host) return c->fail(-22, "vv_transformer_steps_apg: the evaluation times t_host are required");
+    if (((uintptr_t)apg->eta | (uintptr_t)apg->norm_rms) % 4) return c->fail(-22, "vv_transformer_steps_apg: eta and norm_rms must be float arrays");
+    return transformer_steps_impl(c, *a, nullptr, stream, guide_host, ld_guide, false, apg, false);
+}
+
+int vv_transformer_apg_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
+    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_apg_ws_bytes: bad arguments");
+    vv_steps_args a{};
+    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
+    return transformer_steps_impl(c, a, bytes, nullptr, nullptr, 0, true, nullptr, true);
 }
 
 // --------------------------------------------------------------------------------------- decode
@@ -1521,12 +1569,25 @@ int vv_istft_head(vv_ctx* c, int B, int T_max, const float* head, int ld_head, c
 }
 int vv_ode_stage(vv_ctx* c, const vv_ode_stage_args* a, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage: null arguments") : -22;
-    SINGLE(c, vvk_ode_stage(a, nullptr, (hipStream_t)st, &m__));
+    SINGLE(c, vvk_ode_stage(a, nullptr, nullptr, (hipStream_t)st, &m__));
 }
 int vv_ode_stage_guided(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_guided: null arguments") : -22;
     if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_guided: u_row must be an int32 array");
-    SINGLE(c, vvk_ode_stage(a, u_row, (hipStream_t)st, &m__));
+    SINGLE(c, vvk_ode_stage(a, u_row, nullptr, (hipStream_t)st, &m__));
+}
+int vv_ode_stage_apg(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row, const vv_apg_stage_args* apg, void* st) {
+    if (!apg) return vv_ode_stage_guided(c, a, u_row, st);
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_apg: null arguments") : -22;
+    if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_apg: u_row must be an int32 array");
+    SINGLE(c, vvk_ode_stage(a, u_row, apg, (hipStream_t)st, &m__));
+}
+int vv_apg_coef(vv_ctx* c, const vv_apg_coef_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_apg_coef: null arguments") : -22;
+    if (((uintptr_t)a->u_row | (uintptr_t)a->row_src | (uintptr_t)a->row_start | (uintptr_t)a->len | (uintptr_t)a->g_item | (uintptr_t)a->eta |
+         (uintptr_t)a->norm_rms) % 4)
+        return c->fail(-22, "vv_apg_coef: the index and item arrays must be 4-byte aligned");
+    SINGLE(c, vvk_apg_coef(a, 3, (hipStream_t)st, &m__));
 }
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));

@@ -213,12 +213,16 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, c
 // GUIDED (N8): the unconditional row of packed row r is pred row u_row[r] (an absolute row of pred, inside [BN, BN + Ru)); u_row[r] < 0:
 // the item is not guided at this evaluation, it has no unconditional row and k_i = pc.  One body, so a mapped row runs the very
 // arithmetic of the plain kernel.
+// APG (N11): the item's strength is coef[b][0] = A_b in place of g (the combine is written exactly as the plain one), and where
+// coef[b][1] = C_b != 0 the slope also takes C_b d, d = fmaf(1 - t_e, pc, x_e) the conditional data estimate at the state x_e the DiT was
+// evaluated at (x through row_src, or the packed stage state when xe_packed) -- never the buffer x_out of the same launch.
 struct OdeStagePrev { const float* k[3]; float c[3]; };
-template <bool GUIDED>
+template <bool GUIDED, bool APG>
 __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
                                                         const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
                                                         OdeStagePrev pv, float c_new, float* __restrict__ k_out, float* __restrict__ x_out,
-                                                        const int* __restrict__ u_row) {
+                                                        const int* __restrict__ u_row, const float* __restrict__ apg_coef,
+                                                        const float* x_e, int xe_packed, float omt) {
     const int c4 = n_mel >> 2;
     const size_t total = (size_t)BN * c4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -226,7 +230,13 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
         const size_t row = i / c4;
         const float4 pc = *(const float4*)(pred + row * ldp + c);
         const size_t xr = row_src ? (size_t)row_src[row] : row;
-        const float cfg = g_item ? g_item[xr / (size_t)seq_n] : g;
+        float cfg, apg_c = 0.f;
+        if (APG) {
+            const float2 ac = *(const float2*)(apg_coef + 2 * (xr / (size_t)seq_n));
+            cfg = ac.x; apg_c = ac.y;
+        } else {
+            cfg = g_item ? g_item[xr / (size_t)seq_n] : g;
+        }
         const int ur = GUIDED ? u_row[row] : 0;
         float4 k = pc;
         if (!GUIDED || ur >= 0) {
@@ -235,6 +245,13 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
             k.y = pc.y + (pc.y - pu.y) * cfg;
             k.z = pc.z + (pc.z - pu.z) * cfg;
             k.w = pc.w + (pc.w - pu.w) * cfg;
+            if (APG && apg_c != 0.f) {
+                const float4 xe = *(const float4*)(x_e + (xe_packed ? row : xr) * n_mel + c);
+                k.x = fmaf(apg_c, fmaf(omt, pc.x, xe.x), k.x);
+                k.y = fmaf(apg_c, fmaf(omt, pc.y, xe.y), k.y);
+                k.z = fmaf(apg_c, fmaf(omt, pc.z, xe.z), k.z);
+                k.w = fmaf(apg_c, fmaf(omt, pc.w, xe.w), k.w);
+            }
         }
         if (k_out) *(float4*)(k_out + row * n_mel + c) = k;
         float4 xv = *(const float4*)(x + xr * n_mel + c);
@@ -249,6 +266,85 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
         }
         *(float4*)(x_out ? x_out + row * n_mel + c : x + xr * n_mel + c) = xv;
     }
+}
+
+// ---------------------------------------------------------------- N11: projected guidance (APG), the per-item reduction
+// Partial sums of one (frame tile, item): S1 = sum D d, S2 = sum d d, S3 = sum D D over the tile's valid frames and the n_mel columns,
+// D = pc - pu, d = x_e + (1 - t_e) pc, formed and accumulated in float64 from the fp32 inputs.  Tiles are VV_APG_TILE frames counted from
+// the ITEM's frame 0, and float4 q of the tile (frame q / c4, columns 4 (q % c4)) always goes to thread q % 256, its four elements in
+// order, the threads' sums through one fixed LDS tree: an item's partials are a function of its own rows alone, whatever its place in
+// the batch, its neighbours, N, the lanes or the guided subset.  A row whose u_row is < 0 contributes nothing (the coefficient kernel
+// zeroes such an item).  grid (n_tiles, B); a tile past the item's length writes nothing and is never read.
+__global__ __launch_bounds__(256) void apg_reduce_kernel(const float* __restrict__ pred, int ldp, int Rc, int n_mel,
+                                                         const int* __restrict__ u_row, const float* __restrict__ x_e,
+                                                         const int* __restrict__ row_src, const int* __restrict__ row_start,
+                                                         const int* __restrict__ len, int n_tiles, double omt, double* __restrict__ partials) {
+    __shared__ double red[3][256];
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);   // inside the Rc conditional rows and the item's n_tiles partials, whatever the tables say
+    const int f0 = tile * VV_APG_TILE;
+    if (f0 >= n) return;
+    const int c4 = n_mel >> 2;
+    const int total = min(VV_APG_TILE, n - f0) * c4;
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const int c = (q % c4) * 4;
+        const size_t row = (size_t)r0 + f0 + q / c4;
+        const int ur = u_row ? u_row[row] : (int)row + Rc;
+        if (ur < 0) continue;
+        const float4 pc = *(const float4*)(pred + row * ldp + c);
+        const float4 pu = *(const float4*)(pred + (size_t)ur * ldp + c);
+        const float4 xe = *(const float4*)(x_e + (row_src ? (size_t)row_src[row] : row) * n_mel + c);
+        const float pcv[4] = {pc.x, pc.y, pc.z, pc.w}, puv[4] = {pu.x, pu.y, pu.z, pu.w}, xev[4] = {xe.x, xe.y, xe.z, xe.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double D = (double)pcv[j] - (double)puv[j];
+            const double d = fma(omt, (double)pcv[j], (double)xev[j]);
+            s1 = fma(D, d, s1); s2 = fma(d, d, s2); s3 = fma(D, D, s3);
+        }
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2; red[2][threadIdx.x] = s3;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+            red[2][threadIdx.x] += red[2][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) partials[((size_t)b * n_tiles + tile) * 3 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// One wave per item: lane j < 3 adds the item's partials S_{j+1} in ascending tile order, lane 0 turns them into coef[b] = {A, C} (float64,
+// one fp32 rounding each):  s = r / ((1 - t_e) sqrt(S3 / n)) where r > 0 and that RMS exceeds it, else 1;  A = g s;
+// C = g s (eta - 1) S1 / S2, 0 when S2 == 0.  {0, 0} for an item without rows or whose first row is not guided (u_row < 0).
+__global__ __launch_bounds__(64) void apg_coef_kernel(const double* __restrict__ partials, int n_tiles, int Rc, int n_mel,
+                                                      const int* __restrict__ u_row, const int* __restrict__ row_start,
+                                                      const int* __restrict__ len, double omt, float g, const float* __restrict__ g_item,
+                                                      const float* __restrict__ eta, const float* __restrict__ norm_rms,
+                                                      float* __restrict__ coef) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);
+    const bool guided = n > 0 && (!u_row || u_row[r0] >= 0);
+    double s = 0.0;
+    if (guided && lane < 3) {
+        const int nt = (n + VV_APG_TILE - 1) / VV_APG_TILE;
+        for (int t = 0; t < nt; ++t) s += partials[((size_t)b * n_tiles + t) * 3 + lane];
+    }
+    const double S1 = __shfl(s, 0), S2 = __shfl(s, 1), S3 = __shfl(s, 2);
+    if (lane != 0) return;
+    float A = 0.f, Cc = 0.f;
+    if (guided) {
+        const double gb = (double)(g_item ? g_item[b] : g), e = eta ? (double)eta[b] : 1.0, r = norm_rms ? (double)norm_rms[b] : 0.0;
+        const double rms = omt * sqrt(S3 / ((double)n * (double)n_mel));
+        const double sc = (r > 0.0 && rms > r) ? r / rms : 1.0;
+        A = (float)(gb * sc);
+        Cc = (e == 1.0 || S2 == 0.0) ? 0.f : (float)(gb * sc * (e - 1.0) * S1 / S2);
+    }
+    coef[2 * b] = A; coef[2 * b + 1] = Cc;
 }
 
 // ---------------------------------------------------------------- text: embed gather + position table
@@ -602,7 +698,7 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
     return 0;
 }
 
-int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, hipStream_t st, const char** err) {
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err) {
     if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
     if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
     if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
@@ -618,14 +714,42 @@ int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, hipStream_t st, 
     }
     if (al % 16) { *err = "ode_stage: buffers must be 16-byte aligned"; return -22; }
     if (a->x_out && (a->x_out == a->x || a->x_out == a->k_out)) { *err = "ode_stage: x_out must be a buffer of its own"; return -22; }
+    if (apg) {
+        if (!apg->coef || !apg->x_e || a->seq_n < 1) { *err = "ode_stage: APG needs coef, x_e and the padded sequence length seq_n"; return -22; }
+        if (((uintptr_t)apg->coef % 8) || ((uintptr_t)apg->x_e % 16)) { *err = "ode_stage: APG coef must be 8-byte and x_e 16-byte aligned"; return -22; }
+        if (apg->x_e == a->x_out || apg->x_e == a->k_out) { *err = "ode_stage: APG x_e aliases an output of the launch"; return -22; }
+        if (!(apg->t_e == apg->t_e)) { *err = "ode_stage: NaN evaluation time"; return -22; }
+    }
     const int grid = grid_for((size_t)a->Rc * a->n_mel / 4);
-    if (u_row)
-        ode_stage_kernel<true><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
-                                                     a->coef[a->n_prev], a->k_out, a->x_out, u_row);
-    else
-        ode_stage_kernel<false><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
-                                                      a->coef[a->n_prev], a->k_out, a->x_out, nullptr);
+    const float omt = apg ? 1.0f - apg->t_e : 0.f;
+#define STAGE_GO(G, A) ode_stage_kernel<G, A><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv, \
+        a->coef[a->n_prev], a->k_out, a->x_out, u_row, apg ? apg->coef : nullptr, apg ? apg->x_e : nullptr, apg ? apg->x_e_packed : 0, omt)
+    if (apg) { if (u_row) STAGE_GO(true, true); else STAGE_GO(false, true); }
+    else if (u_row) STAGE_GO(true, false);
+    else STAGE_GO(false, false);
+#undef STAGE_GO
     VVK_CHECK_LAUNCH();
+    return 0;
+}
+
+// N11: the two kernels behind vv_apg_coef.  which & 1: the reduction, which & 2: the coefficients.
+int vvk_apg_coef(const vv_apg_coef_args* a, int which, hipStream_t st, const char** err) {
+    if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "apg_coef: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
+    if (!a->pred || !a->x_e || !a->row_start || !a->len || !a->partials || !a->coef) { *err = "apg_coef: pred, x_e, row_start, len, partials and coef are required"; return -22; }
+    if (a->B < 1 || a->B > VVK_GUIDE_MAX_ITEMS || a->n_tiles < 1) { *err = "apg_coef: 1..1024 items, n_tiles >= 1"; return -22; }
+    if (((uintptr_t)a->pred | (uintptr_t)a->x_e) % 16 || (uintptr_t)a->partials % 8 || (uintptr_t)a->coef % 8) { *err = "apg_coef: pred and x_e 16-byte, partials and coef 8-byte aligned"; return -22; }
+    if (!(a->t_e == a->t_e)) { *err = "apg_coef: NaN evaluation time"; return -22; }
+    const double omt = 1.0 - (double)a->t_e;
+    if (which & 1) {
+        apg_reduce_kernel<<<dim3(a->n_tiles, a->B), 256, 0, st>>>(a->pred, a->ldp, a->Rc, a->n_mel, a->u_row, a->x_e, a->row_src, a->row_start,
+                                                                   a->len, a->n_tiles, omt, a->partials);
+        VVK_CHECK_LAUNCH();
+    }
+    if (which & 2) {
+        apg_coef_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->n_mel, a->u_row, a->row_start, a->len, omt, a->g, a->g_item,
+                                             a->eta, a->norm_rms, a->coef);
+        VVK_CHECK_LAUNCH();
+    }
     return 0;
 }
 

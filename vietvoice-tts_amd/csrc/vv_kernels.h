@@ -30,7 +30,10 @@ int vvk_pack_cat(int dtype, const float* x, const float* cat, const float* cat_d
 int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, const int* row_src, hipStream_t st,
                   const char** err);
 // u_row (N8, optional [Rc] device): conditional packed row -> the row of pred that holds its unconditional prediction, -1 = none (k = pc)
-int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, hipStream_t st, const char** err);
+// apg (N11, optional): the item coefficients {A, C} and the evaluation state of the projected combine
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err);
+// N11: apg_reduce_kernel (which & 1) and apg_coef_kernel (which & 2) of one evaluation
+int vvk_apg_coef(const vv_apg_coef_args* a, int which, hipStream_t st, const char** err);
 // N8 guidance subsets: flags [B] on the HOST (they travel as kernel arguments), at most VVK_GUIDE_MAX_ITEMS items per launch
 #define VVK_GUIDE_MAX_ITEMS 1024
 int vvk_guided_tables(const int* seq_len, const unsigned char* flags, int B, int N, int Rc, int Ru, int* row_start, int* rs_rel, int* kv_len,

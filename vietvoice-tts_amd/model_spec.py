@@ -261,6 +261,24 @@ def guidance_mask(plan: OdePlan, interval, strengths) -> Optional[torch.Tensor]:
     return None if bool(mask.all()) else mask
 
 
+def check_apg(eta, norm) -> Optional[Tuple[float, Optional[float]]]:
+    """N11 projected guidance (Sadat et al. 2025) of one item: ``eta`` scales the part of the guidance difference parallel to the
+    conditional data estimate (None = 1, plain CFG's), ``norm`` caps the RMS of the data-space difference (None = no cap).  Returns
+    (eta, norm) as floats, or None when the pair is "off" (eta None or 1 and no cap: the plain rule).  ValueError for an eta that is
+    not finite and a norm that is not finite and > 0."""
+    def num(v, what):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise ValueError(f"{what} must be a number or None")
+        return float(v)
+    e = 1.0 if eta is None else num(eta, "apg_eta")
+    if not math.isfinite(e):
+        raise ValueError("apg_eta must be finite or None")
+    r = None if norm is None else num(norm, "apg_norm")
+    if r is not None and not (math.isfinite(r) and r > 0.0):
+        raise ValueError("apg_norm must be finite and > 0, or None")
+    return None if (e == 1.0 and r is None) else (e, r)
+
+
 NOISE_SOURCES = ("host", "device")      # ModelConfig.noise_source: torch.randn on the host (default) | vv_noise_fill on the device (N9)
 
 

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ODE_MAX_EVALS, ModelSpec, guidance_mask, ode_plan
+from .model_spec import ODE_MAX_EVALS, ModelSpec, check_apg, guidance_mask, ode_plan
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VVTTS_LIB") or os.path.join(_HERE, "libvvtts_hip.so")   # VVTTS_LIB: A/B builds in tools/
@@ -109,6 +109,23 @@ class vv_ode_stage_args(C.Structure):
                 ("g", C.c_float), ("g_item", C.c_void_p), ("seq_n", C.c_int32), ("row_src", C.c_void_p)]
 
 
+class vv_apg_args(C.Structure):
+    _fields_ = [("eta", C.c_void_p), ("norm_rms", C.c_void_p), ("t_host", C.c_void_p)]
+
+
+class vv_apg_coef_args(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("ldp", C.c_int32), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("u_row", C.c_void_p),
+                ("x_e", C.c_void_p), ("row_src", C.c_void_p), ("B", C.c_int32), ("n_tiles", C.c_int32), ("row_start", C.c_void_p),
+                ("len", C.c_void_p), ("t_e", C.c_float), ("g", C.c_float), ("g_item", C.c_void_p), ("eta", C.c_void_p),
+                ("norm_rms", C.c_void_p), ("partials", C.c_void_p), ("coef", C.c_void_p)]
+
+
+class vv_apg_stage_args(C.Structure):
+    _fields_ = [("coef", C.c_void_p), ("x_e", C.c_void_p), ("x_e_packed", C.c_int32), ("t_e", C.c_float)]
+
+
+APG_TILE = 32                 # VV_APG_TILE of include/vvtts.h: frames per partial sum of the projected-guidance reduction
+
 EXPORTS = {
     # name: (restype, argtypes)
     "vv_version": (C.c_char_p, []),
@@ -124,6 +141,10 @@ EXPORTS = {
     "vv_transformer_steps_guided": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.c_void_p]),
     "vv_transformer_guided_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vv_ode_stage_guided": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.c_void_p]),
+    "vv_transformer_steps_apg": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.POINTER(vv_apg_args), C.c_void_p]),
+    "vv_transformer_apg_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vv_apg_coef": (C.c_int, [C.c_void_p, C.POINTER(vv_apg_coef_args), C.c_void_p]),
+    "vv_ode_stage_apg": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_apg_stage_args), C.c_void_p]),
     "vv_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_preprocess_h": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -387,6 +408,7 @@ class HipSynth:
             self.n_steps = n_steps
             self.n_evals = n_steps * plan.s
             self.plan = plan             # the evaluation times a guidance interval is compared with (guidance_mask)
+            self._t_host = (C.c_float * self.n_evals)(*[float(v) for v in plan.t])     # the same times for projected guidance (vv_apg_args.t_host)
             self.grid_generation += 1    # vv_set_ode_plan frees and reallocates the tables a captured step graph points into
 
     # ------------------------------------------------------------------ stages
@@ -432,21 +454,39 @@ class HipSynth:
         or one per item) and the B strengths (a None strength = the model's); None = every item guided everywhere."""
         return guidance_mask(self.plan, interval, [self.spec.cfg_strength if v is None else v for v in strengths])
 
+    def apg_tensors(self, etas, norms):
+        """N11: the ``apg`` of transformer_steps from B host values each -- eta (None = 1) and the RMS cap (None = no cap), validated by
+        model_spec.check_apg.  None when projected guidance is off for every item (the call then goes to the existing entries), else
+        (eta, norm) fp32 [B] on the device, a cap of 0 standing for "none"."""
+        etas, norms = list(etas), list(norms)
+        if len(etas) != len(norms):
+            raise ValueError("apg_tensors: one eta and one norm per item")
+        pairs = [check_apg(e, r) for e, r in zip(etas, norms)]
+        if all(p is None for p in pairs):
+            return None
+        eta = torch.tensor([1.0 if p is None else p[0] for p in pairs], dtype=torch.float32).to(self.device)
+        norm = torch.tensor([0.0 if p is None or p[1] is None else p[1] for p in pairs], dtype=torch.float32).to(self.device)
+        return eta, norm
+
     def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None,
-                          cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, apg=None) -> torch.Tensor:
         """x fp32 [B,N,n_mel] updated in place on the device.  seq_len_host (optional list / array of the B lengths, the same
         values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
         cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's.
         guide (optional uint8 [n_evals, B] on the HOST, N8): guided(b, e) of every evaluation of the plan in force
-        (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere."""
+        (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere.
+        apg (optional pair (eta, norm) of fp32 [B] device tensors, either None, N11): projected guidance per item
+        (vv_transformer_steps_apg; apg_tensors builds it); None, or a pair of Nones = off: the existing entries."""
         B, N, M = x.shape
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
         if seq_len_host is None:
             seq_len_host = pre.get("seq_len_host")
-        if cfg is not None or guide is not None:
+        if apg is not None and apg[0] is None and apg[1] is None:
+            apg = None
+        if cfg is not None or guide is not None or apg is not None:
             assert cfg is None or (cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,)), "cfg: fp32 [B] on the device"
             host = None if seq_len_host is None else (C.c_int32 * B)(*[int(v) for v in seq_len_host])
-            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide)
+            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg)
             return x
         with self._lock, torch.cuda.device(self.device):
             tail = (pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr(), pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr(),
@@ -467,13 +507,27 @@ class HipSynth:
             self._check(self.lib.vv_transformer_guided_ws_bytes(self.ctx, int(B), int(N), host, C.byref(nb)))
         return int(nb.value)
 
+    def apg_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
+        """Bytes of a caller-owned workspace for a call with projected guidance (vv_transformer_apg_ws_bytes; the same with any mask)."""
+        host = (C.c_int32 * B)(*[int(v) for v in seq_len_host])
+        nb = C.c_uint64()
+        with self._lock:
+            self._check(self.lib.vv_transformer_apg_ws_bytes(self.ctx, int(B), int(N), host, C.byref(nb)))
+        return int(nb.value)
+
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
                              cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                             guide: Optional[torch.Tensor] = None) -> None:
+                             guide: Optional[torch.Tensor] = None, apg=None) -> None:
         """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
         the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host).  guide: a contiguous uint8
         HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
-        ld_guide >= B)."""
+        ld_guide >= B).  apg: None, or a pair (eta, norm) of fp32 [B] device tensors (either None), handed to
+        vv_transformer_steps_apg with the times of the plan in force."""
+        B = x.shape[0]
+        if apg is not None:
+            if len(apg) != 2 or any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                                                           and t.is_contiguous() and t.shape == (B,)) for t in apg):
+                raise ValueError("apg must be a pair (eta, norm) of fp32 [B] device tensors or Nones")
         if guide is not None:
             if not (isinstance(guide, torch.Tensor) and guide.device.type == "cpu" and guide.dtype == torch.uint8 and guide.dim() == 2
                     and guide.is_contiguous() and guide.shape[0] == self.n_evals):
@@ -490,7 +544,11 @@ class HipSynth:
             a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
         a.cfg_item = _ptr(cfg)
         with self._lock, torch.cuda.device(self.device):
-            if guide is not None:
+            if apg is not None:
+                q = vv_apg_args(_ptr(apg[0]), _ptr(apg[1]), C.cast(self._t_host, C.c_void_p))
+                self._check(self.lib.vv_transformer_steps_apg(self.ctx, C.byref(a), None if guide is None else guide.data_ptr(),
+                                                              0 if guide is None else int(guide.shape[1]), C.byref(q), self._stream()))
+            elif guide is not None:
                 self._check(self.lib.vv_transformer_steps_guided(self.ctx, C.byref(a), guide.data_ptr(), int(guide.shape[1]), self._stream()))
             else:
                 self._check(self.lib.vv_transformer_steps_ex(self.ctx, C.byref(a), self._stream()))
@@ -564,19 +622,20 @@ class HipSynth:
 
     def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: Optional[torch.Tensor], t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
-                         audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, noise_keys=None):
+                         audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, noise_keys=None,
+                         apg=None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
         noise fp32 [B, N, n_mel] on the device, or None with noise_keys = (model_spec.noise_keys rows): the noise is then drawn on the
         device (``noise``) and nothing of it crosses PCIe.  Exactly one of the two.
         gen_frames (host list, optional): per-item generated frames; lets the vocoder run in length buckets on ragged batches.
         seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
         cfg (optional fp32 [B] on the device): per-item guidance strength.  guide (optional uint8 [n_evals, B] on the host): the
-        guidance mask of transformer_steps."""
+        guidance mask of transformer_steps.  apg (optional pair of fp32 [B] device tensors): its projected guidance."""
         self._one_noise(noise, noise_keys)
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, seq_len, N)
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
             if pcm.shape[1] < t_gen_max * self.spec.hop_length:
@@ -645,12 +704,12 @@ class HipSynth:
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
                    noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
-                   guide: Optional[torch.Tensor] = None, noise_keys=None):
+                   guide: Optional[torch.Tensor] = None, noise_keys=None, apg=None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
         transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device) or, in its place, noise_keys =
-        model_spec.noise_keys rows (drawn on the device; exactly one of the two).
+        model_spec.noise_keys rows (drawn on the device; exactly one of the two).  cfg / guide / apg: as transformer_steps.
         Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = min(L_b, the vocoder's
         output of N_b frames) samples -- L_b with the HiFi-GAN (hop * N_b >= L_b), hop * (N_b - 1) with Vocos (the rest is zeros)."""
         s = self.spec
@@ -666,7 +725,7 @@ class HipSynth:
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, pre["seq_len"], N)
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
