@@ -566,6 +566,31 @@ VV_API int vv_pcm_resample(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int
 VV_API int vv_pcm_encode(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_n, int kind, uint8_t* y,
                          int64_t n_y, void* stream);
 
+
+/* ---- N12 loudness normalisation of the joined signal: ITU-R BS.1770-4 integrated loudness with both gates, a gain to a
+ * target level under a SAMPLE-peak ceiling, applied in HBM.  The arithmetic is pinned by core/audio_processor.py (normalize_loudness),
+ * which the kernels equal bit for bit; the call never synchronises and reads nothing back.
+ *   x        int16, the requests' joined signals at the model rate; sub = rate / 10 samples (a 100 ms sub-block), sub >= VV_LOUD_RUN
+ *   rows     R x 4 int64 {src_off, n, dst_off, run_off} in device memory and the same rows in HOST memory (rows_host, checked by the call):
+ *            request r is x[src_off, +n) -> y[dst_off, +n); run_off = the sum over the rows before it of
+ *            (n / sub) * ceil(sub / VV_LOUD_RUN) + ceil((n % sub) / VV_LOUD_RUN), its first run in the scratch
+ *   tables   43 float64 on the device, computed on the host for the rate (audio_processor.loudness_tables): the two biquads b1[3] a1[2]
+ *            b2[3] a2[2], the zero-input run tables M_full[4][4] and M_last[4][4] (row major), ABS = 10^((-70 + 0.691) / 10)
+ *   params   R x 2 float64 {T, c}: T = 10^((target + 0.691) / 10), T <= 0 = measure only; c = 32767 * 10^(peak_dbfs / 20)
+ *   stats    R x 4 float64 {zbar, kept, P, g}: gated mean square, blocks kept, max |x|, the gain (exactly 1 when nothing is kept, T <= 0
+ *            or P = 0).  The loudness itself, -0.691 + 10 log10(zbar), is the host's to compute.
+ *   y        int16: y[i] = clamp(rint(x[i] * g), -32768, 32767) in float64, ties to even, written once each, nothing outside the rows.
+ *            NULL = measure only; y == x with dst_off == src_off = in place.  Rows must not overlap on y (the caller's check).  y may start
+ *            at any even byte: the 8-byte stores are laid on its address.
+ *   ws       ws_bytes >= what vv_pcm_loudness_ws_bytes returns for the rows' total runs, 8-byte aligned.
+ * -22, and nothing is launched, for sub < VV_LOUD_RUN, R < 1, a null or misaligned pointer, a ws that is too small, a row outside
+ * n_x / n_y or with a wrong run_off. */
+#define VV_LOUD_RUN 128
+VV_API uint64_t vv_pcm_loudness_ws_bytes(int64_t total_runs, int R);
+VV_API int vv_pcm_loudness(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int64_t sub,
+                           const double* tables, const double* params, int16_t* y, int64_t n_y, double* stats, void* ws, uint64_t ws_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,205 @@ def encode_output(x: np.ndarray, encoding: str) -> np.ndarray:
     raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
 
 
+# ---------------------------------------------------------------------- N12: loudness normalisation (ITU-R BS.1770-4 integrated, gated)
+# The arithmetic below IS the specification: the device kernels (csrc/vv_loudness.hip) compute the same float64
+# operations in the same order, so this mirror and the device agree bit for bit, and so does a request alone or in a batch.
+LOUD_RUN = 128                       # VV_LOUD_RUN: samples per independent run of the recurrence, counted from a sub-block's first sample
+LOUD_TABLE_DOUBLES = 43              # b1[3] a1[2] | b2[3] a2[2] | M_full[4][4] | M_last[4][4] | ABS
+LOUDNESS_RANGE = (-60.0, -5.0)       # accepted targets, LUFS
+PEAK_DBFS_RANGE = (-20.0, 0.0)       # accepted sample-peak ceilings, dBFS
+_LOUD_TABLES = {}
+
+
+def check_loudness(loudness, peak_dbfs=-1.0):
+    """Validate a loudness target (LUFS, None = off) and a sample-peak ceiling (dBFS): -> (float or None, float)."""
+    if loudness is not None:
+        if isinstance(loudness, bool) or not isinstance(loudness, (int, float, np.integer, np.floating)):
+            raise ValueError("output_loudness must be a number of LUFS or None")
+        loudness = float(loudness)
+        if not LOUDNESS_RANGE[0] <= loudness <= LOUDNESS_RANGE[1]:             # NaN fails both comparisons
+            raise ValueError("output_loudness must be between -60 and -5 LUFS")
+    if isinstance(peak_dbfs, bool) or not isinstance(peak_dbfs, (int, float, np.integer, np.floating)):
+        raise ValueError("output_peak_dbfs must be a number of dBFS")
+    peak_dbfs = float(peak_dbfs)
+    if not PEAK_DBFS_RANGE[0] <= peak_dbfs <= PEAK_DBFS_RANGE[1]:
+        raise ValueError("output_peak_dbfs must be between -20 and 0 dBFS")
+    return loudness, peak_dbfs
+
+
+def k_weighting(sr: int):
+    """(b1, a1, b2, a2) of the K-weighting at ``sr`` Hz: the shelf and the high-pass of BS.1770 from their analogue prototypes through the
+    bilinear transform (a = [a1, a2] without the leading 1).  At 48 kHz this is the Recommendation's table to 14 digits."""
+    sr = int(sr)
+    f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+    K = np.tan(np.pi * f0 / sr)
+    Vh = np.power(10.0, G / 20.0)
+    Vb = np.power(Vh, 0.4996667741545416)
+    a0 = 1.0 + K / Q + K * K
+    b1 = np.array([(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0], np.float64)
+    a1 = np.array([2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], np.float64)
+    f0, Q = 38.13547087602444, 0.5003270373238773
+    K = np.tan(np.pi * f0 / sr)
+    a0 = 1.0 + K / Q + K * K
+    b2 = np.array([1.0, -2.0, 1.0], np.float64)
+    a2 = np.array([2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0], np.float64)
+    return b1, a1, b2, a2
+
+
+def _loud_step(u, s, b1, a1, b2, a2):
+    """One sample of the two biquads, direct form II transposed; u and the four states are arrays over runs.  Every product and sum is
+    rounded separately (numpy never fuses), in the order of the specification.  -> (y2, new states)."""
+    s0, s1, s2, s3 = s
+    y1 = b1[0] * u + s0
+    n0 = (b1[1] * u - a1[0] * y1) + s1
+    n1 = b1[2] * u - a1[1] * y1
+    y2 = b2[0] * y1 + s2
+    n2 = (b2[1] * y1 - a2[0] * y2) + s3
+    n3 = b2[2] * y1 - a2[1] * y2
+    return y2, (n0, n1, n2, n3)
+
+
+def _loud_run_lengths(sub: int):
+    """(runs per sub-block, length of the last one): 2400 = 18 * 128 + 96 -> (19, 96)."""
+    rps = -(-int(sub) // LOUD_RUN)
+    return rps, int(sub) - (rps - 1) * LOUD_RUN
+
+
+def loudness_tables(sr: int) -> np.ndarray:
+    """The float64 table the device reads (LOUD_TABLE_DOUBLES values): coefficients, M_full, M_last (row major; column j = the state
+    after a run's length of zero input from unit state j, computed with the step above), ABS = 10^((-70 + 0.691) / 10)."""
+    sr = int(sr)
+    if sr not in _LOUD_TABLES:
+        if sr < 10 * LOUD_RUN or sr % 10:
+            raise ValueError(f"loudness: the sample rate must be a multiple of 10 Hz and at least {10 * LOUD_RUN} Hz, got {sr}")
+        b1, a1, b2, a2 = k_weighting(sr)
+        _rps, last = _loud_run_lengths(sr // 10)
+
+        def transition(length):
+            s = tuple(np.eye(4, dtype=np.float64)[i].copy() for i in range(4))      # s[i][j] = state i when started from unit state j
+            zero = np.zeros(4, np.float64)
+            for _ in range(length):
+                _y, s = _loud_step(zero, s, b1, a1, b2, a2)
+            return np.stack(s)                                                     # [i][j]
+
+        t = np.concatenate([b1, a1, b2, a2, transition(LOUD_RUN).reshape(-1), transition(last).reshape(-1),
+                            [np.power(10.0, (-70.0 + 0.691) / 10.0)]]).astype(np.float64)
+        assert t.size == LOUD_TABLE_DOUBLES
+        t.setflags(write=False)
+        _LOUD_TABLES[sr] = t
+    return _LOUD_TABLES[sr]
+
+
+def loudness_target(target) -> float:
+    """T = 10^((target + 0.691) / 10): the mean square a signal of ``target`` LUFS has after K-weighting; 0 = measure only."""
+    return 0.0 if target is None else float(np.power(10.0, (float(target) + 0.691) / 10.0))
+
+
+def loudness_ceiling(peak_dbfs: float) -> float:
+    """c = 32767 * 10^(peak_dbfs / 20): the largest sample magnitude the gain may produce."""
+    return float(32767.0 * np.power(10.0, float(peak_dbfs) / 20.0))
+
+
+def loudness_gate(q, sub: int):
+    """Gated mean of BS.1770 from the sub-block sums q_j (100 ms each, ``sub`` samples), linear domain only: 400 ms blocks
+    z_j = (((q_j + q_j+1) + q_j+2) + q_j+3) / (4 sub); absolute gate z > ABS; relative gate z > 0.1 * mean of those; both strict.
+    Every mean is a sequential ascending sum over a count.  -> (zbar, kept); (0.0, 0) when nothing is kept."""
+    q = np.asarray(q, np.float64).reshape(-1)
+    if q.size < 4:
+        return 0.0, 0
+    z = (((q[:-3] + q[1:-2]) + q[2:-1]) + q[3:]) / np.float64(4 * int(sub))
+    ABS = np.power(10.0, (-70.0 + 0.691) / 10.0)
+    a = z[z > ABS]
+    if a.size == 0:
+        return 0.0, 0
+    gamma = 0.1 * (np.cumsum(a)[-1] / np.float64(a.size))            # np.cumsum accumulates strictly in order
+    k = a[a > gamma]
+    if k.size == 0:
+        return 0.0, 0
+    return float(np.cumsum(k)[-1] / np.float64(k.size)), int(k.size)
+
+
+def _loud_subblock_sums(x: np.ndarray, sr: int) -> np.ndarray:
+    """q_j of the complete 100 ms sub-blocks of int16 ``x`` by the run decomposition of the specification (passes A, B, C)."""
+    t = loudness_tables(sr)
+    b1, a1, b2, a2 = t[0:3], t[3:5], t[5:8], t[8:10]
+    M = (t[10:26].reshape(4, 4), t[26:42].reshape(4, 4))
+    sub = int(sr) // 10
+    rps, last = _loud_run_lengths(sub)
+    J = x.size // sub
+    if J == 0:
+        return np.zeros(0, np.float64)
+    u = (x[: J * sub].astype(np.float64) / 32768.0).reshape(J, sub)
+    full = u[:, : (rps - 1) * LOUD_RUN].reshape(J, rps - 1, LOUD_RUN)              # the full runs and the last run of every sub-block
+    tail = u[:, (rps - 1) * LOUD_RUN:]
+
+    def run(block, s, power):
+        """block [..., L]; s = four arrays [...]; -> (end states, sum of y2^2 in sample order)."""
+        p = np.zeros(block.shape[:-1], np.float64)
+        for i in range(block.shape[-1]):
+            y2, s = _loud_step(block[..., i], s, b1, a1, b2, a2)
+            if power:
+                p = p + y2 * y2
+        return s, p
+
+    z4 = lambda shape: tuple(np.zeros(shape, np.float64) for _ in range(4))
+    Ef, _ = run(full, z4(full.shape[:-1]), False)                                  # pass A: zero-state end states
+    El, _ = run(tail, z4((J,)), False)
+    E = np.empty((J, rps, 4), np.float64)
+    for i in range(4):
+        E[:, : rps - 1, i] = Ef[i]
+        E[:, rps - 1, i] = El[i]
+    E = E.reshape(J * rps, 4)
+    S0 = np.empty_like(E)                                                          # pass B: every run's start state, in ascending run order
+    S = np.zeros(4, np.float64)
+    for r in range(J * rps):
+        S0[r] = S
+        m = M[1] if r % rps == rps - 1 else M[0]
+        S = ((((m[:, 0] * S[0] + m[:, 1] * S[1]) + m[:, 2] * S[2]) + m[:, 3] * S[3]) + E[r])
+    S0 = S0.reshape(J, rps, 4)
+    _, pf = run(full, tuple(S0[:, : rps - 1, i] for i in range(4)), True)          # pass C: from the true start states
+    _, pl = run(tail, tuple(S0[:, rps - 1, i] for i in range(4)), True)
+    q = np.zeros(J, np.float64)
+    for k in range(rps - 1):                                                       # ascending sum of the sub-block's runs
+        q = q + pf[:, k]
+    return q + pl
+
+
+def _as_pcm16(pcm) -> np.ndarray:
+    x = np.asarray(pcm).reshape(-1)
+    if x.dtype != np.int16:
+        raise ValueError("loudness: int16 PCM expected")
+    return x
+
+
+def measure_loudness(pcm, sr: int):
+    """Integrated loudness of int16 ``pcm`` at ``sr`` Hz (BS.1770-4 gating, K-weighting by the bilinear transform at ``sr``; the incomplete
+    last 100 ms are not measured).  -> (L in LUFS or -inf when no block is kept, zbar, kept, sample peak max |x|)."""
+    x = _as_pcm16(pcm)
+    zbar, kept = loudness_gate(_loud_subblock_sums(x, sr), int(sr) // 10)
+    peak = int(np.abs(x.astype(np.int32)).max(initial=0))
+    return (float(-0.691 + 10.0 * np.log10(zbar)) if kept else float("-inf")), zbar, kept, peak
+
+
+def loudness_gain(zbar: float, kept: int, peak: int, T: float, c: float) -> float:
+    """The gain of the specification: sqrt(T / zbar), limited so that peak * g <= c; exactly 1 when nothing is kept, T <= 0 or peak == 0."""
+    if kept < 1 or not T > 0.0 or peak == 0:
+        return 1.0
+    g = np.sqrt(np.float64(T) / np.float64(zbar))
+    if np.float64(peak) * g > np.float64(c):
+        g = np.float64(c) / np.float64(peak)
+    return float(g)
+
+
+def normalize_loudness(pcm, sr: int, target, peak_dbfs: float = -1.0) -> np.ndarray:
+    """int16 ``pcm`` scaled to ``target`` LUFS under a sample-peak ceiling of ``peak_dbfs``: the host mirror of vv_pcm_loudness, bit for
+    bit.  y = clamp(rint(x * g)) in float64, ties to even; target None = a copy."""
+    x = _as_pcm16(pcm)
+    _L, zbar, kept, peak = measure_loudness(x, sr)
+    g = loudness_gain(zbar, kept, peak, loudness_target(target), loudness_ceiling(peak_dbfs))
+    return np.clip(np.rint(x.astype(np.float64) * np.float64(g)), -32768.0, 32767.0).astype(np.int16)
+
+
 class AudioProcessor:
     """Static helpers, same names and semantics as the reference class."""
 

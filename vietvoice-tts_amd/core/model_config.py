@@ -76,6 +76,10 @@ class ModelConfig:
     output_sample_rate: Optional[int] = None   # None = sample_rate; else the output is rate-converted (band-limited polyphase FIR, vv_pcm_resample)
     output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode).  A rate or an encoding runs on the
                                             # device on the HIP engine, through the host mirrors on injected sessions
+    output_loudness: Optional[float] = None  # programme loudness of every utterance in LUFS (ITU-R BS.1770-4 integrated, gated), -60 ... -5; None = off.
+                                            # Measured and applied after the join, before the output rate and the encoding (vv_pcm_loudness on the HIP
+                                            # engine, audio_processor.normalize_loudness on injected sessions).  Not available in synthesize_stream
+    output_peak_dbfs: float = -1.0          # sample-peak ceiling of the loudness gain in dBFS, -20 ... 0 (no oversampled true peak)
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -104,6 +108,8 @@ class ModelConfig:
             self.output_sample_rate = int(self.output_sample_rate)
             if not 4000 <= self.output_sample_rate <= 192000:
                 raise ValueError("output_sample_rate must be between 4000 and 192000 Hz")
+        from .audio_processor import check_loudness
+        self.output_loudness, self.output_peak_dbfs = check_loudness(self.output_loudness, self.output_peak_dbfs)
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

@@ -165,31 +165,42 @@ class TTSEngine:
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
 
-    def _device_output(self) -> bool:
+    def _device_output(self, loudness=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate or an encoding is set.  False = today's path: one copy per chunk group, the numpy join."""
+        rate, an encoding or a loudness target (the engine's, or a request's own: ``loudness``) is set.  False = today's path: one copy
+        per chunk group, the numpy join."""
         rate, enc = self._output_options()
-        return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16")
+        return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16"
+                                                                  or self.config.output_loudness is not None or loudness is not None)
 
-    def _finish_host(self, waves) -> np.ndarray:
-        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of the output rate / encoding."""
-        from .audio_processor import encode_output, resample_output
+    def _finish_host(self, waves, loudness=None) -> np.ndarray:
+        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of the loudness normalisation
+        (N12; ``loudness`` = the request's own target, None = the engine's), the output rate and the encoding."""
+        from .audio_processor import encode_output, normalize_loudness, resample_output
         final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
+        loudness = self.config.output_loudness if loudness is None else loudness
+        if loudness is not None:
+            final = normalize_loudness(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, loudness, self.config.output_peak_dbfs)
         rate, enc = self._output_options()
         if rate is not None:
             final = resample_output(final, self.config.sample_rate, rate)
         return encode_output(final, enc) if enc != "pcm16" else final
 
-    def _finish_device(self, dev_pcm, counts) -> List[np.ndarray]:
+    def _finish_device(self, dev_pcm, counts, loudness=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
-        one HipSynth.finish_output call (join, rate, encoding in HBM; one device-to-host copy)."""
+        one HipSynth.finish_output call (join, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per request its
+        own target or None (= the engine's)."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
             plans.append(spans[pos: pos + n])
             pos += n
         rate, enc = self._output_options()
-        return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc)
+        loud = self.config.output_loudness
+        if loudness is not None:
+            loud = [loud if v is None else v for v in loudness]
+        return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
+                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
                            apg_etas=None, apg_norms=None):
@@ -355,7 +366,15 @@ class TTSEngine:
         Overlap-save: the improved cross-fade only rewrites the last ``cross_fade_duration`` of what has been joined
         so far (audio_processor.py:122-192), so everything before that tail is final and can be yielded.  The joiner
         (``CrossfadeStream``) keeps only that tail: each raw chunk is clip-repaired once, emitted samples are never
-        revisited, and the concatenation of all yielded blocks equals ``synthesize(text)`` sample for sample."""
+        revisited, and the concatenation of all yielded blocks equals ``synthesize(text)`` sample for sample.
+        With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance."""
+        if self.config.output_loudness is not None:       # checked here, not inside the generator: the caller hears of it without iterating
+            raise ValueError("synthesize_stream cannot honour output_loudness: the integrated measure needs the whole utterance; "
+                             "use synthesize, or unset output_loudness")
+        return self._stream_blocks(text, gender, group, area, emotion, sample_iteration, reference_audio, reference_text, chunks_per_step)
+
+    def _stream_blocks(self, text, gender, group, area, emotion, sample_iteration, reference_audio, reference_text, chunks_per_step):
+        """The generator behind ``synthesize_stream``."""
         speed = self.config.speed
         ref_audio, ref_text = self.model_session_manager.select_sample(gender, group, area, emotion, sample_iteration,
                                                                        reference_audio, reference_text)
@@ -447,7 +466,8 @@ class TTSEngine:
                                                apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]))
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
-                    wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options())[0]
+                    wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options(),
+                                             loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs)[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

@@ -11,7 +11,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.4 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.5 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -650,6 +650,45 @@ int vv_pcm_encode(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows,
         return c->fail(-22, "vv_pcm_encode: bad arguments (n_rows >= 1; kind 1 = mu-law, 2 = A-law; y 8-byte aligned; no null pointer)");
     Prof p(c, VV_PROF_ELEMWISE, 0, 2.0 * (double)n_x + (double)n_y, st);
     KCHK(c, vvk_pcm_encode(x, (long long)n_x, (const long long*)rows, n_rows, (long long)max_n, kind, y, (long long)n_y, st, &m__));
+    return 0;
+}
+
+// N12: loudness normalisation of the joined signal.  The rows come in host memory too, so everything is checked before a launch.
+uint64_t vv_pcm_loudness_ws_bytes(int64_t total_runs, int R) { return vvk_pcm_loudness_ws_bytes((long long)total_runs, R); }
+
+int vv_pcm_loudness(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int64_t sub,
+                    const double* tables, const double* params, int16_t* y, int64_t n_y, double* stats, void* ws, uint64_t ws_bytes,
+                    void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (R < 1 || R > 65535 || sub < VV_LOUD_RUN || sub > (1 << 24) || n_x < 0 || n_y < 0)
+        return c->fail(-22, "vv_pcm_loudness: bad sizes (1 <= R <= 65535; sub >= %d)", VV_LOUD_RUN);
+    if (!x || !rows || !rows_host || !tables || !params || !stats || !ws)
+        return c->fail(-22, "vv_pcm_loudness: null pointer (x, rows, rows_host, tables, params, stats, ws)");
+    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)tables % 8 || (uintptr_t)params % 8 || (uintptr_t)stats % 8 ||
+        (uintptr_t)ws % 8)
+        return c->fail(-22, "vv_pcm_loudness: misaligned pointer (x, y 2 bytes; rows, tables, params, stats, ws 8)");
+    const int64_t rps = (sub + VV_LOUD_RUN - 1) / VV_LOUD_RUN;
+    int64_t total_runs = 0, max_n = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 4 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[1] > n_x || q[0] > n_x - q[1] || q[1] >= ((int64_t)1 << 40))
+            return c->fail(-22, "vv_pcm_loudness: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (y && (q[2] < 0 || q[1] > n_y || q[2] > n_y - q[1]))
+            return c->fail(-22, "vv_pcm_loudness: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (y == x && q[2] != q[0]) return c->fail(-22, "vv_pcm_loudness: in place (y == x) needs dst_off == src_off, row %d", r);
+        if (q[3] != total_runs) return c->fail(-22, "vv_pcm_loudness: row %d: run_off is the sum of the runs of the rows before it", r);
+        const int64_t J = q[1] / sub;
+        total_runs += J * rps + (q[1] - J * sub + VV_LOUD_RUN - 1) / VV_LOUD_RUN;
+        if (q[1] > max_n) max_n = q[1];
+    }
+    if (ws_bytes < vvk_pcm_loudness_ws_bytes((long long)total_runs, R))
+        return c->fail(-22, "vv_pcm_loudness: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
+                       (unsigned long long)vvk_pcm_loudness_ws_bytes((long long)total_runs, R));
+    Prof p(c, VV_PROF_ELEMWISE, 60.0 * (double)n_x, 6.0 * (double)n_x + 128.0 * (double)total_runs, st);
+    KCHK(c, vvk_pcm_loudness(x, (long long)n_x, (const long long*)rows, R, (long long)sub, (long long)total_runs, (long long)max_n, tables,
+                             params, y, (long long)n_y, stats, ws, st, &m__));
     return 0;
 }
 

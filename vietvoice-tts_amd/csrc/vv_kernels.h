@@ -81,6 +81,11 @@ int vvk_pcm_resample(const int16_t* x, long long n_x, const long long* rows, int
                      int up, int down, int skip, int16_t* y, long long n_y, hipStream_t st, const char** err);
 int vvk_pcm_encode(const int16_t* x, long long n_x, const long long* rows, int n_rows, long long max_n, int kind, uint8_t* y, long long n_y,
                    hipStream_t st, const char** err);
+// N12 loudness normalisation (vv_loudness.hip): BS.1770 gated measurement by runs of 128 samples, gain under a peak ceiling, apply
+unsigned long long vvk_pcm_loudness_ws_bytes(long long total_runs, int R);
+int vvk_pcm_loudness(const int16_t* x, long long n_x, const long long* rows, int R, long long sub, long long total_runs, long long max_n,
+                     const double* tables, const double* params, int16_t* y, long long n_y, double* stats, void* ws, hipStream_t st,
+                     const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

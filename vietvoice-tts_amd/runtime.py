@@ -197,6 +197,9 @@ EXPORTS = {
     "vv_pcm_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "vv_pcm_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vv_pcm_loudness_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
+    "vv_pcm_loudness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -270,6 +273,7 @@ def _dt(s) -> Tuple[int, torch.dtype]:
 
 
 JOIN_MAX_N = 24576            # VV_JOIN_MAX_N of include/vvtts.h: the largest junction vv_join_chunks walks
+LOUD_RUN = 128                # VV_LOUD_RUN of include/vvtts.h: samples per independent run of the K-weighting recurrence
 _I64_MAX = (1 << 63) - 1
 
 
@@ -850,13 +854,94 @@ class HipSynth:
                                                y.data_ptr(), n_y, self._stream()))
         return y[:n_y]
 
+    # ------------------------------------------------------------------ loudness normalisation (N12)
+    def _loudness_tables(self, sr: int) -> torch.Tensor:
+        from .core.audio_processor import loudness_tables
+        cache = self.__dict__.setdefault("_loud_tables", {})
+        if int(sr) not in cache:
+            cache[int(sr)] = torch.from_numpy(loudness_tables(int(sr)).copy()).to(self.device)
+        return cache[int(sr)]
+
+    def pcm_loudness(self, x: torch.Tensor, rows, sr: int, targets, peak_dbfs: float = -1.0, out: Optional[torch.Tensor] = None,
+                     stats: bool = False):
+        """Loudness normalisation of R joined signals in one call (vv_pcm_loudness), bit for bit
+        core.audio_processor.normalize_loudness.  x int16 flat on the device at ``sr`` Hz; rows = HOST rows (src_off, n, dst_off);
+        targets = one LUFS value, or per request a value or None (None = measured, copied through unchanged); peak_dbfs = the sample-peak
+        ceiling.  out = None: a new buffer; out = "measure": nothing is written; out = a flat int16 device tensor (x itself with
+        dst_off == src_off = in place).  -> the output (None when measuring), and with ``stats`` also the R x 4 float64 DEVICE tensor
+        {zbar, kept, P, g}.  The rows are validated here; the call never synchronises."""
+        from .core.audio_processor import check_loudness, loudness_ceiling, loudness_target
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        sr = int(sr)
+        if sr % 10 or sr // 10 < LOUD_RUN:
+            raise ValueError(f"pcm_loudness: the sample rate must be a multiple of 10 Hz and at least {10 * LOUD_RUN} Hz, got {sr}")
+        sub = sr // 10
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) != 3 for r in rows) or len(rows) > 65535:
+            raise ValueError("pcm_loudness: 1 to 65535 rows of 3 entries {src_off, n, dst_off}")
+        R = len(rows)
+        if not isinstance(targets, (list, tuple)):
+            targets = [targets] * R
+        if len(targets) != R:
+            raise ValueError("pcm_loudness: one target per row")
+        par = []
+        for t in targets:
+            t, pk = check_loudness(t, peak_dbfs)
+            par.append([loudness_target(t), loudness_ceiling(pk)])
+        measure = isinstance(out, str) and out == "measure"
+        n_x = x.numel()
+        rps = -(-sub // LOUD_RUN)
+        full, runs, spans = [], 0, []
+        for so, n, do in rows:
+            if min(so, n, do) < 0 or so + n > n_x:
+                raise ValueError(f"pcm_loudness: row {[so, n, do]} does not fit the {n_x} samples of x")
+            full.append([so, n, do, runs])
+            runs += (n // sub) * rps + -(-(n % sub) // LOUD_RUN)
+            spans.append((do, do + n))
+        y = None
+        if not measure:
+            n_y = max(e for _b, e in spans)
+            if out is None:
+                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
+            else:
+                y = out
+                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
+            if y.numel() < n_y:
+                raise ValueError(f"pcm_loudness: out holds {y.numel()} samples, {n_y} are needed")
+            spans.sort()
+            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+                raise ValueError("pcm_loudness: rows overlap on the output")
+            if y.data_ptr() == x.data_ptr() and any(r[0] != r[2] for r in rows):
+                raise ValueError("pcm_loudness: in place needs dst_off == src_off")
+        rows_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 4)
+        rows_d = rows_h.to(self.device)
+        par_d = torch.tensor(par, dtype=torch.float64).reshape(-1, 2).to(self.device)
+        st = torch.empty((R, 4), dtype=torch.float64, device=self.device)
+        ws_bytes = int(self.lib.vv_pcm_loudness_ws_bytes(runs, R))
+        ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_pcm_loudness(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, sub,
+                                                 self._loudness_tables(sr).data_ptr(), par_d.data_ptr(), _ptr(y), 0 if y is None else y.numel(),
+                                                 st.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
+        return (y, st) if stats else y
+
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16"):
-        """The whole output stage of R requests on the caller's stream: join (-> output rate) (-> G.711), then ONE device-to-host copy of
-        the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.  -> a list of R numpy arrays:
-        int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
+                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0):
+        """The whole output stage of R requests on the caller's stream: join (-> loudness) (-> output rate) (-> G.711), then ONE
+        device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.
+        loudness = a target in LUFS for every request, or a per-request list with None entries (N12; None = nothing new is called);
+        peak_dbfs = its sample-peak ceiling.  -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
         from .core.audio_processor import resample_len
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
+        if isinstance(loudness, (list, tuple)):
+            if len(loudness) != len(lens):
+                raise ValueError("finish_output: one loudness entry per request")
+            if all(v is None for v in loudness):
+                loudness = None
+        if loudness is not None:           # in place on the joined buffer: the apply pass is elementwise
+            sel = [i for i in range(len(lens)) if not isinstance(loudness, (list, tuple)) or loudness[i] is not None]
+            tg = [loudness[i] for i in sel] if isinstance(loudness, (list, tuple)) else loudness
+            self.pcm_loudness(buf, [[offs[i], lens[i], offs[i]] for i in sel], sample_rate, tg, peak_dbfs, out=buf)
         if rate is not None and int(rate) != int(sample_rate):
             _taps, up, down, _skip = self._output_taps(int(sample_rate), int(rate))
             rows, pos = [], 0
