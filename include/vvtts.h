@@ -591,6 +591,43 @@ VV_API int vv_pcm_loudness(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int
                            const double* tables, const double* params, int16_t* y, int64_t n_y, double* stats, void* ws, uint64_t ws_bytes,
                            void* stream);
 
+
+/* ---- N13 look-ahead peak limiter of the joined signal: a sample-peak or 4x oversampled true-peak estimate, the gain
+ * that holds it under the ceiling, a sliding minimum and a raised-cosine window average over the look-ahead L, applied in HBM.  The
+ * arithmetic is pinned by core/audio_processor.py (limit_peaks), which the kernels equal bit for bit: all of it float64, every product
+ * and sum rounded on its own, every sum in ascending order.  Per request, v = 0 outside [0, n) and every other index clamped to it:
+ *     v[i] = x[i] * g
+ *     e[i] = |v[i]|                                           (mode 0, "sample")
+ *          = max(|v[i]|, |u1[i]|, |u2[i]|, |u3[i]|),  u_p[i] = sum_{j = -H+1 .. H} taps[4H + p - 4j] * v[i + j]      (mode 1, "true")
+ *     r[i] = c / e[i] where e[i] > c, else 1;    m[i] = min r[i - L .. i + L];    A[i] = sum_{k = -L .. L} window[k + L] * (1 - m[i + k])
+ *     s[i] = min(1 - A[i], r[i]);    y[i] = clamp(rint(v[i] * s[i]), -32768, 32767), ties to even
+ * so max |y| <= ceil(c) for any input, s is exactly 1 wherever no e > c lies within 2L + H samples, and y[i] depends on
+ * x[i - W .. i + W] only, W = 2L + VV_LIMIT_H: a block computed with W samples of context on each side equals the whole signal on its
+ * interior, which is all a stream needs.  The call never synchronises and reads nothing back.
+ *   x        int16, the requests' joined signals at the model rate
+ *   rows     R x 5 int64 {src_off, n, dst_off, out_lo, out_n} in device memory and the same rows in HOST memory (rows_host, checked by
+ *            the call): the limiter is computed over x[src_off, +n) as a whole signal; y[out_lo, out_lo + out_n) of it is written at
+ *            y[dst_off, +out_n).  Plain use: out_lo = 0, out_n = n
+ *   window   2L + 1 float64 on the device: 0.5 (1 + cos(pi k / (L + 1))) over its sum (audio_processor.limiter_window)
+ *   taps     8 VV_LIMIT_H + 1 float64 on the device: sinc(k / 4) * kaiser(8H + 1, 8.0) (audio_processor.limiter_taps); read in mode 1
+ *   params   R x 3 float64 {T, c, g0}: c = 32767 * 10^(peak_dbfs / 20); the pre-gain g = g0, or with meas given and T > 0
+ *            (T = 10^((target + 0.691) / 10)) g = sqrt(T / zbar), NOT capped by the peak, exactly 1 when kept = 0 or P = 0
+ *   meas     R x 4 float64 {zbar, kept, P, g}: the stats of a vv_pcm_loudness measure call on the same requests, read on the device; or NULL
+ *   stats    R x 4 float64 {g, e_max, s_min, n_limited} over the row's n samples (n_limited = samples with s < 1); exact
+ *   y        int16, written once each, nothing outside the rows' windows.  NULL = measure only; y == x with
+ *            dst_off == src_off + out_lo = in place.  Rows must not overlap on y (the caller's check).  y may start at any even byte
+ *   ws       ws_bytes >= vv_pcm_limit_ws_bytes(sum of n, sum of ceil(n / vv_pcm_limit_tile(L)), R), 8-byte aligned
+ * -22, and nothing is launched, for no context, R < 1, L outside 1 ... VV_LIMIT_MAX_L, a mode other than 0 or 1, a null or misaligned
+ * pointer, a ws that is too small, a negative field, out_lo + out_n > n, a row outside n_x / n_y.
+ * Not bounded: the true peak of the OUTPUT (the gain curve and the rounding change the interpolation), and a later rate change. */
+#define VV_LIMIT_H 12
+#define VV_LIMIT_MAX_L 1024
+VV_API int vv_pcm_limit_tile(int L);      /* samples per workgroup of the gain pass at look-ahead L (-22 outside 1 ... VV_LIMIT_MAX_L) */
+VV_API uint64_t vv_pcm_limit_ws_bytes(int64_t total_samples, int64_t total_tiles, int R);
+VV_API int vv_pcm_limit(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int L, int mode,
+                        const double* window, const double* taps, const double* params, const double* meas, int16_t* y, int64_t n_y,
+                        double* stats, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ import io
 import struct
 from math import gcd
 from pathlib import Path
-from typing import List, Tuple, Union
+from typing import List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -412,13 +412,134 @@ def loudness_gain(zbar: float, kept: int, peak: int, T: float, c: float) -> floa
     return float(g)
 
 
-def normalize_loudness(pcm, sr: int, target, peak_dbfs: float = -1.0) -> np.ndarray:
+def normalize_loudness(pcm, sr: int, target, peak_dbfs: float = -1.0, limiter=None) -> np.ndarray:
     """int16 ``pcm`` scaled to ``target`` LUFS under a sample-peak ceiling of ``peak_dbfs``: the host mirror of vv_pcm_loudness, bit for
-    bit.  y = clamp(rint(x * g)) in float64, ties to even; target None = a copy."""
+    bit.  y = clamp(rint(x * g)) in float64, ties to even; target None = a copy.  ``limiter`` = "sample" | "true" (N13): the gain is NOT
+    capped by the peak; the look-ahead limiter (limit_peaks) holds the ceiling instead, so a peaky voice reaches the target too."""
     x = _as_pcm16(pcm)
     _L, zbar, kept, peak = measure_loudness(x, sr)
+    if limiter is not None:
+        return limit_peaks(x, sr, peak_dbfs, limiter, gain=limiter_pregain(zbar, kept, peak, loudness_target(target)))[0]
     g = loudness_gain(zbar, kept, peak, loudness_target(target), loudness_ceiling(peak_dbfs))
     return np.clip(np.rint(x.astype(np.float64) * np.float64(g)), -32768.0, 32767.0).astype(np.int16)
+
+
+# ---------------------------------------------------------------------- N13: look-ahead peak limiter (sample or 4x oversampled true peak)
+# As with N12 the arithmetic below IS the specification (DESIGN §8 N13) and csrc/vv_limiter.hip computes the same float64 operations in
+# the same order.  Every quantity is a finite-window function of the input (a sliding minimum and a window average, no recursion), so a
+# sample's value depends on the 2L + H samples on either side only: alone, in a batch or cut into stream blocks it is the same.
+LIMIT_H = 12                         # VV_LIMIT_H: half length of the 4x interpolator in input samples (24 taps per phase)
+LIMIT_MAX_L = 1024                   # VV_LIMIT_MAX_L: the largest look-ahead in samples
+LIMITER_LOOKAHEAD_S = 0.005          # look-ahead in seconds: L = round(sr * 0.005) = 120 samples at 24 kHz
+LIMITER_MODES = ("sample", "true")   # mode 0 / 1 of vv_pcm_limit
+_LIMIT_TAPS = []
+_LIMIT_WINDOWS = {}
+
+
+def check_limiter(mode):
+    """Validate ``output_limiter``: None (off), "sample" or "true".  -> the value."""
+    if mode is not None and (not isinstance(mode, str) or mode not in LIMITER_MODES):
+        raise ValueError('output_limiter must be None, "sample" or "true"')
+    return mode
+
+
+def limiter_lookahead(sr: int) -> int:
+    """L = round(sr * LIMITER_LOOKAHEAD_S) samples, which must lie in 1 ... LIMIT_MAX_L."""
+    L = int(round(int(sr) * LIMITER_LOOKAHEAD_S))
+    if not 1 <= L <= LIMIT_MAX_L:
+        raise ValueError(f"limiter: a look-ahead of {LIMITER_LOOKAHEAD_S} s at {sr} Hz is {L} samples, outside 1 ... {LIMIT_MAX_L}")
+    return L
+
+
+def _check_lookahead(L) -> int:
+    if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= LIMIT_MAX_L:
+        raise ValueError(f"limiter: the look-ahead L must be an integer in 1 ... {LIMIT_MAX_L}")
+    return int(L)
+
+
+def limiter_taps() -> np.ndarray:
+    """h[k + 4H] = sinc(k / 4) * kaiser(8H + 1, 8.0)[k + 4H], k = -4H ... 4H: the 4x interpolator (8H + 1 float64; phase 0 is the sample
+    itself).  The device reads this table and never recomputes it."""
+    if not _LIMIT_TAPS:
+        k = np.arange(-4 * LIMIT_H, 4 * LIMIT_H + 1, dtype=np.float64)
+        h = (np.sinc(k / 4.0) * np.kaiser(8 * LIMIT_H + 1, 8.0)).astype(np.float64)
+        h.setflags(write=False)
+        _LIMIT_TAPS.append(h)
+    return _LIMIT_TAPS[0]
+
+
+def limiter_window(L: int) -> np.ndarray:
+    """w[k] = 0.5 (1 + cos(pi k / (L + 1))), k = -L ... L, divided by its numpy sum (2L + 1 float64): the average of step 5."""
+    L = _check_lookahead(L)
+    if L not in _LIMIT_WINDOWS:
+        k = np.arange(-L, L + 1, dtype=np.float64)
+        w = 0.5 * (1.0 + np.cos(np.pi * k / np.float64(L + 1)))
+        w = (w / w.sum()).astype(np.float64)
+        w.setflags(write=False)
+        _LIMIT_WINDOWS[L] = w
+    return _LIMIT_WINDOWS[L]
+
+
+def limiter_pregain(zbar: float, kept: int, peak: int, T: float) -> float:
+    """The pre-gain of the limiter under a loudness target: sqrt(T / zbar), NOT capped by the peak; exactly 1 when nothing is kept,
+    T <= 0 or peak == 0."""
+    if kept < 1 or not T > 0.0 or peak == 0:
+        return 1.0
+    return float(np.sqrt(np.float64(T) / np.float64(zbar)))
+
+
+def limiter_gains(pcm, c: float, mode: str, gain: float = 1.0, L: int = 120):
+    """Steps 1 to 6 of the specification on int16 ``pcm`` as a whole signal: -> (v, e, s), float64 arrays of its length."""
+    x = _as_pcm16(pcm)
+    check_limiter(mode)
+    if mode is None:
+        raise ValueError("limiter: a mode is needed")
+    L = _check_lookahead(L)
+    n, H = x.size, LIMIT_H
+    v = x.astype(np.float64) * np.float64(gain)                                    # 1
+    e = np.abs(v)                                                                  # 2
+    if mode == "true" and n:
+        h = limiter_taps()
+        vp = np.concatenate([np.zeros(H, np.float64), v, np.zeros(H, np.float64)])  # vp[i + H] = v[i], zero outside
+        for p in (1, 2, 3):
+            u = np.zeros(n, np.float64)
+            for j in range(-H + 1, H + 1):
+                u = u + h[4 * H + p - 4 * j] * vp[j + H: j + H + n]
+            e = np.maximum(e, np.abs(u))
+    c = np.float64(c)
+    over = e > c
+    s = np.ones(n, np.float64)
+    if not over.any():                                   # A is a sum of exact zeros: s is exactly 1 everywhere
+        return v, e, s
+    r = np.ones(n, np.float64)                                                     # 3
+    r[over] = c / e[over]
+    rp = np.concatenate([np.full(L, r[0]), r, np.full(L, r[-1])])                  # 4: r[clamp(j, 0, n - 1)]
+    m = rp[0: n].copy()
+    for k in range(1, 2 * L + 1):
+        np.minimum(m, rp[k: k + n], out=m)
+    d = 1.0 - m                                                                    # 5
+    dp = np.concatenate([np.full(L, d[0]), d, np.full(L, d[-1])])
+    w = limiter_window(L)
+    A = np.zeros(n, np.float64)
+    for k in range(2 * L + 1):
+        A = A + w[k] * dp[k: k + n]
+    return v, e, np.minimum(1.0 - A, r)                                            # 6
+
+
+def limit_peaks(pcm, sr: int, peak_dbfs: float = -1.0, mode: str = "true", gain: float = 1.0, L: Optional[int] = None):
+    """The look-ahead limiter of DESIGN §8 N13 on int16 ``pcm`` at ``sr`` Hz: the host mirror of vv_pcm_limit, bit for bit.
+    y = clamp(rint((x * gain) * s)) with the gain curve s of limiter_gains, so that max |y| <= ceil(c), c = loudness_ceiling(peak_dbfs).
+    mode "sample" limits the samples, "true" the 4x oversampled estimate of the peak between them.  L = the look-ahead in samples
+    (None = limiter_lookahead(sr)).  -> (int16 array, stats {g, e_max, s_min, n_limited})."""
+    x = _as_pcm16(pcm)
+    _t, peak_dbfs = check_loudness(None, peak_dbfs)
+    if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or not 0.0 < float(gain) < float("inf"):
+        raise ValueError("limiter: the gain must be a positive finite number")
+    L = limiter_lookahead(sr) if L is None else _check_lookahead(L)
+    v, e, s = limiter_gains(x, loudness_ceiling(peak_dbfs), mode, float(gain), L)
+    y = np.clip(np.rint(v * s), -32768.0, 32767.0).astype(np.int16)               # 7
+    stats = {"g": float(gain), "e_max": float(e.max(initial=0.0)), "s_min": float(s.min(initial=1.0)), "n_limited": int((s < 1.0).sum())}
+    return y, stats
 
 
 class AudioProcessor:
@@ -671,3 +792,41 @@ class OutputStream:
             return np.zeros(0, np.uint8 if self.encoding != "pcm16" else np.int16)
         y = self._emit(resample_len(self.n_seen, self.up, self.down))
         return self._encode(y) if self.encoding != "pcm16" else y
+
+
+class LimiterStream:
+    """The limiter of DESIGN §8 N13 for a STREAM of joined blocks at the model rate (``synthesize_stream``).  A sample depends on the
+    W = 2L + H samples on either side only, so ``push`` holds the newest W samples back, keeps W samples of context before them (2W of
+    history in all) and returns what became final; ``flush`` returns the rest.  The concatenation equals ``limit_peaks`` of the whole
+    signal bit for bit.  ``backend(hist, out_lo, out_n)`` computes the limiter over ``hist`` as a whole signal and returns
+    y[out_lo, out_lo + out_n): the host mirror, or the device kernel (HipSynth.limiter_stream_backend)."""
+
+    def __init__(self, sr: int, peak_dbfs: float = -1.0, mode: str = "true", backend=None, L: Optional[int] = None):
+        if check_limiter(mode) is None:
+            raise ValueError("LimiterStream: a mode is needed")
+        self.L = limiter_lookahead(sr) if L is None else _check_lookahead(L)
+        self.W = 2 * self.L + LIMIT_H
+        self._backend = backend or (lambda hist, lo, n: limit_peaks(hist, sr, peak_dbfs, mode, 1.0, self.L)[0][lo: lo + n])
+        self.hist = np.zeros(0, np.int16)     # input samples i0 ... n_seen - 1
+        self.i0 = 0
+        self.n_seen = 0
+        self.done = 0                         # samples returned so far
+
+    def _emit(self, end: int) -> np.ndarray:
+        if end <= self.done:
+            return np.zeros(0, np.int16)
+        y = np.asarray(self._backend(self.hist, self.done - self.i0, end - self.done), np.int16).reshape(-1)
+        self.done = end
+        keep_from = max(self.done - self.W, 0)                    # the oldest sample the next output depends on
+        if keep_from > self.i0:
+            self.hist, self.i0 = self.hist[keep_from - self.i0:], keep_from
+        return y
+
+    def push(self, block: np.ndarray) -> np.ndarray:
+        block = _as_pcm16(block)
+        self.hist = np.concatenate([self.hist, block])
+        self.n_seen += block.size
+        return self._emit(self.n_seen - self.W)
+
+    def flush(self) -> np.ndarray:
+        return self._emit(self.n_seen)

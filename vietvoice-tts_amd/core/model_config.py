@@ -80,6 +80,10 @@ class ModelConfig:
                                             # Measured and applied after the join, before the output rate and the encoding (vv_pcm_loudness on the HIP
                                             # engine, audio_processor.normalize_loudness on injected sessions).  Not available in synthesize_stream
     output_peak_dbfs: float = -1.0          # sample-peak ceiling of the loudness gain in dBFS, -20 ... 0 (no oversampled true peak)
+    output_limiter: Optional[str] = None    # None | "sample" | "true": a look-ahead limiter (5 ms) holds output_peak_dbfs instead of a smaller
+                                            # gain: with output_loudness the gain is no longer capped by the largest sample, without it the pre-gain is 1.
+                                            # "true" limits a 4x oversampled estimate of the peak between the samples.  vv_pcm_limit on the HIP engine,
+                                            # audio_processor.limit_peaks on injected sessions; synthesize_stream honours it (without output_loudness)
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -110,6 +114,8 @@ class ModelConfig:
                 raise ValueError("output_sample_rate must be between 4000 and 192000 Hz")
         from .audio_processor import check_loudness
         self.output_loudness, self.output_peak_dbfs = check_loudness(self.output_loudness, self.output_peak_dbfs)
+        from .audio_processor import check_limiter
+        check_limiter(self.output_limiter)
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

@@ -165,31 +165,37 @@ class TTSEngine:
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
 
-    def _device_output(self, loudness=None) -> bool:
+    def _device_output(self, loudness=None, limiter=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate, an encoding or a loudness target (the engine's, or a request's own: ``loudness``) is set.  False = today's path: one copy
-        per chunk group, the numpy join."""
+        rate, an encoding, a loudness target or a limiter (the engine's, or a request's own: ``loudness``, ``limiter``) is set.
+        False = today's path: one copy per chunk group, the numpy join."""
         rate, enc = self._output_options()
         return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16"
-                                                                  or self.config.output_loudness is not None or loudness is not None)
+                                                                  or self.config.output_loudness is not None or loudness is not None
+                                                                  or self.config.output_limiter is not None or limiter is not None)
 
-    def _finish_host(self, waves, loudness=None) -> np.ndarray:
+    def _finish_host(self, waves, loudness=None, limiter=None) -> np.ndarray:
         """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of the loudness normalisation
-        (N12; ``loudness`` = the request's own target, None = the engine's), the output rate and the encoding."""
-        from .audio_processor import encode_output, normalize_loudness, resample_output
+        (N12; ``loudness`` = the request's own target, None = the engine's), the limiter (N13; ``limiter`` likewise), the output rate
+        and the encoding."""
+        from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output
         final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
         loudness = self.config.output_loudness if loudness is None else loudness
+        limiter = self.config.output_limiter if limiter is None else limiter
         if loudness is not None:
-            final = normalize_loudness(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, loudness, self.config.output_peak_dbfs)
+            final = normalize_loudness(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, loudness, self.config.output_peak_dbfs,
+                                       **({} if limiter is None else {"limiter": limiter}))
+        elif limiter is not None:
+            final = limit_peaks(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, self.config.output_peak_dbfs, limiter)[0]
         rate, enc = self._output_options()
         if rate is not None:
             final = resample_output(final, self.config.sample_rate, rate)
         return encode_output(final, enc) if enc != "pcm16" else final
 
-    def _finish_device(self, dev_pcm, counts, loudness=None) -> List[np.ndarray]:
+    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
         one HipSynth.finish_output call (join, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per request its
-        own target or None (= the engine's)."""
+        own target or None (= the engine's); ``limiter`` likewise (N13)."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
@@ -199,8 +205,16 @@ class TTSEngine:
         loud = self.config.output_loudness
         if loudness is not None:
             loud = [loud if v is None else v for v in loudness]
+        lim = self.config.output_limiter
+        if limiter is not None:
+            lim = [lim if v is None else v for v in limiter]
+            if all(v is None for v in lim):
+                lim = None
+        if lim is None:                    # no limiter anywhere: exactly the call of N12
+            return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
+                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs)
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs)
+                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
                            apg_etas=None, apg_norms=None):
@@ -367,7 +381,8 @@ class TTSEngine:
         so far (audio_processor.py:122-192), so everything before that tail is final and can be yielded.  The joiner
         (``CrossfadeStream``) keeps only that tail: each raw chunk is clip-repaired once, emitted samples are never
         revisited, and the concatenation of all yielded blocks equals ``synthesize(text)`` sample for sample.
-        With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance."""
+        With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance.
+        ``output_limiter`` alone streams (N13): a LimiterStream in front of the output rate / encoding holds back 2L + H samples."""
         if self.config.output_loudness is not None:       # checked here, not inside the generator: the caller hears of it without iterating
             raise ValueError("synthesize_stream cannot honour output_loudness: the integrated measure needs the whole utterance; "
                              "use synthesize, or unset output_loudness")
@@ -395,6 +410,13 @@ class TTSEngine:
                 eng = self.model_session_manager.engine
                 backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
                 ostream = OutputStream(self.config.sample_rate, rate, enc, *backends)
+            lstream = None
+            if self.config.output_limiter is not None:            # N13: finite look-ahead, so the blocks still add up to synthesize()'s result
+                from .audio_processor import LimiterStream
+                eng = self.model_session_manager.engine
+                lstream = LimiterStream(self.config.sample_rate, self.config.output_peak_dbfs, self.config.output_limiter,
+                                        None if eng is None else eng.limiter_stream_backend(self.config.sample_rate, self.config.output_peak_dbfs,
+                                                                                            self.config.output_limiter))
             step = max(1, int(chunks_per_step))
             for lo in range(0, len(inputs_list), step):
                 with self._lock:
@@ -404,6 +426,14 @@ class TTSEngine:
                         waves = self._synthesize_sessions(inputs_list[lo: lo + step])
                 blocks = [joiner.push(w) for w in waves]
                 block = np.concatenate(blocks) if len(blocks) > 1 else blocks[0]
+                if lstream is not None:
+                    block = lstream.push(np.ascontiguousarray(block, dtype=np.int16))
+                if ostream is not None:
+                    block = ostream.push(block)
+                if block.size:
+                    yield block
+            if lstream is not None:
+                block = lstream.flush()
                 if ostream is not None:
                     block = ostream.push(block)
                 if block.size:
@@ -467,7 +497,8 @@ class TTSEngine:
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options(),
-                                             loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs)[0]
+                                             loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs,
+                                             **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}))[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

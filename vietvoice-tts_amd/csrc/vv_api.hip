@@ -11,7 +11,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.5 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.6 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -689,6 +689,54 @@ int vv_pcm_loudness(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* row
     Prof p(c, VV_PROF_ELEMWISE, 60.0 * (double)n_x, 6.0 * (double)n_x + 128.0 * (double)total_runs, st);
     KCHK(c, vvk_pcm_loudness(x, (long long)n_x, (const long long*)rows, R, (long long)sub, (long long)total_runs, (long long)max_n, tables,
                              params, y, (long long)n_y, stats, ws, st, &m__));
+    return 0;
+}
+
+// N13: look-ahead peak limiter of the joined signal.  As with N12 the rows come in host memory too: everything is checked before a launch.
+int vv_pcm_limit_tile(int L) { return L < 1 || L > VV_LIMIT_MAX_L ? -22 : vvk_pcm_limit_tile(L); }
+
+uint64_t vv_pcm_limit_ws_bytes(int64_t total_samples, int64_t total_tiles, int R) {
+    return vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R);
+}
+
+int vv_pcm_limit(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int L, int mode,
+                 const double* window, const double* taps, const double* params, const double* meas, int16_t* y, int64_t n_y, double* stats,
+                 void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (R < 1 || R > 65535 || L < 1 || L > VV_LIMIT_MAX_L || (mode != 0 && mode != 1) || n_x < 0 || n_y < 0)
+        return c->fail(-22, "vv_pcm_limit: bad sizes (1 <= R <= 65535; 1 <= L <= %d; mode 0 or 1)", VV_LIMIT_MAX_L);
+    if (!x || !rows || !rows_host || !window || !taps || !params || !stats || !ws)
+        return c->fail(-22, "vv_pcm_limit: null pointer (x, rows, rows_host, window, taps, params, stats, ws)");
+    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)window % 8 || (uintptr_t)taps % 8 || (uintptr_t)params % 8 ||
+        (uintptr_t)meas % 8 || (uintptr_t)stats % 8 || (uintptr_t)ws % 8)
+        return c->fail(-22, "vv_pcm_limit: misaligned pointer (x, y 2 bytes; rows, window, taps, params, meas, stats, ws 8)");
+    const int64_t tile = vvk_pcm_limit_tile(L);
+    int64_t total_samples = 0, total_tiles = 0, max_tiles = 0, max_out = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 5 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[4] < 0) return c->fail(-22, "vv_pcm_limit: row %d has a negative field", r);
+        if (q[1] > n_x || q[0] > n_x - q[1] || q[1] >= ((int64_t)1 << 40))
+            return c->fail(-22, "vv_pcm_limit: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (q[3] > q[1] || q[4] > q[1] - q[3]) return c->fail(-22, "vv_pcm_limit: row %d: out_lo + out_n exceeds n", r);
+        if (y && (q[4] > n_y || q[2] > n_y - q[4]))
+            return c->fail(-22, "vv_pcm_limit: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (y == x && q[4] > 0 && q[2] != q[0] + q[3])
+            return c->fail(-22, "vv_pcm_limit: in place (y == x) needs dst_off == src_off + out_lo, row %d", r);
+        const int64_t nt = (q[1] + tile - 1) / tile;
+        total_samples += q[1];
+        total_tiles += nt;
+        if (nt > max_tiles) max_tiles = nt;
+        if (q[4] > max_out) max_out = q[4];
+    }
+    if (ws_bytes < vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R))
+        return c->fail(-22, "vv_pcm_limit: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
+                       (unsigned long long)vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R));
+    Prof p(c, VV_PROF_ELEMWISE, (mode ? 640.0 : 500.0) * (double)total_samples * (double)(2 * L + 1) / 241.0,
+           20.0 * (double)total_samples + 2.0 * (double)max_out * R, st);
+    KCHK(c, vvk_pcm_limit(x, (long long)n_x, (const long long*)rows, R, L, mode, (long long)total_samples, (long long)total_tiles,
+                          (long long)max_tiles, (long long)max_out, window, taps, params, meas, y, (long long)n_y, stats, ws, st, &m__));
     return 0;
 }
 

@@ -86,6 +86,13 @@ unsigned long long vvk_pcm_loudness_ws_bytes(long long total_runs, int R);
 int vvk_pcm_loudness(const int16_t* x, long long n_x, const long long* rows, int R, long long sub, long long total_runs, long long max_n,
                      const double* tables, const double* params, int16_t* y, long long n_y, double* stats, void* ws, hipStream_t st,
                      const char** err);
+// N13 look-ahead peak limiter (vv_limiter.hip): gain plane by tiles (tile = vvk_pcm_limit_tile(L) samples), per-request stats, apply
+int vvk_pcm_limit_tile(int L);
+unsigned long long vvk_pcm_limit_ws_bytes(long long total_samples, long long total_tiles, int R);
+int vvk_pcm_limit(const int16_t* x, long long n_x, const long long* rows, int R, int L, int mode, long long total_samples,
+                  long long total_tiles, long long max_tiles, long long max_out, const double* window, const double* taps,
+                  const double* params, const double* meas, int16_t* y, long long n_y, double* stats, void* ws, hipStream_t st,
+                  const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

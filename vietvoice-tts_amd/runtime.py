@@ -200,6 +200,10 @@ EXPORTS = {
     "vv_pcm_loudness_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
     "vv_pcm_loudness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_pcm_limit_tile": (C.c_int, [C.c_int]),
+    "vv_pcm_limit_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int64, C.c_int]),
+    "vv_pcm_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -925,12 +929,114 @@ class HipSynth:
                                                  st.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
         return (y, st) if stats else y
 
+    # ------------------------------------------------------------------ look-ahead peak limiter (N13)
+    def _limiter_tables(self, L: int):
+        """(window, taps, tile) for a look-ahead: the host's float64 tables on the device, cached per L."""
+        from .core.audio_processor import limiter_taps, limiter_window
+        cache = self.__dict__.setdefault("_limit_tables", {})
+        if int(L) not in cache:
+            cache[int(L)] = (torch.from_numpy(limiter_window(int(L)).copy()).to(self.device),
+                             torch.from_numpy(limiter_taps().copy()).to(self.device), int(self.lib.vv_pcm_limit_tile(int(L))))
+        return cache[int(L)]
+
+    def pcm_limit(self, x: torch.Tensor, rows, sr: int, peak_dbfs: float = -1.0, mode: str = "true", gain=1.0, meas: Optional[torch.Tensor] = None,
+                  targets=None, L: Optional[int] = None, out=None, stats: bool = False):
+        """The look-ahead limiter on R joined signals in one call (vv_pcm_limit), bit for bit
+        core.audio_processor.limit_peaks.  x int16 flat on the device at ``sr`` Hz; rows = HOST rows (src_off, n, dst_off) or
+        (src_off, n, dst_off, out_lo, out_n): the limiter runs over the row's n samples as a whole signal and y[out_lo, +out_n) of it is
+        written at dst_off.  mode "sample" | "true"; peak_dbfs = the ceiling; gain = the pre-gain (one value or one per row).
+        meas = the R x 4 device tensor of a pcm_loudness(out="measure", stats=True) call on the same rows, with targets = one LUFS value
+        or per row a value or None: rows with a target take the uncapped loudness gain from meas on the device, the others ``gain``.
+        L = the look-ahead in samples (None = 5 ms).  out = None: a new buffer; "measure": nothing is written; a flat int16 device tensor
+        (x itself with dst_off == src_off + out_lo = in place).  -> the output (None when measuring), and with ``stats`` also the R x 4
+        float64 DEVICE tensor {g, e_max, s_min, n_limited}.  The rows are validated here; the call never synchronises."""
+        from .core.audio_processor import (LIMITER_MODES, _check_lookahead, check_limiter, check_loudness, limiter_lookahead, loudness_ceiling,
+                                           loudness_target)
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        if check_limiter(mode) is None:
+            raise ValueError("pcm_limit: a mode is needed")
+        L = limiter_lookahead(sr) if L is None else _check_lookahead(L)
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) not in (3, 5) for r in rows) or len(rows) > 65535:
+            raise ValueError("pcm_limit: 1 to 65535 rows of 3 entries {src_off, n, dst_off} or 5 {src_off, n, dst_off, out_lo, out_n}")
+        rows = [r if len(r) == 5 else [r[0], r[1], r[2], 0, r[1]] for r in rows]
+        R = len(rows)
+        if not isinstance(targets, (list, tuple)):
+            targets = [targets] * R
+        gains = list(gain) if isinstance(gain, (list, tuple)) else [gain] * R
+        if len(targets) != R or len(gains) != R:
+            raise ValueError("pcm_limit: one target and one gain per row")
+        if meas is None and any(t is not None for t in targets):
+            raise ValueError("pcm_limit: a loudness target needs meas, the stats of a pcm_loudness measure call")
+        if meas is not None:
+            assert meas.is_cuda and meas.dtype == torch.float64 and meas.is_contiguous() and tuple(meas.shape) == (R, 4)
+        c = loudness_ceiling(check_loudness(None, peak_dbfs)[1])
+        par = []
+        for t, g0 in zip(targets, gains):
+            if isinstance(g0, bool) or not isinstance(g0, (int, float)) or not 0.0 < float(g0) < float("inf"):
+                raise ValueError("pcm_limit: the gain must be a positive finite number")
+            par.append([loudness_target(check_loudness(t, peak_dbfs)[0]), c, float(g0)])
+        window, taps, tile = self._limiter_tables(L)
+        measure = isinstance(out, str) and out == "measure"
+        n_x = x.numel()
+        samples, tiles, spans = 0, 0, []
+        for so, n, do, lo, on in rows:
+            if min(so, n, do, lo, on) < 0 or so + n > n_x or lo + on > n:
+                raise ValueError(f"pcm_limit: row {[so, n, do, lo, on]} does not fit the {n_x} samples of x or its own n")
+            samples += n
+            tiles += -(-n // tile)
+            if on:
+                spans.append((do, do + on))
+        y = None
+        if not measure:
+            n_y = max((e for _b, e in spans), default=0)
+            if out is None:
+                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
+            else:
+                y = out
+                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
+            if y.numel() < n_y:
+                raise ValueError(f"pcm_limit: out holds {y.numel()} samples, {n_y} are needed")
+            spans.sort()
+            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+                raise ValueError("pcm_limit: rows overlap on the output")
+            if y.data_ptr() == x.data_ptr() and any(r[4] and r[2] != r[0] + r[3] for r in rows):
+                raise ValueError("pcm_limit: in place needs dst_off == src_off + out_lo")
+        rows_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 5)
+        rows_d = rows_h.to(self.device)
+        par_d = torch.tensor(par, dtype=torch.float64).reshape(-1, 3).to(self.device)
+        st = torch.empty((R, 4), dtype=torch.float64, device=self.device)
+        ws_bytes = int(self.lib.vv_pcm_limit_ws_bytes(samples, tiles, R))
+        ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_pcm_limit(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, L, LIMITER_MODES.index(mode),
+                                              window.data_ptr(), taps.data_ptr(), par_d.data_ptr(), _ptr(meas), _ptr(y),
+                                              0 if y is None else y.numel(), st.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
+        return (y, st) if stats else y
+
+    def limiter_stream_backend(self, sr: int, peak_dbfs: float = -1.0, mode: str = "true", L: Optional[int] = None):
+        """The ``backend(hist, out_lo, out_n)`` callable of core.audio_processor.LimiterStream on this device: the block and its context go
+        up, vv_pcm_limit runs over them as one signal and writes the window alone, which comes back."""
+        import numpy as np
+
+        def backend(hist, out_lo, out_n):
+            hist = np.ascontiguousarray(hist, dtype=np.int16).reshape(-1)
+            if out_n <= 0:
+                return np.zeros(0, np.int16)
+            y = self.pcm_limit(torch.from_numpy(hist).to(self.device), [[0, hist.size, 0, int(out_lo), int(out_n)]], sr, peak_dbfs, mode, L=L)
+            return y[: int(out_n)].cpu().numpy()
+
+        return backend
+
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0):
-        """The whole output stage of R requests on the caller's stream: join (-> loudness) (-> output rate) (-> G.711), then ONE
-        device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.
+                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None):
+        """The whole output stage of R requests on the caller's stream: join (-> loudness) (-> limiter) (-> output rate) (-> G.711), then
+        ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.
         loudness = a target in LUFS for every request, or a per-request list with None entries (N12; None = nothing new is called);
-        peak_dbfs = its sample-peak ceiling.  -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
+        peak_dbfs = its sample-peak ceiling.  limiter = None | "sample" | "true" for every request, or a per-request list (N13; None =
+        nothing new is called): a request with a limiter is measured only (pcm_loudness, out="measure") and takes its uncapped loudness
+        gain, or the gain 1 without a target, through pcm_limit in place; the others keep the capped gain of N12.
+        -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
         from .core.audio_processor import resample_len
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
         if isinstance(loudness, (list, tuple)):
@@ -938,7 +1044,27 @@ class HipSynth:
                 raise ValueError("finish_output: one loudness entry per request")
             if all(v is None for v in loudness):
                 loudness = None
-        if loudness is not None:           # in place on the joined buffer: the apply pass is elementwise
+        if isinstance(limiter, (list, tuple)):
+            if len(limiter) != len(lens):
+                raise ValueError("finish_output: one limiter entry per request")
+            if all(v is None for v in limiter):
+                limiter = None
+        if limiter is not None:
+            from .core.audio_processor import LIMITER_MODES, check_limiter
+            lims = [check_limiter(v) for v in (limiter if isinstance(limiter, (list, tuple)) else [limiter] * len(lens))]
+            louds = list(loudness) if isinstance(loudness, (list, tuple)) else [loudness] * len(lens)
+            plain = [i for i in range(len(lens)) if lims[i] is None and louds[i] is not None]
+            if plain:                      # the requests without a limiter: the capped gain of N12, as below
+                self.pcm_loudness(buf, [[offs[i], lens[i], offs[i]] for i in plain], sample_rate, [louds[i] for i in plain], peak_dbfs, out=buf)
+            for mode in LIMITER_MODES:
+                sel = [i for i in range(len(lens)) if lims[i] == mode]
+                if not sel:
+                    continue
+                rows, tg, meas = [[offs[i], lens[i], offs[i]] for i in sel], [louds[i] for i in sel], None
+                if any(t is not None for t in tg):
+                    _none, meas = self.pcm_loudness(buf, rows, sample_rate, tg, peak_dbfs, out="measure", stats=True)
+                self.pcm_limit(buf, rows, sample_rate, peak_dbfs, mode, meas=meas, targets=tg if meas is not None else None, out=buf)
+        elif loudness is not None:         # in place on the joined buffer: the apply pass is elementwise
             sel = [i for i in range(len(lens)) if not isinstance(loudness, (list, tuple)) or loudness[i] is not None]
             tg = [loudness[i] for i in sel] if isinstance(loudness, (list, tuple)) else loudness
             self.pcm_loudness(buf, [[offs[i], lens[i], offs[i]] for i in sel], sample_rate, tg, peak_dbfs, out=buf)
