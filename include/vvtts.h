@@ -317,6 +317,9 @@ typedef struct vv_gemm_args {
     int32_t M, N, K;
     const float *bias, *gate, *cos_q, *sin_q, *cos_k, *sin_k;
     int32_t n_store, seq_n, rope_dim;
+    /* n_store (VV_EPI_STORE only; 0 = N): the caller relies on columns [0, n_store) being written and on NOTHING at or past n_store
+       rounded up to a multiple of 4 (8 for bf16 output) ever being written; the columns in between may or may not be (the kernels
+       store 4 or 8 columns at a time).  vv_gemm refuses a non-zero n_store in the other epilogue modes (-22). */
     const float *rope_cs_q, *rope_cs_k;   /* optional compact [pos][64] (cos,sin) pair tables, see vv_rope_compact */
     int32_t tile;   /* 0 = auto (bf16: the persistent 256x256 kernel when M >= 4096, N % 256 == 0 and the shape has at least one round of
                        256-tiles for the chip's CUs or N >= 3072, below that 128x128 tiles or, for launches that do not fill the chip, 64-token x 128-feature

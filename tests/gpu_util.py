@@ -917,3 +917,402 @@ def posconv_cases():
         cs.append(PosCase(f"seq_n{seq_n}", seq_n, groups, lens, n_seq=2 * len(lens), resid=i % 2 == 0, pad=0 if i % 4 == 3 else 8))
     cs.append(PosCase("full_seq_n300", 300, 2, None, n_seq=3, resid=True, pad=8))
     return cs
+
+
+# ------------------------------------------------------------------------------------ GEMM: float64 reference, launch wrapper, cases
+# (tests/test_gemm_gpu.py runs the grid, tests/test_gemm_ref_cpu.py checks the claims made here; profiles/gemm_parity/notes.md)
+MODE_STORE, MODE_QKV_ROPE, MODE_GATE_RES, MODE_GATE_STORE = 0, 1, 2, 3
+ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU = 0, 1, 2, 3
+ACT_SLOPE = 1.13                        # bounds |f'| of tanh-GELU (1.129), erf-GELU (1.129) and SiLU (1.100)
+ACT_ALLOW = 8.0 * EPS24                 # x |z_e|: the epilogue's own roundings of f(z) (profiles/gemm_parity/notes.md; checked without a device)
+ROPE_FACTOR = 4.0                       # between two fp32 evaluations of one formula
+ROPE_THETA = 10000.0
+Q_SCALE = 0.125                         # the q tables carry the softmax scale: a q column roped with the k table shows
+# the kernels by the names used in the claims: gemm_kernel<T, CFG> and the persistent kernel's two store paths
+K_F32_128, K_F32_256 = "gemm_kernel<f32,0>", "gemm_kernel<f32,2>"
+K_BF16_128, K_BF16_64, K_BF16_RING, K_BF16_W16 = "gemm_kernel<bf16,0>", "gemm_kernel<bf16,3>", "gemm_kernel<bf16,4>", "gemm_kernel<bf16,2>"
+K_PP_STAGED, K_PP_PLAIN = "gemm_pp_kernel/staged", "gemm_pp_kernel/plain"
+# form -> (operand dtype, tile argument, rows per tile, BK)
+GEMM_FORMS = {"f32_128": (torch.float32, 128, 128, 32), "f32_256": (torch.float32, 256, 256, 32), "bf16_64": (torch.bfloat16, 64, 64, 64),
+              "bf16_128": (torch.bfloat16, 128, 128, 64), "bf16_6464": (torch.bfloat16, 6464, 64, 64), "pp": (torch.bfloat16, 256, 256, 64),
+              "w16": (torch.bfloat16, 256, 256, 64)}
+_FORM_KERNEL = {"f32_128": K_F32_128, "f32_256": K_F32_256, "bf16_64": K_BF16_64, "bf16_128": K_BF16_128, "bf16_6464": K_BF16_RING, "w16": K_BF16_W16}
+
+
+def gemm_act(z, act):
+    """Exact activation of a float64 (or, for the yardstick, fp32) tensor."""
+    if act == ACT_GELU_TANH:
+        return F.gelu(z, approximate="tanh")
+    if act == ACT_GELU_ERF:
+        return F.gelu(z)
+    if act == ACT_SILU:
+        return F.silu(z)
+    return z
+
+
+def rope_angles(pos, theta=ROPE_THETA):
+    """float64 [len(pos)][32]: pos x theta^(-2i/64)."""
+    return pos.double()[:, None] * theta ** (-torch.arange(32, dtype=torch.float64)[None, :] * 2.0 / 64.0)
+
+
+def rope_full_tables(seq_n, theta=ROPE_THETA):
+    """The four fp32 pair-duplicated tables [seq_n][64] (cos_q, sin_q, cos_k, sin_k); the q tables carry Q_SCALE."""
+    ang = torch.repeat_interleave(rope_angles(torch.arange(seq_n), theta), 2, dim=1)
+    c, s = ang.cos(), ang.sin()
+    return [(c * Q_SCALE).float(), (s * Q_SCALE).float(), c.float(), s.float()]
+
+
+def rope_compact(cos, sin):
+    """[pos][64] (cos, sin) per pair from two pair-duplicated tables: what vv_rope_compact writes."""
+    t = torch.empty_like(cos)
+    t[:, 0::2], t[:, 1::2] = cos[:, 0::2], sin[:, 0::2]
+    return t
+
+
+def rope_computed_emulation(pos, theta=ROPE_THETA):
+    """fp32 emulation of rope_pair_computed's steps up to the argument of v_cos / v_sin -> the angle it stands for, float64 rad in
+    [0, 2 pi), [len(pos)][32].  k1 = log2f(theta) / 32 and k0 = fp32(log2(2 pi)) as vvk_gemm sets them; the fma rounds once."""
+    f32 = torch.float32
+    k1 = (torch.log2(torch.tensor(theta, dtype=f32)) / 32.0).double()
+    k0 = torch.tensor(2.6514961294723187, dtype=f32).double()
+    ex = -(torch.arange(32, dtype=torch.float64) * k1 + k0).to(f32)             # one rounding: the product is exact in float64
+    rev = pos.to(f32)[:, None] * torch.exp2(ex)[None, :]                        # v_exp_f32, then one fp32 product
+    fr = rev - torch.floor(rev)                                                 # v_fract_f32: exact
+    return fr.double() * (2.0 * math.pi)
+
+
+_ROPE_MODEL = {}
+
+
+def rope_angle_model(theta=ROPE_THETA, n_pos=4096):
+    """-> (kappa, theta0) of  |angle error| <= kappa 2^-24 angle + theta0, MEASURED on the CPU: the emulation above against the float64
+    angle at positions 0 .. n_pos - 1 and all 32 pairs.  kappa: the worst relative figure where the angle is at least one radian (the
+    error is a relative one there: roundings of the exponent and the product); theta0: what is left over that line anywhere."""
+    if (theta, n_pos) not in _ROPE_MODEL:
+        pos = torch.arange(n_pos)
+        true = rope_angles(pos, theta)
+        d = rope_computed_emulation(pos, theta) - torch.remainder(true, 2.0 * math.pi)
+        d = (torch.remainder(d + math.pi, 2.0 * math.pi) - math.pi).abs()
+        big = true >= 1.0
+        kappa = float((d[big] / (EPS24 * true[big])).max())
+        theta0 = float((d - kappa * EPS24 * true).clamp_min(0.0).max())
+        _ROPE_MODEL[(theta, n_pos)] = (kappa, theta0)
+    return _ROPE_MODEL[(theta, n_pos)]
+
+
+def gemm_dispatch(bf16_in, out_bytes, M, N, K, lda, ldw, ldc, act, tile, cus=256, chip_share=0):
+    """launch() of vv_gemm.hip restated for a chip of `cus` CUs -> the kernel a launch reaches."""
+    T = "bf16" if bf16_in else "f32"
+    big = tile == 256 or (tile == 0 and M >= 4096 and N % 256 == 0)
+    share = 2 if chip_share == 2 else 1
+    if bf16_in:
+        if tile == 0 and big and N < 3072 and ((M + 255) // 256) * (N // 256) < cus // share:
+            big = False
+        fits = K >= 128 and act != ACT_GELU_ERF and M * lda * 2 < 2 ** 31 and N * ldw * 2 < 2 ** 31 and M * ldc * out_bytes < 2 ** 31 - 256
+        if big and fits:
+            return K_PP_STAGED if out_bytes == 2 else K_PP_PLAIN
+    if big:
+        return f"gemm_kernel<{T},2>"
+    if bf16_in:
+        if tile == 6464 and M * lda * 2 < 2 ** 31 and N * ldw * 2 < 2 ** 31:
+            return K_BF16_RING
+        t64 = tile == 64
+        if tile == 0:
+            t, c = ((M + 127) // 128) * (N // 128), cus // share
+            t64 = t <= 3 * c and (2 * t + 3 * c - 1) // (3 * c) <= (t + 2 * c - 1) // (2 * c)
+        if t64:
+            return K_BF16_64
+    return f"gemm_kernel<{T},0>"
+
+
+_TILE_OF_KERNEL = {K_F32_128: 128, K_F32_256: 256, K_BF16_128: 128, K_BF16_64: 64, K_BF16_RING: 6464, K_BF16_W16: 256, K_PP_STAGED: 256, K_PP_PLAIN: 256}
+
+
+class GemmCase:
+    """One problem of the GEMM grid.  form: key of GEMM_FORMS (the tile argument and the operand dtype); kernel: the kernel the case
+    CLAIMS to reach (checked against gemm_dispatch).  rope: None / 'tables' / 'compact' / 'by_row' / 'computed'.  tile: overrides the
+    form's tile argument (0 = automatic; the case is then also compared bit for bit with the forced tile the rule names).  twins: more
+    tile arguments whose output must be bit-identical."""
+
+    def __init__(self, name, section, form, *, M, N, K, mode=MODE_STORE, act=ACT_NONE, out_f32=False, gated=True, rope=None, seq_n=0, rope_dim=0,
+                 use_pos=False, skip_q=False, n_store=0, tile=None, twins=(), kernel=None):
+        self.name, self.section, self.form = name, section, form
+        self.dtype, form_tile, self.rows_per_tile, self.BK = GEMM_FORMS[form]
+        self.tile = form_tile if tile is None else tile
+        self.M, self.N, self.K, self.mode, self.act, self.gated = M, N, K, mode, act, gated
+        self.bf16_in = self.dtype == torch.bfloat16
+        self.out_f32 = out_f32 or not self.bf16_in or mode == MODE_GATE_RES
+        self.out_dtype = torch.float32 if self.out_f32 else torch.bfloat16
+        self.rope, self.seq_n, self.rope_dim, self.use_pos, self.skip_q, self.n_store, self.twins = rope, seq_n, rope_dim, use_pos, skip_q, n_store, tuple(twins)
+        self.kernel = kernel or (_FORM_KERNEL[form] if form != "pp" else (K_PP_PLAIN if self.out_f32 else K_PP_STAGED))
+        self.m_tiles = (M + self.rows_per_tile - 1) // self.rows_per_tile
+        self._ops, self._refs = None, None
+
+    def store_quantum(self):
+        return 4 if self.out_f32 else 8
+
+    def ld(self, padded):
+        """-> (lda, ldw, ldc) of the contiguous or the padded launch."""
+        return (self.K + 8, self.K + 16, self.N + self.store_quantum()) if padded else (self.K, self.K, self.N)
+
+    def reached(self, padded, tile=None):
+        lda, ldw, ldc = self.ld(padded)
+        return gemm_dispatch(self.bf16_in, 4 if self.out_f32 else 2, self.M, self.N, self.K, lda, ldw, ldc, self.act, self.tile if tile is None else tile)
+
+    def positions(self):
+        """Rope position of every row: a table that is NOT row % seq_n when the case passes one."""
+        m = torch.arange(self.M)
+        return ((m * 11 + 3) % self.seq_n) if self.use_pos else (m % self.seq_n)
+
+    def ops(self):
+        """Operands as the kernel gets them: A [M][K], W [N][K] in the operand dtype (randn, W / sqrt(K)); bias, gate fp32 of UNIT scale;
+        x0 fp32 [M][N] (the residual stream); the four rope tables."""
+        if self._ops is None:
+            g = torch.Generator().manual_seed(sum(ord(ch) * (i + 1) for i, ch in enumerate(self.name)) % 100003)
+            o = _Ops()
+            o.A = torch.randn(self.M, self.K, generator=g).to(self.dtype)
+            o.W = (torch.randn(self.N, self.K, generator=g) / math.sqrt(self.K)).to(self.dtype)
+            o.bias, o.gate = torch.randn(self.N, generator=g), torch.randn(self.N, generator=g)
+            o.x0 = torch.randn(self.M, self.N, generator=g) if self.mode == MODE_GATE_RES else None
+            o.tables = rope_full_tables(self.seq_n) if self.mode == MODE_QKV_ROPE else None
+            o.pos = self.positions() if self.mode == MODE_QKV_ROPE else None
+            self._ops = o
+        return self._ops
+
+    def refs(self):
+        """-> the float64 reference of the case (gemm_ref), computed once."""
+        if self._refs is None:
+            self._refs = gemm_ref(self)
+        return self._refs
+
+
+def _rope_cs(case, o, mode):
+    """-> (c, s), each [M][2 rope_dim]: cos and sin per COLUMN of the q and k blocks (pair-duplicated), float64 (fp32 for the yardstick)."""
+    D = case.rope_dim
+    if case.rope == "computed":
+        ang = torch.repeat_interleave(rope_angles(o.pos), 2, dim=1)             # [M][64]
+        c, s = ang.cos(), ang.sin()
+        if mode == "f32":
+            c, s = c.float(), s.float()
+        reps = 2 * D // 64
+        return c.repeat(1, reps), s.repeat(1, reps)
+    conv = (lambda t: t) if mode == "f32" else (lambda t: t.double())
+    cq, sq, ck, sk = (conv(t[o.pos]) for t in o.tables)
+    h = D // 64
+    return torch.cat([cq.repeat(1, h), ck.repeat(1, h)], 1), torch.cat([sq.repeat(1, h), sk.repeat(1, h)], 1)
+
+
+def gemm_eval(case, o, mode, act=None):
+    """The case's expression on operands o.  mode 'f64': the float64 reference; 'abs': A_e, the same expression with every operand
+    replaced by its absolute value (an activation: 1.13 A_z); 'f32': the yardstick, the CPU library in fp32.  -> (out, z)."""
+    act = case.act if act is None else act
+    if mode == "f32":
+        pos = lambda t: t.float()
+    elif mode == "abs":
+        pos = lambda t: t.double().abs()
+    else:
+        pos = lambda t: t.double()
+    z = pos(o.A) @ pos(o.W).t() + pos(o.bias)[None, :]
+    if case.mode == MODE_STORE:
+        if act == ACT_NONE:
+            return z, z
+        return (ACT_SLOPE * z if mode == "abs" else gemm_act(z, act)), z
+    if case.mode == MODE_GATE_STORE:
+        return pos(o.gate)[None, :] * z, z
+    if case.mode == MODE_GATE_RES:
+        return (pos(o.x0) + (pos(o.gate)[None, :] * z if case.gated else z)), z
+    D, lo = case.rope_dim, (case.rope_dim if case.skip_q else 0)
+    c, s = _rope_cs(case, o, mode)
+    if mode == "abs":
+        c, s = c.abs(), s.abs()
+    out = z.clone()
+    a, b = z[:, lo:2 * D:2], z[:, lo + 1:2 * D:2]
+    cc, ss = c[:, lo:2 * D:2], s[:, lo:2 * D:2]
+    if mode == "abs":
+        out[:, lo:2 * D:2], out[:, lo + 1:2 * D:2] = a * cc + b * ss, b * cc + a * ss
+    else:
+        out[:, lo:2 * D:2], out[:, lo + 1:2 * D:2] = a * cc - b * ss, b * cc + a * ss
+    return out, z
+
+
+def gemm_allow(case, ref, z, o, bf16_out=None):
+    """The per-element allowances on top of the accumulation bound: the bf16 store, the activation's own roundings, the fp32 angle of the
+    computed rope."""
+    bf16_out = (not case.out_f32) if bf16_out is None else bf16_out
+    allow = torch.zeros_like(ref)
+    if bf16_out:
+        allow += BF16_STORE * ref.abs()
+    if case.mode == MODE_STORE and case.act != ACT_NONE:
+        allow += ACT_ALLOW * z.abs()
+    if case.mode == MODE_QKV_ROPE and case.rope == "computed":
+        kappa, theta0 = rope_angle_model()
+        dth = torch.repeat_interleave(kappa * EPS24 * rope_angles(o.pos) + theta0, 2, dim=1)        # [M][64], per column
+        D, lo = case.rope_dim, (case.rope_dim if case.skip_q else 0)
+        dth = dth.repeat(1, 2 * D // 64)
+        pair = z[:, 0:2 * D:2].abs() + z[:, 1:2 * D:2].abs()
+        add = ROPE_FACTOR * dth[:, :2 * D] * torch.repeat_interleave(pair, 2, dim=1)
+        allow[:, lo:2 * D] += add[:, lo:]
+    return allow
+
+
+def gemm_ref(case, o=None):
+    """-> an object with ref (float64 [M][N]), A (the scale A_e), z (float64 A W^T + bias), allow (gemm_allow), yard (the fp32 CPU library's
+    err under the metric, no allowance) and bound."""
+    o = case.ops() if o is None else o
+    r = _Ops()
+    r.ref, r.z = gemm_eval(case, o, "f64")
+    r.A, _ = gemm_eval(case, o, "abs")
+    r.f32, _ = gemm_eval(case, o, "f32")
+    r.allow = gemm_allow(case, r.ref, r.z, o)
+    r.yard = parity_err(r.f32, r.ref, r.A)[0]
+    r.bound = gemm_bound(r.yard)
+    return r
+
+
+def gemm_bound(yardstick):
+    """max(8 x 2^-24, 4 x yardstick): conv_bound's rule, for its reasons -- the floor is one product rounding plus the epilogue's few
+    (bias, gate, residual / the rope pair's products), the 4 stands between the kernel's one chain of K / 32 MFMA steps per element and
+    the CPU library's vector lanes.  Never fitted to a measurement; tests/test_gemm_ref_cpu.py holds it under (K + 8) 2^-24."""
+    return max(8.0 * EPS24, 4.0 * yardstick)
+
+
+def gemm_written_cols(case):
+    """-> (columns below this are compared, columns from this on must keep the fill): n_store, and n_store rounded up to the store quantum."""
+    if not case.n_store:
+        return case.N, case.N
+    q = case.store_quantum()
+    return case.n_store, min(case.N, (case.n_store + q - 1) // q * q)
+
+
+def gemm_launch(eng, case, *, padded, tile=None, o=None, tail=None):
+    """One launch of a case -> the M x N view of C on the CPU.  C is a view inside a larger buffer of CONV_FILL: CONV_GUARD rows in front
+    and behind, and (padded) 8 / 4 padding columns for bf16 / fp32 output; A and W are views with lda = K + 8 / ldw = K + 16 (padded)
+    whose padding columns and two more rows hold NaN; bias and gate are followed by NaN.  The guard rows and padding columns are checked
+    after the launch.  Fresh rows of C hold the fill (the residual stream x0 in MODE_GATE_RES)."""
+    o = case.ops() if o is None else o
+    M, N, K, G = case.M, case.N, case.K, CONV_GUARD
+    lda, ldw, ldc = case.ld(padded)
+    Ab = torch.full((M + 2, lda), NAN, dtype=case.dtype, device=DEV)
+    Wb = torch.full((N + 2, ldw), NAN, dtype=case.dtype, device=DEV)
+    Ab[:M, :K], Wb[:N, :K] = o.A.to(DEV), o.W.to(DEV)
+    vecs = []
+    for v in (o.bias, o.gate):
+        t = torch.full((N + 4,), NAN, device=DEV)
+        t[:N] = v.to(DEV)
+        vecs.append(t[:N])
+    Cb = torch.full((G + M + G, ldc), CONV_FILL, dtype=case.out_dtype, device=DEV)
+    Cv = Cb[G:G + M, :N]
+    if case.mode == MODE_GATE_RES:
+        Cv.copy_(o.x0.to(DEV))
+    kw = dict(mode=case.mode, act=case.act, out_dtype=rt.VV_F32 if case.out_f32 else rt.VV_BF16, n_store=case.n_store,
+              tile=case.tile if tile is None else tile, tail=tail)
+    if case.mode in (MODE_GATE_RES, MODE_GATE_STORE) and case.gated:
+        kw["gate"] = vecs[1]
+    if case.mode == MODE_QKV_ROPE:
+        ropes = [t.to(DEV) for t in o.tables]
+        if case.rope in ("compact", "by_row"):
+            cs = [rope_compact(o.tables[0], o.tables[1]), rope_compact(o.tables[2], o.tables[3])]
+            if case.rope == "by_row":
+                cs = [t[o.pos] for t in cs]
+                kw["rope_by_row"] = 1
+            ropes += [t.contiguous().to(DEV) for t in cs]
+        kw.update(ropes=ropes, seq_n=case.seq_n, rope_dim=case.rope_dim, rope_skip_q=1 if case.skip_q else 0,
+                  rope_theta=ROPE_THETA if case.rope == "computed" else 0.0)
+        if case.use_pos:
+            kw["rope_pos"] = o.pos.to(torch.int32).to(DEV)
+    gemm(eng, Ab[:M, :K], Wb[:N, :K], bias=vecs[0], C_io=Cv, **kw)
+    whole = Cb.cpu()
+    what = f"{case.name} tile={kw['tile']} padded={padded}"
+    assert bool((whole[:G].float() == CONV_FILL).all()), f"{what}: the guard rows in front of C were written"
+    assert bool((whole[G + M:].float() == CONV_FILL).all()), f"{what}: the guard rows behind C were written"
+    assert bool((whole[G:G + M, N:].float() == CONV_FILL).all()), f"{what}: the padding columns of C were written"
+    return whole[G:G + M, :N]
+
+
+GEMM_M_EDGES = (1, 15, 17, 63, 65, 129, 255, 257)
+GEMM_M_WALK = {"f32_128": 1025, "f32_256": 2100, "bf16_64": 577, "bf16_128": 1025, "bf16_6464": 577, "pp": 2100, "w16": 2100}
+_BF16_TWINS = (64, 6464, 256)
+
+
+def gemm_cases():
+    """One base shape per form (M = 200, N = 256, K = 2 K-tiles; the persistent kernel K = 128, its 16-wave fallback K = 64) and ONE axis
+    varied at a time: M around every tile / wave / MFMA row count and once with m_tiles > 8 and a ragged last tile; N; K in K-tiles;
+    every epilogue the form builds; n_store.  The bf16_128 epilogue cases carry the other bf16 tilings as bit-identical twins."""
+    cs = []
+    for form, (dt, tile, rows, BK) in GEMM_FORMS.items():
+        bf = dt == torch.bfloat16
+        K0 = 64 if form == "w16" else (128 if bf else 64)
+        base = dict(M=200, N=256, K=K0)
+        w16_act = dict(act=ACT_GELU_TANH) if form == "w16" else {}
+        add = lambda name, section, **kw: cs.append(GemmCase(f"{form}_{name}", section, form, **{**base, **kw}))
+        for M in GEMM_M_EDGES + (GEMM_M_WALK[form],):
+            add(f"M{M}", "M", M=M, **w16_act)
+        for N in ((256, 768) if rows == 256 else (128, 384, 768)):
+            add(f"N{N}", "N", N=N, **w16_act)
+        if form == "pp":
+            ks = (192, 320, 512)
+        elif form == "w16":
+            ks = ()                     # K = 64 is what routes a plain bf16 launch here; the erf-GELU cases below vary K
+        else:
+            ks = (BK, 3 * BK, 5 * BK, 512)
+        for K in ks:
+            add(f"K{K}", "K", K=K)
+        if form == "w16":
+            for K in (64, 128, 192, 320, 512):
+                add(f"erf_K{K}", "K", K=K, act=ACT_GELU_ERF)
+            add("erf_M2100", "M", M=2100, K=128, act=ACT_GELU_ERF)
+        # ---- epilogues
+        tw = dict(twins=_BF16_TWINS) if form == "bf16_128" else {}
+        add("store", "epilogue", **tw)
+        for an, act in (("gelu_tanh", ACT_GELU_TANH), ("gelu_erf", ACT_GELU_ERF), ("silu", ACT_SILU)):
+            kernel = dict(kernel=K_BF16_W16) if (form == "pp" and act == ACT_GELU_ERF) else {}
+            add(an, "epilogue", act=act, **tw, **kernel)
+        if bf:
+            add("store_f32out", "epilogue", out_f32=True, **tw)
+            add("gelu_tanh_f32out", "epilogue", act=ACT_GELU_TANH, out_f32=True, **tw)
+        add("gate_res", "epilogue", mode=MODE_GATE_RES, **tw)
+        add("res_ungated", "epilogue", mode=MODE_GATE_RES, gated=False, **tw)
+        add("gate_store", "epilogue", mode=MODE_GATE_STORE, **tw)
+        # rope: N = 512 = q | k | v of rope_dim 128 and 128 plain columns behind v (N > 3 rope_dim); M = 200 = 2 sequences of 70 and a ragged third
+        rp = dict(mode=MODE_QKV_ROPE, N=512, rope_dim=128, seq_n=70)
+        add("rope_tables", "epilogue", rope="tables", **rp, **tw)
+        add("rope_tables_pos", "epilogue", rope="tables", use_pos=True, **rp, **tw)
+        add("rope_tables_skip_q", "epilogue", rope="tables", skip_q=True, **rp, **tw)
+        add("rope_tight", "epilogue", rope="tables", **{**rp, "N": 384 if rows != 256 else 768, "rope_dim": 128 if rows != 256 else 256})
+        if bf:
+            add("rope_compact", "epilogue", rope="compact", **rp, **tw)
+            add("rope_compact_pos", "epilogue", rope="compact", use_pos=True, **rp)
+            for sn in (70, 4096):
+                Mc = 200 if sn == 70 else 4096 + 200
+                add(f"rope_computed_s{sn}", "epilogue", rope="computed", **{**rp, "seq_n": sn, "M": Mc}, **(tw if sn == 70 else {}))
+            add("rope_computed_pos_skip_q", "epilogue", rope="computed", use_pos=True, skip_q=True, **{**rp, "seq_n": 4096, "M": 300})
+        if form == "pp":
+            add("rope_by_row", "epilogue", rope="by_row", **rp)
+            add("rope_by_row_pos", "epilogue", rope="by_row", use_pos=True, **rp)
+        # ---- n_store (plain store only: the ABI refuses it elsewhere), both output types
+        for ns in (100, 132):
+            add(f"nstore{ns}", "n_store", n_store=ns, out_f32=not bf, **w16_act)
+            if bf:
+                add(f"nstore{ns}_f32out", "n_store", n_store=ns, out_f32=True, **w16_act)
+    # ---- tile = 0: the automatic choice, bit-identical to the forced form the dispatch rule names
+    cs.append(GemmCase("auto_f32_small", "auto", "f32_128", M=200, N=256, K=64, tile=0))
+    cs.append(GemmCase("auto_f32_big", "auto", "f32_256", M=4100, N=256, K=32, tile=0))
+    cs.append(GemmCase("auto_bf16_small", "auto", "bf16_64", M=200, N=256, K=128, tile=0))
+    cs.append(GemmCase("auto_bf16_mid", "auto", "bf16_128", M=12300, N=1024, K=64, tile=0))
+    cs.append(GemmCase("auto_bf16_pp", "auto", "pp", M=4096 + 9, N=3072, K=128, tile=0, act=ACT_GELU_TANH))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+# the persistent workgroup that walks more than one tile (602 tiles on 256 CUs), whole output; and the split-K tail shape
+GEMM_WALK = dict(M=256 * 300 + 77, N=512, K=128)
+GEMM_TAIL = dict(M=136 * 256 - 100, N=512, K=512)
+
+
+def gemm_walk_cases():
+    return [GemmCase("pp_walk_gate_store", "walk", "pp", mode=MODE_GATE_STORE, **GEMM_WALK),
+            GemmCase("pp_walk_gelu_tanh", "walk", "pp", act=ACT_GELU_TANH, **GEMM_WALK)]
+
+
+def gemm_tail_case():
+    return GemmCase("pp_split_k_tail", "tail", "pp", mode=MODE_GATE_STORE, **GEMM_TAIL)

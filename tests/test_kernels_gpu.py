@@ -594,7 +594,8 @@ def test_gemm_three_tilings_give_the_same_bits(hip_tiny, M):
 @pytest.mark.parametrize("K", [64, 128, 192, 2048])
 def test_gemm_ring_tiling_short_and_long_k(hip_tiny, K):
     """The three-stage ring of the 64 x 64 tiling at the ends of its range: one K-tile (nothing to prefetch), two (no steady state), three,
-    and the FF2 depth (32 K-tiles), ragged M, gate store: equal to the 128 x 128 kernel bit for bit, fresh rows past M untouched."""
+    and the FF2 depth (32 K-tiles), ragged M, gate store: equal to the 128 x 128 kernel bit for bit.  (C is exactly [M][N] here: rows past M and columns past N are
+    watched by the guard rows and padding columns of tests/test_gemm_gpu.py, not by this test.)"""
     rt, gu = _imports()
     eng = hip_tiny["f32"]
     g = torch.Generator().manual_seed(K)

@@ -987,9 +987,12 @@ struct KernelSetup {
 // The persistent kernel addresses its operands through buffer resources with a 31-bit num_records: operands of 2 GiB or more
 // take the plain-pointer kernels (64-bit addressing) instead.  The split-K tail exists in the persistent kernel only, so the
 // planner applies the same condition -- planner and launcher agree for every shape (M = 300,000, K = 4096: no tail).
+// The output's bound is 256 bytes tighter: the kernel drops a store by giving it an offset in [0x7fffff00, 0x7ffffff0] (the 16 counted
+// stores of the prologue, the lanes past M or n_store), which has to lie past num_records = M * ldc * sizeof(To) to be dropped.
+constexpr size_t PP_DROP_FLOOR = ((size_t)1 << 31) - 256;
 inline bool pp_fits(int M, int N, int K, int lda, int ldw, int ldc, size_t out_size, int act) {
     return K >= 128 && act != VV_ACT_GELU_ERF && (size_t)M * lda * 2 < ((size_t)1 << 31) && (size_t)N * ldw * 2 < ((size_t)1 << 31) &&
-           (size_t)M * ldc * out_size < ((size_t)1 << 31);
+           (size_t)M * ldc * out_size < PP_DROP_FLOOR;
 }
 
 void tail_plan(int M, int N, int K, int lda, int ldw, int ldc, int n_cu, int* row0, int* parts) {
@@ -1110,7 +1113,12 @@ int vvk_gemm(const vvk_gemm_args* g, hipStream_t st, const char** err) {
     if (g->K % BK != 0) { *err = "gemm: K must be a multiple of BK (64 bf16 / 32 f32)"; return -22; }
     if (((size_t)g->lda * esz) % 16 || ((size_t)g->ldw * esz) % 16 || ((uintptr_t)g->A % 16) || ((uintptr_t)g->W % 16) ||
         ((uintptr_t)g->C % 16) || (g->ldc % 4)) { *err = "gemm: operands must be 16-byte aligned"; return -22; }
+    // ldc % 4 is enough for bf16 output too.  The persistent kernel's staged path stores 16 bytes per lane at row * ldc * 2 bytes
+    // (buffer_store_dwordx4, or the non-temporal global_store_dwordx4): with ldc % 8 == 4 odd rows are 8-byte aligned only.  Both are
+    // vector-memory instructions, for which the CDNA ISA asks dword alignment of a dword-or-wider access and no more (the 16-byte rule
+    // is the LDS's, for ds_*_b128); an 8-byte aligned row costs a second cache-line segment per store, never a fault or a torn value.
     if (g->lda < g->K || g->ldw < g->K) { *err = "gemm: leading dimension smaller than K"; return -22; }
+    if (g->n_store != 0 && g->mode != MODE_STORE) { *err = "gemm: n_store is for the plain store epilogue (VV_EPI_STORE) only"; return -22; }
     if (g->tile != 0 && g->tile != 128 && g->tile != 256 && !((g->tile == 64 || g->tile == 6464) && g->dtype == VV_BF16)) { *err = "gemm: tile must be 0 (auto), 128, 256, or 64 / 6464 (bf16)"; return -22; }
     if (g->tile == 256 && g->N % 256) { *err = "gemm: the 256 tile needs N % 256 == 0"; return -22; }
     EpiArgs e{};                 // value-initialised: a field this function forgets is zero, never stack garbage
@@ -1129,7 +1137,7 @@ int vvk_gemm(const vvk_gemm_args* g, hipStream_t st, const char** err) {
         if (parts != g->tail_parts || row0 != g->tail_row0 || !g->C_tail || ((uintptr_t)g->C_tail % 16)) {
             *err = "gemm: split-K tail does not match vv_gemm_tail_plan for this shape"; return -22;
         }
-        if ((size_t)(g->M - row0) * g->ldc * 4 >= ((size_t)1 << 31)) { *err = "gemm: split-K tail buffer of 2 GiB or more"; return -22; }
+        if ((size_t)(g->M - row0) * g->ldc * 4 >= PP_DROP_FLOOR) { *err = "gemm: split-K tail buffer of 2 GiB or more"; return -22; }
         e.c_part = (char*)g->C_tail; e.tail_panel0 = row0 / 256; e.ks = parts;
     }
     e.rope_dim = g->rope_dim; e.rope_lo = g->rope_skip_q ? g->rope_dim : 0; e.pos_tab = g->rope_pos;
