@@ -631,6 +631,36 @@ VV_API int vv_pcm_limit(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_
                         const double* window, const double* taps, const double* params, const double* meas, int16_t* y, int64_t n_y,
                         double* stats, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ---- N14 pitch and tempo of the joined signal: a WSOLA time stretch by p / q; the pitch half is a vv_pcm_resample call
+ * on its result.  The arithmetic is pinned by core/audio_processor.py (time_stretch), which the kernels equal bit for bit.  Per request,
+ * with N = VV_WSOLA_N, HS = VV_WSOLA_HS, D = VV_WSOLA_D, x = 0 outside [0, n), n_s = ceil(n p / q), M = ceil(n_s / HS), pos_0 = -HS:
+ *     for m = 1 ... M:  a_m = floor((m - 1) HS q / p);   c(d) = sum_{k < N} x[pos_{m-1} + HS + k] * x[a_m + d + k],  d = -D ... D - 1,
+ *                       an exact integer;   pos_m = a_m + d*, d* = the largest c, among equals the smallest |d|, the negative one first
+ *     for i < n_s:      m = i / HS + 1, k = i - (m - 1) HS;
+ *                       y[i] = clamp(rint(window[k + HS] * x[pos_{m-1} + HS + k] + window[k] * x[pos_m + k]), -32768, 32767)
+ * in float64, the two products rounded on their own, one sum, ties to even.  Every output sample is written exactly once.  The
+ * correlation is not normalised.  p == q is NOT an identity of this recipe and is refused.  The call never synchronises and reads
+ * nothing back.
+ *   x        int16, the requests' joined signals
+ *   rows     R x 6 int64 {src_off, n, dst_off, p, q, pos_off} in device memory and the same rows in HOST memory (rows_host, checked by
+ *            the call): x[src_off, +n) is stretched to y[dst_off, +n_s), its frame positions go to pos[pos_off, +M + 1)
+ *   window   VV_WSOLA_N float64 on the device: 0.5 - 0.5 cos(2 pi k / N) (audio_processor.wsola_window); the device evaluates no cosine
+ *   y        int16, must not overlap x; nothing outside the rows' outputs is written.  y may start at any even byte.  NULL = the search
+ *            alone: pos is written, no sample
+ *   pos      int32 [n_pos]: pos_0 ... pos_M of every request, for the caller
+ *   ws       ws_bytes >= vv_pcm_stretch_ws_bytes(R), 8-byte aligned
+ * -22, and nothing is launched, for no context, R < 1, p == q, p or q outside 1 ... VV_WSOLA_MAX_PQ, p / q outside [1/4, 4], a null or
+ * misaligned pointer, a ws that is too small, a negative field, n > 2^30, a row outside n_x / n_y / n_pos, rows that overlap on y or
+ * on pos, y overlapping x. */
+#define VV_WSOLA_N 512
+#define VV_WSOLA_HS 256
+#define VV_WSOLA_D 128
+#define VV_WSOLA_MAX_PQ 2048
+VV_API uint64_t vv_pcm_stretch_ws_bytes(int R);
+VV_API int vv_pcm_stretch(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R,
+                          const double* window, int16_t* y, int64_t n_y, int32_t* pos, int64_t n_pos, void* ws, uint64_t ws_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

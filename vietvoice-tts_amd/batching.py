@@ -35,13 +35,14 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "t0", "n_req")
 
     def __init__(self):
         self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
         self.etas, self.norms = [], []
         self.louds = []               # per REQUEST: its own loudness target (N12) or None
         self.lims = []                # per REQUEST: its own limiter mode (N13) or None
+        self.pitches, self.tempos = [], []      # per REQUEST: its own pitch / tempo (N14) or None
 
 
 class BatchingFrontend:
@@ -74,7 +75,8 @@ class BatchingFrontend:
 
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
                cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
-               loudness: Optional[float] = None, limiter: Optional[str] = None, **voice) -> Future:
+               loudness: Optional[float] = None, limiter: Optional[str] = None, pitch: Optional[float] = None, tempo: Optional[float] = None,
+               **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
@@ -82,13 +84,17 @@ class BatchingFrontend:
         ``apg_eta`` / ``apg_norm``: this request's projected guidance (model_spec.check_apg; None = the engine's value), per item as well:
         plain and projected requests share one batch.  ``loudness``: this request's programme loudness in LUFS (-60 ... -5, DESIGN §8 N12;
         None = the engine's ``output_loudness``), measured and applied to this request alone in the batch's one finish_output call.
-        ``limiter``: this request's limiter, "sample" or "true" (None = the engine's ``output_limiter``), carried the same way."""
+        ``limiter``: this request's limiter, "sample" or "true" (None = the engine's ``output_limiter``), carried the same way.
+        ``pitch`` (semitones, -12 ... 12) / ``tempo`` (0.5 ... 2.0): this request's prosody (None = the engine's
+        ``output_pitch`` / ``output_tempo``), applied to this request alone; its batch neighbours are copied untouched."""
         fut: Future = Future()
         try:
             from .core.audio_processor import check_loudness
             loudness, _pk = check_loudness(loudness)
             from .core.audio_processor import check_limiter
             check_limiter(limiter)
+            from .core.audio_processor import check_prosody
+            pitch, tempo = check_prosody(pitch, tempo)
             from .model_spec import check_apg, check_cfg_interval
             cfg_interval = check_cfg_interval(cfg_interval)
             check_apg(apg_eta, apg_norm)
@@ -108,7 +114,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -141,7 +147,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter = req
+        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -176,6 +182,8 @@ class BatchingFrontend:
         batch.norms.extend([apg_norm] * len(inputs))
         batch.louds.append(loudness)
         batch.lims.append(limiter)
+        batch.pitches.append(pitch)
+        batch.tempos.append(tempo)
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -284,7 +292,8 @@ class BatchingFrontend:
             if eng.model_session_manager.engine is not None:
                 own = next((v for v in batch.louds if v is not None), None)      # N12: a request's own target takes the device stage too
                 own_lim = next((v for v in batch.lims if v is not None), None)      # N13: and so does a request's own limiter
-                dev_out = eng._device_output(own, own_lim)      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
+                own_pros = next((v for v in batch.pitches + batch.tempos if v is not None), None)      # N14: and its own pitch or tempo
+                dev_out = eng._device_output(own, own_lim, own_pros)      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
                 if batch.keys:
                     waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
                                                    device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
@@ -324,7 +333,8 @@ class BatchingFrontend:
             return
         if isinstance(waves, tuple):          # device output stage: (device PCM, spans) -- one finish_output call for the whole batch
             try:
-                finals = eng._finish_device(waves, [n for _f, n in batch.plans], loudness=batch.louds, limiter=batch.lims)
+                finals = eng._finish_device(waves, [n for _f, n in batch.plans], loudness=batch.louds, limiter=batch.lims,
+                                            pitch=batch.pitches, tempo=batch.tempos)
             except Exception as e:        # noqa: BLE001
                 self._fail(batch, e)
                 return
@@ -333,9 +343,9 @@ class BatchingFrontend:
                 self.requests_done += 1
             return
         pos = 0
-        for (fut, n), loud, lim in zip(batch.plans, batch.louds, batch.lims):
+        for (fut, n), loud, lim, pit, tem in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos):
             try:
-                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim)
+                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem)
                 fut.set_result((final, time.time() - batch.t0))
             except Exception as e:        # noqa: BLE001
                 fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))

@@ -28,9 +28,10 @@ from __future__ import annotations
 
 import io
 import struct
+from fractions import Fraction
 from math import gcd
 from pathlib import Path
-from typing import List, Optional, Tuple, Union
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
@@ -540,6 +541,131 @@ def limit_peaks(pcm, sr: int, peak_dbfs: float = -1.0, mode: str = "true", gain:
     y = np.clip(np.rint(v * s), -32768.0, 32767.0).astype(np.int16)               # 7
     stats = {"g": float(gain), "e_max": float(e.max(initial=0.0)), "s_min": float(s.min(initial=1.0)), "n_limited": int((s < 1.0).sum())}
     return y, stats
+
+
+# ---------------------------------------------------------------------- N14: pitch and tempo (WSOLA time stretch, then a rate conversion)
+# The arithmetic below IS the specification and csrc/vv_prosody.hip computes the same operations: an exact integer
+# cross-correlation search per frame and one float64 two-term blend per output sample, so the device equals this mirror bit for bit
+# and a request is the same alone or in a batch.
+WSOLA_N = 512                        # VV_WSOLA_N: frame length
+WSOLA_HS = 256                       # VV_WSOLA_HS: synthesis hop
+WSOLA_D = 128                        # VV_WSOLA_D: search radius, candidates -D ... D - 1
+WSOLA_MAX_PQ = 2048                  # p and q of a stretch ratio lie in 1 ... 2048, p / q in [1/4, 4]
+PITCH_RANGE = (-12.0, 12.0)          # accepted output_pitch, semitones
+TEMPO_RANGE = (0.5, 2.0)             # accepted output_tempo
+PROSODY_MAX_DEN = 32                 # both ratios are rounded to a fraction of at most this denominator
+_WSOLA_WINDOW = []
+
+
+class ProsodyPlan(NamedTuple):
+    """What prosody_plan decides for one request of n samples: the stretch ratio p / q (lowest terms), the pitch ratio p_r / q_r, the
+    stretched length n_s and the final length n_f."""
+    p: int
+    q: int
+    p_r: int
+    q_r: int
+    n_s: int
+    n_f: int
+
+
+def check_prosody(pitch=None, tempo=None):
+    """Validate ``output_pitch`` (semitones, -12 ... 12) and ``output_tempo`` (0.5 ... 2.0); None = off.  -> (float or None, float or None)."""
+    out = []
+    for name, v, (lo, hi), unit in (("output_pitch", pitch, PITCH_RANGE, "semitones"), ("output_tempo", tempo, TEMPO_RANGE, "times the speed")):
+        if v is not None:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise ValueError(f"{name} must be a number ({unit}) or None")
+            v = float(v)
+            if not lo <= v <= hi:                                                  # NaN fails both comparisons
+                raise ValueError(f"{name} must be between {lo:g} and {hi:g} ({unit})")
+        out.append(v)
+    return out[0], out[1]
+
+
+def prosody_plan(n: int, pitch=None, tempo=None) -> Optional[ProsodyPlan]:
+    """The one place where the options become ratios.  r = Fraction(2 ** (pitch / 12)).limit_denominator(32) = p_r / q_r (within 3.8 cents
+    of the ideal at every integer semitone), tau = Fraction(tempo).limit_denominator(32); the signal is stretched by p / q = r / tau to
+    n_s = ceil(n p / q) samples and then converted from rate p_r to rate q_r, of which the first n_f = ceil(n / tau) samples are kept.
+    None when both ratios reduce to 1: nothing is to be done."""
+    pitch, tempo = check_prosody(pitch, tempo)
+    r = Fraction(2.0 ** (pitch / 12.0)).limit_denominator(PROSODY_MAX_DEN) if pitch is not None else Fraction(1)
+    tau = Fraction(tempo).limit_denominator(PROSODY_MAX_DEN) if tempo is not None else Fraction(1)
+    if r == 1 and tau == 1:
+        return None
+    s = r / tau
+    n = int(n)
+    return ProsodyPlan(s.numerator, s.denominator, r.numerator, r.denominator, -(-n * s.numerator // s.denominator),
+                       -(-n * tau.denominator // tau.numerator))
+
+
+def wsola_window() -> np.ndarray:
+    """w[k] = 0.5 - 0.5 cos(2 pi k / N), k = 0 ... N - 1 (float64).  The device reads this table and never evaluates a cosine."""
+    if not _WSOLA_WINDOW:
+        w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(WSOLA_N, dtype=np.float64) / np.float64(WSOLA_N))).astype(np.float64)
+        w.setflags(write=False)
+        _WSOLA_WINDOW.append(w)
+    return _WSOLA_WINDOW[0]
+
+
+def check_stretch_ratio(p, q) -> Tuple[int, int]:
+    """A stretch ratio p / q as vv_pcm_stretch takes it: integers in 1 ... 2048, p != q, 1/4 <= p / q <= 4."""
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in (p, q)):
+        raise ValueError("time_stretch: p and q must be integers")
+    p, q = int(p), int(q)
+    if not (1 <= p <= WSOLA_MAX_PQ and 1 <= q <= WSOLA_MAX_PQ) or p == q or 4 * p < q or p > 4 * q:
+        raise ValueError(f"time_stretch: p and q in 1 ... {WSOLA_MAX_PQ}, p != q, 1/4 <= p / q <= 4")
+    return p, q
+
+
+def time_stretch(pcm, p: int, q: int):
+    """WSOLA time stretch of int16 ``pcm`` by p / q: the host mirror of vv_pcm_stretch, bit for bit.
+    -> (int16 [ceil(n p / q)], pos int32 [M + 1]).  Frame m >= 1 is taken from x at pos_m = a_m + delta, a_m = floor((m - 1) HS q / p),
+    where delta in -D ... D - 1 maximises the integer correlation with the natural continuation of frame m - 1 (x[pos_{m-1} + HS + k]);
+    among equal maxima the smallest |delta| wins, the negative one first.  x is zero outside [0, n).  Output sample i of hop m - 1 is
+    rint(w[k + HS] x[pos_{m-1} + HS + k] + w[k] x[pos_m + k]), k = i - (m - 1) HS: two products rounded on their own, one sum."""
+    x = _as_pcm16(pcm)
+    p, q = check_stretch_ratio(p, q)
+    N, HS, D = WSOLA_N, WSOLA_HS, WSOLA_D
+    n = x.size
+    n_s = -(-n * p // q)
+    M = -(-n_s // HS)
+    left, right = HS + D, N + HS + D + 8                    # pos_0 = -HS, pos_m >= -D after it; a_m <= n, so pos_m + HS + N <= n + D + HS + N
+    xp = np.zeros(left + n + right, np.int64)
+    xp[left: left + n] = x
+    pos = np.zeros(M + 1, np.int64)
+    pos[0] = -HS
+    delta = np.arange(-D, D, dtype=np.int64)
+    rank = 2 * np.abs(delta) - (delta < 0)                  # 0, -1, 1, -2, 2, ...: the order among equal maxima
+    for m in range(1, M + 1):
+        a = (m - 1) * HS * q // p
+        t = xp[left + pos[m - 1] + HS: left + pos[m - 1] + HS + N]
+        span = xp[left + a - D: left + a - D + N + 2 * D]
+        c = np.lib.stride_tricks.sliding_window_view(span, N)[: 2 * D] @ t       # int64: exact, |c| < 2^40
+        pos[m] = a + delta[np.argmax(c * 512 + (511 - rank))]
+    if n_s == 0:
+        return np.zeros(0, np.int16), pos.astype(np.int32)
+    w = wsola_window()
+    i = np.arange(n_s, dtype=np.int64)
+    m, k = i // HS + 1, i % HS
+    tail = w[k + HS] * xp[left + pos[m - 1] + HS + k].astype(np.float64)
+    head = w[k] * xp[left + pos[m] + k].astype(np.float64)
+    return np.clip(np.rint(tail + head), -32768.0, 32767.0).astype(np.int16), pos.astype(np.int32)
+
+
+def shift_prosody(pcm, pitch=None, tempo=None) -> np.ndarray:
+    """Pitch (semitones) and tempo of int16 ``pcm`` after prosody_plan: the stretch by p / q, then resample_rows through
+    resample_design(src = p_r, dst = q_r) for the first n_f samples.  The host mirror of the prosody step of HipSynth.finish_output
+    (the stretch bit for bit; the rate conversion to the bound of resample_rows)."""
+    x = _as_pcm16(pcm)
+    plan = prosody_plan(x.size, pitch, tempo)
+    if plan is None:
+        return x
+    if plan.p != plan.q:
+        x = time_stretch(x, plan.p, plan.q)[0]
+    if plan.p_r != plan.q_r:
+        taps, up, down, skip = output_design(plan.p_r, plan.q_r)
+        x = resample_rows(x, taps, up, down, skip, 0, 0, plan.n_f)
+    return x
 
 
 class AudioProcessor:

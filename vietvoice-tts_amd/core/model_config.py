@@ -84,6 +84,11 @@ class ModelConfig:
                                             # gain: with output_loudness the gain is no longer capped by the largest sample, without it the pre-gain is 1.
                                             # "true" limits a 4x oversampled estimate of the peak between the samples.  vv_pcm_limit on the HIP engine,
                                             # audio_processor.limit_peaks on injected sessions; synthesize_stream honours it (without output_loudness)
+    output_pitch: Optional[float] = None    # pitch shift in semitones, -12 ... 12: a WSOLA time stretch of the joined signal, then a rate
+                                            # conversion, before the loudness step.  The formants move with the pitch.  vv_pcm_stretch on the HIP
+                                            # engine, audio_processor.shift_prosody on injected sessions.  Not available in synthesize_stream
+    output_tempo: Optional[float] = None    # tempo, 0.5 ... 2.0 times the speed, by the same stretch: the synthesis itself is untouched (``speed``
+                                            # asks the model for another duration instead)
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -116,6 +121,8 @@ class ModelConfig:
         self.output_loudness, self.output_peak_dbfs = check_loudness(self.output_loudness, self.output_peak_dbfs)
         from .audio_processor import check_limiter
         check_limiter(self.output_limiter)
+        from .audio_processor import check_prosody
+        self.output_pitch, self.output_tempo = check_prosody(self.output_pitch, self.output_tempo)
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

@@ -165,21 +165,27 @@ class TTSEngine:
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
 
-    def _device_output(self, loudness=None, limiter=None) -> bool:
+    def _device_output(self, loudness=None, limiter=None, prosody=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate, an encoding, a loudness target or a limiter (the engine's, or a request's own: ``loudness``, ``limiter``) is set.
-        False = today's path: one copy per chunk group, the numpy join."""
+        rate, an encoding, a loudness target, a limiter, a pitch or a tempo (the engine's, or a request's own: ``loudness``, ``limiter``,
+        ``prosody``) is set.  False = today's path: one copy per chunk group, the numpy join."""
         rate, enc = self._output_options()
         return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16"
                                                                   or self.config.output_loudness is not None or loudness is not None
-                                                                  or self.config.output_limiter is not None or limiter is not None)
+                                                                  or self.config.output_limiter is not None or limiter is not None
+                                                                  or self.config.output_pitch is not None or self.config.output_tempo is not None
+                                                                  or prosody is not None)
 
-    def _finish_host(self, waves, loudness=None, limiter=None) -> np.ndarray:
-        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of the loudness normalisation
-        (N12; ``loudness`` = the request's own target, None = the engine's), the limiter (N13; ``limiter`` likewise), the output rate
-        and the encoding."""
-        from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output
+    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None) -> np.ndarray:
+        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of pitch and tempo (N14;
+        ``pitch`` / ``tempo`` = the request's own, None = the engine's), the loudness normalisation (N12; ``loudness`` likewise), the
+        limiter (N13; ``limiter`` likewise), the output rate and the encoding."""
+        from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output, shift_prosody
         final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
+        pitch = self.config.output_pitch if pitch is None else pitch
+        tempo = self.config.output_tempo if tempo is None else tempo
+        if pitch is not None or tempo is not None:
+            final = shift_prosody(np.ascontiguousarray(final, dtype=np.int16), pitch, tempo)
         loudness = self.config.output_loudness if loudness is None else loudness
         limiter = self.config.output_limiter if limiter is None else limiter
         if loudness is not None:
@@ -192,10 +198,10 @@ class TTSEngine:
             final = resample_output(final, self.config.sample_rate, rate)
         return encode_output(final, enc) if enc != "pcm16" else final
 
-    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None) -> List[np.ndarray]:
+    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
-        one HipSynth.finish_output call (join, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per request its
-        own target or None (= the engine's); ``limiter`` likewise (N13)."""
+        one HipSynth.finish_output call (join, prosody, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per
+        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14) likewise."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
@@ -210,11 +216,16 @@ class TTSEngine:
             lim = [lim if v is None else v for v in limiter]
             if all(v is None for v in lim):
                 lim = None
+        pros = {}
+        for key, own, mine in (("pitch", pitch, self.config.output_pitch), ("tempo", tempo, self.config.output_tempo)):
+            vals = [mine] * len(counts) if own is None else [mine if v is None else v for v in own]
+            if any(v is not None for v in vals):           # no pitch and no tempo anywhere: exactly the call of N13
+                pros[key] = vals
         if lim is None:                    # no limiter anywhere: exactly the call of N12
             return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs)
+                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs, **pros)
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim)
+                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **pros)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
                            apg_etas=None, apg_norms=None):
@@ -382,7 +393,11 @@ class TTSEngine:
         (``CrossfadeStream``) keeps only that tail: each raw chunk is clip-repaired once, emitted samples are never
         revisited, and the concatenation of all yielded blocks equals ``synthesize(text)`` sample for sample.
         With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance.
-        ``output_limiter`` alone streams (N13): a LimiterStream in front of the output rate / encoding holds back 2L + H samples."""
+        ``output_limiter`` alone streams (N13): a LimiterStream in front of the output rate / encoding holds back 2L + H samples.
+        ``output_pitch`` / ``output_tempo`` raise ValueError at once as well (N14): every frame position depends on the whole past."""
+        if self.config.output_pitch is not None or self.config.output_tempo is not None:
+            raise ValueError("synthesize_stream cannot honour output_pitch / output_tempo: the chain of frame positions needs the whole "
+                             "utterance; use synthesize, or unset them")
         if self.config.output_loudness is not None:       # checked here, not inside the generator: the caller hears of it without iterating
             raise ValueError("synthesize_stream cannot honour output_loudness: the integrated measure needs the whole utterance; "
                              "use synthesize, or unset output_loudness")
@@ -498,7 +513,9 @@ class TTSEngine:
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options(),
                                              loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs,
-                                             **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}))[0]
+                                             **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}),
+                                             **({} if cfg.output_pitch is None and cfg.output_tempo is None
+                                                else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}))[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

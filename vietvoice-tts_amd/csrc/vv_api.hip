@@ -2,16 +2,18 @@
 // transformer-steps / decode launch sequences, and HIP-event profiling per kernel class.
 // No torch types, no exceptions across the ABI, no device allocation inside the step loop.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.6 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.7 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -737,6 +739,55 @@ int vv_pcm_limit(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, 
            20.0 * (double)total_samples + 2.0 * (double)max_out * R, st);
     KCHK(c, vvk_pcm_limit(x, (long long)n_x, (const long long*)rows, R, L, mode, (long long)total_samples, (long long)total_tiles,
                           (long long)max_tiles, (long long)max_out, window, taps, params, meas, y, (long long)n_y, stats, ws, st, &m__));
+    return 0;
+}
+
+// N14: WSOLA time stretch of the joined signal.  As with N12 and N13 the rows come in host memory too: everything is checked before a launch.
+uint64_t vv_pcm_stretch_ws_bytes(int R) { return vvk_pcm_stretch_ws_bytes(R); }
+
+int vv_pcm_stretch(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* window,
+                   int16_t* y, int64_t n_y, int32_t* pos, int64_t n_pos, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0 || n_pos < 0) return c->fail(-22, "vv_pcm_stretch: bad sizes (1 <= R <= 65535)");
+    if (!x || !rows || !rows_host || !window || !pos || !ws)
+        return c->fail(-22, "vv_pcm_stretch: null pointer (x, rows, rows_host, window, pos, ws)");
+    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)window % 8 || (uintptr_t)pos % 4 || (uintptr_t)ws % 8)
+        return c->fail(-22, "vv_pcm_stretch: misaligned pointer (x, y 2 bytes; pos 4; rows, window, ws 8)");
+    if (y && (uintptr_t)y < (uintptr_t)(x + n_x) && (uintptr_t)x < (uintptr_t)(y + n_y))
+        return c->fail(-22, "vv_pcm_stretch: y overlaps x (an output sample reads two frames of the input: not in place)");
+    if (ws_bytes < vvk_pcm_stretch_ws_bytes(R))
+        return c->fail(-22, "vv_pcm_stretch: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
+                       (unsigned long long)vvk_pcm_stretch_ws_bytes(R));
+    std::vector<std::pair<int64_t, int64_t>> on_y, on_pos;
+    int64_t total_out = 0, total_frames = 0, max_out = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 6 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[5] < 0) return c->fail(-22, "vv_pcm_stretch: row %d has a negative field", r);
+        if (q[3] < 1 || q[3] > VV_WSOLA_MAX_PQ || q[4] < 1 || q[4] > VV_WSOLA_MAX_PQ || q[3] == q[4] || 4 * q[3] < q[4] || q[3] > 4 * q[4])
+            return c->fail(-22, "vv_pcm_stretch: row %d: p and q in 1 ... %d, p != q, 1/4 <= p / q <= 4", r, VV_WSOLA_MAX_PQ);
+        if (q[1] > n_x || q[0] > n_x - q[1] || q[1] > ((int64_t)1 << 30))
+            return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        const int64_t n_s = (q[1] * q[3] + q[4] - 1) / q[4], M = (n_s + VV_WSOLA_HS - 1) / VV_WSOLA_HS;
+        if (y && (n_s > n_y || q[2] > n_y - n_s)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (M + 1 > n_pos || q[5] > n_pos - (M + 1)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld entries of pos", r, (long long)n_pos);
+        if (y && n_s > 0) on_y.emplace_back(q[2], q[2] + n_s);
+        on_pos.emplace_back(q[5], q[5] + M + 1);
+        total_out += n_s;
+        total_frames += M;
+        if (n_s > max_out) max_out = n_s;
+    }
+    for (auto* spans : {&on_y, &on_pos}) {
+        std::sort(spans->begin(), spans->end());
+        for (size_t i = 1; i < spans->size(); ++i)
+            if ((*spans)[i].first < (*spans)[i - 1].second)
+                return c->fail(-22, "vv_pcm_stretch: rows overlap on %s", spans == &on_y ? "y" : "pos");
+    }
+    Prof p(c, VV_PROF_ELEMWISE, 2.0 * (double)total_frames * VV_WSOLA_N * 2 * VV_WSOLA_D + 3.0 * (double)total_out,
+           2.0 * (double)total_frames * (2 * VV_WSOLA_N + 2 * VV_WSOLA_D) + 6.0 * (double)total_out, st);
+    KCHK(c, vvk_pcm_stretch(x, (long long)n_x, (const long long*)rows, R, (long long)max_out, window, y, (long long)n_y, (int*)pos,
+                            (long long)n_pos, ws, st, &m__));
     return 0;
 }
 

@@ -93,6 +93,10 @@ int vvk_pcm_limit(const int16_t* x, long long n_x, const long long* rows, int R,
                   long long total_tiles, long long max_tiles, long long max_out, const double* window, const double* taps,
                   const double* params, const double* meas, int16_t* y, long long n_y, double* stats, void* ws, hipStream_t st,
                   const char** err);
+// N14 WSOLA time stretch (vv_prosody.hip): the sequential frame search per request, then the blend; rows R x 6 {src_off, n, dst_off, p, q, pos_off}
+unsigned long long vvk_pcm_stretch_ws_bytes(int R);
+int vvk_pcm_stretch(const int16_t* x, long long n_x, const long long* rows, int R, long long max_out, const double* window, int16_t* y,
+                    long long n_y, int* pos, long long n_pos, void* ws, hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

@@ -204,6 +204,9 @@ EXPORTS = {
     "vv_pcm_limit_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int64, C.c_int]),
     "vv_pcm_limit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_pcm_stretch_ws_bytes": (C.c_uint64, [C.c_int]),
+    "vv_pcm_stretch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                 C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -803,10 +806,11 @@ class HipSynth:
             cache[(src, dst)] = (torch.from_numpy(taps).to(self.device), up, down, skip)
         return cache[(src, dst)]
 
-    def pcm_resample(self, x: torch.Tensor, rows, src: int, dst: int, n_y: Optional[int] = None) -> torch.Tensor:
+    def pcm_resample(self, x: torch.Tensor, rows, src: int, dst: int, n_y: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Output rate (vv_pcm_resample): x int16 flat on the device at ``src`` Hz, rows = HOST rows {src_off, n_in, dst_off, n_out, m0, i0}
         (include/vvtts.h) -> int16 [n_y] at ``dst`` Hz through voice_bank.resample_design(src, dst).  A whole clip is m0 = i0 = 0 and
-        n_out = ceil(n_in * up / down).  The rows are validated here (in range of both buffers, disjoint on the output)."""
+        n_out = ceil(n_in * up / down).  The rows are validated here (in range of both buffers, disjoint on the output).
+        out (optional) = an existing flat int16 device buffer to write into (n_y = its length); what the rows read must not be written."""
         assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous()
         if int(src) == int(dst):
             raise ValueError("pcm_resample: equal rates need no launch")
@@ -815,6 +819,9 @@ class HipSynth:
         if not rows or any(len(r) != 6 for r in rows):
             raise ValueError("pcm_resample: rows of 6 entries {src_off, n_in, dst_off, n_out, m0, i0}")
         n_x = x.numel()
+        if out is not None:
+            assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.dim() == 1
+            n_y = out.numel()
         n_y = max((r[2] + r[3] for r in rows), default=0) if n_y is None else int(n_y)
         spans = []
         for so, n_in, do, n_out, m0, i0 in rows:
@@ -824,7 +831,7 @@ class HipSynth:
         spans.sort()
         if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
             raise ValueError("pcm_resample: rows overlap on the output")
-        y = torch.empty((max(n_y, 1),), dtype=torch.int16, device=self.device)
+        y = torch.empty((max(n_y, 1),), dtype=torch.int16, device=self.device) if out is None else out
         d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 6).to(self.device)
         with self._lock, torch.cuda.device(self.device):
             self._check(self.lib.vv_pcm_resample(self.ctx, x.data_ptr(), n_x, d.data_ptr(), len(rows), max(r[3] for r in rows), taps.data_ptr(),
@@ -1028,10 +1035,102 @@ class HipSynth:
 
         return backend
 
+    # ------------------------------------------------------------------ pitch and tempo (N14)
+    def pcm_stretch(self, x: torch.Tensor, rows, out: Optional[torch.Tensor] = None):
+        """The WSOLA time stretch on R joined signals in one call (vv_pcm_stretch), bit for bit
+        core.audio_processor.time_stretch.  x int16 flat on the device; rows = HOST rows (src_off, n, dst_off, p, q): x[src_off, +n) is
+        stretched by p / q to ceil(n p / q) samples at dst_off.  out = None: a new buffer; "positions": the search alone, no sample is
+        written and y is None; or a flat int16 device tensor that does not overlap x.  -> (y, pos, pos_offs): pos is the int32 device tensor of every frame position, request r's pos_0 ... pos_M are
+        pos[pos_offs[r] : pos_offs[r + 1]].  The rows are validated here; the call never synchronises."""
+        from .core.audio_processor import WSOLA_HS, check_stretch_ratio, wsola_window
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) != 5 for r in rows) or len(rows) > 65535:
+            raise ValueError("pcm_stretch: 1 to 65535 rows of 5 entries {src_off, n, dst_off, p, q}")
+        n_x, spans, full, pos_offs = x.numel(), [], [], [0]
+        for so, n, do, p, q in rows:
+            check_stretch_ratio(p, q)
+            if min(so, n, do) < 0 or so + n > n_x or n > 1 << 30:
+                raise ValueError(f"pcm_stretch: row {[so, n, do, p, q]} does not fit the {n_x} samples of x")
+            n_s = -(-n * p // q)
+            if n_s:
+                spans.append((do, do + n_s))
+            full.append([so, n, do, p, q, pos_offs[-1]])
+            pos_offs.append(pos_offs[-1] + -(-n_s // WSOLA_HS) + 1)
+        n_y, y = max((e for _b, e in spans), default=0), None
+        if not (isinstance(out, str) and out == "positions"):
+            if out is None:
+                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
+            else:
+                y = out
+                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
+            if y.numel() < n_y:
+                raise ValueError(f"pcm_stretch: out holds {y.numel()} samples, {n_y} are needed")
+            spans.sort()
+            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
+                raise ValueError("pcm_stretch: rows overlap on the output")
+            if y.data_ptr() < x.data_ptr() + 2 * n_x and x.data_ptr() < y.data_ptr() + 2 * y.numel():
+                raise ValueError("pcm_stretch: out overlaps x (the stretch is not in place)")
+        if "_wsola_window" not in self.__dict__:
+            self._wsola_window = torch.from_numpy(wsola_window().copy()).to(self.device)
+        R = len(full)
+        rows_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 6)
+        rows_d = rows_h.to(self.device)
+        pos = torch.empty((pos_offs[-1],), dtype=torch.int32, device=self.device)
+        ws = torch.empty((int(self.lib.vv_pcm_stretch_ws_bytes(R)) // 8 + 1,), dtype=torch.int64, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_pcm_stretch(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, self._wsola_window.data_ptr(),
+                                                _ptr(y), 0 if y is None else y.numel(), pos.data_ptr(), pos.numel(), ws.data_ptr(), ws.numel() * 8,
+                                                self._stream()))
+        return y, pos, pos_offs
+
+    def _prosody(self, buf: torch.Tensor, offs, lens, pitch, tempo):
+        """The prosody step of finish_output: -> (new buffer, offsets, lengths).  Every request gets its place in a new buffer, on 8-sample
+        boundaries as in plan_join: a request with a stretch alone is stretched into it, one with a pitch is stretched into an
+        intermediate region behind it and converted from there (one vv_pcm_resample call per distinct pitch ratio), one without prosody
+        is copied sample for sample."""
+        from .core.audio_processor import prosody_plan
+        R = len(lens)
+        plans = [prosody_plan(lens[i], pitch[i], tempo[i]) for i in range(R)]
+        new_offs, new_lens, end = [], [], 0
+        for i in range(R):
+            end = -(-end // 8) * 8
+            new_offs.append(end)
+            new_lens.append(lens[i] if plans[i] is None else plans[i].n_f)
+            end += new_lens[i]
+        base = -(-end // 8) * 8
+        mid, tmp = {}, base                                # behind the results: the stretched signals that still await their rate conversion
+        for i, pl in enumerate(plans):
+            if pl is not None and pl.p != pl.q and pl.p_r != pl.q_r:
+                mid[i] = tmp
+                tmp = -(-(tmp + pl.n_s) // 8) * 8
+        new = torch.empty((max(tmp, 8),), dtype=torch.int16, device=self.device)
+        stretch, convert = [], {}
+        for i, pl in enumerate(plans):
+            if pl is None:
+                new[new_offs[i]: new_offs[i] + lens[i]].copy_(buf[offs[i]: offs[i] + lens[i]])
+                continue
+            if pl.p != pl.q:
+                stretch.append([offs[i], lens[i], mid.get(i, new_offs[i]), pl.p, pl.q])
+            if pl.p_r != pl.q_r:               # from the stretched signal, or straight from the joined one when tempo == pitch ratio
+                convert.setdefault((pl.p_r, pl.q_r), []).append((i, pl.p != pl.q))
+        if stretch:
+            self.pcm_stretch(buf, stretch, out=new)
+        for (p_r, q_r), items in sorted(convert.items()):
+            for from_new in (True, False):
+                rows = [[mid[i] - base if from_new else offs[i], plans[i].n_s if from_new else lens[i], new_offs[i], plans[i].n_f, 0, 0]
+                        for i, stretched in items if stretched == from_new and plans[i].n_f > 0]
+                if rows:                       # source and destination are separate parts of ``new``
+                    self.pcm_resample(new[base:] if from_new else buf, rows, p_r, q_r, out=new[:base])
+        return new[:max(base, 8)], new_offs, new_lens
+
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None):
-        """The whole output stage of R requests on the caller's stream: join (-> loudness) (-> limiter) (-> output rate) (-> G.711), then
-        ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len) spans.
+                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None):
+        """The whole output stage of R requests on the caller's stream: join (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
+        (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
+        spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
+        new is called): core.audio_processor.prosody_plan turns them into a WSOLA stretch and a rate conversion on the joined signal, and
+        every later step runs on the result, so levels and the ceiling are those of what is heard.
         loudness = a target in LUFS for every request, or a per-request list with None entries (N12; None = nothing new is called);
         peak_dbfs = its sample-peak ceiling.  limiter = None | "sample" | "true" for every request, or a per-request list (N13; None =
         nothing new is called): a request with a limiter is measured only (pcm_loudness, out="measure") and takes its uncapped loudness
@@ -1039,6 +1138,11 @@ class HipSynth:
         -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), or uint8 G.711 codes."""
         from .core.audio_processor import resample_len
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
+        pitch, tempo = [list(v) if isinstance(v, (list, tuple)) else [v] * len(lens) for v in (pitch, tempo)]
+        if len(pitch) != len(lens) or len(tempo) != len(lens):
+            raise ValueError("finish_output: one pitch and one tempo entry per request")
+        if any(v is not None for v in pitch + tempo):
+            buf, offs, lens = self._prosody(buf, offs, lens, pitch, tempo)
         if isinstance(loudness, (list, tuple)):
             if len(loudness) != len(lens):
                 raise ValueError("finish_output: one loudness entry per request")
