@@ -661,6 +661,33 @@ VV_API int vv_pcm_stretch(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int6
                           const double* window, int16_t* y, int64_t n_y, int32_t* pos, int64_t n_pos, void* ws, uint64_t ws_bytes,
                           void* stream);
 
+/* ---- N15 FLAC output (RFC 9639): the final PCM of R requests as FLAC frames -- mono, 16 bits, frames of VV_FLAC_BLOCK
+ * samples (the last one of a signal may be shorter), fixed predictors only.  The recipe is pinned by core/audio_processor.py
+ * (flac_choose, flac_encode_frame), which the kernels equal byte for byte.  Per frame of m samples:
+ *     constant    if and only if all samples are equal
+ *     Fixed(o, po) o = 0 ... min(4, m - 1), po = 0 ... 4 with 2^po | m and (m >> po) > o: the o-th finite difference, Rice coded per
+ *                 partition under the k in 0 ... 14 with the fewest bits (the lowest such k)
+ *     verbatim    only when strictly smaller than every Fixed candidate
+ * the fewest bits win, ties go to the lower o, then the lower po.  The escape code is never written.  Every frame carries its number
+ * (frame0 + its index in the row), a CRC-8 of its header and a CRC-16 of the whole.  The stream header (fLaC + STREAMINFO, 42 bytes) is
+ * the host's: audio_processor.flac_stream_header.  The call never synchronises and reads nothing back; no global atomics.
+ *   x        int16, the requests' final signals
+ *   rows     R x 4 int64 {src_off, n, frame0, last} in device memory and the same rows in HOST memory (rows_host, checked by the call):
+ *            x[src_off, +n) becomes ceil(n / VV_FLAC_BLOCK) frames.  last = 0: a block of a stream, n a multiple of VV_FLAC_BLOCK
+ *   y        uint8 [n_y]: the frames of all rows back to back from y[0], in row order; nothing at or beyond info[R][0] is written.
+ *            n_y >= the sum of vv_flac_frame_bound over the frames.  Must not overlap x
+ *   info     (R + 1) x 3 int64 on the device: row r = {byte offset of its first frame, smallest frame, largest frame in bytes},
+ *            row R = {total bytes, 0, 0}
+ *   ws       ws_bytes >= vv_pcm_flac_ws_bytes(sum of the rows' frames, R), 8-byte aligned
+ * -22, and nothing is launched, for no context, R < 1 or R > 65535 (a row is one index of the launch grid), a null or misaligned pointer,
+ * a negative field, n < 1, frame0 + frames > 2^31, last outside 0 / 1 or last = 0 with a partial frame, a row outside n_x, n_y below the sum of the frame bounds, a ws that is too small,
+ * a rate outside 1 ... 655350, y overlapping x. */
+#define VV_FLAC_BLOCK 4096
+VV_API uint64_t vv_flac_frame_bound(int64_t m);      /* no frame of m samples (1 ... VV_FLAC_BLOCK) is longer; 0 outside that range */
+VV_API uint64_t vv_pcm_flac_ws_bytes(int64_t total_frames, int R);
+VV_API int vv_pcm_flac(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
+                       uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,7 +135,8 @@ def _resample_polyphase(x: np.ndarray, src: int, dst: int) -> np.ndarray:
     return resample_poly(x.astype(np.float64), dst // g, src // g).astype(np.float32)
 
 
-OUTPUT_ENCODINGS = ("pcm16", "ulaw", "alaw")      # ModelConfig.output_encoding; G.711 = WAVE format tags 7 (mu-law) / 6 (A-law)
+OUTPUT_ENCODINGS = ("pcm16", "ulaw", "alaw", "flac")      # ModelConfig.output_encoding; G.711 = WAVE format tags 7 (mu-law) / 6 (A-law);
+                                                          # "flac" = a complete FLAC file, lossless (N15)
 _WAVE_TAG = {"pcm16": 1, "alaw": 6, "ulaw": 7}
 _DESIGNS = {}
 
@@ -213,14 +214,224 @@ def lin2alaw(x: np.ndarray) -> np.ndarray:
     return (code ^ mask).astype(np.uint8)
 
 
-def encode_output(x: np.ndarray, encoding: str) -> np.ndarray:
+def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000) -> np.ndarray:
+    """``x`` int16 -> the encoding's bytes.  "flac" gives the complete file (stream header + frames) as uint8 and is
+    the one encoding that needs ``sample_rate``."""
     if encoding == "pcm16":
         return x
     if encoding == "ulaw":
         return lin2ulaw(x)
     if encoding == "alaw":
         return lin2alaw(x)
+    if encoding == "flac":
+        pcm = _flac_pcm(x)
+        if pcm.size == 0:
+            return np.frombuffer(flac_stream_header(sample_rate, 0), np.uint8).copy()
+        frames, lo, hi = flac_encode_frames(pcm, sample_rate)
+        return np.concatenate([np.frombuffer(flac_stream_header(sample_rate, pcm.size, lo, hi), np.uint8), frames])
     raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+
+
+# ---------------------------------------------------------------------- N15: FLAC output (RFC 9639), fixed predictors, mono, 16 bits
+# The arithmetic below IS the specification (DESIGN §8 N15): csrc/vv_flac.hip makes the same exhaustive, exact choice per frame and packs
+# the same bits, so this mirror and the device agree byte for byte, and so does a request alone or in a batch.  Per frame of m samples:
+#   constant   if and only if all m samples are equal (24 bits)
+#   Fixed(o, po), o = 0 ... min(4, m - 1), po = 0 ... 4 with 2^po | m and (m >> po) > o: the o-th finite difference, Rice coded per
+#              partition with the parameter k in 0 ... 14 that gives the fewest bits (the lowest such k):
+#              8 + 16 o + 6 + sum over partitions (4 + min_k [count (k + 1) + sum (u >> k)]) bits, u = 2 r (r >= 0), -2 r - 1 (r < 0)
+#   verbatim   8 + 16 m bits, only when strictly smaller than every Fixed candidate
+# the fewest bits win; ties go to the lower o, then the lower po.  |order-4 difference of int16| < 2^20, so u < 2^21 and k <= 14 always
+# suffices: the escape code is never written.  Every frame is independent: header (CRC-8), one subframe, zero bits to the byte, CRC-16.
+FLAC_BLOCK = 4096                    # VV_FLAC_BLOCK: samples per frame, the last one of a signal may be shorter
+FLAC_MAX_ORDER = 4
+FLAC_MAX_PART_ORDER = 4
+FLAC_MAX_RICE = 14
+FLAC_MAX_RATE = 655350               # 16 bits of tens of Hz in a frame header; STREAMINFO itself has 20 bits of Hz
+_FLAC_RATE_CODE = {88200: 1, 176400: 2, 192000: 3, 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10, 96000: 11}
+
+
+def _crc_table(poly: int, width: int) -> List[int]:
+    top, mask, table = 1 << (width - 1), (1 << width) - 1, []
+    for b in range(256):
+        c = b << (width - 8)
+        for _ in range(8):
+            c = ((c << 1) ^ poly) & mask if c & top else (c << 1) & mask
+        table.append(c)
+    return table
+
+
+_CRC8_TABLE = _crc_table(0x07, 8)
+_CRC16_TABLE = _crc_table(0x8005, 16)
+
+
+def flac_crc8(data: bytes) -> int:
+    """CRC-8 of a FLAC frame header: polynomial 0x07, initial value 0, not reflected."""
+    c = 0
+    for b in bytes(data):
+        c = _CRC8_TABLE[c ^ b]
+    return c
+
+
+def flac_crc16(data: bytes) -> int:
+    """CRC-16 of a FLAC frame: polynomial 0x8005, initial value 0, not reflected."""
+    c = 0
+    for b in bytes(data):
+        c = ((c << 8) & 0xFFFF) ^ _CRC16_TABLE[(c >> 8) ^ b]
+    return c
+
+
+def flac_frame_bound(m: int) -> int:
+    """vv_flac_frame_bound: no frame of m samples is longer -- 15 header bytes at most (4 fixed, 6 of frame number, 2 of block size,
+    2 of rate, CRC-8), the subframe header, m verbatim samples, CRC-16."""
+    return 15 + 1 + 2 * int(m) + 2 if m >= 1 else 0
+
+
+def _flac_pcm(pcm) -> np.ndarray:
+    x = np.asarray(pcm).reshape(-1)
+    if x.dtype != np.int16:
+        raise ValueError("FLAC: int16 PCM expected")
+    return x
+
+
+def _check_flac_rate(sample_rate) -> int:
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) <= FLAC_MAX_RATE:
+        raise ValueError(f"FLAC: a sample rate in 1 ... {FLAC_MAX_RATE} Hz is needed")
+    return int(sample_rate)
+
+
+def flac_stream_header(sample_rate: int, total_samples: int, min_frame: int = 0, max_frame: int = 0) -> bytes:
+    """The 42 bytes in front of the frames: ``fLaC`` and one STREAMINFO block (the last metadata block): block size 4096 / 4096, the
+    smallest and largest frame in bytes (0 = not known), rate, mono, 16 bits, total samples (0 = not known: a stream), and an MD5 of
+    zeros, which means "not computed"."""
+    sr, n = _check_flac_rate(sample_rate), int(total_samples)
+    if not 0 <= n < 1 << 36 or not 0 <= int(min_frame) < 1 << 24 or not 0 <= int(max_frame) < 1 << 24:
+        raise ValueError("FLAC: total samples below 2^36 and frame sizes below 2^24 are needed")
+    packed = (sr << 44) | (0 << 41) | (15 << 36) | n                       # 20 bits rate, 3 channels - 1, 5 bits - 1, 36 total samples
+    return (b"fLaC" + bytes([0x80, 0, 0, 34]) + struct.pack(">HH", FLAC_BLOCK, FLAC_BLOCK) + int(min_frame).to_bytes(3, "big") +
+            int(max_frame).to_bytes(3, "big") + packed.to_bytes(8, "big") + bytes(16))
+
+
+def _flac_utf8(v: int) -> bytes:
+    """The frame number in the extended UTF-8 coding: 1 to 6 bytes for up to 31 bits."""
+    if v < 0x80:
+        return bytes([v])
+    n = 2
+    while v >= 1 << (5 * n + 1):                                            # 2 bytes hold 11 bits, 3: 16, 4: 21, 5: 26, 6: 31
+        n += 1
+    lead = (0xFF << (8 - n)) & 0xFF | (v >> (6 * (n - 1)))
+    return bytes([lead] + [0x80 | ((v >> (6 * i)) & 0x3F) for i in range(n - 2, -1, -1)])
+
+
+def _flac_frame_header(m: int, sample_rate: int, number: int) -> bytes:
+    code = _FLAC_RATE_CODE.get(sample_rate)
+    tail = b""
+    if code is None:
+        if sample_rate <= 65535:
+            code, tail = 13, struct.pack(">H", sample_rate)
+        elif sample_rate % 10 == 0:
+            code, tail = 14, struct.pack(">H", sample_rate // 10)
+        else:
+            code = 0                                                        # from STREAMINFO
+    bs = 12 if m == FLAC_BLOCK else 7
+    head = bytes([0xFF, 0xF8, (bs << 4) | code, 0x08]) + _flac_utf8(number) + (b"" if m == FLAC_BLOCK else struct.pack(">H", m - 1)) + tail
+    return head + bytes([flac_crc8(head)])
+
+
+def flac_choose(x: np.ndarray):
+    """The subframe of one frame: -> (kind, o, po, ks, bits), kind = "constant" | "verbatim" | "fixed", ks = the Rice parameter of each
+    of the 2^po partitions, bits = the subframe's exact size.  Exhaustive over (o, po) and, per partition, k."""
+    x = np.asarray(x).reshape(-1).astype(np.int64)
+    m = x.size
+    if m < 1 or m > FLAC_BLOCK:
+        raise ValueError(f"a FLAC frame holds 1 ... {FLAC_BLOCK} samples")
+    if (x == x[0]).all():
+        return "constant", 0, 0, [], 24
+    pmax = 0
+    while pmax < FLAC_MAX_PART_ORDER and m % (2 << pmax) == 0:
+        pmax += 1
+    shifts = np.arange(FLAC_MAX_RICE + 1).reshape(-1, 1, 1)
+    best = None
+    for o in range(min(FLAC_MAX_ORDER, m - 1) + 1):
+        r = np.diff(x, n=o)
+        u = np.zeros(m, np.int64)                                           # the o warm-up samples count as u = 0: nothing in any sum
+        u[o:] = np.where(r >= 0, 2 * r, -2 * r - 1)
+        sums = (u.reshape(1, 1 << pmax, -1) >> shifts).sum(axis=2)          # [k][finest partition]
+        for po in range(pmax, -1, -1):
+            if po < pmax:
+                sums = sums[:, 0::2] + sums[:, 1::2]                        # additive over partitions
+            if (m >> po) <= o:
+                continue
+            count = np.full(1 << po, m >> po, np.int64)
+            count[0] -= o
+            cost = count.reshape(1, -1) * (shifts.reshape(-1, 1) + 1) + sums
+            ks = cost.argmin(axis=0)                                        # the first minimum: the lowest k
+            bits = 8 + 16 * o + 6 + int((4 + cost.min(axis=0)).sum())
+            if best is None or (bits, o, po) < (best[4], best[1], best[2]):
+                best = ("fixed", o, po, [int(k) for k in ks], bits)
+    if 8 + 16 * m < best[4]:
+        return "verbatim", 0, 0, [], 8 + 16 * m
+    return best
+
+
+def _put(bits: np.ndarray, pos, value, n: int):
+    """n bits of each value, most significant first, from bit position pos on."""
+    pos, value = np.asarray(pos, np.int64), np.asarray(value, np.int64)
+    for b in range(n):
+        bits[pos + b] = (value >> (n - 1 - b)) & 1
+
+
+def flac_encode_frame(x: np.ndarray, sample_rate: int, number: int) -> bytes:
+    """One complete frame of 1 ... 4096 int16 samples with frame number ``number``."""
+    x = np.asarray(x).reshape(-1).astype(np.int64)
+    m = x.size
+    kind, o, po, ks, n_bits = flac_choose(x)
+    bits = np.zeros(n_bits, np.uint8)
+    if kind == "constant":
+        _put(bits, 8, x[0] & 0xFFFF, 16)                                    # subframe header 0 000000 0
+    elif kind == "verbatim":
+        _put(bits, 0, 0x02, 8)
+        _put(bits, 8 + 16 * np.arange(m), x & 0xFFFF, 16)
+    else:
+        _put(bits, 0, (8 | o) << 1, 8)
+        _put(bits, 8 + 16 * np.arange(o), x[:o] & 0xFFFF, 16)
+        base = 8 + 16 * o
+        _put(bits, base, po, 6)                                             # coding method 00, partition order
+        r = np.diff(x, n=o)
+        u = np.where(r >= 0, 2 * r, -2 * r - 1)
+        ps = m >> po
+        count = np.full(1 << po, ps, np.int64)
+        count[0] -= o
+        k = np.repeat(np.asarray(ks, np.int64), count)
+        first = np.concatenate([[0], np.cumsum(count)[:-1]])                # each partition's first residual carries its parameter
+        q = u >> k
+        lens = q + 1 + k
+        lens[first] += 4
+        stop = base + 6 + np.cumsum(lens) - 1 - k                           # the one bit that ends the run of q zeros
+        _put(bits, stop[first] - q[first] - 4, np.asarray(ks, np.int64), 4)
+        bits[stop] = 1
+        for b in range(int(k.max())):
+            sel = k > b
+            bits[stop[sel] + 1 + b] = (u[sel] >> (k[sel] - 1 - b)) & 1
+        assert stop[-1] + k[-1] + 1 == n_bits
+    body = _flac_frame_header(m, sample_rate, number) + np.packbits(bits).tobytes()
+    return body + struct.pack(">H", flac_crc16(body))
+
+
+def flac_encode_frames(pcm, sample_rate: int, frame0: int = 0, last: bool = True):
+    """The frames of an int16 signal, the host mirror of vv_pcm_flac: ceil(n / 4096) frames numbered from ``frame0``,
+    back to back.  ``last=False`` = a block of a stream: n must be a multiple of 4096.  -> (uint8 frames, smallest frame, largest frame
+    in bytes); (empty, 0, 0) for an empty signal."""
+    pcm = _flac_pcm(pcm)
+    sr, frame0 = _check_flac_rate(sample_rate), int(frame0)
+    n_frames = -(-pcm.size // FLAC_BLOCK)
+    if frame0 < 0 or frame0 + n_frames > 1 << 31:
+        raise ValueError("FLAC: frame numbers run from 0 to 2^31 - 1")
+    if not last and pcm.size % FLAC_BLOCK:
+        raise ValueError(f"FLAC: a block that is not the last one holds whole frames of {FLAC_BLOCK} samples")
+    frames = [flac_encode_frame(pcm[f * FLAC_BLOCK: (f + 1) * FLAC_BLOCK], sr, frame0 + f) for f in range(n_frames)]
+    if not frames:
+        return np.zeros(0, np.uint8), 0, 0
+    return np.frombuffer(b"".join(frames), np.uint8).copy(), min(map(len, frames)), max(map(len, frames))
 
 
 # ---------------------------------------------------------------------- N12: loudness normalisation (ITU-R BS.1770-4 integrated, gated)
@@ -734,6 +945,12 @@ class AudioProcessor:
         return b"RIFF" + struct.pack("<I", len(body)) + body
 
     @staticmethod
+    def _flac_bytes(flat: np.ndarray) -> bytes:
+        if flat.dtype != np.uint8 or flat.size < 42 or flat[:4].tobytes() != b"fLaC":
+            raise ValueError("flac audio must be the uint8 bytes of a FLAC file (encode_output(x, 'flac', rate))")
+        return flat.tobytes()
+
+    @staticmethod
     def save_audio(audio: np.ndarray, file_path: str, sample_rate: int, encoding: str = "pcm16") -> None:
         if audio.size == 0:
             raise ValueError("Cannot save empty audio.")
@@ -741,6 +958,10 @@ class AudioProcessor:
             raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
         Path(file_path).parent.mkdir(parents=True, exist_ok=True)
         flat = np.asarray(audio).reshape(-1)
+        if encoding == "flac":                       # already a complete file (N15): written as it is
+            with open(file_path, "wb") as fh:
+                fh.write(AudioProcessor._flac_bytes(flat))
+            return
         if encoding != "pcm16":                      # already companded (uint8) by the output stage
             if flat.dtype != np.uint8:
                 raise ValueError(f"{encoding} audio must be uint8 G.711 codes")
@@ -763,6 +984,8 @@ class AudioProcessor:
         if encoding != "pcm16":
             if encoding not in OUTPUT_ENCODINGS:
                 raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+            if encoding == "flac":                   # not a WAVE file: the FLAC file the output stage made, as it is
+                return AudioProcessor._flac_bytes(np.asarray(audio).reshape(-1))
             return AudioProcessor._g711_wav(np.asarray(audio).reshape(-1), sample_rate, encoding)
         buf = io.BytesIO()
         flat = np.asarray(audio).reshape(-1).astype("<i2")
@@ -876,6 +1099,8 @@ class OutputStream:
     (HipSynth.output_stream_backends).  ``push`` returns what became final, ``flush`` the rest (inputs past the end are zeros)."""
 
     def __init__(self, src: int, dst, encoding: str = "pcm16", resample=None, encode=None):
+        if encoding == "flac":
+            raise ValueError("OutputStream: FLAC frames span blocks; put a FlacStream behind an OutputStream with encoding 'pcm16'")
         self.rate = None if dst is None or int(dst) == int(src) else int(dst)
         self.encoding = encoding
         if self.rate is not None:
@@ -918,6 +1143,42 @@ class OutputStream:
             return np.zeros(0, np.uint8 if self.encoding != "pcm16" else np.int16)
         y = self._emit(resample_len(self.n_seen, self.up, self.down))
         return self._encode(y) if self.encoding != "pcm16" else y
+
+
+class FlacStream:
+    """FLAC for a STREAM of final int16 blocks at the output rate (``synthesize_stream``), behind the OutputStream.  Frames
+    are independent, so it carries only the fewer-than-4096 samples that do not fill a frame yet and the next frame number.  The first
+    ``push`` starts with the stream header (total samples 0 = not known), every ``push`` returns the whole frames in hand, ``flush`` the
+    remainder as the final short frame.  The concatenation is a valid stream whose frames equal ``flac_encode_frames`` of the whole
+    signal.  ``encode(pcm, frame0, last)`` returns the frames' bytes: the host mirror, or the device kernel
+    (HipSynth.output_stream_backends)."""
+
+    def __init__(self, sample_rate: int, encode=None):
+        self.rate = _check_flac_rate(sample_rate)
+        self._encode = encode or (lambda pcm, frame0, last: flac_encode_frames(pcm, self.rate, frame0, last)[0])
+        self.left = np.zeros(0, np.int16)
+        self.frame = 0
+        self.started = False
+
+    def _out(self, pcm: np.ndarray, last: bool) -> np.ndarray:
+        parts = []
+        if not self.started:
+            parts.append(np.frombuffer(flac_stream_header(self.rate, 0), np.uint8))
+            self.started = True
+        if pcm.size:
+            parts.append(np.asarray(self._encode(pcm, self.frame, last), np.uint8).reshape(-1))
+            self.frame += -(-pcm.size // FLAC_BLOCK)
+        return np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+
+    def push(self, block: np.ndarray) -> np.ndarray:
+        have = np.concatenate([self.left, _flac_pcm(block)])
+        whole = have.size - have.size % FLAC_BLOCK
+        self.left = have[whole:]
+        return self._out(have[:whole], False)
+
+    def flush(self) -> np.ndarray:
+        rest, self.left = self.left, np.zeros(0, np.int16)
+        return self._out(rest, True)
 
 
 class LimiterStream:

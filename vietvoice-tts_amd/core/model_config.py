@@ -74,7 +74,7 @@ class ModelConfig:
     output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
                                             # function); "device" = vv_join_chunks in HBM, bit for bit the same samples, one copy of the final bytes
     output_sample_rate: Optional[int] = None   # None = sample_rate; else the output is rate-converted (band-limited polyphase FIR, vv_pcm_resample)
-    output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode).  A rate or an encoding runs on the
+    output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode) | "flac" (a FLAC file, lossless, vv_pcm_flac: N15).  A rate or an encoding runs on the
                                             # device on the HIP engine, through the host mirrors on injected sessions
     output_loudness: Optional[float] = None  # programme loudness of every utterance in LUFS (ITU-R BS.1770-4 integrated, gated), -60 ... -5; None = off.
                                             # Measured and applied after the join, before the output rate and the encoding (vv_pcm_loudness on the HIP
@@ -109,8 +109,9 @@ class ModelConfig:
             raise ValueError(f"noise_source must be one of {list(NOISE_SOURCES)}")
         if self.output_stage not in ("host", "device"):
             raise ValueError("output_stage must be 'host' or 'device'")
-        if self.output_encoding not in ("pcm16", "ulaw", "alaw"):
-            raise ValueError("output_encoding must be one of ['pcm16', 'ulaw', 'alaw']")
+        from .audio_processor import OUTPUT_ENCODINGS
+        if self.output_encoding not in OUTPUT_ENCODINGS:
+            raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
         if self.output_sample_rate is not None:
             if isinstance(self.output_sample_rate, bool) or int(self.output_sample_rate) != self.output_sample_rate:
                 raise ValueError("output_sample_rate must be an integer number of Hz or None")

@@ -196,7 +196,7 @@ class TTSEngine:
         rate, enc = self._output_options()
         if rate is not None:
             final = resample_output(final, self.config.sample_rate, rate)
-        return encode_output(final, enc) if enc != "pcm16" else final
+        return encode_output(final, enc, self.output_rate) if enc != "pcm16" else final
 
     def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
@@ -386,7 +386,7 @@ class TTSEngine:
     def synthesize_stream(self, text: str, gender: Optional[str] = None, group: Optional[str] = None, area: Optional[str] = None,
                           emotion: Optional[str] = None, sample_iteration: Optional[int] = None,
                           reference_audio: Optional[str] = None, reference_text: Optional[str] = None, chunks_per_step: int = 1):
-        """Generator of PCM blocks (int16 at the output rate, or uint8 G.711 codes): audio is emitted as soon as a group of ``chunks_per_step``
+        """Generator of PCM blocks (int16 at the output rate, uint8 G.711 codes, or the bytes of a FLAC stream: N15): audio is emitted as soon as a group of ``chunks_per_step``
         chunks is synthesised instead of after the whole text (the reference buffers everything, api/app.py:59-65).
         Overlap-save: the improved cross-fade only rewrites the last ``cross_fade_duration`` of what has been joined
         so far (audio_processor.py:122-192), so everything before that tail is final and can be yielded.  The joiner
@@ -419,8 +419,15 @@ class TTSEngine:
             # N10: a rate or an encoding is applied to every final block by an OutputStream that carries the filter's position and history
             # (on the HIP engine through the device kernels, blocks re-uploaded), so that the blocks still add up to synthesize()'s result
             rate, enc = self._output_options()
-            ostream = None
-            if rate is not None or enc != "pcm16":
+            ostream = fstream = None
+            if enc == "flac":                  # N15: frames are independent, so FLAC streams -- a FlacStream behind the rate conversion
+                from .audio_processor import FlacStream, OutputStream
+                eng = self.model_session_manager.engine
+                backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
+                if rate is not None:
+                    ostream = OutputStream(self.config.sample_rate, rate, "pcm16", backends[0], None)
+                fstream = FlacStream(self.output_rate, backends[1])
+            elif rate is not None or enc != "pcm16":
                 from .audio_processor import OutputStream
                 eng = self.model_session_manager.engine
                 backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
@@ -445,16 +452,26 @@ class TTSEngine:
                     block = lstream.push(np.ascontiguousarray(block, dtype=np.int16))
                 if ostream is not None:
                     block = ostream.push(block)
+                if fstream is not None:
+                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
                 if block.size:
                     yield block
             if lstream is not None:
                 block = lstream.flush()
                 if ostream is not None:
                     block = ostream.push(block)
+                if fstream is not None:
+                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
                 if block.size:
                     yield block
             if ostream is not None:
                 block = ostream.flush()
+                if fstream is not None:
+                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
+                if block.size:
+                    yield block
+            if fstream is not None:
+                block = fstream.flush()
                 if block.size:
                     yield block
         except Exception as e:

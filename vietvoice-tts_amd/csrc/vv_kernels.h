@@ -97,6 +97,12 @@ int vvk_pcm_limit(const int16_t* x, long long n_x, const long long* rows, int R,
 unsigned long long vvk_pcm_stretch_ws_bytes(int R);
 int vvk_pcm_stretch(const int16_t* x, long long n_x, const long long* rows, int R, long long max_out, const double* window, int16_t* y,
                     long long n_y, int* pos, long long n_pos, void* ws, hipStream_t st, const char** err);
+// N15 FLAC output (vv_flac.hip): per frame of 4096 samples the exhaustive fixed-predictor / Rice search, the frames' offsets, the bit packing;
+// rows R x 4 {src_off, n, frame0, last}
+unsigned long long vvk_flac_frame_bound(long long m);
+unsigned long long vvk_pcm_flac_ws_bytes(long long total_frames, int R);
+int vvk_pcm_flac(const int16_t* x, long long n_x, const long long* rows, int R, int rate, long long total_frames, long long max_frames,
+                 uint8_t* y, long long n_y, long long* info, void* ws, hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,
