@@ -390,6 +390,9 @@ typedef struct vv_ln_args {
     int32_t delta_tail_parts, delta2_tail_parts;   /*   it is the sum, in part order, of fp32 delta_tail [parts][R - tail_row0][ld_delta] */
     const void *delta_tail, *delta2_tail;          /*   rounded once to delta_dtype (0 / 1 parts = none)                       */
 } vv_ln_args;
+/* Refused with -22 (nothing is launched, nothing written): R < 1; D outside [4, 1024] or not a multiple of 4; ldx, ldy not multiples of 4
+ * or below D; ld_delta likewise when delta is given; delta2 without delta; a tail (parts > 1) without its delta or its buffer, with
+ * tail_row0 outside [0, R), more than 8 parts or a buffer that is not 16-byte aligned.  w / b NULL = 1 - add_one / 0. */
 VV_API int vv_layernorm(vv_ctx* ctx, const vv_ln_args* args, void* stream);
 
 typedef struct vv_posconv_args {
@@ -455,6 +458,23 @@ VV_API int vv_vocos_im2col(vv_ctx* ctx, const float* x, int B, int N, const int3
                            float* out, int ld_out, void* stream);
 VV_API int vv_istft_head(vv_ctx* ctx, int B, int T_max, const float* head, int ld_head, const int32_t* n_frames, int16_t* pcm, int ld_pcm,
                          int32_t* pcm_len, float* wave_f32, void* stream);
+/* Text-stack single-kernel entries (unit parity): thin wrappers over the kernels vv_preprocess chains (and, for vv_dwconv, the Vocos
+ * backbone).  A violated precondition is refused with -22 before anything is launched.  Sequence s of n_seq reads seq_len[s % B].
+ * vv_text_embed: out [2 B][N][Dt] f32 = emb[id] + pos[t]; sequences [0, B) take id = ids[b][t] + 1 for t < min(text_len[b], ld_ids)
+ *   and the filler id 0 behind it, sequences [B, 2 B) (the drop half) the filler everywhere; id is clamped to [0, vocab_rows - 1].
+ *   emb [vocab_rows][Dt], pos [>= N][Dt], out: 16-byte aligned; Dt % 4 == 0; B, N, ld_ids, vocab_rows >= 1.
+ * vv_dwconv: depthwise conv along tokens, in / out [n_seq][N][C] f32 (distinct buffers), w [C][KW], bias [C]; tokens outside
+ *   [0, min(seq_len, N)) read as zero (seq_len NULL = N; a length <= 0 leaves the bias), every one of the N output rows is written.
+ *   in, out, bias 16-byte aligned; C % 4 == 0; KW odd; B >= 1 when seq_len is given.
+ * vv_grn: x [n_seq][N][C] of dtype (VV_DTYPE_F32 / VV_DTYPE_BF16), in place: x = x * (gamma * nx + 1) + beta on all N rows, nx = g / (mean_c g + 1e-6),
+ *   g[c] = sqrt(sumsq[s][c]), sumsq [n_seq][C] f32 (caller's scratch, written) = the sum of x^2 over the tokens [0, min(seq_len, N)).
+ *   x aligned to 4 elements, beta to 16 bytes; C % 64 == 0, C <= 8192; B >= 1 when seq_len is given. */
+VV_API int vv_text_embed(vv_ctx* ctx, const int32_t* ids, int ld_ids, const int32_t* text_len, const float* emb, const float* pos,
+                         int vocab_rows, float* out, int B, int N, int Dt, void* stream);
+VV_API int vv_dwconv(vv_ctx* ctx, const float* in, float* out, const float* w, const float* bias, const int32_t* seq_len, int B, int n_seq,
+                     int N, int C, int KW, void* stream);
+VV_API int vv_grn(vv_ctx* ctx, int dtype, void* x, float* sumsq, const float* gamma, const float* beta, const int32_t* seq_len, int B,
+                  int n_seq, int N, int C, void* stream);
 VV_API int vv_conv_post(vv_ctx* ctx, const float* in, const float* w, float bias, int16_t* pcm, int ld_pcm, float* wave_f32,
                  int B, int C, int T, int KW, float pre_slope, const int32_t* len_in, void* stream);
 VV_API int vv_mel(vv_ctx* ctx, const int16_t* audio, int ld_audio, const int32_t* audio_len, float* mel, int B, int F_max,

@@ -1,5 +1,7 @@
 """Helpers for the -m gpu parity tests: call single kernels through the C ABI."""
+import copy
 import ctypes as C
+import dataclasses
 import math
 
 import torch
@@ -1316,3 +1318,942 @@ def gemm_walk_cases():
 
 def gemm_tail_case():
     return GemmCase("pp_split_k_tail", "tail", "pp", mode=MODE_GATE_STORE, **GEMM_TAIL)
+
+
+# ------------------------------------------------------------------------------------ norms and the text kernels: cases, float64 references, bounds
+# (tests/test_norm_gpu.py runs the cases on the device, tests/test_norm_ref_cpu.py checks the claims made here without one;
+#  profiles/norm_parity/notes.md).  Every reference is float64 on the operands as the kernel receives them; A_e is the same expression on
+# absolute values; the metric is parity_err; every bound is max(c 2^-24, 4 x yardstick) with c counted from the kernel's roundings (each
+# docstring gives the count) and the yardstick the CPU library in fp32 on the same operands.  No constant is fitted to a device result.
+
+NORM_GUARD = 3                          # guard rows in front of and behind an output with a leading dimension
+MISH_SLOPE = 1.09                       # bounds |mish'| (1.0884 at z = 1.49)
+# |act_apply(z, mish) - mish(z)| <= 12 x 2^-24 |z|.  The roundings of x t / (t + 2), t = n (n + 2), n = exp2(1.4427 x): the rounded
+# argument moves x by one relative rounding (|f'| |x| 2^-24 <= 1.09), v_exp_f32 is good to 1 ulp = 2 x 2^-24 of n, which is a shift of x
+# by that much (<= 2 |x| 2^-24 through x tanh'(..) <= |x|), then n + 2, n (n + 2), t + 2, v_rcp_f32 (1 ulp = 2), x t and the last product:
+# 7 relative roundings of a value <= |x|.  1.09 + 2 + 7 = 10.1, taken as 12 (tests/test_norm_ref_cpu.py: an fp32 emulation on a dense grid).
+MISH_ALLOW = 12.0 * EPS24
+EPS_F32 = float(torch.tensor(1e-6, dtype=torch.float32))        # the 1e-6 the kernels hold as a float
+
+
+def _nan_rows(t, ld, tail_rows):
+    """[R][W] host tensor -> device [R + tail_rows][ld] whose padding columns and tail rows hold NaN (float) or 2^30 (int)."""
+    R, W = t.shape
+    fill = NAN if t.dtype.is_floating_point else 2 ** 30
+    buf = torch.full((R + tail_rows, ld), fill, dtype=t.dtype, device=DEV)
+    buf[:R, :W] = t.to(DEV)
+    return buf
+
+
+def _nan_tail(t, tail=8, head=0):
+    """Any host tensor, flat on the device, `head` NaN elements in front of it and `tail` behind -> (keep-alive, pointer of the data)."""
+    fill = NAN if t.dtype.is_floating_point else 2 ** 30
+    buf = torch.full((head + t.numel() + tail,), fill, dtype=t.dtype, device=DEV)
+    buf[head:head + t.numel()] = t.reshape(-1).to(DEV)
+    return buf, buf.data_ptr() + head * t.element_size()
+
+
+def _pad_intact(buf, R, W, what):
+    """The padding of a buffer made by _nan_rows still holds its poison."""
+    bad = (lambda v: ~torch.isnan(v)) if buf.dtype.is_floating_point else (lambda v: v != 2 ** 30)
+    assert not bool(bad(buf[:R, W:]).any()), f"{what}: a padding column was written"
+    assert not bool(bad(buf[R:]).any()), f"{what}: a row behind the last was written"
+
+
+def _rows_out(R, W, ld, dtype):
+    """-> (whole buffer [G + R + G][ld] of CONV_FILL, the [R][ld] view in its middle)."""
+    buf = torch.full((R + 2 * NORM_GUARD, ld), CONV_FILL, dtype=dtype, device=DEV)
+    return buf, buf[NORM_GUARD:NORM_GUARD + R]
+
+
+def _rows_out_intact(buf, R, W, what):
+    assert bool((buf[:NORM_GUARD] == CONV_FILL).all()) and bool((buf[NORM_GUARD + R:] == CONV_FILL).all()), f"{what}: a guard row was written"
+    assert bool((buf[NORM_GUARD:NORM_GUARD + R, W:] == CONV_FILL).all()), f"{what}: a padding column of the output was written"
+
+
+def _butterfly64(v):
+    """wave_sum of vv_common.h on a [..., 64] fp32 tensor: v += v[lane ^ o], o = 32 .. 1; every lane ends with the same sum."""
+    lane = torch.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lane ^ o]
+    return v[..., 0]
+
+
+def mish_f32_emulation(x):
+    """act_apply(x, VV_ACT_MISH) step by step in fp32."""
+    n = torch.exp2(torch.tensor(1.4426950408889634, dtype=torch.float32) * x)
+    t = n * (n + 2.0)
+    return torch.where(x > 20.0, x, x * t * (1.0 / (t + 2.0)))
+
+
+# ---- LayerNorm (ln_mod_kernel)
+LN_DATA = ("normal", "mean300", "const", "outlier", "tiny")
+
+
+@dataclasses.dataclass(frozen=True)
+class LnCase:
+    name: str
+    D: int = 260
+    R: int = 5
+    out_bf16: bool = False
+    delta_bf16: bool = False
+    add_one: int = 1
+    has_w: bool = True
+    has_b: bool = True
+    n_delta: int = 0
+    keep_x: int = 0
+    tail_row0: int = 0
+    tail_parts: tuple = (0, 0)          # split-K parts of delta and of delta2 (0 = that delta has no tail)
+    data: str = "normal"
+    seed: int = 0
+    eps: float = 1e-6
+    kernel = "ln_mod_kernel"
+
+    @property
+    def out_dtype(self):
+        return torch.bfloat16 if self.out_bf16 else torch.float32
+
+    @property
+    def delta_dtype(self):
+        return torch.bfloat16 if self.delta_bf16 else torch.float32
+
+    def ops(self):
+        g = torch.Generator().manual_seed(7000 + self.seed)
+        R, D = self.R, self.D
+        o = _Ops()
+        z = torch.randn(R, D, generator=g)
+        if self.data == "mean300":
+            o.x = 300.0 + 0.03 * z
+        elif self.data == "const":
+            o.x = (1.7 + 0.25 * torch.arange(R, dtype=torch.float32))[:, None].expand(R, D).contiguous()
+        elif self.data == "outlier":
+            o.x = z.clone()
+            o.x[:, -1] = 1e4
+        elif self.data == "tiny":
+            o.x = 1e-4 * z
+        else:
+            o.x = z
+        o.w, o.b = torch.randn(D, generator=g) * 0.3, torch.randn(D, generator=g) * 0.3
+        o.d = [(torch.randn(R, D, generator=g) * 0.5).to(self.delta_dtype) for _ in range(2)]
+        o.t = [torch.randn(max(p, 1), R - self.tail_row0, D, generator=g) * 0.25 for p in self.tail_parts]
+        return o
+
+    def refs(self, o=None):
+        return ln_ref(self, o)
+
+
+def ln_delta(case, o, i):
+    """What the kernel adds for delta i, as fp32: the delta itself, and on the rows of a split-K tail the fp32 parts summed in part order,
+    the SUM rounded once to the delta's dtype."""
+    e = o.d[i].float().clone()
+    p = case.tail_parts[i]
+    if p:
+        acc = o.t[i][0].clone()
+        for k in range(1, p):
+            acc = acc + o.t[i][k]
+        e[case.tail_row0:] = acc.to(case.delta_dtype).float()
+    return e
+
+
+def ln_stream(case, o):
+    """The fp32 residual stream the kernel normalises (and writes back unless keep_x): (x + d1) + d2, exact."""
+    xs = o.x
+    for i in range(case.n_delta):
+        xs = xs + ln_delta(case, o, i)
+    return xs
+
+
+def _ln_wb(case, o):
+    one = float(case.add_one)
+    return (o.w if case.has_w else torch.full((case.D,), 1.0 - one)), (o.b if case.has_b else torch.zeros(case.D)), one
+
+
+def ln_eval(case, o, mode, xs=None):
+    xs = ln_stream(case, o) if xs is None else xs
+    w, b, one = _ln_wb(case, o)
+    if mode == "f32":
+        return F.layer_norm(xs, (case.D,), eps=case.eps) * (w + one) + b
+    X, wf = xs.double(), w.double() + one
+    mean = X.mean(1, keepdim=True)
+    rstd = (((X - mean) ** 2).mean(1, keepdim=True) + float(torch.tensor(case.eps, dtype=torch.float32))).rsqrt()
+    if mode == "abs":
+        return (X.abs() + X.abs().mean(1, keepdim=True)) * rstd * wf.abs() + b.double().abs()
+    return (X - mean) * rstd * wf + b.double()
+
+
+LN_C = 44.0
+
+
+def ln_bound(yardstick):
+    """max(44 x 2^-24, 4 x yardstick).  The roundings of ln_mod_kernel, each relative to a term A_e dominates: the mean takes at most 16
+    serial adds per lane (4 register groups x (3 adds of the float4 + 1 accumulate)), 6 shuffle levels and the division: 23, against
+    mean|x| rstd |w + one|.  The variance: the subtraction and the square of every term (3 on the square), the same 23 for the sum and the
+    division, the + eps: 27, halved by the inverse square root, plus 2 for v_rsq_f32 (1 ulp): 15.5, against |x - mean| rstd |w + one|.
+    The affine: x - mean, x rstd, w + one, the product, + b: 5.  23 + 15.5 + 5 = 43.5."""
+    return max(LN_C * EPS24, 4.0 * yardstick)
+
+
+def ln_ref(case, o=None):
+    o = case.ops() if o is None else o
+    r = _Ops()
+    r.xs = ln_stream(case, o)
+    r.ref, r.A, r.f32 = ln_eval(case, o, "f64", r.xs), ln_eval(case, o, "abs", r.xs), ln_eval(case, o, "f32", r.xs)
+    r.allow = BF16_STORE * r.ref.abs() if case.out_bf16 else None
+    r.yard = parity_err(r.f32, r.ref, r.A)[0]
+    r.bound = ln_bound(r.yard)
+    return r
+
+
+def ln_emulate(case, o, xs=None):
+    """ln_mod_kernel's arithmetic in fp32, in its order: lane l holds the float4s l, l + 64, l + 128, l + 192 of the row."""
+    xs = ln_stream(case, o) if xs is None else xs
+    R, D = xs.shape
+    w, b, one = _ln_wb(case, o)
+    X = torch.zeros(R, 1024)
+    X[:, :D] = xs
+    live = (torch.arange(1024) < D).view(1, 4, 64, 4)
+    X = X.view(R, 4, 64, 4)
+    def lanes(v):                                         # [R][4 groups][64][4] -> per-lane serial sum over the groups, then the butterfly
+        g = (v[..., 0] + v[..., 1]) + (v[..., 2] + v[..., 3])
+        s = torch.zeros(R, 64)
+        for i in range(4):
+            s = s + g[:, i]
+        return _butterfly64(s)
+    mean = (lanes(X) / torch.tensor(float(D))).view(R, 1, 1, 1)
+    a = torch.where(live, X - mean, torch.zeros(()))
+    rstd = torch.rsqrt(lanes(a * a) / torch.tensor(float(D)) + torch.tensor(case.eps, dtype=torch.float32)).view(R, 1, 1, 1)
+    y = ((X - mean) * rstd).reshape(R, 1024)[:, :D] * (w + one) + b
+    return y.to(case.out_dtype)
+
+
+def ln_launch(eng, case, o, *, padded, expect_error=False, mutate=None):
+    """One launch -> (y [R][D] on the CPU in the output dtype, the stream x after the launch [R][D]).  Padded: ldx = D + 4, ldy = D + 8,
+    ld_delta = D + 12, NaN in every padding column.  Always: two NaN rows behind x, the deltas and each tail part block, NaN behind w and
+    b, NaN in the delta's own tail rows, guard rows around y; all of it checked after the launch."""
+    R, D = case.R, case.D
+    ldx, ldy, ldd = (D + 4, D + 8, D + 12) if padded else (D, D, D)
+    keep = []
+    dx = _nan_rows(o.x, ldx, 2)
+    ybuf, y = _rows_out(R, D, ldy, case.out_dtype)
+    a = rt.vv_ln_args()
+    a.out_dtype = rt.VV_BF16 if case.out_bf16 else rt.VV_F32
+    a.x, a.ldx, a.y, a.ldy, a.R, a.D, a.add_one, a.eps, a.keep_x = dx.data_ptr(), ldx, y.data_ptr(), ldy, R, D, case.add_one, case.eps, case.keep_x
+    if case.has_w:
+        kw, a.w = _nan_tail(o.w)
+        keep.append(kw)
+    if case.has_b:
+        kb, a.b = _nan_tail(o.b)
+        keep.append(kb)
+    a.delta_dtype = rt.VV_BF16 if case.delta_bf16 else rt.VV_F32
+    for i in range(case.n_delta):
+        d = o.d[i].clone()
+        if case.tail_parts[i]:
+            d[case.tail_row0:] = NAN                       # the GEMM leaves these rows unwritten: the kernel must not read them
+        dd = _nan_rows(d, ldd, 2)
+        keep.append(dd)
+        if i == 0:
+            a.delta, a.ld_delta = dd.data_ptr(), ldd
+        else:
+            a.delta2 = dd.data_ptr()
+        p = case.tail_parts[i]
+        if p:
+            tr = R - case.tail_row0
+            tb = _nan_rows(o.t[i][:p].reshape(p * tr, D), ldd, 2)
+            keep.append(tb)
+            if i == 0:
+                a.delta_tail, a.delta_tail_parts = tb.data_ptr(), p
+            else:
+                a.delta2_tail, a.delta2_tail_parts = tb.data_ptr(), p
+    if any(case.tail_parts):
+        a.tail_row0 = case.tail_row0
+    if mutate is not None:
+        mutate(a)
+    rc = eng.lib.vv_layernorm(eng.ctx, C.byref(a), stream())
+    torch.cuda.synchronize()
+    what = f"{case.name} ({'padded' if padded else 'contiguous'})"
+    if expect_error:
+        assert rc == -22, (what, rc)
+        assert bool((ybuf == CONV_FILL).all()), f"{what}: a refused launch wrote y"
+        assert torch.equal(dx[:R, :min(D, ldx)].cpu(), o.x[:, :min(D, ldx)]), f"{what}: a refused launch wrote x"
+        return None, None
+    check(eng, rc)
+    _rows_out_intact(ybuf, R, D, what)
+    _pad_intact(dx, R, D, what + " x")
+    return y[:, :D].cpu(), dx[:R, :D].cpu()
+
+
+def ln_cases():
+    """One base shape (D = 260: a partly filled second register group; R = 5: a second workgroup with one live wave), one axis at a time."""
+    cs = []
+    for ob in (False, True):
+        for db in (False, True):
+            tag = ("bf16" if ob else "f32") + "_" + ("bf16" if db else "f32")
+            for D in (4, 60, 252, 256, 260, 512, 1020, 1024):
+                cs.append(LnCase(f"ln/{tag}/D{D}", D=D, out_bf16=ob, delta_bf16=db, n_delta=1, seed=D))
+    for tag, ob, db in (("f32_f32", False, False), ("bf16_bf16", True, True)):
+        k = dict(out_bf16=ob, delta_bf16=db)
+        for R in (1, 3, 4, 5, 37):
+            cs.append(LnCase(f"ln/{tag}/R{R}", R=R, n_delta=2, seed=100 + R, **k))
+        for add_one in (0, 1):
+            for hw, hb in ((True, True), (False, True), (True, False), (False, False)):
+                cs.append(LnCase(f"ln/{tag}/one{add_one}_w{int(hw)}_b{int(hb)}", add_one=add_one, has_w=hw, has_b=hb, seed=120, **k))
+        for nd, keep in ((0, 0), (1, 0), (1, 1), (2, 0), (2, 1)):
+            cs.append(LnCase(f"ln/{tag}/delta{nd}_keep{keep}", n_delta=nd, keep_x=keep, seed=130 + nd, **k))
+        for parts in (2, 3, 8):
+            for r0 in (0, 1, 4):
+                for which, tp in (("d1", (parts, 0)), ("d2", (0, parts)), ("both", (parts, parts))):
+                    cs.append(LnCase(f"ln/{tag}/tail{parts}_row{r0}_{which}", n_delta=2, tail_row0=r0, tail_parts=tp, seed=140 + parts, **k))
+        for data in LN_DATA:
+            cs.append(LnCase(f"ln/{tag}/{data}", data=data, seed=150, **k))
+    cs.append(LnCase("ln/bf16_bf16/D1020_tail3_keep", D=1020, out_bf16=True, delta_bf16=True, n_delta=2, keep_x=1, tail_row0=4, tail_parts=(3, 3), seed=160))
+    cs.append(LnCase("ln/f32_bf16/D4_R1_delta2", D=4, R=1, delta_bf16=True, n_delta=2, seed=161))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+# ---- GroupNorm (groupnorm_kernel)
+ACT_MISH = 4
+
+
+@dataclasses.dataclass(frozen=True)
+class GnCase:
+    name: str
+    B: int = 2
+    C: int = 8
+    T: int = 300
+    G: int = 2
+    has_gamma: bool = True
+    has_beta: bool = True
+    act: int = 0
+    data: str = "normal"                # normal | mean300 | first<k> | last<k>: that element of every slab set to k x the slab's spread
+    offset: int = 0                     # floats between a 16-byte boundary and x / y: 1 takes the scalar path at T % 4 == 0
+    seed: int = 0
+    eps: float = 1e-5
+    kernel = "groupnorm_kernel"
+
+    @property
+    def n(self):
+        return self.C // self.G * self.T
+
+    @property
+    def vec(self):
+        return self.T % 4 == 0 and self.offset % 4 == 0 and self.n % 4 == 0
+
+    def ops(self):
+        g = torch.Generator().manual_seed(8000 + self.seed)
+        o = _Ops()
+        z = torch.randn(self.B, self.C, self.T, generator=g)
+        o.x = 300.0 + 0.03 * z if self.data == "mean300" else z
+        if self.data.startswith(("first", "last")):
+            k = float(self.data.lstrip("firstla"))
+            slab = o.x.view(self.B, self.G, self.n)
+            slab[:, :, 0 if self.data.startswith("first") else -1] = k
+        o.gamma, o.beta = torch.randn(self.C, generator=g), torch.randn(self.C, generator=g)
+        return o
+
+    def refs(self, o=None):
+        return gn_ref(self, o)
+
+
+def gn_eval(case, o, mode):
+    """-> (output, pre-activation z)."""
+    ga = o.gamma if case.has_gamma else torch.ones(case.C)
+    be = o.beta if case.has_beta else torch.zeros(case.C)
+    if mode == "f32":
+        z = F.group_norm(o.x, case.G, ga, be, eps=case.eps)
+        return (F.mish(z) if case.act == ACT_MISH else z), z
+    X = o.x.double().view(case.B, case.G, case.n)
+    mean = X.mean(2, keepdim=True)
+    rstd = (((X - mean) ** 2).mean(2, keepdim=True) + float(torch.tensor(case.eps, dtype=torch.float32))).rsqrt()
+    ga, be = ga.double()[None, :, None], be.double()[None, :, None]
+    if mode == "abs":
+        z = ((X.abs() + X.abs().mean(2, keepdim=True)) * rstd).view(o.x.shape) * ga.abs() + be.abs()
+        return (MISH_SLOPE * z if case.act == ACT_MISH else z), z
+    z = ((X - mean) * rstd).view(o.x.shape) * ga + be
+    return (F.mish(z) if case.act == ACT_MISH else z), z
+
+
+def gn_c(case):
+    """The roundings of groupnorm_kernel for a slab of n elements, depth = the serial adds of one thread (ceil(n / 4 / 256) + 2 on the
+    vector path: the float4's two levels and the accumulate; ceil(n / 256) on the scalar one), + 6 shuffle levels + 2 LDS levels + the
+    division = depth + 9 for a sum.  The mean is m0 + d, d = the mean of fl(x - m0): whatever m0's own error, the mean's error is d's:
+    the subtraction, the sum (depth + 9) of terms of up to |x| + |m0| <= 2 mean-scale, the last add: 2 (depth + 10) + 1.  The variance:
+    3 on each square, depth + 9, - d^2 and + eps: depth + 14, halved, + 2 for v_rsq_f32.  The affine: x - mean, gamma x rstd, the
+    product, + beta: 4."""
+    depth = (-(-(case.n // 4) // 256) + 2) if case.vec else -(-case.n // 256)
+    return 2.0 * (depth + 10) + 1 + (depth + 14) / 2.0 + 2 + 4
+
+
+def gn_bound(case, yardstick):
+    return max(gn_c(case) * EPS24, 4.0 * yardstick)
+
+
+def gn_ref(case, o=None):
+    o = case.ops() if o is None else o
+    r = _Ops()
+    (r.ref, r.z), (r.A, _), (r.f32, _) = gn_eval(case, o, "f64"), gn_eval(case, o, "abs"), gn_eval(case, o, "f32")
+    r.allow = MISH_ALLOW * r.z.abs() if case.act == ACT_MISH else None
+    r.yard = parity_err(r.f32, r.ref, r.A)[0]
+    r.bound = gn_bound(case, r.yard)
+    return r
+
+
+def _gn_sum(case, v):
+    """One workgroup's sum over a slab, [B][G][n] fp32 -> [B][G][1]: thread t takes the float4s (or floats) t, t + 256, ...; wave
+    butterflies; (r0 + r1) + (r2 + r3)."""
+    B, G, n = v.shape
+    if case.vec:
+        per = -(-(n // 4) // 256)
+        p = torch.zeros(B, G, per * 1024)
+        p[..., :n] = v
+        p = p.view(B, G, per, 256, 4)
+        p = (p[..., 0] + p[..., 1]) + (p[..., 2] + p[..., 3])
+    else:
+        per = -(-n // 256)
+        p = torch.zeros(B, G, per * 256)
+        p[..., :n] = v
+        p = p.view(B, G, per, 256)
+    s = torch.zeros(B, G, 256)
+    for i in range(per):
+        s = s + p[:, :, i]
+    w = _butterfly64(s.view(B, G, 4, 64))
+    return ((w[..., 0] + w[..., 1]) + (w[..., 2] + w[..., 3])).unsqueeze(-1)
+
+
+def gn_emulate(case, o, form="two_pass"):
+    """groupnorm_kernel's arithmetic in fp32.  form: two_pass (the kernel), first_shift (the one-pass variance shifted by the slab's
+    first element: the kernel before profiles/norm_parity), unshifted (sum and sum of squares of x itself)."""
+    X = o.x.view(case.B, case.G, case.n)
+    n = torch.tensor(float(case.n))
+    if form == "two_pass":
+        m0 = _gn_sum(case, X) / n
+        a = X - m0
+        sd = _gn_sum(case, a) / n
+        var = (_gn_sum(case, a * a) / n - sd * sd).clamp_min(0.0)
+        mean = m0 + sd
+    else:
+        p = X[..., :1] if form == "first_shift" else torch.zeros(case.B, case.G, 1)
+        a = X - p
+        sd = _gn_sum(case, a) / n
+        var = (_gn_sum(case, a * a) / n - sd * sd).clamp_min(0.0)
+        mean = p + sd
+    rstd = torch.rsqrt(var + torch.tensor(case.eps, dtype=torch.float32))
+    ga = (o.gamma if case.has_gamma else torch.ones(case.C)).view(1, case.G, -1, 1)
+    be = (o.beta if case.has_beta else torch.zeros(case.C)).view(1, case.G, -1, 1)
+    z = (X - mean).view(case.B, case.G, case.C // case.G, case.T) * (ga * rstd.unsqueeze(-1)) + be
+    z = z.view(o.x.shape)
+    return mish_f32_emulation(z) if case.act == ACT_MISH else z
+
+
+def gn_launch(eng, case, o, *, padded):
+    """One launch -> y [B][C][T] on the CPU.  y sits between guard bands of CONV_FILL; gamma and beta are followed by NaN; padded: x has
+    NaN in front of and behind it.  `offset` floats shift both x and y off the 16-byte grid."""
+    off = case.offset
+    head = 4 + off if padded or off else 0
+    kx, px = _nan_tail(o.x, tail=8 if padded else 0, head=head)
+    ybuf, y = _guarded(o.x.shape, CONV_GUARD + off, CONV_FILL)
+    keep, pg, pb = [], None, None
+    if case.has_gamma:
+        k1, pg = _nan_tail(o.gamma)
+        keep.append(k1)
+    if case.has_beta:
+        k2, pb = _nan_tail(o.beta)
+        keep.append(k2)
+    check(eng, eng.lib.vv_groupnorm(eng.ctx, px, y.data_ptr(), pg, pb, case.B, case.C, case.T, case.G, case.eps, case.act, stream()))
+    torch.cuda.synchronize()
+    _bands_intact(ybuf, CONV_GUARD + off, CONV_FILL, case.name)
+    return y.cpu()
+
+
+def gn_cases():
+    cs = [GnCase("gn/base")]
+    for name, (B, C, T, G) in (("n40", (1, 4, 20, 2)), ("n2400", (1, 8, 600, 2)), ("cpg1", (2, 4, 64, 4)), ("G1", (1, 6, 100, 1)),
+                               ("G_eq_C", (1, 8, 36, 8)), ("T301", (2, 8, 301, 2)), ("T303", (2, 8, 303, 2)), ("T1", (1, 8, 1, 2))):
+        cs.append(GnCase(f"gn/{name}", B=B, C=C, T=T, G=G, seed=len(cs)))
+    cs.append(GnCase("gn/offset1", offset=1, seed=20))
+    cs.append(GnCase("gn/offset1_n40", B=1, C=4, T=20, G=2, offset=1, seed=21))
+    for hg, hb in ((False, True), (True, False), (False, False)):
+        cs.append(GnCase(f"gn/gamma{int(hg)}_beta{int(hb)}", has_gamma=hg, has_beta=hb, seed=22))
+    cs.append(GnCase("gn/mish", act=ACT_MISH, seed=23))
+    cs.append(GnCase("gn/mish_T301", T=301, act=ACT_MISH, seed=24))
+    cs.append(GnCase("gn/mean300", data="mean300", seed=25))
+    cs.append(GnCase("gn/mean300_T301", T=301, data="mean300", seed=26))
+    for k in (10, 100, 1000):
+        for where in ("first", "last"):
+            cs.append(GnCase(f"gn/{where}{k}", data=f"{where}{k}", seed=30 + k))
+            cs.append(GnCase(f"gn/{where}{k}_n2400", B=1, C=8, T=600, G=2, data=f"{where}{k}", seed=31 + k))
+            cs.append(GnCase(f"gn/{where}{k}_T301", T=301, data=f"{where}{k}", seed=32 + k))
+    assert len({c.name for c in cs}) == len(cs)
+    return cs
+
+
+# ---- the text stack: text_embed_kernel, dwconv_kernel, grn_stats_kernel + grn_apply_kernel
+def _lens(lens, n_seq, N):
+    """Per-sequence valid length as the kernels take it: seq_len[s % B] clamped to [0, N]; None = N."""
+    return [N if lens is None else max(min(lens[s % len(lens)], N), 0) for s in range(n_seq)]
+
+
+@dataclasses.dataclass(frozen=True)
+class TeCase:
+    name: str
+    B: int = 2
+    N: int = 9
+    Dt: int = 8
+    ld_ids: int = 6
+    vocab_rows: int = 5
+    text_len: tuple = (4, 6)
+    seed: int = 0
+    kernel = "text_embed_kernel"
+
+    def ops(self):
+        g = torch.Generator().manual_seed(9000 + self.seed)
+        o = _Ops()
+        # ids walk through vocab_rows - 3 .. vocab_rows + 1 and -2: id + 1 reaches the last row and is clamped beyond it on both sides
+        o.ids = (torch.arange(self.B * self.ld_ids).view(self.B, self.ld_ids) % 6 + self.vocab_rows - 4).to(torch.int32)
+        o.ids[:, 0] = -2
+        o.emb, o.pos = torch.randn(self.vocab_rows, self.Dt, generator=g), torch.randn(self.N, self.Dt, generator=g)
+        o.text_len = torch.tensor(self.text_len, dtype=torch.int32)
+        return o
+
+
+def te_ref(case, o):
+    """fp32, bit for bit: emb[clamp(id)] + pos[t]; the drop half [B, 2 B) and everything behind the text take the filler id 0."""
+    out = torch.empty(2 * case.B, case.N, case.Dt)
+    for s in range(2 * case.B):
+        b = s % case.B
+        for t in range(case.N):
+            i = int(o.ids[b, t]) + 1 if (s < case.B and t < int(o.text_len[b]) and t < case.ld_ids) else 0
+            out[s, t] = o.emb[min(max(i, 0), case.vocab_rows - 1)] + o.pos[t]
+    return out
+
+
+def te_launch(eng, case, o, *, padded):
+    """ids carry one row of 2^30 behind them, text_len, emb and pos are followed by NaN / 2^30; padded: emb and pos start 4 floats into
+    their allocations behind NaN.  (ld_ids is the kernel's bound on t, not only a stride: it stays the case's.)"""
+    ids = _nan_rows(o.ids, case.ld_ids, 1)
+    h = 4 if padded else 0
+    (k1, pe), (k2, pp), (k3, pl) = _nan_tail(o.emb, head=h), _nan_tail(o.pos, head=h), _nan_tail(o.text_len)
+    obuf, out = _guarded((2 * case.B, case.N, case.Dt), CONV_GUARD, CONV_FILL)
+    rc = eng.lib.vv_text_embed(eng.ctx, ids.data_ptr(), case.ld_ids, pl, pe, pp, case.vocab_rows, out.data_ptr(), case.B, case.N, case.Dt, stream())
+    check(eng, rc)
+    torch.cuda.synchronize()
+    _bands_intact(obuf, CONV_GUARD, CONV_FILL, case.name)
+    return out.cpu()
+
+
+def te_cases():
+    cs = [TeCase("te/base")]
+    for name, tl in (("len0", (0, 0)), ("len1", (1, 1)), ("len_ld", (6, 6)), ("len_gt_ld", (8, 50)), ("len_gt_N", (30, 9))):
+        cs.append(TeCase(f"te/{name}", text_len=tl, seed=len(cs)))
+    cs.append(TeCase("te/N_gt_all", N=20, text_len=(3, 5), seed=10))
+    cs.append(TeCase("te/N_lt_ld", N=4, text_len=(6, 2), seed=11))
+    cs.append(TeCase("te/B1_Dt4", B=1, Dt=4, text_len=(5,), seed=12))
+    cs.append(TeCase("te/Dt100_blocks", B=3, N=40, Dt=100, ld_ids=33, text_len=(33, 1, 17), seed=13))      # more than one workgroup
+    return cs
+
+
+@dataclasses.dataclass(frozen=True)
+class DwCase:
+    name: str
+    KW: int = 7
+    C: int = 64
+    N: int = 40
+    B: int = 2
+    lens: tuple = (40, 17)              # None: seq_len NULL
+    seed: int = 0
+    kernel = "dwconv_kernel"
+
+    @property
+    def n_seq(self):
+        return 2 * self.B
+
+    def ops(self):
+        g = torch.Generator().manual_seed(9500 + self.seed)
+        o = _Ops()
+        o.x = torch.randn(self.n_seq, self.N, self.C, generator=g)
+        o.w = torch.randn(self.C, self.KW, generator=g) / math.sqrt(self.KW)
+        o.bias = torch.randn(self.C, generator=g) * 0.3
+        o.lens = _lens(self.lens, self.n_seq, self.N)
+        return o
+
+    def refs(self, o=None):
+        return dw_ref(self, o)
+
+
+def dw_eval(case, o, mode):
+    dt = torch.float32 if mode == "f32" else torch.float64
+    x, w, b = o.x.to(dt).clone(), o.w.to(dt), o.bias.to(dt)
+    for s, L in enumerate(o.lens):
+        x[s, L:] = 0.0                                    # input beyond len is zero, exactly as the kernel skips it
+    if mode == "abs":
+        x, w, b = x.abs(), w.abs(), b.abs()
+    return F.conv1d(x.transpose(1, 2), w[:, None, :], b, padding=case.KW // 2, groups=case.C).transpose(1, 2).contiguous()
+
+
+def dw_bound(case, yardstick):
+    """max((KW + 2) x 2^-24, 4 x yardstick): one chain per element, bias first: KW products (one rounding each, together <= 2^-24 A_e)
+    and KW adds whose partial sums never exceed A_e; + 1 of room for a compiler that does not contract to FMA."""
+    return max((case.KW + 2) * EPS24, 4.0 * yardstick)
+
+
+def dw_ref(case, o=None):
+    o = case.ops() if o is None else o
+    r = _Ops()
+    r.ref, r.A, r.f32 = dw_eval(case, o, "f64"), dw_eval(case, o, "abs"), dw_eval(case, o, "f32")
+    r.allow = None
+    r.yard = parity_err(r.f32, r.ref, r.A)[0]
+    r.bound = dw_bound(case, r.yard)
+    return r
+
+
+def dw_emulate(case, o):
+    """dwconv_kernel in fp32: acc = bias, then += w[c][k] x in tap order, taps outside [0, len) skipped."""
+    out = o.bias.expand(case.n_seq, case.N, case.C).clone()
+    pad = case.KW // 2
+    for k in range(case.KW):
+        for s, L in enumerate(o.lens):
+            lo, hi = max(0, pad - k), min(case.N, L + pad - k)          # t with 0 <= t + k - pad < L
+            if hi > lo:
+                out[s, lo:hi] = out[s, lo:hi] + o.w[:, k] * o.x[s, lo + k - pad:hi + k - pad]
+    return out
+
+
+def dw_launch(eng, case, o, *, padded):
+    """Input rows at and beyond a sequence's len hold NaN (the kernel must not read them); NaN behind in, w, bias and seq_len; padded:
+    in starts 4 floats into its allocation, behind NaN."""
+    x = o.x.clone()
+    for s, L in enumerate(o.lens):
+        x[s, L:] = NAN
+    kx, px = _nan_tail(x, head=4 if padded else 0)
+    (k1, pw), (k2, pb) = _nan_tail(o.w), _nan_tail(o.bias)
+    k3, pl = (None, None) if case.lens is None else _nan_tail(torch.tensor(case.lens, dtype=torch.int32))
+    obuf, out = _guarded(o.x.shape, CONV_GUARD, CONV_FILL)
+    check(eng, eng.lib.vv_dwconv(eng.ctx, px, out.data_ptr(), pw, pb, pl, case.B, case.n_seq, case.N, case.C, case.KW, stream()))
+    torch.cuda.synchronize()
+    _bands_intact(obuf, CONV_GUARD, CONV_FILL, case.name)
+    return out.cpu()
+
+
+def dw_cases():
+    cs = [DwCase("dw/base")]
+    for KW in (3, 7, 31):
+        for N in sorted({1, 2, KW // 2, 40}):
+            cs.append(DwCase(f"dw/K{KW}_N{N}", KW=KW, N=N, lens=(N, max(N // 2, 1)), seed=len(cs)))
+    for C in (4, 100):
+        cs.append(DwCase(f"dw/C{C}", C=C, seed=len(cs)))
+    for name, lens in (("len0_1", (0, 1)), ("lenN_gtN", (40, 45)), ("len_null", None), ("len_neg", (-3, 39))):
+        cs.append(DwCase(f"dw/{name}", lens=lens, seed=len(cs)))
+    cs.append(DwCase("dw/B3_K31", KW=31, B=3, lens=(40, 15, 16), seed=len(cs)))
+    return cs
+
+
+@dataclasses.dataclass(frozen=True)
+class GrnCase:
+    name: str
+    C: int = 128
+    N: int = 40
+    B: int = 2
+    lens: tuple = (40, 17)
+    bf16: bool = False
+    zero_channel: int = -1
+    seed: int = 0
+    kernel = "grn_stats_kernel+grn_apply_kernel"
+
+    @property
+    def n_seq(self):
+        return 2 * self.B
+
+    @property
+    def dtype(self):
+        return torch.bfloat16 if self.bf16 else torch.float32
+
+    def ops(self):
+        g = torch.Generator().manual_seed(9700 + self.seed)
+        o = _Ops()
+        o.x = torch.randn(self.n_seq, self.N, self.C, generator=g).to(self.dtype)
+        if self.zero_channel >= 0:
+            o.x[:, :, self.zero_channel] = 0.0
+        o.gamma, o.beta = torch.randn(self.C, generator=g), torch.randn(self.C, generator=g) * 0.3
+        o.lens = _lens(self.lens, self.n_seq, self.N)
+        return o
+
+    def refs(self, o=None):
+        return grn_ref(self, o)
+
+
+def grn_eval(case, o, mode):
+    """-> (y [n_seq][N][C], sumsq [n_seq][C]).  The statistics run over the valid tokens, the apply over all N rows."""
+    dt = torch.float32 if mode == "f32" else torch.float64
+    x, ga, be = o.x.to(dt), o.gamma.to(dt), o.beta.to(dt)
+    ss = torch.stack([(x[s, :L] ** 2).sum(0) for s, L in enumerate(o.lens)])
+    g = ss.sqrt()
+    nx = (g / (g.mean(1, keepdim=True) + torch.tensor(1e-6, dtype=torch.float32).to(dt)))[:, None, :]
+    if mode == "abs":
+        return x.abs() * (ga.abs() * nx + 1.0) + be.abs(), ss
+    return x * (ga * nx + 1.0) + be, ss
+
+
+def grn_counts(case, o):
+    """(c of the output, c of sumsq).  sumsq: the square, ceil(len / 4) serial adds of a token phase, two LDS levels: S = ceil(len / 4) + 3.
+    The output: g = sqrt(sumsq) carries S / 2 + 1; the channel mean another ceil(C / 256) serial adds, 6 shuffle levels, 2 LDS levels and
+    the division on top of that; + 1e-6, g / mean, gamma x, + 1, x scale, + beta: 6.  Together S + ceil(C / 256) + 17."""
+    S = -(-max(o.lens) // 4) + 3
+    return S + -(-case.C // 256) + 17.0, float(S)
+
+
+def grn_ref(case, o=None):
+    o = case.ops() if o is None else o
+    r = _Ops()
+    (r.ref, r.ss), (r.A, _), (r.f32, r.ss32) = grn_eval(case, o, "f64"), grn_eval(case, o, "abs"), grn_eval(case, o, "f32")
+    r.allow = BF16_STORE * r.ref.abs() if case.bf16 else None
+    r.yard = parity_err(r.f32, r.ref, r.A)[0]
+    c, cs = grn_counts(case, o)
+    r.bound = max(c * EPS24, 4.0 * r.yard)
+    r.ss_A = r.ss.clamp_min(1e-300)                       # a channel without energy must give an exact zero
+    r.ss_yard = parity_err(r.ss32, r.ss, r.ss_A)[0]
+    r.ss_bound = max(cs * EPS24, 4.0 * r.ss_yard)
+    return r
+
+
+def grn_emulate(case, o):
+    """The two kernels in fp32: phase p sums tokens p, p + 4, ...; (r0 + r1) + (r2 + r3); then the mean over channels by 256 threads."""
+    x = o.x.float()
+    ss = torch.zeros(case.n_seq, case.C)
+    for s, L in enumerate(o.lens):
+        ph = []
+        for p in range(4):
+            acc = torch.zeros(case.C)
+            for t in range(p, L, 4):
+                acc = acc + x[s, t] * x[s, t]
+            ph.append(acc)
+        ss[s] = (ph[0] + ph[1]) + (ph[2] + ph[3])
+    g = ss.sqrt()
+    per = -(-case.C // 256)
+    gp = torch.zeros(case.n_seq, per * 256)
+    gp[:, :case.C] = g
+    part = torch.zeros(case.n_seq, 256)
+    for i in range(per):
+        part = part + gp[:, i * 256:(i + 1) * 256]
+    w = _butterfly64(part.view(case.n_seq, 4, 64))
+    mean = (((w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])) / torch.tensor(float(case.C)))[:, None]
+    sc = o.gamma * (g / (mean + torch.tensor(1e-6, dtype=torch.float32))) + 1.0
+    return (x * sc[:, None, :] + o.beta).to(case.dtype), ss
+
+
+def grn_launch(eng, case, o, *, padded):
+    """In place.  x sits between guard bands (CONV_FILL, finite: the apply pass reads only its own rows); sumsq likewise; NaN behind
+    gamma, beta and seq_len.  padded: a wider guard, so that x lands elsewhere on the 16-byte grid."""
+    guard = CONV_GUARD + (8 if padded else 0)
+    xbuf, x = _guarded(o.x.shape, guard, CONV_FILL, init=o.x, dtype=case.dtype)
+    sbuf, ss = _guarded((case.n_seq, case.C), CONV_GUARD, CONV_FILL)
+    (k1, pg), (k2, pb) = _nan_tail(o.gamma), _nan_tail(o.beta)
+    k3, pl = (None, None) if case.lens is None else _nan_tail(torch.tensor(case.lens, dtype=torch.int32))
+    check(eng, eng.lib.vv_grn(eng.ctx, rt.VV_BF16 if case.bf16 else rt.VV_F32, x.data_ptr(), ss.data_ptr(), pg, pb, pl, case.B, case.n_seq,
+                              case.N, case.C, stream()))
+    torch.cuda.synchronize()
+    _bands_intact(xbuf, guard, CONV_FILL, case.name + " x")
+    _bands_intact(sbuf, CONV_GUARD, CONV_FILL, case.name + " sumsq")
+    return x.cpu(), ss.cpu()
+
+
+def grn_cases():
+    cs = []
+    for bf in (False, True):
+        tag = "bf16" if bf else "f32"
+        cs.append(GrnCase(f"grn/{tag}/base", bf16=bf))
+        for C in (64, 192):
+            cs.append(GrnCase(f"grn/{tag}/C{C}", C=C, bf16=bf, seed=C))
+        for N in (1, 15, 16, 17):
+            cs.append(GrnCase(f"grn/{tag}/N{N}", N=N, lens=(N, max(N - 2, 1)), bf16=bf, seed=N))
+        for name, lens in (("len0_1", (0, 1)), ("lenN", (40, 40)), ("len_null", None)):
+            cs.append(GrnCase(f"grn/{tag}/{name}", lens=lens, bf16=bf, seed=50))
+        cs.append(GrnCase(f"grn/{tag}/zero_channel", zero_channel=65, bf16=bf, seed=51))
+        cs.append(GrnCase(f"grn/{tag}/C512_B1", C=512, B=1, lens=(33,), bf16=bf, seed=52))       # two channels per thread in the mean
+    return cs
+
+
+# ---- mel front end (mel_kernel)
+# x |log|.  The build lowers logf(x) in mel_kernel to y = v_log_f32(x), then r = y ln2_hi, r += fma(y, ln2_hi, -r) + y ln2_lo (the kernel's
+# assembly: v_log_f32, v_mul 0x3f317217, v_fma, v_fmac 0x3377d1cf, v_fmac 0x3f317217): v_log_f32 is specified to 1 ulp of the base-2
+# logarithm, 2 x 2^-24 of it and so of the result; the product by ln 2 is carried in two floats; one rounding of the result (2^-24).
+# Together 3 x 2^-24, i.e. up to 1.5 ulp off the correctly rounded float.
+MEL_LOG_ALLOW = 3.0 * EPS24
+
+
+def mel_tables(spec):
+    """The fp32 tables the kernel is bound to (pack.py): the periodic Hann window and the filterbank [n_fft / 2 + 1][n_mel]."""
+    from vietvoice_tts_amd.model_spec import mel_filterbank
+    return torch.hann_window(spec.win_length, periodic=True, dtype=torch.float32), mel_filterbank(spec).float()
+
+
+@dataclasses.dataclass(frozen=True)
+class MelCase:
+    name: str
+    lens: tuple
+    signal: str = "noise"               # noise | zero (item 0 silent) | square (+-full scale, -32768 included) | impulse (sample 0 / the last sample)
+    seed: int = 0
+    kernel = "mel_kernel"
+
+    def ops(self):
+        g = torch.Generator().manual_seed(9900 + self.seed)
+        o = _Ops()
+        S = max(self.lens)
+        a = (torch.randn(2, S, generator=g) * 4000).clamp(-30000, 30000).to(torch.int16)
+        if self.signal == "zero":
+            a[0] = 0
+        elif self.signal == "square":
+            hi = (torch.arange(S) // 25) % 2 == 0
+            a[:] = torch.where(hi, torch.tensor(32767, dtype=torch.int16), torch.tensor(-32768, dtype=torch.int16))
+        elif self.signal == "impulse":
+            a[:] = 0
+            a[0, 0] = 20000
+            a[1, self.lens[1] - 1] = -20000
+        for b, L in enumerate(self.lens):
+            a[b, L:] = 32767                              # what lies behind audio_len inside ld_audio is never read
+        o.audio = a
+        return o
+
+
+def _mel_frames(a, L, spec, window, edge_repeat=False):
+    """int16 clip a[:L] -> float64 frames [L // hop + 1][n_fft], centred, reflected without repeating the edge sample, windowed."""
+    n_fft, hop = spec.n_fft, spec.hop_length
+    pos = torch.arange(L // hop + 1)[:, None] * hop + torch.arange(n_fft)[None, :] - n_fft // 2
+    if edge_repeat:
+        pos = torch.where(pos < 0, -pos - 1, pos)
+        pos = torch.where(pos >= L, 2 * L - 1 - pos, pos)
+    else:
+        pos = torch.where(pos < 0, -pos, pos)
+        pos = torch.where(pos >= L, 2 * (L - 1) - pos, pos)
+    pos = pos.clamp(0, L - 1)
+    return a[:L].double()[pos] / 32768.0 * window.double()[None, :]
+
+
+def mel_eval(case, o, spec, mode, variant=None):
+    """-> (log-mel [2][F_max][n_mel], linear mel): float64 from the fp32 tables (mode f64), or A_e in the linear domain (mode abs).  Frames
+    behind an item's own are zeros.  variant: a deliberately wrong front end (the mutation table of tests/test_norm_ref_cpu.py)."""
+    window, fb = mel_tables(spec)
+    if variant == "sym_hann":
+        window = torch.hann_window(spec.win_length, periodic=False, dtype=torch.float32)
+    if variant == "fb_shift":
+        fb = torch.roll(fb, 1, dims=1)
+    floor = float(torch.tensor(1e-6 if variant == "floor1e-6" else 1e-5, dtype=torch.float32))
+    F_max = max(case.lens) // spec.hop_length + 1
+    out = torch.zeros(2, F_max, spec.n_mel, dtype=torch.float64)
+    lin = torch.zeros_like(out)
+    for b, L in enumerate(case.lens):
+        fr = _mel_frames(o.audio[b], L, spec, window, edge_repeat=variant == "edge_repeat")
+        if mode == "abs":
+            l = (math.sqrt(2.0) * fr.abs().sum(1))[:, None] * fb.double().sum(0)[None, :]
+        else:
+            mag = torch.fft.rfft(fr, dim=1).abs()
+            l = (mag ** 2 if variant == "power" else mag) @ fb.double()
+        n = fr.shape[0] - (1 if variant == "last_frame_missing" else 0)
+        lin[b, :n] = l[:n]
+        out[b, :n] = l[:n].clamp_min(floor).log()
+    return out, lin
+
+
+def mel_c(spec):
+    """The roundings of mel_kernel against sum |fr|: the window product, the rounded twiddle, the n_fft FMAs of one bin's chain: n_fft + 2
+    on re and on im, which is what sqrt(2) sum |fr| bounds for the magnitude; re^2, im^2, their sum and the root: 3; the filterbank's FMAs
+    that add something (the most non-zero entries of a column) and the final rounding: K + 1."""
+    _, fb = mel_tables(spec)
+    return float(spec.n_fft + 2 + 3 + int((fb != 0).sum(0).max()) + 1)
+
+
+def mel_ref(case, spec, orc, o=None):
+    """ref / A / allow in the log domain: A = A_lin / max(lin_ref, 1e-5) (the slope of the log at the clamped reference: a near-silent bin
+    is covered by that denominator, not skipped), allow = logf's own ulp.  Frames behind a clip: ref 0, nothing allowed."""
+    o = case.ops() if o is None else o
+    r = _Ops()
+    r.ref, r.lin = mel_eval(case, o, spec, "f64")
+    _, A_lin = mel_eval(case, o, spec, "abs")
+    floor = float(torch.tensor(1e-5, dtype=torch.float32))
+    r.A = (A_lin / r.lin.clamp_min(floor)).clamp_min(1e-300)
+    r.allow = MEL_LOG_ALLOW * r.ref.abs()
+    r.f32 = torch.zeros(r.ref.shape)
+    orc = copy.copy(orc)                                  # the fp32 oracle on the SAME operands: the window and filterbank the kernel is bound to
+    orc.window, orc.fb = mel_tables(spec)
+    for b, L in enumerate(case.lens):
+        m = orc.mel(o.audio[b, :L])
+        r.f32[b, :m.shape[0]] = m
+    r.yard = parity_err(r.f32, r.ref, r.A, r.allow)[0]
+    r.bound = max(mel_c(spec) * EPS24, 4.0 * r.yard)
+    return r
+
+
+def _fma32(a, b, c):
+    """fp32 fma through float64: the product of two floats is exact there."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def mel_emulate(case, o, spec):
+    """mel_kernel in fp32: one FMA chain over n per bin with the rounded twiddle table, the magnitude, one FMA chain over the bins."""
+    window, fb = mel_tables(spec)
+    n_fft, nb = spec.n_fft, spec.n_fft // 2 + 1
+    ang = 2.0 * math.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft
+    tc, ts = ang.cos().float(), ang.sin().float()
+    F_max = max(case.lens) // spec.hop_length + 1
+    out = torch.zeros(2, F_max, spec.n_mel)
+    k = torch.arange(nb)
+    for b, L in enumerate(case.lens):
+        fr = ((o.audio[b].float()[:L])[_mel_pos(L, spec)] * torch.tensor(1.0 / 32768.0)) * window[None, :]
+        re, im = torch.zeros(fr.shape[0], nb), torch.zeros(fr.shape[0], nb)
+        for n in range(n_fft):
+            idx = (n * k) & (n_fft - 1)
+            re, im = _fma32(fr[:, n, None], tc[idx][None, :], re), _fma32(fr[:, n, None], ts[idx][None, :], im)
+        mag = torch.sqrt(re * re + im * im)
+        acc = torch.zeros(fr.shape[0], spec.n_mel)
+        for j in range(nb):
+            acc = _fma32(fb[j][None, :], mag[:, j, None], acc)
+        out[b, :fr.shape[0]] = torch.log(acc.clamp_min(1e-5))
+    return out
+
+
+def _mel_pos(L, spec):
+    pos = torch.arange(L // spec.hop_length + 1)[:, None] * spec.hop_length + torch.arange(spec.n_fft)[None, :] - spec.n_fft // 2
+    pos = torch.where(pos < 0, -pos, pos)
+    pos = torch.where(pos >= L, 2 * (L - 1) - pos, pos)
+    return pos.clamp(0, L - 1)
+
+
+def mel_launch(eng, case, o, spec, *, padded):
+    """-> mel [2][F_max][n_mel] on the CPU.  padded: ld_audio = the longest clip + 37, 32767 in every sample behind an audio_len and in
+    a row behind the last; the output sits between guard bands."""
+    S = max(case.lens)
+    ld = S + (37 if padded else 0)
+    a = torch.full((3, ld), 32767, dtype=torch.int16)
+    a[:2, :S] = o.audio
+    da = a.to(DEV)
+    kl, pl = _nan_tail(torch.tensor(case.lens, dtype=torch.int32))
+    F_max = S // spec.hop_length + 1
+    mbuf, mel = _guarded((2, F_max, spec.n_mel), CONV_GUARD, CONV_FILL)
+    mel.fill_(CONV_FILL)
+    check(eng, eng.lib.vv_mel(eng.ctx, da.data_ptr(), ld, pl, mel.data_ptr(), 2, F_max, stream()))
+    torch.cuda.synchronize()
+    _bands_intact(mbuf, CONV_GUARD, CONV_FILL, case.name)
+    return mel.cpu()
+
+
+def mel_cases(spec):
+    h, half = spec.hop_length, spec.n_fft // 2
+    cs = [MelCase("mel/noise/shortest", (half + 1, half + 1)),
+          MelCase("mel/noise/k_hop", (6 * h, 4 * h), seed=1),
+          MelCase("mel/noise/k_hop_plus1", (6 * h + 1, 4 * h + 1), seed=2),
+          MelCase("mel/noise/k_hop_minus1", (6 * h - 1, 4 * h - 1), seed=3),
+          MelCase("mel/noise/one_short", (6 * h + 164, half + 1), seed=4),
+          MelCase("mel/zero", (6 * h, 4 * h + 76), signal="zero", seed=5),
+          MelCase("mel/square", (6 * h, 6 * h + 1), signal="square", seed=6),
+          MelCase("mel/impulse", (6 * h, 6 * h - 1), signal="impulse", seed=7)]
+    return cs
+
+
+def old_metric(got, ref32):
+    """The whole-tensor figure the earlier tests bound: max |got - ref| / max |ref| against the fp32 library."""
+    return float((got.double() - ref32.double()).abs().max() / (ref32.double().abs().max() + 1e-12))
+
+
+def norm_line(case, err, r, old, where, bound=None, yard=None):
+    b, y = (r.bound if bound is None else bound), (r.yard if yard is None else yard)
+    return (f"NORM_PARITY case={case.name} kernel={case.kernel} err={err:.3e} yardstick={y:.3e} bound={b:.3e} "
+            f"err/bound={err / b:.3f} old_metric={old:.3e} worst_index={where}")

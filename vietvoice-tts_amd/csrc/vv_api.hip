@@ -1771,6 +1771,35 @@ int vv_apg_coef(vv_ctx* c, const vv_apg_coef_args* a, void* st) {
         return c->fail(-22, "vv_apg_coef: the index and item arrays must be 4-byte aligned");
     SINGLE(c, vvk_apg_coef(a, 3, (hipStream_t)st, &m__));
 }
+// single-kernel entries (unit parity) of the text stack: the checks live here, the stages call the launchers with operands they own
+int vv_text_embed(vv_ctx* c, const int32_t* ids, int ld_ids, const int32_t* text_len, const float* emb, const float* pos, int vocab_rows,
+                  float* out, int B, int N, int Dt, void* st) {
+    if (!c) return -22;
+    if (!ids || !text_len || !emb || !pos || !out || B < 1 || N < 1 || ld_ids < 1 || vocab_rows < 1 || Dt < 4 || Dt % 4)
+        return c->fail(-22, "vv_text_embed: bad arguments (B, N, ld_ids, vocab_rows >= 1, Dt a multiple of 4)");
+    if (((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)out) % 16 || ((uintptr_t)ids | (uintptr_t)text_len) % 4)
+        return c->fail(-22, "vv_text_embed: emb, pos and out must be 16-byte aligned, ids and text_len 4-byte");
+    SINGLE(c, vvk_text_embed(ids, ld_ids, text_len, emb, pos, out, B, N, Dt, vocab_rows, (hipStream_t)st, &m__));
+}
+int vv_dwconv(vv_ctx* c, const float* in, float* out, const float* w, const float* bias, const int32_t* seq_len, int B, int n_seq, int N, int C,
+              int KW, void* st) {
+    if (!c) return -22;
+    if (!in || !out || !w || !bias || in == out || n_seq < 1 || N < 1 || C < 4 || C % 4 || KW < 1 || !(KW & 1) || (seq_len && B < 1))
+        return c->fail(-22, "vv_dwconv: bad arguments (out a buffer of its own, C a multiple of 4, KW odd, B >= 1 with seq_len)");
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)bias) % 16 || ((uintptr_t)w | (uintptr_t)seq_len) % 4)
+        return c->fail(-22, "vv_dwconv: in, out and bias must be 16-byte aligned, w and seq_len 4-byte");
+    SINGLE(c, vvk_dwconv(in, out, w, bias, seq_len, seq_len ? B : 1, n_seq, N, C, KW, (hipStream_t)st, &m__));
+}
+int vv_grn(vv_ctx* c, int dtype, void* x, float* sumsq, const float* gamma, const float* beta, const int32_t* seq_len, int B, int n_seq, int N,
+           int C, void* st) {
+    if (!c) return -22;
+    if ((dtype != VV_DTYPE_F32 && dtype != VV_DTYPE_BF16) || !x || !sumsq || !gamma || !beta || n_seq < 1 || N < 1 || C < 64 || C % 64 || C > 8192 ||
+        (seq_len && B < 1))
+        return c->fail(-22, "vv_grn: bad arguments (dtype f32 / bf16, C a multiple of 64 up to 8192, B >= 1 with seq_len)");
+    if ((uintptr_t)x % (dtype == VV_DTYPE_BF16 ? 8 : 16) || (uintptr_t)beta % 16 || ((uintptr_t)sumsq | (uintptr_t)gamma | (uintptr_t)seq_len) % 4)
+        return c->fail(-22, "vv_grn: x must be aligned to 4 elements, beta to 16 bytes, sumsq, gamma and seq_len to 4");
+    SINGLE(c, vvk_grn(dtype, x, sumsq, gamma, beta, seq_len, seq_len ? B : 1, n_seq, N, C, (hipStream_t)st, &m__));
+}
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));
 }

@@ -575,42 +575,55 @@ __global__ __launch_bounds__(256) void guided_tables_kernel(const int* __restric
 }
 
 // ---------------------------------------------------------------- K5: GroupNorm over channel-major slabs [B][C][T]
-// One workgroup per (group, batch item) slab of (C / G) x T contiguous floats.  Two passes, 2 reads + 1 write per element:
-// (1) sum and sum of squares of (x - p), p = the slab's first element (a shifted one-pass variance: no cancellation for data with
-// a large mean), 16-byte loads, wave-shuffle + LDS reductions; (2) normalise with the per-channel affine and the optional fused
-// activation, 16-byte loads and stores.  A slab that is not 16-byte aligned or whose T is not a multiple of 4 takes scalar accesses.
+// One workgroup per (group, batch item) slab of (C / G) x T contiguous floats, which stays in the caches: 3 reads + 1 write per element.
+// (1) m0 = sum x / n; (2) the sums of (x - m0) and (x - m0)^2: the corrected two-pass variance, mean = m0 + d, var = q / n - d^2 with
+// d = sum (x - m0) / n, a few roundings of m0 -- accurate whatever single elements hold (a shift by the slab's first element, the earlier
+// form, lost five digits when that element was an outlier: profiles/norm_parity/notes.md); (3) normalise with the per-channel affine and
+// the optional fused activation.  16-byte loads and stores, wave-shuffle + LDS reductions; a slab that is not 16-byte aligned or whose T
+// is not a multiple of 4 takes scalar accesses.
 __global__ __launch_bounds__(256) void groupnorm_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int C, int T, int G, float eps, int act) {
-    __shared__ float red[2][4];
+    __shared__ float red[3][4];
     const int b = blockIdx.y, g = blockIdx.x;
     const int cpg = C / G;
     const size_t n = (size_t)cpg * T;
     const float* xs = x + ((size_t)b * C + (size_t)g * cpg) * T;
     float* ys = y + ((size_t)b * C + (size_t)g * cpg) * T;
     const bool vec = (T & 3) == 0 && (((uintptr_t)xs | (uintptr_t)ys) & 15) == 0;
-    const float p = xs[0];
-    float s = 0.f, q = 0.f;
+    const size_t n4 = n >> 2;
+    float s0 = 0.f;
     if (vec) {
-        const size_t n4 = n >> 2;
         for (size_t i = threadIdx.x; i < n4; i += 256) {
             const float4 v = *(const float4*)(xs + i * 4);
-            const float a0 = v.x - p, a1 = v.y - p, a2 = v.z - p, a3 = v.w - p;
+            s0 += (v.x + v.y) + (v.z + v.w);
+        }
+    } else {
+        for (size_t i = threadIdx.x; i < n; i += 256) s0 += xs[i];
+    }
+    s0 = wave_sum(s0);
+    if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = s0;
+    __syncthreads();
+    const float m0 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)n;
+    float s = 0.f, q = 0.f;
+    if (vec) {
+        for (size_t i = threadIdx.x; i < n4; i += 256) {
+            const float4 v = *(const float4*)(xs + i * 4);
+            const float a0 = v.x - m0, a1 = v.y - m0, a2 = v.z - m0, a3 = v.w - m0;
             s += (a0 + a1) + (a2 + a3);
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
     } else {
-        for (size_t i = threadIdx.x; i < n; i += 256) { const float d = xs[i] - p; s += d; q += d * d; }
+        for (size_t i = threadIdx.x; i < n; i += 256) { const float d = xs[i] - m0; s += d; q += d * d; }
     }
     s = wave_sum(s); q = wave_sum(q);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = q; }
+    if ((threadIdx.x & 63) == 0) { red[1][threadIdx.x >> 6] = s; red[2][threadIdx.x >> 6] = q; }
     __syncthreads();
-    const float sd = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)n;      // mean of x - p
-    const float var = fmaxf(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)n - sd * sd, 0.f);
-    const float mean = p + sd, rstd = rsqrtf(var + eps);
+    const float sd = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)n;      // mean of x - m0: the rounding m0 carries
+    const float var = fmaxf(((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) / (float)n - sd * sd, 0.f);
+    const float mean = m0 + sd, rstd = rsqrtf(var + eps);
     if (vec) {
         const int t4 = T >> 2;
-        const size_t n4 = n >> 2;
         for (size_t i = threadIdx.x; i < n4; i += 256) {
             const int c = g * cpg + (int)(i / t4);
             const float ga = (gamma ? gamma[c] : 1.f) * rstd, be = beta ? beta[c] : 0.f;
@@ -656,8 +669,10 @@ inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) /
 
 int vvk_ln_mod(const vv_ln_args* a, hipStream_t st, const char** err) {
     if (a->R <= 0) { *err = "ln: empty"; return -22; }
-    if (a->D % 4 || a->D > 1024 || a->ldx % 4 || a->ldy % 4) { *err = "ln: D must be a multiple of 4 and <= 1024"; return -22; }
+    if (a->D < 4 || a->D % 4 || a->D > 1024 || a->ldx % 4 || a->ldy % 4) { *err = "ln: D must be a multiple of 4 within [4, 1024]"; return -22; }
+    if (a->ldx < a->D || a->ldy < a->D) { *err = "ln: ldx and ldy must be at least D"; return -22; }
     if (a->delta && (a->ld_delta % 4 || a->ld_delta < a->D)) { *err = "ln: bad delta leading dimension"; return -22; }
+    if (a->delta2 && !a->delta) { *err = "ln: delta2 without delta"; return -22; }
     const int grid = (a->R + 3) / 4;
     float* x = const_cast<float*>(a->x);
     const bool ob = a->out_dtype == VV_BF16, db = a->delta_dtype == VV_BF16;
