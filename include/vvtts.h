@@ -708,6 +708,28 @@ VV_API uint64_t vv_pcm_flac_ws_bytes(int64_t total_frames, int R);
 VV_API int vv_pcm_flac(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
                        uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ---- N16 LPC subframes for the FLAC output, opt-in: vv_pcm_flac with linear predictors of order 1 ... lpc_order among
+ * the candidates of every frame that is not constant.  vv_pcm_flac itself is unchanged.  The recipe is pinned by core/audio_processor.py
+ * (flac_lpc_coefficients, flac_choose(x, lpc_order)), which the kernels equal byte for byte.  Per frame of m >= 3 samples x:
+ *     window      w[i] = ((i (m - 1 - i)) << 10) / A, A = h (m - 1 - h), h = (m - 1) / 2, in integers (Welch, 0 ... 1024); xw = x w
+ *     lags        R[l] = sum xw[i] xw[i + l], l = 0 ... min(lpc_order, m - 1), exact in int64; R[0] = 0: no LPC candidate
+ *     Levinson    float64, every operation rounded to nearest on its own (no fused multiply-add): err = R[0]; for p = 1, 2, ...:
+ *                 acc = R[p] - a[1] R[p - 1] - ... - a[p - 1] R[1] (in that order), k = acc / err, a'[j] = a[j] - k a[p - j], a'[p] = k,
+ *                 err = err (1 - k k); not err > 0 ends the candidates at order p
+ *     quantise    12 bits: shift = min(11 - e, 15) with max |a[j]| = f 2^e, 0.5 <= f < 1 (shift < 0 or a maximum of 0: no candidate at
+ *                 this order); fe = 0; for j = 1 ... p: fe += a[j] 2^shift, q[j] = clamp(floor(fe + 0.5), -2048, 2047), fe -= q[j]
+ *     residual    r[n] = x[n] - ((sum q[j] x[n - j]) >> shift), n >= p, arithmetic shift; Rice coded exactly as for Fixed
+ *     size        8 + 16 p + 4 + 5 + 12 p + 6 + the partitions
+ * the fewest bits win among constant / Fixed / LPC / verbatim; ties go to Fixed before LPC, then the lower order, then the lower po;
+ * verbatim only when strictly smaller than all others: no frame is larger than vv_pcm_flac's.  Subframe: header byte (32 | (p - 1)) << 1,
+ * p warm-up samples, precision - 1 = 11 (4 bits), shift (5 bits), q[1] ... q[p] (12 bits each, two's complement), the residual.
+ * Arguments, results and refusals as for vv_pcm_flac, with ws_bytes >= vv_pcm_flac_lpc_ws_bytes(sum of the rows' frames, R, lpc_order);
+ * also -22 for lpc_order outside 1 ... VV_FLAC_MAX_LPC_ORDER (the workspace function then returns 0). */
+#define VV_FLAC_MAX_LPC_ORDER 12
+VV_API uint64_t vv_pcm_flac_lpc_ws_bytes(int64_t total_frames, int R, int lpc_order);
+VV_API int vv_pcm_flac_lpc(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
+                           int lpc_order, uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

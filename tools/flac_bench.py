@@ -13,7 +13,10 @@ badly).  Reports bytes out over bytes in, and -- with --bench-json, the line ben
 the FLAC call as a share of the timed synthesis step.  Before timing, the device bytes of two requests are checked against the mirror.
 The split between the kernels comes from a kernel trace of this tool in a run of its own (profiles/flac/notes.md).
 
-    python tools/flac_bench.py [--reps 21] [--pcm-dir DIR] [--bench-json FILE] [--out profiles/flac/flac_bench.json]
+--lpc-order 8,12 adds, per order, vv_pcm_flac_lpc over the same requests: its bytes (two requests checked against the
+mirror with that order) and its call time, alternated with vv_pcm_flac so that both see the same box at the same time.
+
+    python tools/flac_bench.py [--reps 21] [--pcm-dir DIR] [--bench-json FILE] [--lpc-order 8,12] [--out profiles/flac/flac_bench.json]
 
 Prints one JSON line.  There is nothing to measure without a HIP device."""
 import argparse
@@ -29,7 +32,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from vietvoice_tts_amd import runtime as rt  # noqa: E402
-from vietvoice_tts_amd.core.audio_processor import FLAC_BLOCK, flac_encode_frames, flac_frame_bound  # noqa: E402
+from vietvoice_tts_amd.core.audio_processor import FLAC_BLOCK, FLAC_MAX_LPC_ORDER, flac_encode_frames, flac_frame_bound  # noqa: E402
 from vietvoice_tts_amd.model_spec import ModelSpec, make_synthetic_weights  # noqa: E402
 
 SR, HOP, B = 24000, 256, 32
@@ -95,7 +98,7 @@ def stats(ts):
     return {"median_ms": round(float(np.median(ts)), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
 
-def measure(eng, signals, reps):
+def measure(eng, signals, reps, lpc_orders=()):
     lib, dev = eng.lib, eng.device
     offs, at = [], 0
     for s in signals:
@@ -149,10 +152,38 @@ def measure(eng, signals, reps):
     for _ in range(3):
         t_two += host_ms(flac_copies, reps // 3 + 1)
         t_one += host_ms(lambda: x.cpu(), reps // 3 + 1)
-    return {"requests": R, "audio_s": round(n_in / SR, 1), "frames": frames, "bytes_in": 2 * n_in, "bytes_out": total,
-            "ratio_out_over_in": round(total / (2 * n_in), 4), "flac_call": stats(t_flac), "ulaw_call": stats(t_ulaw),
-            "flac_two_copies": stats(t_two), "pcm_one_copy": stats(t_one),
-            "flac_gb_per_s_of_pcm": round(2 * n_in / (np.median(t_flac) * 1e-3) / 1e9, 2)}
+    res = {"requests": R, "audio_s": round(n_in / SR, 1), "frames": frames, "bytes_in": 2 * n_in, "bytes_out": total,
+           "ratio_out_over_in": round(total / (2 * n_in), 4), "flac_call": stats(t_flac), "ulaw_call": stats(t_ulaw),
+           "flac_two_copies": stats(t_two), "pcm_one_copy": stats(t_one),
+           "flac_gb_per_s_of_pcm": round(2 * n_in / (np.median(t_flac) * 1e-3) / 1e9, 2)}
+    if lpc_orders:                                             # N16: vv_pcm_flac_lpc per order, alternated with vv_pcm_flac
+        ws_l = torch.empty((int(lib.vv_pcm_flac_lpc_ws_bytes(frames, R, max(lpc_orders))) // 8 + 1,), dtype=torch.int64, device=dev)
+
+        def lpc(order):
+            rc = lib.vv_pcm_flac_lpc(eng.ctx, x.data_ptr(), x.numel(), rows_d.data_ptr(), rows_h.data_ptr(), R, SR, order, y.data_ptr(), n_y,
+                                     info.data_ptr(), ws_l.data_ptr(), ws_l.numel() * 8, stream)
+            assert rc == 0, lib.vv_last_error(eng.ctx)
+
+        sizes = {}
+        for order in lpc_orders:
+            lpc(order)
+            torch.cuda.synchronize()
+            hinfo = info.cpu().numpy()
+            sizes[order] = int(hinfo[R, 0])
+            host = y[: sizes[order]].cpu().numpy()
+            for r in (0, R - 1):
+                want = flac_encode_frames(signals[r], SR, lpc_order=order)[0]
+                assert np.array_equal(host[int(hinfo[r, 0]): int(hinfo[r + 1, 0])], want), "the device bytes differ from the host mirror"
+        t_plain, t_lpc = [], {order: [] for order in lpc_orders}
+        for _ in range(3):
+            t_plain += events_ms(flac, reps // 3 + 1)
+            for order in lpc_orders:
+                t_lpc[order] += events_ms(lambda: lpc(order), reps // 3 + 1)
+        res["flac_call_beside_lpc"] = stats(t_plain)
+        res["lpc"] = {str(order): {"bytes_out": sizes[order], "ratio_out_over_in": round(sizes[order] / (2 * n_in), 4),
+                                   "bytes_over_fixed_only": round(sizes[order] / total, 4), "call": stats(t_lpc[order]),
+                                   "call_over_flac_call": round(float(np.median(t_lpc[order]) / np.median(t_plain)), 2)} for order in lpc_orders}
+    return res
 
 
 def main():
@@ -160,15 +191,18 @@ def main():
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--pcm-dir", default="", help="bench.py --dump-outputs DIR of the same session: the synthetic model's PCM")
     ap.add_argument("--bench-json", default="", help="a file with the JSON line bench.py printed in the same session on the same box")
+    ap.add_argument("--lpc-order", default="", help="comma-separated LPC orders (1 ... 12) to measure vv_pcm_flac_lpc at, e.g. 8,12")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "flac_bench times the GPU path; there is nothing to measure without a HIP device"
     spec = ModelSpec.tiny()                   # the kernels under the clock take their sizes as arguments; the context can be small
     eng = rt.HipSynth(spec, make_synthetic_weights(spec), acoustic_dtype="bf16", nfe_step=4)
     res = {"metric": "output_flac", "reps": a.reps, "sample_rate": SR, **device_identity()}
-    res["speechlike"] = measure(eng, speech_input(), a.reps)
+    orders = tuple(int(v) for v in a.lpc_order.split(",") if v)
+    assert all(1 <= p <= FLAC_MAX_LPC_ORDER for p in orders), f"--lpc-order: orders in 1 ... {FLAC_MAX_LPC_ORDER}"
+    res["speechlike"] = measure(eng, speech_input(), a.reps, orders)
     if a.pcm_dir:
-        res["synthetic_model_pcm"] = measure(eng, model_input(a.pcm_dir), a.reps)
+        res["synthetic_model_pcm"] = measure(eng, model_input(a.pcm_dir), a.reps, orders)
     if a.bench_json:
         with open(a.bench_json) as f:
             line = [ln for ln in f.read().splitlines() if ln.startswith("{")][-1]

@@ -2,10 +2,11 @@
 // a barrier for __syncthreads, compiler atomics for the LDS atomics, workgroups one after the other, every buffer an exact-size heap
 // block -- so that address and undefined-behaviour sanitizers see an index past an end.  tools/flac_host_check.py builds this file with
 // -fsanitize=address,undefined, feeds it the rows of the GPU test and compares the bytes with the numpy mirror.
-//   flac_host_check IN OUT
+//   flac_host_check IN OUT [LPC_ORDER]      (LPC_ORDER 1 ... 12: the kernels of vv_pcm_flac_lpc, N16; needs -ffp-contract=off)
 // IN : int64 {R, n_x, n_y, rate}; rows R x 4 int64; x n_x int16; y n_y bytes
 // OUT: info (R + 1) x 3 int64; y n_y bytes
 #include <barrier>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +51,8 @@ template <typename T> static T* block(long long n) { return (T*)malloc(sizeof(T)
 
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
+    const int lpc_order = argc > 3 ? atoi(argv[3]) : 0;
+    if (lpc_order < 0 || lpc_order > MAXL) return 2;
     FILE* f = fopen(argv[1], "rb");
     if (!f) return 2;
     long long hdr[4];
@@ -71,16 +74,19 @@ int main(int argc, char** argv) {
     long long* off = block<long long>(total);
     int* rec = block<int>(REC * total);
     long long* info = block<long long>(3 * (R + 1));
+    int* lrec = block<int>(lpc_order ? LREC * total : 0);
     const dim3 grid((unsigned)most, (unsigned)R);
     launch(dim3(1), NT, [&]() { flac_plan_kernel(rows, (int)R, n_x, fbase); });
-    launch(grid, NT, [&]() { flac_analyse_kernel(x, n_x, rows, rate, fbase, total, rec); });
+    if (lpc_order) launch(grid, NT, [&]() { flac_analyse_kernel<true>(x, n_x, rows, rate, fbase, total, rec, lpc_order, lrec); });
+    else launch(grid, NT, [&]() { flac_analyse_kernel<false>(x, n_x, rows, rate, fbase, total, rec, 0, nullptr); });
     launch(dim3(1), NT, [&]() { flac_scan_kernel(fbase, (int)R, total, rec, off, info); });
-    launch(grid, NT, [&]() { flac_pack_kernel(x, n_x, rows, rate, fbase, total, off, rec, y, n_y); });
+    if (lpc_order) launch(grid, NT, [&]() { flac_pack_kernel<true>(x, n_x, rows, rate, fbase, total, off, rec, y, n_y, lrec); });
+    else launch(grid, NT, [&]() { flac_pack_kernel<false>(x, n_x, rows, rate, fbase, total, off, rec, y, n_y, nullptr); });
     f = fopen(argv[2], "wb");
     if (!f) return 2;
     fwrite(info, 8, 3 * (R + 1), f);
     fwrite(y, 1, n_y, f);
     fclose(f);
-    free(rows); free(x); free(y); free(fbase); free(off); free(rec); free(info);
+    free(rows); free(x); free(y); free(fbase); free(off); free(rec); free(info); free(lrec);
     return 0;
 }

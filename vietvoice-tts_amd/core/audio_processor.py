@@ -27,6 +27,7 @@ The polyphase resampler of earlier rounds stays available as an explicit opt-in 
 from __future__ import annotations
 
 import io
+import math
 import struct
 from fractions import Fraction
 from math import gcd
@@ -214,9 +215,11 @@ def lin2alaw(x: np.ndarray) -> np.ndarray:
     return (code ^ mask).astype(np.uint8)
 
 
-def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000) -> np.ndarray:
+def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000, lpc_order: int = 0) -> np.ndarray:
     """``x`` int16 -> the encoding's bytes.  "flac" gives the complete file (stream header + frames) as uint8 and is
-    the one encoding that needs ``sample_rate``."""
+    the one encoding that needs ``sample_rate``; ``lpc_order`` 1 ... 12 adds LPC subframes to it (N16) and is refused elsewhere."""
+    if check_flac_lpc_order(lpc_order) and encoding != "flac":
+        raise ValueError("lpc_order belongs to the encoding 'flac'")
     if encoding == "pcm16":
         return x
     if encoding == "ulaw":
@@ -227,7 +230,7 @@ def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000) -> np.
         pcm = _flac_pcm(x)
         if pcm.size == 0:
             return np.frombuffer(flac_stream_header(sample_rate, 0), np.uint8).copy()
-        frames, lo, hi = flac_encode_frames(pcm, sample_rate)
+        frames, lo, hi = flac_encode_frames(pcm, sample_rate, lpc_order=lpc_order)
         return np.concatenate([np.frombuffer(flac_stream_header(sample_rate, pcm.size, lo, hi), np.uint8), frames])
     raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
 
@@ -242,11 +245,17 @@ def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000) -> np.
 #   verbatim   8 + 16 m bits, only when strictly smaller than every Fixed candidate
 # the fewest bits win; ties go to the lower o, then the lower po.  |order-4 difference of int16| < 2^20, so u < 2^21 and k <= 14 always
 # suffices: the escape code is never written.  Every frame is independent: header (CRC-8), one subframe, zero bits to the byte, CRC-16.
+# N16 (opt-in, ``lpc_order`` 1 ... 12; 0 is all of the above, untouched): LPC(p, po), p = 1 ... min(lpc_order, m - 1), beside the Fixed
+# candidates, from flac_lpc_coefficients (integer Welch window and lags, float64 Levinson-Durbin with one rounding per operation, 12-bit
+# coefficients): 8 + 16 p + 4 + 5 + 12 p + 6 + the same partition sums over x[n] - ((sum q[j] x[n - j]) >> shift).  The fewest bits win
+# among constant / Fixed / LPC / verbatim; ties go to Fixed before LPC, then the lower order, then the lower po.
 FLAC_BLOCK = 4096                    # VV_FLAC_BLOCK: samples per frame, the last one of a signal may be shorter
 FLAC_MAX_ORDER = 4
 FLAC_MAX_PART_ORDER = 4
 FLAC_MAX_RICE = 14
 FLAC_MAX_RATE = 655350               # 16 bits of tens of Hz in a frame header; STREAMINFO itself has 20 bits of Hz
+FLAC_MAX_LPC_ORDER = 12              # ModelConfig.flac_lpc_order: the subset limit of the format at rates up to 48 kHz (N16)
+FLAC_LPC_PRECISION = 12              # bits of a quantised predictor coefficient
 _FLAC_RATE_CODE = {88200: 1, 176400: 2, 192000: 3, 8000: 4, 16000: 5, 22050: 6, 24000: 7, 32000: 8, 44100: 9, 48000: 10, 96000: 11}
 
 
@@ -299,6 +308,12 @@ def _check_flac_rate(sample_rate) -> int:
     return int(sample_rate)
 
 
+def check_flac_lpc_order(lpc_order) -> int:
+    if isinstance(lpc_order, bool) or not isinstance(lpc_order, (int, np.integer)) or not 0 <= int(lpc_order) <= FLAC_MAX_LPC_ORDER:
+        raise ValueError(f"flac_lpc_order must be an integer in 0 ... {FLAC_MAX_LPC_ORDER} (0 = fixed predictors only)")
+    return int(lpc_order)
+
+
 def flac_stream_header(sample_rate: int, total_samples: int, min_frame: int = 0, max_frame: int = 0) -> bytes:
     """The 42 bytes in front of the frames: ``fLaC`` and one STREAMINFO block (the last metadata block): block size 4096 / 4096, the
     smallest and largest frame in bytes (0 = not known), rate, mono, 16 bits, total samples (0 = not known: a stream), and an MD5 of
@@ -337,39 +352,111 @@ def _flac_frame_header(m: int, sample_rate: int, number: int) -> bytes:
     return head + bytes([flac_crc8(head)])
 
 
-def flac_choose(x: np.ndarray):
+def _flac_rice(u: np.ndarray, o: int, pmax: int):
+    """The Rice search of one predictor: u = the zigzag values of all m positions, zeros at the o warm-up samples.  -> (po, ks, bits) of
+    the partition order that needs the fewest bits (the lowest of equals), bits = the 6 of method and order, and per partition 4 and
+    the codes under its best k (the lowest of equals); None if no partition order holds more than o samples."""
+    m = u.size
+    shifts = np.arange(FLAC_MAX_RICE + 1).reshape(-1, 1, 1)
+    sums = (u.reshape(1, 1 << pmax, -1) >> shifts).sum(axis=2)              # [k][finest partition]
+    best = None
+    for po in range(pmax, -1, -1):
+        if po < pmax:
+            sums = sums[:, 0::2] + sums[:, 1::2]                            # additive over partitions
+        if (m >> po) <= o:
+            continue
+        count = np.full(1 << po, m >> po, np.int64)
+        count[0] -= o
+        cost = count.reshape(1, -1) * (shifts.reshape(-1, 1) + 1) + sums
+        bits = 6 + int((4 + cost.min(axis=0)).sum())
+        if best is None or bits <= best[2]:                                 # descending po: the lowest of equals stays
+            best = (po, [int(k) for k in cost.argmin(axis=0)], bits)        # the first minimum: the lowest k
+    return best
+
+
+def _flac_zigzag(r: np.ndarray, m: int) -> np.ndarray:
+    u = np.zeros(m, np.int64)                                               # the warm-up samples count as u = 0: nothing in any sum
+    u[m - r.size:] = np.where(r >= 0, 2 * r, -2 * r - 1)
+    return u
+
+
+def flac_lpc_coefficients(x: np.ndarray, max_order: int):
+    """The quantised predictors of one frame: -> {p: (shift, [q1 ... qp])} for the orders 1 ... min(max_order, m - 1)
+    that are candidates.  Welch window and autocorrelation in exact integers, Levinson-Durbin in float64 with one rounding per written
+    operation (csrc/vv_flac.hip does the same operations in the same order), 12-bit coefficients with the error fed forward."""
+    x = np.asarray(x).reshape(-1).astype(np.int64)
+    m, out = x.size, {}
+    if m < 3 or max_order < 1:
+        return out
+    h = (m - 1) // 2
+    i = np.arange(m, dtype=np.int64)
+    xw = x * (((i * (m - 1 - i)) << 10) // (h * ((m - 1) - h)))             # |xw| <= 2^25
+    lags = min(int(max_order), m - 1)
+    R = [int((xw[: m - lag] * xw[lag:]).sum()) for lag in range(lags + 1)]  # |R| <= 4096 * 2^50: exact in int64
+    if R[0] == 0:
+        return out
+    Rf = [float(v) for v in R]
+    a, err = [0.0], Rf[0]                                                   # a[1 ... p]: x[n] ~ sum a[j] x[n - j]
+    for p in range(1, lags + 1):
+        acc = Rf[p]
+        for j in range(1, p):
+            acc = acc - a[j] * Rf[p - j]
+        k = acc / err
+        a = [0.0] + [a[j] - k * a[p - j] for j in range(1, p)] + [k]
+        err = err * (1.0 - k * k)
+        if not err > 0.0:
+            break
+        cmax = max(abs(v) for v in a[1:])
+        if cmax == 0.0:
+            continue
+        shift = min(FLAC_LPC_PRECISION - 1 - math.frexp(cmax)[1], 15)
+        if shift < 0:
+            continue
+        fe, q = 0.0, []
+        for j in range(1, p + 1):
+            fe = fe + math.ldexp(a[j], shift)
+            q.append(int(min(max(math.floor(fe + 0.5), -(1 << (FLAC_LPC_PRECISION - 1))), (1 << (FLAC_LPC_PRECISION - 1)) - 1)))
+            fe = fe - q[-1]
+        out[p] = (shift, q)
+    return out
+
+
+def _flac_lpc_residual(x: np.ndarray, shift: int, q) -> np.ndarray:
+    """x[n] - ((sum q[j] x[n - j]) >> shift) for n >= p, x int64: the sum stays below 12 * 2^26, the shift is arithmetic."""
+    p, m = len(q), x.size
+    pred = np.zeros(m - p, np.int64)
+    for j in range(1, p + 1):
+        pred += int(q[j - 1]) * x[p - j: m - j]
+    return x[p:] - (pred >> shift)
+
+
+def flac_choose(x: np.ndarray, lpc_order: int = 0):
     """The subframe of one frame: -> (kind, o, po, ks, bits), kind = "constant" | "verbatim" | "fixed", ks = the Rice parameter of each
-    of the 2^po partitions, bits = the subframe's exact size.  Exhaustive over (o, po) and, per partition, k."""
+    of the 2^po partitions, bits = the subframe's exact size.  Exhaustive over (o, po) and, per partition, k.  With ``lpc_order`` 1 ...
+    12 (N16) the predictors of flac_lpc_coefficients run as well: kind may be "lpc" and the tuple ends with (shift, [q1 ... qo])."""
     x = np.asarray(x).reshape(-1).astype(np.int64)
     m = x.size
     if m < 1 or m > FLAC_BLOCK:
         raise ValueError(f"a FLAC frame holds 1 ... {FLAC_BLOCK} samples")
+    lpc_order = check_flac_lpc_order(lpc_order)
+    tail = ((0, []),) if lpc_order else ()
     if (x == x[0]).all():
-        return "constant", 0, 0, [], 24
+        return ("constant", 0, 0, [], 24) + tail
     pmax = 0
     while pmax < FLAC_MAX_PART_ORDER and m % (2 << pmax) == 0:
         pmax += 1
-    shifts = np.arange(FLAC_MAX_RICE + 1).reshape(-1, 1, 1)
     best = None
     for o in range(min(FLAC_MAX_ORDER, m - 1) + 1):
-        r = np.diff(x, n=o)
-        u = np.zeros(m, np.int64)                                           # the o warm-up samples count as u = 0: nothing in any sum
-        u[o:] = np.where(r >= 0, 2 * r, -2 * r - 1)
-        sums = (u.reshape(1, 1 << pmax, -1) >> shifts).sum(axis=2)          # [k][finest partition]
-        for po in range(pmax, -1, -1):
-            if po < pmax:
-                sums = sums[:, 0::2] + sums[:, 1::2]                        # additive over partitions
-            if (m >> po) <= o:
-                continue
-            count = np.full(1 << po, m >> po, np.int64)
-            count[0] -= o
-            cost = count.reshape(1, -1) * (shifts.reshape(-1, 1) + 1) + sums
-            ks = cost.argmin(axis=0)                                        # the first minimum: the lowest k
-            bits = 8 + 16 * o + 6 + int((4 + cost.min(axis=0)).sum())
-            if best is None or (bits, o, po) < (best[4], best[1], best[2]):
-                best = ("fixed", o, po, [int(k) for k in ks], bits)
+        po, ks, bits = _flac_rice(_flac_zigzag(np.diff(x, n=o), m), o, pmax)
+        if best is None or 8 + 16 * o + bits < best[4]:                     # ascending o: the lowest of equals stays
+            best = ("fixed", o, po, ks, 8 + 16 * o + bits) + tail
+    for p, (shift, q) in sorted(flac_lpc_coefficients(x, lpc_order).items()):
+        po, ks, bits = _flac_rice(_flac_zigzag(_flac_lpc_residual(x, shift, q), m), p, pmax)
+        bits += 8 + 16 * p + 4 + 5 + FLAC_LPC_PRECISION * p
+        if bits < best[4]:                                                  # Fixed before LPC, then the lower order
+            best = ("lpc", p, po, ks, bits, (shift, q))
     if 8 + 16 * m < best[4]:
-        return "verbatim", 0, 0, [], 8 + 16 * m
+        return ("verbatim", 0, 0, [], 8 + 16 * m) + tail
     return best
 
 
@@ -380,11 +467,11 @@ def _put(bits: np.ndarray, pos, value, n: int):
         bits[pos + b] = (value >> (n - 1 - b)) & 1
 
 
-def flac_encode_frame(x: np.ndarray, sample_rate: int, number: int) -> bytes:
-    """One complete frame of 1 ... 4096 int16 samples with frame number ``number``."""
+def flac_encode_frame(x: np.ndarray, sample_rate: int, number: int, lpc_order: int = 0) -> bytes:
+    """One complete frame of 1 ... 4096 int16 samples with frame number ``number``; ``lpc_order`` as for flac_choose."""
     x = np.asarray(x).reshape(-1).astype(np.int64)
     m = x.size
-    kind, o, po, ks, n_bits = flac_choose(x)
+    kind, o, po, ks, n_bits, *lpc = flac_choose(x, lpc_order)
     bits = np.zeros(n_bits, np.uint8)
     if kind == "constant":
         _put(bits, 8, x[0] & 0xFFFF, 16)                                    # subframe header 0 000000 0
@@ -392,11 +479,20 @@ def flac_encode_frame(x: np.ndarray, sample_rate: int, number: int) -> bytes:
         _put(bits, 0, 0x02, 8)
         _put(bits, 8 + 16 * np.arange(m), x & 0xFFFF, 16)
     else:
-        _put(bits, 0, (8 | o) << 1, 8)
         _put(bits, 8 + 16 * np.arange(o), x[:o] & 0xFFFF, 16)
         base = 8 + 16 * o
+        if kind == "lpc":
+            shift, q = lpc[0]
+            _put(bits, 0, (32 | (o - 1)) << 1, 8)
+            _put(bits, base, FLAC_LPC_PRECISION - 1, 4)
+            _put(bits, base + 4, shift, 5)
+            _put(bits, base + 9 + FLAC_LPC_PRECISION * np.arange(o), np.asarray(q, np.int64) & ((1 << FLAC_LPC_PRECISION) - 1), FLAC_LPC_PRECISION)
+            base += 9 + FLAC_LPC_PRECISION * o
+            r = _flac_lpc_residual(x, shift, q)
+        else:
+            _put(bits, 0, (8 | o) << 1, 8)
+            r = np.diff(x, n=o)
         _put(bits, base, po, 6)                                             # coding method 00, partition order
-        r = np.diff(x, n=o)
         u = np.where(r >= 0, 2 * r, -2 * r - 1)
         ps = m >> po
         count = np.full(1 << po, ps, np.int64)
@@ -417,18 +513,18 @@ def flac_encode_frame(x: np.ndarray, sample_rate: int, number: int) -> bytes:
     return body + struct.pack(">H", flac_crc16(body))
 
 
-def flac_encode_frames(pcm, sample_rate: int, frame0: int = 0, last: bool = True):
+def flac_encode_frames(pcm, sample_rate: int, frame0: int = 0, last: bool = True, lpc_order: int = 0):
     """The frames of an int16 signal, the host mirror of vv_pcm_flac: ceil(n / 4096) frames numbered from ``frame0``,
-    back to back.  ``last=False`` = a block of a stream: n must be a multiple of 4096.  -> (uint8 frames, smallest frame, largest frame
-    in bytes); (empty, 0, 0) for an empty signal."""
+    back to back.  ``last=False`` = a block of a stream: n must be a multiple of 4096.  ``lpc_order`` 1 ... 12 = the mirror of
+    vv_pcm_flac_lpc (N16).  -> (uint8 frames, smallest frame, largest frame in bytes); (empty, 0, 0) for an empty signal."""
     pcm = _flac_pcm(pcm)
-    sr, frame0 = _check_flac_rate(sample_rate), int(frame0)
+    sr, frame0, lpc_order = _check_flac_rate(sample_rate), int(frame0), check_flac_lpc_order(lpc_order)
     n_frames = -(-pcm.size // FLAC_BLOCK)
     if frame0 < 0 or frame0 + n_frames > 1 << 31:
         raise ValueError("FLAC: frame numbers run from 0 to 2^31 - 1")
     if not last and pcm.size % FLAC_BLOCK:
         raise ValueError(f"FLAC: a block that is not the last one holds whole frames of {FLAC_BLOCK} samples")
-    frames = [flac_encode_frame(pcm[f * FLAC_BLOCK: (f + 1) * FLAC_BLOCK], sr, frame0 + f) for f in range(n_frames)]
+    frames = [flac_encode_frame(pcm[f * FLAC_BLOCK: (f + 1) * FLAC_BLOCK], sr, frame0 + f, lpc_order) for f in range(n_frames)]
     if not frames:
         return np.zeros(0, np.uint8), 0, 0
     return np.frombuffer(b"".join(frames), np.uint8).copy(), min(map(len, frames)), max(map(len, frames))
@@ -1151,11 +1247,13 @@ class FlacStream:
     ``push`` starts with the stream header (total samples 0 = not known), every ``push`` returns the whole frames in hand, ``flush`` the
     remainder as the final short frame.  The concatenation is a valid stream whose frames equal ``flac_encode_frames`` of the whole
     signal.  ``encode(pcm, frame0, last)`` returns the frames' bytes: the host mirror, or the device kernel
-    (HipSynth.output_stream_backends)."""
+    (HipSynth.output_stream_backends).  With ``lpc_order`` 1 ... 12 (N16) the back end is called as
+    ``encode(pcm, frame0, last, lpc_order)``."""
 
-    def __init__(self, sample_rate: int, encode=None):
-        self.rate = _check_flac_rate(sample_rate)
-        self._encode = encode or (lambda pcm, frame0, last: flac_encode_frames(pcm, self.rate, frame0, last)[0])
+    def __init__(self, sample_rate: int, encode=None, lpc_order: int = 0):
+        self.rate, self.lpc_order = _check_flac_rate(sample_rate), check_flac_lpc_order(lpc_order)
+        encode = encode or (lambda pcm, frame0, last, order=0: flac_encode_frames(pcm, self.rate, frame0, last, order)[0])
+        self._encode = encode if not self.lpc_order else (lambda pcm, frame0, last: encode(pcm, frame0, last, self.lpc_order))
         self.left = np.zeros(0, np.int16)
         self.frame = 0
         self.started = False

@@ -76,6 +76,9 @@ class ModelConfig:
     output_sample_rate: Optional[int] = None   # None = sample_rate; else the output is rate-converted (band-limited polyphase FIR, vv_pcm_resample)
     output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode) | "flac" (a FLAC file, lossless, vv_pcm_flac: N15).  A rate or an encoding runs on the
                                             # device on the HIP engine, through the host mirrors on injected sessions
+    flac_lpc_order: int = 0                 # highest LPC order the FLAC encoder tries per frame, 1 ... 12 (vv_pcm_flac_lpc): smaller files on
+                                            # tonal material, the same samples back.  0 = fixed predictors only, the encoder of N15 byte for byte.  Needs
+                                            # output_encoding "flac"
     output_loudness: Optional[float] = None  # programme loudness of every utterance in LUFS (ITU-R BS.1770-4 integrated, gated), -60 ... -5; None = off.
                                             # Measured and applied after the join, before the output rate and the encoding (vv_pcm_loudness on the HIP
                                             # engine, audio_processor.normalize_loudness on injected sessions).  Not available in synthesize_stream
@@ -112,6 +115,9 @@ class ModelConfig:
         from .audio_processor import OUTPUT_ENCODINGS
         if self.output_encoding not in OUTPUT_ENCODINGS:
             raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+        from .audio_processor import check_flac_lpc_order
+        if check_flac_lpc_order(self.flac_lpc_order) and self.output_encoding != "flac":
+            raise ValueError("flac_lpc_order above 0 needs output_encoding 'flac'")
         if self.output_sample_rate is not None:
             if isinstance(self.output_sample_rate, bool) or int(self.output_sample_rate) != self.output_sample_rate:
                 raise ValueError("output_sample_rate must be an integer number of Hz or None")

@@ -161,6 +161,10 @@ class TTSEngine:
         rate = cfg.output_sample_rate
         return (None if rate is None or int(rate) == int(cfg.sample_rate) else int(rate)), cfg.output_encoding
 
+    def _flac_options(self, key: str = "lpc_order") -> dict:
+        """N16: {key: flac_lpc_order} when LPC subframes are asked for, else nothing: the calls of N15 as they were."""
+        return {key: self.config.flac_lpc_order} if self.config.flac_lpc_order else {}
+
     @property
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
@@ -196,7 +200,7 @@ class TTSEngine:
         rate, enc = self._output_options()
         if rate is not None:
             final = resample_output(final, self.config.sample_rate, rate)
-        return encode_output(final, enc, self.output_rate) if enc != "pcm16" else final
+        return encode_output(final, enc, self.output_rate, **self._flac_options()) if enc != "pcm16" else final
 
     def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
@@ -216,16 +220,16 @@ class TTSEngine:
             lim = [lim if v is None else v for v in limiter]
             if all(v is None for v in lim):
                 lim = None
-        pros = {}
+        opts = self._flac_options("flac_lpc_order")
         for key, own, mine in (("pitch", pitch, self.config.output_pitch), ("tempo", tempo, self.config.output_tempo)):
             vals = [mine] * len(counts) if own is None else [mine if v is None else v for v in own]
             if any(v is not None for v in vals):           # no pitch and no tempo anywhere: exactly the call of N13
-                pros[key] = vals
+                opts[key] = vals
         if lim is None:                    # no limiter anywhere: exactly the call of N12
             return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs, **pros)
+                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs, **opts)
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **pros)
+                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **opts)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
                            apg_etas=None, apg_norms=None):
@@ -426,7 +430,7 @@ class TTSEngine:
                 backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
                 if rate is not None:
                     ostream = OutputStream(self.config.sample_rate, rate, "pcm16", backends[0], None)
-                fstream = FlacStream(self.output_rate, backends[1])
+                fstream = FlacStream(self.output_rate, backends[1], **self._flac_options())
             elif rate is not None or enc != "pcm16":
                 from .audio_processor import OutputStream
                 eng = self.model_session_manager.engine
@@ -532,7 +536,8 @@ class TTSEngine:
                                              loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs,
                                              **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}),
                                              **({} if cfg.output_pitch is None and cfg.output_tempo is None
-                                                else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}))[0]
+                                                else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}),
+                                             **self._flac_options("flac_lpc_order"))[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

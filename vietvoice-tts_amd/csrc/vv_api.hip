@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.8 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.9 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -796,43 +796,63 @@ uint64_t vv_flac_frame_bound(int64_t m) { return vvk_flac_frame_bound((long long
 
 uint64_t vv_pcm_flac_ws_bytes(int64_t total_frames, int R) { return vvk_pcm_flac_ws_bytes((long long)total_frames, R); }
 
-int vv_pcm_flac(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate, uint8_t* y,
-                int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream) {
-    if (!c) return -22;
+// both entries: lpc_order 0 = vv_pcm_flac (N15), 1 ... 12 = vv_pcm_flac_lpc (N16)
+static int pcm_flac(vv_ctx* c, const char* name, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
+                    int lpc_order, uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream) {
     hipSetDevice(c->device);
     hipStream_t st = (hipStream_t)stream;
-    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0) return c->fail(-22, "vv_pcm_flac: bad sizes (1 <= R <= 65535)");
-    if (sample_rate < 1 || sample_rate > 655350) return c->fail(-22, "vv_pcm_flac: a sample rate in 1 ... 655350 Hz is needed");
-    if (!x || !rows || !rows_host || !y || !info || !ws) return c->fail(-22, "vv_pcm_flac: null pointer (x, rows, rows_host, y, info, ws)");
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0) return c->fail(-22, "%s: bad sizes (1 <= R <= 65535)", name);
+    if (sample_rate < 1 || sample_rate > 655350) return c->fail(-22, "%s: a sample rate in 1 ... 655350 Hz is needed", name);
+    if (!x || !rows || !rows_host || !y || !info || !ws) return c->fail(-22, "%s: null pointer (x, rows, rows_host, y, info, ws)", name);
     if ((uintptr_t)x % 2 || (uintptr_t)rows % 8 || (uintptr_t)rows_host % 8 || (uintptr_t)info % 8 || (uintptr_t)ws % 8)
-        return c->fail(-22, "vv_pcm_flac: misaligned pointer (x 2 bytes; rows, rows_host, info, ws 8)");
+        return c->fail(-22, "%s: misaligned pointer (x 2 bytes; rows, rows_host, info, ws 8)", name);
     if ((uintptr_t)y < (uintptr_t)(x + n_x) && (uintptr_t)x < (uintptr_t)(y + n_y))
-        return c->fail(-22, "vv_pcm_flac: y overlaps x (a frame is packed while others are still read)");
+        return c->fail(-22, "%s: y overlaps x (a frame is packed while others are still read)", name);
     int64_t total_frames = 0, max_frames = 0, total_samples = 0;
     uint64_t need = 0;
     for (int r = 0; r < R; ++r) {
         const int64_t* q = rows_host + 4 * (size_t)r;
-        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "vv_pcm_flac: row %d has a negative field", r);
-        if (q[1] < 1) return c->fail(-22, "vv_pcm_flac: row %d is empty (n >= 1)", r);
-        if (q[1] > n_x || q[0] > n_x - q[1]) return c->fail(-22, "vv_pcm_flac: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "%s: row %d has a negative field", name, r);
+        if (q[1] < 1) return c->fail(-22, "%s: row %d is empty (n >= 1)", name, r);
+        if (q[1] > n_x || q[0] > n_x - q[1]) return c->fail(-22, "%s: row %d does not fit the %lld samples of x", name, r, (long long)n_x);
         const int64_t frames = (q[1] + VV_FLAC_BLOCK - 1) / VV_FLAC_BLOCK;
-        if (q[2] > ((int64_t)1 << 31) - frames) return c->fail(-22, "vv_pcm_flac: row %d: frame0 + frames exceeds 2^31", r);
+        if (q[2] > ((int64_t)1 << 31) - frames) return c->fail(-22, "%s: row %d: frame0 + frames exceeds 2^31", name, r);
         if (q[3] > 1 || (q[3] == 0 && q[1] % VV_FLAC_BLOCK))
-            return c->fail(-22, "vv_pcm_flac: row %d: last is 0 or 1, and last = 0 needs n to be a multiple of %d", r, VV_FLAC_BLOCK);
+            return c->fail(-22, "%s: row %d: last is 0 or 1, and last = 0 needs n to be a multiple of %d", name, r, VV_FLAC_BLOCK);
         need += (uint64_t)(frames - 1) * vvk_flac_frame_bound(VV_FLAC_BLOCK) + vvk_flac_frame_bound(q[1] - (frames - 1) * VV_FLAC_BLOCK);
         total_frames += frames;
         total_samples += q[1];
         if (frames > max_frames) max_frames = frames;
     }
     if ((uint64_t)n_y < need)
-        return c->fail(-22, "vv_pcm_flac: y of %lld bytes, the frame bounds add up to %llu", (long long)n_y, (unsigned long long)need);
-    if (ws_bytes < vvk_pcm_flac_ws_bytes((long long)total_frames, R))
-        return c->fail(-22, "vv_pcm_flac: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
-                       (unsigned long long)vvk_pcm_flac_ws_bytes((long long)total_frames, R));
-    Prof p(c, VV_PROF_ELEMWISE, 200.0 * (double)total_samples, 4.0 * (double)total_samples + 2.0 * (double)need, st);
-    KCHK(c, vvk_pcm_flac(x, (long long)n_x, (const long long*)rows, R, sample_rate, (long long)total_frames, (long long)max_frames, y, (long long)n_y,
+        return c->fail(-22, "%s: y of %lld bytes, the frame bounds add up to %llu", name, (long long)n_y, (unsigned long long)need);
+    const uint64_t ws_need = lpc_order ? vvk_pcm_flac_lpc_ws_bytes((long long)total_frames, R) : vvk_pcm_flac_ws_bytes((long long)total_frames, R);
+    if (ws_bytes < ws_need)
+        return c->fail(-22, "%s: ws of %llu bytes, %llu are needed", name, (unsigned long long)ws_bytes,
+                       (unsigned long long)ws_need);
+    Prof p(c, VV_PROF_ELEMWISE, (lpc_order ? 800.0 : 200.0) * (double)total_samples, 4.0 * (double)total_samples + 2.0 * (double)need, st);
+    KCHK(c, vvk_pcm_flac(x, (long long)n_x, (const long long*)rows, R, sample_rate, lpc_order, (long long)total_frames, (long long)max_frames, y, (long long)n_y,
                          (long long*)info, ws, st, &m__));
     return 0;
+}
+
+int vv_pcm_flac(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate, uint8_t* y,
+                int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    return pcm_flac(c, "vv_pcm_flac", x, n_x, rows, rows_host, R, sample_rate, 0, y, n_y, info, ws, ws_bytes, stream);
+}
+
+// N16: the same with LPC subframes of order 1 ... lpc_order among the candidates; the workspace also holds the frames' predictors
+uint64_t vv_pcm_flac_lpc_ws_bytes(int64_t total_frames, int R, int lpc_order) {
+    return lpc_order < 1 || lpc_order > VV_FLAC_MAX_LPC_ORDER ? 0 : vvk_pcm_flac_lpc_ws_bytes((long long)total_frames, R);
+}
+
+int vv_pcm_flac_lpc(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate, int lpc_order,
+                    uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    if (lpc_order < 1 || lpc_order > VV_FLAC_MAX_LPC_ORDER)
+        return c->fail(-22, "vv_pcm_flac_lpc: lpc_order in 1 ... %d is needed (vv_pcm_flac is the encoder without LPC)", VV_FLAC_MAX_LPC_ORDER);
+    return pcm_flac(c, "vv_pcm_flac_lpc", x, n_x, rows, rows_host, R, sample_rate, lpc_order, y, n_y, info, ws, ws_bytes, stream);
 }
 
 // --------------------------------------------------------------------------- transformer steps

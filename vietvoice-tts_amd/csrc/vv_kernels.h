@@ -100,8 +100,10 @@ int vvk_pcm_stretch(const int16_t* x, long long n_x, const long long* rows, int 
 // N15 FLAC output (vv_flac.hip): per frame of 4096 samples the exhaustive fixed-predictor / Rice search, the frames' offsets, the bit packing;
 // rows R x 4 {src_off, n, frame0, last}
 unsigned long long vvk_flac_frame_bound(long long m);
+// lpc_order 0 = N15; 1 ... 12 = N16: LPC subframes among the candidates, with vvk_pcm_flac_lpc_ws_bytes of scratch
 unsigned long long vvk_pcm_flac_ws_bytes(long long total_frames, int R);
-int vvk_pcm_flac(const int16_t* x, long long n_x, const long long* rows, int R, int rate, long long total_frames, long long max_frames,
+unsigned long long vvk_pcm_flac_lpc_ws_bytes(long long total_frames, int R);
+int vvk_pcm_flac(const int16_t* x, long long n_x, const long long* rows, int R, int rate, int lpc_order, long long total_frames, long long max_frames,
                  uint8_t* y, long long n_y, long long* info, void* ws, hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);

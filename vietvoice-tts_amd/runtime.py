@@ -212,6 +212,9 @@ EXPORTS = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_flac_frame_bound": (C.c_uint64, [C.c_int64]),
     "vv_pcm_flac_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
+    "vv_pcm_flac_lpc_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int, C.c_int]),
+    "vv_pcm_flac_lpc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_pcm_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                               C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_pcm_stretch_ws_bytes": (C.c_uint64, [C.c_int]),
@@ -1135,14 +1138,16 @@ class HipSynth:
         return new[:max(base, 8)], new_offs, new_lens
 
     # ------------------------------------------------------------------ FLAC output (N15)
-    def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int):
+    def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int, lpc_order: int = 0):
         """FLAC frames of R final signals in one call (vv_pcm_flac), byte for byte core.audio_processor.flac_encode_frames.
+        lpc_order 1 ... 12: with LPC subframes (vv_pcm_flac_lpc; N16), byte for byte the mirror with that order; 0 = vv_pcm_flac as ever.
         x int16 flat on the device; rows = HOST rows (src_off, n, frame0, last): x[src_off, +n) becomes ceil(n / 4096) frames numbered from
         frame0; last = 0 = a block of a stream (n a multiple of 4096).  -> (y, info): y the uint8 device buffer with the frames of all rows
         back to back, info the (R + 1) x 3 int64 device tensor {offset of the row's first frame, smallest frame, largest frame} with
         info[R][0] = the total bytes.  The rows are validated here; the call never synchronises."""
-        from .core.audio_processor import FLAC_BLOCK, FLAC_MAX_RATE, flac_frame_bound
+        from .core.audio_processor import FLAC_BLOCK, FLAC_MAX_RATE, check_flac_lpc_order, flac_frame_bound
         assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        lpc_order = check_flac_lpc_order(lpc_order)
         rows = [[int(v) for v in r] for r in rows]
         if not rows or any(len(r) != 4 for r in rows) or len(rows) > 65535:
             raise ValueError("pcm_flac: 1 to 65535 rows of 4 entries {src_off, n, frame0, last}")
@@ -1161,14 +1166,19 @@ class HipSynth:
         rows_d = rows_h.to(self.device)
         y = torch.empty((n_y,), dtype=torch.uint8, device=self.device)
         info = torch.empty((R + 1, 3), dtype=torch.int64, device=self.device)
-        ws = torch.empty((int(self.lib.vv_pcm_flac_ws_bytes(frames, R)) // 8 + 1,), dtype=torch.int64, device=self.device)
+        ws_bytes = self.lib.vv_pcm_flac_lpc_ws_bytes(frames, R, lpc_order) if lpc_order else self.lib.vv_pcm_flac_ws_bytes(frames, R)
+        ws = torch.empty((int(ws_bytes) // 8 + 1,), dtype=torch.int64, device=self.device)
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_flac(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), y.data_ptr(), n_y,
-                                             info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
+            if lpc_order:
+                self._check(self.lib.vv_pcm_flac_lpc(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), lpc_order,
+                                                     y.data_ptr(), n_y, info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
+            else:
+                self._check(self.lib.vv_pcm_flac(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), y.data_ptr(), n_y,
+                                                 info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
         return y, info
 
-    def _flac_files(self, buf: torch.Tensor, offs, lens, sample_rate: int):
-        """The last step of finish_output with encoding "flac": one vv_pcm_flac call over the requests, ONE small copy of info (24 (R + 1)
+    def _flac_files(self, buf: torch.Tensor, offs, lens, sample_rate: int, lpc_order: int = 0):
+        """The last step of finish_output with encoding "flac": one vv_pcm_flac (lpc_order > 0: vv_pcm_flac_lpc) call over the requests, ONE small copy of info (24 (R + 1)
         bytes, the one synchronisation), one copy of exactly info[R][0] bytes; the host puts each request's stream header in front, with
         its true sample count and its frame sizes.  An empty request is a header alone."""
         import numpy as np
@@ -1176,7 +1186,7 @@ class HipSynth:
         sel = [i for i, n in enumerate(lens) if n > 0]
         frames = {}
         if sel:
-            y, info = self.pcm_flac(buf, [[offs[i], lens[i], 0, 1] for i in sel], sample_rate)
+            y, info = self.pcm_flac(buf, [[offs[i], lens[i], 0, 1] for i in sel], sample_rate, lpc_order)
             info = info.cpu().numpy()
             total = int(info[len(sel), 0])
             host = y[:total].cpu().numpy()
@@ -1190,7 +1200,7 @@ class HipSynth:
         return out
 
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None):
+                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0):
         """The whole output stage of R requests on the caller's stream: join (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
         (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
         spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
@@ -1201,9 +1211,12 @@ class HipSynth:
         nothing new is called): a request with a limiter is measured only (pcm_loudness, out="measure") and takes its uncapped loudness
         gain, or the gain 1 without a target, through pcm_limit in place; the others keep the capped gain of N12.
         encoding "flac" (N15): the final PCM goes through pcm_flac instead of the one copy: a small copy of the frames' sizes, then a copy
-        of exactly the frames' bytes; each request comes back as a complete FLAC file.
+        of exactly the frames' bytes; each request comes back as a complete FLAC file.  flac_lpc_order 1 ... 12 (N16) adds LPC subframes
+        (vv_pcm_flac_lpc instead of vv_pcm_flac) and is refused with another encoding.
         -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
-        from .core.audio_processor import resample_len
+        from .core.audio_processor import check_flac_lpc_order, resample_len
+        if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
+            raise ValueError("finish_output: flac_lpc_order belongs to the encoding 'flac'")
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
         pitch, tempo = [list(v) if isinstance(v, (list, tuple)) else [v] * len(lens) for v in (pitch, tempo)]
         if len(pitch) != len(lens) or len(tempo) != len(lens):
@@ -1249,7 +1262,7 @@ class HipSynth:
             buf = self.pcm_resample(buf, rows, sample_rate, rate, n_y=pos) if pos else buf[:0]
             offs, lens = [r[2] for r in rows], [r[3] for r in rows]
         if encoding == "flac":             # N15: variable-length output -- the frames' total comes back first, then exactly that many bytes
-            return self._flac_files(buf, offs, lens, int(sample_rate) if rate is None else int(rate))
+            return self._flac_files(buf, offs, lens, int(sample_rate) if rate is None else int(rate), flac_lpc_order)
         if encoding != "pcm16":
             rows, pos = [], 0
             for o, n in zip(offs, lens):
@@ -1263,7 +1276,8 @@ class HipSynth:
     def output_stream_backends(self, sample_rate: int, rate: Optional[int], encoding: str, max_upload: int = 1 << 18):
         """(resample, encode) callables for core.audio_processor.OutputStream on this device: host blocks go up in pieces of at most
         ``max_upload`` samples (0.5 MB), through vv_pcm_resample / vv_pcm_encode, and come back.  With encoding "flac" the second one is
-        the ``encode(pcm, frame0, last)`` of core.audio_processor.FlacStream (vv_pcm_flac), which sits behind the OutputStream."""
+        the ``encode(pcm, frame0, last[, lpc_order])`` of core.audio_processor.FlacStream (vv_pcm_flac, vv_pcm_flac_lpc), which sits behind
+        the OutputStream."""
         import numpy as np
 
         def up_(x):
@@ -1283,11 +1297,11 @@ class HipSynth:
                 return np.zeros(0, np.uint8)
             return self.pcm_encode(up_(y), [[0, y.size, 0]], encoding, n_y=y.size).cpu().numpy()
 
-        def flac(pcm, frame0, last):       # FlacStream's back end (N15): whole blocks (last = False) and the final short frame alike
+        def flac(pcm, frame0, last, lpc_order=0):      # FlacStream's back end (N15, N16): whole blocks (last = False) and the final short frame alike
             pcm = np.asarray(pcm, dtype=np.int16).reshape(-1)
             if pcm.size == 0:
                 return np.zeros(0, np.uint8)
-            y, info = self.pcm_flac(up_(pcm), [[0, pcm.size, int(frame0), 1 if last else 0]], sample_rate if rate is None else rate)
+            y, info = self.pcm_flac(up_(pcm), [[0, pcm.size, int(frame0), 1 if last else 0]], sample_rate if rate is None else rate, lpc_order)
             return y[: int(info[1, 0])].cpu().numpy()
 
         return (resample if rate is not None and int(rate) != int(sample_rate) else None), \
