@@ -730,6 +730,52 @@ VV_API uint64_t vv_pcm_flac_lpc_ws_bytes(int64_t total_frames, int R, int lpc_or
 VV_API int vv_pcm_flac_lpc(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
                            int lpc_order, uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ---- N17 FLAC input (RFC 9639): reference clips stored as FLAC become the interleaved PCM vv_ingest_pcm reads, on the
+ * device -- 1 ... 8 channels, 8 / 16 / 24 bits, constant / verbatim / Fixed 0 ... 4 / LPC 1 ... 32 subframes, wasted bits, residual methods 0
+ * and 1 with partition orders 0 ... 15 and escape partitions, fixed and variable blocking.  The recipe is pinned by core/audio_processor.py
+ * (flac_container, flac_frame_index, flac_decode), which the kernels equal sample for sample, and in reason code and byte for a refusal:
+ *   host     the container: optional ID3v2 tag, "fLaC", metadata blocks (STREAMINFO first; the rest skipped); one row per clip
+ *   chain    frame 0 starts at the clip's first byte, every next frame at the byte after the previous CRC-16; a sync code anywhere else
+ *            is not a frame.  total > 0: the chain ends when that many samples came (bytes behind are ignored) and must meet it exactly;
+ *            total = 0: the chain must end exactly at the clip's last byte
+ *   header   in this order: sync 0xFFF8 | blocking bit; reserved bit, block-size code 0, rate code 15, channel code > 10, depth code 3,
+ *            reserved bit (VV_FLAC_RESERVED); the coded number, 1 ... 7 bytes, syntax only; the 8- / 16-bit block size - 1 (65536 is
+ *            reserved); the 8- / 16-bit rate (kHz, Hz, tens of Hz); CRC-8 (poly 0x07); then channels, depth and rate equal to the row's,
+ *            the blocking bit equal to the clip's first, block <= max block (VV_FLAC_BAD_HEADER)
+ *   measure  per subframe: pad bit 0, type (0 constant, 1 verbatim, 8 ... 12 Fixed, 32 ... 63 LPC; others reserved), wasted flag and unary
+ *            count (wasted < depth), warm-up samples, LPC: precision - 1 (15 reserved), shift (5 bits signed, negative refused),
+ *            coefficients; residual: method (2, 3 reserved), partition order po with 2^po | block and block >> po >= order
+ *            (VV_FLAC_PARTITION), per partition a parameter of 4 / 5 bits (all ones = escape: 5 bits raw width, then raw samples) and Rice
+ *            codes (unary quotient, then the low bits).  Then zero bits to the byte and the CRC-16 (poly 0x8005).  Nothing at or past
+ *            min(clip end, frame start + vv_flac_decode_frame_bound) is read: VV_FLAC_OVERRUN / VV_FLAC_FRAME_TOO_LONG
+ *   restore  only after every clip's chain passed: prediction sums in 64 bits, arithmetic shift, + residual; each restored sample must
+ *            fit depth - wasted bits (VV_FLAC_RANGE; the side channel has one bit more), then << wasted
+ *   channels left/side, side/right, mid/side ((mid << 1 | side & 1) +- side) >> 1; 8 bits -> int8, 16 -> int16 LE, 24 -> int32 LE with the
+ *            sign pad in the lowest byte and the sample above it; a value outside the width wraps.  The MD5 is not verified.
+ * A refusal's byte is the first byte of the frame that holds the problem (chain: where the next frame was expected), from the clip's first.
+ *   data     the frame bytes of the R clips, each 4-byte aligned, 8 bytes of padding behind the last clip; 8-byte aligned
+ *   rows     R x 8 int64 on the device, rows_host the same on the host (checked before a launch): {byte offset, n_bytes, channels, bits,
+ *            min block, max block, rate, total samples (0 = unknown)}, ascending
+ *   info     R x 4 int64 (device): {status, byte, frames, samples}; the host reads it between the two calls
+ *   ws       ws_bytes >= vv_flac_index_ws_bytes(n_bytes, R); vv_flac_decode reads the frame table vv_flac_index left there
+ *   lay      R x 6 int64 (device, and lay_host): {pcm byte offset, frames, samples, frames in front, samples x channels in front, samples
+ *            in front}; a refused clip has frames = samples = 0
+ *   info2    R x 2 int64 (device): {status, byte} of the first frame that failed the range check
+ *   ws2      ws2_bytes >= vv_flac_decode_ws_bytes(sum of samples x channels, sum of frames)
+ * -22 and nothing launched: null or misaligned pointers, rows outside the buffers, R outside 1 ... 65535, a workspace too small,
+ * overlapping buffers.  No global atomics; the result does not depend on the batch. */
+#define VV_FLAC_MAX_CLIP 67108864
+enum { VV_FLAC_OK = 0, VV_FLAC_BAD_HEADER = 1, VV_FLAC_CRC8 = 2, VV_FLAC_CRC16 = 3, VV_FLAC_RESERVED = 4, VV_FLAC_PARTITION = 5, VV_FLAC_RANGE = 6,
+       VV_FLAC_OVERRUN = 7, VV_FLAC_CHAIN = 8, VV_FLAC_FRAME_TOO_LONG = 9, VV_FLAC_CLIP_TOO_LONG = 10 };
+VV_API uint64_t vv_flac_decode_frame_bound(int block, int channels, int bits);      /* 2 x the verbatim frame + 64; 0 for sizes out of range */
+VV_API uint64_t vv_flac_index_ws_bytes(int64_t n_bytes, int R);
+VV_API uint64_t vv_flac_decode_ws_bytes(int64_t plane_samples, int64_t total_frames);
+VV_API int vv_flac_index(vv_ctx* ctx, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, int64_t* info,
+                         void* ws, uint64_t ws_bytes, void* stream);
+VV_API int vv_flac_decode(vv_ctx* ctx, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, const int64_t* lay,
+                          const int64_t* lay_host, const void* ws, uint64_t ws_bytes, uint8_t* pcm, int64_t n_pcm, int64_t* info2, void* ws2,
+                          uint64_t ws2_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -530,6 +530,398 @@ def flac_encode_frames(pcm, sample_rate: int, frame0: int = 0, last: bool = True
     return np.frombuffer(b"".join(frames), np.uint8).copy(), min(map(len, frames)), max(map(len, frames))
 
 
+# ---------------------------------------------------------------------- N17: FLAC input (RFC 9639), the whole format at 8 / 16 / 24 bits
+# The arithmetic below IS the specification: csrc/vv_flac_decode.hip runs the same checks in the same order, so this
+# mirror and the device give the same samples for a valid stream and the same reason code and byte position for a malformed one.
+#   container : optional ID3v2 tag, ``fLaC``, metadata blocks (STREAMINFO first, once; every other block skipped by its length)
+#   chain     : frame 0 starts at the first byte after the metadata, every next frame at the byte after the previous CRC-16; a sync
+#               pattern anywhere else is not a frame.  A known total ends the chain (bytes behind it are ignored) and must be met
+#               exactly; with total 0 the chain must end exactly at the end of the data
+#   header    : checked in this order -- sync, reserved bits and codes, syntax of the coded number (1 ... 7 bytes, its value is ignored),
+#               the optional block-size / rate fields, CRC-8, then agreement with STREAMINFO (channels, depth, rate, block <= max block)
+#               and with the first frame's blocking bit
+#   measure   : the subframes are walked without restoring them (types, wasted bits, orders, precision, shift, partitions, Rice codes),
+#               then zero padding to the byte and the CRC-16.  The walk reads nothing at or past min(end of data, frame start +
+#               flac_decode_frame_bound): a read across that limit gives zeros and ends the frame with "overrun" (the data ended) or
+#               "frame too long" (the bound did)
+#   restore   : after EVERY frame of the chain has passed the above: 64-bit sums, arithmetic shift, every restored sample must fit its
+#               subframe's depth less the wasted bits ("sample out of range"), then the wasted bits are shifted back
+#   channels  : left/side, side/right, mid/side in integers; a result wraps to the stream's width as an integer cast does
+# A refusal's position is the first byte of the frame that holds the problem (for a chain problem: where the next frame was expected).
+# The MD5 of STREAMINFO is not verified.
+FLAC_MAX_CLIP = 1 << 26              # VV_FLAC_MAX_CLIP: samples per channel of one decoded clip
+
+
+class FlacStatus:
+    """Reason codes of a refused FLAC stream: one enum for this mirror and csrc/vv_flac_decode.hip (VV_FLAC_* in include/vvtts.h)."""
+    OK, BAD_HEADER, CRC8, CRC16, RESERVED, PARTITION, RANGE, OVERRUN, CHAIN, FRAME_TOO_LONG, CLIP_TOO_LONG = range(11)
+    NAMES = ("ok", "bad header", "header CRC-8 mismatch", "frame CRC-16 mismatch", "reserved code", "partition misfit",
+             "sample out of range", "overrun", "chain / total mismatch", "frame too long", "clip too long")
+
+
+class FlacError(ValueError):
+    """``malformed FLAC: <reason> at byte <position>``; ``code`` is a FlacStatus, ``position`` a byte offset into the data given."""
+
+    def __init__(self, code: int, position: int, detail: str = ""):
+        self.code, self.position = int(code), int(position)
+        super().__init__(f"malformed FLAC: {detail or FlacStatus.NAMES[self.code]} at byte {self.position}")
+
+
+class FlacInfo(NamedTuple):
+    min_block: int
+    max_block: int
+    rate: int
+    channels: int
+    bits: int
+    total: int                       # samples per channel, 0 = unknown
+    start: int                       # the byte at which the frames start
+
+
+def flac_container(data: bytes) -> FlacInfo:
+    """Byte parsing only: ID3v2 tag (skipped by its sync-safe size), ``fLaC``, the metadata blocks.  The MD5 is not read."""
+    data, pos = bytes(data), 0
+    if data[:3] == b"ID3":
+        if len(data) < 10 or any(b & 0x80 for b in data[6:10]):
+            raise FlacError(FlacStatus.BAD_HEADER, 0, "truncated or malformed ID3v2 tag")
+        pos = 10 + ((data[6] << 21) | (data[7] << 14) | (data[8] << 7) | data[9]) + (10 if data[5] & 0x10 else 0)
+    if data[pos:pos + 4] != b"fLaC":
+        raise FlacError(FlacStatus.BAD_HEADER, pos, "no fLaC marker")
+    pos, info, last = pos + 4, None, False
+    while not last:
+        if pos + 4 > len(data):
+            raise FlacError(FlacStatus.BAD_HEADER, pos, "truncated metadata block")
+        last, kind, size = bool(data[pos] & 0x80), data[pos] & 0x7F, int.from_bytes(data[pos + 1:pos + 4], "big")
+        if pos + 4 + size > len(data):
+            raise FlacError(FlacStatus.BAD_HEADER, pos, "truncated metadata block")
+        if (kind == 0) != (info is None) or (kind == 0 and size != 34):
+            raise FlacError(FlacStatus.BAD_HEADER, pos, "STREAMINFO must be the first metadata block, 34 bytes, once")
+        if kind == 0:
+            b = data[pos + 4:pos + 38]
+            packed = int.from_bytes(b[10:18], "big")
+            info = (int.from_bytes(b[0:2], "big"), int.from_bytes(b[2:4], "big"), packed >> 44, ((packed >> 41) & 7) + 1,
+                    ((packed >> 36) & 31) + 1, packed & ((1 << 36) - 1), pos)
+        pos += 4 + size
+    lo, hi, rate, ch, bits, total, at = info
+    if rate == 0:
+        raise FlacError(FlacStatus.BAD_HEADER, at, "sample rate 0")
+    if bits not in (8, 16, 24):
+        raise FlacError(FlacStatus.BAD_HEADER, at, f"{bits} bits per sample (8, 16 and 24 are decoded)")
+    if lo > hi or hi < 16:
+        raise FlacError(FlacStatus.BAD_HEADER, at, "block sizes (min <= max, max >= 16)")
+    if total > FLAC_MAX_CLIP:
+        raise FlacError(FlacStatus.CLIP_TOO_LONG, at)
+    return FlacInfo(lo, hi, rate, ch, bits, total, pos)
+
+
+def flac_decode_frame_bound(block: int, channels: int, bits: int) -> int:
+    """vv_flac_decode_frame_bound: the longest frame the decoder follows -- twice the verbatim frame (16 header bytes, per channel a
+    subframe header and ``block`` samples of bits + 1, CRC-16) plus 64.  No encoder emits more than verbatim."""
+    return 2 * (16 + int(channels) * (2 + (int(block) * (int(bits) + 1) + 7) // 8) + 2) + 64
+
+
+_FLAC_DEPTH_OF_CODE = {1: 8, 2: 12, 4: 16, 5: 20, 6: 24, 7: 32}
+_FLAC_RATE_OF_CODE = {v: k for k, v in _FLAC_RATE_CODE.items()}
+_FLAC_FIXED = ((), (1,), (2, -1), (3, -3, 1), (4, -6, 4, -1))
+
+
+def _flac_header(data: bytes, p: int, end: int, info: FlacInfo, blocking: int):
+    """The frame header expected at byte p: -> (status, header bytes with the CRC-8, block size, channel assignment code)."""
+    S = FlacStatus
+    if p + 4 > end:
+        return S.OVERRUN, 0, 0, 0
+    b1, b2, b3 = data[p + 1], data[p + 2], data[p + 3]
+    if data[p] != 0xFF or (b1 & 0xFC) != 0xF8:
+        return S.BAD_HEADER, 0, 0, 0
+    bsc, rc, cc, dc = b2 >> 4, b2 & 15, b3 >> 4, (b3 >> 1) & 7
+    if (b1 & 2) or bsc == 0 or rc == 15 or cc > 10 or dc == 3 or (b3 & 1):
+        return S.RESERVED, 0, 0, 0
+    q = p + 4
+    if q + 1 > end:
+        return S.OVERRUN, 0, 0, 0
+    lead, n = data[q], 0
+    while n < 8 and lead & (0x80 >> n):
+        n += 1
+    if n == 1 or n == 8:
+        return S.BAD_HEADER, 0, 0, 0
+    n = max(n, 1)
+    if q + n > end:
+        return S.OVERRUN, 0, 0, 0
+    if any((data[q + i] & 0xC0) != 0x80 for i in range(1, n)):
+        return S.BAD_HEADER, 0, 0, 0
+    q += n
+    extra = 1 if bsc == 6 else 2 if bsc == 7 else 0
+    if q + extra > end:
+        return S.OVERRUN, 0, 0, 0
+    v = int.from_bytes(data[q:q + extra], "big")
+    q += extra
+    if bsc == 7 and v == 65535:
+        return S.RESERVED, 0, 0, 0
+    bs = 192 if bsc == 1 else 576 << (bsc - 2) if bsc <= 5 else v + 1 if bsc <= 7 else 256 << (bsc - 8)
+    extra = 1 if rc == 12 else 2 if rc in (13, 14) else 0
+    if q + extra > end:
+        return S.OVERRUN, 0, 0, 0
+    v = int.from_bytes(data[q:q + extra], "big")
+    q += extra
+    rate = info.rate if rc == 0 else v * 1000 if rc == 12 else v if rc == 13 else v * 10 if rc == 14 else _FLAC_RATE_OF_CODE[rc]
+    if q + 1 > end:
+        return S.OVERRUN, 0, 0, 0
+    if flac_crc8(data[p:q]) != data[q]:
+        return S.CRC8, 0, 0, 0
+    if ((cc + 1 if cc < 8 else 2) != info.channels or (dc and _FLAC_DEPTH_OF_CODE[dc] != info.bits) or rate != info.rate
+            or (b1 & 1) != blocking or bs > info.max_block):
+        return S.BAD_HEADER, 0, 0, 0
+    return S.OK, q + 1 - p, bs, cc
+
+
+class _FlacBits:
+    """The bit reader both sides share: nothing at or past ``limit`` (in bits) is read; a read across it gives zeros and sets ``over``."""
+
+    def __init__(self, data: bytes, pos: int, limit: int):
+        self.data, self.pos, self.limit, self.over = data, pos, limit, False
+
+    def take(self, n: int) -> int:                     # n <= 32
+        pos = self.pos
+        self.pos = pos + n
+        if pos + n > self.limit:
+            self.over = True
+            return 0
+        if n == 0:
+            return 0
+        hi = (pos + n + 7) >> 3
+        return (int.from_bytes(self.data[pos >> 3:hi], "big") >> (8 * hi - pos - n)) & ((1 << n) - 1)
+
+    def signed(self, n: int) -> int:
+        v = self.take(n)
+        return v - (1 << n) if n and v >> (n - 1) else v
+
+    def skip(self, n: int):
+        self.pos += n
+        if self.pos > self.limit:
+            self.over = True
+
+    def unary(self) -> int:
+        n = 0
+        while True:
+            avail = min(32, self.limit - self.pos)
+            if avail <= 0:
+                self.over = True
+                return n
+            pos = self.pos
+            hi = (pos + avail + 7) >> 3
+            v = (int.from_bytes(self.data[pos >> 3:hi], "big") >> (8 * hi - pos - avail)) & ((1 << avail) - 1)
+            if v:
+                lz = avail - v.bit_length()
+                self.pos = pos + lz + 1
+                return n + lz
+            n += avail
+            self.pos = pos + avail
+
+
+def _flac_subframe(r: _FlacBits, bs: int, depth: int, restore: bool):
+    """One subframe at the reader's position.  restore = False: walk it (-> status, None); True: restore it (-> status, samples)."""
+    S = FlacStatus
+    h = r.take(8)
+    if r.over:
+        return S.OVERRUN, None
+    if h & 0x80:
+        return S.RESERVED, None
+    t, w = (h >> 1) & 63, 0
+    if h & 1:
+        w = r.unary() + 1
+        if r.over:
+            return S.OVERRUN, None
+    if w >= depth:
+        return S.RESERVED, None
+    de, out = depth - w, None
+    lo, hi = -(1 << (de - 1)), (1 << (de - 1)) - 1
+    if t == 0:
+        if restore:
+            out = [r.signed(de)] * bs
+        else:
+            r.skip(de)
+    elif t == 1:
+        if restore:
+            out = [r.signed(de) for _ in range(bs)]
+        else:
+            r.skip(de * bs)
+    elif 8 <= t <= 12 or t >= 32:
+        lpc = t >= 32
+        o = (t & 31) + 1 if lpc else t - 8
+        if o > bs:
+            return S.PARTITION, None
+        if restore:
+            out = [r.signed(de) for _ in range(o)]
+        else:
+            r.skip(o * de)
+        if r.over:
+            return S.OVERRUN, None
+        coef, shift = _FLAC_FIXED[0 if lpc else o], 0
+        if lpc:
+            pq = r.take(9)
+            if r.over:
+                return S.OVERRUN, None
+            prec, shift = (pq >> 5) + 1, pq & 15
+            if prec == 16 or pq & 16:
+                return S.RESERVED, None
+            if restore:
+                coef = [r.signed(prec) for _ in range(o)]
+            else:
+                r.skip(o * prec)
+            if r.over:
+                return S.OVERRUN, None
+        m = r.take(6)
+        if r.over:
+            return S.OVERRUN, None
+        method, po = m >> 4, m & 15
+        if method > 1:
+            return S.RESERVED, None
+        if bs & ((1 << po) - 1) or (bs >> po) < o:
+            return S.PARTITION, None
+        pb = 4 + method
+        for part in range(1 << po):
+            n = (bs >> po) - (o if part == 0 else 0)
+            k = r.take(pb)
+            if r.over:
+                return S.OVERRUN, None
+            raw = -1
+            if k == (1 << pb) - 1:
+                raw = r.take(5)
+                if r.over:
+                    return S.OVERRUN, None
+                if not restore:
+                    r.skip(n * raw)
+                    n = 0
+            for _ in range(n):
+                if raw >= 0:
+                    res = r.signed(raw)
+                else:
+                    u = r.unary()
+                    if restore:
+                        u = (u << k) | r.take(k)
+                        res = (u >> 1) ^ -(u & 1)
+                    else:
+                        r.skip(k)
+                if r.over:
+                    return S.OVERRUN, None
+                if restore:
+                    i, pred = len(out), 0
+                    for j, c in enumerate(coef):
+                        pred += c * out[i - 1 - j]
+                    v = (pred >> shift) + res
+                    if v < lo or v > hi:
+                        return S.RANGE, None
+                    out.append(v)
+            if r.over:
+                return S.OVERRUN, None
+    else:
+        return S.RESERVED, None
+    if r.over:
+        return S.OVERRUN, None
+    if restore and w:
+        out = [v << w for v in out]
+    return S.OK, out
+
+
+def _flac_depth(info: FlacInfo, assign: int, c: int) -> int:
+    return info.bits + (1 if (assign == 8 and c == 1) or (assign == 9 and c == 0) or (assign == 10 and c == 1) else 0)
+
+
+def _flac_measure(data: bytes, p: int, end: int, info: FlacInfo, hlen: int, bs: int, assign: int):
+    """The frame at byte p behind its header: -> (status, the byte after its CRC-16, the subframes' first bits counted from p)."""
+    S = FlacStatus
+    bound = p + flac_decode_frame_bound(bs, info.channels, info.bits)
+    over = S.FRAME_TOO_LONG if bound <= end else S.OVERRUN
+    r = _FlacBits(data, 8 * (p + hlen), 8 * min(bound, end))
+    subs = []
+    for c in range(info.channels):
+        subs.append(r.pos - 8 * p)
+        st, _ = _flac_subframe(r, bs, _flac_depth(info, assign, c), False)
+        if st:
+            return (over if st == S.OVERRUN else st), 0, subs
+    pad = r.take(-r.pos % 8)
+    if r.over:
+        return over, 0, subs
+    if pad:
+        return S.RESERVED, 0, subs
+    crc = r.take(16)
+    if r.over:
+        return over, 0, subs
+    e = r.pos >> 3
+    if flac_crc16(data[p:e - 2]) != crc:
+        return S.CRC16, 0, subs
+    return S.OK, e, subs
+
+
+def flac_frame_index(data: bytes, info: FlacInfo):
+    """The chain of frames: -> [(byte, block size, channel assignment, subframe bits)], samples per channel.  Raises FlacError."""
+    S = FlacStatus
+    data, p, end, samples, frames = bytes(data), info.start, len(data), 0, []
+    blocking = data[p + 1] & 1 if p + 1 < end else 0
+    while not (info.total and samples == info.total):
+        if p == end:
+            if info.total:
+                raise FlacError(S.CHAIN, p)
+            break
+        st, hlen, bs, assign = _flac_header(data, p, end, info, blocking)
+        if st:
+            raise FlacError(st, p)
+        st, e, subs = _flac_measure(data, p, end, info, hlen, bs, assign)
+        if st:
+            raise FlacError(st, p)
+        if samples + bs > FLAC_MAX_CLIP:
+            raise FlacError(S.CLIP_TOO_LONG, p)
+        if info.total and samples + bs > info.total:
+            raise FlacError(S.CHAIN, p)
+        frames.append((p, bs, assign, subs))
+        samples += bs
+        p = e
+    return frames, samples
+
+
+def flac_pcm_layout(planes: np.ndarray, bits: int) -> np.ndarray:
+    """(n, channels) int64 samples of ``bits`` -> what ``_decode_wav`` holds for the same PCM: int8, int16, or int32 with the sample in
+    the upper three bytes and the sign pad in the lowest.  A value outside the depth wraps, as an integer cast does."""
+    if bits == 8:
+        return planes.astype(np.int8)
+    if bits == 16:
+        return planes.astype(np.int16)
+    v = planes & 0xFFFFFF
+    return ((v << 8) | np.where(v & 0x800000, 0xFF, 0)).astype(np.uint32).view(np.int32)
+
+
+def flac_decode(data: bytes) -> Tuple[np.ndarray, int, int]:
+    """FLAC bytes -> (frames (n, channels) int8 | int16 | int32, sample width in bytes, rate): the triple ``_decode_wav`` gives for the
+    WAV of the same PCM, so that decode(flac of x) == decode(wav of x) element for element.  The specification of vv_flac_index /
+    vv_flac_decode, in Python integers.  The MD5 of STREAMINFO is NOT verified.  What pydub + ffmpeg would hold for a
+    24-bit FLAC cannot be pinned offline (as for 24-bit WAV: the module docstring).  Raises FlacError (a ValueError)."""
+    data = bytes(data)
+    info = flac_container(data)
+    frames, samples = flac_frame_index(data, info)
+    out = np.zeros((samples, info.channels), np.int64)
+    at = 0
+    for p, bs, assign, subs in frames:
+        ch = []
+        for c in range(info.channels):
+            st, x = _flac_subframe(_FlacBits(data, 8 * p + subs[c], 8 * len(data)), bs, _flac_depth(info, assign, c), True)
+            if st:
+                raise FlacError(st, p)
+            ch.append(np.array(x, np.int64))
+        if assign == 8:
+            ch[1] = ch[0] - ch[1]
+        elif assign == 9:
+            ch[0] = ch[0] + ch[1]
+        elif assign == 10:
+            mid = (ch[0] << 1) | (ch[1] & 1)
+            ch[0], ch[1] = (mid + ch[1]) >> 1, (mid - ch[1]) >> 1
+        out[at:at + bs] = np.stack(ch, axis=1)
+        at += bs
+    return np.ascontiguousarray(flac_pcm_layout(out, info.bits)), {8: 1, 16: 2, 24: 4}[info.bits], info.rate
+
+
+def is_flac(data: bytes) -> bool:
+    return data[:4] == b"fLaC" or data[:3] == b"ID3"
+
+
 # ---------------------------------------------------------------------- N12: loudness normalisation (ITU-R BS.1770-4 integrated, gated)
 # The arithmetic below IS the specification (DESIGN §8 N12): the device kernels (csrc/vv_loudness.hip) compute the same float64
 # operations in the same order, so this mirror and the device agree bit for bit, and so does a request alone or in a batch.
@@ -990,11 +1382,21 @@ class AudioProcessor:
     @staticmethod
     def decode(path_or_bytes: Union[str, bytes]) -> Tuple[np.ndarray, int, int]:
         """-> (integer frames (n, channels), sample width, rate); container parsing only, no arithmetic on samples."""
-        return _decode_wav(AudioProcessor._read_bytes(path_or_bytes))
+        data = AudioProcessor._read_bytes(path_or_bytes)
+        if data[:4] != b"RIFF" and is_flac(data):          # N17: ``fLaC``, or an ID3v2 tag in front of it
+            return flac_decode(data)
+        if data[:4] != b"RIFF":
+            raise ValueError("unsupported audio container: only RIFF/WAVE and FLAC can be decoded in this build (no ffmpeg)")
+        return _decode_wav(data)
 
     @staticmethod
     def probe_duration(path_or_bytes: Union[str, bytes]) -> float:
-        frames, _w, rate = AudioProcessor.decode(path_or_bytes)
+        data = AudioProcessor._read_bytes(path_or_bytes)
+        if data[:4] != b"RIFF" and is_flac(data):          # a FLAC with a known total: STREAMINFO alone, nothing is decoded
+            info = flac_container(data)
+            if info.total:
+                return info.total / float(info.rate)
+        frames, _w, rate = AudioProcessor.decode(data)
         return frames.shape[0] / float(rate)
 
     @staticmethod

@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.9 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.10 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -853,6 +853,98 @@ int vv_pcm_flac_lpc(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* row
     if (lpc_order < 1 || lpc_order > VV_FLAC_MAX_LPC_ORDER)
         return c->fail(-22, "vv_pcm_flac_lpc: lpc_order in 1 ... %d is needed (vv_pcm_flac is the encoder without LPC)", VV_FLAC_MAX_LPC_ORDER);
     return pcm_flac(c, "vv_pcm_flac_lpc", x, n_x, rows, rows_host, R, sample_rate, lpc_order, y, n_y, info, ws, ws_bytes, stream);
+}
+
+// N17: FLAC input.  The rows come in host memory too: everything the host can see is checked before a launch; a refused call launches
+// nothing.  What the bytes of the streams say is the kernels' business (csrc/vv_flac_decode.hip: every read bounded).
+uint64_t vv_flac_decode_frame_bound(int block, int channels, int bits) {
+    return bits != 8 && bits != 16 && bits != 24 ? 0 : vvk_flac_decode_frame_bound(block, channels, bits);
+}
+
+uint64_t vv_flac_index_ws_bytes(int64_t n_bytes, int R) { return vvk_flac_index_ws_bytes((long long)n_bytes, R); }
+
+uint64_t vv_flac_decode_ws_bytes(int64_t plane_samples, int64_t total_frames) { return vvk_flac_decode_ws_bytes((long long)plane_samples, (long long)total_frames); }
+
+static bool spans_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
+// the rows of both calls: ascending, 4-byte aligned, 8 bytes of padding behind the last; -> 0 or the refusal
+static int flac_rows(vv_ctx* c, const char* name, const int64_t* rows, const int64_t* rows_host, int R, int64_t n_bytes, int* max_channels) {
+    if (R < 1 || R > 65535 || n_bytes < 8 || n_bytes > ((int64_t)1 << 31) - 64)
+        return c->fail(-22, "%s: bad sizes (1 <= R <= 65535, 8 <= n_bytes <= 2^31 - 64)", name);
+    if (!rows || !rows_host) return c->fail(-22, "%s: null pointer (rows, rows_host)", name);
+    if ((uintptr_t)rows % 8 || (uintptr_t)rows_host % 8) return c->fail(-22, "%s: misaligned pointer (rows, rows_host: 8 bytes)", name);
+    int64_t at = 0;
+    *max_channels = 1;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 8 * (size_t)r;
+        if (q[0] < at || q[0] % 4 || q[1] < 0 || q[1] > n_bytes - 8 || q[0] > n_bytes - 8 - q[1])
+            return c->fail(-22, "%s: row %d: the clips lie in ascending order, 4-byte aligned, inside data less 8 bytes of padding", name, r);
+        if (q[2] < 1 || q[2] > 8 || (q[3] != 8 && q[3] != 16 && q[3] != 24) || q[5] < 16 || q[5] > 65535 || q[4] < 0 || q[4] > q[5] || q[6] < 1 ||
+            q[6] > 1048575 || q[7] < 0 || q[7] > VV_FLAC_MAX_CLIP)
+            return c->fail(-22, "%s: row %d: channels 1 ... 8, bits 8 / 16 / 24, 16 <= max block <= 65535, min <= max, rate 1 ... 1048575, total <= 2^26", name, r);
+        at = q[0] + q[1];
+        if (q[2] > *max_channels) *max_channels = (int)q[2];
+    }
+    return 0;
+}
+
+int vv_flac_index(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, int64_t* info, void* ws,
+                  uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    int maxch = 1;
+    if (int e = flac_rows(c, "vv_flac_index", rows, rows_host, R, n_bytes, &maxch)) return e;
+    if (!data || !info || !ws) return c->fail(-22, "vv_flac_index: null pointer (data, info, ws)");
+    if ((uintptr_t)data % 8 || (uintptr_t)info % 8 || (uintptr_t)ws % 8) return c->fail(-22, "vv_flac_index: misaligned pointer (data, info, ws: 8 bytes)");
+    const uint64_t need = vvk_flac_index_ws_bytes((long long)n_bytes, R);
+    if (ws_bytes < need) return c->fail(-22, "vv_flac_index: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes, (unsigned long long)need);
+    if (spans_overlap(data, (uint64_t)n_bytes, ws, ws_bytes) || spans_overlap(info, 32ull * R, ws, ws_bytes) || spans_overlap(data, (uint64_t)n_bytes, info, 32ull * R))
+        return c->fail(-22, "vv_flac_index: data, info and ws overlap");
+    Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * (double)n_bytes, st);
+    KCHK(c, vvk_flac_index(data, (long long)n_bytes, (const long long*)rows, R, (long long*)info, ws, st, &m__));
+    return 0;
+}
+
+int vv_flac_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, const int64_t* lay,
+                   const int64_t* lay_host, const void* ws, uint64_t ws_bytes, uint8_t* pcm, int64_t n_pcm, int64_t* info2, void* ws2, uint64_t ws2_bytes,
+                   void* stream) {
+    if (!c) return -22;
+    hipSetDevice(c->device);
+    hipStream_t st = (hipStream_t)stream;
+    int maxch = 1;
+    if (int e = flac_rows(c, "vv_flac_decode", rows, rows_host, R, n_bytes, &maxch)) return e;
+    if (!data || !lay || !lay_host || !ws || !pcm || !info2 || !ws2 || n_pcm < 0)
+        return c->fail(-22, "vv_flac_decode: null pointer (data, lay, lay_host, ws, pcm, info2, ws2)");
+    if ((uintptr_t)data % 8 || (uintptr_t)lay % 8 || (uintptr_t)lay_host % 8 || (uintptr_t)ws % 8 || (uintptr_t)info2 % 8 || (uintptr_t)ws2 % 8)
+        return c->fail(-22, "vv_flac_decode: misaligned pointer (data, lay, lay_host, ws, info2, ws2: 8 bytes)");
+    int64_t F = 0, S = 0, P = 0, at = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* l = lay_host + 6 * (size_t)r;
+        const int64_t* q = rows_host + 8 * (size_t)r;
+        const int64_t width = q[3] == 24 ? 4 : q[3] / 8;
+        if (l[1] < 0 || l[2] < 0 || l[2] > VV_FLAC_MAX_CLIP || l[1] > l[2] || l[1] > q[1] || l[3] != F || l[4] != P || l[5] != S)
+            return c->fail(-22, "vv_flac_decode: lay row %d: frames <= samples <= 2^26 and the three prefix sums are needed", r);
+        const int64_t bytes = l[2] * q[2] * width;
+        if (l[0] < at || l[0] > n_pcm - bytes) return c->fail(-22, "vv_flac_decode: lay row %d does not fit the %lld bytes of pcm, in ascending order", r, (long long)n_pcm);
+        at = l[0] + bytes;
+        F += l[1]; S += l[2]; P += l[2] * q[2];
+    }
+    const uint64_t need = vvk_flac_index_ws_bytes((long long)n_bytes, R), need2 = vvk_flac_decode_ws_bytes((long long)P, (long long)F);
+    if (ws_bytes < need || ws2_bytes < need2)
+        return c->fail(-22, "vv_flac_decode: ws of %llu bytes (%llu needed), ws2 of %llu (%llu needed)", (unsigned long long)ws_bytes, (unsigned long long)need,
+                       (unsigned long long)ws2_bytes, (unsigned long long)need2);
+    const void* span[5] = {data, ws, pcm, info2, ws2};
+    const uint64_t len[5] = {(uint64_t)n_bytes, ws_bytes, (uint64_t)n_pcm, 16ull * R, ws2_bytes};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (len[i] && len[j] && spans_overlap(span[i], len[i], span[j], len[j])) return c->fail(-22, "vv_flac_decode: data, ws, pcm, info2 and ws2 overlap");
+    Prof p(c, VV_PROF_ELEMWISE, 40.0 * (double)P, 2.0 * (double)n_bytes + 8.0 * (double)P + (double)n_pcm, st);
+    KCHK(c, vvk_flac_decode(data, (long long)n_bytes, (const long long*)rows, R, (const long long*)lay, (long long)F, (long long)S, (long long)P, maxch,
+                            (void*)ws, pcm, (long long)n_pcm, (long long*)info2, ws2, st, &m__));
+    return 0;
 }
 
 // --------------------------------------------------------------------------- transformer steps

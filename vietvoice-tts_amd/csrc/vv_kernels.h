@@ -105,6 +105,16 @@ unsigned long long vvk_pcm_flac_ws_bytes(long long total_frames, int R);
 unsigned long long vvk_pcm_flac_lpc_ws_bytes(long long total_frames, int R);
 int vvk_pcm_flac(const int16_t* x, long long n_x, const long long* rows, int R, int rate, int lpc_order, long long total_frames, long long max_frames,
                  uint8_t* y, long long n_y, long long* info, void* ws, hipStream_t st, const char** err);
+// N17 FLAC input (vv_flac_decode.hip): candidate scan, per-candidate measure, per-clip chain; then restore, verdict, interleave.
+// rows R x 8 {byte offset, n_bytes, channels, bits, min block, max block, rate, total}; lay R x 6 {pcm byte offset, frames, samples, frames in
+// front, plane samples in front, samples in front}
+unsigned long long vvk_flac_decode_frame_bound(int block, int channels, int bits);
+unsigned long long vvk_flac_index_ws_bytes(long long n_bytes, int R);
+unsigned long long vvk_flac_decode_ws_bytes(long long n_plane, long long total_frames);
+int vvk_flac_index(const uint8_t* data, long long n_bytes, const long long* rows, int R, long long* info, void* ws, hipStream_t st, const char** err);
+int vvk_flac_decode(const uint8_t* data, long long n_bytes, const long long* rows, int R, const long long* lay, long long total_frames,
+                    long long total_samples, long long n_plane, int max_channels, void* ws, uint8_t* pcm, long long n_pcm, long long* info2, void* ws2,
+                    hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

@@ -217,6 +217,12 @@ EXPORTS = {
                                   C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_pcm_flac": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                               C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_flac_decode_frame_bound": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
+    "vv_flac_index_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
+    "vv_flac_decode_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int64]),
+    "vv_flac_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_flac_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_pcm_stretch_ws_bytes": (C.c_uint64, [C.c_int]),
     "vv_pcm_stretch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                  C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
@@ -1176,6 +1182,129 @@ class HipSynth:
                 self._check(self.lib.vv_pcm_flac(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), y.data_ptr(), n_y,
                                                  info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
         return y, info
+
+    # ------------------------------------------------------------------ FLAC input (N17)
+    @staticmethod
+    def _flac_rows(rows, n_bytes: int, name: str):
+        from .core.audio_processor import FLAC_MAX_CLIP
+        rows = [[int(v) for v in r] for r in rows]
+        if not rows or any(len(r) != 8 for r in rows) or len(rows) > 65535:
+            raise ValueError(f"{name}: 1 to 65535 rows of 8 entries {{byte offset, n_bytes, channels, bits, min block, max block, rate, total}}")
+        at = 0
+        for r in rows:
+            off, n, ch, bits, lo, hi, rate, total = r
+            if (off < at or off % 4 or n < 0 or off + n + 8 > n_bytes or not 1 <= ch <= 8 or bits not in (8, 16, 24) or not 16 <= hi <= 65535
+                    or not 0 <= lo <= hi or not 1 <= rate <= 1048575 or not 0 <= total <= FLAC_MAX_CLIP):
+                raise ValueError(f"{name}: row {r} does not fit the {n_bytes} bytes of data (ascending, 4-byte aligned, 8 bytes of padding behind "
+                                 f"the last clip) or the decoder's limits")
+            at = off + n
+        return rows
+
+    def flac_index(self, data: torch.Tensor, rows):
+        """vv_flac_index: the frames of R FLAC clips whose frame bytes lie back to back in ``data`` (uint8 on the device,
+        each clip 4-byte aligned, 8 bytes of padding behind the last).  rows = HOST rows {byte offset, n_bytes, channels, bits, min block,
+        max block, rate, total}.  -> (info R x 4 int64 on the device {status, byte, frames, samples}, the workspace flac_decode consumes).
+        The rows are validated here before anything is launched; the call never synchronises."""
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
+        n_bytes = data.numel()
+        if not 8 <= n_bytes <= (1 << 31) - 64 or data.data_ptr() % 8:
+            raise ValueError("flac_index: 8 ... 2^31 - 64 bytes of data, 8-byte aligned")
+        rows = self._flac_rows(rows, n_bytes, "flac_index")
+        R = len(rows)
+        rows_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8)
+        rows_d = rows_h.to(self.device)
+        info = torch.empty((R, 4), dtype=torch.int64, device=self.device)
+        ws = torch.empty((int(self.lib.vv_flac_index_ws_bytes(n_bytes, R)) // 8 + 1,), dtype=torch.int64, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_flac_index(self.ctx, data.data_ptr(), n_bytes, rows_d.data_ptr(), rows_h.data_ptr(), R, info.data_ptr(),
+                                               ws.data_ptr(), ws.numel() * 8, self._stream()))
+        return info, (ws, rows_h, rows_d)
+
+    def flac_decode(self, data: torch.Tensor, index, lay, pcm: torch.Tensor):
+        """vv_flac_decode: the clips ``flac_index`` passed, into ``pcm`` (uint8 on the device) as the interleaved little-endian PCM
+        vv_ingest_pcm reads.  index = flac_index's second result; lay = HOST rows {pcm byte offset, frames, samples} per clip (a refused
+        clip: frames = samples = 0).  -> info2 R x 2 int64 on the device {status, byte}: non-zero where a restored sample left its range."""
+        ws, rows_h, rows_d = index
+        assert data.is_cuda and data.dtype == torch.uint8 and pcm.is_cuda and pcm.dtype == torch.uint8 and pcm.is_contiguous() and pcm.dim() == 1
+        R, n_pcm = rows_h.shape[0], pcm.numel()
+        lay = [[int(v) for v in r] for r in lay]
+        if len(lay) != R or any(len(r) != 3 for r in lay):
+            raise ValueError("flac_decode: one row {pcm byte offset, frames, samples} per clip")
+        full, F, S, P, at = [], 0, 0, 0, 0
+        for (off, frames, samples), row in zip(lay, rows_h.tolist()):
+            nbytes = samples * row[2] * (4 if row[3] == 24 else row[3] // 8)
+            if off < at or frames < 0 or samples < frames or off + nbytes > n_pcm:
+                raise ValueError(f"flac_decode: row {[off, frames, samples]} does not fit the {n_pcm} bytes of pcm, in ascending order")
+            full.append([off, frames, samples, F, P, S])
+            at, F, S, P = off + nbytes, F + frames, S + samples, P + samples * row[2]
+        lay_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 6)
+        lay_d = lay_h.to(self.device)
+        info2 = torch.empty((R, 2), dtype=torch.int64, device=self.device)
+        ws2 = torch.empty((int(self.lib.vv_flac_decode_ws_bytes(P, F)) // 8 + 1,), dtype=torch.int64, device=self.device)
+        with self._lock, torch.cuda.device(self.device):
+            self._check(self.lib.vv_flac_decode(self.ctx, data.data_ptr(), data.numel(), rows_d.data_ptr(), rows_h.data_ptr(), R, lay_d.data_ptr(),
+                                                lay_h.data_ptr(), ws.data_ptr(), ws.numel() * 8, pcm.data_ptr(), n_pcm, info2.data_ptr(),
+                                                ws2.data_ptr(), ws2.numel() * 8, self._stream()))
+        return info2
+
+    def flac_clips(self, files, pcm: Optional[torch.Tensor] = None, pcm_offsets=None):
+        """Complete FLAC files (bytes) -> their PCM on the device, without a decoded sample crossing the bus: container parsing on the
+        host, one upload of the frame bytes, flac_index, ONE small readback of info (32 R bytes, the synchronisation), flac_decode, one
+        small readback of info2.  -> (pcm uint8 on the device, [per file: (byte offset, frames, width, rate, channels) or the FlacError
+        the mirror would raise]).  A refused file does not disturb the others.  With ``pcm`` / ``pcm_offsets`` None the buffer is laid
+        out here (4-byte aligned clips); else ``pcm_offsets(sizes) -> (buffer, offsets)`` lets the caller place the clips in a buffer
+        it shares with other PCM."""
+        from .core.audio_processor import FlacError, flac_container
+        infos, parts, rows, pos = [], [], [], 0
+        for data in files:
+            data = bytes(data)
+            try:
+                fi = flac_container(data)
+            except FlacError as e:
+                infos.append(e)
+                continue
+            infos.append(fi)
+            body = data[fi.start:]
+            rows.append([pos, len(body), fi.channels, fi.bits, fi.min_block, fi.max_block, fi.rate, fi.total])
+            parts.append(body + b"\0" * (-len(body) % 4))
+            pos += len(parts[-1])
+        live = [i for i, fi in enumerate(infos) if not isinstance(fi, FlacError)]
+        out, sizes, lay = list(infos), [0] * len(files), []
+        if live:
+            buf = torch.frombuffer(bytearray(b"".join(parts) + b"\0" * (-pos % 8 + 8)), dtype=torch.uint8).to(self.device)
+            info_d, index = self.flac_index(buf, rows)
+            info = info_d.cpu().tolist()                          # the one synchronisation in front of the layout
+            for i, (status, byte, frames, samples), row in zip(live, info, rows):
+                if status:
+                    out[i] = FlacError(status, infos[i].start + byte)
+                    lay.append([0, 0])
+                else:
+                    sizes[i] = samples * row[2] * (4 if row[3] == 24 else row[3] // 8)
+                    lay.append([frames, samples])
+        if pcm_offsets is None:
+            offs, at = [], 0
+            for n in sizes:
+                offs.append(at)
+                at += n + (-n % 4)
+            pcm = torch.empty((max(at, 8),), dtype=torch.uint8, device=self.device)
+        else:
+            pcm, offs = pcm_offsets(sizes)
+        if live:
+            at = 0
+            for j, i in enumerate(live):                          # a refused clip sits, empty, where the previous one ended
+                if lay[j][1]:
+                    at = offs[i]
+                lay[j] = [at] + lay[j]
+                at += sizes[i]
+            info2 = self.flac_decode(buf, index, lay, pcm).cpu().tolist()
+            for j, i in enumerate(live):
+                if isinstance(out[i], FlacError):
+                    continue
+                if info2[j][0]:
+                    out[i] = FlacError(info2[j][0], infos[i].start + info2[j][1])
+                else:
+                    out[i] = (offs[i], lay[j][2], {8: 1, 16: 2, 24: 4}[rows[j][3]], rows[j][6], rows[j][2])
+        return pcm, out
 
     def _flac_files(self, buf: torch.Tensor, offs, lens, sample_rate: int, lpc_order: int = 0):
         """The last step of finish_output with encoding "flac": one vv_pcm_flac (lpc_order > 0: vv_pcm_flac_lpc) call over the requests, ONE small copy of info (24 (R + 1)

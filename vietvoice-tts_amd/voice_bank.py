@@ -6,7 +6,8 @@ The reference re-opens the model tar, re-decodes and re-normalises the clip on e
 (core/model.py:204-211, core/audio_processor.py:15-44) and carries an unused ``sample_cache``
 (core/tts_engine.py:30).  Here:
 
-  host   : RIFF/WAVE byte parsing (no arithmetic on samples), one descriptor row per clip
+  host   : RIFF/WAVE and FLAC container parsing (no arithmetic on samples), one descriptor row per clip
+  device : vv_flac_index + vv_flac_decode = a FLAC clip's frames -> the same interleaved PCM bytes a WAV clip uploads (N17, RFC 9639)
   device : vv_ingest_pcm  = pydub set_channels(1) / set_frame_rate = audioop.tomono + audioop.ratecv, -> float32
            vv_normalize_clips = numpy-ordered float32 mean / peak / scale / int16 truncation
            -- bit-exact to AudioProcessor.load_audio (tests/test_ingest_gpu.py); clips of one ``ingest_many`` call batched on grid.y
@@ -25,7 +26,7 @@ from typing import Dict, List, Tuple, Union
 
 import numpy as np
 
-from .core.audio_processor import AudioProcessor, ratecv_len, tomono
+from .core.audio_processor import AudioProcessor, is_flac, ratecv_len, tomono
 
 
 def resample_design(src: int, dst: int) -> Tuple[np.ndarray, int, int, int]:
@@ -96,11 +97,17 @@ class VoiceBank:
                 self.hits += 1                    # repeated inside this call: ingested once
         if todo:
             dev = self.synth.device
-            decoded = [AudioProcessor.decode(it) for it in todo.values()]          # host: container parsing only
-            if any(f.shape[0] == 0 for f, _w, _r in decoded):
+            raw = [AudioProcessor._read_bytes(it) for it in todo.values()]
+            flac = {j: d for j, d in enumerate(raw) if d[:4] != b"RIFF" and is_flac(d)}        # N17: decoded on the device
+            if flac and self.resampler != "ratecv":                                 # opt-in path: device-decoded frames come back
+                back = self._flac_frames(list(flac.values()))
+                flac = dict(zip(flac, back))
+            decoded = [flac[j] if j in flac and self.resampler != "ratecv" else None if j in flac else AudioProcessor.decode(d)
+                       for j, d in enumerate(raw)]                                   # host: container parsing only
+            if any(d is not None and d[0].shape[0] == 0 for d in decoded):
                 raise ValueError("empty audio clip")
             if self.resampler == "ratecv":
-                x, lens = self._ingest_ratecv(decoded, dev)
+                x, lens = self._ingest_ratecv(decoded, dev, flac)
             else:
                 x, lens = self._ingest_polyphase(decoded, dev)
             off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -121,22 +128,63 @@ class VoiceBank:
                 self.bytes -= old.nbytes
         return [self._entries[k] for k in keys]
 
-    def _ingest_ratecv(self, decoded, dev):
-        """One vv_ingest_pcm launch for all clips: interleaved PCM bytes back to back (4-byte aligned) + descriptor rows."""
+    def _flac_frames(self, files):
+        """FLAC files -> [(frames (n, channels), width, rate)] through the device decoder, copied back (the opt-in polyphase path)."""
+        pcm, res = self.synth.flac_clips(files)
+        host, out = pcm.cpu().numpy(), []
+        for r in res:
+            if isinstance(r, Exception):
+                raise r
+            off, n, width, rate, ch = r
+            out.append((host[off: off + n * ch * width].view({1: np.int8, 2: np.int16, 4: np.int32}[width]).reshape(n, ch).copy(), width, rate))
+        return out
+
+    def _ingest_ratecv(self, decoded, dev, flac=None):
+        """One vv_ingest_pcm launch for all clips: interleaved PCM bytes back to back (4-byte aligned) + descriptor rows.  A FLAC clip
+        (``decoded[j] is None``, its file in ``flac[j]``) is decoded on the device (vv_flac_index / vv_flac_decode) into the same byte
+        buffer, behind the uploaded WAV clips: no decoded sample crosses the bus."""
         import torch
-        parts, desc, pos, out_pos = [], [], 0, 0
-        for frames, width, rate in decoded:
+        parts, clips, pos = [], {}, 0
+        for j, d in enumerate(decoded):
+            if d is None:
+                continue
+            frames, width, rate = d
             if frames.shape[1] > 2:
                 tomono(frames)                    # range check only (OverflowError like the reference); the mix itself runs on the device
             raw = frames.tobytes()
-            g = gcd(rate, self.sample_rate)
-            n_out = ratecv_len(frames.shape[0], rate, self.sample_rate) if rate != self.sample_rate else frames.shape[0]
-            desc.append([pos, width, frames.shape[1], frames.shape[0], rate // g, self.sample_rate // g, out_pos, n_out])
+            clips[j] = (pos, width, frames.shape[1], frames.shape[0], rate)
             pad = -len(raw) % 4
             parts.append(raw + b"\0" * pad)
             pos += len(raw) + pad
+        if flac:
+            def place(sizes):
+                offs, at = [], pos
+                for n in sizes:
+                    offs.append(at)
+                    at += n + (-n % 4)
+                buf = torch.empty((max(at, 8),), dtype=torch.uint8, device=dev)
+                if pos:
+                    buf[:pos] = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
+                return buf, offs
+            buf, res = self.synth.flac_clips([flac[j] for j in sorted(flac)], pcm_offsets=place)
+            for j, r in zip(sorted(flac), res):
+                if isinstance(r, Exception):
+                    raise r
+                off, n, width, rate, ch = r
+                if n == 0:
+                    raise ValueError("empty audio clip")
+                if ch > 2:                        # the same range check, on a copy of this clip alone
+                    tomono(buf[off: off + n * ch * width].cpu().numpy().view({1: np.int8, 2: np.int16, 4: np.int32}[width]).reshape(n, ch))
+                clips[j] = (off, width, ch, n, rate)
+        else:
+            buf = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
+        desc, out_pos = [], 0
+        for j in range(len(decoded)):
+            off, width, ch, n, rate = clips[j]
+            g = gcd(rate, self.sample_rate)
+            n_out = ratecv_len(n, rate, self.sample_rate) if rate != self.sample_rate else n
+            desc.append([off, width, ch, n, rate // g, self.sample_rate // g, out_pos, n_out])
             out_pos += n_out
-        buf = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
         return self.synth.ingest_pcm(buf, desc, out_pos), [d[7] for d in desc]
 
     def _ingest_polyphase(self, decoded, dev):
