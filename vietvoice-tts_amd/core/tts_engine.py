@@ -225,9 +225,6 @@ class TTSEngine:
             vals = [mine] * len(counts) if own is None else [mine if v is None else v for v in own]
             if any(v is not None for v in vals):           # no pitch and no tempo anywhere: exactly the call of N13
                 opts[key] = vals
-        if lim is None:                    # no limiter anywhere: exactly the call of N12
-            return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                                   loudness=loud, peak_dbfs=self.config.output_peak_dbfs, **opts)
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
                                                                loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **opts)
 

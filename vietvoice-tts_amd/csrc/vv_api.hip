@@ -208,6 +208,54 @@ int launch_gemm(vv_ctx* c, Gemm g, int cls, hipStream_t st, double alg_flops = -
 
 std::string blk(int i, const char* s) { return "blocks." + std::to_string(i) + s; }
 
+// ---- the checks the PCM entries (N10 ... N17) share.  Each refusal is -22 with the entry's name in front, before anything is launched.
+// the prologue, behind the entry's own ``if (!c) return -22``: the context's device is made current -> the caller's stream
+inline hipStream_t enter(vv_ctx* c, void* stream) {
+    hipSetDevice(c->device);
+    return (hipStream_t)stream;
+}
+
+// off + n <= total for non-negative off and n, without forming the sum
+inline bool fits(int64_t off, int64_t n, int64_t total) { return off >= 0 && n >= 0 && n <= total && off <= total - n; }
+
+inline bool spans_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
+
+struct PtrArg { const char* name; const void* p; unsigned align = 1; bool may_be_null = false; };
+
+int check_ptrs(vv_ctx* c, const char* entry, std::initializer_list<PtrArg> args) {
+    for (const PtrArg& a : args) {
+        if (!a.p && !a.may_be_null) return c->fail(-22, "%s: null pointer (%s)", entry, a.name);
+        if ((uintptr_t)a.p % a.align) return c->fail(-22, "%s: misaligned pointer (%s: %u bytes)", entry, a.name, a.align);
+    }
+    return 0;
+}
+
+int check_ws(vv_ctx* c, const char* entry, uint64_t have, uint64_t need, const char* what = "ws") {
+    return have < need ? c->fail(-22, "%s: %s of %llu bytes, %llu are needed", entry, what, (unsigned long long)have, (unsigned long long)need) : 0;
+}
+
+// the clip rows of vv_flac_index and vv_flac_decode: ascending, 4-byte aligned, 8 bytes of padding behind the last; -> 0 or the refusal
+int flac_rows(vv_ctx* c, const char* name, const int64_t* rows, const int64_t* rows_host, int R, int64_t n_bytes, int* max_channels) {
+    if (R < 1 || R > 65535 || n_bytes < 8 || n_bytes > ((int64_t)1 << 31) - 64)
+        return c->fail(-22, "%s: bad sizes (1 <= R <= 65535, 8 <= n_bytes <= 2^31 - 64)", name);
+    if (int e = check_ptrs(c, name, {{"rows", rows, 8}, {"rows_host", rows_host, 8}})) return e;
+    int64_t at = 0;
+    *max_channels = 1;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 8 * (size_t)r;
+        if (q[0] < at || q[0] % 4 || !fits(q[0], q[1], n_bytes - 8))
+            return c->fail(-22, "%s: row %d: the clips lie in ascending order, 4-byte aligned, inside data less 8 bytes of padding", name, r);
+        if (q[2] < 1 || q[2] > 8 || (q[3] != 8 && q[3] != 16 && q[3] != 24) || q[5] < 16 || q[5] > 65535 || q[4] < 0 || q[4] > q[5] || q[6] < 1 ||
+            q[6] > 1048575 || q[7] < 0 || q[7] > VV_FLAC_MAX_CLIP)
+            return c->fail(-22, "%s: row %d: channels 1 ... 8, bits 8 / 16 / 24, 16 <= max block <= 65535, min <= max, rate 1 ... 1048575, total <= 2^26", name, r);
+        at = q[0] + q[1];
+        if (q[2] > *max_channels) *max_channels = (int)q[2];
+    }
+    return 0;
+}
+
 }  // namespace
 
 // =====================================================================================  ABI
@@ -603,21 +651,20 @@ int vv_join_chunks(vv_ctx* c, const int16_t* pcm, int64_t n_pcm, const int64_t* 
                    const int64_t* req_rows, const int64_t* req_rows_host, int R, const double* fade, int64_t n_fade, int max_n, int64_t max_len,
                    int16_t* out, int64_t n_out, void* ws, void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (R < 1 || n_chunks < R || !pcm || !chunk_rows || !req_rows || !out || !ws || max_n < 0 || max_n > vvk_join_max_n() || (uintptr_t)out % 16)
-        return c->fail(-22, "vv_join_chunks: bad arguments (1 <= R <= n_chunks; pcm, rows, out, ws not null; out 16-byte aligned; max_n <= %d)",
-                       vvk_join_max_n());
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || n_chunks < R || max_n < 0 || max_n > vvk_join_max_n())
+        return c->fail(-22, "vv_join_chunks: bad arguments (1 <= R <= n_chunks; max_n <= %d)", vvk_join_max_n());
+    if (int e = check_ptrs(c, "vv_join_chunks", {{"pcm", pcm}, {"chunk_rows", chunk_rows}, {"req_rows", req_rows}, {"out", out, 16}, {"ws", ws}})) return e;
     if ((chunk_rows_host == nullptr) != (req_rows_host == nullptr)) return c->fail(-22, "vv_join_chunks: host rows come as a pair or not at all");
     if (chunk_rows_host) {               // the same rows on the host: checked here, before anything is launched
         for (int r = 0; r < R; ++r) {
             const int64_t* q = req_rows_host + 4 * (size_t)r;
-            if (q[0] < 0 || q[1] < 1 || q[0] + q[1] > n_chunks || q[2] < 0 || q[3] < 0 || q[2] + q[3] > n_out)
+            if (q[1] < 1 || !fits(q[0], q[1], n_chunks) || !fits(q[2], q[3], n_out))
                 return c->fail(-22, "vv_join_chunks: request row %d does not fit the chunk rows or the output", r);
             for (int64_t k = q[0]; k < q[0] + q[1]; ++k) {
                 const int64_t* w = chunk_rows_host + 8 * (size_t)k;
-                if (w[0] < 0 || w[1] < 0 || w[0] + w[1] > n_pcm || w[2] < 0 || w[3] < 0 || w[3] > max_n || w[1] > max_len || w[7] != r ||
-                    (w[3] > 0 && (w[5] < 0 || w[5] + 2 * w[3] > n_fade)))
+                if (!fits(w[0], w[1], n_pcm) || w[2] < 0 || w[3] < 0 || w[3] > max_n || w[1] > max_len || w[7] != r ||
+                    (w[3] > 0 && !fits(w[5], 2 * w[3], n_fade)))
                     return c->fail(-22, "vv_join_chunks: chunk row %lld does not fit the buffers", (long long)k);
                 if (q[1] >= 2 && w[1] <= 0)
                     return c->fail(-22, "vv_join_chunks: chunk %lld is empty inside a request of %lld chunks", (long long)k, (long long)q[1]);
@@ -633,10 +680,10 @@ int vv_join_chunks(vv_ctx* c, const int16_t* pcm, int64_t n_pcm, const int64_t* 
 int vv_pcm_resample(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_out, const double* taps, int n_taps,
                     int up, int down, int skip, int16_t* y, int64_t n_y, void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (n_rows < 1 || !x || !rows || !taps || !y || n_taps < 1 || up < 1 || down < 1 || skip < 0 || max_out < 0)
-        return c->fail(-22, "vv_pcm_resample: bad arguments (n_rows, n_taps, up, down >= 1; skip, max_out >= 0; no null pointer)");
+    hipStream_t st = enter(c, stream);
+    if (n_rows < 1 || n_taps < 1 || up < 1 || down < 1 || skip < 0 || max_out < 0)
+        return c->fail(-22, "vv_pcm_resample: bad arguments (n_rows, n_taps, up, down >= 1; skip, max_out >= 0)");
+    if (int e = check_ptrs(c, "vv_pcm_resample", {{"x", x}, {"rows", rows}, {"taps", taps}, {"y", y}})) return e;
     Prof p(c, VV_PROF_ELEMWISE, 2.0 * (double)n_y * (n_taps / up + 1), 2.0 * (double)(n_x + n_y), st);
     KCHK(c, vvk_pcm_resample(x, (long long)n_x, (const long long*)rows, n_rows, (long long)max_out, taps, n_taps, up, down, skip, y, (long long)n_y,
                              st, &m__));
@@ -646,10 +693,10 @@ int vv_pcm_resample(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* row
 int vv_pcm_encode(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, int n_rows, int64_t max_n, int kind, uint8_t* y, int64_t n_y,
                   void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (n_rows < 1 || !x || !rows || !y || (kind != 1 && kind != 2) || max_n < 0 || (uintptr_t)y % 8)
-        return c->fail(-22, "vv_pcm_encode: bad arguments (n_rows >= 1; kind 1 = mu-law, 2 = A-law; y 8-byte aligned; no null pointer)");
+    hipStream_t st = enter(c, stream);
+    if (n_rows < 1 || (kind != 1 && kind != 2) || max_n < 0)
+        return c->fail(-22, "vv_pcm_encode: bad arguments (n_rows >= 1; kind 1 = mu-law, 2 = A-law)");
+    if (int e = check_ptrs(c, "vv_pcm_encode", {{"x", x}, {"rows", rows}, {"y", y, 8}})) return e;
     Prof p(c, VV_PROF_ELEMWISE, 0, 2.0 * (double)n_x + (double)n_y, st);
     KCHK(c, vvk_pcm_encode(x, (long long)n_x, (const long long*)rows, n_rows, (long long)max_n, kind, y, (long long)n_y, st, &m__));
     return 0;
@@ -662,32 +709,25 @@ int vv_pcm_loudness(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* row
                     const double* tables, const double* params, int16_t* y, int64_t n_y, double* stats, void* ws, uint64_t ws_bytes,
                     void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     if (R < 1 || R > 65535 || sub < VV_LOUD_RUN || sub > (1 << 24) || n_x < 0 || n_y < 0)
         return c->fail(-22, "vv_pcm_loudness: bad sizes (1 <= R <= 65535; sub >= %d)", VV_LOUD_RUN);
-    if (!x || !rows || !rows_host || !tables || !params || !stats || !ws)
-        return c->fail(-22, "vv_pcm_loudness: null pointer (x, rows, rows_host, tables, params, stats, ws)");
-    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)tables % 8 || (uintptr_t)params % 8 || (uintptr_t)stats % 8 ||
-        (uintptr_t)ws % 8)
-        return c->fail(-22, "vv_pcm_loudness: misaligned pointer (x, y 2 bytes; rows, tables, params, stats, ws 8)");
+    if (int e = check_ptrs(c, "vv_pcm_loudness", {{"x", x, 2}, {"y", y, 2, true}, {"rows", rows, 8}, {"rows_host", rows_host}, {"tables", tables, 8},
+                                                  {"params", params, 8}, {"stats", stats, 8}, {"ws", ws, 8}})) return e;
     const int64_t rps = (sub + VV_LOUD_RUN - 1) / VV_LOUD_RUN;
     int64_t total_runs = 0, max_n = 0;
     for (int r = 0; r < R; ++r) {
         const int64_t* q = rows_host + 4 * (size_t)r;
-        if (q[0] < 0 || q[1] < 0 || q[1] > n_x || q[0] > n_x - q[1] || q[1] >= ((int64_t)1 << 40))
+        if (!fits(q[0], q[1], n_x) || q[1] >= ((int64_t)1 << 40))
             return c->fail(-22, "vv_pcm_loudness: row %d does not fit the %lld samples of x", r, (long long)n_x);
-        if (y && (q[2] < 0 || q[1] > n_y || q[2] > n_y - q[1]))
-            return c->fail(-22, "vv_pcm_loudness: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (y && !fits(q[2], q[1], n_y)) return c->fail(-22, "vv_pcm_loudness: row %d does not fit the %lld samples of y", r, (long long)n_y);
         if (y == x && q[2] != q[0]) return c->fail(-22, "vv_pcm_loudness: in place (y == x) needs dst_off == src_off, row %d", r);
         if (q[3] != total_runs) return c->fail(-22, "vv_pcm_loudness: row %d: run_off is the sum of the runs of the rows before it", r);
         const int64_t J = q[1] / sub;
         total_runs += J * rps + (q[1] - J * sub + VV_LOUD_RUN - 1) / VV_LOUD_RUN;
         if (q[1] > max_n) max_n = q[1];
     }
-    if (ws_bytes < vvk_pcm_loudness_ws_bytes((long long)total_runs, R))
-        return c->fail(-22, "vv_pcm_loudness: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
-                       (unsigned long long)vvk_pcm_loudness_ws_bytes((long long)total_runs, R));
+    if (int e = check_ws(c, "vv_pcm_loudness", ws_bytes, vvk_pcm_loudness_ws_bytes((long long)total_runs, R))) return e;
     Prof p(c, VV_PROF_ELEMWISE, 60.0 * (double)n_x, 6.0 * (double)n_x + 128.0 * (double)total_runs, st);
     KCHK(c, vvk_pcm_loudness(x, (long long)n_x, (const long long*)rows, R, (long long)sub, (long long)total_runs, (long long)max_n, tables,
                              params, y, (long long)n_y, stats, ws, st, &m__));
@@ -705,25 +745,20 @@ int vv_pcm_limit(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, 
                  const double* window, const double* taps, const double* params, const double* meas, int16_t* y, int64_t n_y, double* stats,
                  void* ws, uint64_t ws_bytes, void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     if (R < 1 || R > 65535 || L < 1 || L > VV_LIMIT_MAX_L || (mode != 0 && mode != 1) || n_x < 0 || n_y < 0)
         return c->fail(-22, "vv_pcm_limit: bad sizes (1 <= R <= 65535; 1 <= L <= %d; mode 0 or 1)", VV_LIMIT_MAX_L);
-    if (!x || !rows || !rows_host || !window || !taps || !params || !stats || !ws)
-        return c->fail(-22, "vv_pcm_limit: null pointer (x, rows, rows_host, window, taps, params, stats, ws)");
-    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)window % 8 || (uintptr_t)taps % 8 || (uintptr_t)params % 8 ||
-        (uintptr_t)meas % 8 || (uintptr_t)stats % 8 || (uintptr_t)ws % 8)
-        return c->fail(-22, "vv_pcm_limit: misaligned pointer (x, y 2 bytes; rows, window, taps, params, meas, stats, ws 8)");
+    if (int e = check_ptrs(c, "vv_pcm_limit", {{"x", x, 2}, {"y", y, 2, true}, {"rows", rows, 8}, {"rows_host", rows_host}, {"window", window, 8},
+                                               {"taps", taps, 8}, {"params", params, 8}, {"meas", meas, 8, true}, {"stats", stats, 8}, {"ws", ws, 8}})) return e;
     const int64_t tile = vvk_pcm_limit_tile(L);
     int64_t total_samples = 0, total_tiles = 0, max_tiles = 0, max_out = 0;
     for (int r = 0; r < R; ++r) {
         const int64_t* q = rows_host + 5 * (size_t)r;
         if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[4] < 0) return c->fail(-22, "vv_pcm_limit: row %d has a negative field", r);
-        if (q[1] > n_x || q[0] > n_x - q[1] || q[1] >= ((int64_t)1 << 40))
+        if (!fits(q[0], q[1], n_x) || q[1] >= ((int64_t)1 << 40))
             return c->fail(-22, "vv_pcm_limit: row %d does not fit the %lld samples of x", r, (long long)n_x);
-        if (q[3] > q[1] || q[4] > q[1] - q[3]) return c->fail(-22, "vv_pcm_limit: row %d: out_lo + out_n exceeds n", r);
-        if (y && (q[4] > n_y || q[2] > n_y - q[4]))
-            return c->fail(-22, "vv_pcm_limit: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (!fits(q[3], q[4], q[1])) return c->fail(-22, "vv_pcm_limit: row %d: out_lo + out_n exceeds n", r);
+        if (y && !fits(q[2], q[4], n_y)) return c->fail(-22, "vv_pcm_limit: row %d does not fit the %lld samples of y", r, (long long)n_y);
         if (y == x && q[4] > 0 && q[2] != q[0] + q[3])
             return c->fail(-22, "vv_pcm_limit: in place (y == x) needs dst_off == src_off + out_lo, row %d", r);
         const int64_t nt = (q[1] + tile - 1) / tile;
@@ -732,9 +767,7 @@ int vv_pcm_limit(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, 
         if (nt > max_tiles) max_tiles = nt;
         if (q[4] > max_out) max_out = q[4];
     }
-    if (ws_bytes < vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R))
-        return c->fail(-22, "vv_pcm_limit: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
-                       (unsigned long long)vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R));
+    if (int e = check_ws(c, "vv_pcm_limit", ws_bytes, vvk_pcm_limit_ws_bytes((long long)total_samples, (long long)total_tiles, R))) return e;
     Prof p(c, VV_PROF_ELEMWISE, (mode ? 640.0 : 500.0) * (double)total_samples * (double)(2 * L + 1) / 241.0,
            20.0 * (double)total_samples + 2.0 * (double)max_out * R, st);
     KCHK(c, vvk_pcm_limit(x, (long long)n_x, (const long long*)rows, R, L, mode, (long long)total_samples, (long long)total_tiles,
@@ -748,18 +781,13 @@ uint64_t vv_pcm_stretch_ws_bytes(int R) { return vvk_pcm_stretch_ws_bytes(R); }
 int vv_pcm_stretch(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* window,
                    int16_t* y, int64_t n_y, int32_t* pos, int64_t n_pos, void* ws, uint64_t ws_bytes, void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     if (R < 1 || R > 65535 || n_x < 0 || n_y < 0 || n_pos < 0) return c->fail(-22, "vv_pcm_stretch: bad sizes (1 <= R <= 65535)");
-    if (!x || !rows || !rows_host || !window || !pos || !ws)
-        return c->fail(-22, "vv_pcm_stretch: null pointer (x, rows, rows_host, window, pos, ws)");
-    if ((uintptr_t)x % 2 || (uintptr_t)y % 2 || (uintptr_t)rows % 8 || (uintptr_t)window % 8 || (uintptr_t)pos % 4 || (uintptr_t)ws % 8)
-        return c->fail(-22, "vv_pcm_stretch: misaligned pointer (x, y 2 bytes; pos 4; rows, window, ws 8)");
-    if (y && (uintptr_t)y < (uintptr_t)(x + n_x) && (uintptr_t)x < (uintptr_t)(y + n_y))
+    if (int e = check_ptrs(c, "vv_pcm_stretch", {{"x", x, 2}, {"y", y, 2, true}, {"rows", rows, 8}, {"rows_host", rows_host}, {"window", window, 8},
+                                                 {"pos", pos, 4}, {"ws", ws, 8}})) return e;
+    if (y && spans_overlap(x, 2ull * n_x, y, 2ull * n_y))
         return c->fail(-22, "vv_pcm_stretch: y overlaps x (an output sample reads two frames of the input: not in place)");
-    if (ws_bytes < vvk_pcm_stretch_ws_bytes(R))
-        return c->fail(-22, "vv_pcm_stretch: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes,
-                       (unsigned long long)vvk_pcm_stretch_ws_bytes(R));
+    if (int e = check_ws(c, "vv_pcm_stretch", ws_bytes, vvk_pcm_stretch_ws_bytes(R))) return e;
     std::vector<std::pair<int64_t, int64_t>> on_y, on_pos;
     int64_t total_out = 0, total_frames = 0, max_out = 0;
     for (int r = 0; r < R; ++r) {
@@ -767,11 +795,11 @@ int vv_pcm_stretch(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows
         if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[5] < 0) return c->fail(-22, "vv_pcm_stretch: row %d has a negative field", r);
         if (q[3] < 1 || q[3] > VV_WSOLA_MAX_PQ || q[4] < 1 || q[4] > VV_WSOLA_MAX_PQ || q[3] == q[4] || 4 * q[3] < q[4] || q[3] > 4 * q[4])
             return c->fail(-22, "vv_pcm_stretch: row %d: p and q in 1 ... %d, p != q, 1/4 <= p / q <= 4", r, VV_WSOLA_MAX_PQ);
-        if (q[1] > n_x || q[0] > n_x - q[1] || q[1] > ((int64_t)1 << 30))
+        if (!fits(q[0], q[1], n_x) || q[1] > ((int64_t)1 << 30))
             return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld samples of x", r, (long long)n_x);
         const int64_t n_s = (q[1] * q[3] + q[4] - 1) / q[4], M = (n_s + VV_WSOLA_HS - 1) / VV_WSOLA_HS;
-        if (y && (n_s > n_y || q[2] > n_y - n_s)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld samples of y", r, (long long)n_y);
-        if (M + 1 > n_pos || q[5] > n_pos - (M + 1)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld entries of pos", r, (long long)n_pos);
+        if (y && !fits(q[2], n_s, n_y)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (!fits(q[5], M + 1, n_pos)) return c->fail(-22, "vv_pcm_stretch: row %d does not fit the %lld entries of pos", r, (long long)n_pos);
         if (y && n_s > 0) on_y.emplace_back(q[2], q[2] + n_s);
         on_pos.emplace_back(q[5], q[5] + M + 1);
         total_out += n_s;
@@ -799,24 +827,20 @@ uint64_t vv_pcm_flac_ws_bytes(int64_t total_frames, int R) { return vvk_pcm_flac
 // both entries: lpc_order 0 = vv_pcm_flac (N15), 1 ... 12 = vv_pcm_flac_lpc (N16)
 static int pcm_flac(vv_ctx* c, const char* name, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int sample_rate,
                     int lpc_order, uint8_t* y, int64_t n_y, int64_t* info, void* ws, uint64_t ws_bytes, void* stream) {
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     if (R < 1 || R > 65535 || n_x < 0 || n_y < 0) return c->fail(-22, "%s: bad sizes (1 <= R <= 65535)", name);
     if (sample_rate < 1 || sample_rate > 655350) return c->fail(-22, "%s: a sample rate in 1 ... 655350 Hz is needed", name);
-    if (!x || !rows || !rows_host || !y || !info || !ws) return c->fail(-22, "%s: null pointer (x, rows, rows_host, y, info, ws)", name);
-    if ((uintptr_t)x % 2 || (uintptr_t)rows % 8 || (uintptr_t)rows_host % 8 || (uintptr_t)info % 8 || (uintptr_t)ws % 8)
-        return c->fail(-22, "%s: misaligned pointer (x 2 bytes; rows, rows_host, info, ws 8)", name);
-    if ((uintptr_t)y < (uintptr_t)(x + n_x) && (uintptr_t)x < (uintptr_t)(y + n_y))
-        return c->fail(-22, "%s: y overlaps x (a frame is packed while others are still read)", name);
+    if (int e = check_ptrs(c, name, {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host, 8}, {"y", y}, {"info", info, 8}, {"ws", ws, 8}})) return e;
+    if (spans_overlap(x, 2ull * n_x, y, (uint64_t)n_y)) return c->fail(-22, "%s: y overlaps x (a frame is packed while others are still read)", name);
     int64_t total_frames = 0, max_frames = 0, total_samples = 0;
     uint64_t need = 0;
     for (int r = 0; r < R; ++r) {
         const int64_t* q = rows_host + 4 * (size_t)r;
         if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "%s: row %d has a negative field", name, r);
         if (q[1] < 1) return c->fail(-22, "%s: row %d is empty (n >= 1)", name, r);
-        if (q[1] > n_x || q[0] > n_x - q[1]) return c->fail(-22, "%s: row %d does not fit the %lld samples of x", name, r, (long long)n_x);
+        if (!fits(q[0], q[1], n_x)) return c->fail(-22, "%s: row %d does not fit the %lld samples of x", name, r, (long long)n_x);
         const int64_t frames = (q[1] + VV_FLAC_BLOCK - 1) / VV_FLAC_BLOCK;
-        if (q[2] > ((int64_t)1 << 31) - frames) return c->fail(-22, "%s: row %d: frame0 + frames exceeds 2^31", name, r);
+        if (!fits(q[2], frames, (int64_t)1 << 31)) return c->fail(-22, "%s: row %d: frame0 + frames exceeds 2^31", name, r);
         if (q[3] > 1 || (q[3] == 0 && q[1] % VV_FLAC_BLOCK))
             return c->fail(-22, "%s: row %d: last is 0 or 1, and last = 0 needs n to be a multiple of %d", name, r, VV_FLAC_BLOCK);
         need += (uint64_t)(frames - 1) * vvk_flac_frame_bound(VV_FLAC_BLOCK) + vvk_flac_frame_bound(q[1] - (frames - 1) * VV_FLAC_BLOCK);
@@ -826,10 +850,8 @@ static int pcm_flac(vv_ctx* c, const char* name, const int16_t* x, int64_t n_x, 
     }
     if ((uint64_t)n_y < need)
         return c->fail(-22, "%s: y of %lld bytes, the frame bounds add up to %llu", name, (long long)n_y, (unsigned long long)need);
-    const uint64_t ws_need = lpc_order ? vvk_pcm_flac_lpc_ws_bytes((long long)total_frames, R) : vvk_pcm_flac_ws_bytes((long long)total_frames, R);
-    if (ws_bytes < ws_need)
-        return c->fail(-22, "%s: ws of %llu bytes, %llu are needed", name, (unsigned long long)ws_bytes,
-                       (unsigned long long)ws_need);
+    if (int e = check_ws(c, name, ws_bytes, lpc_order ? vvk_pcm_flac_lpc_ws_bytes((long long)total_frames, R) : vvk_pcm_flac_ws_bytes((long long)total_frames, R)))
+        return e;
     Prof p(c, VV_PROF_ELEMWISE, (lpc_order ? 800.0 : 200.0) * (double)total_samples, 4.0 * (double)total_samples + 2.0 * (double)need, st);
     KCHK(c, vvk_pcm_flac(x, (long long)n_x, (const long long*)rows, R, sample_rate, lpc_order, (long long)total_frames, (long long)max_frames, y, (long long)n_y,
                          (long long*)info, ws, st, &m__));
@@ -865,42 +887,14 @@ uint64_t vv_flac_index_ws_bytes(int64_t n_bytes, int R) { return vvk_flac_index_
 
 uint64_t vv_flac_decode_ws_bytes(int64_t plane_samples, int64_t total_frames) { return vvk_flac_decode_ws_bytes((long long)plane_samples, (long long)total_frames); }
 
-static bool spans_overlap(const void* a, uint64_t na, const void* b, uint64_t nb) {
-    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-}
-
-// the rows of both calls: ascending, 4-byte aligned, 8 bytes of padding behind the last; -> 0 or the refusal
-static int flac_rows(vv_ctx* c, const char* name, const int64_t* rows, const int64_t* rows_host, int R, int64_t n_bytes, int* max_channels) {
-    if (R < 1 || R > 65535 || n_bytes < 8 || n_bytes > ((int64_t)1 << 31) - 64)
-        return c->fail(-22, "%s: bad sizes (1 <= R <= 65535, 8 <= n_bytes <= 2^31 - 64)", name);
-    if (!rows || !rows_host) return c->fail(-22, "%s: null pointer (rows, rows_host)", name);
-    if ((uintptr_t)rows % 8 || (uintptr_t)rows_host % 8) return c->fail(-22, "%s: misaligned pointer (rows, rows_host: 8 bytes)", name);
-    int64_t at = 0;
-    *max_channels = 1;
-    for (int r = 0; r < R; ++r) {
-        const int64_t* q = rows_host + 8 * (size_t)r;
-        if (q[0] < at || q[0] % 4 || q[1] < 0 || q[1] > n_bytes - 8 || q[0] > n_bytes - 8 - q[1])
-            return c->fail(-22, "%s: row %d: the clips lie in ascending order, 4-byte aligned, inside data less 8 bytes of padding", name, r);
-        if (q[2] < 1 || q[2] > 8 || (q[3] != 8 && q[3] != 16 && q[3] != 24) || q[5] < 16 || q[5] > 65535 || q[4] < 0 || q[4] > q[5] || q[6] < 1 ||
-            q[6] > 1048575 || q[7] < 0 || q[7] > VV_FLAC_MAX_CLIP)
-            return c->fail(-22, "%s: row %d: channels 1 ... 8, bits 8 / 16 / 24, 16 <= max block <= 65535, min <= max, rate 1 ... 1048575, total <= 2^26", name, r);
-        at = q[0] + q[1];
-        if (q[2] > *max_channels) *max_channels = (int)q[2];
-    }
-    return 0;
-}
-
 int vv_flac_index(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, int64_t* info, void* ws,
                   uint64_t ws_bytes, void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     int maxch = 1;
     if (int e = flac_rows(c, "vv_flac_index", rows, rows_host, R, n_bytes, &maxch)) return e;
-    if (!data || !info || !ws) return c->fail(-22, "vv_flac_index: null pointer (data, info, ws)");
-    if ((uintptr_t)data % 8 || (uintptr_t)info % 8 || (uintptr_t)ws % 8) return c->fail(-22, "vv_flac_index: misaligned pointer (data, info, ws: 8 bytes)");
-    const uint64_t need = vvk_flac_index_ws_bytes((long long)n_bytes, R);
-    if (ws_bytes < need) return c->fail(-22, "vv_flac_index: ws of %llu bytes, %llu are needed", (unsigned long long)ws_bytes, (unsigned long long)need);
+    if (int e = check_ptrs(c, "vv_flac_index", {{"data", data, 8}, {"info", info, 8}, {"ws", ws, 8}})) return e;
+    if (int e = check_ws(c, "vv_flac_index", ws_bytes, vvk_flac_index_ws_bytes((long long)n_bytes, R))) return e;
     if (spans_overlap(data, (uint64_t)n_bytes, ws, ws_bytes) || spans_overlap(info, 32ull * R, ws, ws_bytes) || spans_overlap(data, (uint64_t)n_bytes, info, 32ull * R))
         return c->fail(-22, "vv_flac_index: data, info and ws overlap");
     Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * (double)n_bytes, st);
@@ -912,14 +906,12 @@ int vv_flac_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_
                    const int64_t* lay_host, const void* ws, uint64_t ws_bytes, uint8_t* pcm, int64_t n_pcm, int64_t* info2, void* ws2, uint64_t ws2_bytes,
                    void* stream) {
     if (!c) return -22;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = enter(c, stream);
     int maxch = 1;
     if (int e = flac_rows(c, "vv_flac_decode", rows, rows_host, R, n_bytes, &maxch)) return e;
-    if (!data || !lay || !lay_host || !ws || !pcm || !info2 || !ws2 || n_pcm < 0)
-        return c->fail(-22, "vv_flac_decode: null pointer (data, lay, lay_host, ws, pcm, info2, ws2)");
-    if ((uintptr_t)data % 8 || (uintptr_t)lay % 8 || (uintptr_t)lay_host % 8 || (uintptr_t)ws % 8 || (uintptr_t)info2 % 8 || (uintptr_t)ws2 % 8)
-        return c->fail(-22, "vv_flac_decode: misaligned pointer (data, lay, lay_host, ws, info2, ws2: 8 bytes)");
+    if (n_pcm < 0) return c->fail(-22, "vv_flac_decode: bad sizes (n_pcm >= 0)");
+    if (int e = check_ptrs(c, "vv_flac_decode", {{"data", data, 8}, {"lay", lay, 8}, {"lay_host", lay_host, 8}, {"ws", ws, 8}, {"pcm", pcm},
+                                                 {"info2", info2, 8}, {"ws2", ws2, 8}})) return e;
     int64_t F = 0, S = 0, P = 0, at = 0;
     for (int r = 0; r < R; ++r) {
         const int64_t* l = lay_host + 6 * (size_t)r;
@@ -928,14 +920,12 @@ int vv_flac_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_
         if (l[1] < 0 || l[2] < 0 || l[2] > VV_FLAC_MAX_CLIP || l[1] > l[2] || l[1] > q[1] || l[3] != F || l[4] != P || l[5] != S)
             return c->fail(-22, "vv_flac_decode: lay row %d: frames <= samples <= 2^26 and the three prefix sums are needed", r);
         const int64_t bytes = l[2] * q[2] * width;
-        if (l[0] < at || l[0] > n_pcm - bytes) return c->fail(-22, "vv_flac_decode: lay row %d does not fit the %lld bytes of pcm, in ascending order", r, (long long)n_pcm);
+        if (l[0] < at || !fits(l[0], bytes, n_pcm)) return c->fail(-22, "vv_flac_decode: lay row %d does not fit the %lld bytes of pcm, in ascending order", r, (long long)n_pcm);
         at = l[0] + bytes;
         F += l[1]; S += l[2]; P += l[2] * q[2];
     }
-    const uint64_t need = vvk_flac_index_ws_bytes((long long)n_bytes, R), need2 = vvk_flac_decode_ws_bytes((long long)P, (long long)F);
-    if (ws_bytes < need || ws2_bytes < need2)
-        return c->fail(-22, "vv_flac_decode: ws of %llu bytes (%llu needed), ws2 of %llu (%llu needed)", (unsigned long long)ws_bytes, (unsigned long long)need,
-                       (unsigned long long)ws2_bytes, (unsigned long long)need2);
+    if (int e = check_ws(c, "vv_flac_decode", ws_bytes, vvk_flac_index_ws_bytes((long long)n_bytes, R))) return e;
+    if (int e = check_ws(c, "vv_flac_decode", ws2_bytes, vvk_flac_decode_ws_bytes((long long)P, (long long)F), "ws2")) return e;
     const void* span[5] = {data, ws, pcm, info2, ws2};
     const uint64_t len[5] = {(uint64_t)n_bytes, ws_bytes, (uint64_t)n_pcm, 16ull * R, ws2_bytes};
     for (int i = 0; i < 5; ++i)

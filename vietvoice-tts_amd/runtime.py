@@ -17,6 +17,7 @@ import torch
 
 from . import pack
 from .model_spec import ODE_MAX_EVALS, ModelSpec, check_apg, guidance_mask, ode_plan
+from .pcm_stage import JOIN_MAX_N, LOUD_RUN, PcmStage, _ptr, plan_join  # noqa: F401  (the constants and plan_join stay importable from here)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VVTTS_LIB") or os.path.join(_HERE, "libvvtts_hip.so")   # VVTTS_LIB: A/B builds in tools/
@@ -286,10 +287,6 @@ def vocos_cfg_from_spec(spec: ModelSpec) -> vv_vocos_cfg:
     return v
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
-
-
 def _dt(s) -> Tuple[int, torch.dtype]:
     if s in ("bf16", "bfloat16", torch.bfloat16, VV_BF16):
         return VV_BF16, torch.bfloat16
@@ -298,58 +295,8 @@ def _dt(s) -> Tuple[int, torch.dtype]:
     raise ValueError(f"acoustic dtype must be bf16 or fp32, got {s!r}")
 
 
-JOIN_MAX_N = 24576            # VV_JOIN_MAX_N of include/vvtts.h: the largest junction vv_join_chunks walks
-LOUD_RUN = 128                # VV_LOUD_RUN of include/vvtts.h: samples per independent run of the K-weighting recurrence
-_I64_MAX = (1 << 63) - 1
-
-
-def plan_join(requests, cross_fade_duration: float, sample_rate: int, align: int = 8):
-    """The host side of vv_join_chunks: every length is known here, so every junction size, position and final owner is too.
-    requests = per request a list of chunks (src_off, len) in joining order.  Returns (chunk rows WITHOUT tab_off resolved: column 5 holds
-    n, request rows, joined lengths, sorted distinct n, total output samples); request r's result starts at an ``align``-sample boundary.
-    Mirrors AudioProcessor.concatenate_with_crossfade_improved: n = min(int(cross_fade_duration * sample_rate), joined so far, len(next));
-    a request of one chunk is copied untouched; an empty chunk inside a longer request is refused (the reference raises on it in
-    fix_clipped_audio), and so is an empty request."""
-    cf = int(cross_fade_duration * sample_rate) if cross_fade_duration > 0 else 0
-    rows, reqs, lens, out_pos = [], [], [], 0
-    for r, chunks in enumerate(requests):
-        chunks = [(int(a), int(b)) for a, b in chunks]
-        if not chunks:
-            raise ValueError("join_chunks: a request without chunks")
-        c0 = len(rows)
-        if len(chunks) == 1:
-            so, ln = chunks[0]
-            if ln < 0:
-                raise ValueError("join_chunks: negative chunk length")
-            rows.append([so, ln, 0, 0, _I64_MAX, 0, 0, r])
-            total = ln
-        else:
-            total, pos_n = 0, []
-            for k, (so, ln) in enumerate(chunks):
-                if ln <= 0:
-                    raise ValueError("join_chunks: an empty chunk inside a request of two or more chunks")
-                n = min(cf, total, ln) if k else 0
-                if n > JOIN_MAX_N:
-                    raise ValueError(f"join_chunks: a junction of {n} samples, more than {JOIN_MAX_N}")
-                pos_n.append((total - n, n))
-                total = total - n + ln
-            fin = _I64_MAX
-            fins = []
-            for P, _n in reversed(pos_n):          # fin_k = the smallest position of a later chunk
-                fins.append(fin)
-                fin = min(fin, P)
-            fins.reverse()
-            for (so, ln), (P, n), f in zip(chunks, pos_n, fins):
-                rows.append([so, ln, P, n, f, n, 1, r])
-        out_pos = -(-out_pos // align) * align
-        reqs.append([c0, len(chunks), out_pos, total])
-        lens.append(total)
-        out_pos += total
-    return rows, reqs, lens, sorted({row[3] for row in rows if row[3] > 0}), out_pos
-
-
-class HipSynth:
-    """One GPU's synthesis engine: weights resident in HBM, three device-resident stages.
+class HipSynth(PcmStage):
+    """One GPU's synthesis engine: weights resident in HBM, three device-resident stages, and the PCM stage of pcm_stage.py.
 
     flat_weights: optional pre-filled flat uint8 device buffer (e.g. received by RCCL broadcast);
     otherwise ``weights`` (fp32 CPU dict) is packed and uploaded here.
@@ -357,6 +304,7 @@ class HipSynth:
 
     def __init__(self, spec: ModelSpec, weights: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda:0",
                  acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None, ode_method="euler"):
+        super().__init__()
         self.lib = load_library()
         if not torch.cuda.is_available():
             raise HipUnavailable("no HIP device is visible to torch; the synthesis hot path runs only on the GPU")
@@ -759,682 +707,6 @@ class HipSynth:
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
-
-    # ------------------------------------------------------------------ the output stage (N10): join, output rate, G.711
-    def _fade_tables(self, ns):
-        """c = cos(linspace(0, pi / 2, n)) ** 2 | s = sin(..) ** 2 per distinct n, computed by numpy on the HOST (the expression of the
-        reference's mix) and kept in one float64 device buffer: -> (buffer, {n: offset in doubles})."""
-        import numpy as np
-        cache = self.__dict__.setdefault("_fade_cache", {"off": {}, "host": [], "dev": None, "size": 0})
-        new = [n for n in ns if n not in cache["off"]]
-        if new:
-            if cache["size"] + 2 * sum(new) > (1 << 22):       # 32 MB of tables: start over
-                cache.update(off={}, host=[], dev=None, size=0)
-                new = list(ns)
-            for n in new:
-                theta = np.linspace(0, np.pi / 2, n)
-                cache["off"][n] = cache["size"]
-                cache["host"] += [np.cos(theta) ** 2, np.sin(theta) ** 2]
-                cache["size"] += 2 * n
-            cache["dev"] = torch.from_numpy(np.concatenate(cache["host"])).to(self.device)
-        if cache["dev"] is None:
-            cache["dev"] = torch.zeros(2, dtype=torch.float64, device=self.device)
-        return cache["dev"], cache["off"]
-
-    def join_chunks(self, pcm: torch.Tensor, requests, cross_fade_duration: float, sample_rate: int, out: Optional[torch.Tensor] = None,
-                    out_base: int = 0):
-        """AudioProcessor.concatenate_with_crossfade_improved for R requests in one call (vv_join_chunks), bit for bit.
-        pcm int16 on the device (vv_decode's plane, taken flat); requests = per request the (src_off, len) spans of its chunks in joining
-        order.  -> (out int16 flat, offsets, lengths): request r is out[offsets[r] : offsets[r] + lengths[r]].  out (optional) = an
-        existing flat int16 buffer, the results then start out_base samples into it (out_base % 8 == 0).  The rows are planned and
-        validated here, on the host, before anything is launched; the call never synchronises."""
-        assert pcm.is_cuda and pcm.dtype == torch.int16 and pcm.is_contiguous()
-        n_pcm = pcm.numel()
-        rows, reqs, lens, ns, total = plan_join(requests, cross_fade_duration, sample_rate)
-        if out_base < 0 or out_base % 8:
-            raise ValueError("join_chunks: out_base must be a non-negative multiple of 8 samples")
-        for row in rows:
-            if row[0] < 0 or row[0] + row[1] > n_pcm:
-                raise ValueError(f"join_chunks: chunk ({row[0]}, {row[1]}) does not fit the {n_pcm} samples of pcm")
-        if total + out_base >= 1 << 40 or len(rows) > 65535:
-            raise ValueError("join_chunks: too many chunks or samples for one call")
-        if out is None:
-            out = torch.empty((max(total + out_base, 8),), dtype=torch.int16, device=self.device)
-        assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.dim() == 1
-        if out.numel() < total + out_base:
-            raise ValueError(f"join_chunks: out holds {out.numel()} samples, {total + out_base} are needed")
-        fade, off = self._fade_tables(ns)
-        for row in rows:
-            row[5] = off[row[3]] if row[3] > 0 else 0
-        for rq in reqs:
-            rq[2] += out_base
-        rows_h, reqs_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8), torch.tensor(reqs, dtype=torch.int64).reshape(-1, 4)
-        rows_d, reqs_d = rows_h.to(self.device), reqs_h.to(self.device)
-        ws = torch.empty((2 * len(rows),), dtype=torch.int32, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_join_chunks(self.ctx, pcm.data_ptr(), n_pcm, rows_d.data_ptr(), rows_h.data_ptr(), len(rows),
-                                                reqs_d.data_ptr(), reqs_h.data_ptr(), len(reqs), fade.data_ptr(), fade.numel(), max(ns, default=0), max(r[1] for r in rows), out.data_ptr(),
-                                                out.numel(), ws.data_ptr(), self._stream()))
-        return out, [rq[2] for rq in reqs], lens
-
-    def _output_taps(self, src: int, dst: int):
-        from .core.audio_processor import output_design
-        cache = self.__dict__.setdefault("_out_taps", {})
-        if (src, dst) not in cache:
-            taps, up, down, skip = output_design(src, dst)
-            cache[(src, dst)] = (torch.from_numpy(taps).to(self.device), up, down, skip)
-        return cache[(src, dst)]
-
-    def pcm_resample(self, x: torch.Tensor, rows, src: int, dst: int, n_y: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Output rate (vv_pcm_resample): x int16 flat on the device at ``src`` Hz, rows = HOST rows {src_off, n_in, dst_off, n_out, m0, i0}
-        (include/vvtts.h) -> int16 [n_y] at ``dst`` Hz through voice_bank.resample_design(src, dst).  A whole clip is m0 = i0 = 0 and
-        n_out = ceil(n_in * up / down).  The rows are validated here (in range of both buffers, disjoint on the output).
-        out (optional) = an existing flat int16 device buffer to write into (n_y = its length); what the rows read must not be written."""
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous()
-        if int(src) == int(dst):
-            raise ValueError("pcm_resample: equal rates need no launch")
-        taps, up, down, skip = self._output_taps(int(src), int(dst))
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 6 for r in rows):
-            raise ValueError("pcm_resample: rows of 6 entries {src_off, n_in, dst_off, n_out, m0, i0}")
-        n_x = x.numel()
-        if out is not None:
-            assert out.is_cuda and out.dtype == torch.int16 and out.is_contiguous() and out.dim() == 1
-            n_y = out.numel()
-        n_y = max((r[2] + r[3] for r in rows), default=0) if n_y is None else int(n_y)
-        spans = []
-        for so, n_in, do, n_out, m0, i0 in rows:
-            if min(so, n_in, do, n_out, m0, i0) < 0 or so + n_in > n_x or do + n_out > n_y or (m0 + n_out + skip) * down >= 1 << 62:
-                raise ValueError(f"pcm_resample: row {[so, n_in, do, n_out, m0, i0]} does not fit the buffers ({n_x} in, {n_y} out)")
-            spans.append((do, do + n_out))
-        spans.sort()
-        if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
-            raise ValueError("pcm_resample: rows overlap on the output")
-        y = torch.empty((max(n_y, 1),), dtype=torch.int16, device=self.device) if out is None else out
-        d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 6).to(self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_resample(self.ctx, x.data_ptr(), n_x, d.data_ptr(), len(rows), max(r[3] for r in rows), taps.data_ptr(),
-                                                 taps.numel(), up, down, skip, y.data_ptr(), n_y, self._stream()))
-        return y[:n_y]
-
-    def pcm_encode(self, x: torch.Tensor, rows, encoding: str, n_y: Optional[int] = None) -> torch.Tensor:
-        """G.711 (vv_pcm_encode): x int16 flat on the device, rows = HOST rows {src_off, n, dst_off} -> uint8 [n_y]; encoding "ulaw" | "alaw",
-        bit-exact to audioop.lin2ulaw / lin2alaw at width 2.  The rows are validated here."""
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous()
-        kind = {"ulaw": 1, "alaw": 2}.get(encoding)
-        if kind is None:
-            raise ValueError("pcm_encode: encoding is 'ulaw' or 'alaw'")
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 3 for r in rows):
-            raise ValueError("pcm_encode: rows of 3 entries {src_off, n, dst_off}")
-        n_x = x.numel()
-        n_y = max((r[2] + r[1] for r in rows), default=0) if n_y is None else int(n_y)
-        spans = []
-        for so, n, do in rows:
-            if min(so, n, do) < 0 or so + n > n_x or do + n > n_y:
-                raise ValueError(f"pcm_encode: row {[so, n, do]} does not fit the buffers ({n_x} in, {n_y} out)")
-            spans.append((do, do + n))
-        spans.sort()
-        if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
-            raise ValueError("pcm_encode: rows overlap on the output")
-        y = torch.empty((max(n_y, 8),), dtype=torch.uint8, device=self.device)
-        d = torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_encode(self.ctx, x.data_ptr(), n_x, d.data_ptr(), len(rows), max(r[1] for r in rows), kind,
-                                               y.data_ptr(), n_y, self._stream()))
-        return y[:n_y]
-
-    # ------------------------------------------------------------------ loudness normalisation (N12)
-    def _loudness_tables(self, sr: int) -> torch.Tensor:
-        from .core.audio_processor import loudness_tables
-        cache = self.__dict__.setdefault("_loud_tables", {})
-        if int(sr) not in cache:
-            cache[int(sr)] = torch.from_numpy(loudness_tables(int(sr)).copy()).to(self.device)
-        return cache[int(sr)]
-
-    def pcm_loudness(self, x: torch.Tensor, rows, sr: int, targets, peak_dbfs: float = -1.0, out: Optional[torch.Tensor] = None,
-                     stats: bool = False):
-        """Loudness normalisation of R joined signals in one call (vv_pcm_loudness), bit for bit
-        core.audio_processor.normalize_loudness.  x int16 flat on the device at ``sr`` Hz; rows = HOST rows (src_off, n, dst_off);
-        targets = one LUFS value, or per request a value or None (None = measured, copied through unchanged); peak_dbfs = the sample-peak
-        ceiling.  out = None: a new buffer; out = "measure": nothing is written; out = a flat int16 device tensor (x itself with
-        dst_off == src_off = in place).  -> the output (None when measuring), and with ``stats`` also the R x 4 float64 DEVICE tensor
-        {zbar, kept, P, g}.  The rows are validated here; the call never synchronises."""
-        from .core.audio_processor import check_loudness, loudness_ceiling, loudness_target
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
-        sr = int(sr)
-        if sr % 10 or sr // 10 < LOUD_RUN:
-            raise ValueError(f"pcm_loudness: the sample rate must be a multiple of 10 Hz and at least {10 * LOUD_RUN} Hz, got {sr}")
-        sub = sr // 10
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 3 for r in rows) or len(rows) > 65535:
-            raise ValueError("pcm_loudness: 1 to 65535 rows of 3 entries {src_off, n, dst_off}")
-        R = len(rows)
-        if not isinstance(targets, (list, tuple)):
-            targets = [targets] * R
-        if len(targets) != R:
-            raise ValueError("pcm_loudness: one target per row")
-        par = []
-        for t in targets:
-            t, pk = check_loudness(t, peak_dbfs)
-            par.append([loudness_target(t), loudness_ceiling(pk)])
-        measure = isinstance(out, str) and out == "measure"
-        n_x = x.numel()
-        rps = -(-sub // LOUD_RUN)
-        full, runs, spans = [], 0, []
-        for so, n, do in rows:
-            if min(so, n, do) < 0 or so + n > n_x:
-                raise ValueError(f"pcm_loudness: row {[so, n, do]} does not fit the {n_x} samples of x")
-            full.append([so, n, do, runs])
-            runs += (n // sub) * rps + -(-(n % sub) // LOUD_RUN)
-            spans.append((do, do + n))
-        y = None
-        if not measure:
-            n_y = max(e for _b, e in spans)
-            if out is None:
-                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
-            else:
-                y = out
-                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
-            if y.numel() < n_y:
-                raise ValueError(f"pcm_loudness: out holds {y.numel()} samples, {n_y} are needed")
-            spans.sort()
-            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
-                raise ValueError("pcm_loudness: rows overlap on the output")
-            if y.data_ptr() == x.data_ptr() and any(r[0] != r[2] for r in rows):
-                raise ValueError("pcm_loudness: in place needs dst_off == src_off")
-        rows_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 4)
-        rows_d = rows_h.to(self.device)
-        par_d = torch.tensor(par, dtype=torch.float64).reshape(-1, 2).to(self.device)
-        st = torch.empty((R, 4), dtype=torch.float64, device=self.device)
-        ws_bytes = int(self.lib.vv_pcm_loudness_ws_bytes(runs, R))
-        ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_loudness(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, sub,
-                                                 self._loudness_tables(sr).data_ptr(), par_d.data_ptr(), _ptr(y), 0 if y is None else y.numel(),
-                                                 st.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
-        return (y, st) if stats else y
-
-    # ------------------------------------------------------------------ look-ahead peak limiter (N13)
-    def _limiter_tables(self, L: int):
-        """(window, taps, tile) for a look-ahead: the host's float64 tables on the device, cached per L."""
-        from .core.audio_processor import limiter_taps, limiter_window
-        cache = self.__dict__.setdefault("_limit_tables", {})
-        if int(L) not in cache:
-            cache[int(L)] = (torch.from_numpy(limiter_window(int(L)).copy()).to(self.device),
-                             torch.from_numpy(limiter_taps().copy()).to(self.device), int(self.lib.vv_pcm_limit_tile(int(L))))
-        return cache[int(L)]
-
-    def pcm_limit(self, x: torch.Tensor, rows, sr: int, peak_dbfs: float = -1.0, mode: str = "true", gain=1.0, meas: Optional[torch.Tensor] = None,
-                  targets=None, L: Optional[int] = None, out=None, stats: bool = False):
-        """The look-ahead limiter on R joined signals in one call (vv_pcm_limit), bit for bit
-        core.audio_processor.limit_peaks.  x int16 flat on the device at ``sr`` Hz; rows = HOST rows (src_off, n, dst_off) or
-        (src_off, n, dst_off, out_lo, out_n): the limiter runs over the row's n samples as a whole signal and y[out_lo, +out_n) of it is
-        written at dst_off.  mode "sample" | "true"; peak_dbfs = the ceiling; gain = the pre-gain (one value or one per row).
-        meas = the R x 4 device tensor of a pcm_loudness(out="measure", stats=True) call on the same rows, with targets = one LUFS value
-        or per row a value or None: rows with a target take the uncapped loudness gain from meas on the device, the others ``gain``.
-        L = the look-ahead in samples (None = 5 ms).  out = None: a new buffer; "measure": nothing is written; a flat int16 device tensor
-        (x itself with dst_off == src_off + out_lo = in place).  -> the output (None when measuring), and with ``stats`` also the R x 4
-        float64 DEVICE tensor {g, e_max, s_min, n_limited}.  The rows are validated here; the call never synchronises."""
-        from .core.audio_processor import (LIMITER_MODES, _check_lookahead, check_limiter, check_loudness, limiter_lookahead, loudness_ceiling,
-                                           loudness_target)
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
-        if check_limiter(mode) is None:
-            raise ValueError("pcm_limit: a mode is needed")
-        L = limiter_lookahead(sr) if L is None else _check_lookahead(L)
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) not in (3, 5) for r in rows) or len(rows) > 65535:
-            raise ValueError("pcm_limit: 1 to 65535 rows of 3 entries {src_off, n, dst_off} or 5 {src_off, n, dst_off, out_lo, out_n}")
-        rows = [r if len(r) == 5 else [r[0], r[1], r[2], 0, r[1]] for r in rows]
-        R = len(rows)
-        if not isinstance(targets, (list, tuple)):
-            targets = [targets] * R
-        gains = list(gain) if isinstance(gain, (list, tuple)) else [gain] * R
-        if len(targets) != R or len(gains) != R:
-            raise ValueError("pcm_limit: one target and one gain per row")
-        if meas is None and any(t is not None for t in targets):
-            raise ValueError("pcm_limit: a loudness target needs meas, the stats of a pcm_loudness measure call")
-        if meas is not None:
-            assert meas.is_cuda and meas.dtype == torch.float64 and meas.is_contiguous() and tuple(meas.shape) == (R, 4)
-        c = loudness_ceiling(check_loudness(None, peak_dbfs)[1])
-        par = []
-        for t, g0 in zip(targets, gains):
-            if isinstance(g0, bool) or not isinstance(g0, (int, float)) or not 0.0 < float(g0) < float("inf"):
-                raise ValueError("pcm_limit: the gain must be a positive finite number")
-            par.append([loudness_target(check_loudness(t, peak_dbfs)[0]), c, float(g0)])
-        window, taps, tile = self._limiter_tables(L)
-        measure = isinstance(out, str) and out == "measure"
-        n_x = x.numel()
-        samples, tiles, spans = 0, 0, []
-        for so, n, do, lo, on in rows:
-            if min(so, n, do, lo, on) < 0 or so + n > n_x or lo + on > n:
-                raise ValueError(f"pcm_limit: row {[so, n, do, lo, on]} does not fit the {n_x} samples of x or its own n")
-            samples += n
-            tiles += -(-n // tile)
-            if on:
-                spans.append((do, do + on))
-        y = None
-        if not measure:
-            n_y = max((e for _b, e in spans), default=0)
-            if out is None:
-                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
-            else:
-                y = out
-                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
-            if y.numel() < n_y:
-                raise ValueError(f"pcm_limit: out holds {y.numel()} samples, {n_y} are needed")
-            spans.sort()
-            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
-                raise ValueError("pcm_limit: rows overlap on the output")
-            if y.data_ptr() == x.data_ptr() and any(r[4] and r[2] != r[0] + r[3] for r in rows):
-                raise ValueError("pcm_limit: in place needs dst_off == src_off + out_lo")
-        rows_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 5)
-        rows_d = rows_h.to(self.device)
-        par_d = torch.tensor(par, dtype=torch.float64).reshape(-1, 3).to(self.device)
-        st = torch.empty((R, 4), dtype=torch.float64, device=self.device)
-        ws_bytes = int(self.lib.vv_pcm_limit_ws_bytes(samples, tiles, R))
-        ws = torch.empty((ws_bytes // 8 + 1,), dtype=torch.float64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_limit(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, L, LIMITER_MODES.index(mode),
-                                              window.data_ptr(), taps.data_ptr(), par_d.data_ptr(), _ptr(meas), _ptr(y),
-                                              0 if y is None else y.numel(), st.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
-        return (y, st) if stats else y
-
-    def limiter_stream_backend(self, sr: int, peak_dbfs: float = -1.0, mode: str = "true", L: Optional[int] = None):
-        """The ``backend(hist, out_lo, out_n)`` callable of core.audio_processor.LimiterStream on this device: the block and its context go
-        up, vv_pcm_limit runs over them as one signal and writes the window alone, which comes back."""
-        import numpy as np
-
-        def backend(hist, out_lo, out_n):
-            hist = np.ascontiguousarray(hist, dtype=np.int16).reshape(-1)
-            if out_n <= 0:
-                return np.zeros(0, np.int16)
-            y = self.pcm_limit(torch.from_numpy(hist).to(self.device), [[0, hist.size, 0, int(out_lo), int(out_n)]], sr, peak_dbfs, mode, L=L)
-            return y[: int(out_n)].cpu().numpy()
-
-        return backend
-
-    # ------------------------------------------------------------------ pitch and tempo (N14)
-    def pcm_stretch(self, x: torch.Tensor, rows, out: Optional[torch.Tensor] = None):
-        """The WSOLA time stretch on R joined signals in one call (vv_pcm_stretch), bit for bit
-        core.audio_processor.time_stretch.  x int16 flat on the device; rows = HOST rows (src_off, n, dst_off, p, q): x[src_off, +n) is
-        stretched by p / q to ceil(n p / q) samples at dst_off.  out = None: a new buffer; "positions": the search alone, no sample is
-        written and y is None; or a flat int16 device tensor that does not overlap x.  -> (y, pos, pos_offs): pos is the int32 device tensor of every frame position, request r's pos_0 ... pos_M are
-        pos[pos_offs[r] : pos_offs[r + 1]].  The rows are validated here; the call never synchronises."""
-        from .core.audio_processor import WSOLA_HS, check_stretch_ratio, wsola_window
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 5 for r in rows) or len(rows) > 65535:
-            raise ValueError("pcm_stretch: 1 to 65535 rows of 5 entries {src_off, n, dst_off, p, q}")
-        n_x, spans, full, pos_offs = x.numel(), [], [], [0]
-        for so, n, do, p, q in rows:
-            check_stretch_ratio(p, q)
-            if min(so, n, do) < 0 or so + n > n_x or n > 1 << 30:
-                raise ValueError(f"pcm_stretch: row {[so, n, do, p, q]} does not fit the {n_x} samples of x")
-            n_s = -(-n * p // q)
-            if n_s:
-                spans.append((do, do + n_s))
-            full.append([so, n, do, p, q, pos_offs[-1]])
-            pos_offs.append(pos_offs[-1] + -(-n_s // WSOLA_HS) + 1)
-        n_y, y = max((e for _b, e in spans), default=0), None
-        if not (isinstance(out, str) and out == "positions"):
-            if out is None:
-                y = torch.empty((max(n_y, 4),), dtype=torch.int16, device=self.device)
-            else:
-                y = out
-                assert y.is_cuda and y.dtype == torch.int16 and y.is_contiguous() and y.dim() == 1
-            if y.numel() < n_y:
-                raise ValueError(f"pcm_stretch: out holds {y.numel()} samples, {n_y} are needed")
-            spans.sort()
-            if any(spans[i][0] < spans[i - 1][1] for i in range(1, len(spans))):
-                raise ValueError("pcm_stretch: rows overlap on the output")
-            if y.data_ptr() < x.data_ptr() + 2 * n_x and x.data_ptr() < y.data_ptr() + 2 * y.numel():
-                raise ValueError("pcm_stretch: out overlaps x (the stretch is not in place)")
-        if "_wsola_window" not in self.__dict__:
-            self._wsola_window = torch.from_numpy(wsola_window().copy()).to(self.device)
-        R = len(full)
-        rows_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 6)
-        rows_d = rows_h.to(self.device)
-        pos = torch.empty((pos_offs[-1],), dtype=torch.int32, device=self.device)
-        ws = torch.empty((int(self.lib.vv_pcm_stretch_ws_bytes(R)) // 8 + 1,), dtype=torch.int64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_pcm_stretch(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, self._wsola_window.data_ptr(),
-                                                _ptr(y), 0 if y is None else y.numel(), pos.data_ptr(), pos.numel(), ws.data_ptr(), ws.numel() * 8,
-                                                self._stream()))
-        return y, pos, pos_offs
-
-    def _prosody(self, buf: torch.Tensor, offs, lens, pitch, tempo):
-        """The prosody step of finish_output: -> (new buffer, offsets, lengths).  Every request gets its place in a new buffer, on 8-sample
-        boundaries as in plan_join: a request with a stretch alone is stretched into it, one with a pitch is stretched into an
-        intermediate region behind it and converted from there (one vv_pcm_resample call per distinct pitch ratio), one without prosody
-        is copied sample for sample."""
-        from .core.audio_processor import prosody_plan
-        R = len(lens)
-        plans = [prosody_plan(lens[i], pitch[i], tempo[i]) for i in range(R)]
-        new_offs, new_lens, end = [], [], 0
-        for i in range(R):
-            end = -(-end // 8) * 8
-            new_offs.append(end)
-            new_lens.append(lens[i] if plans[i] is None else plans[i].n_f)
-            end += new_lens[i]
-        base = -(-end // 8) * 8
-        mid, tmp = {}, base                                # behind the results: the stretched signals that still await their rate conversion
-        for i, pl in enumerate(plans):
-            if pl is not None and pl.p != pl.q and pl.p_r != pl.q_r:
-                mid[i] = tmp
-                tmp = -(-(tmp + pl.n_s) // 8) * 8
-        new = torch.empty((max(tmp, 8),), dtype=torch.int16, device=self.device)
-        stretch, convert = [], {}
-        for i, pl in enumerate(plans):
-            if pl is None:
-                new[new_offs[i]: new_offs[i] + lens[i]].copy_(buf[offs[i]: offs[i] + lens[i]])
-                continue
-            if pl.p != pl.q:
-                stretch.append([offs[i], lens[i], mid.get(i, new_offs[i]), pl.p, pl.q])
-            if pl.p_r != pl.q_r:               # from the stretched signal, or straight from the joined one when tempo == pitch ratio
-                convert.setdefault((pl.p_r, pl.q_r), []).append((i, pl.p != pl.q))
-        if stretch:
-            self.pcm_stretch(buf, stretch, out=new)
-        for (p_r, q_r), items in sorted(convert.items()):
-            for from_new in (True, False):
-                rows = [[mid[i] - base if from_new else offs[i], plans[i].n_s if from_new else lens[i], new_offs[i], plans[i].n_f, 0, 0]
-                        for i, stretched in items if stretched == from_new and plans[i].n_f > 0]
-                if rows:                       # source and destination are separate parts of ``new``
-                    self.pcm_resample(new[base:] if from_new else buf, rows, p_r, q_r, out=new[:base])
-        return new[:max(base, 8)], new_offs, new_lens
-
-    # ------------------------------------------------------------------ FLAC output (N15)
-    def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int, lpc_order: int = 0):
-        """FLAC frames of R final signals in one call (vv_pcm_flac), byte for byte core.audio_processor.flac_encode_frames.
-        lpc_order 1 ... 12: with LPC subframes (vv_pcm_flac_lpc; N16), byte for byte the mirror with that order; 0 = vv_pcm_flac as ever.
-        x int16 flat on the device; rows = HOST rows (src_off, n, frame0, last): x[src_off, +n) becomes ceil(n / 4096) frames numbered from
-        frame0; last = 0 = a block of a stream (n a multiple of 4096).  -> (y, info): y the uint8 device buffer with the frames of all rows
-        back to back, info the (R + 1) x 3 int64 device tensor {offset of the row's first frame, smallest frame, largest frame} with
-        info[R][0] = the total bytes.  The rows are validated here; the call never synchronises."""
-        from .core.audio_processor import FLAC_BLOCK, FLAC_MAX_RATE, check_flac_lpc_order, flac_frame_bound
-        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
-        lpc_order = check_flac_lpc_order(lpc_order)
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 4 for r in rows) or len(rows) > 65535:
-            raise ValueError("pcm_flac: 1 to 65535 rows of 4 entries {src_off, n, frame0, last}")
-        if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or not 1 <= int(sample_rate) <= FLAC_MAX_RATE:
-            raise ValueError(f"pcm_flac: a sample rate in 1 ... {FLAC_MAX_RATE} Hz is needed")
-        n_x, n_y, frames = x.numel(), 0, 0
-        for so, n, f0, last in rows:
-            nf = -(-n // FLAC_BLOCK)
-            if so < 0 or n < 1 or so + n > n_x or f0 < 0 or f0 + nf > 1 << 31 or last not in (0, 1) or (not last and n % FLAC_BLOCK):
-                raise ValueError(f"pcm_flac: row {[so, n, f0, last]} does not fit the {n_x} samples of x, the frame numbers below 2^31 or "
-                                 f"whole frames of {FLAC_BLOCK} samples where last = 0")
-            n_y += (nf - 1) * flac_frame_bound(FLAC_BLOCK) + flac_frame_bound(n - (nf - 1) * FLAC_BLOCK)
-            frames += nf
-        R = len(rows)
-        rows_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 4)
-        rows_d = rows_h.to(self.device)
-        y = torch.empty((n_y,), dtype=torch.uint8, device=self.device)
-        info = torch.empty((R + 1, 3), dtype=torch.int64, device=self.device)
-        ws_bytes = self.lib.vv_pcm_flac_lpc_ws_bytes(frames, R, lpc_order) if lpc_order else self.lib.vv_pcm_flac_ws_bytes(frames, R)
-        ws = torch.empty((int(ws_bytes) // 8 + 1,), dtype=torch.int64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            if lpc_order:
-                self._check(self.lib.vv_pcm_flac_lpc(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), lpc_order,
-                                                     y.data_ptr(), n_y, info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
-            else:
-                self._check(self.lib.vv_pcm_flac(self.ctx, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, int(sample_rate), y.data_ptr(), n_y,
-                                                 info.data_ptr(), ws.data_ptr(), ws.numel() * 8, self._stream()))
-        return y, info
-
-    # ------------------------------------------------------------------ FLAC input (N17)
-    @staticmethod
-    def _flac_rows(rows, n_bytes: int, name: str):
-        from .core.audio_processor import FLAC_MAX_CLIP
-        rows = [[int(v) for v in r] for r in rows]
-        if not rows or any(len(r) != 8 for r in rows) or len(rows) > 65535:
-            raise ValueError(f"{name}: 1 to 65535 rows of 8 entries {{byte offset, n_bytes, channels, bits, min block, max block, rate, total}}")
-        at = 0
-        for r in rows:
-            off, n, ch, bits, lo, hi, rate, total = r
-            if (off < at or off % 4 or n < 0 or off + n + 8 > n_bytes or not 1 <= ch <= 8 or bits not in (8, 16, 24) or not 16 <= hi <= 65535
-                    or not 0 <= lo <= hi or not 1 <= rate <= 1048575 or not 0 <= total <= FLAC_MAX_CLIP):
-                raise ValueError(f"{name}: row {r} does not fit the {n_bytes} bytes of data (ascending, 4-byte aligned, 8 bytes of padding behind "
-                                 f"the last clip) or the decoder's limits")
-            at = off + n
-        return rows
-
-    def flac_index(self, data: torch.Tensor, rows):
-        """vv_flac_index: the frames of R FLAC clips whose frame bytes lie back to back in ``data`` (uint8 on the device,
-        each clip 4-byte aligned, 8 bytes of padding behind the last).  rows = HOST rows {byte offset, n_bytes, channels, bits, min block,
-        max block, rate, total}.  -> (info R x 4 int64 on the device {status, byte, frames, samples}, the workspace flac_decode consumes).
-        The rows are validated here before anything is launched; the call never synchronises."""
-        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
-        n_bytes = data.numel()
-        if not 8 <= n_bytes <= (1 << 31) - 64 or data.data_ptr() % 8:
-            raise ValueError("flac_index: 8 ... 2^31 - 64 bytes of data, 8-byte aligned")
-        rows = self._flac_rows(rows, n_bytes, "flac_index")
-        R = len(rows)
-        rows_h = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8)
-        rows_d = rows_h.to(self.device)
-        info = torch.empty((R, 4), dtype=torch.int64, device=self.device)
-        ws = torch.empty((int(self.lib.vv_flac_index_ws_bytes(n_bytes, R)) // 8 + 1,), dtype=torch.int64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_flac_index(self.ctx, data.data_ptr(), n_bytes, rows_d.data_ptr(), rows_h.data_ptr(), R, info.data_ptr(),
-                                               ws.data_ptr(), ws.numel() * 8, self._stream()))
-        return info, (ws, rows_h, rows_d)
-
-    def flac_decode(self, data: torch.Tensor, index, lay, pcm: torch.Tensor):
-        """vv_flac_decode: the clips ``flac_index`` passed, into ``pcm`` (uint8 on the device) as the interleaved little-endian PCM
-        vv_ingest_pcm reads.  index = flac_index's second result; lay = HOST rows {pcm byte offset, frames, samples} per clip (a refused
-        clip: frames = samples = 0).  -> info2 R x 2 int64 on the device {status, byte}: non-zero where a restored sample left its range."""
-        ws, rows_h, rows_d = index
-        assert data.is_cuda and data.dtype == torch.uint8 and pcm.is_cuda and pcm.dtype == torch.uint8 and pcm.is_contiguous() and pcm.dim() == 1
-        R, n_pcm = rows_h.shape[0], pcm.numel()
-        lay = [[int(v) for v in r] for r in lay]
-        if len(lay) != R or any(len(r) != 3 for r in lay):
-            raise ValueError("flac_decode: one row {pcm byte offset, frames, samples} per clip")
-        full, F, S, P, at = [], 0, 0, 0, 0
-        for (off, frames, samples), row in zip(lay, rows_h.tolist()):
-            nbytes = samples * row[2] * (4 if row[3] == 24 else row[3] // 8)
-            if off < at or frames < 0 or samples < frames or off + nbytes > n_pcm:
-                raise ValueError(f"flac_decode: row {[off, frames, samples]} does not fit the {n_pcm} bytes of pcm, in ascending order")
-            full.append([off, frames, samples, F, P, S])
-            at, F, S, P = off + nbytes, F + frames, S + samples, P + samples * row[2]
-        lay_h = torch.tensor(full, dtype=torch.int64).reshape(-1, 6)
-        lay_d = lay_h.to(self.device)
-        info2 = torch.empty((R, 2), dtype=torch.int64, device=self.device)
-        ws2 = torch.empty((int(self.lib.vv_flac_decode_ws_bytes(P, F)) // 8 + 1,), dtype=torch.int64, device=self.device)
-        with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_flac_decode(self.ctx, data.data_ptr(), data.numel(), rows_d.data_ptr(), rows_h.data_ptr(), R, lay_d.data_ptr(),
-                                                lay_h.data_ptr(), ws.data_ptr(), ws.numel() * 8, pcm.data_ptr(), n_pcm, info2.data_ptr(),
-                                                ws2.data_ptr(), ws2.numel() * 8, self._stream()))
-        return info2
-
-    def flac_clips(self, files, pcm: Optional[torch.Tensor] = None, pcm_offsets=None):
-        """Complete FLAC files (bytes) -> their PCM on the device, without a decoded sample crossing the bus: container parsing on the
-        host, one upload of the frame bytes, flac_index, ONE small readback of info (32 R bytes, the synchronisation), flac_decode, one
-        small readback of info2.  -> (pcm uint8 on the device, [per file: (byte offset, frames, width, rate, channels) or the FlacError
-        the mirror would raise]).  A refused file does not disturb the others.  With ``pcm`` / ``pcm_offsets`` None the buffer is laid
-        out here (4-byte aligned clips); else ``pcm_offsets(sizes) -> (buffer, offsets)`` lets the caller place the clips in a buffer
-        it shares with other PCM."""
-        from .core.audio_processor import FlacError, flac_container
-        infos, parts, rows, pos = [], [], [], 0
-        for data in files:
-            data = bytes(data)
-            try:
-                fi = flac_container(data)
-            except FlacError as e:
-                infos.append(e)
-                continue
-            infos.append(fi)
-            body = data[fi.start:]
-            rows.append([pos, len(body), fi.channels, fi.bits, fi.min_block, fi.max_block, fi.rate, fi.total])
-            parts.append(body + b"\0" * (-len(body) % 4))
-            pos += len(parts[-1])
-        live = [i for i, fi in enumerate(infos) if not isinstance(fi, FlacError)]
-        out, sizes, lay = list(infos), [0] * len(files), []
-        if live:
-            buf = torch.frombuffer(bytearray(b"".join(parts) + b"\0" * (-pos % 8 + 8)), dtype=torch.uint8).to(self.device)
-            info_d, index = self.flac_index(buf, rows)
-            info = info_d.cpu().tolist()                          # the one synchronisation in front of the layout
-            for i, (status, byte, frames, samples), row in zip(live, info, rows):
-                if status:
-                    out[i] = FlacError(status, infos[i].start + byte)
-                    lay.append([0, 0])
-                else:
-                    sizes[i] = samples * row[2] * (4 if row[3] == 24 else row[3] // 8)
-                    lay.append([frames, samples])
-        if pcm_offsets is None:
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += n + (-n % 4)
-            pcm = torch.empty((max(at, 8),), dtype=torch.uint8, device=self.device)
-        else:
-            pcm, offs = pcm_offsets(sizes)
-        if live:
-            at = 0
-            for j, i in enumerate(live):                          # a refused clip sits, empty, where the previous one ended
-                if lay[j][1]:
-                    at = offs[i]
-                lay[j] = [at] + lay[j]
-                at += sizes[i]
-            info2 = self.flac_decode(buf, index, lay, pcm).cpu().tolist()
-            for j, i in enumerate(live):
-                if isinstance(out[i], FlacError):
-                    continue
-                if info2[j][0]:
-                    out[i] = FlacError(info2[j][0], infos[i].start + info2[j][1])
-                else:
-                    out[i] = (offs[i], lay[j][2], {8: 1, 16: 2, 24: 4}[rows[j][3]], rows[j][6], rows[j][2])
-        return pcm, out
-
-    def _flac_files(self, buf: torch.Tensor, offs, lens, sample_rate: int, lpc_order: int = 0):
-        """The last step of finish_output with encoding "flac": one vv_pcm_flac (lpc_order > 0: vv_pcm_flac_lpc) call over the requests, ONE small copy of info (24 (R + 1)
-        bytes, the one synchronisation), one copy of exactly info[R][0] bytes; the host puts each request's stream header in front, with
-        its true sample count and its frame sizes.  An empty request is a header alone."""
-        import numpy as np
-        from .core.audio_processor import flac_stream_header
-        sel = [i for i, n in enumerate(lens) if n > 0]
-        frames = {}
-        if sel:
-            y, info = self.pcm_flac(buf, [[offs[i], lens[i], 0, 1] for i in sel], sample_rate, lpc_order)
-            info = info.cpu().numpy()
-            total = int(info[len(sel), 0])
-            host = y[:total].cpu().numpy()
-            for j, i in enumerate(sel):
-                end = int(info[j + 1, 0]) if j + 1 < len(sel) else total
-                frames[i] = (host[int(info[j, 0]): end], int(info[j, 1]), int(info[j, 2]))
-        out = []
-        for i, n in enumerate(lens):
-            data, lo, hi = frames.get(i, (np.zeros(0, np.uint8), 0, 0))
-            out.append(np.concatenate([np.frombuffer(flac_stream_header(sample_rate, n, lo, hi), np.uint8), data]))
-        return out
-
-    def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0):
-        """The whole output stage of R requests on the caller's stream: join (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
-        (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
-        spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
-        new is called): core.audio_processor.prosody_plan turns them into a WSOLA stretch and a rate conversion on the joined signal, and
-        every later step runs on the result, so levels and the ceiling are those of what is heard.
-        loudness = a target in LUFS for every request, or a per-request list with None entries (N12; None = nothing new is called);
-        peak_dbfs = its sample-peak ceiling.  limiter = None | "sample" | "true" for every request, or a per-request list (N13; None =
-        nothing new is called): a request with a limiter is measured only (pcm_loudness, out="measure") and takes its uncapped loudness
-        gain, or the gain 1 without a target, through pcm_limit in place; the others keep the capped gain of N12.
-        encoding "flac" (N15): the final PCM goes through pcm_flac instead of the one copy: a small copy of the frames' sizes, then a copy
-        of exactly the frames' bytes; each request comes back as a complete FLAC file.  flac_lpc_order 1 ... 12 (N16) adds LPC subframes
-        (vv_pcm_flac_lpc instead of vv_pcm_flac) and is refused with another encoding.
-        -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
-        from .core.audio_processor import check_flac_lpc_order, resample_len
-        if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
-            raise ValueError("finish_output: flac_lpc_order belongs to the encoding 'flac'")
-        buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
-        pitch, tempo = [list(v) if isinstance(v, (list, tuple)) else [v] * len(lens) for v in (pitch, tempo)]
-        if len(pitch) != len(lens) or len(tempo) != len(lens):
-            raise ValueError("finish_output: one pitch and one tempo entry per request")
-        if any(v is not None for v in pitch + tempo):
-            buf, offs, lens = self._prosody(buf, offs, lens, pitch, tempo)
-        if isinstance(loudness, (list, tuple)):
-            if len(loudness) != len(lens):
-                raise ValueError("finish_output: one loudness entry per request")
-            if all(v is None for v in loudness):
-                loudness = None
-        if isinstance(limiter, (list, tuple)):
-            if len(limiter) != len(lens):
-                raise ValueError("finish_output: one limiter entry per request")
-            if all(v is None for v in limiter):
-                limiter = None
-        if limiter is not None:
-            from .core.audio_processor import LIMITER_MODES, check_limiter
-            lims = [check_limiter(v) for v in (limiter if isinstance(limiter, (list, tuple)) else [limiter] * len(lens))]
-            louds = list(loudness) if isinstance(loudness, (list, tuple)) else [loudness] * len(lens)
-            plain = [i for i in range(len(lens)) if lims[i] is None and louds[i] is not None]
-            if plain:                      # the requests without a limiter: the capped gain of N12, as below
-                self.pcm_loudness(buf, [[offs[i], lens[i], offs[i]] for i in plain], sample_rate, [louds[i] for i in plain], peak_dbfs, out=buf)
-            for mode in LIMITER_MODES:
-                sel = [i for i in range(len(lens)) if lims[i] == mode]
-                if not sel:
-                    continue
-                rows, tg, meas = [[offs[i], lens[i], offs[i]] for i in sel], [louds[i] for i in sel], None
-                if any(t is not None for t in tg):
-                    _none, meas = self.pcm_loudness(buf, rows, sample_rate, tg, peak_dbfs, out="measure", stats=True)
-                self.pcm_limit(buf, rows, sample_rate, peak_dbfs, mode, meas=meas, targets=tg if meas is not None else None, out=buf)
-        elif loudness is not None:         # in place on the joined buffer: the apply pass is elementwise
-            sel = [i for i in range(len(lens)) if not isinstance(loudness, (list, tuple)) or loudness[i] is not None]
-            tg = [loudness[i] for i in sel] if isinstance(loudness, (list, tuple)) else loudness
-            self.pcm_loudness(buf, [[offs[i], lens[i], offs[i]] for i in sel], sample_rate, tg, peak_dbfs, out=buf)
-        if rate is not None and int(rate) != int(sample_rate):
-            _taps, up, down, _skip = self._output_taps(int(sample_rate), int(rate))
-            rows, pos = [], 0
-            for o, n in zip(offs, lens):
-                n_out = resample_len(n, up, down)
-                rows.append([o, n, pos, n_out, 0, 0])
-                pos += n_out
-            buf = self.pcm_resample(buf, rows, sample_rate, rate, n_y=pos) if pos else buf[:0]
-            offs, lens = [r[2] for r in rows], [r[3] for r in rows]
-        if encoding == "flac":             # N15: variable-length output -- the frames' total comes back first, then exactly that many bytes
-            return self._flac_files(buf, offs, lens, int(sample_rate) if rate is None else int(rate), flac_lpc_order)
-        if encoding != "pcm16":
-            rows, pos = [], 0
-            for o, n in zip(offs, lens):
-                rows.append([o, n, pos])
-                pos += n
-            buf = self.pcm_encode(buf, rows, encoding, n_y=pos) if pos else torch.empty((0,), dtype=torch.uint8, device=self.device)
-            offs = [r[2] for r in rows]
-        host = buf.cpu().numpy()
-        return [host[o: o + n] for o, n in zip(offs, lens)]
-
-    def output_stream_backends(self, sample_rate: int, rate: Optional[int], encoding: str, max_upload: int = 1 << 18):
-        """(resample, encode) callables for core.audio_processor.OutputStream on this device: host blocks go up in pieces of at most
-        ``max_upload`` samples (0.5 MB), through vv_pcm_resample / vv_pcm_encode, and come back.  With encoding "flac" the second one is
-        the ``encode(pcm, frame0, last[, lpc_order])`` of core.audio_processor.FlacStream (vv_pcm_flac, vv_pcm_flac_lpc), which sits behind
-        the OutputStream."""
-        import numpy as np
-
-        def up_(x):
-            parts = [torch.from_numpy(np.ascontiguousarray(x[i: i + max_upload])).to(self.device) for i in range(0, x.size, max_upload)]
-            return parts[0] if len(parts) == 1 else torch.cat(parts)
-
-        def resample(x, m0, i0, n_out):
-            x = np.asarray(x, dtype=np.int16).reshape(-1)
-            if n_out <= 0:
-                return np.zeros(0, np.int16)
-            xd = up_(x) if x.size else torch.zeros((8,), dtype=torch.int16, device=self.device)
-            return self.pcm_resample(xd, [[0, x.size, 0, n_out, m0, i0]], sample_rate, rate, n_y=n_out).cpu().numpy()
-
-        def encode(y):
-            y = np.asarray(y, dtype=np.int16).reshape(-1)
-            if y.size == 0:
-                return np.zeros(0, np.uint8)
-            return self.pcm_encode(up_(y), [[0, y.size, 0]], encoding, n_y=y.size).cpu().numpy()
-
-        def flac(pcm, frame0, last, lpc_order=0):      # FlacStream's back end (N15, N16): whole blocks (last = False) and the final short frame alike
-            pcm = np.asarray(pcm, dtype=np.int16).reshape(-1)
-            if pcm.size == 0:
-                return np.zeros(0, np.uint8)
-            y, info = self.pcm_flac(up_(pcm), [[0, pcm.size, int(frame0), 1 if last else 0]], sample_rate if rate is None else rate, lpc_order)
-            return y[: int(info[1, 0])].cpu().numpy()
-
-        return (resample if rate is not None and int(rate) != int(sample_rate) else None), \
-            (flac if encoding == "flac" else encode if encoding != "pcm16" else None)
 
     # ------------------------------------------------------------------ hipGraph-captured vocoder step (config 5)
     def capture_decode(self, B: int, N: int, t_gen_max: int) -> "GraphedDecode":
