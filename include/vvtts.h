@@ -776,6 +776,39 @@ VV_API int vv_flac_decode(vv_ctx* ctx, const uint8_t* data, int64_t n_bytes, con
                           const int64_t* lay_host, const void* ws, uint64_t ws_bytes, uint8_t* pcm, int64_t n_pcm, int64_t* info2, void* ws2,
                           uint64_t ws2_bytes, void* stream);
 
+/* ---- N18 formant-preserving pitch shift: the envelope correction behind the rate conversion that makes the pitch.  x is a
+ * request's joined signal (n samples), y what the prosody step made of it (n_f = ceil(n td / tn) samples, tn / td the tempo fraction), z the
+ * result: y filtered so that its LPC envelope is x's again.  The arithmetic is pinned by core/audio_processor.py (formant_filters,
+ * apply_formant_filters), which the kernels equal bit for bit.  With P, NA, H, L below, M = ceil(n_f / H), per frame m = 0 ... M and for
+ * each of (s, c) = (y, m H) and (x, floor(m H tn / td)), s = 0 outside the signal:
+ *     d[k] = s[c - NA/2 + k] - s[c - NA/2 + k - 1];  xw[k] = rint(wa[k] d[k]) as an integer;  R[l] = sum_{k >= l} xw[k] xw[k - l], l <= P, exact
+ *     flat if R[0] = 0; else Rf[0] = R[0] + R[0] 2^-20 and the Levinson recurrence of N16 up to order P; flat if err is ever not > 0
+ *     A[0] = 1, A[k] = -(a[k] g[k])
+ * per frame:  r[t] = (t <= P ? A_y[t] : 0) - A_x[1] r[t - 1] - ... - A_x[min(t, P)] r[t - min(t, P)], t < L (k ascending);
+ *             h_m[t] = sqrt(err_x / err_y) r[t]; either analysis flat: h_m = the unit impulse
+ * per sample i < n_f, m = i / H + 1, k = i - (m - 1) H:  v_a = sum_{j < L} h_{m-1}[j] y[i - j], v_b with h_m, each from +0.0 with j
+ *             ascending, y = 0 in front of the signal;  z[i] = clamp(rint(window[k + H] v_a + window[k] v_b), -32768, 32767)
+ * in float64, every operation rounded on its own (no fused multiply-add), ties to even.  The call never synchronises and reads nothing back.
+ *   x, y     int16, the signals before and after the prosody step
+ *   rows     R x 7 int64 {x_off, n, y_off, n_f, z_off, tn, td} in device memory and the same rows in HOST memory (rows_host, checked by the
+ *            call)
+ *   wa       VV_FORMANT_NA float64 on the device: 0.5 - 0.5 cos(2 pi k / NA);  g: VV_FORMANT_P + 1 float64: g[0] = 1, g[k] = g[k - 1] * 0.995
+ *            (audio_processor.formant_tables);  window: the VV_WSOLA_N float64 of vv_pcm_stretch.  The device evaluates no cosine, no power
+ *   z        int16 [n_z], must overlap neither x nor y; nothing outside the rows' outputs is written.  z may start at any even byte
+ *   h_out    NULL, or float64 [n_h] for a test: every frame's L taps, request after request, M + 1 frames each
+ *   ws       ws_bytes >= vv_pcm_formant_ws_bytes(sum of M + 1, R), 8-byte aligned
+ * -22, and nothing is launched, for no context, R < 1 or R > 65535, a null or misaligned pointer, a ws or an h_out that is too small, a
+ * negative field, n > 2^30, tn or td outside 1 ... VV_WSOLA_MAX_PQ, n_f != ceil(n td / tn), a row outside n_x / n_y / n_z, rows that overlap
+ * on z, z overlapping x or y. */
+#define VV_FORMANT_P 24
+#define VV_FORMANT_NA 1024
+#define VV_FORMANT_H 256
+#define VV_FORMANT_L 2048
+VV_API uint64_t vv_pcm_formant_ws_bytes(int64_t total_frames, int R);
+VV_API int vv_pcm_formant(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int16_t* y, int64_t n_y, const int64_t* rows,
+                          const int64_t* rows_host, int R, const double* wa, const double* g, const double* window, int16_t* z, int64_t n_z,
+                          double* h_out, int64_t n_h, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,7 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "formants", "t0", "n_req")
 
     def __init__(self):
         self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
@@ -43,6 +43,7 @@ class _Batch:
         self.louds = []               # per REQUEST: its own loudness target (N12) or None
         self.lims = []                # per REQUEST: its own limiter mode (N13) or None
         self.pitches, self.tempos = [], []      # per REQUEST: its own pitch / tempo (N14) or None
+        self.formants = []                      # per REQUEST: its own formants mode (N18) or None
 
 
 class BatchingFrontend:
@@ -76,7 +77,7 @@ class BatchingFrontend:
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
                cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
                loudness: Optional[float] = None, limiter: Optional[str] = None, pitch: Optional[float] = None, tempo: Optional[float] = None,
-               **voice) -> Future:
+               formants: Optional[str] = None, **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
@@ -86,7 +87,9 @@ class BatchingFrontend:
         None = the engine's ``output_loudness``), measured and applied to this request alone in the batch's one finish_output call.
         ``limiter``: this request's limiter, "sample" or "true" (None = the engine's ``output_limiter``), carried the same way.
         ``pitch`` (semitones, -12 ... 12) / ``tempo`` (0.5 ... 2.0): this request's prosody (None = the engine's
-        ``output_pitch`` / ``output_tempo``), applied to this request alone; its batch neighbours are copied untouched."""
+        ``output_pitch`` / ``output_tempo``), applied to this request alone; its batch neighbours are copied untouched.
+        ``formants``: "shift" or "keep" (None = the engine's ``output_formants``): what this request's pitch does to its
+        spectral envelope, carried the same way."""
         fut: Future = Future()
         try:
             from .core.audio_processor import check_loudness
@@ -95,6 +98,8 @@ class BatchingFrontend:
             check_limiter(limiter)
             from .core.audio_processor import check_prosody
             pitch, tempo = check_prosody(pitch, tempo)
+            from .core.audio_processor import check_formants
+            formants = None if formants is None else check_formants(formants)
             from .model_spec import check_apg, check_cfg_interval
             cfg_interval = check_cfg_interval(cfg_interval)
             check_apg(apg_eta, apg_norm)
@@ -114,7 +119,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -147,7 +152,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo = req
+        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -184,6 +189,7 @@ class BatchingFrontend:
         batch.lims.append(limiter)
         batch.pitches.append(pitch)
         batch.tempos.append(tempo)
+        batch.formants.append(formants)
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -334,7 +340,8 @@ class BatchingFrontend:
         if isinstance(waves, tuple):          # device output stage: (device PCM, spans) -- one finish_output call for the whole batch
             try:
                 finals = eng._finish_device(waves, [n for _f, n in batch.plans], loudness=batch.louds, limiter=batch.lims,
-                                            pitch=batch.pitches, tempo=batch.tempos)
+                                            pitch=batch.pitches, tempo=batch.tempos,
+                                            **({} if all(v is None for v in batch.formants) else {"formants": batch.formants}))
             except Exception as e:        # noqa: BLE001
                 self._fail(batch, e)
                 return
@@ -343,9 +350,9 @@ class BatchingFrontend:
                 self.requests_done += 1
             return
         pos = 0
-        for (fut, n), loud, lim, pit, tem in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos):
+        for (fut, n), loud, lim, pit, tem, fmt in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos, batch.formants):
             try:
-                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem)
+                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem, **({} if fmt is None else {"formants": fmt}))
                 fut.set_result((final, time.time() - batch.t0))
             except Exception as e:        # noqa: BLE001
                 fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))

@@ -1351,11 +1351,13 @@ def time_stretch(pcm, p: int, q: int):
     return np.clip(np.rint(tail + head), -32768.0, 32767.0).astype(np.int16), pos.astype(np.int32)
 
 
-def shift_prosody(pcm, pitch=None, tempo=None) -> np.ndarray:
+def shift_prosody(pcm, pitch=None, tempo=None, formants="shift") -> np.ndarray:
     """Pitch (semitones) and tempo of int16 ``pcm`` after prosody_plan: the stretch by p / q, then resample_rows through
     resample_design(src = p_r, dst = q_r) for the first n_f samples.  The host mirror of the prosody step of HipSynth.finish_output
-    (the stretch bit for bit; the rate conversion to the bound of resample_rows)."""
-    x = _as_pcm16(pcm)
+    (the stretch bit for bit; the rate conversion to the bound of resample_rows).  formants = "keep" (N18): where the pitch ratio is not
+    1, keep_formants puts the spectral envelope of ``pcm`` back on the result."""
+    keep = check_formants(formants) == "keep"
+    src = x = _as_pcm16(pcm)
     plan = prosody_plan(x.size, pitch, tempo)
     if plan is None:
         return x
@@ -1364,7 +1366,148 @@ def shift_prosody(pcm, pitch=None, tempo=None) -> np.ndarray:
     if plan.p_r != plan.q_r:
         taps, up, down, skip = output_design(plan.p_r, plan.q_r)
         x = resample_rows(x, taps, up, down, skip, 0, 0, plan.n_f)
+        if keep:
+            x = keep_formants(src, x, *prosody_tempo(plan))
     return x
+
+
+# ---------------------------------------------------------------------- N18: formant-preserving pitch shift (LPC envelope correction)
+# The arithmetic below IS the specification and csrc/vv_formant.hip computes the same operations in the same order: per
+# hop of H samples an all-pole envelope of the shifted signal y and of the source x at the same moment (windowed first difference, exact
+# integer autocorrelation, the Levinson-Durbin recurrence of flac_lpc_coefficients), the filter gain A_y(z) / A_x(z) cut at L taps, and
+# the two filters of a hop blended under the WSOLA window.  Every floating-point operation is one float64 operation, rounded on its own.
+FORMANT_MODES = ("shift", "keep")    # ModelConfig.output_formants: "shift" = the envelope moves with the pitch (N14 as ever)
+FORMANT_P = 24                       # VV_FORMANT_P: LPC order
+FORMANT_NA = 1024                    # VV_FORMANT_NA: analysis window length
+FORMANT_H = WSOLA_HS                 # VV_FORMANT_H: hop
+FORMANT_L = 2048                     # VV_FORMANT_L: filter taps (gamma^L = 3.5e-5: what is cut off lies 89 dB below the response's start)
+FORMANT_GAMMA = 0.995                # bandwidth expansion: A[k] = -(a[k] gamma^k); 0.99 left the 2500 Hz resonance of the test vowel shifted at -4 semitones
+FORMANT_NOISE = 2.0 ** -20           # white-noise term: R[0] += R[0] 2^-20
+_FORMANT_TABLES = []
+
+
+def check_formants(formants):
+    """Validate ``output_formants``: "shift" | "keep"; None = "shift".  -> the mode."""
+    if formants is None:
+        return "shift"
+    if not isinstance(formants, str) or formants not in FORMANT_MODES:
+        raise ValueError(f"output_formants must be one of {FORMANT_MODES}")
+    return formants
+
+
+def prosody_tempo(plan: ProsodyPlan) -> Tuple[int, int]:
+    """The tempo fraction tn / td (lowest terms) of a plan: tau = (p_r / q_r) / (p / q), so that n_f = ceil(n td / tn)."""
+    tau = Fraction(plan.p_r * plan.q, plan.q_r * plan.p)
+    return tau.numerator, tau.denominator
+
+
+def formant_tables():
+    """(wa, g): wa[k] = 0.5 - 0.5 cos(2 pi k / NA), k < NA; g[0] = 1, g[k] = g[k - 1] * gamma, k <= P (float64).  The device reads these
+    tables and evaluates neither a cosine nor a power."""
+    if not _FORMANT_TABLES:
+        wa = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(FORMANT_NA, dtype=np.float64) / np.float64(FORMANT_NA))).astype(np.float64)
+        g = np.ones(FORMANT_P + 1, np.float64)
+        for k in range(1, FORMANT_P + 1):
+            g[k] = g[k - 1] * np.float64(FORMANT_GAMMA)
+        wa.setflags(write=False)
+        g.setflags(write=False)
+        _FORMANT_TABLES.append((wa, g))
+    return _FORMANT_TABLES[0]
+
+
+def _formant_analysis(s: np.ndarray, centres: np.ndarray):
+    """Step 1 for every frame of one signal at once (each operation elementwise over the frames, so each frame sees the written order):
+    -> (A [F][P + 1], err [F], flat [F])."""
+    P, NA = FORMANT_P, FORMANT_NA
+    wa, g = formant_tables()
+    F, left = centres.size, NA // 2 + 1
+    sp = np.zeros(left + max(s.size, int(centres.max(initial=0)) + NA // 2) + 1, np.int64)
+    sp[left: left + s.size] = s
+    idx = left + centres[:, None] - NA // 2 + np.arange(NA, dtype=np.int64)[None, :]
+    d = sp[idx] - sp[idx - 1]
+    xw = np.rint(wa[None, :] * d.astype(np.float64)).astype(np.int64)                  # |xw| < 2^17
+    R = np.stack([(xw[:, lag:] * xw[:, : NA - lag]).sum(axis=1) for lag in range(P + 1)], axis=1)      # exact: every sum below 2^44
+    flat = R[:, 0] == 0
+    Rf = R.astype(np.float64)
+    Rf[:, 0] = Rf[:, 0] + Rf[:, 0] * FORMANT_NOISE
+    a, err = np.zeros((F, P + 1), np.float64), Rf[:, 0].copy()
+    with np.errstate(all="ignore"):                         # a flat frame goes on as 0 / 0: its numbers are never used
+        for p in range(1, P + 1):
+            acc = Rf[:, p].copy()
+            for j in range(1, p):
+                acc = acc - a[:, j] * Rf[:, p - j]
+            k = acc / err
+            new = a.copy()
+            for j in range(1, p):
+                new[:, j] = a[:, j] - k * a[:, p - j]
+            new[:, p] = k
+            a = new
+            err = err * (1.0 - k * k)
+            flat = flat | ~(err > 0.0)
+    A = -(a * g[None, :])
+    A[:, 0] = 1.0
+    return A, err, flat
+
+
+def _formant_frames(n: int, n_f: int, tn: int, td: int):
+    if isinstance(tn, bool) or isinstance(td, bool) or int(tn) != tn or int(td) != td or not (1 <= tn <= WSOLA_MAX_PQ and 1 <= td <= WSOLA_MAX_PQ):
+        raise ValueError(f"keep_formants: tn and td are integers in 1 ... {WSOLA_MAX_PQ}")
+    tn, td = int(tn), int(td)
+    if n_f != -(-n * td // tn):
+        raise ValueError(f"keep_formants: y holds {n_f} samples, ceil(n td / tn) = {-(-n * td // tn)} are needed")
+    m = np.arange(-(-n_f // FORMANT_H) + 1, dtype=np.int64)
+    return m * FORMANT_H, (m * FORMANT_H * tn) // td
+
+
+def formant_filters(x, y, tn: int = 1, td: int = 1, parts: bool = False):
+    """Steps 1 and 2: -> (h float64 [M + 1][L], flat bool [M + 1]), M = ceil(n_f / H).  Frame m looks at y around m H and
+    at x around floor(m H tn / td); h_m = gain * the first L samples of the impulse response of A_y(z) / A_x(z), gain = sqrt(err_x /
+    err_y); a frame with a flat analysis on either side keeps the unit impulse.  parts: also (A_y, A_x, err_y, err_x) for a test."""
+    x, y = _as_pcm16(x).astype(np.int64), _as_pcm16(y).astype(np.int64)
+    P, L = FORMANT_P, FORMANT_L
+    c_y, c_x = _formant_frames(x.size, y.size, tn, td)
+    Ay, ey, fy = _formant_analysis(y, c_y)
+    Ax, ex, fx = _formant_analysis(x, c_x)
+    flat = fy | fx
+    F = c_y.size
+    r = np.zeros((F, L), np.float64)
+    with np.errstate(all="ignore"):
+        gain = np.sqrt(ex / ey)
+        for t in range(L):
+            acc = Ay[:, t].copy() if t <= P else np.zeros(F, np.float64)
+            for k in range(1, min(t, P) + 1):
+                acc = acc - Ax[:, k] * r[:, t - k]
+            r[:, t] = acc
+        h = gain[:, None] * r
+    h[flat] = 0.0
+    h[flat, 0] = 1.0
+    return (h, flat, (Ay, Ax, ey, ex)) if parts else (h, flat)
+
+
+def apply_formant_filters(y, h: np.ndarray) -> np.ndarray:
+    """Step 3: z[i] = clamp(rint(w[k + H] v_a + w[k] v_b)), v_a = sum_j h_{m-1}[j] y[i - j], v_b the same with h_m, m = i // H + 1,
+    k = i % H; each sum takes j ascending from +0.0, every product rounded on its own, y zero in front of the signal."""
+    y = _as_pcm16(y)
+    H, L, n_f = FORMANT_H, FORMANT_L, y.size
+    w = wsola_window()
+    yp = np.concatenate([np.zeros(L - 1, np.float64), y.astype(np.float64)])
+    z = np.zeros(n_f, np.int16)
+    for m1 in range(-(-n_f // H)):
+        lo, hi = m1 * H, min(n_f, (m1 + 1) * H)
+        Y = np.lib.stride_tricks.sliding_window_view(yp[lo: hi + L - 1], L)[:, ::-1]          # Y[i][j] = y[lo + i - j]
+        va = np.cumsum(Y * h[m1][None, :], axis=1)[:, -1]                                      # cumsum adds in order, one rounding each
+        vb = np.cumsum(Y * h[m1 + 1][None, :], axis=1)[:, -1]
+        k = np.arange(hi - lo)
+        z[lo: hi] = np.clip(np.rint(w[k + H] * va + w[k] * vb), -32768.0, 32767.0).astype(np.int16)
+    return z
+
+
+def keep_formants(x, y, tn: int = 1, td: int = 1) -> np.ndarray:
+    """The envelope correction of a pitch shift: the host mirror of vv_pcm_formant, bit for bit.  x = the int16 signal
+    before the prosody step (n samples), y = what the step made of it (n_f = ceil(n td / tn) samples, tn / td the tempo fraction).
+    -> int16 [n_f]: y filtered so that its LPC envelope is x's again, its harmonics where the shift put them."""
+    h, _flat = formant_filters(x, y, tn, td)
+    return apply_formant_filters(y, h)
 
 
 class AudioProcessor:

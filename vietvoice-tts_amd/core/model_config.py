@@ -92,6 +92,10 @@ class ModelConfig:
                                             # engine, audio_processor.shift_prosody on injected sessions.  Not available in synthesize_stream
     output_tempo: Optional[float] = None    # tempo, 0.5 ... 2.0 times the speed, by the same stretch: the synthesis itself is untouched (``speed``
                                             # asks the model for another duration instead)
+    output_formants: str = "shift"          # "shift" | "keep" (DESIGN §8 N18): what output_pitch does to the spectral envelope.  "shift" = it moves with
+                                            # the pitch (N14 as ever); "keep" = an LPC envelope correction behind the rate conversion puts the envelope of
+                                            # the joined signal back, the harmonics stay where the pitch put them.  Acts only where the pitch ratio is not
+                                            # 1.  vv_pcm_formant on the HIP engine, audio_processor.keep_formants on injected sessions
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -130,6 +134,8 @@ class ModelConfig:
         check_limiter(self.output_limiter)
         from .audio_processor import check_prosody
         self.output_pitch, self.output_tempo = check_prosody(self.output_pitch, self.output_tempo)
+        from .audio_processor import check_formants
+        self.output_formants = check_formants(self.output_formants)
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

@@ -180,7 +180,7 @@ class TTSEngine:
                                                                   or self.config.output_pitch is not None or self.config.output_tempo is not None
                                                                   or prosody is not None)
 
-    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None) -> np.ndarray:
+    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None, formants=None) -> np.ndarray:
         """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of pitch and tempo (N14;
         ``pitch`` / ``tempo`` = the request's own, None = the engine's), the loudness normalisation (N12; ``loudness`` likewise), the
         limiter (N13; ``limiter`` likewise), the output rate and the encoding."""
@@ -189,7 +189,8 @@ class TTSEngine:
         pitch = self.config.output_pitch if pitch is None else pitch
         tempo = self.config.output_tempo if tempo is None else tempo
         if pitch is not None or tempo is not None:
-            final = shift_prosody(np.ascontiguousarray(final, dtype=np.int16), pitch, tempo)
+            keep = (self.config.output_formants if formants is None else formants) == "keep"      # N18; "shift": the call of N14
+            final = shift_prosody(np.ascontiguousarray(final, dtype=np.int16), pitch, tempo, **({"formants": "keep"} if keep else {}))
         loudness = self.config.output_loudness if loudness is None else loudness
         limiter = self.config.output_limiter if limiter is None else limiter
         if loudness is not None:
@@ -202,10 +203,10 @@ class TTSEngine:
             final = resample_output(final, self.config.sample_rate, rate)
         return encode_output(final, enc, self.output_rate, **self._flac_options()) if enc != "pcm16" else final
 
-    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None) -> List[np.ndarray]:
+    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None, formants=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
         one HipSynth.finish_output call (join, prosody, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per
-        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14) likewise."""
+        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14) and ``formants`` (N18) likewise."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
@@ -225,6 +226,9 @@ class TTSEngine:
             vals = [mine] * len(counts) if own is None else [mine if v is None else v for v in own]
             if any(v is not None for v in vals):           # no pitch and no tempo anywhere: exactly the call of N13
                 opts[key] = vals
+        keep = [self.config.output_formants] * len(counts) if formants is None else [self.config.output_formants if v is None else v for v in formants]
+        if "keep" in keep and "pitch" in opts:             # "shift" everywhere, or no pitch anywhere: exactly the call of N14
+            opts["formants"] = keep
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
                                                                loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **opts)
 
@@ -534,6 +538,7 @@ class TTSEngine:
                                              **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}),
                                              **({} if cfg.output_pitch is None and cfg.output_tempo is None
                                                 else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}),
+                                             **({"formants": "keep"} if cfg.output_formants == "keep" and cfg.output_pitch is not None else {}),
                                              **self._flac_options("flac_lpc_order"))[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)

@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.10 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.11 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -816,6 +816,50 @@ int vv_pcm_stretch(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows
            2.0 * (double)total_frames * (2 * VV_WSOLA_N + 2 * VV_WSOLA_D) + 6.0 * (double)total_out, st);
     KCHK(c, vvk_pcm_stretch(x, (long long)n_x, (const long long*)rows, R, (long long)max_out, window, y, (long long)n_y, (int*)pos,
                             (long long)n_pos, ws, st, &m__));
+    return 0;
+}
+
+// N18: the envelope correction of a pitch shift.  As with N12 ... N14 the rows come in host memory too: everything is checked before a launch.
+uint64_t vv_pcm_formant_ws_bytes(int64_t total_frames, int R) { return vvk_pcm_formant_ws_bytes((long long)total_frames, R); }
+
+int vv_pcm_formant(vv_ctx* c, const int16_t* x, int64_t n_x, const int16_t* y, int64_t n_y, const int64_t* rows, const int64_t* rows_host, int R,
+                   const double* wa, const double* g, const double* window, int16_t* z, int64_t n_z, double* h_out, int64_t n_h, void* ws,
+                   uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0 || n_z < 0 || n_h < 0) return c->fail(-22, "vv_pcm_formant: bad sizes (1 <= R <= 65535)");
+    if (int e = check_ptrs(c, "vv_pcm_formant", {{"x", x, 2}, {"y", y, 2}, {"rows", rows, 8}, {"rows_host", rows_host}, {"wa", wa, 8}, {"g", g, 8},
+                                                 {"window", window, 8}, {"z", z, 2}, {"h_out", h_out, 8, true}, {"ws", ws, 8}})) return e;
+    if (spans_overlap(x, 2ull * n_x, z, 2ull * n_z) || spans_overlap(y, 2ull * n_y, z, 2ull * n_z))
+        return c->fail(-22, "vv_pcm_formant: z overlaps x or y (an output sample reads L samples of y: not in place)");
+    std::vector<std::pair<int64_t, int64_t>> on_z;
+    int64_t total_frames = 0, max_frames = 0, total_out = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 7 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[4] < 0) return c->fail(-22, "vv_pcm_formant: row %d has a negative field", r);
+        if (q[5] < 1 || q[5] > VV_WSOLA_MAX_PQ || q[6] < 1 || q[6] > VV_WSOLA_MAX_PQ)
+            return c->fail(-22, "vv_pcm_formant: row %d: tn and td in 1 ... %d", r, VV_WSOLA_MAX_PQ);
+        if (!fits(q[0], q[1], n_x) || q[1] > ((int64_t)1 << 30))
+            return c->fail(-22, "vv_pcm_formant: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (q[3] != (q[1] * q[6] + q[5] - 1) / q[5]) return c->fail(-22, "vv_pcm_formant: row %d: n_f is not ceil(n td / tn)", r);
+        if (!fits(q[2], q[3], n_y)) return c->fail(-22, "vv_pcm_formant: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        if (!fits(q[4], q[3], n_z)) return c->fail(-22, "vv_pcm_formant: row %d does not fit the %lld samples of z", r, (long long)n_z);
+        const int64_t frames = (q[3] + VV_FORMANT_H - 1) / VV_FORMANT_H + 1;
+        if (q[3] > 0) on_z.emplace_back(q[4], q[4] + q[3]);
+        total_frames += frames;
+        total_out += q[3];
+        if (frames > max_frames) max_frames = frames;
+    }
+    std::sort(on_z.begin(), on_z.end());
+    for (size_t i = 1; i < on_z.size(); ++i)
+        if (on_z[i].first < on_z[i - 1].second) return c->fail(-22, "vv_pcm_formant: rows overlap on z");
+    if (h_out && n_h / VV_FORMANT_L < total_frames)
+        return c->fail(-22, "vv_pcm_formant: h_out of %lld doubles, %lld are needed", (long long)n_h, (long long)total_frames * VV_FORMANT_L);
+    if (int e = check_ws(c, "vv_pcm_formant", ws_bytes, vvk_pcm_formant_ws_bytes((long long)total_frames, R))) return e;
+    Prof p(c, VV_PROF_ELEMWISE, 4.0 * (double)total_out * VV_FORMANT_L + 2.0 * (double)total_frames * VV_FORMANT_L * VV_FORMANT_P,
+           24.0 * (double)total_frames * VV_FORMANT_L + 4.0 * (double)total_out, st);
+    KCHK(c, vvk_pcm_formant(x, (long long)n_x, y, (long long)n_y, (const long long*)rows, R, (long long)total_frames, (long long)max_frames, wa, g,
+                            window, z, (long long)n_z, h_out, ws, st, &m__));
     return 0;
 }
 

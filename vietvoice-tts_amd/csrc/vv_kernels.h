@@ -97,6 +97,12 @@ int vvk_pcm_limit(const int16_t* x, long long n_x, const long long* rows, int R,
 unsigned long long vvk_pcm_stretch_ws_bytes(int R);
 int vvk_pcm_stretch(const int16_t* x, long long n_x, const long long* rows, int R, long long max_out, const double* window, int16_t* y,
                     long long n_y, int* pos, long long n_pos, void* ws, hipStream_t st, const char** err);
+// N18 formant-preserving pitch shift (vv_formant.hip): per-frame LPC analysis of y and x, the filter A_y / A_x cut at L taps, the blended FIR;
+// rows R x 7 {x_off, n, y_off, n_f, z_off, tn, td}
+unsigned long long vvk_pcm_formant_ws_bytes(long long total_frames, int R);
+int vvk_pcm_formant(const int16_t* x, long long n_x, const int16_t* y, long long n_y, const long long* rows, int R, long long total_frames,
+                    long long max_frames, const double* wa, const double* g, const double* window, int16_t* z, long long n_z, double* h_out,
+                    void* ws, hipStream_t st, const char** err);
 // N15 FLAC output (vv_flac.hip): per frame of 4096 samples the exhaustive fixed-predictor / Rice search, the frames' offsets, the bit packing;
 // rows R x 4 {src_off, n, frame0, last}
 unsigned long long vvk_flac_frame_bound(long long m);

@@ -1,4 +1,4 @@
-"""The PCM stage of HipSynth (DESIGN §8 N10 ... N17, layering described there): per call a pure plan_* function of host values (every
+"""The PCM stage of HipSynth (DESIGN §8 N10 ... N18, layering described there): per call a pure plan_* function of host values (every
 ValueError, the row table, the derived sizes; no GPU needed) and a launch method of PcmStage, which HipSynth inherits."""
 from typing import Optional
 
@@ -237,6 +237,39 @@ def plan_prosody(offs, lens, pitch, tempo):
             convert.setdefault((pl.p_r, pl.q_r, i not in mid), []).append(src + [new_offs[i], pl.n_f, 0, 0])
     converts = [(not joined, p_r, q_r, rows) for (p_r, q_r, joined), rows in sorted(convert.items())]
     return new_offs, new_lens, base, max(-(-size // 8) * 8, 8), copies, stretch, converts
+
+
+def plan_formant(rows, n_x: int, n_y: int, out_n: Optional[int] = None, overlaps: bool = False):
+    """vv_pcm_formant's rows {x_off, n, y_off, n_f, z_off, tn, td}, validated -> (rows, frame offsets [R + 1]: request r's frames 0 ... M
+    are frame_offs[r] ... frame_offs[r + 1] - 1, n_z); out_n: _out_arg; overlaps: out shares memory with x or y."""
+    from .core.audio_processor import FORMANT_H, WSOLA_MAX_PQ
+    rows = _int_rows("pcm_formant", rows, (7,), "7 entries {x_off, n, y_off, n_f, z_off, tn, td}")
+    spans, frame_offs = [], [0]
+    for r in rows:
+        xo, n, yo, n_f, zo, tn, td = r
+        if not (1 <= tn <= WSOLA_MAX_PQ and 1 <= td <= WSOLA_MAX_PQ):
+            raise ValueError(f"pcm_formant: row {r}: tn and td in 1 ... {WSOLA_MAX_PQ}")
+        if min(xo, n, yo, n_f, zo) < 0 or xo + n > n_x or yo + n_f > n_y or n > 1 << 30:
+            raise ValueError(f"pcm_formant: row {r} does not fit the buffers ({n_x} samples of x, {n_y} of y)")
+        if n_f != -(-n * td // tn):
+            raise ValueError(f"pcm_formant: row {r}: n_f is not ceil(n td / tn) = {-(-n * td // tn)}")
+        if n_f:
+            spans.append((zo, zo + n_f))
+        frame_offs.append(frame_offs[-1] + -(-n_f // FORMANT_H) + 1)
+    if overlaps:
+        raise ValueError("pcm_formant: out overlaps x or y (the filter is not in place)")
+    return rows, frame_offs, _spans("pcm_formant", spans, out_n)
+
+
+def plan_keep(plans, offs, lens, new_offs, new_lens, formants):
+    """The requests of a prosody step that ask for formants = "keep" and have a pitch: -> their vv_pcm_formant rows, z_off = y_off (the
+    result takes the place of the converted signal in a buffer of the same layout).  plans = prosody_plan per request."""
+    from .core.audio_processor import prosody_tempo
+    rows = []
+    for i, pl in enumerate(plans):
+        if formants[i] == "keep" and pl is not None and pl.p_r != pl.q_r and pl.n_f > 0:
+            rows.append([offs[i], lens[i], new_offs[i], new_lens[i], new_offs[i], *prosody_tempo(pl)])
+    return rows
 
 
 def plan_flac(rows, n_x: int, sample_rate, lpc_order: int = 0):
@@ -506,8 +539,10 @@ class PcmStage:
                    0 if y is None else y.numel(), pos.data_ptr(), pos.numel(), ws.data_ptr(), ws.numel() * 8)
         return y, pos, pos_offs
 
-    def _prosody(self, buf: torch.Tensor, offs, lens, pitch, tempo):
-        """The prosody step of finish_output after plan_prosody: -> (new buffer, offsets, lengths)."""
+    def _prosody(self, buf: torch.Tensor, offs, lens, pitch, tempo, formants=None):
+        """The prosody step of finish_output after plan_prosody: -> (new buffer, offsets, lengths).  formants = per request "shift" |
+        "keep" (N18; None = "shift" everywhere, nothing new is called): the converted signal of a request with "keep" and a pitch goes
+        through pcm_formant, against its joined signal in ``buf``, into a second buffer of the same layout."""
         new_offs, new_lens, base, size, copies, stretch, converts = plan_prosody(offs, lens, pitch, tempo)
         new = torch.empty((size,), dtype=torch.int16, device=self.device)
         for src, dst, n in copies:
@@ -516,7 +551,43 @@ class PcmStage:
             self.pcm_stretch(buf, stretch, out=new)
         for from_new, p_r, q_r, rows in converts:          # source and destination are separate parts of ``new``
             self.pcm_resample(new[base:] if from_new else buf, rows, p_r, q_r, out=new[:base])
-        return new[:max(base, 8)], new_offs, new_lens
+        out = new[:max(base, 8)]
+        if formants is not None and "keep" in formants:
+            from .core.audio_processor import prosody_plan
+            keep = plan_keep([prosody_plan(n, p, t) for n, p, t in zip(lens, pitch, tempo)], offs, lens, new_offs, new_lens, formants)
+            if keep:
+                kept = out.clone()                          # the others stay as they are; z overlaps neither x nor y
+                self.pcm_formant(buf, out, keep, out=kept)
+                out = kept
+        return out, new_offs, new_lens
+
+    # ------------------------------------------------------------------ formant-preserving pitch shift (N18)
+    @property
+    def _formant_tables(self):
+        return self._table("formant", "formant_tables")
+
+    def pcm_formant(self, x: torch.Tensor, y: torch.Tensor, rows, out: Optional[torch.Tensor] = None, taps: bool = False):
+        """The envelope correction of a pitch shift on R requests in one call (vv_pcm_formant), bit for bit
+        core.audio_processor.keep_formants.  x int16 flat on the device: the joined signals; y int16 flat: what the prosody step made of
+        them; rows = HOST rows (x_off, n, y_off, n_f, z_off, tn, td): tn / td the tempo fraction, n_f = ceil(n td / tn).  out = None: a new
+        buffer, or a flat int16 device tensor that overlaps neither x nor y.  -> z, or with ``taps`` (z, h, frame_offs): h the float64
+        device tensor [frames][L] of every frame's filter, request r's frames h[frame_offs[r] : frame_offs[r + 1]].  The rows are
+        validated here; the call never synchronises."""
+        for t in (x, y):
+            assert t.is_cuda and t.dtype == torch.int16 and t.is_contiguous() and t.dim() == 1
+        n_x, n_y = x.numel(), y.numel()
+        shared = isinstance(out, torch.Tensor) and any(out.data_ptr() < t.data_ptr() + 2 * t.numel() and t.data_ptr() < out.data_ptr() + 2 * out.numel()
+                                                       for t in (x, y))
+        rows, frame_offs, n_z = plan_formant(rows, n_x, n_y, _out_arg(out)[0], shared)
+        from .core.audio_processor import FORMANT_L
+        z, R = self._out(out, n_z), len(rows)
+        rows_d, rows_h = self._upload(rows)
+        wa, g = self._formant_tables
+        h = torch.empty((frame_offs[-1], FORMANT_L), dtype=torch.float64, device=self.device) if taps else None
+        ws = self._ws(self.lib.vv_pcm_formant_ws_bytes(frame_offs[-1], R))
+        self._call(self.lib.vv_pcm_formant, x.data_ptr(), n_x, y.data_ptr(), n_y, rows_d.data_ptr(), rows_h.data_ptr(), R, wa.data_ptr(), g.data_ptr(),
+                   self._wsola_window.data_ptr(), z.data_ptr(), z.numel(), _ptr(h), 0 if h is None else h.numel(), ws.data_ptr(), ws.numel() * 8)
+        return (z, h, frame_offs) if taps else z
 
     # ------------------------------------------------------------------ FLAC output (N15, N16)
     def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int, lpc_order: int = 0):
@@ -645,7 +716,8 @@ class PcmStage:
         return out
 
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
-                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0):
+                      encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0,
+                      formants=None):
         """The whole output stage of R requests on the caller's stream: join (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
         (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
         spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
@@ -658,14 +730,20 @@ class PcmStage:
         encoding "flac" (N15): the final PCM goes through pcm_flac instead of the one copy: a small copy of the frames' sizes, then a copy
         of exactly the frames' bytes; each request comes back as a complete FLAC file.  flac_lpc_order 1 ... 12 (N16) adds LPC subframes
         (vv_pcm_flac_lpc instead of vv_pcm_flac) and is refused with another encoding.
+        formants (N18) = "shift" | "keep" for every request, or a per-request list; None = "shift": a request with "keep" and a pitch
+        ratio other than 1 has the spectral envelope of its joined signal put back by pcm_formant, directly behind the rate conversion
+        that makes the pitch; a request with tempo alone or without prosody runs nothing new.
         -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
         from .core.audio_processor import check_flac_lpc_order, resample_len
         if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
             raise ValueError("finish_output: flac_lpc_order belongs to the encoding 'flac'")
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
         pitch, tempo, groups = plan_finish(len(lens), loudness, limiter, pitch, tempo)
+        if formants is not None:
+            from .core.audio_processor import check_formants
+            formants = [check_formants(f) for f in _per_request("finish_output", formants, len(lens), "formants entry per request")]
         if pitch is not None:
-            buf, offs, lens = self._prosody(buf, offs, lens, pitch, tempo)
+            buf, offs, lens = self._prosody(buf, offs, lens, pitch, tempo, formants)
         for mode, sel, tg in groups:       # in place on the joined buffer: the apply passes are elementwise
             rows, meas = [[offs[i], lens[i], offs[i]] for i in sel], None
             if mode is None:
