@@ -982,9 +982,8 @@ int vv_flac_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_
 }
 
 // --------------------------------------------------------------------------- transformer steps
-// ws_only != nullptr: only compute the workspace bytes the call would take (nothing is launched; the data pointers may be null).
-// args.ws != nullptr: take them from that caller-owned block instead of the context's (what a captured hipGraph must point into).
-//
+// The stage in four parts: the call (StepsCall), the lane plan (lane_plan: host values in, sizes out; lane_bufs names the buffers), the
+// launches of one lane (StepsRun) and the schedule (steps_schedule: order, streams, forks and joins); transformer_steps runs them.
 // LANES (round 4): a batch of independent items may run as TWO half batches ("lanes") on two HIP streams at once -- lane 0 on the
 // caller's stream, lane 1 on a context-owned side stream forked from it and joined back before the call returns.  Every kernel of
 // the path is row- or sequence-local with one arithmetic whatever the launch size (tests/test_mixed256_gpu.py), so the lanes produce
@@ -1027,12 +1026,72 @@ struct GuideState {
     double sum_sq = 0;                 // sum of len^2 over them
 };
 
+// One call of the stage, as every entry hands it over.
+// guide != nullptr (N8, vv_transformer_steps_guided): HOST flags [evaluations of the plan][ld_guide], guided(b, e) at guide[e * ld_guide + b];
+// an item that is not guided at an evaluation has no unconditional rows there.
+// apg != nullptr (N11, vv_transformer_steps_apg): the projected combine -- per evaluation and lane, apg_reduce_kernel and apg_coef_kernel in
+// front of the stage kernel, on its stream.
+// ws_form, named by a size query: the workspace of a plain call, with the tables of a mask's subsets on top (whatever the mask), or with
+// APG's on top of those (with or without a mask).  A call with a mask or with APG implies its form.
+enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG };
+struct StepsCall {
+    vv_steps_args a{};
+    const uint8_t* guide = nullptr; int ld_guide = 0;
+    const vv_apg_args* apg = nullptr;
+    WsForm ws_form = WS_PLAIN;
+    uint64_t* ws_only = nullptr;       // a size query: only the workspace bytes of the call (nothing is launched; the data pointers may be null)
+    bool guided = false, with_apg = false, rk = false;     // derived once, by transformer_steps
+};
+struct StepDims { int D, FF, M, CD, es, KP, MP; };
+
+// The lane plan, from host values alone.  Option "lanes" 1 = one lane, 2 = two whenever there are two to make, 0 (default) = two when
+// both halves still fill the persistent GEMM for several rounds (bf16, >= VV_LANE_MIN_ROWS packed rows in all).  Two items or more: ITEM
+// lanes, cut at the item boundary closest to half of the rows.  One problem only (a single item, or a batch under the row threshold with
+// "lanes" 2): its two CFG BRANCHES are the lanes -- the conditional rows [0, Rc) and the unconditional rows [Rc, 2 Rc) of the same packed
+// buffers are independent from the conditioning pack at the top of a step to the CFG combine at its end, so the side stream is forked
+// and joined once per step around them.
+struct LanePlan { int n_lanes = 1, cut = 0; bool branch_lanes = false; Lane lanes[2]; };
+LanePlan lane_plan(const vv_ctx* c, const StepDims& d, const std::vector<int>& hlen, int N) {
+    LanePlan P;
+    const int B = (int)hlen.size();
+    const bool tails = c->split_k_tail && c->dt == VV_DTYPE_BF16;
+    size_t Rc_all = 0;
+    for (int v : hlen) Rc_all += v;
+    const bool two = c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS);
+    if (two && B >= 2) {
+        size_t acc = 0, best = (size_t)-1;
+        for (int b = 1; b < B; ++b) {
+            acc += hlen[b - 1];
+            const size_t dist = acc * 2 > Rc_all ? acc * 2 - Rc_all : Rc_all - acc * 2;
+            if (dist < best) { best = dist; P.cut = b; }
+        }
+        P.n_lanes = 2;
+    }
+    P.branch_lanes = two && P.n_lanes == 1 && !tails;
+    const int cuts[3] = {0, P.n_lanes == 2 ? P.cut : B, B};
+    for (int li = 0; li < P.n_lanes; ++li) {
+        Lane& L = P.lanes[li];
+        L.b0 = cuts[li]; L.B = cuts[li + 1] - cuts[li];
+        for (int b = L.b0; b < L.b0 + L.B; ++b) { L.Rc += hlen[b]; L.sum_sq += 2.0 * hlen[b] * hlen[b]; L.uniform = L.uniform && hlen[b] == N; }
+        L.R = 2 * L.Rc; L.n_seq = 2 * L.B;
+        // split-K tails of the two N = D gate-store GEMMs (out-proj K = D, FF2 K = FF): same row0 (it depends on M and N only)
+        if (tails) {
+            int r0o = 0, r0f = 0;
+            if (c->split_k_tail == 1) vvk_gemm_tail_plan((int)L.R, d.D, d.D, d.D, d.D, d.D, &r0o, &L.tp_o);     // (M, N, K, lda, ldw, ldc) of the launches
+            vvk_gemm_tail_plan((int)L.R, d.D, d.FF, d.FF, d.FF, d.D, &r0f, &L.tp_f);
+            if (L.tp_o && L.tp_f && r0o != r0f) L.tp_o = L.tp_f = 0;   // cannot happen (row0 is a function of M, N and the CU count); refuse rather than mix
+            L.tail_row0 = L.tp_o ? r0o : r0f;
+        }
+        L.tail_rows = (L.tp_o || L.tp_f) ? L.R - L.tail_row0 : 0;
+        L.n_tab = 2 * (size_t)L.B + L.Rc + L.R;          // row_start[2B] | row_src[Rc] | row_pos[R]
+    }
+    return P;
+}
+
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided, bool apg) {
-    const vv_model_cfg& g = c->cfg;
-    const size_t R = L.R, es = c->esz(), D = g.dim, FF = D * g.ff_mult, M = g.n_mel;
-    const size_t KP = pad_to(2 * g.n_mel + g.text_dim, 64), MP = pad_to(g.n_mel, 128);
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg) {
+    const size_t R = L.R, es = d.es, D = d.D, FF = d.FF, M = d.M, KP = d.KP, MP = d.MP;
     L.xcat = a.take<char>(es * R * KP);
     L.h = a.take<char>(es * R * D); L.h2 = a.take<char>(es * R * D); L.h3 = a.take<char>(es * R * D);
     L.xres = a.take<float>(R * D);
@@ -1040,6 +1099,8 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided, bool apg)
     L.pred = a.take<float>(R * MP); L.kv_len = a.take<int>(2 * L.B);
     L.csq = a.take<float>((size_t)N * 64); L.csk = a.take<float>((size_t)N * 64);
     L.tab = a.take<int>(L.n_tab);                  // row_start[2B] | row_src[Rc] | row_pos[R]
+    L.row_start = L.tab; L.row_src = L.tab + 2 * L.B; L.row_pos = L.row_src + L.Rc;
+    L.qkv_pos = L.uniform ? nullptr : L.row_pos;   // every sequence N rows: position = packed row mod N, no table lookup
     L.csq_rows = a.take<float>(R * 64); L.csk_rows = a.take<float>(R * 64);     // compact rope tables gathered per packed row, once per call
     L.h2_tail = a.take<float>(L.tail_rows * D * (L.tp_o > 1 ? L.tp_o : 0));     // fp32 [parts][tail_rows][D] K parts of the tail rows' deltas
     L.h3_tail = a.take<float>(L.tail_rows * D * (L.tp_f > 1 ? L.tp_f : 0));
@@ -1058,148 +1119,52 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, int N, bool guided, bool apg)
         if (c->ode_s > 1) L.xs2 = a.take<float>(L.Rc * M);
     }
 }
-}  // namespace
 
-// guide != nullptr (N8, vv_transformer_steps_guided): HOST flags [evaluations of the plan][ld_guide], guided(b, e) at guide[e * ld_guide + b];
-// an item that is not guided at an evaluation has no unconditional rows there.  guided_ws: the workspace of such a call (the tables of
-// the subsets on top of the plain call's bytes), whatever the mask.
-// apg != nullptr (N11, vv_transformer_steps_apg): the projected combine -- per evaluation and lane, apg_reduce_kernel and apg_coef_kernel in
-// front of the stage kernel, on its stream.  apg_ws: the workspace of such a call (with the tables of a mask, whether one is given or not).
-static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t* ws_only, void* stream, const uint8_t* guide = nullptr,
-                                  int ld_guide = 0, bool guided_ws = false, const vv_apg_args* apg = nullptr, bool apg_ws = false) {
-    if (!c) return -22;
-    const bool with_apg = apg != nullptr || apg_ws;
-    const bool guided = guide != nullptr || guided_ws || with_apg;
-    const int B = args.B, N = args.N, step0 = args.step0, n_steps = args.n_steps;
-    const int32_t *seq_len = args.seq_len, *seq_len_host = args.seq_len_host;
-    float* x = args.x;
-    const float *cat = args.cat_mel_text, *cat_drop = args.cat_mel_text_drop, *cfg_item = args.cfg_item, *rope_cos_q = args.rope_cos_q,
-                *rope_sin_q = args.rope_sin_q, *rope_cos_k = args.rope_cos_k, *rope_sin_k = args.rope_sin_k;
-    if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
-    if (B < 1 || N < 1 || (!ws_only && (!seq_len || !x || !cat || !cat_drop || !rope_cos_q || !rope_sin_q || !rope_cos_k || !rope_sin_k)))
-        return c->fail(-22, "vv_transformer_steps: bad arguments");
-    if (step0 < 0 || n_steps < 0 || step0 + n_steps > c->n_steps) return c->fail(-22, "vv_transformer_steps: steps [%d,%d) outside the time grid (%d)", step0, step0 + n_steps, c->n_steps);
-    if (guide && ld_guide < B) return c->fail(-22, "vv_transformer_steps_guided: ld_guide = %d < B = %d", ld_guide, B);
-    if (guide && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_guided: a guidance mask cannot be combined with option split_k_tail (its tail plan depends on the row count)");
-    if (guided && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_guided: at most %d items per call", VVK_GUIDE_MAX_ITEMS);
-    const vv_model_cfg& g = c->cfg;
-    hipSetDevice(c->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int D = g.dim, FF = D * g.ff_mult, M = g.n_mel, CD = M + g.text_dim, es = c->esz();
-    const int KP = pad_to(M + CD, 64), MP = pad_to(M, 128);
-    if ((size_t)2 * B * N > (size_t)1 << 30) return c->fail(-22, "batch too large");
-    // Ragged rows are PACKED: sequence (branch, b) owns rows [row_start, +len_b) of every activation buffer, the conditional
-    // branch first, so GEMMs / norms / convs touch sum(len) rows instead of B x N_max.  The host needs the row count for the
-    // launch shapes: the caller hands the lengths over on the host as well (vv_transformer_steps_h: no synchronisation at all,
-    // the call can be captured into a hipGraph), or they are read back once (4*B bytes, one stream synchronisation).  The row
-    // tables themselves are built on the device.  x, cat and cat_drop keep their padded [B][N] layout (row_src maps).
-    std::vector<int> hlen(B);
-    if (seq_len_host) {
-        std::copy(seq_len_host, seq_len_host + B, hlen.begin());
-    } else {
-        HIPCHK(c, hipMemcpyAsync(hlen.data(), seq_len, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    size_t Rc_all = 0;
-    for (int b = 0; b < B; ++b) {
-        if (hlen[b] < 1 || hlen[b] > N) return c->fail(-22, "vv_transformer_steps: seq_len[%d] = %d outside [1, %d]", b, hlen[b], N);
-        Rc_all += hlen[b];
-    }
-    if (2 * Rc_all * 3 * (size_t)D * es >= ((size_t)1 << 31))
-        return c->fail(-22, "vv_transformer_steps: %zu packed rows make a %zu-byte qkv buffer; kernels address it with 32-bit byte offsets "
-                            "(< 2 GiB) -- synthesise fewer units per call", 2 * Rc_all, 2 * Rc_all * 3 * (size_t)D * es);
-    // lane plan: option "lanes" 1 = one lane, 2 = two whenever B >= 2, 0 (default) = two when both halves still fill the persistent
-    // GEMM for several rounds (>= VV_LANE_MIN_ROWS packed rows in all); the cut is the item boundary closest to half of the rows
-    int n_lanes = 1, cuts[3] = {0, B, B};
-    if (B >= 2 && (c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS))) {
-        size_t acc = 0, best = (size_t)-1;
-        for (int b = 1; b < B; ++b) {
-            acc += hlen[b - 1];
-            const size_t d = acc * 2 > Rc_all ? acc * 2 - Rc_all : Rc_all - acc * 2;
-            if (d < best) { best = d; cuts[1] = b; }
-        }
-        n_lanes = 2; cuts[2] = B;
-    }
-    // One problem only (a single item, or a batch under the row threshold with "lanes" 2): its two CFG BRANCHES are the lanes -- the
-    // conditional rows [0, Rc) and the unconditional rows [Rc, 2 Rc) of the same packed buffers are independent from the conditioning
-    // pack at the top of a step to the CFG combine at its end, so the side stream is forked and joined once per step around them.
-    const bool branch_lanes = n_lanes == 1 && !(c->split_k_tail && c->dt == VV_DTYPE_BF16) &&
-                              (c->lanes == 2 || (c->lanes == 0 && c->dt == VV_DTYPE_BF16 && 2 * Rc_all >= (size_t)VV_LANE_MIN_ROWS));
-    Lane lanes[2];
-    const int ns = c->ode_s, S = c->n_steps * ns;      // S: rows of the modulation tables (evaluations)
-    const bool rk = ns > 1 || cfg_item != nullptr || guide != nullptr || apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
-    for (int li = 0; li < n_lanes; ++li) {
-        Lane& L = lanes[li];
-        L.b0 = cuts[li]; L.B = cuts[li + 1] - cuts[li];
-        for (int b = L.b0; b < L.b0 + L.B; ++b) { L.Rc += hlen[b]; L.sum_sq += 2.0 * hlen[b] * hlen[b]; L.uniform = L.uniform && hlen[b] == N; }
-        L.R = 2 * L.Rc; L.n_seq = 2 * L.B;
-        // split-K tails of the two N = D gate-store GEMMs (out-proj K = D, FF2 K = FF): same row0 (it depends on M and N only)
-        if (c->split_k_tail && c->dt == VV_DTYPE_BF16) {
-            int r0o = 0, r0f = 0;
-            if (c->split_k_tail == 1) vvk_gemm_tail_plan((int)L.R, D, D, D, D, D, &r0o, &L.tp_o);          // (M, N, K, lda, ldw, ldc) of the launches below
-            vvk_gemm_tail_plan((int)L.R, D, FF, FF, FF, D, &r0f, &L.tp_f);
-            if (L.tp_o && L.tp_f && r0o != r0f) L.tp_o = L.tp_f = 0;   // cannot happen (row0 is a function of M, N and the CU count); refuse rather than mix
-            L.tail_row0 = L.tp_o ? r0o : r0f;
-        }
-        L.tail_rows = (L.tp_o || L.tp_f) ? L.R - L.tail_row0 : 0;
-        L.n_tab = 2 * (size_t)L.B + L.Rc + L.R;          // row_start[2B] | row_src[Rc] | row_pos[R]
-    }
-    auto bufs = [&](Arena& a) { for (int li = 0; li < n_lanes; ++li) lane_bufs(a, lanes[li], c, N, guided, with_apg); };
-    if (ws_only) { *ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
-    if (int r = plan_ws(c, args.ws, (size_t)args.ws_bytes, bufs)) return r;
-    for (int li = 1; li < (branch_lanes ? 2 : n_lanes); ++li)
-        if (!c->side_stream[li - 1]) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream[li - 1], hipStreamNonBlocking));
-            HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[li - 1], hipEventDisableTiming));
-        }
-    if ((n_lanes > 1 || branch_lanes) && !c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    for (int li = 0; li < n_lanes; ++li) {
-        Lane& L = lanes[li];
-        L.seq_len = seq_len + L.b0; L.x = x + (size_t)L.b0 * N * M; L.cat = cat + (size_t)L.b0 * N * CD; L.cat_drop = cat_drop + (size_t)L.b0 * N * CD;
-        L.st = li == 0 ? st : c->side_stream[li - 1];
-        L.row_start = L.tab; L.row_src = L.tab + 2 * L.B; L.row_pos = L.row_src + L.Rc;
-        L.qkv_pos = L.uniform ? nullptr : L.row_pos;   // every sequence N rows: position = packed row mod N, no table lookup
-    }
+// The launches of one call, lane by lane: every member fills the arguments of its kernels for the Lane (or view of one) it is given and
+// launches them on that Lane's stream.  None records or waits on an event or picks a stream: that is steps_schedule's.
+struct StepsRun : StepDims {
+    vv_ctx* c; const vv_model_cfg& g;
+    const StepsCall& q; const std::vector<int>& hlen; const LanePlan& P;
+    const int N, ns, S;                // S: rows of the modulation tables (evaluations)
     // bf16: the query side of the rope moves from the QKV GEMM's epilogue into the attention kernel's Q load (option "rope_q_attn",
     // default on; profiles/r04/attention_notes.md); the fp32 (numerics) path keeps all of it in the GEMM
-    const float rope_theta = c->dt == VV_DTYPE_BF16 ? c->rope_theta : 0.f;        // computed rope: both q and k in the GEMM epilogue, scale in attention
-    const int q_rope_attn = (c->rope_q_attn && c->dt == VV_DTYPE_BF16 && !(rope_theta > 0.f)) ? 1 : 0;
-
-    auto setup = [&](Lane& L) -> int {
-        hipStream_t st = L.st;
+    const float rope_theta; const int q_rope_attn;     // rope_theta > 0, computed rope: both q and k in the GEMM epilogue, scale in attention
+    StepsRun(vv_ctx* c_, const StepDims& d, const StepsCall& q_, const std::vector<int>& hlen_, const LanePlan& P_)
+        : StepDims(d), c(c_), g(c_->cfg), q(q_), hlen(hlen_), P(P_), N(q_.a.N), ns(c_->ode_s), S(c_->n_steps * c_->ode_s),
+          rope_theta(c_->dt == VV_DTYPE_BF16 ? c_->rope_theta : 0.f),
+          q_rope_attn((c_->rope_q_attn && c_->dt == VV_DTYPE_BF16 && !(rope_theta > 0.f)) ? 1 : 0) {}
+    // once per call and lane: the row tables, the compact rope tables and (no mask) the first conditioning pack, every column
+    int setup(Lane& L) const {
         // kv_len: the clamped lengths of the tables, both branches -- what attention and posconv run on (never the raw device lengths)
-        KCHK(c, vvk_row_tables(L.seq_len, L.B, N, (int)L.Rc, L.tab, L.tab + 2 * L.B, L.tab + 2 * L.B + L.Rc, L.kv_len, st, &m__));
-        KCHK(c, vvk_rope_compact(rope_cos_q, rope_sin_q, L.csq, N, st, &m__));
-        KCHK(c, vvk_rope_compact(rope_cos_k, rope_sin_k, L.csk, N, st, &m__));
-        if (guide) return 0;                             // N8: the row-gathered rope tables and the pack follow the evaluation's subset (guide_eval)
+        KCHK(c, vvk_row_tables(L.seq_len, L.B, N, (int)L.Rc, L.tab, L.tab + 2 * L.B, L.tab + 2 * L.B + L.Rc, L.kv_len, L.st, &m__));
+        KCHK(c, vvk_rope_compact(q.a.rope_cos_q, q.a.rope_sin_q, L.csq, N, L.st, &m__));
+        KCHK(c, vvk_rope_compact(q.a.rope_cos_k, q.a.rope_sin_k, L.csk, N, L.st, &m__));
+        if (q.guide) return 0;                            // N8: the row-gathered rope tables and the pack follow the evaluation's subset (guide_eval)
         if (c->rope_rows) {
-            KCHK(c, vvk_rope_rows(L.csq, L.row_pos, L.csq_rows, (int)L.R, st, &m__));
-            KCHK(c, vvk_rope_rows(L.csk, L.row_pos, L.csk_rows, (int)L.R, st, &m__));
+            KCHK(c, vvk_rope_rows(L.csq, L.row_pos, L.csq_rows, (int)L.R, L.st, &m__));
+            KCHK(c, vvk_rope_rows(L.csk, L.row_pos, L.csk_rows, (int)L.R, L.st, &m__));
         }
-        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.R * (M + CD) / 2 + (double)es * L.R * KP, st);
-        KCHK(c, vvk_pack_cat(c->dt, L.x, L.cat, L.cat_drop, L.xcat, KP, (int)L.Rc, M, CD, 0, L.row_src, st, &m__));
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.R * (M + CD) / 2 + (double)es * L.R * KP, L.st);
+        KCHK(c, vvk_pack_cat(c->dt, L.x, L.cat, L.cat_drop, L.xcat, KP, (int)L.Rc, M, CD, 0, L.row_src, L.st, &m__));
         return 0;
-    };
-    // input embedding of step s: proj, then conv position embedding (two grouped convs + Mish) + residual
-    // stage i > 0 of step s reads the stage state (packed rows, no row map) instead of x
+    }
     // the state stage i >= 1 is evaluated at: under APG the stages alternate between two buffers (stage i - 1 wrote it, stage i reads it as x_e
     // while it writes the other one)
-    auto stage_state = [&](const Lane& L, int i) -> float* { return (apg && !(i & 1)) ? L.xs2 : L.xs; };
-    auto step_pack = [&](Lane& L, int s, int i) -> int {
-        hipStream_t st = L.st;
-        const size_t Rc = L.Rc;
-        if (s != step0 || i > 0) {
-            Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * Rc * M + 2.0 * es * Rc * M, st);
-            KCHK(c, vvk_pack_cat(c->dt, i ? stage_state(L, i) : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)Rc, M, CD, 1, i ? nullptr : L.row_src, st, &m__));
-        }
+    float* stage_state(const Lane& L, int i) const { return (q.apg && !(i & 1)) ? L.xs2 : L.xs; }
+    // the conditioning pack of stage i of step s (setup packed the call's first evaluation): the n_mel state columns, read from x or,
+    // for a stage i > 0, from the stage state (packed rows, no row map)
+    int pack(Lane& L, GuideState& G, int s, int i) const {
+        if (q.guide) return guide_eval(L, G, i, s * ns + i);
+        if (s == q.a.step0 && i == 0) return 0;
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M + 2.0 * es * L.Rc * M, L.st);
+        KCHK(c, vvk_pack_cat(c->dt, i ? stage_state(L, i) : L.x, L.cat, L.cat_drop, L.xcat, KP, (int)L.Rc, M, CD, 1, i ? nullptr : L.row_src, L.st, &m__));
         return 0;
-    };
+    }
     // N8: evaluation e of a call with a mask -- the lane's guided subset, its tables when the subset differs from the previous evaluation's
     // (always at the call's first), and the pack: every column of the rows whose content moved (all rows at the call's first evaluation,
-    // the unconditional rows after a change of subset), else the n_mel state columns alone, as step_pack
-    auto guide_eval = [&](Lane& L, GuideState& G, int i, int e) -> int {
-        hipStream_t st = L.st;
-        const uint8_t* row = guide + (size_t)e * ld_guide + L.b0;
+    // the unconditional rows after a change of subset), else the n_mel state columns alone, as the plain pack
+    int guide_eval(Lane& L, GuideState& G, int i, int e) const {
+        const uint8_t* row = q.guide + (size_t)e * q.ld_guide + L.b0;
         std::vector<uint8_t> f(L.B);
         size_t Ru = 0; int Bu = 0; double sq = 0;
         for (int b = 0; b < L.B; ++b) {
@@ -1209,122 +1174,112 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         const bool first = G.flags.empty(), changed = first || f != G.flags;
         if (changed) {
             KCHK(c, vvk_guided_tables(L.seq_len, f.data(), L.B, N, (int)L.Rc, (int)Ru, L.g_row_start, L.g_rs_rel, L.g_kv_len, L.g_row_pos, L.u_src,
-                                      L.u_crow, L.u_row, st, &m__));
+                                      L.u_crow, L.u_row, L.st, &m__));
             if (c->rope_rows) {
-                KCHK(c, vvk_rope_rows(L.csq, L.g_row_pos, L.csq_rows, (int)(L.Rc + Ru), st, &m__));
-                KCHK(c, vvk_rope_rows(L.csk, L.g_row_pos, L.csk_rows, (int)(L.Rc + Ru), st, &m__));
+                KCHK(c, vvk_rope_rows(L.csq, L.g_row_pos, L.csq_rows, (int)(L.Rc + Ru), L.st, &m__));
+                KCHK(c, vvk_rope_rows(L.csk, L.g_row_pos, L.csk_rows, (int)(L.Rc + Ru), L.st, &m__));
             }
             G.flags = f; G.Ru = Ru; G.Bu = Bu; G.sum_sq = sq;
         }
         const float* xin = i ? stage_state(L, i) : L.x;
         const int Rc = (int)L.Rc, R = (int)(L.Rc + Ru);
-        auto pack = [&](int row0, int n_rows, int only_x) -> int {
-            Prof p(c, VV_PROF_ELEMWISE, 0, only_x ? (4.0 + es) * n_rows * M : 4.0 * n_rows * (M + CD) + (double)es * n_rows * KP, st);
+        auto rows = [&](int row0, int n_rows, int only_x) -> int {
+            Prof p(c, VV_PROF_ELEMWISE, 0, only_x ? (4.0 + es) * n_rows * M : 4.0 * n_rows * (M + CD) + (double)es * n_rows * KP, L.st);
             KCHK(c, vvk_pack_cat_guided(c->dt, xin, L.cat, L.cat_drop, L.xcat, KP, Rc, row0, n_rows, M, CD, only_x, i ? 1 : 0, L.row_src, L.u_src,
-                                        L.u_crow, st, &m__));
+                                        L.u_crow, L.st, &m__));
             return 0;
         };
-        if (first || !changed) return pack(0, R, first ? 0 : 1);
-        if (int r = pack(0, Rc, 1)) return r;
-        return Ru ? pack(Rc, (int)Ru, 0) : 0;
-    };
-    // (s below: the EVALUATION index step * ns + stage, the row of the modulation tables)
-    auto step_head = [&](Lane& L, int s) -> int {
-        (void)s;
-        hipStream_t st = L.st;
+        if (first || !changed) return rows(0, R, first ? 0 : 1);
+        if (int r = rows(0, Rc, 1)) return r;
+        return Ru ? rows(Rc, (int)Ru, 0) : 0;
+    }
+    // input embedding: proj, then conv position embedding (two grouped convs + Mish) + residual
+    int step_head(Lane& L) const {
         const size_t R = L.R;
         Gemm proj = gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_NONE_, L.xcat, KP, "input.proj.weight", KP, "input.proj.bias", L.h, D, (int)R, D, KP);
-        if (int r = launch_gemm(c, proj, VV_PROF_GEMM, st, 2.0 * R * D * (M + CD))) return r;
+        if (int r = launch_gemm(c, proj, VV_PROF_GEMM, L.st, 2.0 * R * D * (M + CD))) return r;
         for (int j = 1; j <= 2; ++j) {
             vv_posconv_args a{};
-            a.dtype = c->dt; a.out_dtype = (j == 1) ? c->dt : VV_DTYPE_F32;
-            a.in = (j == 1) ? L.h : L.h2; a.ld_in = D;
+            a.dtype = c->dt; a.out_dtype = (j == 1) ? c->dt : VV_DTYPE_F32; a.in = (j == 1) ? L.h : L.h2; a.ld_in = D;
             const std::string wn = "input.pos_conv" + std::to_string(j) + ".weight", bn = "input.pos_conv" + std::to_string(j) + ".bias";
             a.W = c->W(wn); a.bias = c->Wf(bn);
             a.out = (j == 1) ? (void*)L.h2 : (void*)L.xres; a.ld_out = D;
             a.resid = (j == 2) ? L.h : nullptr; a.ld_resid = D;
             a.n_seq = L.n_seq; a.seq_n = N; a.groups = g.pos_conv_groups; a.KW = g.pos_conv_k; a.B = L.n_seq; a.seq_len = L.kv_len; a.row_start = L.row_start;
-            Prof p(c, VV_PROF_POSCONV, 2.0 * R * D * 64 * g.pos_conv_k, (double)es * R * D * 2 + (j == 2 ? 4.0 * R * D : 0), st);
-            KCHK(c, vvk_posconv(&a, st, &m__));
+            Prof p(c, VV_PROF_POSCONV, 2.0 * R * D * 64 * g.pos_conv_k, (double)es * R * D * 2 + (j == 2 ? 4.0 * R * D : 0), L.st);
+            KCHK(c, vvk_posconv(&a, L.st, &m__));
         }
         L.pending = false;
         return 0;
-    };
+    }
     // Residual stream protocol: a branch GEMM writes delta = gate * (out + bias) (operand dtype) and a LayerNorm kernel adds
     // it while it streams x anyway (no read-modify-write in a GEMM epilogue).  x is REWRITTEN ONCE PER BLOCK: the norm
     // before the MLP normalises x + d_attn without storing it (keep_x), the next block's first norm stores
     // (x + d_attn) + d_mlp -- the same additions in the same order, a third fewer bytes written by the norm kernels.
-    auto block = [&](Lane& L, int s, int l) -> int {
-        hipStream_t st = L.st;
-        const size_t R = L.R;
+    // The residual LayerNorm behind a block (or, nothing pending, behind the step head): x + both deltas of that block -> L.h
+    vv_ln_args residual_ln(const Lane& L, const float* scale, const float* shift, int keep_x) const {
         const bool pending = L.pending;
-        const float* mod = c->modtab + ((size_t)l * S + s) * 6 * D;
+        vv_ln_args a{}; a.out_dtype = c->dt; a.x = L.xres; a.ldx = D; a.y = L.h; a.ldy = D; a.R = (int)L.R; a.D = D; a.add_one = 1; a.eps = 1e-6f;
+        a.delta_dtype = c->dt; a.ld_delta = D; a.tail_row0 = L.tail_row0; a.delta_tail = L.h2_tail; a.delta2_tail = L.h3_tail;
+        a.delta_tail_parts = pending ? L.tp_o : 0; a.delta2_tail_parts = pending ? L.tp_f : 0;
+        a.w = scale; a.b = shift; a.keep_x = keep_x; a.delta = pending ? L.h2 : nullptr; a.delta2 = pending ? L.h3 : nullptr;
+        return a;
+    }
+    // block l of evaluation e (= step * ns + stage, the row of the modulation tables)
+    int block(Lane& L, int e, int l) const {
+        const size_t R = L.R;
+        const float* mod = c->modtab + ((size_t)l * S + e) * 6 * D;
         const std::string qkvw = blk(l, ".attn.qkv.weight"), qkvb = blk(l, ".attn.qkv.bias"), ow = blk(l, ".attn.out.weight"),
                           ob = blk(l, ".attn.out.bias"), f1w = blk(l, ".ff1.weight"), f1b = blk(l, ".ff1.bias"),
                           f2w = blk(l, ".ff2.weight"), f2b = blk(l, ".ff2.bias");
-        vv_ln_args a{}; a.out_dtype = c->dt; a.x = L.xres; a.ldx = D; a.y = L.h; a.ldy = D; a.R = (int)R; a.D = D; a.add_one = 1; a.eps = 1e-6f;
-        a.delta_dtype = c->dt; a.ld_delta = D;
-        a.tail_row0 = L.tail_row0; a.delta_tail = L.h2_tail; a.delta2_tail = L.h3_tail;
-        a.delta_tail_parts = pending ? L.tp_o : 0; a.delta2_tail_parts = pending ? L.tp_f : 0;
-        a.w = mod + D; a.b = mod;                       // scale_msa, shift_msa
-        a.delta = pending ? L.h2 : nullptr; a.delta2 = pending ? L.h3 : nullptr; a.keep_x = 0;
-        { Prof p(c, VV_PROF_NORM, 0, (4.0 + es) * R * D + (pending ? (4.0 + 2.0 * es) * R * D : 0), st); KCHK(c, vvk_ln_mod(&a, st, &m__)); }
+        vv_ln_args a = residual_ln(L, mod + D, mod, 0);  // scale_msa, shift_msa; x is stored
+        { Prof p(c, VV_PROF_NORM, 0, (4.0 + es) * R * D + (L.pending ? (4.0 + 2.0 * es) * R * D : 0), L.st); KCHK(c, vvk_ln_mod(&a, L.st, &m__)); }
         Gemm qkv = gemm_args(c, c->dt, c->dt, VV_EPI_QKV_ROPE, VV_ACT_NONE_, L.h, D, qkvw.c_str(), D, qkvb.c_str(), L.qkv, 3 * D, (int)R, 3 * D, D);
-        qkv.cos_q = rope_cos_q; qkv.sin_q = rope_sin_q; qkv.cos_k = rope_cos_k; qkv.sin_k = rope_sin_k;
+        qkv.cos_q = q.a.rope_cos_q; qkv.sin_q = q.a.rope_sin_q; qkv.cos_k = q.a.rope_cos_k; qkv.sin_k = q.a.rope_sin_k;
         qkv.rope_cs_q = c->rope_rows ? L.csq_rows : L.csq; qkv.rope_cs_k = c->rope_rows ? L.csk_rows : L.csk; qkv.rope_by_row = c->rope_rows;
         qkv.seq_n = N; qkv.rope_dim = D; qkv.rope_pos = L.qkv_pos; qkv.rope_skip_q = q_rope_attn; qkv.rope_theta = rope_theta;
-        if (int r = launch_gemm(c, qkv, VV_PROF_GEMM, st)) return r;
+        if (int r = launch_gemm(c, qkv, VV_PROF_GEMM, L.st)) return r;
         {
             vv_attn_args t{}; t.dtype = c->dt; t.qkv = L.qkv; t.ld_qkv = 3 * D; t.out = L.att; t.ld_out = D; t.n_seq = L.n_seq; t.seq_n = N;
             t.heads = g.heads; t.dim = D; t.kv_len = L.kv_len; t.row_start = L.row_start; t.total_rows = (int)R;
-            t.rope_cs_q = q_rope_attn ? L.csq : nullptr;
-            t.q_scale = rope_theta > 0.f ? 1.0f / sqrtf((float)g.head_dim) : 0.f;
-            Prof p(c, VV_PROF_ATTN, 4.0 * g.heads * L.sum_sq * 64, (double)es * R * 4 * D, st);
-            KCHK(c, vvk_attention(&t, st, &m__));
+            t.rope_cs_q = q_rope_attn ? L.csq : nullptr; t.q_scale = rope_theta > 0.f ? 1.0f / sqrtf((float)g.head_dim) : 0.f;
+            Prof p(c, VV_PROF_ATTN, 4.0 * g.heads * L.sum_sq * 64, (double)es * R * 4 * D, L.st);
+            KCHK(c, vvk_attention(&t, L.st, &m__));
         }
         Gemm out = gemm_args(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.att, D, ow.c_str(), D, ob.c_str(), L.h2, D, (int)R, D, D);
         out.gate = mod + 2 * D;                         // gate_msa
         if (L.tp_o) { out.C_tail = L.h2_tail; out.tail_row0 = L.tail_row0; out.tail_parts = L.tp_o; }
-        if (int r = launch_gemm(c, out, VV_PROF_GEMM, st)) return r;
+        if (int r = launch_gemm(c, out, VV_PROF_GEMM, L.st)) return r;
         a.w = mod + 4 * D; a.b = mod + 3 * D;           // scale_mlp, shift_mlp
         a.delta = L.h2; a.delta2 = nullptr; a.keep_x = 1; a.delta_tail_parts = L.tp_o; a.delta2_tail_parts = 0;
-        { Prof p(c, VV_PROF_NORM, 0, (4.0 + 2.0 * es) * R * D, st); KCHK(c, vvk_ln_mod(&a, st, &m__)); }
-        if (int r = launch_gemm(c, gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_TANH_, L.h, D, f1w.c_str(), D, f1b.c_str(), L.ffm, FF, (int)R, FF, D), VV_PROF_GEMM, st)) return r;
+        { Prof p(c, VV_PROF_NORM, 0, (4.0 + 2.0 * es) * R * D, L.st); KCHK(c, vvk_ln_mod(&a, L.st, &m__)); }
+        if (int r = launch_gemm(c, gemm_args(c, c->dt, c->dt, VV_EPI_STORE, VV_ACT_GELU_TANH_, L.h, D, f1w.c_str(), D, f1b.c_str(), L.ffm, FF, (int)R, FF, D), VV_PROF_GEMM, L.st)) return r;
         Gemm ff2 = gemm_args(c, c->dt, c->dt, VV_EPI_GATE_STORE, VV_ACT_NONE_, L.ffm, FF, f2w.c_str(), FF, f2b.c_str(), L.h3, D, (int)R, D, FF);
         ff2.gate = mod + 5 * D;                         // gate_mlp
         if (L.tp_f) { ff2.C_tail = L.h3_tail; ff2.tail_row0 = L.tail_row0; ff2.tail_parts = L.tp_f; }
-        if (int r = launch_gemm(c, ff2, VV_PROF_GEMM, st)) return r;
+        if (int r = launch_gemm(c, ff2, VV_PROF_GEMM, L.st)) return r;
         L.pending = true;
         return 0;
-    };
-    auto step_tail = [&](Lane& L, int s) -> int {
-        hipStream_t st = L.st;
+    }
+    // the final norm and projection of evaluation e
+    int step_tail(Lane& L, int e) const {
         const size_t R = L.R;
-        const bool pending = L.pending;
-        {
-            const float* fm = c->fintab + (size_t)s * 2 * D;
-            vv_ln_args a{}; a.out_dtype = c->dt; a.x = L.xres; a.ldx = D; a.y = L.h; a.ldy = D; a.R = (int)R; a.D = D; a.add_one = 1; a.eps = 1e-6f;
-            a.w = fm; a.b = fm + D;                          // scale, shift
-            a.delta = pending ? L.h2 : nullptr; a.delta2 = pending ? L.h3 : nullptr; a.keep_x = 1;     // x is re-initialised by the next step
-            a.delta_dtype = c->dt; a.ld_delta = D;
-            a.tail_row0 = L.tail_row0; a.delta_tail = L.h2_tail; a.delta2_tail = L.h3_tail;
-            a.delta_tail_parts = pending ? L.tp_o : 0; a.delta2_tail_parts = pending ? L.tp_f : 0;
-            Prof p(c, VV_PROF_NORM, 0, es * R * D + (pending ? (4.0 + 2.0 * es) * R * D : 4.0 * R * D), st);
-            KCHK(c, vvk_ln_mod(&a, st, &m__));
-        }
+        const float* fm = c->fintab + (size_t)e * 2 * D;
+        vv_ln_args a = residual_ln(L, fm, fm + D, 1);        // scale, shift; x is re-initialised by the next step
+        { Prof p(c, VV_PROF_NORM, 0, es * R * D + (L.pending ? (4.0 + 2.0 * es) * R * D : 4.0 * R * D), L.st); KCHK(c, vvk_ln_mod(&a, L.st, &m__)); }
         Gemm proj = gemm_args(c, c->dt, VV_DTYPE_F32, VV_EPI_STORE, VV_ACT_NONE_, L.h, D, "final.proj.weight", D, "final.proj.bias", L.pred, MP, (int)R, MP, D);
         proj.n_store = M;
-        return launch_gemm(c, proj, VV_PROF_GEMM, st, 2.0 * R * D * M);
-    };
-    auto step_euler = [&](Lane& L, int s) -> int {
-        hipStream_t st = L.st;
-        Prof p(c, VV_PROF_ELEMWISE, 0, 16.0 * L.Rc * M, st);
-        KCHK(c, vvk_cfg_euler(L.x, L.pred, MP, (int)L.Rc, M, g.cfg_strength, c->dt_host[s], L.row_src, st, &m__));
-        return 0;
-    };
-    // N7: stage i of step s -- CFG combine, slope store, then the next stage's state or (last stage) x in place
-    auto step_stage = [&](Lane& L, int s, int i) -> int {
-        hipStream_t st = L.st;
+        return launch_gemm(c, proj, VV_PROF_GEMM, L.st, 2.0 * R * D * M);
+    }
+    // the combine of stage i of step s.  !rk: exactly the Euler launch of the s = 1 plan (vvk_cfg_euler).  Else N7 -- CFG combine, slope
+    // store, then the next stage's state or (last stage) x in place
+    int combine(Lane& L, int s, int i) const {
+        if (!q.rk) {
+            Prof p(c, VV_PROF_ELEMWISE, 0, 16.0 * L.Rc * M, L.st);
+            KCHK(c, vvk_cfg_euler(L.x, L.pred, MP, (int)L.Rc, M, g.cfg_strength, c->dt_host[s], L.row_src, L.st, &m__));
+            return 0;
+        }
+        const vv_apg_args* apg = q.apg;
         const bool last = i == ns - 1;
         const double h = (double)c->dt_host[s];
         vv_ode_stage_args a{};
@@ -1336,36 +1291,30 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         }
         a.k_out = (!last && c->ode_kslot[i] >= 0) ? L.kbuf[c->ode_kslot[i]] : nullptr;
         a.x_out = last ? nullptr : stage_state(L, i + 1);
-        a.g = g.cfg_strength; a.g_item = cfg_item ? cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
-        const int* u_row = guide ? L.u_row : nullptr;
+        a.g = g.cfg_strength; a.g_item = q.a.cfg_item ? q.a.cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
+        const int* u_row = q.guide ? L.u_row : nullptr;
         vv_apg_stage_args sa{};
         if (apg) {                                       // N11: the item sums of this evaluation, then their coefficients
-            vv_apg_coef_args q{};
-            q.pred = L.pred; q.ldp = MP; q.Rc = (int)L.Rc; q.n_mel = M; q.u_row = u_row;
-            q.x_e = i ? stage_state(L, i) : L.x; q.row_src = i ? nullptr : L.row_src;
-            q.B = L.B; q.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; q.row_start = L.row_start; q.len = L.kv_len;
-            q.t_e = apg->t_host[s * ns + i]; q.g = a.g; q.g_item = a.g_item;
-            q.eta = apg->eta ? apg->eta + L.b0 : nullptr; q.norm_rms = apg->norm_rms ? apg->norm_rms + L.b0 : nullptr;
-            q.partials = L.apg_part; q.coef = L.apg_coef;
-            { Prof p(c, VV_PROF_ELEMWISE, 14.0 * L.Rc * M, 12.0 * L.Rc * M, st); KCHK(c, vvk_apg_coef(&q, 1, st, &m__)); }
-            { Prof p(c, VV_PROF_ELEMWISE, 0, 24.0 * L.B * q.n_tiles, st); KCHK(c, vvk_apg_coef(&q, 2, st, &m__)); }
-            sa.coef = L.apg_coef; sa.x_e = q.x_e; sa.x_e_packed = i ? 1 : 0; sa.t_e = q.t_e;
+            vv_apg_coef_args k{};
+            k.pred = L.pred; k.ldp = MP; k.Rc = (int)L.Rc; k.n_mel = M; k.u_row = u_row;
+            k.x_e = i ? stage_state(L, i) : L.x; k.row_src = i ? nullptr : L.row_src;
+            k.B = L.B; k.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; k.row_start = L.row_start; k.len = L.kv_len;
+            k.t_e = apg->t_host[s * ns + i]; k.g = a.g; k.g_item = a.g_item;
+            k.eta = apg->eta ? apg->eta + L.b0 : nullptr; k.norm_rms = apg->norm_rms ? apg->norm_rms + L.b0 : nullptr;
+            k.partials = L.apg_part; k.coef = L.apg_coef;
+            { Prof p(c, VV_PROF_ELEMWISE, 14.0 * L.Rc * M, 12.0 * L.Rc * M, L.st); KCHK(c, vvk_apg_coef(&k, 1, L.st, &m__)); }
+            { Prof p(c, VV_PROF_ELEMWISE, 0, 24.0 * L.B * k.n_tiles, L.st); KCHK(c, vvk_apg_coef(&k, 2, L.st, &m__)); }
+            sa.coef = L.apg_coef; sa.x_e = k.x_e; sa.x_e_packed = i ? 1 : 0; sa.t_e = k.t_e;
         }
-        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0)), st);
-        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, st, &m__));
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0)), L.st);
+        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__));
         return 0;
-    };
-
-    // Launch order: the lanes alternate block by block, so both streams always hold work and neither lane's enqueue waits for the
-    // other's queue to drain; the device orders each stream by itself.  Item lanes: lane 1 forks from the caller's stream once (what
-    // the caller enqueued before this call is visible to it) and joins back at the end (what the caller enqueues next sees both
-    // lanes).  Branch lanes: the same fork / join once per STEP, between the conditioning pack and the CFG combine.
-    Lane views[2];                                        // what the block-level kernels run on
-    int n_views = n_lanes;
-    auto branch_view = [&](const Lane& L, int v) {
+    }
+    // What the block-level kernels (step_head, block, step_tail) run on: views of the lanes' buffers, two at the most; -> their number.
+    // The schedule gives each its stream.  Branch lanes: view v is the conditional (0) or the unconditional (1) half of the one lane's rows.
+    Lane branch_view(const Lane& L, int v) const {
         Lane V = L;
         const size_t r0 = v ? L.Rc : 0;                 // the unconditional branch's rows follow the conditional branch's
-        V.st = v ? c->side_stream[0] : st;
         V.R = L.Rc; V.n_seq = L.B; V.sum_sq = L.sum_sq / 2;
         V.xcat += r0 * KP * es; V.h += r0 * D * es; V.h2 += r0 * D * es; V.h3 += r0 * D * es; V.att += r0 * D * es;
         V.qkv += r0 * 3 * D * es; V.ffm += r0 * FF * es; V.xres += r0 * D; V.pred += r0 * MP;
@@ -1373,89 +1322,162 @@ static int transformer_steps_impl(vv_ctx* c, const vv_steps_args& args, uint64_t
         // row_start / kv_len: the conditional branch's entries serve both views (same lengths, rows relative to the view's base);
         // row_pos: the first Rc entries (a row's position does not depend on its branch)
         return V;
-    };
-    if (branch_lanes) {
-        n_views = 2;
-        for (int v = 0; v < 2; ++v) views[v] = branch_view(lanes[0], v);
-    } else {
-        for (int li = 0; li < n_lanes; ++li) views[li] = lanes[li];
     }
-    // N8: the views of one evaluation under a mask -- Rc + Ru rows and B + Bu sequences on the subset's tables.  Branch lanes: the side
-    // stream's view is the Ru compacted rows (sequence starts relative to the unconditional half); there is none when Ru = 0.
-    GuideState gstate[2];
-    auto guided_views = [&]() {
-        if (branch_lanes) {
-            const Lane& L = lanes[0];
-            const GuideState& G = gstate[0];
-            n_views = G.Ru ? 2 : 1;
-            for (int v = 0; v < n_views; ++v) {
-                Lane& V = views[v];
-                V = branch_view(L, v);
+    // The views of one evaluation.  gstate == nullptr (no mask): the lanes themselves, or the two halves of the one lane.
+    // N8, under a mask: Rc + Ru rows and B + Bu sequences on the subset's tables.  Branch lanes: the side stream's view is the Ru
+    // compacted rows (sequence starts relative to the unconditional half); there is none when Ru = 0.
+    int lane_views(const GuideState* gstate, Lane* views) const {
+        const int n_views = !P.branch_lanes ? P.n_lanes : (gstate && !gstate[0].Ru) ? 1 : 2;
+        for (int v = 0; v < n_views; ++v) {
+            const Lane& L = P.lanes[P.branch_lanes ? 0 : v];
+            Lane& V = views[v] = P.branch_lanes ? branch_view(L, v) : L;
+            if (!gstate) continue;
+            const GuideState& G = gstate[P.branch_lanes ? 0 : v];
+            if (P.branch_lanes) {
                 V.row_start = v ? L.g_rs_rel : L.g_row_start; V.kv_len = v ? L.g_kv_len + L.B : L.g_kv_len;
                 V.qkv_pos = L.uniform ? nullptr : (v ? L.g_row_pos + L.Rc : L.g_row_pos);
                 if (v) { V.R = G.Ru; V.n_seq = G.Bu; V.sum_sq = G.sum_sq; }
+            } else {
+                V.R = V.Rc + G.Ru; V.n_seq = V.B + G.Bu; V.sum_sq = V.sum_sq / 2 + G.sum_sq;
+                V.row_start = V.g_row_start; V.kv_len = V.g_kv_len; V.qkv_pos = V.uniform ? nullptr : V.g_row_pos;
             }
-            return;
         }
-        for (int li = 0; li < n_lanes; ++li) {
-            Lane& V = views[li];
-            const GuideState& G = gstate[li];
-            V = lanes[li];
-            V.R = V.Rc + G.Ru; V.n_seq = V.B + G.Bu; V.sum_sq = V.sum_sq / 2 + G.sum_sq;
-            V.row_start = V.g_row_start; V.kv_len = V.g_kv_len; V.qkv_pos = V.uniform ? nullptr : V.g_row_pos;
-        }
-    };
+        return n_views;
+    }
+};
+
+// The schedule of one call: order, streams (lane and view 0: the caller's, 1: the context's side stream, made on first use), forks, joins.
+// Launch order: the lanes alternate block by block, so both streams always hold work and neither lane's enqueue waits for the
+// other's queue to drain; the device orders each stream by itself.  Item lanes: lane 1 forks from the caller's stream once (what
+// the caller enqueued before this call is visible to it) and joins back at the end (what the caller enqueues next sees both
+// lanes).  Branch lanes: the same fork / join once per STEP, between the conditioning pack and the CFG combine.
+int steps_schedule(const StepsRun& r, Lane* lanes, hipStream_t st) {
+    vv_ctx* c = r.c;
+    const int n_lanes = r.P.n_lanes, step0 = r.q.a.step0, n_steps = r.q.a.n_steps;
+    const bool branch_lanes = r.P.branch_lanes, guide = r.q.guide != nullptr;
+    if ((n_lanes > 1 || branch_lanes) && !c->side_stream[0]) {
+        HIPCHK(c, hipStreamCreateWithFlags(&c->side_stream[0], hipStreamNonBlocking));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_join[0], hipEventDisableTiming));
+    }
+    if ((n_lanes > 1 || branch_lanes) && !c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    const hipStream_t streams[2] = {st, c->side_stream[0]};
     auto fork = [&]() -> int {
-        HIPCHK(c, hipEventRecord(c->ev_fork, st));
-        HIPCHK(c, hipStreamWaitEvent(c->side_stream[0], c->ev_fork, 0));
+        HIPCHK(c, hipEventRecord(c->ev_fork, st)); HIPCHK(c, hipStreamWaitEvent(c->side_stream[0], c->ev_fork, 0));
         return 0;
     };
-    auto join = [&]() {                                   // always reached, also after a failed launch: the side stream must not outlive the call
-        hipEventRecord(c->ev_join[0], c->side_stream[0]);
-        hipStreamWaitEvent(st, c->ev_join[0], 0);
+    // always reached, also after a failed launch: the side stream must not outlive the call
+    auto join = [&]() { hipEventRecord(c->ev_join[0], c->side_stream[0]); hipStreamWaitEvent(st, c->ev_join[0], 0); };
+    Lane views[2]; GuideState gstate[2];
+    auto make_views = [&](const GuideState* gs) {         // view v runs on stream v, as lane v does
+        const int n = r.lane_views(gs, views);
+        for (int v = 0; v < n; ++v) views[v].st = streams[v];
+        return c->chip_share = n;
     };
-    int rc = 0;
-    c->chip_share = n_views;
+    for (int li = 0; li < n_lanes; ++li) lanes[li].st = streams[li];
+    int n_views = make_views(nullptr), rc = 0;
     if (n_lanes > 1) rc = fork();
-    for (int li = 0; li < n_lanes && !rc; ++li) rc = setup(lanes[li]);
+    for (int li = 0; li < n_lanes && !rc; ++li) rc = r.setup(lanes[li]);
     for (int s = step0; s < step0 + n_steps && !rc; ++s)
-        for (int i = 0; i < ns && !rc; ++i) {             // the evaluations of one ODE step (one for Euler); branch lanes fork / join around each
-            const int e = s * ns + i;
-            if (guide) {
-                for (int li = 0; li < n_lanes && !rc; ++li) rc = guide_eval(lanes[li], gstate[li], i, e);
-                guided_views();
-                c->chip_share = n_views;
-            } else {
-                for (int li = 0; li < n_lanes && !rc; ++li) rc = step_pack(lanes[li], s, i);
-            }
+        for (int i = 0; i < r.ns && !rc; ++i) {           // the evaluations of one ODE step (one for Euler); branch lanes fork / join around each
+            const int e = s * r.ns + i;
+            for (int li = 0; li < n_lanes && !rc; ++li) rc = r.pack(lanes[li], gstate[li], s, i);
+            if (guide) n_views = make_views(gstate);      // N8: the views follow the evaluation's guided subset
             const bool want_fork = branch_lanes && n_views == 2;   // N8: an evaluation without unconditional rows neither forks nor joins
             if (want_fork && !rc) rc = fork();
             const bool forked = want_fork && !rc;
-            for (int v = 0; v < n_views && !rc; ++v) rc = step_head(views[v], e);
-            for (int l = 0; l < g.depth && !rc; ++l)
-                for (int v = 0; v < n_views && !rc; ++v) rc = block(views[v], e, l);
-            for (int v = 0; v < n_views && !rc; ++v) rc = step_tail(views[v], e);
+            for (int v = 0; v < n_views && !rc; ++v) rc = r.step_head(views[v]);
+            for (int l = 0; l < r.g.depth && !rc; ++l)
+                for (int v = 0; v < n_views && !rc; ++v) rc = r.block(views[v], e, l);
+            for (int v = 0; v < n_views && !rc; ++v) rc = r.step_tail(views[v], e);
             if (forked) join();
-            for (int li = 0; li < n_lanes && !rc; ++li) rc = rk ? step_stage(lanes[li], s, i) : step_euler(lanes[li], s);
+            for (int li = 0; li < n_lanes && !rc; ++li) rc = r.combine(lanes[li], s, i);
         }
     if (n_lanes > 1) join();
     c->chip_share = 1;
     return rc;
 }
+}  // namespace
 
-// the arguments of the positional entries as the struct the stage runs on
-static vv_steps_args steps_args(int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat, const float* cat_drop,
-                                const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k, int step0, int n_steps) {
-    vv_steps_args a{};
+// The stage: the checks every entry shares, the host lengths, the lane plan, the workspace, the schedule.
+// q.a.ws != nullptr: the workspace is taken from that caller-owned block instead of the context's (what a captured hipGraph must point into).
+static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
+    if (!c) return -22;
+    const vv_steps_args& a = q.a;
+    q.with_apg = q.apg != nullptr || q.ws_form == WS_APG; q.guided = q.guide != nullptr || q.ws_form != WS_PLAIN || q.with_apg;
+    q.rk = c->ode_s > 1 || a.cfg_item != nullptr || q.guide != nullptr || q.apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
+    const int B = a.B, N = a.N;
+    if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
+    if (B < 1 || N < 1 || (!q.ws_only && (!a.seq_len || !a.x || !a.cat_mel_text || !a.cat_mel_text_drop || !a.rope_cos_q || !a.rope_sin_q || !a.rope_cos_k || !a.rope_sin_k)))
+        return c->fail(-22, "vv_transformer_steps: bad arguments");
+    if (a.step0 < 0 || a.n_steps < 0 || a.step0 + a.n_steps > c->n_steps) return c->fail(-22, "vv_transformer_steps: steps [%d,%d) outside the time grid (%d)", a.step0, a.step0 + a.n_steps, c->n_steps);
+    if (q.guide && q.ld_guide < B) return c->fail(-22, "vv_transformer_steps_guided: ld_guide = %d < B = %d", q.ld_guide, B);
+    if (q.guide && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_guided: a guidance mask cannot be combined with option split_k_tail (its tail plan depends on the row count)");
+    if (q.guided && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_guided: at most %d items per call", VVK_GUIDE_MAX_ITEMS);
+    hipStream_t st = enter(c, stream);
+    const vv_model_cfg& g = c->cfg;
+    const StepDims d{g.dim, g.dim * g.ff_mult, g.n_mel, g.n_mel + g.text_dim, c->esz(), pad_to(2 * g.n_mel + g.text_dim, 64), pad_to(g.n_mel, 128)};
+    if ((size_t)2 * B * N > (size_t)1 << 30) return c->fail(-22, "batch too large");
+    // Ragged rows are PACKED: sequence (branch, b) owns rows [row_start, +len_b) of every activation buffer, the conditional
+    // branch first, so GEMMs / norms / convs touch sum(len) rows instead of B x N_max.  The host needs the row count for the
+    // launch shapes: the caller hands the lengths over on the host as well (vv_transformer_steps_h: no synchronisation at all,
+    // the call can be captured into a hipGraph), or they are read back once (4*B bytes, one stream synchronisation).  The row
+    // tables themselves are built on the device.  x, cat and cat_drop keep their padded [B][N] layout (row_src maps).
+    std::vector<int> hlen(B);
+    if (a.seq_len_host) std::copy(a.seq_len_host, a.seq_len_host + B, hlen.begin());
+    else {
+        HIPCHK(c, hipMemcpyAsync(hlen.data(), a.seq_len, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    size_t Rc_all = 0;
+    for (int b = 0; b < B; ++b) {
+        if (hlen[b] < 1 || hlen[b] > N) return c->fail(-22, "vv_transformer_steps: seq_len[%d] = %d outside [1, %d]", b, hlen[b], N);
+        Rc_all += hlen[b];
+    }
+    if (2 * Rc_all * 3 * (size_t)d.D * d.es >= ((size_t)1 << 31))
+        return c->fail(-22, "vv_transformer_steps: %zu packed rows make a %zu-byte qkv buffer; kernels address it with 32-bit byte offsets "
+                            "(< 2 GiB) -- synthesise fewer units per call", 2 * Rc_all, 2 * Rc_all * 3 * (size_t)d.D * d.es);
+    LanePlan P = lane_plan(c, d, hlen, N);
+    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg); };
+    if (q.ws_only) { *q.ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
+    if (int r = plan_ws(c, a.ws, (size_t)a.ws_bytes, bufs)) return r;
+    for (int li = 0; li < P.n_lanes; ++li) {              // each lane's slice of the call's arrays
+        Lane& L = P.lanes[li];
+        L.seq_len = a.seq_len + L.b0; L.x = a.x + (size_t)L.b0 * N * d.M;
+        L.cat = a.cat_mel_text + (size_t)L.b0 * N * d.CD; L.cat_drop = a.cat_mel_text_drop + (size_t)L.b0 * N * d.CD;
+    }
+    return steps_schedule(StepsRun(c, d, q, hlen, P), P.lanes, st);
+}
+
+// the arguments of the positional entries as the call the stage runs on
+static StepsCall steps_call(int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat, const float* cat_drop,
+                            const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k, int step0, int n_steps) {
+    StepsCall q; vv_steps_args& a = q.a;
     a.B = B; a.N = N; a.seq_len = seq_len; a.seq_len_host = seq_len_host; a.x = x; a.cat_mel_text = cat; a.cat_mel_text_drop = cat_drop;
     a.rope_cos_q = rope_cos_q; a.rope_sin_q = rope_sin_q; a.rope_cos_k = rope_cos_k; a.rope_sin_k = rope_sin_k; a.step0 = step0; a.n_steps = n_steps;
-    return a;
+    return q;
+}
+// the struct entries (_ex, _guided, _apg): what they check of their arguments, under the entry's name, and the call
+static int steps_struct_call(vv_ctx* c, const char* entry, const vv_steps_args* a, const uint8_t* guide, int ld_guide, const vv_apg_args* apg, void* stream) {
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "%s: null arguments", entry);
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "%s: a workspace block needs the host lengths", entry);
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "%s: cfg_item must be a float array", entry);
+    if (apg && !apg->t_host) return c->fail(-22, "%s: the evaluation times t_host are required", entry);
+    if (apg && ((uintptr_t)apg->eta | (uintptr_t)apg->norm_rms) % 4) return c->fail(-22, "%s: eta and norm_rms must be float arrays", entry);
+    StepsCall q; q.a = *a; q.guide = guide; q.ld_guide = ld_guide; q.apg = apg;
+    return transformer_steps(c, q, stream);
+}
+// the three size queries: nothing is launched, so no device pointer is needed
+static int steps_ws_query(vv_ctx* c, const char* entry, WsForm form, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
+    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "%s: bad arguments", entry);
+    StepsCall q; q.a.B = B; q.a.N = N; q.a.seq_len_host = seq_len_host; q.ws_form = form; q.ws_only = bytes;
+    return transformer_steps(c, q, nullptr);
 }
 
 int vv_transformer_steps(vv_ctx* c, int B, int N, const int32_t* seq_len, float* x, const float* cat, const float* cat_drop,
                          const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k, const float* rope_sin_k,
                          int step0, int n_steps, void* stream) {
-    return transformer_steps_impl(c, steps_args(B, N, seq_len, nullptr, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), nullptr, stream);
+    return transformer_steps(c, steps_call(B, N, seq_len, nullptr, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), stream);
 }
 
 // Same, with the per-item lengths ALSO given on the host (they must equal the device array): no read-back, no stream
@@ -1464,71 +1486,48 @@ int vv_transformer_steps_h(vv_ctx* c, int B, int N, const int32_t* seq_len, cons
                            const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
                            const float* rope_sin_k, int step0, int n_steps, void* stream) {
     if (c && !seq_len_host) return c->fail(-22, "vv_transformer_steps_h: host lengths missing");
-    return transformer_steps_impl(c, steps_args(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), nullptr, stream);
+    return transformer_steps(c, steps_call(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps), stream);
 }
 
 // The same call with every intermediate taken from a CALLER-OWNED block (>= vv_transformer_ws_bytes for the same B, N and host
 // lengths, 256-byte aligned): no allocation and no synchronisation anywhere in the call, and nothing it points at can move -- the
 // form to capture into a hipGraph (all Euler steps of an utterance + vv_decode_into = one graph launch).
 int vv_transformer_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
-    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_ws_bytes: bad arguments");
-    vv_steps_args a{};                                    // nothing is launched: no device pointer is needed
-    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
-    return transformer_steps_impl(c, a, bytes, nullptr);
+    return steps_ws_query(c, "vv_transformer_ws_bytes", WS_PLAIN, B, N, seq_len_host, bytes);
 }
 
 int vv_transformer_steps_into(vv_ctx* c, int B, int N, const int32_t* seq_len, const int32_t* seq_len_host, float* x, const float* cat,
                               const float* cat_drop, const float* rope_cos_q, const float* rope_sin_q, const float* rope_cos_k,
                               const float* rope_sin_k, int step0, int n_steps, void* ws, uint64_t ws_bytes, void* stream) {
     if (c && (!seq_len_host || !ws)) return c->fail(-22, "vv_transformer_steps_into: host lengths and a workspace block are required");
-    vv_steps_args a = steps_args(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps);
-    a.ws = ws; a.ws_bytes = ws_bytes;
-    return transformer_steps_impl(c, a, nullptr, stream);
+    StepsCall q = steps_call(B, N, seq_len, seq_len_host, x, cat, cat_drop, rope_cos_q, rope_sin_q, rope_cos_k, rope_sin_k, step0, n_steps);
+    q.a.ws = ws; q.a.ws_bytes = ws_bytes;
+    return transformer_steps(c, q, stream);
 }
 
 // N7: the struct-argument form -- the arguments of the three entries above plus a guidance strength per item
 int vv_transformer_steps_ex(vv_ctx* c, const vv_steps_args* a, void* stream) {
-    if (!c) return -22;
-    if (!a) return c->fail(-22, "vv_transformer_steps_ex: null arguments");
-    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_ex: a workspace block needs the host lengths");
-    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_ex: cfg_item must be a float array");
-    return transformer_steps_impl(c, *a, nullptr, stream);
+    return steps_struct_call(c, "vv_transformer_steps_ex", a, nullptr, 0, nullptr, stream);
 }
 
 // N8: a guidance mask on top of vv_transformer_steps_ex (include/vvtts.h)
 int vv_transformer_steps_guided(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, void* stream) {
     if (!guide_host) return vv_transformer_steps_ex(c, a, stream);
-    if (!c) return -22;
-    if (!a) return c->fail(-22, "vv_transformer_steps_guided: null arguments");
-    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_guided: a workspace block needs the host lengths");
-    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_guided: cfg_item must be a float array");
-    return transformer_steps_impl(c, *a, nullptr, stream, guide_host, ld_guide, false);
+    return steps_struct_call(c, "vv_transformer_steps_guided", a, guide_host, ld_guide, nullptr, stream);
 }
 
 int vv_transformer_guided_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
-    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_guided_ws_bytes: bad arguments");
-    vv_steps_args a{};
-    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
-    return transformer_steps_impl(c, a, bytes, nullptr, nullptr, 0, true);
+    return steps_ws_query(c, "vv_transformer_guided_ws_bytes", WS_GUIDED, B, N, seq_len_host, bytes);
 }
 
 // N11: projected guidance on top of vv_transformer_steps_guided (include/vvtts.h)
 int vv_transformer_steps_apg(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, const vv_apg_args* apg, void* stream) {
     if (!apg) return vv_transformer_steps_guided(c, a, guide_host, ld_guide, stream);
-    if (!c) return -22;
-    if (!a) return c->fail(-22, "vv_transformer_steps_apg: null arguments");
-    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_apg: a workspace block needs the host lengths");
-    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_apg: cfg_item must be a float array");
-    if (!apg->t_host) return c->fail(-22, "vv_transformer_steps_apg: the evaluation times t_host are required");
-    if (((uintptr_t)apg->eta | (uintptr_t)apg->norm_rms) % 4) return c->fail(-22, "vv_transformer_steps_apg: eta and norm_rms must be float arrays");
-    return transformer_steps_impl(c, *a, nullptr, stream, guide_host, ld_guide, false, apg, false);
+    return steps_struct_call(c, "vv_transformer_steps_apg", a, guide_host, ld_guide, apg, stream);
 }
 
 int vv_transformer_apg_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
-    if (c && (!seq_len_host || !bytes)) return c->fail(-22, "vv_transformer_apg_ws_bytes: bad arguments");
-    vv_steps_args a{};
-    a.B = B; a.N = N; a.seq_len_host = seq_len_host;
-    return transformer_steps_impl(c, a, bytes, nullptr, nullptr, 0, true, nullptr, true);
+    return steps_ws_query(c, "vv_transformer_apg_ws_bytes", WS_APG, B, N, seq_len_host, bytes);
 }
 
 // --------------------------------------------------------------------------------------- decode

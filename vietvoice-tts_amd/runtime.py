@@ -298,6 +298,16 @@ def _dt(s) -> Tuple[int, torch.dtype]:
     raise ValueError(f"acoustic dtype must be bf16 or fp32, got {s!r}")
 
 
+def _host_lens(B: int, values):
+    """B per-item lengths on the host, as the int32 array the ``*_h`` entries and ``seq_len_host`` fields take."""
+    return (C.c_int32 * B)(*[int(v) for v in values])
+
+
+def _pre_ptrs(pre) -> Tuple[int, ...]:
+    """The conditioning and rope tables of a ``pre`` dict as pointers, in the order the step entries take them."""
+    return tuple(pre[k].data_ptr() for k in ("cat_mel_text", "cat_mel_text_drop", "rope_cos_q", "rope_sin_q", "rope_cos_k", "rope_sin_k"))
+
+
 class HipSynth(PcmStage):
     """One GPU's synthesis engine: weights resident in HBM, three device-resident stages, and the PCM stage of pcm_stage.py.
 
@@ -408,8 +418,7 @@ class HipSynth(PcmStage):
         mal = int(max_audio_len if max_audio_len is not None else audio.shape[1])
         with self._lock, torch.cuda.device(self.device):
             if audio_len_host is not None:
-                host = (C.c_int32 * B)(*[int(v) for v in audio_len_host])
-                self._check(self.lib.vv_preprocess_h(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(), host,
+                self._check(self.lib.vv_preprocess_h(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(), _host_lens(B, audio_len_host),
                                                      text_ids.data_ptr(), text_ids.shape[1], text_len.data_ptr(), seq_len.data_ptr(),
                                                      cat.data_ptr(), cat_drop.data_ptr(), ref_len.data_ptr(), self._stream()))
             else:
@@ -466,35 +475,31 @@ class HipSynth(PcmStage):
             apg = None
         if cfg is not None or guide is not None or apg is not None:
             assert cfg is None or (cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,)), "cfg: fp32 [B] on the device"
-            host = None if seq_len_host is None else (C.c_int32 * B)(*[int(v) for v in seq_len_host])
+            host = None if seq_len_host is None else _host_lens(B, seq_len_host)
             self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg)
             return x
         with self._lock, torch.cuda.device(self.device):
-            tail = (pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr(), pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr(),
-                    pre["rope_cos_k"].data_ptr(), pre["rope_sin_k"].data_ptr(), step0, n_steps, self._stream())
+            tail = _pre_ptrs(pre) + (step0, n_steps, self._stream())
             if seq_len_host is not None:
-                host = (C.c_int32 * B)(*[int(v) for v in seq_len_host])
-                assert len(host) == B
-                self._check(self.lib.vv_transformer_steps_h(self.ctx, B, N, pre["seq_len"].data_ptr(), host, x.data_ptr(), *tail))
+                self._check(self.lib.vv_transformer_steps_h(self.ctx, B, N, pre["seq_len"].data_ptr(), _host_lens(B, seq_len_host), x.data_ptr(), *tail))
             else:
                 self._check(self.lib.vv_transformer_steps(self.ctx, B, N, pre["seq_len"].data_ptr(), x.data_ptr(), *tail))
         return x
 
-    def guided_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
-        """Bytes of a caller-owned workspace for a call with a guidance mask (vv_transformer_guided_ws_bytes; the same for every mask)."""
-        host = (C.c_int32 * B)(*[int(v) for v in seq_len_host])
+    def _steps_ws_bytes(self, entry, B: int, N: int, host) -> int:
+        """One of the three size queries of the transformer stage (``entry``) for the B host lengths ``host`` (a ctypes int32 array)."""
         nb = C.c_uint64()
         with self._lock:
-            self._check(self.lib.vv_transformer_guided_ws_bytes(self.ctx, int(B), int(N), host, C.byref(nb)))
+            self._check(entry(self.ctx, int(B), int(N), host, C.byref(nb)))
         return int(nb.value)
+
+    def guided_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
+        """Bytes of a caller-owned workspace for a call with a guidance mask (vv_transformer_guided_ws_bytes; the same for every mask)."""
+        return self._steps_ws_bytes(self.lib.vv_transformer_guided_ws_bytes, B, N, _host_lens(B, seq_len_host))
 
     def apg_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
         """Bytes of a caller-owned workspace for a call with projected guidance (vv_transformer_apg_ws_bytes; the same with any mask)."""
-        host = (C.c_int32 * B)(*[int(v) for v in seq_len_host])
-        nb = C.c_uint64()
-        with self._lock:
-            self._check(self.lib.vv_transformer_apg_ws_bytes(self.ctx, int(B), int(N), host, C.byref(nb)))
-        return int(nb.value)
+        return self._steps_ws_bytes(self.lib.vv_transformer_apg_ws_bytes, B, N, _host_lens(B, seq_len_host))
 
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
                              cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
@@ -504,7 +509,7 @@ class HipSynth(PcmStage):
         HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
         ld_guide >= B).  apg: None, or a pair (eta, norm) of fp32 [B] device tensors (either None), handed to
         vv_transformer_steps_apg with the times of the plan in force."""
-        B = x.shape[0]
+        B, N, _ = x.shape
         if apg is not None:
             if len(apg) != 2 or any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
                                                            and t.is_contiguous() and t.shape == (B,)) for t in apg):
@@ -513,13 +518,10 @@ class HipSynth(PcmStage):
             if not (isinstance(guide, torch.Tensor) and guide.device.type == "cpu" and guide.dtype == torch.uint8 and guide.dim() == 2
                     and guide.is_contiguous() and guide.shape[0] == self.n_evals):
                 raise ValueError(f"guide must be a contiguous uint8 host tensor [{self.n_evals} evaluations, >= B]")
-        B, N, _ = x.shape
         a = vv_steps_args()
         a.B, a.N, a.seq_len, a.x = B, N, pre["seq_len"].data_ptr(), x.data_ptr()
         a.seq_len_host = None if host is None else C.cast(host, C.c_void_p)
-        a.cat_mel_text, a.cat_mel_text_drop = pre["cat_mel_text"].data_ptr(), pre["cat_mel_text_drop"].data_ptr()
-        a.rope_cos_q, a.rope_sin_q = pre["rope_cos_q"].data_ptr(), pre["rope_sin_q"].data_ptr()
-        a.rope_cos_k, a.rope_sin_k = pre["rope_cos_k"].data_ptr(), pre["rope_sin_k"].data_ptr()
+        a.cat_mel_text, a.cat_mel_text_drop, a.rope_cos_q, a.rope_sin_q, a.rope_cos_k, a.rope_sin_k = _pre_ptrs(pre)
         a.step0, a.n_steps = int(step0), int(n_steps)
         if ws is not None:
             a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
@@ -665,9 +667,8 @@ class HipSynth(PcmStage):
         cat_drop = torch.empty_like(cat)
         ref_len = torch.empty((B,), dtype=torch.int32, device=self.device)
         mal = int(max_audio_len if max_audio_len is not None else audio.shape[1])
-        host = (C.c_int32 * B)(*[int(v) for v in audio_len_host])
         with self._lock, torch.cuda.device(self.device):
-            self._check(self.lib.vv_preprocess_edit(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(), host,
+            self._check(self.lib.vv_preprocess_edit(self.ctx, B, N, audio.data_ptr(), audio.shape[1], mal, audio_len.data_ptr(), _host_lens(B, audio_len_host),
                                                     text_ids.data_ptr(), text_ids.shape[1], text_len.data_ptr(), seq_len.data_ptr(),
                                                     cat.data_ptr(), cat_drop.data_ptr(), ref_len.data_ptr(), keep.data_ptr(), keep.shape[1],
                                                     self._stream()))
@@ -885,11 +886,10 @@ class GraphedSteps:
         self.ref_len = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.pcm = torch.zeros((B, t_gen_max * s.hop_length), dtype=torch.int16, device=dev)
         self.pcm_len = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self._host = (C.c_int32 * B)(*self.seq_host)
-        nb_t, nb_d = C.c_uint64(), C.c_uint64()
-        eng._check(eng.lib.vv_transformer_ws_bytes(eng.ctx, B, N, self._host, C.byref(nb_t)))
+        self._host = _host_lens(B, self.seq_host)
+        nb_t, nb_d = eng._steps_ws_bytes(eng.lib.vv_transformer_ws_bytes, B, N, self._host), C.c_uint64()
         eng._check(eng.lib.vv_decode_ws_bytes(eng.ctx, B, t_gen_max, C.byref(nb_d)))
-        self.ws = torch.empty((max(int(nb_t.value), int(nb_d.value)),), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty((max(nb_t, int(nb_d.value)),), dtype=torch.uint8, device=dev)
         self._launch()                                   # warm-up: sets kernel attributes before capture
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
