@@ -809,6 +809,44 @@ VV_API int vv_pcm_formant(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int1
                           const int64_t* rows_host, int R, const double* wa, const double* g, const double* window, int16_t* z, int64_t n_z,
                           double* h_out, int64_t n_h, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ---- N19 vocoder-bias denoiser: spectral subtraction against a stationary profile, first in the output chain (behind the
+ * join, before pitch and tempo).  bias is the magnitude spectrum the vocoder emits for an empty mel (vv_pcm_denoise_bias of that output), or
+ * the caller's own.  The arithmetic is pinned by core/audio_processor.py (denoise_fft, denoise_pcm, denoise_bias), which the kernels equal
+ * bit for bit.  With N, H below, x a request's n int16 samples (0 outside), M = ceil(n / H), frames f = 0 ... M + 2 starting at (f - 3) H:
+ *     transform: radix-2 decimation in time behind a bit reversal, stages of half-length h = 1, 2, ... N / 2; per butterfly (a, b) with
+ *                (c, s) = twiddles[j N / (2 h)]:  tr = br c - bi s;  ti = br s + bi c;  a' = a + t;  b' = a - t  (the stages with c = 1, s = 0
+ *                carry their products out like the others); the inverse negates s and does not scale
+ *     per frame: forward transform of w[k] x[(f - 3) H + k] with a zero imaginary part; for all N bins mag = sqrt(re re + im im),
+ *                d = mag - strength bias[k <= N / 2 ? k : N - k], g = d > 0 ? d / mag : 0, re g and im g; inverse transform; real part times w[k]
+ *     per hop i < M: acc = +0.0, then the contributions of frames i, i + 1, i + 2, i + 3 in that order;
+ *                y = clamp(rint(acc / 1536), -32768, 32767) for the samples of the hop inside n
+ *     bias of a signal: per bin 0 ... N / 2 the sum of mag over the full frames (start f H >= 0, f H + N <= n) from +0.0 with f ascending,
+ *                divided by their count
+ * in float64, every operation rounded on its own (no fused multiply-add), ties to even.  Strength 0, or an all-zero bias, gives the input
+ * back sample for sample (computed, not short-circuited).  The calls never synchronise and read nothing back.
+ *   rows       R x 4 int64 {x_off, n, y_off, bias_row} in device memory and the same rows in HOST memory (rows_host, checked by the call)
+ *   strengths  R float64 in device memory and the same values in HOST memory (strengths_host, checked by the call): 0 ... 16
+ *   bias       n_bias x 513 float64 on the device;  window: N float64, 0.5 - 0.5 cos(2 pi k / N);  twiddles: N float64, cos(2 pi k / N) for
+ *              k < N / 2, then -sin(2 pi k / N) (audio_processor.denoise_tables).  The device evaluates no cosine, no sine
+ *   y          int16 [n_y], must not overlap x (a hop reads the input under its neighbours); nothing outside the rows' outputs is written
+ *   mag_out    NULL, or float64 [n_mag] for a test: the N magnitudes of every frame, request after request, M + 3 frames each
+ *   ws         ws_bytes >= vv_pcm_denoise_ws_bytes(R), 8-byte aligned
+ * vv_pcm_denoise_bias takes the same rows (y_off and bias_row are not used) and writes R x 513 float64 to out [n_out]; a signal needs
+ * N <= n <= VV_DENOISE_BIAS_MAX_N; ws_bytes >= vv_pcm_denoise_bias_ws_bytes(sum of the full frames, R).
+ * -22, and nothing is launched, for no context, R < 1 or R > 65535, a null or misaligned pointer, a ws, a mag_out or an out that is too small,
+ * a negative field, n > 2^30, bias_row outside n_bias, a strength that is negative, not finite or above 16, a row outside n_x / n_y, rows that
+ * overlap on y, y overlapping x; for the bias a signal without a full frame or above the limit. */
+#define VV_DENOISE_N 1024
+#define VV_DENOISE_H 256
+#define VV_DENOISE_BIAS_MAX_N 1048576
+VV_API uint64_t vv_pcm_denoise_ws_bytes(int R);
+VV_API int vv_pcm_denoise(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* strengths,
+                          const double* strengths_host, const double* bias, int64_t n_bias, const double* window, const double* twiddles, int16_t* y,
+                          int64_t n_y, double* mag_out, int64_t n_mag, void* ws, uint64_t ws_bytes, void* stream);
+VV_API uint64_t vv_pcm_denoise_bias_ws_bytes(int64_t total_frames, int R);
+VV_API int vv_pcm_denoise_bias(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* window,
+                               const double* twiddles, double* out, int64_t n_out, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,7 @@ import numpy as np
 
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "formants", "t0", "n_req")
+    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "formants", "denoises", "t0", "n_req")
 
     def __init__(self):
         self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
@@ -44,6 +44,7 @@ class _Batch:
         self.lims = []                # per REQUEST: its own limiter mode (N13) or None
         self.pitches, self.tempos = [], []      # per REQUEST: its own pitch / tempo (N14) or None
         self.formants = []                      # per REQUEST: its own formants mode (N18) or None
+        self.denoises = []                      # per REQUEST: its own denoiser strength (N19) or None
 
 
 class BatchingFrontend:
@@ -77,7 +78,7 @@ class BatchingFrontend:
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
                cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
                loudness: Optional[float] = None, limiter: Optional[str] = None, pitch: Optional[float] = None, tempo: Optional[float] = None,
-               formants: Optional[str] = None, **voice) -> Future:
+               formants: Optional[str] = None, denoise: Optional[float] = None, **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
@@ -89,7 +90,9 @@ class BatchingFrontend:
         ``pitch`` (semitones, -12 ... 12) / ``tempo`` (0.5 ... 2.0): this request's prosody (None = the engine's
         ``output_pitch`` / ``output_tempo``), applied to this request alone; its batch neighbours are copied untouched.
         ``formants``: "shift" or "keep" (None = the engine's ``output_formants``): what this request's pitch does to its
-        spectral envelope, carried the same way."""
+        spectral envelope, carried the same way.
+        ``denoise``: this request's denoiser strength, 0 < s <= 16 (None = the engine's ``output_denoise``), applied to this
+        request alone, against the engine's bias profile."""
         fut: Future = Future()
         try:
             from .core.audio_processor import check_loudness
@@ -100,6 +103,8 @@ class BatchingFrontend:
             pitch, tempo = check_prosody(pitch, tempo)
             from .core.audio_processor import check_formants
             formants = None if formants is None else check_formants(formants)
+            from .core.audio_processor import check_denoise
+            denoise = check_denoise(denoise)
             from .model_spec import check_apg, check_cfg_interval
             cfg_interval = check_cfg_interval(cfg_interval)
             check_apg(apg_eta, apg_norm)
@@ -119,7 +124,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants))
+            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -152,7 +157,7 @@ class BatchingFrontend:
     def _prepare_one(self, req, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants = req
+        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise = req
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -190,6 +195,7 @@ class BatchingFrontend:
         batch.pitches.append(pitch)
         batch.tempos.append(tempo)
         batch.formants.append(formants)
+        batch.denoises.append(denoise)
         batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
@@ -299,7 +305,8 @@ class BatchingFrontend:
                 own = next((v for v in batch.louds if v is not None), None)      # N12: a request's own target takes the device stage too
                 own_lim = next((v for v in batch.lims if v is not None), None)      # N13: and so does a request's own limiter
                 own_pros = next((v for v in batch.pitches + batch.tempos if v is not None), None)      # N14: and its own pitch or tempo
-                dev_out = eng._device_output(own, own_lim, own_pros)      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
+                own_den = next((v for v in batch.denoises if v is not None), None)      # N19: and its own denoiser strength
+                dev_out = eng._device_output(own, own_lim, own_pros, own_den)      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
                 if batch.keys:
                     waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
                                                    device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
@@ -341,7 +348,8 @@ class BatchingFrontend:
             try:
                 finals = eng._finish_device(waves, [n for _f, n in batch.plans], loudness=batch.louds, limiter=batch.lims,
                                             pitch=batch.pitches, tempo=batch.tempos,
-                                            **({} if all(v is None for v in batch.formants) else {"formants": batch.formants}))
+                                            **({} if all(v is None for v in batch.formants) else {"formants": batch.formants}),
+                                            **({} if all(v is None for v in batch.denoises) else {"denoise": batch.denoises}))
             except Exception as e:        # noqa: BLE001
                 self._fail(batch, e)
                 return
@@ -350,9 +358,10 @@ class BatchingFrontend:
                 self.requests_done += 1
             return
         pos = 0
-        for (fut, n), loud, lim, pit, tem, fmt in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos, batch.formants):
+        for (fut, n), loud, lim, pit, tem, fmt, den in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos, batch.formants, batch.denoises):
             try:
-                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem, **({} if fmt is None else {"formants": fmt}))
+                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem, **({} if fmt is None else {"formants": fmt}),
+                                         **({} if den is None else {"denoise": den}))
                 fut.set_result((final, time.time() - batch.t0))
             except Exception as e:        # noqa: BLE001
                 fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))

@@ -1510,6 +1510,146 @@ def keep_formants(x, y, tn: int = 1, td: int = 1) -> np.ndarray:
     return apply_formant_filters(y, h)
 
 
+# ---------------------------------------------------------------------------- vocoder-bias denoiser
+# Spectral subtraction against a stationary profile, the "denoiser" of the public HiFi-GAN / WaveGlow inference code: the magnitude spectrum
+# the vocoder emits for an empty mel (the bias) times a strength is taken off the STFT magnitudes of an utterance, clamped at zero, the
+# phases kept.  The arithmetic below is the specification of vv_pcm_denoise (csrc/vv_denoise.hip), which equals it bit for bit: float64,
+# every operation rounded on its own, and a transform whose butterflies are written out -- radix-2 decimation in time behind a bit
+# reversal, stages of half-length h = 1, 2, ... N / 2; per butterfly (a, b) of a stage with tw = (c, s) = twiddle[j N / (2 h)]:
+#     tr = br c - bi s;  ti = br s + bi c;  a' = a + t;  b' = a - t                 (four products, two sums, then the two results)
+# with the products of the first stages (c = 1, s = 0) carried out like all others.  The inverse is the same with s negated, unscaled.
+DENOISE_N = 1024                     # VV_DENOISE_N: frame length and transform size, independent of the model's n_fft
+DENOISE_H = 256                      # VV_DENOISE_H: hop; every sample lies under four frames, sum of w^2 = 1.5 there
+DENOISE_BINS = DENOISE_N // 2 + 1    # entries of a bias profile
+DENOISE_SCALE = 1536.0               # N * 1.5: the unscaled inverse transform times the window's overlap sum
+DENOISE_MAX_STRENGTH = 16.0
+DENOISE_BIAS_MAX_N = 1 << 20         # the longest signal denoise_bias / vv_pcm_denoise_bias measure
+_DENOISE_TABLES = []
+
+
+def check_denoise(strength):
+    """Validate ``output_denoise``: None = off, else a strength s with 0 < s <= 16.  -> None or the float."""
+    if strength is None:
+        return None
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 < float(strength) <= DENOISE_MAX_STRENGTH:
+        raise ValueError(f"output_denoise must be None or a strength in (0, {DENOISE_MAX_STRENGTH:g}]")
+    return float(strength)
+
+
+def check_denoise_bias(bias):
+    """Validate a bias profile: DENOISE_BINS finite non-negative numbers.  -> float64 [513] (None stays None)."""
+    if bias is None:
+        return None
+    try:
+        b = np.asarray(bias, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"output_denoise_bias must be a sequence of {DENOISE_BINS} numbers") from None
+    if b.shape != (DENOISE_BINS,) or not np.all(np.isfinite(b)) or np.any(b < 0.0):
+        raise ValueError(f"output_denoise_bias must be a sequence of {DENOISE_BINS} finite non-negative numbers")
+    return b
+
+
+def denoise_tables():
+    """(w, tw): w[k] = 0.5 - 0.5 cos(2 pi k / N), k < N; tw [2][N / 2] = cos(2 pi k / N), -sin(2 pi k / N) (float64).  The device reads
+    these tables and evaluates neither a cosine nor a sine."""
+    if not _DENOISE_TABLES:
+        N = DENOISE_N
+        w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(N, dtype=np.float64) / np.float64(N))).astype(np.float64)
+        a = 2.0 * np.pi * np.arange(N // 2, dtype=np.float64) / np.float64(N)
+        tw = np.stack([np.cos(a), -np.sin(a)]).astype(np.float64)
+        rev = np.zeros(N, np.int64)
+        for b in range(N.bit_length() - 1):
+            rev |= ((np.arange(N) >> b) & 1) << (N.bit_length() - 2 - b)
+        for t in (w, tw, rev):
+            t.setflags(write=False)
+        _DENOISE_TABLES.append((w, tw, rev))
+    return _DENOISE_TABLES[0][:2]
+
+
+def denoise_fft(re: np.ndarray, im: np.ndarray, inverse: bool = False):
+    """The transform of the specification on every row of re, im [F][N] at once (each operation elementwise over the rows, so each row
+    sees the written order) -> (re, im) [F][N], unscaled in both directions."""
+    denoise_tables()
+    _w, tw, rev = _DENOISE_TABLES[0]
+    N = DENOISE_N
+    F = re.shape[0]
+    c, s = tw[0], (-tw[1] if inverse else tw[1])
+    re, im = np.ascontiguousarray(re[:, rev]), np.ascontiguousarray(im[:, rev])
+    h = 1
+    while h < N:
+        step = N // (2 * h)
+        cj, sj = c[::step][None, None, :], s[::step][None, None, :]                   # twiddle[j step], j < h
+        R, I = re.reshape(F, N // (2 * h), 2, h), im.reshape(F, N // (2 * h), 2, h)
+        ar, ai, br, bi = R[:, :, 0, :], I[:, :, 0, :], R[:, :, 1, :], I[:, :, 1, :]
+        tr = br * cj - bi * sj
+        ti = br * sj + bi * cj
+        re = np.stack([ar + tr, ar - tr], axis=2).reshape(F, N)
+        im = np.stack([ai + ti, ai - ti], axis=2).reshape(F, N)
+        h *= 2
+    return re, im
+
+
+def _denoise_frames(x: np.ndarray, starts: np.ndarray) -> np.ndarray:
+    """w[k] x[start + k] for every start, x zero outside the signal -> float64 [F][N]."""
+    N = DENOISE_N
+    w = denoise_tables()[0]
+    xp = np.zeros(x.size + 2 * N + int(starts.max(initial=0)) + 1, np.float64)
+    xp[N: N + x.size] = x
+    return w[None, :] * xp[N + starts[:, None] + np.arange(N, dtype=np.int64)[None, :]]
+
+
+def denoise_bias(pcm) -> np.ndarray:
+    """The bias profile of a signal, the mirror of vv_pcm_denoise_bias: per bin 0 ... N / 2 the mean magnitude over the
+    full frames, those that start at a multiple of H at or behind sample 0 and end inside the signal, summed from +0.0 with the frame
+    ascending and divided by their count.  -> float64 [513]; a signal without a full frame is refused."""
+    x = _as_pcm16(pcm)
+    N, H = DENOISE_N, DENOISE_H
+    if x.size < N or x.size > DENOISE_BIAS_MAX_N:
+        raise ValueError(f"denoise_bias: a signal of {N} ... {DENOISE_BIAS_MAX_N} samples is needed (one full frame), got {x.size}")
+    starts = np.arange((x.size - N) // H + 1, dtype=np.int64) * H
+    fr = _denoise_frames(x, starts)
+    re, im = denoise_fft(fr, np.zeros_like(fr))
+    re, im = re[:, :DENOISE_BINS], im[:, :DENOISE_BINS]
+    mag = np.sqrt(re * re + im * im)
+    acc = np.zeros(DENOISE_BINS, np.float64)
+    for f in range(starts.size):
+        acc = acc + mag[f]
+    return acc / np.float64(starts.size)
+
+
+def denoise_pcm(pcm, bias, strength, mags: bool = False):
+    """The denoiser: the host mirror of vv_pcm_denoise, bit for bit.  pcm int16 [n]; bias = 513 non-negative float64
+    (denoise_bias of the vocoder's output for an empty mel, or the caller's own); strength 0 ... 16 (0 is computed like any other and
+    gives the input back).  With M = ceil(n / H), frames f = 0 ... M + 2 starting at (f - 3) H: forward transform of w u, per bin
+    mag = sqrt(re re + im im), d = mag - s bias, g = d > 0 ? d / mag : 0, re g and im g, inverse transform, real part times w; hop i
+    adds frames i ... i + 3 in that order from +0.0 and z = clamp(rint(acc / 1536)).  -> int16 [n], with ``mags`` also float64 [M + 3][N]."""
+    x = _as_pcm16(pcm)
+    N, H = DENOISE_N, DENOISE_H
+    b = check_denoise_bias(bias)
+    if b is None:
+        raise ValueError("denoise_pcm: a bias profile is needed")
+    if isinstance(strength, bool) or not isinstance(strength, (int, float)) or not 0.0 <= float(strength) <= DENOISE_MAX_STRENGTH:
+        raise ValueError(f"denoise_pcm: the strength is a number in 0 ... {DENOISE_MAX_STRENGTH:g}")
+    s = float(strength)
+    n = x.size
+    M = -(-n // H)
+    starts = (np.arange(M + 3, dtype=np.int64) - 3) * H
+    fr = _denoise_frames(x, starts)                                                   # starts from -3 H on: the padding in front covers them
+    re, im = denoise_fft(fr, np.zeros_like(fr))
+    full = np.concatenate([b, b[N // 2 - 1: 0: -1]])                                  # bin k > N / 2 uses bias[N - k]
+    mag = np.sqrt(re * re + im * im)
+    d = mag - np.float64(s) * full[None, :]
+    g = np.zeros_like(mag)
+    np.divide(d, mag, out=g, where=d > 0.0)
+    re, _im = denoise_fft(re * g, im * g, inverse=True)
+    c = (re * denoise_tables()[0][None, :]).reshape(M + 3, 4, H)
+    acc = np.zeros((M, H), np.float64)
+    for j in range(4):                                                                # frame i + j lies (3 - j) hops into itself at hop i
+        acc = acc + c[j: j + M, 3 - j]
+    z = np.clip(np.rint(acc / DENOISE_SCALE), -32768.0, 32767.0).astype(np.int16).reshape(-1)[:n]
+    return (z, mag) if mags else z
+
+
 class AudioProcessor:
     """Static helpers, same names and semantics as the reference class."""
 

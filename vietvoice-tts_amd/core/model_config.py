@@ -17,7 +17,7 @@ import logging
 import os
 from dataclasses import dataclass, fields
 from pathlib import Path
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 logger = logging.getLogger("vietvoicetts")
 
@@ -96,6 +96,12 @@ class ModelConfig:
                                             # the pitch (N14 as ever); "keep" = an LPC envelope correction behind the rate conversion puts the envelope of
                                             # the joined signal back, the harmonics stay where the pitch put them.  Acts only where the pitch ratio is not
                                             # 1.  vv_pcm_formant on the HIP engine, audio_processor.keep_formants on injected sessions
+    output_denoise: Optional[float] = None  # strength of the vocoder-bias denoiser, 0 < s <= 16: s times a stationary magnitude profile is
+                                            # taken off the STFT magnitudes of the joined signal (clamped at zero, phases kept), before pitch and tempo.
+                                            # vv_pcm_denoise on the HIP engine, audio_processor.denoise_pcm on the host.  Not available in synthesize_stream
+    output_denoise_bias: Optional[Sequence[float]] = None      # the profile: 513 non-negative magnitudes (bins 0 ... 512 of a 1024-point Hann frame of
+                                            # int16 samples).  None = the model's own: what its decoder emits for an empty mel (HipSynth.vocoder_bias),
+                                            # which needs the HIP engine
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -136,6 +142,10 @@ class ModelConfig:
         self.output_pitch, self.output_tempo = check_prosody(self.output_pitch, self.output_tempo)
         from .audio_processor import check_formants
         self.output_formants = check_formants(self.output_formants)
+        from .audio_processor import check_denoise, check_denoise_bias
+        self.output_denoise = check_denoise(self.output_denoise)
+        bias = check_denoise_bias(self.output_denoise_bias)
+        self.output_denoise_bias = None if bias is None else [float(v) for v in bias]      # a plain list: to_dict / JSON keep working
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

@@ -169,23 +169,40 @@ class TTSEngine:
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
 
-    def _device_output(self, loudness=None, limiter=None, prosody=None) -> bool:
+    def _device_output(self, loudness=None, limiter=None, prosody=None, denoise=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate, an encoding, a loudness target, a limiter, a pitch or a tempo (the engine's, or a request's own: ``loudness``, ``limiter``,
-        ``prosody``) is set.  False = today's path: one copy per chunk group, the numpy join."""
+        rate, an encoding, a loudness target, a limiter, a pitch, a tempo or a denoiser strength (the engine's, or a request's own:
+        ``loudness``, ``limiter``, ``prosody``, ``denoise``) is set.  False = today's path: one copy per chunk group, the numpy join."""
         rate, enc = self._output_options()
         return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16"
                                                                   or self.config.output_loudness is not None or loudness is not None
                                                                   or self.config.output_limiter is not None or limiter is not None
                                                                   or self.config.output_pitch is not None or self.config.output_tempo is not None
-                                                                  or prosody is not None)
+                                                                  or prosody is not None
+                                                                  or self.config.output_denoise is not None or denoise is not None)
 
-    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None, formants=None) -> np.ndarray:
-        """One request's chunks -> its final audio on the host: the reference's join, then the host mirrors of pitch and tempo (N14;
+    def _denoise_bias_host(self) -> np.ndarray:
+        """The bias profile the host mirror subtracts (N19): the caller's ``output_denoise_bias``, else the model's own, which only a HIP
+        engine can decode (HipSynth.vocoder_bias; the device's 513 values equal the mirror's bit for bit)."""
+        if self.config.output_denoise_bias is not None:
+            return np.asarray(self.config.output_denoise_bias, dtype=np.float64)
+        eng = self.model_session_manager.engine
+        if eng is None:
+            raise ValueError("output_denoise without output_denoise_bias needs the HIP engine: the model's bias is what its decoder makes of an "
+                             "empty mel; give output_denoise_bias, or unset output_denoise")
+        return eng.vocoder_bias()[0].cpu().numpy()
+
+    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None, formants=None, denoise=None) -> np.ndarray:
+        """One request's chunks -> its final audio on the host: the reference's join, the denoiser's mirror directly behind it (N19;
+        ``denoise`` = the request's own strength, None = the engine's), then the host mirrors of pitch and tempo (N14;
         ``pitch`` / ``tempo`` = the request's own, None = the engine's), the loudness normalisation (N12; ``loudness`` likewise), the
         limiter (N13; ``limiter`` likewise), the output rate and the encoding."""
         from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output, shift_prosody
         final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
+        denoise = self.config.output_denoise if denoise is None else denoise
+        if denoise is not None:
+            from .audio_processor import denoise_pcm
+            final = denoise_pcm(np.ascontiguousarray(final, dtype=np.int16), self._denoise_bias_host(), denoise)
         pitch = self.config.output_pitch if pitch is None else pitch
         tempo = self.config.output_tempo if tempo is None else tempo
         if pitch is not None or tempo is not None:
@@ -203,10 +220,20 @@ class TTSEngine:
             final = resample_output(final, self.config.sample_rate, rate)
         return encode_output(final, enc, self.output_rate, **self._flac_options()) if enc != "pcm16" else final
 
-    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None, formants=None) -> List[np.ndarray]:
+    def _denoise_options(self, own=None, R: int = 1) -> dict:
+        """finish_output's ``denoise`` / ``denoise_bias`` (N19): nothing when no request has a strength -- the call of N18 as it was."""
+        mine = self.config.output_denoise
+        vals = [mine] * R if own is None else [mine if v is None else v for v in own]
+        if all(v is None for v in vals):
+            return {}
+        bias = self.config.output_denoise_bias
+        return {"denoise": vals, **({} if bias is None else {"denoise_bias": bias})}
+
+    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None, formants=None, denoise=None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
         one HipSynth.finish_output call (join, prosody, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per
-        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14) and ``formants`` (N18) likewise."""
+        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14), ``formants`` (N18) and ``denoise``
+        (N19) likewise."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
@@ -229,6 +256,7 @@ class TTSEngine:
         keep = [self.config.output_formants] * len(counts) if formants is None else [self.config.output_formants if v is None else v for v in formants]
         if "keep" in keep and "pitch" in opts:             # "shift" everywhere, or no pitch anywhere: exactly the call of N14
             opts["formants"] = keep
+        opts.update(self._denoise_options(denoise, len(counts)))
         return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
                                                                loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **opts)
 
@@ -399,7 +427,11 @@ class TTSEngine:
         revisited, and the concatenation of all yielded blocks equals ``synthesize(text)`` sample for sample.
         With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance.
         ``output_limiter`` alone streams (N13): a LimiterStream in front of the output rate / encoding holds back 2L + H samples.
-        ``output_pitch`` / ``output_tempo`` raise ValueError at once as well (N14): every frame position depends on the whole past."""
+        ``output_pitch`` / ``output_tempo`` raise ValueError at once as well (N14): every frame position depends on the whole past.
+        ``output_denoise`` (N19) raises ValueError at once too: there is no block-wise denoiser yet."""
+        if self.config.output_denoise is not None:        # N19: frames reach 768 samples back; a block-wise DenoiseStream does not exist yet
+            raise ValueError("synthesize_stream cannot honour output_denoise: the denoiser works on the whole joined utterance; use "
+                             "synthesize, or unset output_denoise")
         if self.config.output_pitch is not None or self.config.output_tempo is not None:
             raise ValueError("synthesize_stream cannot honour output_pitch / output_tempo: the chain of frame positions needs the whole "
                              "utterance; use synthesize, or unset them")
@@ -539,7 +571,7 @@ class TTSEngine:
                                              **({} if cfg.output_pitch is None and cfg.output_tempo is None
                                                 else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}),
                                              **({"formants": "keep"} if cfg.output_formants == "keep" and cfg.output_pitch is not None else {}),
-                                             **self._flac_options("flac_lpc_order"))[0]
+                                             **self._denoise_options(), **self._flac_options("flac_lpc_order"))[0]
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.11 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.12 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -208,7 +208,7 @@ int launch_gemm(vv_ctx* c, Gemm g, int cls, hipStream_t st, double alg_flops = -
 
 std::string blk(int i, const char* s) { return "blocks." + std::to_string(i) + s; }
 
-// ---- the checks the PCM entries (N10 ... N17) share.  Each refusal is -22 with the entry's name in front, before anything is launched.
+// ---- the checks the PCM entries (N10 ... N19) share.  Each refusal is -22 with the entry's name in front, before anything is launched.
 // the prologue, behind the entry's own ``if (!c) return -22``: the context's device is made current -> the caller's stream
 inline hipStream_t enter(vv_ctx* c, void* stream) {
     hipSetDevice(c->device);
@@ -860,6 +860,78 @@ int vv_pcm_formant(vv_ctx* c, const int16_t* x, int64_t n_x, const int16_t* y, i
            24.0 * (double)total_frames * VV_FORMANT_L + 4.0 * (double)total_out, st);
     KCHK(c, vvk_pcm_formant(x, (long long)n_x, y, (long long)n_y, (const long long*)rows, R, (long long)total_frames, (long long)max_frames, wa, g,
                             window, z, (long long)n_z, h_out, ws, st, &m__));
+    return 0;
+}
+
+// N19: the vocoder-bias denoiser.  As with N12 ... N18 the rows come in host memory too, and so do the strengths: everything is checked before
+// a launch.
+uint64_t vv_pcm_denoise_ws_bytes(int R) { return vvk_pcm_denoise_ws_bytes(R); }
+
+int vv_pcm_denoise(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* strengths,
+                   const double* strengths_host, const double* bias, int64_t n_bias, const double* window, const double* twiddles, int16_t* y,
+                   int64_t n_y, double* mag_out, int64_t n_mag, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0 || n_bias < 1 || n_mag < 0) return c->fail(-22, "vv_pcm_denoise: bad sizes (1 <= R <= 65535, n_bias >= 1)");
+    if (int e = check_ptrs(c, "vv_pcm_denoise", {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host}, {"strengths", strengths, 8},
+                                                 {"strengths_host", strengths_host}, {"bias", bias, 8}, {"window", window, 8},
+                                                 {"twiddles", twiddles, 8}, {"y", y, 2}, {"mag_out", mag_out, 8, true}, {"ws", ws, 8}})) return e;
+    if (spans_overlap(x, 2ull * n_x, y, 2ull * n_y))
+        return c->fail(-22, "vv_pcm_denoise: y overlaps x (a hop reads the input under its neighbours: not in place)");
+    std::vector<std::pair<int64_t, int64_t>> on_y;
+    int64_t total_frames = 0, max_hops = 1, total_hops = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 4 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "vv_pcm_denoise: row %d has a negative field", r);
+        if (q[3] >= n_bias) return c->fail(-22, "vv_pcm_denoise: row %d: bias_row %lld of %lld", r, (long long)q[3], (long long)n_bias);
+        if (!(strengths_host[r] >= 0.0 && strengths_host[r] <= 16.0)) return c->fail(-22, "vv_pcm_denoise: row %d: a strength in 0 ... 16 is needed", r);
+        if (!fits(q[0], q[1], n_x) || q[1] > ((int64_t)1 << 30))
+            return c->fail(-22, "vv_pcm_denoise: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (!fits(q[2], q[1], n_y)) return c->fail(-22, "vv_pcm_denoise: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        const int64_t M = (q[1] + VV_DENOISE_H - 1) / VV_DENOISE_H, hops = M > 0 ? M : 1;
+        if (q[1] > 0) on_y.emplace_back(q[2], q[2] + q[1]);
+        total_frames += M + 3;
+        total_hops += hops;
+        if (hops > max_hops) max_hops = hops;
+    }
+    std::sort(on_y.begin(), on_y.end());
+    for (size_t i = 1; i < on_y.size(); ++i)
+        if (on_y[i].first < on_y[i - 1].second) return c->fail(-22, "vv_pcm_denoise: rows overlap on y");
+    if (mag_out && n_mag / VV_DENOISE_N < total_frames)
+        return c->fail(-22, "vv_pcm_denoise: mag_out of %lld doubles, %lld are needed", (long long)n_mag, (long long)total_frames * VV_DENOISE_N);
+    if (int e = check_ws(c, "vv_pcm_denoise", ws_bytes, vvk_pcm_denoise_ws_bytes(R))) return e;
+    Prof p(c, VV_PROF_ELEMWISE, (double)total_hops * 8.0 * 10.0 * 512.0 * 10.0, 16.0 * (double)total_hops * VV_DENOISE_H, st);
+    KCHK(c, vvk_pcm_denoise(x, (long long)n_x, (const long long*)rows, R, (long long)total_frames, (long long)max_hops, strengths, bias,
+                            (long long)n_bias, window, twiddles, y, (long long)n_y, mag_out, ws, st, &m__));
+    return 0;
+}
+
+uint64_t vv_pcm_denoise_bias_ws_bytes(int64_t total_frames, int R) { return vvk_pcm_denoise_bias_ws_bytes((long long)total_frames, R); }
+
+int vv_pcm_denoise_bias(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* window,
+                        const double* twiddles, double* out, int64_t n_out, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_out < 0) return c->fail(-22, "vv_pcm_denoise_bias: bad sizes (1 <= R <= 65535)");
+    if (int e = check_ptrs(c, "vv_pcm_denoise_bias", {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host}, {"window", window, 8},
+                                                      {"twiddles", twiddles, 8}, {"out", out, 8}, {"ws", ws, 8}})) return e;
+    int64_t total_frames = 0, max_frames = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 4 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "vv_pcm_denoise_bias: row %d has a negative field", r);
+        if (q[1] < VV_DENOISE_N || q[1] > VV_DENOISE_BIAS_MAX_N || !fits(q[0], q[1], n_x))
+            return c->fail(-22, "vv_pcm_denoise_bias: row %d: a signal of %d ... %d samples inside the %lld samples of x is needed (one full frame)", r,
+                           VV_DENOISE_N, VV_DENOISE_BIAS_MAX_N, (long long)n_x);
+        const int64_t F = (q[1] - VV_DENOISE_N) / VV_DENOISE_H + 1;
+        total_frames += F;
+        if (F > max_frames) max_frames = F;
+    }
+    if (n_out / (VV_DENOISE_N / 2 + 1) < R)
+        return c->fail(-22, "vv_pcm_denoise_bias: out of %lld doubles, %lld are needed", (long long)n_out, (long long)R * (VV_DENOISE_N / 2 + 1));
+    if (int e = check_ws(c, "vv_pcm_denoise_bias", ws_bytes, vvk_pcm_denoise_bias_ws_bytes((long long)total_frames, R))) return e;
+    Prof p(c, VV_PROF_ELEMWISE, (double)total_frames * 10.0 * 512.0 * 10.0, (double)total_frames * (2.0 * VV_DENOISE_N + 16.0 * (VV_DENOISE_N / 2 + 1)), st);
+    KCHK(c, vvk_pcm_denoise_bias(x, (long long)n_x, (const long long*)rows, R, (long long)total_frames, (long long)max_frames, window, twiddles, out,
+                                 ws, st, &m__));
     return 0;
 }
 

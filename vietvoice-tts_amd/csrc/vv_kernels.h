@@ -103,6 +103,16 @@ unsigned long long vvk_pcm_formant_ws_bytes(long long total_frames, int R);
 int vvk_pcm_formant(const int16_t* x, long long n_x, const int16_t* y, long long n_y, const long long* rows, int R, long long total_frames,
                     long long max_frames, const double* wa, const double* g, const double* window, int16_t* z, long long n_z, double* h_out,
                     void* ws, hipStream_t st, const char** err);
+// N19 vocoder-bias denoiser (vv_denoise.hip): per output hop the four frames above it, forward transform, mag - s bias clamped at zero, inverse,
+// overlap-add; rows R x 4 {x_off, n, y_off, bias_row}.  total_frames = the sum of M + 3, max_hops = the largest max(M, 1)
+unsigned long long vvk_pcm_denoise_ws_bytes(int R);
+int vvk_pcm_denoise(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_hops, const double* strengths,
+                    const double* bias, long long n_bias, const double* window, const double* twiddles, int16_t* y, long long n_y, double* mag_out,
+                    void* ws, hipStream_t st, const char** err);
+// the bias of R signals: the mean magnitude of bins 0 ... 512 over the full frames; total_frames / max_frames count those
+unsigned long long vvk_pcm_denoise_bias_ws_bytes(long long total_frames, int R);
+int vvk_pcm_denoise_bias(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_frames,
+                         const double* window, const double* twiddles, double* out, void* ws, hipStream_t st, const char** err);
 // N15 FLAC output (vv_flac.hip): per frame of 4096 samples the exhaustive fixed-predictor / Rice search, the frames' offsets, the bit packing;
 // rows R x 4 {src_off, n, frame0, last}
 unsigned long long vvk_flac_frame_bound(long long m);

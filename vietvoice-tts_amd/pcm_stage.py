@@ -1,4 +1,4 @@
-"""The PCM stage of HipSynth (DESIGN §8 N10 ... N18, layering described there): per call a pure plan_* function of host values (every
+"""The PCM stage of HipSynth (DESIGN §8 N10 ... N19, layering described there): per call a pure plan_* function of host values (every
 ValueError, the row table, the derived sizes; no GPU needed) and a launch method of PcmStage, which HipSynth inherits."""
 from typing import Optional
 
@@ -272,6 +272,55 @@ def plan_keep(plans, offs, lens, new_offs, new_lens, formants):
     return rows
 
 
+def plan_denoise(rows, strengths, n_x: int, n_bias: int, out_n: Optional[int] = None, overlaps: bool = False):
+    """vv_pcm_denoise's rows {x_off, n, y_off, bias_row} and one strength per row (or one for all), validated -> (rows, strengths as floats,
+    frame offsets [R + 1]: request r's frames 0 ... M + 2 are frame_offs[r] ... frame_offs[r + 1] - 1, n_y); out_n: _out_arg; overlaps: out
+    shares memory with x."""
+    import math
+    from .core.audio_processor import DENOISE_H, DENOISE_MAX_STRENGTH
+    rows = _int_rows("pcm_denoise", rows, (4,), "4 entries {x_off, n, y_off, bias_row}")
+    strengths = _per_request("pcm_denoise", strengths, len(rows), "strength per row")
+    spans, frame_offs, out_s = [], [0], []
+    for r, s in zip(rows, strengths):
+        xo, n, yo, b = r
+        if isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) or not 0.0 <= s <= DENOISE_MAX_STRENGTH:
+            raise ValueError(f"pcm_denoise: row {r}: the strength is a finite number in 0 ... {DENOISE_MAX_STRENGTH:g}")
+        if min(xo, n, yo, b) < 0 or xo + n > n_x or n > 1 << 30:
+            raise ValueError(f"pcm_denoise: row {r} does not fit the buffers ({n_x} samples of x)")
+        if b >= n_bias:
+            raise ValueError(f"pcm_denoise: row {r}: bias_row outside the {n_bias} rows of bias")
+        if n:
+            spans.append((yo, yo + n))
+        out_s.append(float(s))
+        frame_offs.append(frame_offs[-1] + -(-n // DENOISE_H) + 3)
+    if overlaps:
+        raise ValueError("pcm_denoise: out overlaps x (a hop reads the input under its neighbours: not in place)")
+    return rows, out_s, frame_offs, _spans("pcm_denoise", spans, out_n)
+
+
+def plan_denoise_bias(rows, n_x: int):
+    """vv_pcm_denoise_bias's rows {x_off, n, 0, 0}, or {x_off, n}, validated -> (4-entry rows, the sum of the full frames)."""
+    from .core.audio_processor import DENOISE_BIAS_MAX_N, DENOISE_H, DENOISE_N
+    rows = [r + [0] * (4 - len(r)) for r in _int_rows("pcm_denoise_bias", rows, (2, 4), "2 entries {x_off, n} or 4 {x_off, n, 0, 0}")]
+    frames = 0
+    for r in rows:
+        if min(r) < 0 or not DENOISE_N <= r[1] <= DENOISE_BIAS_MAX_N or r[0] + r[1] > n_x:
+            raise ValueError(f"pcm_denoise_bias: row {r}: a signal of {DENOISE_N} ... {DENOISE_BIAS_MAX_N} samples inside the {n_x} samples of x is "
+                             f"needed (one full frame)")
+        frames += (r[1] - DENOISE_N) // DENOISE_H + 1
+    return rows, frames
+
+
+def plan_finish_denoise(R: int, denoise=None):
+    """finish_output's ``denoise``: one strength for every request or a per-request list with None entries -> the list, or None when no
+    request has one (nothing new is then called)."""
+    from .core.audio_processor import check_denoise
+    if denoise is None:
+        return None
+    vals = [check_denoise(v) for v in _per_request("finish_output", denoise, R, "denoise entry per request")]
+    return None if all(v is None for v in vals) else vals
+
+
 def plan_flac(rows, n_x: int, sample_rate, lpc_order: int = 0):
     """vv_pcm_flac's rows (src_off, n, frame0, last) -> (lpc_order, rows, the sum of the frame bounds = n_y, frames)."""
     from .core.audio_processor import FLAC_BLOCK, FLAC_MAX_RATE, check_flac_lpc_order, flac_frame_bound
@@ -343,7 +392,8 @@ def plan_finish(R: int, loudness=None, limiter=None, pitch=None, tempo=None):
 
 # --------------------------------------------------------------------------- the launches
 class PcmStage:
-    """HipSynth's PCM stage: what the methods below need of it is lib, ctx, device, _lock, _check and _stream."""
+    """HipSynth's PCM stage: what the methods below need of it is lib, ctx, device, _lock, _check and _stream (and vocoder_bias, where
+    finish_output is asked to denoise against the model's own profile)."""
 
     def __init__(self):
         self._tables = {"fade": {"off": {}, "host": [], "dev": None, "size": 0}}      # the constant device tables; "fade" grows (_fade_tables)
@@ -589,6 +639,64 @@ class PcmStage:
                    self._wsola_window.data_ptr(), z.data_ptr(), z.numel(), _ptr(h), 0 if h is None else h.numel(), ws.data_ptr(), ws.numel() * 8)
         return (z, h, frame_offs) if taps else z
 
+    # ------------------------------------------------------------------ vocoder-bias denoiser (N19)
+    @property
+    def _denoise_tables(self):
+        """(window [1024], twiddles [2][512]: cos | -sin, contiguous) on the device."""
+        return self._table("denoise", "denoise_tables")
+
+    def pcm_denoise(self, x: torch.Tensor, rows, strengths, bias: torch.Tensor, out: Optional[torch.Tensor] = None, mags: bool = False):
+        """Spectral subtraction of a stationary profile on R requests in one call (vv_pcm_denoise), bit for bit
+        core.audio_processor.denoise_pcm.  x int16 flat on the device; rows = HOST rows (x_off, n, y_off, bias_row); strengths = one value
+        in 0 ... 16 or one per row; bias = float64 [n_bias][513] (or [513]) on the device.  out = None: a new buffer, or a flat int16 device
+        tensor that does not overlap x.  -> y, or with ``mags`` (y, mag, frame_offs): mag the float64 device tensor [frames][1024] of every
+        frame's magnitudes, request r's frames mag[frame_offs[r] : frame_offs[r + 1]].  The rows are validated here; the call never
+        synchronises."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        assert bias.is_cuda and bias.dtype == torch.float64 and bias.is_contiguous() and bias.numel() % 513 == 0 and bias.numel() > 0
+        n_x, n_bias = x.numel(), bias.numel() // 513
+        shared = isinstance(out, torch.Tensor) and out.data_ptr() < x.data_ptr() + 2 * n_x and x.data_ptr() < out.data_ptr() + 2 * out.numel()
+        rows, strengths, frame_offs, n_y = plan_denoise(rows, strengths, n_x, n_bias, _out_arg(out)[0], shared)
+        from .core.audio_processor import DENOISE_N
+        y, R = self._out(out, n_y), len(rows)
+        (rows_d, rows_h), (s_d, s_h) = self._upload(rows), self._upload(strengths, torch.float64)
+        window, tw = self._denoise_tables
+        mag = torch.empty((frame_offs[-1], DENOISE_N), dtype=torch.float64, device=self.device) if mags else None
+        ws = self._ws(self.lib.vv_pcm_denoise_ws_bytes(R))
+        self._call(self.lib.vv_pcm_denoise, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, s_d.data_ptr(), s_h.data_ptr(), bias.data_ptr(),
+                   n_bias, window.data_ptr(), tw.data_ptr(), y.data_ptr(), y.numel(), _ptr(mag), 0 if mag is None else mag.numel(), ws.data_ptr(),
+                   ws.numel() * 8)
+        return (y, mag, frame_offs) if mags else y
+
+    def pcm_denoise_bias(self, x: torch.Tensor, rows) -> torch.Tensor:
+        """The bias profiles of R signals in one call (vv_pcm_denoise_bias), bit for bit core.audio_processor.denoise_bias: x int16 flat on
+        the device, rows = HOST rows (x_off, n) -> float64 [R][513] on the device.  The rows are validated here; the call never synchronises."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        rows, frames = plan_denoise_bias(rows, x.numel())
+        (rows_d, rows_h), R = self._upload(rows), len(rows)
+        window, tw = self._denoise_tables
+        out = torch.empty((R, 513), dtype=torch.float64, device=self.device)
+        ws = self._ws(self.lib.vv_pcm_denoise_bias_ws_bytes(frames, R))
+        self._call(self.lib.vv_pcm_denoise_bias, x.data_ptr(), x.numel(), rows_d.data_ptr(), rows_h.data_ptr(), R, window.data_ptr(), tw.data_ptr(),
+                   out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel() * 8)
+        return out
+
+    def _denoise(self, buf: torch.Tensor, offs, lens, denoise, bias):
+        """The denoise step of finish_output: the requests with a strength go through pcm_denoise into a copy of the joined buffer, the
+        others stay as they are.  bias = None: the model's (vocoder_bias), else 513 values or a float64 device tensor."""
+        import numpy as np
+        rows = [[offs[i], lens[i], offs[i], 0] for i, s in enumerate(denoise) if s is not None and lens[i] > 0]
+        if not rows:
+            return buf
+        if bias is None:
+            bias = self.vocoder_bias()
+        elif not isinstance(bias, torch.Tensor):
+            from .core.audio_processor import check_denoise_bias
+            bias = torch.from_numpy(np.ascontiguousarray(check_denoise_bias(bias))).to(self.device)
+        new = buf.clone()
+        self.pcm_denoise(buf, rows, [s for i, s in enumerate(denoise) if s is not None and lens[i] > 0], bias, out=new)
+        return new
+
     # ------------------------------------------------------------------ FLAC output (N15, N16)
     def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int, lpc_order: int = 0):
         """FLAC frames of R final signals in one call (vv_pcm_flac), byte for byte core.audio_processor.flac_encode_frames.
@@ -717,8 +825,8 @@ class PcmStage:
 
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
                       encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0,
-                      formants=None):
-        """The whole output stage of R requests on the caller's stream: join (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
+                      formants=None, denoise=None, denoise_bias=None):
+        """The whole output stage of R requests on the caller's stream: join (-> denoiser) (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
         (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
         spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
         new is called): core.audio_processor.prosody_plan turns them into a WSOLA stretch and a rate conversion on the joined signal, and
@@ -733,11 +841,17 @@ class PcmStage:
         formants (N18) = "shift" | "keep" for every request, or a per-request list; None = "shift": a request with "keep" and a pitch
         ratio other than 1 has the spectral envelope of its joined signal put back by pcm_formant, directly behind the rate conversion
         that makes the pitch; a request with tempo alone or without prosody runs nothing new.
+        denoise (N19) = one strength (0 < s <= 16) for every request, or a per-request list with None entries; None or all None = nothing
+        new is called.  A request with a strength goes through pcm_denoise directly behind the join and before pitch and tempo, into a new
+        buffer, against denoise_bias: 513 values or a float64 device tensor, None = the model's own (vocoder_bias).
         -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
         from .core.audio_processor import check_flac_lpc_order, resample_len
         if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
             raise ValueError("finish_output: flac_lpc_order belongs to the encoding 'flac'")
         buf, offs, lens = self.join_chunks(pcm, plans, cross_fade_duration, sample_rate)
+        denoise = plan_finish_denoise(len(lens), denoise)
+        if denoise is not None:
+            buf = self._denoise(buf, offs, lens, denoise, denoise_bias)
         pitch, tempo, groups = plan_finish(len(lens), loudness, limiter, pitch, tempo)
         if formants is not None:
             from .core.audio_processor import check_formants

@@ -230,6 +230,12 @@ EXPORTS = {
     "vv_pcm_formant_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
     "vv_pcm_formant": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_pcm_denoise_ws_bytes": (C.c_uint64, [C.c_int]),
+    "vv_pcm_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vv_pcm_denoise_bias_ws_bytes": (C.c_uint64, [C.c_int64, C.c_int]),
+    "vv_pcm_denoise_bias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vv_set_vocos": (C.c_int, [C.c_void_p, C.POINTER(vv_vocos_cfg)]),
     "vv_vocos_im2col": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_istft_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -348,6 +354,7 @@ class HipSynth(PcmStage):
         self._check(self.lib.vv_finalize_weights(self.ctx))
         cq, sq, ck, sk = pack.rope_tables(spec)
         self.rope = tuple(t.to(self.device) for t in (cq, sq, ck, sk))
+        self._vocoder_bias = None        # N19: the decoder's bias profile, float64 [1][513] on the device (vocoder_bias)
         # the tables this engine hands to the transformer stage are the standard ones of spec.rope_theta: the bf16 model may compute the
         # angles in the QKV epilogue instead of reading them (vv_set_rope_theta; the fp32 model reads the tables either way)
         self.grid_generation = 0         # bumped by whatever a captured Euler-step graph has baked in (time grid, rope mode, options)
@@ -546,6 +553,26 @@ class HipSynth(PcmStage):
             self._check(self.lib.vv_decode(self.ctx, B, N, x.data_ptr(), pre["ref_signal_len"].data_ptr(), pre["seq_len"].data_ptr(),
                                            t_gen_max, pcm.data_ptr(), pcm.shape[1], pcm_len.data_ptr(), _ptr(wave), self._stream()))
         return (pcm, pcm_len, wave) if want_wave else (pcm, pcm_len)
+
+    VOCODER_BIAS_FRAMES = 88         # generated frames of the empty mel whose decoded PCM gives the bias (the public denoisers use 88 too)
+
+    def vocoder_bias_pcm(self) -> torch.Tensor:
+        """The decoder's answer to an empty mel: VOCODER_BIAS_FRAMES zero frames, no reference part -> int16 [samples] on the device."""
+        T = self.VOCODER_BIAS_FRAMES
+        x = torch.zeros((1, T, self.spec.n_mel), dtype=torch.float32, device=self.device)
+        pre = {"ref_signal_len": torch.zeros((1,), dtype=torch.int32, device=self.device),
+               "seq_len": torch.full((1,), T, dtype=torch.int32, device=self.device)}
+        pcm, pcm_len = self.decode(x, pre, T)
+        return pcm[0, : int(pcm_len[0])].contiguous()
+
+    def vocoder_bias(self) -> torch.Tensor:
+        """The bias profile of this engine's decoder, HiFi-GAN or Vocos: pcm_denoise_bias of vocoder_bias_pcm(), float64
+        [1][513] on the device.  Computed once per engine: weights and decoder are bound at construction; an option that changes what the
+        decoder computes (set_option) drops it."""
+        if self._vocoder_bias is None:
+            pcm = self.vocoder_bias_pcm()
+            self._vocoder_bias = self.pcm_denoise_bias(pcm, [[0, pcm.numel()]])
+        return self._vocoder_bias
 
     def decode_bucketed(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], gen_frames, pad_frac: float = 0.10, min_units: int = 4):
         """The vocoder works on padded [B][C][T_max] planes (the acoustic stages pack ragged rows, the conv stack does not),
@@ -799,6 +826,7 @@ class HipSynth(PcmStage):
         with self._lock:
             self._check(self.lib.vv_set_option(self.ctx, name.encode(), int(value)))
             self.grid_generation += 1
+            self._vocoder_bias = None        # N19: an option may change what the decoder computes
 
     # ------------------------------------------------------------------ profiling
     def prof_enable(self, on: bool):
