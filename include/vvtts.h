@@ -450,7 +450,8 @@ VV_API int vv_mrf_resblock(vv_ctx* ctx, const vv_mrf_args* args, void* stream);
 
 /* N6 single-kernel entries (unit parity).  vv_vocos_im2col: the embed conv's operand, out [B * T_max][ld_out] f32 (16-byte aligned,
  * ld_out >= embed_k * n_mel, % 4): out[b * T_max + t][j * n_mel + m] = x[b][ref_len[b] + t + j - embed_k / 2][m] inside the item's
- * generated frames [0, min(min(seq_len[b], N) - ref_len[b], T_max)), 0 elsewhere and in the columns past embed_k * n_mel.
+ * generated frames [0, min(min(seq_len[b], N) - ref_len[b], T_max)), 0 elsewhere and in the columns past embed_k * n_mel; ref_len[b] is
+ * clamped to [0, max(min(seq_len[b], N), 0)] first, so no device length addresses a row outside the item.
  * vv_istft_head (finalized Vocos context): head [B][T_max][ld_head] f32 (the head GEMM's output, ld_head >= n_fft + 2), n_frames[B]
  * valid frames per item (device) -> pcm [B][ld_pcm] int16, pcm_len[B] = hop * max(T_b - 1, 0), optional wave_f32 [B][T_max * hop];
  * ld_pcm >= T_max * hop.  Reads only each item's valid frames; uses the context arena. */
@@ -475,6 +476,9 @@ VV_API int vv_dwconv(vv_ctx* ctx, const float* in, float* out, const float* w, c
                      int N, int C, int KW, void* stream);
 VV_API int vv_grn(vv_ctx* ctx, int dtype, void* x, float* sumsq, const float* gamma, const float* beta, const int32_t* seq_len, int B,
                   int n_seq, int N, int C, void* stream);
+/* K13: pcm [B][ld_pcm] int16 = trunc(clamp(32767 * tanh(conv_k7(lrelu(in)) + bias))), in [B][C][T] f32 read as zero from len_in[b]
+ * (optional, clamped to [0, T]) on, w [C][7]; optional wave_f32 [B][T].  Refused with -22 (nothing launched): KW != 7, C outside
+ * [1, 64], pre_slope outside (0, 1], B < 1, T < 1, ld_pcm < T, in / w / pcm NULL, a row of 2 GiB or more. */
 VV_API int vv_conv_post(vv_ctx* ctx, const float* in, const float* w, float bias, int16_t* pcm, int ld_pcm, float* wave_f32,
                  int B, int C, int T, int KW, float pre_slope, const int32_t* len_in, void* stream);
 VV_API int vv_mel(vv_ctx* ctx, const int16_t* audio, int ld_audio, const int32_t* audio_len, float* mel, int B, int F_max,
@@ -525,7 +529,61 @@ VV_API int vv_apg_coef(vv_ctx* ctx, const vv_apg_coef_args* args, void* stream);
  * must not be an output of the launch).  g and g_item are not read.  apg NULL: the call IS vv_ode_stage_guided. */
 typedef struct vv_apg_stage_args { const float* coef; const float* x_e; int32_t x_e_packed; float t_e; } vv_apg_stage_args;
 VV_API int vv_ode_stage_apg(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, const vv_apg_stage_args* apg, void* stream);
+/* K9: x[r] += dt * (p_c + (p_c - p_u) * cfg) over n_mel columns, p_c = pred row r, p_u = pred row BN + r (ld ldp, fp32).  Refused with
+ * -22 (nothing launched): n_mel or ldp not a multiple of 4, BN < 1, n_mel < 4, ldp < n_mel, x or pred NULL or not 16-byte aligned.
+ * vv_cfg_euler_rows: the same update on packed rows -- x row row_src[r] (device [BN] int32, the caller keeps it inside x) takes pred rows r
+ * and BN + r; row_src NULL is vv_cfg_euler. */
 VV_API int vv_cfg_euler(vv_ctx* ctx, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* stream);
+VV_API int vv_cfg_euler_rows(vv_ctx* ctx, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, const int32_t* row_src,
+                             void* stream);
+/* Single-kernel entries (unit parity) of the kernels between the transformer's prediction and the PCM.  Each is the launcher a stage
+ * calls; a violated precondition is refused with -22 before anything is launched, and every array must be 4-byte aligned.
+ * vv_pack_cat (K2): out [2 BN][ldo] of dtype (VV_DTYPE_F32 / VV_DTYPE_BF16, round to nearest even) = [x | cat | 0] for rows [0, BN) and
+ *   [x | cat_drop | 0] for rows [BN, 2 BN): row r of either half reads row row_src[r] (or r when NULL) of x [..][n_mel], cat and cat_drop
+ *   [..][cond_dim]; columns [n_mel + cond_dim, ldo) are zeros.  only_x: only the n_mel state columns are written.  n_mel >= 4, n_mel,
+ *   cond_dim, ldo multiples of 4, ldo >= n_mel + cond_dim, BN >= 1; x, cat, cat_drop 16-byte aligned, out 16-byte (f32) / 8-byte (bf16).
+ * vv_pack_cat_guided (N8): rows [row0, row0 + n_rows) of the same buffer for a guided subset: row r < Rc reads cat row row_src[r], row
+ *   Rc + u reads cat_drop row u_src[u]; the state columns come from x row row_src[r] / u_src[u], or with x_packed (x = the packed stage
+ *   state [Rc][n_mel]) from x row r / u_crow[u].  Rc >= 1, row0 >= 0, n_rows >= 1, the three tables required; otherwise as vv_pack_cat.
+ * vv_row_tables: the packed-row tables from device lengths clamped to [0, N] and to the Rc rows (host count) that exist:
+ *   row_start[2 B] (row_start[B + b] = Rc + row_start[b]), kv_len[2 B], row_src[Rc] = b * N + t, row_pos[2 Rc] = t.  Rows no item owns
+ *   (device lengths summing to fewer than Rc) map to the last item's padding rows min(len + i, N - 1).  B, N, Rc >= 1.
+ * vv_guided_tables: the same with the unconditional half compacted to the items with guided[b] != 0 (HOST [B] bytes), Ru rows:
+ *   row_start[B + j] = Rc + u0, rs_rel[j] = u0, kv_len[B + j] for the j-th guided item, row_pos[Rc + Ru], u_src[Ru], u_crow[Ru],
+ *   u_row[Rc] (Rc + u, or -1 for a row without an unconditional one).  1 <= B <= 1024, N, Rc >= 1, 0 <= Ru <= Rc.
+ * vv_ref_len: ref_len[b] = audio_len[b] / hop + 1.  B, hop >= 1.
+ * vv_decode_len: lens[l][b] = tg_b * mult[l] (l < n_levels, mult device [n_levels]), tg_b = min(sl - min(max(ref_len[b], 0), sl), T_max),
+ *   sl = max(min(seq_len[b], N), 0): the frames vv_mel_slice hands on.  vv_vocos_lens: lens[b] = the same tg_b.
+ * vv_mel_slice (K10): out [B][n_mel][T] f32, out[b][c][t] = x[b][rl + t][c] for t < tg_b (rl = min(max(ref_len[b], 0), sl)), 0 behind;
+ *   x [B][N][n_mel].  B, N, n_mel, T >= 1.
+ * vv_vocos_im2col_ex: vv_vocos_im2col with n_mel and the (odd) tap count k as arguments; needs no Vocos context.
+ * vv_vocos_spectrum: head [R][ld_head] f32 = (log-magnitudes 0..n_fft/2 | phases 0..n_fft/2) -> out [R][n_fft]: column k <= n_fft/2 =
+ *   m_k cos p_k, column n_fft/2 + k (1 <= k < n_fft/2) = m_k sin p_k, m_k = min(exp(o_k), 100).  R >= 1, n_fft even >= 4,
+ *   ld_head >= n_fft + 2.
+ * vv_vocos_ola: frames [B][T_max][ld_f] f32 (windowed, ld_f >= n_fft), lens[B] valid frames (clamped to [0, T_max]), window [n_fft] ->
+ *   sample j of item b = the overlap-add at position j + n_fft/2 over the sum of the window squares there, for j < pcm_len[b] =
+ *   hop * max(T_b - 1, 0), zeros behind up to T_max * hop; pcm int16 = trunc(clamp(y * 32767)), optional wave f32 and pcm_len.
+ *   n_fft even, n_fft % hop == 0, ld_pcm (and ld_wave with wave) >= T_max * hop < 2^31.  Needs no Vocos context. */
+VV_API int vv_pack_cat(vv_ctx* ctx, int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int BN, int n_mel,
+                       int cond_dim, int only_x, const int32_t* row_src, void* stream);
+VV_API int vv_pack_cat_guided(vv_ctx* ctx, int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int Rc,
+                              int row0, int n_rows, int n_mel, int cond_dim, int only_x, int x_packed, const int32_t* row_src,
+                              const int32_t* u_src, const int32_t* u_crow, void* stream);
+VV_API int vv_row_tables(vv_ctx* ctx, const int32_t* seq_len, int B, int N, int Rc, int32_t* row_start, int32_t* row_src, int32_t* row_pos,
+                         int32_t* kv_len, void* stream);
+VV_API int vv_guided_tables(vv_ctx* ctx, const int32_t* seq_len, const uint8_t* guided, int B, int N, int Rc, int Ru, int32_t* row_start,
+                            int32_t* rs_rel, int32_t* kv_len, int32_t* row_pos, int32_t* u_src, int32_t* u_crow, int32_t* u_row, void* stream);
+VV_API int vv_ref_len(vv_ctx* ctx, const int32_t* audio_len, int32_t* ref_len, int B, int hop, void* stream);
+VV_API int vv_decode_len(vv_ctx* ctx, const int32_t* seq_len, const int32_t* ref_len, int32_t* lens, int B, int n_levels, const int32_t* mult,
+                         int N, int T_max, void* stream);
+VV_API int vv_vocos_lens(vv_ctx* ctx, const int32_t* seq_len, const int32_t* ref_len, int32_t* lens, int B, int N, int T_max, void* stream);
+VV_API int vv_mel_slice(vv_ctx* ctx, const float* x, int B, int N, int n_mel, const int32_t* ref_len, const int32_t* seq_len, float* out, int T,
+                        void* stream);
+VV_API int vv_vocos_im2col_ex(vv_ctx* ctx, const float* x, int B, int N, int n_mel, const int32_t* ref_signal_len, const int32_t* seq_len,
+                              int T_max, int k, float* out, int ld_out, void* stream);
+VV_API int vv_vocos_spectrum(vv_ctx* ctx, const float* head, int ld_head, int R, int n_fft, float* out, void* stream);
+VV_API int vv_vocos_ola(vv_ctx* ctx, const float* frames, int ld_f, int B, int T_max, const int32_t* lens, const float* window, int n_fft, int hop,
+                        int16_t* pcm, int ld_pcm, int32_t* pcm_len, float* wave, int ld_wave, void* stream);
 
 /* ---- reference-clip ingest on the device (a8 + SURVEY 8(f) N3).  Together they replace the arithmetic of
  * AudioProcessor.load_audio after RIFF parsing (reference core/audio_processor.py:15-44): pydub's set_channels(1) =

@@ -1731,7 +1731,7 @@ static int decode_impl(vv_ctx* c, int B, int N, const float* x, const int32_t* r
     if (int r = plan_ws(c, ext_ws, (size_t)ext_bytes, [&](Arena& a) { w = hifi_bufs(a, g, plan, B); })) return r;
     auto [v0, buf, lens] = w;
 
-    KCHK(c, vvk_decode_len(seq_len, ref_len, lens, B, nu + 1, c->d_mult, st, &m__));
+    KCHK(c, vvk_decode_len(seq_len, ref_len, lens, B, nu + 1, c->d_mult, N, Ts[0], st, &m__));
     HIPCHK(c, hipMemcpyAsync(pcm_len, lens + (size_t)nu * B, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
     {
         Prof p(c, VV_PROF_ELEMWISE, 0, 8.0 * B * M * Ts[0], st);
@@ -2020,5 +2020,81 @@ int vv_grn(vv_ctx* c, int dtype, void* x, float* sumsq, const float* gamma, cons
 int vv_cfg_euler(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, void* st) {
     SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, nullptr, (hipStream_t)st, &m__));
 }
+// single-kernel entries (unit parity) of the sampler, pack and waveform-head kernels: the launchers hold the checks the stages also pass;
+// what only a caller from outside can get wrong (an array that is not 4-byte aligned, a dtype code) is checked here
+#define ALIGN4(ctx, name, ptrs)                                                                                   \
+    do {                                                                                                              \
+        if (!(ctx)) return -22;                                                                                       \
+        if ((ptrs) % 4) return (ctx)->fail(-22, name ": every array must be 4-byte aligned");                    \
+    } while (0)
+int vv_cfg_euler_rows(vv_ctx* c, float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, const int32_t* row_src, void* st) {
+    ALIGN4(c, "vv_cfg_euler_rows", (uintptr_t)row_src);
+    SINGLE(c, vvk_cfg_euler(x, pred, ldp, BN, n_mel, cfg, dt, row_src, (hipStream_t)st, &m__));
+}
+int vv_pack_cat(vv_ctx* c, int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int BN, int n_mel, int cond_dim,
+                int only_x, const int32_t* row_src, void* st) {
+    ALIGN4(c, "vv_pack_cat", (uintptr_t)row_src);
+    if (dtype != VV_DTYPE_F32 && dtype != VV_DTYPE_BF16) return c->fail(-22, "vv_pack_cat: dtype must be VV_DTYPE_F32 or VV_DTYPE_BF16");
+    SINGLE(c, vvk_pack_cat(dtype, x, cat, cat_drop, out, ldo, BN, n_mel, cond_dim, only_x, row_src, (hipStream_t)st, &m__));
+}
+int vv_pack_cat_guided(vv_ctx* c, int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int Rc, int row0,
+                       int n_rows, int n_mel, int cond_dim, int only_x, int x_packed, const int32_t* row_src, const int32_t* u_src,
+                       const int32_t* u_crow, void* st) {
+    ALIGN4(c, "vv_pack_cat_guided", (uintptr_t)row_src | (uintptr_t)u_src | (uintptr_t)u_crow);
+    if (dtype != VV_DTYPE_F32 && dtype != VV_DTYPE_BF16) return c->fail(-22, "vv_pack_cat_guided: dtype must be VV_DTYPE_F32 or VV_DTYPE_BF16");
+    SINGLE(c, vvk_pack_cat_guided(dtype, x, cat, cat_drop, out, ldo, Rc, row0, n_rows, n_mel, cond_dim, only_x, x_packed, row_src, u_src, u_crow,
+                                  (hipStream_t)st, &m__));
+}
+int vv_row_tables(vv_ctx* c, const int32_t* seq_len, int B, int N, int Rc, int32_t* row_start, int32_t* row_src, int32_t* row_pos, int32_t* kv_len,
+                  void* st) {
+    ALIGN4(c, "vv_row_tables", (uintptr_t)seq_len | (uintptr_t)row_start | (uintptr_t)row_src | (uintptr_t)row_pos | (uintptr_t)kv_len);
+    if (!seq_len || !row_start || !row_src || !row_pos || !kv_len) return c->fail(-22, "vv_row_tables: seq_len and the four tables are required");
+    if ((long long)B * N >= (1ll << 31)) return c->fail(-22, "vv_row_tables: B * N must stay below 2^31 (row_src holds b * N + t)");
+    SINGLE(c, vvk_row_tables(seq_len, B, N, Rc, row_start, row_src, row_pos, kv_len, (hipStream_t)st, &m__));
+}
+int vv_guided_tables(vv_ctx* c, const int32_t* seq_len, const uint8_t* guided, int B, int N, int Rc, int Ru, int32_t* row_start, int32_t* rs_rel,
+                     int32_t* kv_len, int32_t* row_pos, int32_t* u_src, int32_t* u_crow, int32_t* u_row, void* st) {
+    ALIGN4(c, "vv_guided_tables", (uintptr_t)seq_len | (uintptr_t)row_start | (uintptr_t)rs_rel | (uintptr_t)kv_len | (uintptr_t)row_pos |
+                                          (uintptr_t)u_src | (uintptr_t)u_crow | (uintptr_t)u_row);
+    if (!seq_len || !row_start || !rs_rel || !kv_len || !row_pos || !u_src || !u_crow || !u_row)
+        return c->fail(-22, "vv_guided_tables: seq_len and the seven tables are required");
+    if ((long long)B * N >= (1ll << 31)) return c->fail(-22, "vv_guided_tables: B * N must stay below 2^31 (u_src holds b * N + t)");
+    SINGLE(c, vvk_guided_tables(seq_len, guided, B, N, Rc, Ru, row_start, rs_rel, kv_len, row_pos, u_src, u_crow, u_row, (hipStream_t)st, &m__));
+}
+int vv_ref_len(vv_ctx* c, const int32_t* audio_len, int32_t* ref_len, int B, int hop, void* st) {
+    ALIGN4(c, "vv_ref_len", (uintptr_t)audio_len | (uintptr_t)ref_len);
+    SINGLE(c, vvk_ref_len(audio_len, ref_len, B, hop, (hipStream_t)st, &m__));
+}
+int vv_decode_len(vv_ctx* c, const int32_t* seq_len, const int32_t* ref_len, int32_t* lens, int B, int n_levels, const int32_t* mult, int N, int T_max,
+                  void* st) {
+    ALIGN4(c, "vv_decode_len", (uintptr_t)seq_len | (uintptr_t)ref_len | (uintptr_t)lens | (uintptr_t)mult);
+    SINGLE(c, vvk_decode_len(seq_len, ref_len, lens, B, n_levels, mult, N, T_max, (hipStream_t)st, &m__));
+}
+int vv_vocos_lens(vv_ctx* c, const int32_t* seq_len, const int32_t* ref_len, int32_t* lens, int B, int N, int T_max, void* st) {
+    ALIGN4(c, "vv_vocos_lens", (uintptr_t)seq_len | (uintptr_t)ref_len | (uintptr_t)lens);
+    SINGLE(c, vvk_vocos_lens(seq_len, ref_len, lens, B, N, T_max, (hipStream_t)st, &m__));
+}
+int vv_mel_slice(vv_ctx* c, const float* x, int B, int N, int n_mel, const int32_t* ref_len, const int32_t* seq_len, float* out, int T, void* st) {
+    ALIGN4(c, "vv_mel_slice", (uintptr_t)ref_len | (uintptr_t)seq_len | (uintptr_t)x | (uintptr_t)out);
+    SINGLE(c, vvk_mel_slice(x, B, N, n_mel, ref_len, seq_len, out, T, (hipStream_t)st, &m__));
+}
+int vv_vocos_im2col_ex(vv_ctx* c, const float* x, int B, int N, int n_mel, const int32_t* ref_len, const int32_t* seq_len, int T_max, int k, float* out,
+                       int ld_out, void* st) {
+    ALIGN4(c, "vv_vocos_im2col_ex", (uintptr_t)ref_len | (uintptr_t)seq_len);
+    SINGLE(c, vvk_vocos_im2col(x, B, N, n_mel, ref_len, seq_len, T_max, k, out, ld_out, (hipStream_t)st, &m__));
+}
+int vv_vocos_spectrum(vv_ctx* c, const float* head, int ld_head, int R, int n_fft, float* out, void* st) {
+    if (!c) return -22;
+    if (((uintptr_t)head | (uintptr_t)out) % 4) return c->fail(-22, "vv_vocos_spectrum: head and out must be 4-byte aligned");
+    SINGLE(c, vvk_vocos_spectrum(head, ld_head, R, n_fft, out, (hipStream_t)st, &m__));
+}
+int vv_vocos_ola(vv_ctx* c, const float* frames, int ld_f, int B, int T_max, const int32_t* lens, const float* window, int n_fft, int hop,
+                 int16_t* pcm, int ld_pcm, int32_t* pcm_len, float* wave, int ld_wave, void* st) {
+    ALIGN4(c, "vv_vocos_ola", (uintptr_t)lens | (uintptr_t)pcm_len | (uintptr_t)frames | (uintptr_t)window | (uintptr_t)wave);
+    if ((uintptr_t)pcm % 2) return c->fail(-22, "vv_vocos_ola: pcm must be 2-byte aligned");
+    if (n_fft < 2 || n_fft % 2) return c->fail(-22, "vv_vocos_ola: n_fft must be even and at least 2");
+    SINGLE(c, vvk_vocos_ola(frames, ld_f, B, T_max, lens, window, n_fft, hop, pcm, ld_pcm, pcm_len, wave, ld_wave, (hipStream_t)st, &m__));
+}
+#undef ALIGN4
 
 }  // extern "C"

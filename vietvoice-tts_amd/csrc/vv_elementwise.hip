@@ -481,11 +481,14 @@ __global__ void ref_len_kernel(const int* __restrict__ audio_len, int* __restric
     if (b < B) ref_len[b] = audio_len[b] / hop + 1;      // reference core/tts_engine.py:55
 }
 __global__ void decode_len_kernel(const int* __restrict__ seq_len, const int* __restrict__ ref_len, int* __restrict__ lens,
-                                  int B, int n_levels, const int* __restrict__ mult) {
-    // lens[level][b] = max(seq_len - ref_len, 0) * mult[level]
+                                  int B, int n_levels, const int* __restrict__ mult, int N, int T_max) {
+    // lens[level][b] = tg * mult[level], tg = the frames mel_slice_kernel hands to the first level: the slice [ref_len, seq_len) with
+    // both ends clamped into the item's N rows, and at most the T_max columns of the level-0 plane.  The last level is pcm_len: a
+    // device length that disagrees with the host's (stale tensor) never describes more samples than a pcm row holds.
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= B) return;
-    const int tg = max(seq_len[b] - ref_len[b], 0);
+    const int sl = max(min(seq_len[b], N), 0);
+    const int tg = min(sl - min(max(ref_len[b], 0), sl), T_max);
     for (int l = 0; l < n_levels; ++l) lens[l * B + b] = tg * mult[l];
 }
 
@@ -696,6 +699,12 @@ int vvk_ln_mod(const vv_ln_args* a, hipStream_t st, const char** err) {
 int vvk_pack_cat(int dtype, const float* x, const float* cat, const float* cat_drop, void* out, int ldo, int BN, int n_mel,
                  int cond_dim, int only_x, const int* row_src, hipStream_t st, const char** err) {
     if (n_mel % 4 || cond_dim % 4 || ldo % 4 || ldo < n_mel + cond_dim) { *err = "pack_cat: bad widths"; return -22; }
+    if (BN < 1 || n_mel < 4 || cond_dim < 0) { *err = "pack_cat: BN >= 1, n_mel >= 4, cond_dim >= 0"; return -22; }
+    if (!x || !out || (!only_x && cond_dim > 0 && (!cat || !cat_drop))) { *err = "pack_cat: x, out and (unless only_x) cat and cat_drop are required"; return -22; }
+    // both kernels move 4 elements at a time: float4 loads, a float4 or 4 x bf16 store
+    if (((uintptr_t)x | (uintptr_t)cat | (uintptr_t)cat_drop) % 16 || (uintptr_t)out % (dtype == VV_BF16 ? 8 : 16)) {
+        *err = "pack_cat: x, cat and cat_drop must be 16-byte aligned, out 16-byte (f32) or 8-byte (bf16)"; return -22;
+    }
     const size_t total = (size_t)2 * BN * ((only_x ? n_mel : ldo) / 4);
     if (dtype == VV_BF16)
         pack_cat_kernel<bf16><<<grid_for(total), 256, 0, st>>>(x, cat, cat_drop, (bf16*)out, ldo, BN, n_mel, cond_dim, only_x, row_src);
@@ -708,6 +717,9 @@ int vvk_pack_cat(int dtype, const float* x, const float* cat, const float* cat_d
 int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float cfg, float dt, const int* row_src, hipStream_t st,
                   const char** err) {
     if (n_mel % 4 || ldp % 4) { *err = "cfg_euler: widths must be multiples of 4"; return -22; }
+    if (BN < 1 || n_mel < 4 || ldp < n_mel) { *err = "cfg_euler: BN >= 1, n_mel >= 4, ldp >= n_mel"; return -22; }
+    if (!x || !pred) { *err = "cfg_euler: x and pred are required"; return -22; }
+    if (((uintptr_t)x | (uintptr_t)pred) % 16) { *err = "cfg_euler: x and pred must be 16-byte aligned"; return -22; }
     cfg_euler_kernel<<<grid_for((size_t)BN * n_mel / 4), 256, 0, st>>>(x, pred, ldp, BN, n_mel, cfg, dt, row_src);
     VVK_CHECK_LAUNCH();
     return 0;
@@ -773,6 +785,11 @@ int vvk_pack_cat_guided(int dtype, const float* x, const float* cat, const float
                         hipStream_t st, const char** err) {
     if (n_mel % 4 || cond_dim % 4 || ldo % 4 || ldo < n_mel + cond_dim) { *err = "pack_cat_guided: bad widths"; return -22; }
     if (Rc < 1 || row0 < 0 || n_rows < 1 || !row_src || !u_src || !u_crow) { *err = "pack_cat_guided: rows and their three tables"; return -22; }
+    if (n_mel < 4 || cond_dim < 0) { *err = "pack_cat_guided: n_mel >= 4, cond_dim >= 0"; return -22; }
+    if (!x || !out || (!only_x && cond_dim > 0 && (!cat || !cat_drop))) { *err = "pack_cat_guided: x, out and (unless only_x) cat and cat_drop are required"; return -22; }
+    if (((uintptr_t)x | (uintptr_t)cat | (uintptr_t)cat_drop) % 16 || (uintptr_t)out % (dtype == VV_BF16 ? 8 : 16)) {
+        *err = "pack_cat_guided: x, cat and cat_drop must be 16-byte aligned, out 16-byte (f32) or 8-byte (bf16)"; return -22;
+    }
     const size_t total = (size_t)n_rows * ((only_x ? n_mel : ldo) / 4);
     if (dtype == VV_BF16)
         pack_cat_guided_kernel<bf16><<<grid_for(total), 256, 0, st>>>(x, cat, cat_drop, (bf16*)out, ldo, Rc, row0, n_rows, n_mel, cond_dim, only_x,
@@ -842,12 +859,17 @@ int vvk_build_cat(const float* mel, int F_max, const int* ref_len, const float* 
 }
 
 int vvk_ref_len(const int* audio_len, int* ref_len, int B, int hop, hipStream_t st, const char** err) {
+    if (B < 1 || hop < 1 || !audio_len || !ref_len) { *err = "ref_len: B >= 1, hop >= 1, audio_len and ref_len required"; return -22; }
     ref_len_kernel<<<(B + 63) / 64, 64, 0, st>>>(audio_len, ref_len, B, hop);
     VVK_CHECK_LAUNCH();
     return 0;
 }
-int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, hipStream_t st, const char** err) {
-    decode_len_kernel<<<(B + 63) / 64, 64, 0, st>>>(seq_len, ref_len, lens, B, n_levels, mult);
+int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, int N, int T_max, hipStream_t st,
+                   const char** err) {
+    if (B < 1 || n_levels < 1 || N < 1 || T_max < 1 || !seq_len || !ref_len || !lens || !mult) {
+        *err = "decode_len: B, n_levels, N, T_max >= 1, seq_len, ref_len, lens and mult required"; return -22;
+    }
+    decode_len_kernel<<<(B + 63) / 64, 64, 0, st>>>(seq_len, ref_len, lens, B, n_levels, mult, N, T_max);
     VVK_CHECK_LAUNCH();
     return 0;
 }

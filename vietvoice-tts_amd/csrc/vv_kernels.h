@@ -51,7 +51,8 @@ int vvk_grn(int dtype, void* x, float* sumsq, const float* gamma, const float* b
 int vvk_build_cat(const float* mel, int F_max, const int* ref_len, const float* text, float* cat, float* cat_drop, int B, int N,
                   int n_mel, int Dt, hipStream_t st, const char** err, const uint8_t* keep = nullptr, int ld_keep = 0);
 int vvk_ref_len(const int* audio_len, int* ref_len, int B, int hop, hipStream_t st, const char** err);
-int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, hipStream_t st,
+// N, T_max: the item's rows and the level-0 plane's columns -- the frame count is clamped to both, as mel_slice_kernel's slice is
+int vvk_decode_len(const int* seq_len, const int* ref_len, int* lens, int B, int n_levels, const int* mult, int N, int T_max, hipStream_t st,
                    const char** err);
 int vvk_row_tables(const int* seq_len, int B, int N, int Rc, int* row_start, int* row_src, int* row_pos, int* kv_len, hipStream_t st, const char** err);
 int vvk_resample_poly(const float* x, int n_in, const double* h, int n_taps, int up, int down, int skip, float* y, int n_out,

@@ -463,8 +463,11 @@ __global__ __launch_bounds__(256) void mel_slice_kernel(const float* __restrict_
     __shared__ float tile[32][33];
     const int b = blockIdx.z;
     const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
-    const int rl = ref_len[b];
-    const int tg = max(min(seq_len[b], N) - rl, 0);
+    // the slice is rows [rl, sl) of the item: both ends clamped into its N rows, so a negative or oversized device length
+    // gives a shorter or empty slice and never a row in front of x or behind it
+    const int sl = max(min(seq_len[b], N), 0);
+    const int rl = min(max(ref_len[b], 0), sl);
+    const int tg = sl - rl;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
     for (int i = ty; i < 32; i += 8) {
         const int t = t0 + i, c = c0 + tx;
@@ -569,6 +572,8 @@ int vvk_conv_post(const float* in, const float* w, float bias, int16_t* pcm, int
                   float pre_slope, const int* len_in, hipStream_t st, const char** err) {
     if (KW != 7 || C > 64 || C < 1) { *err = "conv_post: k=7 and C<=64 expected"; return -22; }
     if (!(pre_slope > 0.f && pre_slope <= 1.f)) { *err = "conv_post: pre_slope must be in (0, 1]"; return -22; }
+    if (B < 1 || T < 1 || ld_pcm < T) { *err = "conv_post: B >= 1, T >= 1 and ld_pcm >= T"; return -22; }
+    if (!in || !w || !pcm) { *err = "conv_post: in, w and pcm are required"; return -22; }
     dim3 grid((T + 4 * POST_WAVE_OUT - 1) / (4 * POST_WAVE_OUT), B);          // 4 waves x 248 samples per workgroup
     if ((size_t)T * 4 >= ((size_t)1 << 31)) { *err = "conv_post: rows of 2 GiB or more"; return -22; }
     const bool vec = (T & 3) == 0 && ((uintptr_t)in % 16) == 0;
@@ -586,6 +591,9 @@ int vvk_conv_post(const float* in, const float* w, float bias, int16_t* pcm, int
 int vvk_mel_slice(const float* x, int B, int N, int n_mel, const int* ref_len, const int* seq_len, float* out, int T,
                   hipStream_t st, const char** err) {
     if (T <= 0) { *err = "mel_slice: empty"; return -22; }
+    if (B < 1 || N < 1 || n_mel < 1) { *err = "mel_slice: B, N and n_mel must be at least 1"; return -22; }
+    if (!x || !ref_len || !seq_len || !out) { *err = "mel_slice: x, ref_len, seq_len and out are required"; return -22; }
+    if (B > 65535) { *err = "mel_slice: at most 65535 items (grid z)"; return -22; }
     dim3 grid((T + 31) / 32, (n_mel + 31) / 32, B);
     mel_slice_kernel<<<grid, 256, 0, st>>>(x, N, n_mel, ref_len, seq_len, out, T);
     hipError_t he = hipGetLastError();

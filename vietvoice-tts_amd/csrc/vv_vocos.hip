@@ -13,8 +13,13 @@ namespace {
 
 inline int grid_1d(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 32); }
 
+// The generated frames of item b are rows [gen_start, gen_start + gen_frames) of its N rows: both ends of the slice are clamped into
+// [0, min(seq_len, N)] (mel_slice_kernel's rule), so a negative or oversized device length never addresses a row outside the item.
+__device__ __forceinline__ int gen_start(const int* seq_len, const int* ref_len, int b, int N) {
+    return min(max(ref_len[b], 0), max(min(seq_len[b], N), 0));
+}
 __device__ __forceinline__ int gen_frames(const int* seq_len, const int* ref_len, int b, int N, int T_max) {
-    return min(max(min(seq_len[b], N) - ref_len[b], 0), T_max);
+    return min(max(min(seq_len[b], N), 0) - gen_start(seq_len, ref_len, b, N), T_max);
 }
 
 __global__ void vocos_lens_kernel(const int* __restrict__ seq_len, const int* __restrict__ ref_len, int* __restrict__ lens, int B, int N,
@@ -23,7 +28,7 @@ __global__ void vocos_lens_kernel(const int* __restrict__ seq_len, const int* __
     if (b < B) lens[b] = gen_frames(seq_len, ref_len, b, N, T_max);
 }
 
-// out[b * T_max + t][j * M + m] = x[b][ref_len[b] + t + j - k / 2][m] inside the item's generated frames [0, T_b), else 0;
+// out[b * T_max + t][j * M + m] = x[b][gen_start(b) + t + j - k / 2][m] inside the item's generated frames [0, T_b), else 0;
 // columns [k * M, ld_out) are zero (the GEMM's K padding).  Four columns per thread (M % 4 == 0: a float4 never straddles a tap).
 __global__ __launch_bounds__(256) void vocos_im2col_kernel(const float* __restrict__ x, int N, int M, const int* __restrict__ ref_len,
                                                            const int* __restrict__ seq_len, int B, int T_max, int k,
@@ -39,7 +44,7 @@ __global__ __launch_bounds__(256) void vocos_im2col_kernel(const float* __restri
             const int tap = col / M, m = col - tap * M;
             const int tt = t + tap - half;
             if (tt >= 0 && tt < gen_frames(seq_len, ref_len, b, N, T_max))
-                v = *(const float4*)(x + ((size_t)b * N + ref_len[b] + tt) * M + m);
+                v = *(const float4*)(x + ((size_t)b * N + gen_start(seq_len, ref_len, b, N) + tt) * M + m);
         }
         *(float4*)(out + row * ld_out + col) = v;
     }
