@@ -104,6 +104,22 @@ VV_API int vv_set_time_grid(vv_ctx* ctx, const float* sinus_host, const float* d
 VV_API int vv_set_ode_plan(vv_ctx* ctx, const float* sinus_host, const float* dt_host, int n_steps, int s, const double* a,
                            const double* b, void* stream);
 
+/* N20 multistep plan: an Adams-Bashforth method on vv_set_time_grid's tables.  sinus [n_steps][time_freq_dim] and dt
+ * [n_steps] as vv_set_time_grid takes them (ONE evaluation per step, at t_n); beta [n_steps][q] (host, row-major), j = 0 the newest
+ * slope: step n computes x += h_n * sum_j beta[n][j] f_{n-j}, f_n the combined velocity of the step (after guidance and the projected
+ * term), f_{n-1}, f_{n-2} kept from the steps before in q - 1 slope buffers per lane ([rows][n_mel] fp32, a ring; reported by the
+ * vv_transformer_*_ws_bytes queries).  A weight that reaches behind the call's first step must be 0 (model_spec.multistep_weights: the
+ * order at step n is min(q, n + 1)).  -22 for q outside [1, 3], a weight that is not finite, a row that does not sum to 1
+ * (|sum - 1| < 1e-6) or reaches behind step 0; the plan in force then stays as it was.  vv_set_time_grid and vv_set_ode_plan clear it.
+ * The kept slopes live for one call: under this plan every vv_transformer_steps* call starts at step0 = 0 (-22 otherwise). */
+VV_API int vv_set_ode_multistep(vv_ctx* ctx, const float* sinus_host, const float* dt_host, int n_steps, int q, const double* beta,
+                                void* stream);
+/* N20 step report: report (device, [n_steps][B][2] float64, caller-owned) receives per step n and item b {D2, F2} = {sum (f_n - f_{n-1})^2,
+ * sum f_n^2} over the item's rows and the n_mel columns, from every later vv_transformer_steps* call under a multistep plan whose batch
+ * is B items (-22 from that call when its B or the plan's n_steps differ); step 0 stores {0, F2}.  Two small launches per step and lane
+ * and one more slope buffer per lane.  report NULL: off (the default); setting a plan turns it off as well. */
+VV_API int vv_set_ode_report(vv_ctx* ctx, double* report, int n_steps, int B);
+
 /* ---- the three stages (device-resident, batched) ------------------------------------------ */
 /* replaces sessions['preprocess'].run, core/tts_engine.py:133-146.
  * audio [B][ld_audio] int16, audio_len[B], text_ids [B][ld_text] int32, text_len[B], seq_len[B]
@@ -529,6 +545,19 @@ VV_API int vv_apg_coef(vv_ctx* ctx, const vv_apg_coef_args* args, void* stream);
  * must not be an output of the launch).  g and g_item are not read.  apg NULL: the call IS vv_ode_stage_guided. */
 typedef struct vv_apg_stage_args { const float* coef; const float* x_e; int32_t x_e_packed; float t_e; } vv_apg_stage_args;
 VV_API int vv_ode_stage_apg(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, const vv_apg_stage_args* apg, void* stream);
+/* N20 single-kernel entry (unit parity): the sums of the step report.  Item b owns the packed rows [row_start[b], + len[b]) of f and
+ * f_prev ([Rc][n_mel] fp32, 16-byte aligned; row_start, len: device [B] int32, clamped into [0, Rc) and to VV_APG_TILE * n_tiles rows).
+ * partials [B][n_tiles][2] float64 (scratch: the entries of an item's tiles are written, the rest untouched), report [B][2] float64 =
+ * {sum (f - f_prev)^2, sum f^2}: differences, squares and sums in float64, a product and an add each (never fused), tiles of VV_APG_TILE
+ * frames from the item's frame 0, float4 q of a tile on thread q % 256, one fixed tree, the tiles added in ascending order -- an item's
+ * sums depend on its own rows alone.  f_prev NULL: D2 = 0.  {0, 0} for an item without rows. */
+typedef struct vv_ode_diff_args {
+    const float* f; const float* f_prev; int32_t Rc, n_mel;
+    int32_t B, n_tiles;
+    const int32_t* row_start; const int32_t* len;
+    double* partials; double* report;
+} vv_ode_diff_args;
+VV_API int vv_ode_diff_reduce(vv_ctx* ctx, const vv_ode_diff_args* args, void* stream);
 /* K9: x[r] += dt * (p_c + (p_c - p_u) * cfg) over n_mel columns, p_c = pred row r, p_u = pred row BN + r (ld ldp, fp32).  Refused with
  * -22 (nothing launched): n_mel or ldp not a multiple of 4, BN < 1, n_mel < 4, ldp < n_mel, x or pred NULL or not 16-byte aligned.
  * vv_cfg_euler_rows: the same update on packed rows -- x row row_src[r] (device [BN] int32, the caller keeps it inside x) takes pred rows r

@@ -199,7 +199,8 @@ class ModelSessionManager:
             else:
                 from ..runtime import HipSynth
                 self.engine = HipSynth(spec, weights, device=self.config.device, acoustic_dtype=self.config.acoustic_dtype,
-                                       nfe_step=self.config.nfe_step, ode_method=self.config.ode_method)
+                                       nfe_step=self.config.nfe_step, ode_method=self.config.ode_method,
+                                       ode_report=self.config.ode_report)
                 on_device = self._session_key if self.config.noise_source == "device" else None
                 made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval,
                                       noise_keys=on_device if k == "preprocess" else None, apg_eta=self.config.apg_eta,

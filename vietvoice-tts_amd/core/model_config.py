@@ -62,7 +62,12 @@ class ModelConfig:
     decode_graph_cache_entries: int = 8     # captured decode graphs kept per engine (least recently used beyond that)
     decode_graph_cache_bytes: int = 16 << 30   # HBM the cache may pin (shared workspace + per-graph I/O buffers)
     ode_method: str = "euler"               # flow-ODE solver: euler | midpoint | heun2 | heun3 | rk4 (model_spec.ODE_METHODS); nfe_step stays
-                                            # the number of grid points, the DiT runs stages x (nfe_step - 1) times
+                                            # the number of grid points, the DiT runs stages x (nfe_step - 1) times.  Or ab2 | ab3
+                                            # (model_spec.ODE_MULTISTEP): Adams-Bashforth on the slopes of the steps before,
+                                            # nfe_step - 1 evaluations as euler
+    ode_report: bool = False                # N20, needs ab2 | ab3: per step and item the sums (|f_n - f_{n-1}|^2, |f_n|^2) of the combined velocity,
+                                            # reduced on the device -- the local-error term of the Euler step (HipSynth.last_ode_report,
+                                            # TTSEngine.last_ode_report).  Off = nothing is launched or allocated for it
     cfg_strength: Optional[float] = None    # classifier-free guidance strength of every synthesis of this engine; None = the model's
     cfg_interval: Optional[Tuple[float, float]] = None   # guidance only at the evaluations with lo <= t <= hi (limited-interval guidance);
                                             # outside it the unconditional branch is not computed.  None = guidance everywhere
@@ -110,9 +115,12 @@ class ModelConfig:
             raise ValueError("NFE step must be between 1 and 100")
         if self.acoustic_dtype not in ("bf16", "fp32"):
             raise ValueError("acoustic_dtype must be 'bf16' or 'fp32'")
-        from ..model_spec import ODE_METHODS
-        if self.ode_method not in ODE_METHODS:
-            raise ValueError(f"ode_method must be one of {sorted(ODE_METHODS)}")
+        from ..model_spec import ODE_METHODS, ODE_MULTISTEP
+        if self.ode_method not in ODE_METHODS and self.ode_method not in ODE_MULTISTEP:
+            raise ValueError(f"ode_method must be one of {sorted(ODE_METHODS) + sorted(ODE_MULTISTEP)}")
+        self.ode_report = bool(self.ode_report)
+        if self.ode_report and self.ode_method not in ODE_MULTISTEP:
+            raise ValueError(f"ode_report needs a multistep ode_method ({sorted(ODE_MULTISTEP)}): it reports the difference of consecutive slopes")
         if self.cfg_strength is not None:
             self.cfg_strength = float(self.cfg_strength)
             if self.cfg_strength != self.cfg_strength or abs(self.cfg_strength) == float("inf"):

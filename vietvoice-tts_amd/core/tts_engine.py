@@ -49,6 +49,7 @@ class TTSEngine:
         self._lock = threading.Lock()
         self._decode_graphs = None               # DecodeGraphCache, created with the first captured decode (use_hip_graph)
         self._last_plan = []
+        self.last_ode_report = []                # N20 (config.ode_report): the step reports of the last synthesis, float64 [n_steps, B, 2] per GPU batch
 
     def cleanup(self) -> None:
         if self._decode_graphs is not None:       # captured graphs point into the context about to be destroyed, and pin HBM
@@ -280,7 +281,10 @@ class TTSEngine:
         m = self.model_session_manager
         eng, spec = m.engine, m.spec
         dev = eng.device
+        eng.set_ode_report(False)                # the plan may change under it; back on below when the config asks for it
         eng.set_nfe(self.config.nfe_step, self.config.ode_method)
+        eng.set_ode_report(self.config.ode_report)
+        self.last_ode_report = []
         hop = self.config.hop_length
         g_all = [self.config.cfg_strength] * len(inputs_list) if cfg_strengths is None else \
             [self.config.cfg_strength if v is None else float(v) for v in cfg_strengths]
@@ -371,6 +375,8 @@ class TTSEngine:
                                                               None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
                                                               audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg)
+            if self.config.ode_report:
+                self.last_ode_report.append(eng.last_ode_report())
             if device_out:
                 pcm = pcm.clone() if self.config.use_hip_graph else pcm.contiguous()      # a captured graph's output buffer is replayed over
                 for i, j in enumerate(idx):
@@ -554,7 +560,9 @@ class TTSEngine:
             ids = self.text_processor.text_to_indices([list(clean)])
             try:
                 dev = eng.device
+                eng.set_ode_report(False)
                 eng.set_nfe(cfg.nfe_step, cfg.ode_method)
+                eng.set_ode_report(cfg.ode_report)
                 g_item = None if cfg.cfg_strength is None else torch.full((1,), float(cfg.cfg_strength), dtype=torch.float32, device=dev)
                 _x, pcm, n_out = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
                                                torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
@@ -563,6 +571,7 @@ class TTSEngine:
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
                                                guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys,
                                                apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]))
+                self.last_ode_report = [eng.last_ode_report()] if cfg.ode_report else []
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options(),

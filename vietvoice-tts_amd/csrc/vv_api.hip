@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.12 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.13 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -47,6 +47,11 @@ struct vv_ctx {
     double ode_a[16] = {}, ode_b[4] = {1.0, 0, 0, 0};
     int ode_kslot[4] = {-1, -1, -1, -1};   // slope buffer of k_j, -1 = k_j is consumed by the launch that makes it and never read again
     int ode_nk = 0;                     // slope buffers a step needs (<= ode_s - 1)
+    // N20: Adams-Bashforth multistep plan (vv_set_ode_multistep) on the one-stage tables; ms_q 0 = none.  Any other plan clears it.
+    int ms_q = 0;                       // slopes a step combines: the fresh one and ms_q - 1 kept from the steps before
+    std::vector<double> ms_beta;        // [n_steps][ms_q], j = 0 the newest slope
+    double* ode_report = nullptr;       // N20 step report (vv_set_ode_report): caller-owned device [report_steps][report_B][2], nullptr = off
+    int report_steps = 0, report_B = 0;
     // workspace block
     char* ws = nullptr;                 // context-owned block: may MOVE when a later call needs more bytes (ensure_ws)
     size_t ws_cap = 0;
@@ -499,6 +504,8 @@ static int set_plan_impl(vv_ctx* c, const char* who, const float* sinus_host, co
         for (int m = j + 2; m < s; ++m) later = later || c->ode_a[m * 4 + j] != 0.0;
         c->ode_kslot[j] = later ? c->ode_nk++ : -1;
     }
+    c->ms_q = 0; c->ms_beta.clear();             // N20: a multistep plan and a report belong to the plan that was in force
+    c->ode_report = nullptr; c->report_steps = c->report_B = 0;
     return 0;
 }
 
@@ -509,6 +516,39 @@ int vv_set_time_grid(vv_ctx* c, const float* sinus_host, const float* dt_host, i
 
 int vv_set_ode_plan(vv_ctx* c, const float* sinus_host, const float* dt_host, int n_steps, int s, const double* a, const double* b, void* stream) {
     return set_plan_impl(c, "vv_set_ode_plan", sinus_host, dt_host, n_steps, s, a, b, stream);
+}
+
+// N20: an Adams-Bashforth plan = the Euler tables (one evaluation per step) and the weights of the kept slopes.  Everything is validated
+// before the plan in force is touched.
+int vv_set_ode_multistep(vv_ctx* c, const float* sinus_host, const float* dt_host, int n_steps, int q, const double* beta, void* stream) {
+    if (!c) return -22;
+    if (n_steps < 1 || n_steps > 512) return c->fail(-22, "vv_set_ode_multistep: bad arguments");
+    if (q < 1 || q > 3 || !beta) return c->fail(-22, "vv_set_ode_multistep: 1 to 3 slopes per step with their weights");
+    for (int n = 0; n < n_steps; ++n) {
+        double sum = 0;
+        for (int j = 0; j < q; ++j) {
+            const double v = beta[(size_t)n * q + j];
+            if (!std::isfinite(v)) return c->fail(-22, "vv_set_ode_multistep: the weights must be finite");
+            if (j > n && v != 0.0) return c->fail(-22, "vv_set_ode_multistep: step %d has a weight on a slope from before step 0", n);
+            sum += v;
+        }
+        if (!(std::fabs(sum - 1.0) < 1e-6)) return c->fail(-22, "vv_set_ode_multistep: the weights of step %d must sum to 1", n);
+    }
+    const double a = 0.0, b = 1.0;
+    if (int r = set_plan_impl(c, "vv_set_ode_multistep", sinus_host, dt_host, n_steps, 1, &a, &b, stream)) return r;
+    c->ms_q = q;
+    c->ms_beta.assign(beta, beta + (size_t)n_steps * q);
+    return 0;
+}
+
+int vv_set_ode_report(vv_ctx* c, double* report, int n_steps, int B) {
+    if (!c) return -22;
+    if (!report) { c->ode_report = nullptr; c->report_steps = c->report_B = 0; return 0; }
+    if (c->ms_q < 1) return c->fail(-22, "vv_set_ode_report: the report needs a multistep plan (vv_set_ode_multistep)");
+    if (n_steps != c->n_steps || B < 1 || B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_set_ode_report: [%d steps of the plan][1..%d items][2]", c->n_steps, VVK_GUIDE_MAX_ITEMS);
+    if ((uintptr_t)report % 8) return c->fail(-22, "vv_set_ode_report: report must be a float64 array");
+    c->ode_report = report; c->report_steps = n_steps; c->report_B = B;
+    return 0;
 }
 
 // --------------------------------------------------------------------------------- preprocess
@@ -1089,7 +1129,13 @@ struct Lane {
     // stage i reads the state it was evaluated at (x_e) while it writes the next one
     double* apg_part = nullptr;
     float *apg_coef = nullptr, *xs2 = nullptr;
+    // N20 (a multistep plan): the ring of kept slopes, f_m in slot m % ms_ring(c), [Rc][n_mel] fp32 each; the report's partial sums [B][n_tiles][2]
+    float* hist[3] = {};
+    double* rep_part = nullptr;
 };
+// N20: slots of the slope ring.  q - 1 without a report: the fresh slope takes the slot of the oldest one the step reads.  With a report
+// one more (two at the least), so that f_{n-1} outlives the stage launch of step n.
+inline int ms_ring(const vv_ctx* c) { return !c->ms_q ? 0 : c->ode_report ? std::max(c->ms_q, 2) : c->ms_q - 1; }
 // N8: what the host knows of a lane's guided subset at the evaluation in hand
 struct GuideState {
     std::vector<uint8_t> flags;        // [B] of the lane; empty = no tables built yet in this call
@@ -1180,6 +1226,8 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, boo
         L.xs = a.take<float>(L.Rc * M);
         for (int k = 0; k < c->ode_nk; ++k) L.kbuf[k] = a.take<float>(L.Rc * M);
     }
+    for (int k = 0; k < ms_ring(c); ++k) L.hist[k] = a.take<float>(L.Rc * M);        // N20: beside the stage buffers (ode_s is 1 here)
+    if (c->ms_q && c->ode_report) L.rep_part = a.take<double>((size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2);
     if (guided) {                                  // N8: row_start[2B] | rs_rel[B] | kv_len[2B] | row_pos[2 Rc] | u_src[Rc] | u_crow[Rc] | u_row[Rc]
         int* t = a.take<int>(5 * (size_t)L.B + 5 * L.Rc);
         L.g_row_start = t; L.g_rs_rel = t + 2 * L.B; L.g_kv_len = t + 3 * L.B; L.g_row_pos = t + 5 * L.B;
@@ -1354,14 +1402,28 @@ struct StepsRun : StepDims {
         const vv_apg_args* apg = q.apg;
         const bool last = i == ns - 1;
         const double h = (double)c->dt_host[s];
+        const int ring = ms_ring(c);
         vv_ode_stage_args a{};
         a.x = L.x; a.pred = L.pred; a.ldp = MP; a.Rc = (int)L.Rc; a.n_mel = M; a.n_prev = i;
         int n_read = 0;
-        for (int j = 0; j <= i; ++j) {
-            a.coef[j] = (float)(h * (last ? c->ode_b[j] : c->ode_a[(i + 1) * 4 + j]));
-            if (j < i && a.coef[j] != 0.f) { a.k_prev[j] = L.kbuf[c->ode_kslot[j]]; ++n_read; }
+        if (c->ms_q) {
+            // N20: x += h (beta_0 f_s + beta_1 f_{s-1} + beta_2 f_{s-2}) in one launch of the stage kernel.  The call starts at step 0
+            // (transformer_steps), so step s has s slopes behind it and reads nothing an earlier call left: the ring starts empty.
+            const double* beta = c->ms_beta.data() + (size_t)s * c->ms_q;
+            a.n_prev = std::min(c->ms_q - 1, s);
+            for (int j = 1; j <= a.n_prev; ++j) {
+                a.coef[j - 1] = (float)(h * beta[j]);
+                if (a.coef[j - 1] != 0.f) { a.k_prev[j - 1] = L.hist[(s - j) % ring]; ++n_read; }
+            }
+            a.coef[a.n_prev] = (float)(h * beta[0]);
+            a.k_out = (ring && (c->ode_report || s + 1 < c->n_steps)) ? L.hist[s % ring] : nullptr;     // the slot of the oldest slope read
+        } else {
+            for (int j = 0; j <= i; ++j) {
+                a.coef[j] = (float)(h * (last ? c->ode_b[j] : c->ode_a[(i + 1) * 4 + j]));
+                if (j < i && a.coef[j] != 0.f) { a.k_prev[j] = L.kbuf[c->ode_kslot[j]]; ++n_read; }
+            }
+            a.k_out = (!last && c->ode_kslot[i] >= 0) ? L.kbuf[c->ode_kslot[i]] : nullptr;
         }
-        a.k_out = (!last && c->ode_kslot[i] >= 0) ? L.kbuf[c->ode_kslot[i]] : nullptr;
         a.x_out = last ? nullptr : stage_state(L, i + 1);
         a.g = g.cfg_strength; a.g_item = q.a.cfg_item ? q.a.cfg_item + L.b0 : nullptr; a.seq_n = N; a.row_src = L.row_src;
         const int* u_row = q.guide ? L.u_row : nullptr;
@@ -1379,7 +1441,15 @@ struct StepsRun : StepDims {
             sa.coef = L.apg_coef; sa.x_e = k.x_e; sa.x_e_packed = i ? 1 : 0; sa.t_e = k.t_e;
         }
         Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0)), L.st);
-        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__));
+        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__, c->ms_q ? 1 : 0));
+        if (c->ms_q && c->ode_report) {                  // N20: the step report, from the slope just stored and the one before it
+            vv_ode_diff_args r{};
+            r.f = L.hist[s % ring]; r.f_prev = s ? L.hist[(s - 1) % ring] : nullptr; r.Rc = (int)L.Rc; r.n_mel = M;
+            r.B = L.B; r.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; r.row_start = L.row_start; r.len = L.kv_len;
+            r.partials = L.rep_part; r.report = c->ode_report + ((size_t)s * q.a.B + L.b0) * 2;
+            { Prof p2(c, VV_PROF_ELEMWISE, 6.0 * L.Rc * M, 8.0 * L.Rc * M, L.st); KCHK(c, vvk_ode_diff_reduce(&r, 1, L.st, &m__)); }
+            { Prof p2(c, VV_PROF_ELEMWISE, 0, 16.0 * L.B * r.n_tiles, L.st); KCHK(c, vvk_ode_diff_reduce(&r, 2, L.st, &m__)); }
+        }
         return 0;
     }
     // What the block-level kernels (step_head, block, step_tail) run on: views of the lanes' buffers, two at the most; -> their number.
@@ -1476,12 +1546,15 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
     if (!c) return -22;
     const vv_steps_args& a = q.a;
     q.with_apg = q.apg != nullptr || q.ws_form == WS_APG; q.guided = q.guide != nullptr || q.ws_form != WS_PLAIN || q.with_apg;
-    q.rk = c->ode_s > 1 || a.cfg_item != nullptr || q.guide != nullptr || q.apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
+    q.rk = c->ode_s > 1 || c->ms_q > 0 || a.cfg_item != nullptr || q.guide != nullptr || q.apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     const int B = a.B, N = a.N;
     if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
     if (B < 1 || N < 1 || (!q.ws_only && (!a.seq_len || !a.x || !a.cat_mel_text || !a.cat_mel_text_drop || !a.rope_cos_q || !a.rope_sin_q || !a.rope_cos_k || !a.rope_sin_k)))
         return c->fail(-22, "vv_transformer_steps: bad arguments");
     if (a.step0 < 0 || a.n_steps < 0 || a.step0 + a.n_steps > c->n_steps) return c->fail(-22, "vv_transformer_steps: steps [%d,%d) outside the time grid (%d)", a.step0, a.step0 + a.n_steps, c->n_steps);
+    if (c->ms_q && !q.ws_only && a.step0 != 0) return c->fail(-22, "vv_transformer_steps: under a multistep plan a call starts at step 0 (the kept slopes live for one call), got step0 = %d", a.step0);
+    if (c->ms_q && c->ode_report && !q.ws_only && (c->report_B != B || c->report_steps != c->n_steps))
+        return c->fail(-22, "vv_transformer_steps: the step report was set for %d steps of %d items, the call has %d of %d", c->report_steps, c->report_B, c->n_steps, B);
     if (q.guide && q.ld_guide < B) return c->fail(-22, "vv_transformer_steps_guided: ld_guide = %d < B = %d", q.ld_guide, B);
     if (q.guide && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_guided: a guidance mask cannot be combined with option split_k_tail (its tail plan depends on the row count)");
     if (q.guided && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_guided: at most %d items per call", VVK_GUIDE_MAX_ITEMS);
@@ -1980,6 +2053,11 @@ int vv_ode_stage_apg(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_apg: null arguments") : -22;
     if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_apg: u_row must be an int32 array");
     SINGLE(c, vvk_ode_stage(a, u_row, apg, (hipStream_t)st, &m__));
+}
+int vv_ode_diff_reduce(vv_ctx* c, const vv_ode_diff_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_diff_reduce: null arguments") : -22;
+    if (((uintptr_t)a->row_start | (uintptr_t)a->len) % 4) return c->fail(-22, "vv_ode_diff_reduce: the index arrays must be 4-byte aligned");
+    SINGLE(c, vvk_ode_diff_reduce(a, 3, (hipStream_t)st, &m__));
 }
 int vv_apg_coef(vv_ctx* c, const vv_apg_coef_args* a, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_apg_coef: null arguments") : -22;

@@ -220,7 +220,7 @@ struct OdeStagePrev { const float* k[3]; float c[3]; };
 template <bool GUIDED, bool APG>
 __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
                                                         const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
-                                                        OdeStagePrev pv, float c_new, float* __restrict__ k_out, float* __restrict__ x_out,
+                                                        OdeStagePrev pv, float c_new, float* k_out, float* __restrict__ x_out,
                                                         const int* __restrict__ u_row, const float* __restrict__ apg_coef,
                                                         const float* x_e, int xe_packed, float omt) {
     const int c4 = n_mel >> 2;
@@ -253,7 +253,6 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
                 k.w = fmaf(apg_c, fmaf(omt, pc.w, xe.w), k.w);
             }
         }
-        if (k_out) *(float4*)(k_out + row * n_mel + c) = k;
         float4 xv = *(const float4*)(x + xr * n_mel + c);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
@@ -261,6 +260,9 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
                 const float4 kj = *(const float4*)(pv.k[j] + row * n_mel + c);
                 xv.x += pv.c[j] * kj.x; xv.y += pv.c[j] * kj.y; xv.z += pv.c[j] * kj.z; xv.w += pv.c[j] * kj.w;
             }
+        // stored behind the loads of the earlier slopes: under a multistep plan (N20) k_out is the ring slot of the oldest slope this
+        // launch reads, and each element is read and written by this thread alone
+        if (k_out) *(float4*)(k_out + row * n_mel + c) = k;
         if (c_new != 0.f) {
             xv.x += c_new * k.x; xv.y += c_new * k.y; xv.z += c_new * k.z; xv.w += c_new * k.w;
         }
@@ -345,6 +347,73 @@ __global__ __launch_bounds__(64) void apg_coef_kernel(const double* __restrict__
         Cc = (e == 1.0 || S2 == 0.0) ? 0.f : (float)(gb * sc * (e - 1.0) * S1 / S2);
     }
     coef[2 * b] = A; coef[2 * b + 1] = Cc;
+}
+
+// ---------------------------------------------------------------- N20: the step report of a multistep plan, the per-item reduction
+// Partial sums of one (frame tile, item): D2 = sum (f - f_prev)^2 and F2 = sum f^2 over the tile's valid frames and the n_mel columns of
+// the packed slopes f and f_prev ([Rc][n_mel] fp32), every difference, square and sum in float64 and NOT contracted (a product, then an
+// add: what a host mirror does with numpy alone).  f_prev NULL (step 0): D2 = 0.  apg_reduce_kernel's determinism contract: tiles of
+// VV_APG_TILE frames counted from the ITEM's frame 0, float4 q of the tile to thread q % 256 with its four elements in order, one fixed
+// LDS tree -- an item's partials are a function of its own rows alone.  grid (n_tiles, B); a tile past the item's length writes nothing.
+__global__ __launch_bounds__(256) void ode_diff_reduce_kernel(const float* __restrict__ f, const float* __restrict__ f_prev, int Rc, int n_mel,
+                                                              const int* __restrict__ row_start, const int* __restrict__ len, int n_tiles,
+                                                              double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double red[2][256];
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);   // inside the Rc rows and the item's n_tiles partials, whatever the tables say
+    const int f0 = tile * VV_APG_TILE;
+    if (f0 >= n) return;
+    const int c4 = n_mel >> 2;
+    const int total = min(VV_APG_TILE, n - f0) * c4;
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const size_t at = ((size_t)r0 + f0 + q / c4) * n_mel + (q % c4) * 4;
+        const float4 a = *(const float4*)(f + at);
+        const float av[4] = {a.x, a.y, a.z, a.w};
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (f_prev) {
+            const float4 p = *(const float4*)(f_prev + at);
+            pv[0] = p.x; pv[1] = p.y; pv[2] = p.z; pv[3] = p.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = (double)av[j];
+            if (f_prev) {
+                const double d = v - (double)pv[j];
+                const double dd = d * d;
+                s1 = s1 + dd;
+            }
+            const double vv = v * v;
+            s2 = s2 + vv;
+        }
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) partials[((size_t)b * n_tiles + tile) * 2 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// One wave per item: lane j < 2 adds the item's partials in ascending tile order from 0.0 and stores report[b] = {D2, F2}; {0, 0} for an
+// item without rows.
+__global__ __launch_bounds__(64) void ode_diff_finish_kernel(const double* __restrict__ partials, int n_tiles, int Rc,
+                                                             const int* __restrict__ row_start, const int* __restrict__ len,
+                                                             double* __restrict__ report) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (lane >= 2) return;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);
+    const int nt = (n + VV_APG_TILE - 1) / VV_APG_TILE;
+    double s = 0.0;
+    for (int t = 0; t < nt; ++t) s += partials[((size_t)b * n_tiles + t) * 2 + lane];
+    report[2 * b + lane] = s;
 }
 
 // ---------------------------------------------------------------- text: embed gather + position table
@@ -725,7 +794,7 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
     return 0;
 }
 
-int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err) {
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring) {
     if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
     if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
     if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
@@ -737,7 +806,8 @@ int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_sta
         if (!a->k_prev[j]) { *err = "ode_stage: a non-zero coefficient without its slope buffer"; return -22; }
         pv.k[j] = a->k_prev[j]; pv.c[j] = a->coef[j];
         al |= (uintptr_t)a->k_prev[j];
-        if (a->k_prev[j] == a->k_out || a->k_prev[j] == a->x_out) { *err = "ode_stage: an output aliases an earlier slope"; return -22; }
+        // k_out_ring (N20, the steps driver alone): k_out may BE one of the earlier slopes' buffers -- the kernel stores k behind its loads of them
+        if ((a->k_prev[j] == a->k_out && !k_out_ring) || a->k_prev[j] == a->x_out) { *err = "ode_stage: an output aliases an earlier slope"; return -22; }
     }
     if (al % 16) { *err = "ode_stage: buffers must be 16-byte aligned"; return -22; }
     if (a->x_out && (a->x_out == a->x || a->x_out == a->k_out)) { *err = "ode_stage: x_out must be a buffer of its own"; return -22; }
@@ -775,6 +845,23 @@ int vvk_apg_coef(const vv_apg_coef_args* a, int which, hipStream_t st, const cha
     if (which & 2) {
         apg_coef_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->n_mel, a->u_row, a->row_start, a->len, omt, a->g, a->g_item,
                                              a->eta, a->norm_rms, a->coef);
+        VVK_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// N20: the two kernels behind vv_ode_diff_reduce.  which & 1: the reduction, which & 2: the item sums.
+int vvk_ode_diff_reduce(const vv_ode_diff_args* a, int which, hipStream_t st, const char** err) {
+    if (a->n_mel < 4 || a->n_mel % 4 || a->Rc < 1) { *err = "ode_diff_reduce: n_mel must be a multiple of 4, Rc >= 1"; return -22; }
+    if (!a->f || !a->row_start || !a->len || !a->partials || !a->report) { *err = "ode_diff_reduce: f, row_start, len, partials and report are required"; return -22; }
+    if (a->B < 1 || a->B > VVK_GUIDE_MAX_ITEMS || a->n_tiles < 1) { *err = "ode_diff_reduce: 1..1024 items, n_tiles >= 1"; return -22; }
+    if (((uintptr_t)a->f | (uintptr_t)a->f_prev) % 16 || ((uintptr_t)a->partials | (uintptr_t)a->report) % 8) { *err = "ode_diff_reduce: f and f_prev 16-byte, partials and report 8-byte aligned"; return -22; }
+    if (which & 1) {
+        ode_diff_reduce_kernel<<<dim3(a->n_tiles, a->B), 256, 0, st>>>(a->f, a->f_prev, a->Rc, a->n_mel, a->row_start, a->len, a->n_tiles, a->partials);
+        VVK_CHECK_LAUNCH();
+    }
+    if (which & 2) {
+        ode_diff_finish_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->row_start, a->len, a->report);
         VVK_CHECK_LAUNCH();
     }
     return 0;

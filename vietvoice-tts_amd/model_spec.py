@@ -210,11 +210,63 @@ class OdePlan(NamedTuple):
     a: Tuple[Tuple[float, ...], ...]
     b: Tuple[float, ...]
     s: int
+    beta: Optional[Tuple[Tuple[float, ...], ...]] = None     # N20, a multistep plan only: multistep_weights' rows [n_steps][q]
+
+
+# Adams-Bashforth multistep methods of the sampler: name -> q, the slopes a step combines (the fresh one and q - 1 kept
+# from the steps before).  One DiT evaluation per step, as Euler.
+ODE_MULTISTEP: Dict[str, int] = {"ab2": 2, "ab3": 3}
+
+
+def _grid64(nfe_step: int, sway_coef: float) -> torch.Tensor:
+    t = torch.linspace(0.0, 1.0, nfe_step, dtype=torch.float64)
+    return t + sway_coef * (torch.cos(math.pi / 2 * t) - 1.0 + t)
+
+
+def multistep_weights(t64, q: int) -> Tuple[Tuple[float, ...], ...]:
+    """The variable-step Adams-Bashforth weights on the grid ``t64`` (float64 points t_0 < ... < t_n): float64 rows [n_steps][q], j = 0
+    the newest slope, with x_{n+1} = x_n + h_n sum_j beta[n][j] f_{n-j}.  beta[n][j] is the integral over [t_n, t_{n+1}] of the
+    Lagrange basis polynomial of node t_{n-j} among the nodes t_n, ..., t_{n-k+1}, divided by h_n, k = min(q, n + 1) the order used at
+    step n (step 0 is Euler, step 1 AB2, from step 2 on AB3 when q = 3); the entries j >= k are 0.  Computed in exact rationals from the
+    float64 grid and rounded once.  A uniform grid gives (1), (3/2, -1/2), (23/12, -4/3, 5/12)."""
+    q = int(q)
+    if not 1 <= q <= 3:
+        raise ValueError("multistep_weights: q must be 1, 2 or 3")
+    tq = [Fraction(float(v)) for v in t64]
+    if len(tq) < 2 or any(tq[i + 1] <= tq[i] for i in range(len(tq) - 1)):
+        raise ValueError("multistep_weights: the grid must have two points at least and increase strictly")
+    rows = []
+    for n in range(len(tq) - 1):
+        k = min(q, n + 1)
+        h = tq[n + 1] - tq[n]
+        nodes = [tq[n - j] - tq[n] for j in range(k)]           # relative to t_n: 0, -h_{n-1}, -(h_{n-1} + h_{n-2})
+        row = []
+        for j in range(k):
+            poly = [Fraction(1)]                                # coefficients of prod_{m != j} (s - nodes[m]), ascending powers of s
+            den = Fraction(1)
+            for m in range(k):
+                if m == j:
+                    continue
+                poly = [(poly[i - 1] if i > 0 else 0) - nodes[m] * (poly[i] if i < len(poly) else 0) for i in range(len(poly) + 1)]
+                den *= nodes[j] - nodes[m]
+            integral = sum(cf * h ** (i + 1) / (i + 1) for i, cf in enumerate(poly))
+            row.append(float(integral / den / h))
+        rows.append(tuple(row + [0.0] * (q - k)))
+    return tuple(rows)
 
 
 def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
     """The sampler's plan on time_grid's grid: ``nfe_step`` points, ``nfe_step - 1`` ODE steps of ``s`` evaluations each at
-    t_n + c_i h_n (float64, clamped to [0, 1], then fp32 -- like time_grid).  ``ode_plan(n, sway, "euler")`` is time_grid bit for bit."""
+    t_n + c_i h_n (float64, clamped to [0, 1], then fp32 -- like time_grid).  ``ode_plan(n, sway, "euler")`` is time_grid bit for bit.
+
+    A name of ODE_MULTISTEP (N20, "ab2" | "ab3"): the plan of an Adams-Bashforth method -- ``t``, ``dt``, ``a``, ``b`` and ``s`` = 1 are
+    Euler's bit for bit (one evaluation per step, at t_n), and ``beta`` holds multistep_weights' rows on the float64 grid.  No start-up
+    step with extra evaluations is built: step 0 is an Euler step and step 1 of "ab3" an AB2 step.  With that start "ab3" has global
+    order 3 on the model's own sway grid (coefficient -1: the first step is O(n^-2) long, so its O(h_0^2) error is O(n^-4)) and order
+    2 on a uniform grid; "ab2" has order 2 on both."""
+    if isinstance(method, str) and method in ODE_MULTISTEP:
+        e = ode_plan(nfe_step, sway_coef, "euler")
+        return e._replace(beta=multistep_weights(_grid64(nfe_step, sway_coef), ODE_MULTISTEP[method]))
     a, b = ode_tableau(method)
     s = len(b)
     t = torch.linspace(0.0, 1.0, nfe_step, dtype=torch.float64)

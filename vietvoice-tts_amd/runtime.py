@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ODE_MAX_EVALS, ModelSpec, check_apg, guidance_mask, ode_plan
+from .model_spec import ODE_MAX_EVALS, ODE_MULTISTEP, ModelSpec, check_apg, guidance_mask, ode_plan
 from .pcm_stage import JOIN_MAX_N, LOUD_RUN, PcmStage, _ptr, plan_join  # noqa: F401  (the constants and plan_join stay importable from here)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -125,6 +125,11 @@ class vv_apg_stage_args(C.Structure):
     _fields_ = [("coef", C.c_void_p), ("x_e", C.c_void_p), ("x_e_packed", C.c_int32), ("t_e", C.c_float)]
 
 
+class vv_ode_diff_args(C.Structure):
+    _fields_ = [("f", C.c_void_p), ("f_prev", C.c_void_p), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("B", C.c_int32), ("n_tiles", C.c_int32),
+                ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p), ("report", C.c_void_p)]
+
+
 APG_TILE = 32                 # VV_APG_TILE of include/vvtts.h: frames per partial sum of the projected-guidance reduction
 
 EXPORTS = {
@@ -137,6 +142,9 @@ EXPORTS = {
     "vv_finalize_weights": (C.c_int, [C.c_void_p]),
     "vv_set_time_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vv_set_ode_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vv_set_ode_multistep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vv_set_ode_report": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "vv_ode_diff_reduce": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_diff_args), C.c_void_p]),
     "vv_transformer_steps_ex": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p]),
     "vv_ode_stage": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p]),
     "vv_transformer_steps_guided": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.c_void_p]),
@@ -339,7 +347,8 @@ class HipSynth(PcmStage):
     """
 
     def __init__(self, spec: ModelSpec, weights: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda:0",
-                 acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None, ode_method="euler"):
+                 acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None, ode_method="euler",
+                 ode_report: bool = False):
         super().__init__()
         self.lib = load_library()
         if not torch.cuda.is_available():
@@ -377,8 +386,11 @@ class HipSynth(PcmStage):
         self.grid_generation = 0         # bumped by whatever a captured Euler-step graph has baked in (time grid, rope mode, options)
         self.set_rope_theta(float(spec.rope_theta))
         self.nfe_step = None
-        self.ode_method = None           # the solver of the plan in force: a name of model_spec.ODE_METHODS or a custom tableau (a, b)
+        self.ode_method = None           # the solver of the plan in force: a name of model_spec.ODE_METHODS / ODE_MULTISTEP or a custom tableau (a, b)
+        self.ode_report = False          # N20: every transformer_steps call from step 0 leaves its step report (last_ode_report); needs a multistep plan
+        self._ode_report = None          # the last call's report, float64 [n_steps, B, 2] on the device
         self.set_nfe(nfe_step, ode_method)
+        self.set_ode_report(ode_report)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int):
@@ -401,13 +413,17 @@ class HipSynth(PcmStage):
 
     def set_nfe(self, nfe_step: int, ode_method="euler"):
         """The sampler's plan (N7): ``nfe_step`` grid points = ``nfe_step - 1`` ODE steps of the explicit Runge-Kutta method
-        ``ode_method`` (a name of model_spec.ODE_METHODS, or a tableau (a, b)); ``n_evals`` = stages x steps DiT evaluations."""
+        ``ode_method`` (a name of model_spec.ODE_METHODS, or a tableau (a, b)); ``n_evals`` = stages x steps DiT evaluations.  Or (N20) a
+        name of model_spec.ODE_MULTISTEP: Adams-Bashforth on the slopes kept from the steps before, one evaluation per step
+        (vv_set_ode_multistep); a transformer_steps call then starts at step 0."""
         if not isinstance(ode_method, str):
             ode_method = (tuple(tuple(r) for r in ode_method[0]), tuple(ode_method[1]))
         if (nfe_step, ode_method) == (self.nfe_step, self.ode_method):
             return
         if nfe_step < 2:
             raise ValueError("nfe_step must be >= 2")
+        if self.ode_report and not (isinstance(ode_method, str) and ode_method in ODE_MULTISTEP):
+            raise ValueError("ode_report is on: it needs a multistep ode_method (set_ode_report(False) first)")
         plan = ode_plan(nfe_step, self.spec.sway_coef, ode_method)
         n_steps = int(plan.dt.numel())
         if n_steps * plan.s > ODE_MAX_EVALS:
@@ -417,7 +433,12 @@ class HipSynth(PcmStage):
         a = (C.c_double * (plan.s * plan.s))(*[v for r in plan.a for v in r])
         b = (C.c_double * plan.s)(*plan.b)
         with self._lock, torch.cuda.device(self.device):          # under the engine lock: no step call or graph replay runs across the change
-            self._check(self.lib.vv_set_ode_plan(self.ctx, sinus.data_ptr(), dtc.data_ptr(), n_steps, plan.s, a, b, self._stream()))
+            if plan.beta is not None:                             # N20: the Euler tables and the weights of the kept slopes
+                q = len(plan.beta[0])
+                beta = (C.c_double * (n_steps * q))(*[v for r in plan.beta for v in r])
+                self._check(self.lib.vv_set_ode_multistep(self.ctx, sinus.data_ptr(), dtc.data_ptr(), n_steps, q, beta, self._stream()))
+            else:
+                self._check(self.lib.vv_set_ode_plan(self.ctx, sinus.data_ptr(), dtc.data_ptr(), n_steps, plan.s, a, b, self._stream()))
             self.nfe_step = nfe_step
             self.ode_method = ode_method
             self.n_steps = n_steps
@@ -425,6 +446,45 @@ class HipSynth(PcmStage):
             self.plan = plan             # the evaluation times a guidance interval is compared with (guidance_mask)
             self._t_host = (C.c_float * self.n_evals)(*[float(v) for v in plan.t])     # the same times for projected guidance (vv_apg_args.t_host)
             self.grid_generation += 1    # vv_set_ode_plan frees and reallocates the tables a captured step graph points into
+
+    def set_ode_report(self, on: bool):
+        """N20: turn the step report of the multistep plan in force on or off (ModelConfig.ode_report).  On, every transformer_steps call
+        that starts at step 0 leaves float64 [n_steps, B, 2] for last_ode_report; off (the default) launches and allocates nothing."""
+        on = bool(on)
+        if on and self.plan.beta is None:
+            raise ValueError(f"ode_report needs a multistep ode_method ({sorted(ODE_MULTISTEP)}), the plan in force is {self.ode_method!r}")
+        with self._lock:
+            self.ode_report = on
+            if not on:
+                self._ode_report = None
+
+    def last_ode_report(self):
+        """N20: the step report of the last transformer_steps call, numpy float64 [n_steps, B, 2]: per step n and item b (D2, F2) =
+        (sum (f_n - f_{n-1})^2, sum f_n^2) over the item's frames and the n_mel columns, f_n the combined velocity of step n (after
+        guidance and the projected term); row 0 holds (0, F2).  sqrt(D2 / F2) is the relative change of the velocity over the step,
+        the local-error term of an Euler step.  One copy from the device; None when no call has left a report."""
+        with self._lock:
+            rep = self._ode_report
+        return None if rep is None else rep.cpu().numpy()
+
+    class _ReportScope:
+        """The report buffer of one steps call: set in front of it, cleared behind it whatever happens (the library keeps no pointer to a
+        tensor that may be freed)."""
+        def __init__(self, eng, B, step0):
+            self.eng, self.buf = eng, None
+            if eng.ode_report and step0 == 0:
+                self.buf = torch.zeros((eng.n_steps, int(B), 2), dtype=torch.float64, device=eng.device)
+
+        def __enter__(self):
+            if self.buf is not None:
+                self.eng._check(self.eng.lib.vv_set_ode_report(self.eng.ctx, self.buf.data_ptr(), self.eng.n_steps, int(self.buf.shape[1])))
+            return self
+
+        def __exit__(self, et, ev, tb):
+            if self.buf is not None:
+                self.eng.lib.vv_set_ode_report(self.eng.ctx, None, 0, 0)
+                self.eng._ode_report = self.buf if et is None else None
+            return False
 
     # ------------------------------------------------------------------ stages
     def preprocess(self, audio: torch.Tensor, audio_len: torch.Tensor, text_ids: torch.Tensor, text_len: torch.Tensor,
@@ -502,7 +562,7 @@ class HipSynth(PcmStage):
             host = None if seq_len_host is None else _host_lens(B, seq_len_host)
             self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg)
             return x
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
             tail = _pre_ptrs(pre) + (step0, n_steps, self._stream())
             if seq_len_host is not None:
                 self._check(self.lib.vv_transformer_steps_h(self.ctx, B, N, pre["seq_len"].data_ptr(), _host_lens(B, seq_len_host), x.data_ptr(), *tail))
@@ -550,7 +610,7 @@ class HipSynth(PcmStage):
         if ws is not None:
             a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
         a.cfg_item = _ptr(cfg)
-        with self._lock, torch.cuda.device(self.device):
+        with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
             if apg is not None:
                 q = vv_apg_args(_ptr(apg[0]), _ptr(apg[1]), C.cast(self._t_host, C.c_void_p))
                 self._check(self.lib.vv_transformer_steps_apg(self.ctx, C.byref(a), None if guide is None else guide.data_ptr(),
