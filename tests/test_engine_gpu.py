@@ -160,6 +160,30 @@ def test_batching_frontend_batch_composition_invariance(tmp_path):
         e.cleanup()
 
 
+def test_batching_frontend_mixed_request_options_share_one_batch(tmp_path):
+    """Four requests whose own options span all ten fields of RequestOptions ride in ONE batch (device noise, so the serial alone names
+    a request's noise): each comes back byte for byte as when it was submitted alone with the same serial."""
+    from vietvoice_tts_amd.batching import BatchingFrontend
+    e = _engine(tmp_path, noise_source="device")
+    fe = BatchingFrontend(e, max_wait_ms=500.0, max_requests=8)
+    reqs = [dict(text=LONG, speed=0.8, serial=21),
+            dict(text="Xin chào các bạn, hôm nay thế nào?", speed=1.0, serial=22, cfg_strength=1.5, cfg_interval=(0.2, 0.9), loudness=-20.0, limiter="true"),
+            dict(text="Tạm biệt và hẹn gặp lại.", speed=1.3, serial=23, gender="male", apg_eta=0.0, apg_norm=2.0, pitch=3.0, formants="keep", denoise=1.0),
+            dict(text=LONG, speed=1.1, serial=24, tempo=1.25, denoise=2.0, limiter="sample")]
+    try:
+        alone = [fe.submit(**r).result(timeout=300)[0] for r in reqs]
+        n0 = fe.stats()["batches"]
+        assert n0 == len(reqs)
+        outs = [f.result(timeout=300)[0] for f in [fe.submit(**r) for r in reqs]]
+        assert fe.stats()["batches"] == n0 + 1                       # the four really did share a batch
+        for i, (got, want) in enumerate(zip(outs, alone)):
+            assert got.dtype == np.int16 and got.size > 0 and got.shape == want.shape and np.array_equal(got, want), i
+        assert len({o.tobytes() for o in outs}) == 4
+    finally:
+        fe.close()
+        e.cleanup()
+
+
 def test_batching_frontend_batch_composition_invariance_full_bf16(tmp_path):
     """The same promise at FULL model size in the throughput arithmetic (bf16), where it used to be false (the split-K
     tail made a row's arithmetic depend on its position in the launch, and a request alone takes the 128 x 128 GEMM while a batch of

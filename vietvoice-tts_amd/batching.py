@@ -29,22 +29,30 @@ import queue
 import threading
 import time
 from concurrent.futures import Future
-from typing import List, Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 
+from .request_options import RequestOptions
+
+
+class _Request(NamedTuple):
+    """What travels through the request queue."""
+    serial: int
+    text: str
+    speed: Optional[float]
+    voice: dict
+    fut: Future
+    options: RequestOptions
+
 
 class _Batch:
-    __slots__ = ("plans", "flat", "blocks", "keys", "cfgs", "ivals", "etas", "norms", "louds", "lims", "pitches", "tempos", "formants", "denoises", "t0", "n_req")
+    __slots__ = ("reqs", "flat", "blocks", "keys", "t0")
 
     def __init__(self):
-        self.plans, self.flat, self.blocks, self.keys, self.cfgs, self.ivals, self.t0, self.n_req = [], [], [], [], [], [], time.time(), 0
-        self.etas, self.norms = [], []
-        self.louds = []               # per REQUEST: its own loudness target (N12) or None
-        self.lims = []                # per REQUEST: its own limiter mode (N13) or None
-        self.pitches, self.tempos = [], []      # per REQUEST: its own pitch / tempo (N14) or None
-        self.formants = []                      # per REQUEST: its own formants mode (N18) or None
-        self.denoises = []                      # per REQUEST: its own denoiser strength (N19) or None
+        self.reqs = []                # per REQUEST: (its Future, the number of its chunks, its RequestOptions)
+        self.flat, self.blocks, self.keys = [], [], []      # per CHUNK, the requests' one after another: inputs, and noise blocks or key rows
+        self.t0 = time.time()
 
 
 class BatchingFrontend:
@@ -95,28 +103,11 @@ class BatchingFrontend:
         request alone, against the engine's bias profile."""
         fut: Future = Future()
         try:
-            from .core.audio_processor import check_loudness
-            loudness, _pk = check_loudness(loudness)
-            from .core.audio_processor import check_limiter
-            check_limiter(limiter)
-            from .core.audio_processor import check_prosody
-            pitch, tempo = check_prosody(pitch, tempo)
-            from .core.audio_processor import check_formants
-            formants = None if formants is None else check_formants(formants)
-            from .core.audio_processor import check_denoise
-            denoise = check_denoise(denoise)
-            from .model_spec import check_apg, check_cfg_interval
-            cfg_interval = check_cfg_interval(cfg_interval)
-            check_apg(apg_eta, apg_norm)
-            apg_eta, apg_norm = (None if v is None else float(v) for v in (apg_eta, apg_norm))
+            options = RequestOptions.checked(cfg_strength=cfg_strength, cfg_interval=cfg_interval, apg_eta=apg_eta, apg_norm=apg_norm,
+                                             loudness=loudness, limiter=limiter, pitch=pitch, tempo=tempo, formants=formants, denoise=denoise)
         except ValueError as e:
             fut.set_exception(e)
             return fut
-        if cfg_strength is not None:
-            cfg_strength = float(cfg_strength)
-            if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
-                fut.set_exception(ValueError("cfg_strength must be a finite number or None"))
-                return fut
         with self._serial_lock:           # close() raises `_closed` under the same lock: a request is either queued in front of the
             if self._closed or self._stage_down:      # sentinel (and served) or refused here -- never orphaned behind it
                 fut.set_exception(RuntimeError("Speech synthesis failed: the batching front end is closed"))
@@ -124,7 +115,7 @@ class BatchingFrontend:
             if serial is None:
                 serial = self._serial
             self._serial = max(self._serial, serial) + 1
-            self._q.put((serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise))
+            self._q.put(_Request(serial, text, speed, voice, fut, options))
         return fut
 
     def synthesize(self, text: str, speed: Optional[float] = None, **voice) -> Tuple[np.ndarray, float]:
@@ -145,8 +136,8 @@ class BatchingFrontend:
                 req = self._q.get_nowait()
             except queue.Empty:
                 break
-            if req is not None and not req[4].done():
-                req[4].set_exception(RuntimeError("Speech synthesis failed: the batching front end is closed"))
+            if req is not None and not req.fut.done():
+                req.fut.set_exception(RuntimeError("Speech synthesis failed: the batching front end is closed"))
 
     def stats(self) -> dict:
         b = max(self.batches_run, 1)
@@ -154,10 +145,10 @@ class BatchingFrontend:
                 "chunks_per_batch": self.chunks_run / b, "frames_per_batch": self.frames_run / b, "gpu_busy_s": self.gpu_busy_s}
 
     # ------------------------------------------------------------------ stage 1: collect + host preparation
-    def _prepare_one(self, req, batch: _Batch) -> None:
+    def _prepare_one(self, req: _Request, batch: _Batch) -> None:
         import torch
         eng = self.engine
-        serial, text, speed, voice, fut, cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise = req
+        voice, fut = req.voice, req.fut
         try:
             ref_audio, ref_text = eng.model_session_manager.select_sample(
                 voice.get("gender"), voice.get("group"), voice.get("area"), voice.get("emotion"), voice.get("sample_iteration"),
@@ -166,7 +157,7 @@ class BatchingFrontend:
             fut.set_exception(e)
             return
         try:
-            inputs = eng._prepare_inputs(ref_audio, ref_text, text, speed=speed)
+            inputs = eng._prepare_inputs(ref_audio, ref_text, req.text, speed=req.speed)
         except Exception as e:
             fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))
             return
@@ -174,29 +165,18 @@ class BatchingFrontend:
             blocks, keys = [], []
             if eng._device_noise():         # N9: nothing is drawn here -- the request's serial names its Philox streams, chunk by chunk
                 from .model_spec import noise_keys
-                keys = list(noise_keys(eng.config.random_seed, serial, len(inputs)))
+                keys = list(noise_keys(eng.config.random_seed, req.serial, len(inputs)))
             else:
                 n_mel = eng.model_session_manager.spec.n_mel
-                gen = torch.Generator().manual_seed(eng.config.random_seed * 1000003 + serial)
+                gen = torch.Generator().manual_seed(eng.config.random_seed * 1000003 + req.serial)
                 blocks = [torch.randn((int(i[2][0]), n_mel), generator=gen, dtype=torch.float32) for i in inputs]
         except Exception as e:          # noqa: BLE001  (nothing of this request has entered the batch yet)
             fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))
             return
-        batch.plans.append((fut, len(inputs)))
+        batch.reqs.append((fut, len(inputs), req.options))
         batch.flat.extend(inputs)
         batch.blocks.extend(blocks)
         batch.keys.extend(keys)
-        batch.cfgs.extend([cfg_strength] * len(inputs))
-        batch.ivals.extend([cfg_interval] * len(inputs))
-        batch.etas.extend([apg_eta] * len(inputs))
-        batch.norms.extend([apg_norm] * len(inputs))
-        batch.louds.append(loudness)
-        batch.lims.append(limiter)
-        batch.pitches.append(pitch)
-        batch.tempos.append(tempo)
-        batch.formants.append(formants)
-        batch.denoises.append(denoise)
-        batch.n_req += 1
 
     def _collect(self) -> Optional[_Batch]:
         """Block for the first request, then take what arrives within ``max_wait`` -- and whatever is ALREADY queued when the window
@@ -225,11 +205,11 @@ class BatchingFrontend:
             try:
                 self._prepare_one(r, batch)
             except BaseException as e:    # noqa: BLE001  (_prepare_one reports its own failures; this is the last line of defence)
-                if not r[4].done():
-                    r[4].set_exception(RuntimeError(f"Speech synthesis failed: {e!r}"))
+                if not r.fut.done():
+                    r.fut.set_exception(RuntimeError(f"Speech synthesis failed: {e!r}"))
                 if not isinstance(e, Exception):          # the stage is going down: nothing taken off the queue may be left pending
                     for later in reqs[k + 1:]:
-                        later[4].set_exception(RuntimeError(f"Speech synthesis failed: {e!r}"))
+                        later.fut.set_exception(RuntimeError(f"Speech synthesis failed: {e!r}"))
                     self._fail(batch, e)
                     raise
         return batch
@@ -237,7 +217,7 @@ class BatchingFrontend:
     @staticmethod
     def _fail(batch: Optional[_Batch], err) -> None:
         if batch is not None:
-            for fut, _n in batch.plans:
+            for fut, _n, _o in batch.reqs:
                 if not fut.done():
                     fut.set_exception(RuntimeError(f"Speech synthesis failed: {err}"))
 
@@ -277,7 +257,7 @@ class BatchingFrontend:
                     break
                 except queue.Full:
                     pass
-                if batch.n_req < self.max_requests and not self._closing:
+                if len(batch.reqs) < self.max_requests and not self._closing:
                     try:
                         nxt = self._q.get(timeout=0.002)
                     except queue.Empty:
@@ -293,8 +273,8 @@ class BatchingFrontend:
                 req = self._q.get_nowait()
             except queue.Empty:
                 return
-            if req is not None and not req[4].done():
-                req[4].set_exception(RuntimeError(f"Speech synthesis failed: {err}"))
+            if req is not None and not req.fut.done():
+                req.fut.set_exception(RuntimeError(f"Speech synthesis failed: {err}"))
 
     # ------------------------------------------------------------------ stage 2: the GPU
     def _run_batch(self, batch: _Batch):
@@ -302,17 +282,10 @@ class BatchingFrontend:
         t0 = time.perf_counter()
         with eng._lock:
             if eng.model_session_manager.engine is not None:
-                own = next((v for v in batch.louds if v is not None), None)      # N12: a request's own target takes the device stage too
-                own_lim = next((v for v in batch.lims if v is not None), None)      # N13: and so does a request's own limiter
-                own_pros = next((v for v in batch.pitches + batch.tempos if v is not None), None)      # N14: and its own pitch or tempo
-                own_den = next((v for v in batch.denoises if v is not None), None)      # N19: and its own denoiser strength
-                dev_out = eng._device_output(own, own_lim, own_pros, own_den)      # N10: the chunks stay in HBM, _finish joins every request of the batch in one call
-                if batch.keys:
-                    waves = eng._synthesize_device(batch.flat, noise_keys=np.stack(batch.keys), cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
-                                                   device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
-                else:
-                    waves = eng._synthesize_device(batch.flat, noise_blocks=batch.blocks, cfg_strengths=batch.cfgs, cfg_intervals=batch.ivals,
-                                                   device_out=dev_out, apg_etas=batch.etas, apg_norms=batch.norms)
+                # N10: a request's own output option takes the device stage too: the chunks stay in HBM, _finish joins the whole batch in one call
+                dev_out = eng._device_output([o for _f, _n, o in batch.reqs])
+                noise = {"noise_keys": np.stack(batch.keys)} if batch.keys else {"noise_blocks": batch.blocks}
+                waves = eng._synthesize_device(batch.flat, options=[o for _f, n, o in batch.reqs for _chunk in range(n)], device_out=dev_out, **noise)
             else:
                 waves = eng._synthesize_sessions(batch.flat)      # CPU plumbing tests: the oracle sessions draw their own noise
         self.gpu_busy_s += time.perf_counter() - t0
@@ -340,29 +313,22 @@ class BatchingFrontend:
     def _finish(self, batch: _Batch, waves, err) -> None:
         eng = self.engine
         if err is not None:
-            for fut, _n in batch.plans:
-                if not fut.done():
-                    fut.set_exception(RuntimeError(f"Speech synthesis failed: {err}"))
+            self._fail(batch, err)
             return
         if isinstance(waves, tuple):          # device output stage: (device PCM, spans) -- one finish_output call for the whole batch
             try:
-                finals = eng._finish_device(waves, [n for _f, n in batch.plans], loudness=batch.louds, limiter=batch.lims,
-                                            pitch=batch.pitches, tempo=batch.tempos,
-                                            **({} if all(v is None for v in batch.formants) else {"formants": batch.formants}),
-                                            **({} if all(v is None for v in batch.denoises) else {"denoise": batch.denoises}))
+                finals = eng._finish_device(waves, [n for _f, n, _o in batch.reqs], [o for _f, _n, o in batch.reqs])
             except Exception as e:        # noqa: BLE001
                 self._fail(batch, e)
                 return
-            for (fut, _n), final in zip(batch.plans, finals):
+            for (fut, _n, _o), final in zip(batch.reqs, finals):
                 fut.set_result((final, time.time() - batch.t0))
                 self.requests_done += 1
             return
         pos = 0
-        for (fut, n), loud, lim, pit, tem, fmt, den in zip(batch.plans, batch.louds, batch.lims, batch.pitches, batch.tempos, batch.formants, batch.denoises):
+        for fut, n, options in batch.reqs:
             try:
-                final = eng._finish_host(waves[pos: pos + n], loudness=loud, limiter=lim, pitch=pit, tempo=tem, **({} if fmt is None else {"formants": fmt}),
-                                         **({} if den is None else {"denoise": den}))
-                fut.set_result((final, time.time() - batch.t0))
+                fut.set_result((eng._finish_host(waves[pos: pos + n], options), time.time() - batch.t0))
             except Exception as e:        # noqa: BLE001
                 fut.set_exception(RuntimeError(f"Speech synthesis failed: {e}"))
             pos += n

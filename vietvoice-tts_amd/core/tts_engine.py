@@ -28,6 +28,7 @@ from .audio_processor import AudioProcessor
 from .model import ModelSessionManager
 from .model_config import ModelConfig
 from .text_processor import TextProcessor
+from ..request_options import RequestOptions, column
 
 logger = logging.getLogger("vietvoicetts")
 
@@ -162,25 +163,22 @@ class TTSEngine:
         rate = cfg.output_sample_rate
         return (None if rate is None or int(rate) == int(cfg.sample_rate) else int(rate)), cfg.output_encoding
 
-    def _flac_options(self, key: str = "lpc_order") -> dict:
-        """N16: {key: flac_lpc_order} when LPC subframes are asked for, else nothing: the calls of N15 as they were."""
-        return {key: self.config.flac_lpc_order} if self.config.flac_lpc_order else {}
-
     @property
     def output_rate(self) -> int:
         return self._output_options()[0] or self.config.sample_rate
 
-    def _device_output(self, loudness=None, limiter=None, prosody=None, denoise=None) -> bool:
+    def _resolved(self, options, n: int) -> List[RequestOptions]:
+        """``n`` requests' RequestOptions (None = none has any) with the engine's value in every field they leave open."""
+        return [(o or RequestOptions()).resolved(self.config) for o in options or [None] * n]
+
+    def _device_output(self, options=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate, an encoding, a loudness target, a limiter, a pitch, a tempo or a denoiser strength (the engine's, or a request's own:
-        ``loudness``, ``limiter``, ``prosody``, ``denoise``) is set.  False = today's path: one copy per chunk group, the numpy join."""
+        rate, an encoding, a loudness target, a limiter, a pitch, a tempo or a denoiser strength is set: the engine's, or the own one of
+        a request of ``options`` (the batch's RequestOptions).  False = today's path: one copy per chunk group, the numpy join."""
         rate, enc = self._output_options()
-        return self.model_session_manager.engine is not None and (self.config.output_stage == "device" or rate is not None or enc != "pcm16"
-                                                                  or self.config.output_loudness is not None or loudness is not None
-                                                                  or self.config.output_limiter is not None or limiter is not None
-                                                                  or self.config.output_pitch is not None or self.config.output_tempo is not None
-                                                                  or prosody is not None
-                                                                  or self.config.output_denoise is not None or denoise is not None)
+        return self.model_session_manager.engine is not None and (
+            self.config.output_stage == "device" or rate is not None or enc != "pcm16"
+            or any(o.wants_output_stage() for o in self._resolved(options, 1)))
 
     def _denoise_bias_host(self) -> np.ndarray:
         """The bias profile the host mirror subtracts (N19): the caller's ``output_denoise_bias``, else the model's own, which only a HIP
@@ -193,76 +191,53 @@ class TTSEngine:
                              "empty mel; give output_denoise_bias, or unset output_denoise")
         return eng.vocoder_bias()[0].cpu().numpy()
 
-    def _finish_host(self, waves, loudness=None, limiter=None, pitch=None, tempo=None, formants=None, denoise=None) -> np.ndarray:
-        """One request's chunks -> its final audio on the host: the reference's join, the denoiser's mirror directly behind it (N19;
-        ``denoise`` = the request's own strength, None = the engine's), then the host mirrors of pitch and tempo (N14;
-        ``pitch`` / ``tempo`` = the request's own, None = the engine's), the loudness normalisation (N12; ``loudness`` likewise), the
-        limiter (N13; ``limiter`` likewise), the output rate and the encoding."""
+    def _finish_host(self, waves, options: Optional[RequestOptions] = None) -> np.ndarray:
+        """One request's chunks -> its final audio on the host: the reference's join, the denoiser's mirror directly behind it (N19), then
+        the host mirrors of pitch and tempo (N14, N18), the loudness normalisation (N12), the limiter (N13), the output rate and the
+        encoding.  ``options`` = the request's own values, None (or a None field) = the engine's."""
         from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output, shift_prosody
-        final = self.audio_processor.concatenate_with_crossfade_improved(waves, self.config.cross_fade_duration, self.config.sample_rate)
-        denoise = self.config.output_denoise if denoise is None else denoise
-        if denoise is not None:
+        cfg, (o,) = self.config, self._resolved([options], 1)
+        final = self.audio_processor.concatenate_with_crossfade_improved(waves, cfg.cross_fade_duration, cfg.sample_rate)
+        pcm16 = lambda a: np.ascontiguousarray(a, dtype=np.int16)  # noqa: E731
+        if o.denoise is not None:
             from .audio_processor import denoise_pcm
-            final = denoise_pcm(np.ascontiguousarray(final, dtype=np.int16), self._denoise_bias_host(), denoise)
-        pitch = self.config.output_pitch if pitch is None else pitch
-        tempo = self.config.output_tempo if tempo is None else tempo
-        if pitch is not None or tempo is not None:
-            keep = (self.config.output_formants if formants is None else formants) == "keep"      # N18; "shift": the call of N14
-            final = shift_prosody(np.ascontiguousarray(final, dtype=np.int16), pitch, tempo, **({"formants": "keep"} if keep else {}))
-        loudness = self.config.output_loudness if loudness is None else loudness
-        limiter = self.config.output_limiter if limiter is None else limiter
-        if loudness is not None:
-            final = normalize_loudness(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, loudness, self.config.output_peak_dbfs,
-                                       **({} if limiter is None else {"limiter": limiter}))
-        elif limiter is not None:
-            final = limit_peaks(np.ascontiguousarray(final, dtype=np.int16), self.config.sample_rate, self.config.output_peak_dbfs, limiter)[0]
+            final = denoise_pcm(pcm16(final), self._denoise_bias_host(), o.denoise)
+        if o.pitch is not None or o.tempo is not None:
+            final = shift_prosody(pcm16(final), o.pitch, o.tempo, formants=o.formants)
+        if o.loudness is not None:
+            final = normalize_loudness(pcm16(final), cfg.sample_rate, o.loudness, cfg.output_peak_dbfs, limiter=o.limiter)
+        elif o.limiter is not None:
+            final = limit_peaks(pcm16(final), cfg.sample_rate, cfg.output_peak_dbfs, o.limiter)[0]
         rate, enc = self._output_options()
         if rate is not None:
-            final = resample_output(final, self.config.sample_rate, rate)
-        return encode_output(final, enc, self.output_rate, **self._flac_options()) if enc != "pcm16" else final
+            final = resample_output(final, cfg.sample_rate, rate)
+        return encode_output(final, enc, self.output_rate, lpc_order=cfg.flac_lpc_order) if enc != "pcm16" else final
 
-    def _denoise_options(self, own=None, R: int = 1) -> dict:
-        """finish_output's ``denoise`` / ``denoise_bias`` (N19): nothing when no request has a strength -- the call of N18 as it was."""
-        mine = self.config.output_denoise
-        vals = [mine] * R if own is None else [mine if v is None else v for v in own]
-        if all(v is None for v in vals):
-            return {}
-        bias = self.config.output_denoise_bias
-        return {"denoise": vals, **({} if bias is None else {"denoise_bias": bias})}
-
-    def _finish_device(self, dev_pcm, counts, loudness=None, limiter=None, pitch=None, tempo=None, formants=None, denoise=None) -> List[np.ndarray]:
+    def _finish_device(self, dev_pcm, counts, options: Optional[List[RequestOptions]] = None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
-        one HipSynth.finish_output call (join, prosody, loudness, rate, encoding in HBM; one device-to-host copy).  ``loudness`` = per
-        request its own target or None (= the engine's); ``limiter`` (N13), ``pitch`` and ``tempo`` (N14), ``formants`` (N18) and ``denoise``
-        (N19) likewise."""
+        one HipSynth.finish_output call (join, denoiser, prosody, loudness, limiter, rate, encoding in HBM; one device-to-host copy).
+        ``options`` = per request its own values, None (or a None field) = the engine's.  finish_output reads a column that is None for
+        every request as "off" and calls nothing for it."""
         pcm, spans = dev_pcm
         plans, pos = [], 0
         for n in counts:
             plans.append(spans[pos: pos + n])
             pos += n
+        cfg = self.config
+        opts = self._resolved(options, len(counts))
         rate, enc = self._output_options()
-        loud = self.config.output_loudness
-        if loudness is not None:
-            loud = [loud if v is None else v for v in loudness]
-        lim = self.config.output_limiter
-        if limiter is not None:
-            lim = [lim if v is None else v for v in limiter]
-            if all(v is None for v in lim):
-                lim = None
-        opts = self._flac_options("flac_lpc_order")
-        for key, own, mine in (("pitch", pitch, self.config.output_pitch), ("tempo", tempo, self.config.output_tempo)):
-            vals = [mine] * len(counts) if own is None else [mine if v is None else v for v in own]
-            if any(v is not None for v in vals):           # no pitch and no tempo anywhere: exactly the call of N13
-                opts[key] = vals
-        keep = [self.config.output_formants] * len(counts) if formants is None else [self.config.output_formants if v is None else v for v in formants]
-        if "keep" in keep and "pitch" in opts:             # "shift" everywhere, or no pitch anywhere: exactly the call of N14
-            opts["formants"] = keep
-        opts.update(self._denoise_options(denoise, len(counts)))
-        return self.model_session_manager.engine.finish_output(pcm, plans, self.config.cross_fade_duration, self.config.sample_rate, rate, enc,
-                                                               loudness=loud, peak_dbfs=self.config.output_peak_dbfs, limiter=lim, **opts)
+        return self.model_session_manager.engine.finish_output(
+            pcm, plans, cfg.cross_fade_duration, cfg.sample_rate, rate, enc, peak_dbfs=cfg.output_peak_dbfs, flac_lpc_order=cfg.flac_lpc_order,
+            denoise_bias=cfg.output_denoise_bias, **{name: column(opts, name) for name in ("loudness", "limiter", "pitch", "tempo", "formants", "denoise")})
 
-    def _synthesize_device(self, inputs_list, noise_blocks=None, cfg_strengths=None, cfg_intervals=None, noise_keys=None, device_out: bool = False,
-                           apg_etas=None, apg_norms=None):
+    def _set_ode_plan(self) -> None:
+        """The solver and its step report as the config has them now (the report is off while the plan changes under it)."""
+        eng = self.model_session_manager.engine
+        eng.set_ode_report(False)
+        eng.set_nfe(self.config.nfe_step, self.config.ode_method)
+        eng.set_ode_report(self.config.ode_report)
+
+    def _synthesize_device(self, inputs_list, noise_blocks=None, noise_keys=None, device_out: bool = False, options=None):
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
         clips may differ per item (cross-request batches).  One ragged GPU batch per ``max_batch_chunks`` items.
         noise_blocks: optional pre-drawn (N_i, n_mel) fp32 tensors, one per item (the batching front end draws them from
@@ -270,28 +245,21 @@ class TTSEngine:
         noise_keys (N9, ``noise_source="device"``): uint64 [n_items][2] Philox key rows (model_spec.noise_keys), one per item: the noise is
         drawn in HBM by vv_noise_fill, no host tensor is built and none is uploaded.  Default with that source = a call of its own (the
         next call serial); explicit noise_blocks still win.
-        cfg_strengths: optional guidance strength per item (None entries = ``config.cfg_strength``, which None leaves to the model).
-        cfg_intervals: optional guidance interval (lo, hi) per item (None entries = ``config.cfg_interval``).  An item is guided at the
-        evaluations inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed.
-        apg_etas / apg_norms: optional projected guidance per item (None entries = ``config.apg_eta`` / ``config.apg_norm``); items with
-        neither keep the plain combine, in the same batch.
+        options: optional RequestOptions per item (None, a None entry or a None field = the engine's value), read for the acoustic stage:
+        ``cfg_strength`` (None in the config as well leaves it to the model); ``cfg_interval`` (lo, hi): an item is guided at the evaluations
+        inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed; ``apg_eta`` /
+        ``apg_norm``: items with neither keep the plain combine, in the same batch.
         device_out (N10): nothing is copied to the host; returns (int16 device tensor, [(offset, samples) per item]) -- the planes of the
         chunk groups back to back and each item's span in them, the lengths from the host's own frame counts (no readback)."""
         import torch
         m = self.model_session_manager
         eng, spec = m.engine, m.spec
         dev = eng.device
-        eng.set_ode_report(False)                # the plan may change under it; back on below when the config asks for it
-        eng.set_nfe(self.config.nfe_step, self.config.ode_method)
-        eng.set_ode_report(self.config.ode_report)
+        self._set_ode_plan()
         self.last_ode_report = []
         hop = self.config.hop_length
-        g_all = [self.config.cfg_strength] * len(inputs_list) if cfg_strengths is None else \
-            [self.config.cfg_strength if v is None else float(v) for v in cfg_strengths]
-        iv_all = [self.config.cfg_interval] * len(inputs_list) if cfg_intervals is None else \
-            [self.config.cfg_interval if v is None else v for v in cfg_intervals]
-        eta_all = [self.config.apg_eta] * len(inputs_list) if apg_etas is None else [self.config.apg_eta if v is None else v for v in apg_etas]
-        norm_all = [self.config.apg_norm] * len(inputs_list) if apg_norms is None else [self.config.apg_norm if v is None else v for v in apg_norms]
+        opts = self._resolved(options, len(inputs_list))
+        g_all, iv_all, eta_all, norm_all = ([getattr(o, name) for o in opts] for name in ("cfg_strength", "cfg_interval", "apg_eta", "apg_norm"))
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
@@ -457,31 +425,29 @@ class TTSEngine:
                 # device noise: ONE call serial for the whole stream, chunk c under it whatever group it is synthesised in
                 keys = self.model_session_manager.take_noise_keys(len(inputs_list)) if self._device_noise() else None
             self._last_plan = [int(i[2][0]) for i in inputs_list]
-            from .audio_processor import CrossfadeStream
-            joiner = CrossfadeStream(len(inputs_list), self.config.cross_fade_duration, self.config.sample_rate)
-            # N10: a rate or an encoding is applied to every final block by an OutputStream that carries the filter's position and history
-            # (on the HIP engine through the device kernels, blocks re-uploaded), so that the blocks still add up to synthesize()'s result
+            from .audio_processor import CrossfadeStream, FlacStream, LimiterStream, OutputStream
+            cfg, eng = self.config, self.model_session_manager.engine
+            joiner = CrossfadeStream(len(inputs_list), cfg.cross_fade_duration, cfg.sample_rate)
+            # The stages behind the join, in order; each carries the state it needs (on the HIP engine its back end is the device kernel,
+            # blocks re-uploaded), so that the blocks still add up to synthesize()'s result
             rate, enc = self._output_options()
-            ostream = fstream = None
-            if enc == "flac":                  # N15: frames are independent, so FLAC streams -- a FlacStream behind the rate conversion
-                from .audio_processor import FlacStream, OutputStream
-                eng = self.model_session_manager.engine
-                backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
-                if rate is not None:
-                    ostream = OutputStream(self.config.sample_rate, rate, "pcm16", backends[0], None)
-                fstream = FlacStream(self.output_rate, backends[1], **self._flac_options())
-            elif rate is not None or enc != "pcm16":
-                from .audio_processor import OutputStream
-                eng = self.model_session_manager.engine
-                backends = eng.output_stream_backends(self.config.sample_rate, rate, enc) if eng is not None else (None, None)
-                ostream = OutputStream(self.config.sample_rate, rate, enc, *backends)
-            lstream = None
-            if self.config.output_limiter is not None:            # N13: finite look-ahead, so the blocks still add up to synthesize()'s result
-                from .audio_processor import LimiterStream
-                eng = self.model_session_manager.engine
-                lstream = LimiterStream(self.config.sample_rate, self.config.output_peak_dbfs, self.config.output_limiter,
-                                        None if eng is None else eng.limiter_stream_backend(self.config.sample_rate, self.config.output_peak_dbfs,
-                                                                                            self.config.output_limiter))
+            stages = []
+            if cfg.output_limiter is not None:                 # N13: finite look-ahead
+                backend = None if eng is None else eng.limiter_stream_backend(cfg.sample_rate, cfg.output_peak_dbfs, cfg.output_limiter)
+                stages.append(LimiterStream(cfg.sample_rate, cfg.output_peak_dbfs, cfg.output_limiter, backend))
+            if rate is not None or enc != "pcm16":             # N10: the filter's position and history
+                resample, encode = eng.output_stream_backends(cfg.sample_rate, rate, enc) if eng is not None else (None, None)
+                if enc != "flac":
+                    stages.append(OutputStream(cfg.sample_rate, rate, enc, resample, encode))
+                else:                                          # N15: frames are independent -- a FlacStream behind the rate conversion
+                    if rate is not None:
+                        stages.append(OutputStream(cfg.sample_rate, rate, "pcm16", resample, None))
+                    stages.append(FlacStream(self.output_rate, encode, lpc_order=cfg.flac_lpc_order))
+
+            def through(block, stages):                        # handed over as contiguous int16, which PCM blocks are already
+                for stage in stages:
+                    block = stage.push(np.ascontiguousarray(block, dtype=np.int16))
+                return block
             step = max(1, int(chunks_per_step))
             for lo in range(0, len(inputs_list), step):
                 with self._lock:
@@ -490,31 +456,11 @@ class TTSEngine:
                     else:
                         waves = self._synthesize_sessions(inputs_list[lo: lo + step])
                 blocks = [joiner.push(w) for w in waves]
-                block = np.concatenate(blocks) if len(blocks) > 1 else blocks[0]
-                if lstream is not None:
-                    block = lstream.push(np.ascontiguousarray(block, dtype=np.int16))
-                if ostream is not None:
-                    block = ostream.push(block)
-                if fstream is not None:
-                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
+                block = through(np.concatenate(blocks) if len(blocks) > 1 else blocks[0], stages)
                 if block.size:
                     yield block
-            if lstream is not None:
-                block = lstream.flush()
-                if ostream is not None:
-                    block = ostream.push(block)
-                if fstream is not None:
-                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
-                if block.size:
-                    yield block
-            if ostream is not None:
-                block = ostream.flush()
-                if fstream is not None:
-                    block = fstream.push(np.ascontiguousarray(block, dtype=np.int16))
-                if block.size:
-                    yield block
-            if fstream is not None:
-                block = fstream.flush()
+            for k, stage in enumerate(stages):                 # a stage's tail goes through the stages behind it, which are flushed in turn
+                block = through(stage.flush(), stages[k + 1:])
                 if block.size:
                     yield block
         except Exception as e:
@@ -560,9 +506,7 @@ class TTSEngine:
             ids = self.text_processor.text_to_indices([list(clean)])
             try:
                 dev = eng.device
-                eng.set_ode_report(False)
-                eng.set_nfe(cfg.nfe_step, cfg.ode_method)
-                eng.set_ode_report(cfg.ode_report)
+                self._set_ode_plan()
                 g_item = None if cfg.cfg_strength is None else torch.full((1,), float(cfg.cfg_strength), dtype=torch.float32, device=dev)
                 _x, pcm, n_out = eng.edit_batch(entry.pcm_dev, plan.rows(), [plan.spliced_len],
                                                torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(dev),
@@ -574,13 +518,7 @@ class TTSEngine:
                 self.last_ode_report = [eng.last_ode_report()] if cfg.ode_report else []
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
-                    wave = eng.finish_output(pcm[0], [[(0, n_host)]], cfg.cross_fade_duration, sr, *self._output_options(),
-                                             loudness=cfg.output_loudness, peak_dbfs=cfg.output_peak_dbfs,
-                                             **({} if cfg.output_limiter is None else {"limiter": cfg.output_limiter}),
-                                             **({} if cfg.output_pitch is None and cfg.output_tempo is None
-                                                else {"pitch": cfg.output_pitch, "tempo": cfg.output_tempo}),
-                                             **({"formants": "keep"} if cfg.output_formants == "keep" and cfg.output_pitch is not None else {}),
-                                             **self._denoise_options(), **self._flac_options("flac_lpc_order"))[0]
+                    wave = self._finish_device((pcm[0], [(0, n_host)]), [1])[0]      # one request of one span, the engine's options
                 else:
                     wave = pcm[0, : int(n_out[0])].cpu().numpy()      # the spliced length (HiFi-GAN); hop * (N - 1) <= it (Vocos)
             except Exception as e:

@@ -1,0 +1,57 @@
+"""What one request may ask for beside its text, speed and voice: one record from ``BatchingFrontend.submit`` to the stage that consumes
+each value.  A new per-request option is a field here, its check in ``checked``, and its use in that one stage."""
+from __future__ import annotations
+
+from dataclasses import dataclass, replace
+from typing import List, Optional, Tuple
+
+
+@dataclass(frozen=True)
+class RequestOptions:
+    """None = the engine's value (``resolved``)."""
+    cfg_strength: Optional[float] = None                   # the acoustic stage, per chunk (N7)
+    cfg_interval: Optional[Tuple[float, float]] = None     # (N8)
+    apg_eta: Optional[float] = None                        # (N11)
+    apg_norm: Optional[float] = None
+    loudness: Optional[float] = None                       # the output stage, per request (N12)
+    limiter: Optional[str] = None                          # (N13)
+    pitch: Optional[float] = None                          # (N14)
+    tempo: Optional[float] = None
+    formants: Optional[str] = None                         # (N18)
+    denoise: Optional[float] = None                        # (N19)
+
+    @classmethod
+    def checked(cls, cfg_strength=None, cfg_interval=None, apg_eta=None, apg_norm=None, loudness=None, limiter=None, pitch=None, tempo=None,
+                formants=None, denoise=None) -> "RequestOptions":
+        """The validated, normalised record; ValueError in the words of the option's own check, the first in this order."""
+        from .core.audio_processor import check_denoise, check_formants, check_limiter, check_loudness, check_prosody
+        from .model_spec import check_apg, check_cfg_interval
+        loudness, _pk = check_loudness(loudness)
+        check_limiter(limiter)
+        pitch, tempo = check_prosody(pitch, tempo)
+        formants = None if formants is None else check_formants(formants)
+        denoise = check_denoise(denoise)
+        cfg_interval = check_cfg_interval(cfg_interval)
+        check_apg(apg_eta, apg_norm)
+        apg_eta, apg_norm = (None if v is None else float(v) for v in (apg_eta, apg_norm))
+        if cfg_strength is not None:
+            cfg_strength = float(cfg_strength)
+            if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
+                raise ValueError("cfg_strength must be a finite number or None")
+        return cls(cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise)
+
+    def resolved(self, config) -> "RequestOptions":
+        """Every None replaced by the engine's value: the one place that says "own value, else the engine's"."""
+        mine = RequestOptions(config.cfg_strength, config.cfg_interval, config.apg_eta, config.apg_norm, config.output_loudness,
+                              config.output_limiter, config.output_pitch, config.output_tempo, config.output_formants, config.output_denoise)
+        return replace(mine, **{name: v for name, v in vars(self).items() if v is not None})
+
+    def wants_output_stage(self) -> bool:
+        """Some step behind the join is asked for: what ``TTSEngine._device_output`` asks of the requests."""
+        return any(v is not None for v in (self.loudness, self.limiter, self.pitch, self.tempo, self.denoise))
+
+
+def column(options: List[RequestOptions], name: str) -> Optional[list]:
+    """One field of every entry, or None when no entry has it."""
+    vals = [getattr(o, name) for o in options]
+    return None if all(v is None for v in vals) else vals
