@@ -262,6 +262,33 @@ VV_API int vv_transformer_steps_apg(vv_ctx* ctx, const vv_steps_args* args, cons
                                     void* stream);
 VV_API int vv_transformer_apg_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, uint64_t* bytes);
 
+/* N21 guidance reuse: vv_transformer_steps_guided with a THIRD mask value.  guide_host[e * ld_guide + b] is 0 = item b
+ * is not guided at evaluation e (N8), 1 = guided and p_u COMPUTED, 2 = guided and the guidance difference D = p_c - p_u REUSED: the item
+ * has no unconditional rows at that evaluation (exactly like an unguided one: per lane Rc + Ru_e rows, Ru_e the rows of the items with a
+ * 1) and its slope is p_c + D g_b with the D stored at the item's latest evaluation of the same call that had a 1 and the fresh p_c.  D
+ * lives in one [Rc][n_mel] fp32 buffer per lane of the call's workspace and does not outlive the call; it is stored only at evaluations
+ * some later one reads it from (or at every computed one under a report).  A computed row's arithmetic is N8's bit for bit.
+ * reuse (optional): report != NULL asks for the drift report, a caller-owned DEVICE array [n_evals][B][2] float64 with n_evals the
+ * evaluations of the plan in force and B the call's: row (e, b) of an evaluation of the call is {sum (D_new - D_stored)^2, sum D_new^2}
+ * over the item's valid frames and the n_mel columns where b is computed at e (the first sum 0 at its first computed evaluation of the
+ * call), {0, 0} where it reuses or is not guided; rows of evaluations outside the call are not written.  float64, deterministic,
+ * independent of the item's place in the batch (vv_cfg_drift_reduce); two small launches per evaluation and lane in front of the stage
+ * kernel's, none without a report.
+ * A mask without a 2 and no report: the call IS vv_transformer_steps_guided (same launches, same workspace).  Otherwise a caller-owned ws
+ * holds vv_transformer_reuse_ws_bytes bytes: the guided figure plus one D buffer per lane, plus the report's partial sums when
+ * with_report != 0 -- the same figure whatever the mask.  -22, nothing launched and the context left usable, for: a mask value above 2; a 2
+ * at an evaluation of the call for an item with no 1 at an earlier evaluation of the same call; a mask with a 2 and step0 != 0; a report
+ * whose report_B / report_evals are not the call's B and the plan's evaluations; and whatever vv_transformer_steps_guided refuses.  There
+ * is no reuse together with projected guidance (vv_transformer_steps_apg takes no such argument).  The mask reaches the device as kernel
+ * arguments: with host lengths the call does not synchronise and can be captured into a hipGraph. */
+typedef struct vv_reuse_args {
+    double* report;                   /* device [report_evals][report_B][2] float64, optional */
+    int32_t report_B, report_evals;
+} vv_reuse_args;
+VV_API int vv_transformer_steps_reuse(vv_ctx* ctx, const vv_steps_args* args, const uint8_t* guide_host, int ld_guide, const vv_reuse_args* reuse,
+                                      void* stream);
+VV_API int vv_transformer_reuse_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes);
+
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
  * that needs more bytes (vv_ws_generation counts those moves); a launch sequence captured into a hipGraph
@@ -558,6 +585,31 @@ typedef struct vv_ode_diff_args {
     double* partials; double* report;
 } vv_ode_diff_args;
 VV_API int vv_ode_diff_reduce(vv_ctx* ctx, const vv_ode_diff_args* args, void* stream);
+/* N21 single-kernel entries (unit parity).  vv_ode_stage_reuse: vv_ode_stage_guided where the guidance difference D = p_c - p_u (one fp32
+ * subtraction) of an ITEM can be kept in d_buf ([Rc][n_mel] fp32, packed rows, 16-byte aligned, a buffer of its own).  The mode of packed
+ * row r is that of its item row_src[r] / seq_n (or r / seq_n), item_mode_host[item] on the HOST (n_items of them, at most 1024; they travel
+ * as kernel arguments): VV_REUSE_LOAD -- where u_row[r] < 0 the row reads D from d_buf and k = p_c + D g (no row of pred holds its p_u);
+ * VV_REUSE_STORE -- where u_row[r] >= 0 the row's D is also written to d_buf.  A row with u_row[r] >= 0 is computed whatever LOAD says, a
+ * row with u_row[r] < 0 without LOAD is not guided (k = p_c).  Every mode 0: vv_ode_stage_guided bit for bit, and a computed row always is.
+ * reuse NULL: the call IS vv_ode_stage_guided.
+ * vv_cfg_drift_reduce: the sums of the drift report.  Item b owns the packed rows [row_start[b], + len[b]) (as vv_ode_diff_reduce).  Over
+ * its rows with u_row[r] >= 0: D_new = p_c - p_u (fp32, from pred rows r and u_row[r]); report [B][2] float64 = {sum (D_new - d_buf[r])^2,
+ * sum D_new^2}, the first sum 0 for an item whose has_old_host[b] (HOST [B], NULL = none) is 0 -- d_buf is not read for it.  Differences of
+ * the two, squares and sums in float64, a product and an add each (never fused), vv_ode_diff_reduce's tiles and order.  partials
+ * [B][n_tiles][2] float64 scratch. */
+#define VV_REUSE_LOAD 1
+#define VV_REUSE_STORE 2
+typedef struct vv_reuse_stage_args { float* d_buf; const uint8_t* item_mode_host; int32_t n_items; } vv_reuse_stage_args;
+VV_API int vv_ode_stage_reuse(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, const vv_reuse_stage_args* reuse, void* stream);
+typedef struct vv_cfg_drift_args {
+    const float* pred; int32_t ldp, Rc, n_mel;
+    const int32_t* u_row;
+    const float* d_buf; const uint8_t* has_old_host;
+    int32_t B, n_tiles;
+    const int32_t* row_start; const int32_t* len;
+    double* partials; double* report;
+} vv_cfg_drift_args;
+VV_API int vv_cfg_drift_reduce(vv_ctx* ctx, const vv_cfg_drift_args* args, void* stream);
 /* K9: x[r] += dt * (p_c + (p_c - p_u) * cfg) over n_mel columns, p_c = pred row r, p_u = pred row BN + r (ld ldp, fp32).  Refused with
  * -22 (nothing launched): n_mel or ldp not a multiple of 4, BN < 1, n_mel < 4, ldp < n_mel, x or pred NULL or not 16-byte aligned.
  * vv_cfg_euler_rows: the same update on packed rows -- x row row_src[r] (device [BN] int32, the caller keeps it inside x) takes pred rows r

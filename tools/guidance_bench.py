@@ -2,7 +2,8 @@
 """The guidance interval at full size, bf16, Euler on the 32-point grid: HipSynth.transformer_steps of the headline
 shape (B = 32, 256 tokens, N = 1600 frames per item) and of B = 1 under four configurations -- (a) unmasked, the path without a
 mask; (b) an all-ones mask (the same rows through the masked path); (c) an all-zero mask (no unconditional row anywhere); (d) the
-interval (0.25, 0.75).  (a) is run first AND last: the two bracket what the run itself drifts by.  Per configuration: ms per batch,
+interval (0.25, 0.75); and guidance reuse -- (e) reuse k = 2, 3, 4 over the whole grid, the unconditional branch at every
+k-th evaluation; (f) k = 2 inside the interval (0.25, 0.75).  (a) is run first AND last: the two bracket what the run itself drifts by.  Per configuration: ms per batch,
 ms per evaluation, the rows launched over the unmasked rows, and the time over the first (a).  Host clock around calls that end in
 a device synchronise; one warm-up call, then median (and min / max) of --reps.
 
@@ -27,7 +28,7 @@ from vietvoice_tts_amd.runtime import HipSynth  # noqa: E402
 
 SEED, REF_S, TOK, FRAMES = 9527, 6.0, 256, 1600            # the headline unit of bench.py: 6 s reference clip, 256 tokens, N = 1600 frames
 INTERVAL = (0.25, 0.75)
-CONFIGS = ["unmasked", "ones", "zeros", "interval", "unmasked"]
+CONFIGS = ["unmasked", "ones", "zeros", "interval", "reuse2", "reuse3", "reuse4", "interval_reuse2", "unmasked"]
 
 
 def timed(fn, reps):
@@ -48,7 +49,7 @@ def main():
     ap.add_argument("--batches", default="32,1")
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--nfe", type=int, default=32)
-    ap.add_argument("--configs", default="", help="unmasked,ones,zeros,interval in any order instead of the default list (start with unmasked)")
+    ap.add_argument("--configs", default="", help="unmasked,ones,zeros,interval,reuse2,reuse3,reuse4,interval_reuse2 in any order instead of the default list (start with unmasked)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "guidance_bench times the GPU path; there is nothing to measure without a HIP device"
@@ -69,7 +70,9 @@ def main():
         noise = torch.randn((B, N, spec.n_mel), generator=g).to(dev)
         x = torch.empty_like(noise)
         masks = {"unmasked": None, "ones": torch.ones((eng.n_evals, B), dtype=torch.uint8), "zeros": torch.zeros((eng.n_evals, B), dtype=torch.uint8),
-                 "interval": eng.guidance_mask(INTERVAL, [None] * B)}
+                 "interval": eng.guidance_mask(INTERVAL, [None] * B), "reuse2": eng.guidance_mask(None, [None] * B, 2),
+                 "reuse3": eng.guidance_mask(None, [None] * B, 3), "reuse4": eng.guidance_mask(None, [None] * B, 4),
+                 "interval_reuse2": eng.guidance_mask(INTERVAL, [None] * B, 2)}
         rows, base = [], None
         for name in configs:
             guide = masks[name]
@@ -79,7 +82,7 @@ def main():
                 eng.transformer_steps(x, pre, 0, eng.n_steps, guide=guide)
             ts = timed(run, a.reps)
             med = float(np.median(ts))
-            guided = eng.n_evals if guide is None else int(guide[:, 0].sum())
+            guided = eng.n_evals if guide is None else int((guide[:, 0] == 1).sum())      # evaluations with unconditional rows (a 2 reuses: none)
             row = {"config": name, "evaluations": eng.n_evals, "guided_evaluations": guided,
                    "rows_over_unmasked": round((eng.n_evals + guided) / (2.0 * eng.n_evals), 4),
                    "ms": round(med, 2), "ms_min": round(min(ts), 2), "ms_max": round(max(ts), 2), "ms_per_eval": round(med / eng.n_evals, 4),

@@ -74,6 +74,12 @@ class ModelConfig:
     apg_eta: Optional[float] = None         # adaptive projected guidance (model_spec.check_apg): the factor on the part of the guidance difference
                                             # parallel to the conditional data estimate (0 removes it, 1 or None = plain CFG)
     apg_norm: Optional[float] = None        # ... and the cap on the RMS of the data-space guidance difference (None = no cap)
+    cfg_reuse: Optional[int] = None         # guidance reuse: the unconditional branch runs at every k-th guided evaluation of an item
+                                            # only; in between the stored guidance difference p_c - p_u is combined with the fresh p_c.  None or 1 =
+                                            # off (every guided evaluation computes both).  Not combined with apg_eta / apg_norm
+    cfg_reuse_report: bool = False          # N21, needs cfg_reuse > 1: per evaluation and item the sums (|D - D_stored|^2, |D|^2) of the guidance
+                                            # difference at the computed evaluations, reduced on the device -- how far it moved while it was reused
+                                            # (HipSynth.last_cfg_reuse_report, TTSEngine.last_cfg_reuse_report).  Off = nothing is launched or allocated
     noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
                                             # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
     output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
@@ -160,6 +166,13 @@ class ModelConfig:
         check_apg(self.apg_eta, self.apg_norm)                          # finite eta, finite norm > 0; both None (or eta 1) = plain CFG
         self.apg_eta = None if self.apg_eta is None else float(self.apg_eta)
         self.apg_norm = None if self.apg_norm is None else float(self.apg_norm)
+        from ..model_spec import check_cfg_reuse
+        self.cfg_reuse = check_cfg_reuse(self.cfg_reuse)               # an integer >= 1 or None; 1 = off
+        self.cfg_reuse_report = bool(self.cfg_reuse_report)
+        if (self.cfg_reuse or 1) > 1 and check_apg(self.apg_eta, self.apg_norm) is not None:
+            raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
+        if self.cfg_reuse_report and not (self.cfg_reuse or 1) > 1:
+            raise ValueError("cfg_reuse_report needs cfg_reuse > 1: it reports the drift of the reused guidance difference")
         self.validate_paths()
 
     @property

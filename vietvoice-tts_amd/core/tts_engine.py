@@ -50,6 +50,7 @@ class TTSEngine:
         self._lock = threading.Lock()
         self._decode_graphs = None               # DecodeGraphCache, created with the first captured decode (use_hip_graph)
         self._last_plan = []
+        self.last_cfg_reuse_report = []          # N21 (config.cfg_reuse_report): the drift reports of the last synthesis, float64 [n_evals, B, 2] per GPU batch
         self.last_ode_report = []                # N20 (config.ode_report): the step reports of the last synthesis, float64 [n_steps, B, 2] per GPU batch
 
     def cleanup(self) -> None:
@@ -236,6 +237,7 @@ class TTSEngine:
         eng.set_ode_report(False)
         eng.set_nfe(self.config.nfe_step, self.config.ode_method)
         eng.set_ode_report(self.config.ode_report)
+        eng.set_cfg_reuse_report(self.config.cfg_reuse_report)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, noise_keys=None, device_out: bool = False, options=None):
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
@@ -257,9 +259,16 @@ class TTSEngine:
         dev = eng.device
         self._set_ode_plan()
         self.last_ode_report = []
+        self.last_cfg_reuse_report = []
         hop = self.config.hop_length
         opts = self._resolved(options, len(inputs_list))
-        g_all, iv_all, eta_all, norm_all = ([getattr(o, name) for o in opts] for name in ("cfg_strength", "cfg_interval", "apg_eta", "apg_norm"))
+        g_all, iv_all, eta_all, norm_all, reuse_all = ([getattr(o, name) for o in opts]
+                                                       for name in ("cfg_strength", "cfg_interval", "apg_eta", "apg_norm", "cfg_reuse"))
+        from ..model_spec import check_apg
+        apg_on = [check_apg(e, r) is not None for e, r in zip(eta_all, norm_all)]
+        for k, on in zip(reuse_all, apg_on):
+            if (k or 1) > 1 and on:
+                raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
@@ -287,6 +296,11 @@ class TTSEngine:
                 cur.append(i)
                 rows += seq_all[i]
             groups.append(cur)
+        # N21: a call either reuses guidance differences or projects them (APG); items of the two kinds of one group run as two calls (every
+        # kernel of the path is row- or sequence-local, so an item's audio does not depend on which call it sits in)
+        groups = [part for idx in groups
+                  for part in (([[i for i in idx if (reuse_all[i] or 1) > 1], [i for i in idx if not (reuse_all[i] or 1) > 1]]
+                                if any(apg_on[i] for i in idx) and any((reuse_all[i] or 1) > 1 for i in idx) else [idx])) if part]
         for idx in groups:
             group = [inputs_list[i] for i in idx]
             B = len(group)
@@ -329,7 +343,7 @@ class TTSEngine:
             cfg = None                                   # per-item guidance strength: only when some item asks for one
             if any(g_all[j] is not None for j in idx):
                 cfg = torch.tensor([float(spec.cfg_strength) if g_all[j] is None else g_all[j] for j in idx], dtype=torch.float32).to(dev)
-            guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx])     # None: every item guided everywhere
+            guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx], [reuse_all[j] for j in idx])     # None: every item guided everywhere
             apg = eng.apg_tensors([eta_all[j] for j in idx], [norm_all[j] for j in idx])      # None: the plain combine for every item
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
@@ -345,6 +359,8 @@ class TTSEngine:
                                                               audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg)
             if self.config.ode_report:
                 self.last_ode_report.append(eng.last_ode_report())
+            if self.config.cfg_reuse_report:
+                self.last_cfg_reuse_report.append(eng.last_cfg_reuse_report())
             if device_out:
                 pcm = pcm.clone() if self.config.use_hip_graph else pcm.contiguous()      # a captured graph's output buffer is replayed over
                 for i, j in enumerate(idx):
@@ -513,9 +529,10 @@ class TTSEngine:
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
                                                torch.from_numpy(plan.keep.reshape(1, -1)).to(dev),
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
-                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength]), noise_keys=keys,
+                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength], cfg.cfg_reuse), noise_keys=keys,
                                                apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]))
                 self.last_ode_report = [eng.last_ode_report()] if cfg.ode_report else []
+                self.last_cfg_reuse_report = [eng.last_cfg_reuse_report()] if cfg.cfg_reuse_report else []
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = self._finish_device((pcm[0], [(0, n_host)]), [1])[0]      # one request of one span, the engine's options

@@ -1132,6 +1132,9 @@ struct Lane {
     // N20 (a multistep plan): the ring of kept slopes, f_m in slot m % ms_ring(c), [Rc][n_mel] fp32 each; the report's partial sums [B][n_tiles][2]
     float* hist[3] = {};
     double* rep_part = nullptr;
+    // N21 (a call that reuses guidance differences): the lane's stored D = p_c - p_u, [Rc][n_mel] fp32; the drift report's partial sums [B][n_tiles][2]
+    float* d_buf = nullptr;
+    double* drift_part = nullptr;
 };
 // N20: slots of the slope ring.  q - 1 without a report: the fresh slope takes the slot of the oldest one the step reads.  With a report
 // one more (two at the least), so that f_{n-1} outlives the stage launch of step n.
@@ -1151,14 +1154,22 @@ struct GuideState {
 // front of the stage kernel, on its stream.
 // ws_form, named by a size query: the workspace of a plain call, with the tables of a mask's subsets on top (whatever the mask), or with
 // APG's on top of those (with or without a mask).  A call with a mask or with APG implies its form.
-enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG };
+// N21: WS_REUSE / WS_REUSE_REPORT = the guided form plus a D buffer per lane, and the drift report's partial sums.
+enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG, WS_REUSE, WS_REUSE_REPORT };
 struct StepsCall {
     vv_steps_args a{};
     const uint8_t* guide = nullptr; int ld_guide = 0;
     const vv_apg_args* apg = nullptr;
+    // N21 (vv_transformer_steps_reuse): the mask may hold a 2 = "guided, the stored difference reused"; reuse->report asks for the drift report
+    bool reuse_entry = false; const vv_reuse_args* reuse = nullptr;
     WsForm ws_form = WS_PLAIN;
     uint64_t* ws_only = nullptr;       // a size query: only the workspace bytes of the call (nothing is launched; the data pointers may be null)
     bool guided = false, with_apg = false, rk = false;     // derived once, by transformer_steps
+    // N21, derived by transformer_steps: a D buffer is needed (the mask has a 2, or a report is asked for) / the report is on, and per
+    // evaluation of the call and item [(e - step0 * s) * B + b] the stage kernel's mode (VV_REUSE_LOAD | VV_REUSE_STORE) and "a D of this
+    // call is stored" in front of evaluation e
+    bool with_reuse = false, with_drift = false;
+    std::vector<uint8_t> ru_mode, ru_old;
 };
 struct StepDims { int D, FF, M, CD, es, KP, MP; };
 
@@ -1208,7 +1219,7 @@ LanePlan lane_plan(const vv_ctx* c, const StepDims& d, const std::vector<int>& h
 
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg) {
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg, bool reuse, bool drift) {
     const size_t R = L.R, es = d.es, D = d.D, FF = d.FF, M = d.M, KP = d.KP, MP = d.MP;
     L.xcat = a.take<char>(es * R * KP);
     L.h = a.take<char>(es * R * D); L.h2 = a.take<char>(es * R * D); L.h3 = a.take<char>(es * R * D);
@@ -1238,6 +1249,8 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, boo
         L.apg_coef = a.take<float>(2 * (size_t)L.B);
         if (c->ode_s > 1) L.xs2 = a.take<float>(L.Rc * M);
     }
+    if (reuse) L.d_buf = a.take<float>(L.Rc * M);  // N21: behind everything the guided form takes, so that form's offsets stay as they are
+    if (drift) L.drift_part = a.take<double>((size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2);
 }
 
 // The launches of one call, lane by lane: every member fills the arguments of its kernels for the Lane (or view of one) it is given and
@@ -1288,7 +1301,7 @@ struct StepsRun : StepDims {
         std::vector<uint8_t> f(L.B);
         size_t Ru = 0; int Bu = 0; double sq = 0;
         for (int b = 0; b < L.B; ++b) {
-            f[b] = row[b] ? 1 : 0;
+            f[b] = q.with_reuse ? row[b] == 1 : row[b] != 0;      // N21: only a COMPUTED item has unconditional rows; a reusing one is as an unguided one here
             if (f[b]) { Ru += hlen[L.b0 + b]; ++Bu; sq += (double)hlen[L.b0 + b] * hlen[L.b0 + b]; }
         }
         const bool first = G.flags.empty(), changed = first || f != G.flags;
@@ -1440,8 +1453,22 @@ struct StepsRun : StepDims {
             { Prof p(c, VV_PROF_ELEMWISE, 0, 24.0 * L.B * k.n_tiles, L.st); KCHK(c, vvk_apg_coef(&k, 2, L.st, &m__)); }
             sa.coef = L.apg_coef; sa.x_e = k.x_e; sa.x_e_packed = i ? 1 : 0; sa.t_e = k.t_e;
         }
-        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0)), L.st);
-        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__, c->ms_q ? 1 : 0));
+        vv_reuse_stage_args ra{};
+        if (q.with_reuse) {                              // N21: the items' modes at this evaluation; the drift sums before the stage kernel overwrites d_buf
+            const int e = s * ns + i;
+            const size_t at = (size_t)(e - q.a.step0 * ns) * q.a.B + L.b0;
+            ra.d_buf = L.d_buf; ra.item_mode_host = q.ru_mode.data() + at; ra.n_items = L.B;
+            if (q.with_drift) {
+                vv_cfg_drift_args r{};
+                r.pred = L.pred; r.ldp = MP; r.Rc = (int)L.Rc; r.n_mel = M; r.u_row = u_row; r.d_buf = L.d_buf; r.has_old_host = q.ru_old.data() + at;
+                r.B = L.B; r.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; r.row_start = L.row_start; r.len = L.kv_len;
+                r.partials = L.drift_part; r.report = q.reuse->report + ((size_t)e * q.a.B + L.b0) * 2;
+                { Prof p2(c, VV_PROF_ELEMWISE, 6.0 * L.Rc * M, 12.0 * L.Rc * M, L.st); KCHK(c, vvk_cfg_drift_reduce(&r, 1, L.st, &m__)); }
+                { Prof p2(c, VV_PROF_ELEMWISE, 0, 16.0 * L.B * r.n_tiles, L.st); KCHK(c, vvk_cfg_drift_reduce(&r, 2, L.st, &m__)); }
+            }
+        }
+        Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0) + (q.with_reuse ? 1 : 0)), L.st);
+        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__, c->ms_q ? 1 : 0, q.with_reuse ? &ra : nullptr));
         if (c->ms_q && c->ode_report) {                  // N20: the step report, from the slope just stored and the one before it
             vv_ode_diff_args r{};
             r.f = L.hist[s % ring]; r.f_prev = s ? L.hist[(s - 1) % ring] : nullptr; r.Rc = (int)L.Rc; r.n_mel = M;
@@ -1558,6 +1585,40 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
     if (q.guide && q.ld_guide < B) return c->fail(-22, "vv_transformer_steps_guided: ld_guide = %d < B = %d", q.ld_guide, B);
     if (q.guide && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_guided: a guidance mask cannot be combined with option split_k_tail (its tail plan depends on the row count)");
     if (q.guided && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_guided: at most %d items per call", VVK_GUIDE_MAX_ITEMS);
+    q.with_drift = q.ws_form == WS_REUSE_REPORT || (q.reuse && q.reuse->report); q.with_reuse = q.with_drift || q.ws_form == WS_REUSE;
+    if (q.reuse_entry && !q.ws_only) {                    // N21: the mask's values, and what the stage kernel does for each item at each evaluation of the call
+        const int E = c->n_steps * c->ode_s, ns = c->ode_s, e0 = a.step0 * ns, e1 = (a.step0 + a.n_steps) * ns;
+        if (q.with_drift && !q.guide) return c->fail(-22, "vv_transformer_steps_reuse: the drift report needs a mask");
+        if (q.with_drift && ((uintptr_t)q.reuse->report % 8 || q.reuse->report_B != B || q.reuse->report_evals != E))
+            return c->fail(-22, "vv_transformer_steps_reuse: the report is float64 [%d evaluations of the plan][%d items][2], got [%d][%d][2]", E, B, q.reuse->report_evals, q.reuse->report_B);
+        bool has2 = false;
+        for (int e = 0; e < E && q.guide; ++e)
+            for (int b = 0; b < B; ++b) {
+                const uint8_t v = q.guide[(size_t)e * q.ld_guide + b];
+                if (v > 2) return c->fail(-22, "vv_transformer_steps_reuse: mask value %d at evaluation %d, item %d (0 = not guided, 1 = computed, 2 = reused)", (int)v, e, b);
+                has2 = has2 || v == 2;
+            }
+        if (has2 && a.step0 != 0) return c->fail(-22, "vv_transformer_steps_reuse: a call that reuses starts at step 0 (the stored differences live for one call), got step0 = %d", a.step0);
+        q.with_reuse = q.with_reuse || has2;
+        if (q.with_reuse) {
+            q.ru_mode.assign((size_t)(e1 - e0) * B, 0); q.ru_old.assign((size_t)(e1 - e0) * B, 0);
+            for (int b = 0; b < B; ++b) {
+                bool seen = false, need = false;
+                for (int e = e0; e < e1; ++e) {
+                    const uint8_t v = q.guide[(size_t)e * q.ld_guide + b];
+                    if (v == 2 && !seen) return c->fail(-22, "vv_transformer_steps_reuse: item %d reuses at evaluation %d with no computed evaluation before it in the call", b, e);
+                    q.ru_old[(size_t)(e - e0) * B + b] = seen;
+                    if (v == 2) q.ru_mode[(size_t)(e - e0) * B + b] = VV_REUSE_LOAD;
+                    seen = seen || v == 1;
+                }
+                for (int e = e1 - 1; e >= e0; --e) {     // D is stored where a later evaluation reads it (at every computed one under a report)
+                    const uint8_t v = q.guide[(size_t)e * q.ld_guide + b];
+                    if (v == 2) need = true;
+                    if (v == 1) { if (need || q.with_drift) q.ru_mode[(size_t)(e - e0) * B + b] = VV_REUSE_STORE; need = false; }
+                }
+            }
+        }
+    }
     hipStream_t st = enter(c, stream);
     const vv_model_cfg& g = c->cfg;
     const StepDims d{g.dim, g.dim * g.ff_mult, g.n_mel, g.n_mel + g.text_dim, c->esz(), pad_to(2 * g.n_mel + g.text_dim, 64), pad_to(g.n_mel, 128)};
@@ -1582,7 +1643,7 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
         return c->fail(-22, "vv_transformer_steps: %zu packed rows make a %zu-byte qkv buffer; kernels address it with 32-bit byte offsets "
                             "(< 2 GiB) -- synthesise fewer units per call", 2 * Rc_all, 2 * Rc_all * 3 * (size_t)d.D * d.es);
     LanePlan P = lane_plan(c, d, hlen, N);
-    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg); };
+    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg, q.with_reuse, q.with_drift); };
     if (q.ws_only) { *q.ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
     if (int r = plan_ws(c, a.ws, (size_t)a.ws_bytes, bufs)) return r;
     for (int li = 0; li < P.n_lanes; ++li) {              // each lane's slice of the call's arrays
@@ -1673,6 +1734,21 @@ int vv_transformer_steps_apg(vv_ctx* c, const vv_steps_args* a, const uint8_t* g
 
 int vv_transformer_apg_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
     return steps_ws_query(c, "vv_transformer_apg_ws_bytes", WS_APG, B, N, seq_len_host, bytes);
+}
+
+// N21: a third mask value on top of vv_transformer_steps_guided (include/vvtts.h)
+int vv_transformer_steps_reuse(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, const vv_reuse_args* reuse, void* stream) {
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_reuse: null arguments");
+    if (!guide_host && !(reuse && reuse->report)) return vv_transformer_steps_ex(c, a, stream);
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_reuse: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_reuse: cfg_item must be a float array");
+    StepsCall q; q.a = *a; q.guide = guide_host; q.ld_guide = ld_guide; q.reuse_entry = true; q.reuse = reuse;
+    return transformer_steps(c, q, stream);
+}
+
+int vv_transformer_reuse_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes) {
+    return steps_ws_query(c, "vv_transformer_reuse_ws_bytes", with_report ? WS_REUSE_REPORT : WS_REUSE, B, N, seq_len_host, bytes);
 }
 
 // --------------------------------------------------------------------------------------- decode
@@ -2053,6 +2129,17 @@ int vv_ode_stage_apg(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_apg: null arguments") : -22;
     if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_apg: u_row must be an int32 array");
     SINGLE(c, vvk_ode_stage(a, u_row, apg, (hipStream_t)st, &m__));
+}
+int vv_ode_stage_reuse(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row, const vv_reuse_stage_args* reuse, void* st) {
+    if (!reuse) return vv_ode_stage_guided(c, a, u_row, st);
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_reuse: null arguments") : -22;
+    if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_reuse: u_row must be an int32 array");
+    SINGLE(c, vvk_ode_stage(a, u_row, nullptr, (hipStream_t)st, &m__, 0, reuse));
+}
+int vv_cfg_drift_reduce(vv_ctx* c, const vv_cfg_drift_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_cfg_drift_reduce: null arguments") : -22;
+    if (((uintptr_t)a->u_row | (uintptr_t)a->row_start | (uintptr_t)a->len) % 4) return c->fail(-22, "vv_cfg_drift_reduce: the index arrays must be 4-byte aligned");
+    SINGLE(c, vvk_cfg_drift_reduce(a, 3, (hipStream_t)st, &m__));
 }
 int vv_ode_diff_reduce(vv_ctx* c, const vv_ode_diff_args* a, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_ode_diff_reduce: null arguments") : -22;

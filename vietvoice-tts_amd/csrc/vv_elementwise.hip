@@ -4,6 +4,7 @@
 // cross-wave reduction is needed.
 #include "vv_common.h"
 #include "vv_kernels.h"
+#include <type_traits>
 
 namespace {
 
@@ -216,13 +217,24 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, c
 // APG (N11): the item's strength is coef[b][0] = A_b in place of g (the combine is written exactly as the plain one), and where
 // coef[b][1] = C_b != 0 the slope also takes C_b d, d = fmaf(1 - t_e, pc, x_e) the conditional data estimate at the state x_e the DiT was
 // evaluated at (x through row_src, or the packed stage state when xe_packed) -- never the buffer x_out of the same launch.
+// REUSE (N21, on top of GUIDED, never with APG): the guidance difference D = pc - pu of an item is kept in d_buf ([BN][n_mel] fp32, packed
+// rows) between evaluations.  The mode of a row is its ITEM's (row_src[row] / seq_n, as g_item's), two bits that travel as kernel arguments
+// (two GuideFlags; no table on the device): bit `load` -- the item has no unconditional row at this evaluation (u_row < 0) and
+// k_i = pc + D g with D read from d_buf; bit `store` -- the item's D, formed from pred, is also written to d_buf because a later evaluation
+// of the call reads it.  A row with u_row >= 0 is computed whatever `load` says; a row with u_row < 0 and no `load` bit is not guided, k_i =
+// pc.  One body and one combine expression, so a computed row runs the very arithmetic of ode_stage_kernel<true, false>.
 struct OdeStagePrev { const float* k[3]; float c[3]; };
-template <bool GUIDED, bool APG>
+struct GuideFlags { unsigned w[VVK_GUIDE_MAX_ITEMS / 32]; };     // one bit per item of a launch, a kernel argument (N8; N21)
+struct OdeStageReuse { float* d_buf; GuideFlags load, store; };
+struct OdeStageNoReuse {};
+template <bool GUIDED, bool APG, bool REUSE = false>
 __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
                                                         const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
                                                         OdeStagePrev pv, float c_new, float* k_out, float* __restrict__ x_out,
                                                         const int* __restrict__ u_row, const float* __restrict__ apg_coef,
-                                                        const float* x_e, int xe_packed, float omt) {
+                                                        const float* x_e, int xe_packed, float omt,
+                                                        std::conditional_t<REUSE, OdeStageReuse, OdeStageNoReuse> ru) {
+    static_assert(!REUSE || (GUIDED && !APG), "the reuse form sits on the guided kernel and is never combined with APG");
     const int c4 = n_mel >> 2;
     const size_t total = (size_t)BN * c4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -238,13 +250,29 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
             cfg = g_item ? g_item[xr / (size_t)seq_n] : g;
         }
         const int ur = GUIDED ? u_row[row] : 0;
+        bool ru_load = false, ru_store = false;
+        if constexpr (REUSE) {
+            const unsigned item = (unsigned)(xr / (size_t)seq_n) & (VVK_GUIDE_MAX_ITEMS - 1);
+            ru_load = ur < 0 && ((ru.load.w[item >> 5] >> (item & 31)) & 1u);
+            ru_store = ur >= 0 && ((ru.store.w[item >> 5] >> (item & 31)) & 1u);
+        }
         float4 k = pc;
-        if (!GUIDED || ur >= 0) {
-            const float4 pu = *(const float4*)(pred + (GUIDED ? (size_t)ur : row + BN) * ldp + c);
-            k.x = pc.x + (pc.x - pu.x) * cfg;
-            k.y = pc.y + (pc.y - pu.y) * cfg;
-            k.z = pc.z + (pc.z - pu.z) * cfg;
-            k.w = pc.w + (pc.w - pu.w) * cfg;
+        if (!GUIDED || ur >= 0 || ru_load) {
+            float4 D;
+            if constexpr (REUSE) {
+                if (ru_load) D = *(const float4*)(ru.d_buf + row * n_mel + c);
+            }
+            if (!ru_load) {
+                const float4 pu = *(const float4*)(pred + (GUIDED ? (size_t)ur : row + BN) * ldp + c);
+                D.x = pc.x - pu.x; D.y = pc.y - pu.y; D.z = pc.z - pu.z; D.w = pc.w - pu.w;
+            }
+            k.x = pc.x + D.x * cfg;
+            k.y = pc.y + D.y * cfg;
+            k.z = pc.z + D.z * cfg;
+            k.w = pc.w + D.w * cfg;
+            if constexpr (REUSE) {
+                if (ru_store) *(float4*)(ru.d_buf + row * n_mel + c) = D;
+            }
             if (APG && apg_c != 0.f) {
                 const float4 xe = *(const float4*)(x_e + (xe_packed ? row : xr) * n_mel + c);
                 k.x = fmaf(apg_c, fmaf(omt, pc.x, xe.x), k.x);
@@ -414,6 +442,67 @@ __global__ __launch_bounds__(64) void ode_diff_finish_kernel(const double* __res
     double s = 0.0;
     for (int t = 0; t < nt; ++t) s += partials[((size_t)b * n_tiles + t) * 2 + lane];
     report[2 * b + lane] = s;
+}
+
+// ---------------------------------------------------------------- N21: the drift report of guidance reuse, the per-item reduction
+// Partial sums of one (frame tile, item): E2 = sum (D_new - D_old)^2 and N2 = sum D_new^2 over the tile's valid frames and the n_mel columns,
+// D_new = pc - pu the fp32 difference the stage kernel forms from pred through u_row (one fp32 subtraction: the value it stores), D_old the
+// row of d_buf.  Differences of the two, squares and sums in float64 and NOT contracted (a product, then an add).  A row whose u_row is < 0
+// (its item reuses or is not guided here) contributes nothing, so such an item's sums are {0, 0}; an item whose bit of `has_old` is clear
+// (no difference stored yet in this call) does not read d_buf and E2 = 0.  ode_diff_reduce_kernel's determinism contract: tiles of
+// VV_APG_TILE frames counted from the ITEM's frame 0, float4 q of the tile to thread q % 256 with its four elements in order, one fixed LDS
+// tree -- an item's partials are a function of its own rows alone.  grid (n_tiles, B); a tile past the item's length writes nothing.  It
+// runs BEFORE the stage launch that overwrites d_buf.  The item sums are ode_diff_finish_kernel's.
+__global__ __launch_bounds__(256) void cfg_drift_reduce_kernel(const float* __restrict__ pred, int ldp, int Rc, int n_mel,
+                                                               const int* __restrict__ u_row, const float* __restrict__ d_buf, GuideFlags has_old,
+                                                               const int* __restrict__ row_start, const int* __restrict__ len, int n_tiles,
+                                                               double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double red[2][256];
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);   // inside the Rc rows and the item's n_tiles partials, whatever the tables say
+    const int f0 = tile * VV_APG_TILE;
+    if (f0 >= n) return;
+    const bool old = (has_old.w[b >> 5] >> (b & 31)) & 1u;
+    const int c4 = n_mel >> 2;
+    const int total = min(VV_APG_TILE, n - f0) * c4;
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const int c = (q % c4) * 4;
+        const size_t row = (size_t)r0 + f0 + q / c4;
+        const int ur = u_row[row];
+        if (ur < 0) continue;
+        const float4 pc = *(const float4*)(pred + row * ldp + c);
+        const float4 pu = *(const float4*)(pred + (size_t)ur * ldp + c);
+        const float dn[4] = {pc.x - pu.x, pc.y - pu.y, pc.z - pu.z, pc.w - pu.w};
+        float dv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (old) {
+            const float4 p = *(const float4*)(d_buf + row * n_mel + c);
+            dv[0] = p.x; dv[1] = p.y; dv[2] = p.z; dv[3] = p.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = (double)dn[j];
+            if (old) {
+                const double d = v - (double)dv[j];
+                const double dd = d * d;
+                s1 = s1 + dd;
+            }
+            const double vv = v * v;
+            s2 = s2 + vv;
+        }
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) partials[((size_t)b * n_tiles + tile) * 2 + threadIdx.x] = red[threadIdx.x][0];
 }
 
 // ---------------------------------------------------------------- text: embed gather + position table
@@ -604,7 +693,6 @@ __global__ __launch_bounds__(256) void row_tables_kernel(const int* __restrict__
 // that exist, so device lengths that disagree with the host's never index past a table: a guided item past the Ru-th row gets a shorter
 // or empty unconditional sequence (its remaining rows are unguided, u_row -1), and rows of either half that nobody owns map onto the
 // padding rows of the last item.
-struct GuideFlags { unsigned w[32]; };
 __global__ __launch_bounds__(256) void guided_tables_kernel(const int* __restrict__ seq_len, GuideFlags flags, int B, int N, int Rc, int Ru,
                                                             int* __restrict__ row_start, int* __restrict__ rs_rel, int* __restrict__ kv_len,
                                                             int* __restrict__ row_pos, int* __restrict__ u_src, int* __restrict__ u_crow,
@@ -794,7 +882,8 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
     return 0;
 }
 
-int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring) {
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring,
+                  const vv_reuse_stage_args* reuse) {
     if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
     if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
     if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
@@ -819,8 +908,27 @@ int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_sta
     }
     const int grid = grid_for((size_t)a->Rc * a->n_mel / 4);
     const float omt = apg ? 1.0f - apg->t_e : 0.f;
+    if (reuse) {                                         // N21
+        if (apg || !u_row) { *err = "ode_stage: the reuse form needs u_row and is not combined with APG"; return -22; }
+        if (!reuse->d_buf || (uintptr_t)reuse->d_buf % 16 || !reuse->item_mode_host) { *err = "ode_stage: d_buf (16-byte aligned) and the item modes are required"; return -22; }
+        if (a->seq_n < 1 || reuse->n_items < 1 || reuse->n_items > VVK_GUIDE_MAX_ITEMS) { *err = "ode_stage: the reuse form needs seq_n and 1..1024 item modes"; return -22; }
+        if (reuse->d_buf == a->k_out || reuse->d_buf == a->x_out || reuse->d_buf == a->x) { *err = "ode_stage: d_buf must be a buffer of its own"; return -22; }
+        for (int j = 0; j < 3; ++j)
+            if (pv.k[j] == reuse->d_buf) { *err = "ode_stage: d_buf must be a buffer of its own"; return -22; }
+        OdeStageReuse ru{};
+        ru.d_buf = reuse->d_buf;
+        for (int b = 0; b < reuse->n_items; ++b) {
+            if (reuse->item_mode_host[b] & ~3u) { *err = "ode_stage: an item mode is VV_REUSE_LOAD | VV_REUSE_STORE at the most"; return -22; }
+            if (reuse->item_mode_host[b] & VV_REUSE_LOAD) ru.load.w[b >> 5] |= 1u << (b & 31);
+            if (reuse->item_mode_host[b] & VV_REUSE_STORE) ru.store.w[b >> 5] |= 1u << (b & 31);
+        }
+        ode_stage_kernel<true, false, true><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
+                                                                   a->coef[a->n_prev], a->k_out, a->x_out, u_row, nullptr, nullptr, 0, omt, ru);
+        VVK_CHECK_LAUNCH();
+        return 0;
+    }
 #define STAGE_GO(G, A) ode_stage_kernel<G, A><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv, \
-        a->coef[a->n_prev], a->k_out, a->x_out, u_row, apg ? apg->coef : nullptr, apg ? apg->x_e : nullptr, apg ? apg->x_e_packed : 0, omt)
+        a->coef[a->n_prev], a->k_out, a->x_out, u_row, apg ? apg->coef : nullptr, apg ? apg->x_e : nullptr, apg ? apg->x_e_packed : 0, omt, OdeStageNoReuse{})
     if (apg) { if (u_row) STAGE_GO(true, true); else STAGE_GO(false, true); }
     else if (u_row) STAGE_GO(true, false);
     else STAGE_GO(false, false);
@@ -858,6 +966,30 @@ int vvk_ode_diff_reduce(const vv_ode_diff_args* a, int which, hipStream_t st, co
     if (((uintptr_t)a->f | (uintptr_t)a->f_prev) % 16 || ((uintptr_t)a->partials | (uintptr_t)a->report) % 8) { *err = "ode_diff_reduce: f and f_prev 16-byte, partials and report 8-byte aligned"; return -22; }
     if (which & 1) {
         ode_diff_reduce_kernel<<<dim3(a->n_tiles, a->B), 256, 0, st>>>(a->f, a->f_prev, a->Rc, a->n_mel, a->row_start, a->len, a->n_tiles, a->partials);
+        VVK_CHECK_LAUNCH();
+    }
+    if (which & 2) {
+        ode_diff_finish_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->row_start, a->len, a->report);
+        VVK_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// N21: the two kernels behind vv_cfg_drift_reduce.  which & 1: the reduction, which & 2: the item sums (ode_diff_finish_kernel).
+int vvk_cfg_drift_reduce(const vv_cfg_drift_args* a, int which, hipStream_t st, const char** err) {
+    if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "cfg_drift_reduce: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
+    if (!a->pred || !a->u_row || !a->row_start || !a->len || !a->partials || !a->report) { *err = "cfg_drift_reduce: pred, u_row, row_start, len, partials and report are required"; return -22; }
+    if (a->B < 1 || a->B > VVK_GUIDE_MAX_ITEMS || a->n_tiles < 1) { *err = "cfg_drift_reduce: 1..1024 items, n_tiles >= 1"; return -22; }
+    if (((uintptr_t)a->pred | (uintptr_t)a->d_buf) % 16 || ((uintptr_t)a->partials | (uintptr_t)a->report) % 8) { *err = "cfg_drift_reduce: pred and d_buf 16-byte, partials and report 8-byte aligned"; return -22; }
+    GuideFlags old{};
+    for (int b = 0; b < a->B && a->has_old_host; ++b)
+        if (a->has_old_host[b]) old.w[b >> 5] |= 1u << (b & 31);
+    if (a->has_old_host && !a->d_buf)
+        for (unsigned w : old.w)
+            if (w) { *err = "cfg_drift_reduce: an item with a stored difference needs d_buf"; return -22; }
+    if (which & 1) {
+        cfg_drift_reduce_kernel<<<dim3(a->n_tiles, a->B), 256, 0, st>>>(a->pred, a->ldp, a->Rc, a->n_mel, a->u_row, a->d_buf, old, a->row_start, a->len,
+                                                                         a->n_tiles, a->partials);
         VVK_CHECK_LAUNCH();
     }
     if (which & 2) {

@@ -32,7 +32,11 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
 // u_row (N8, optional [Rc] device): conditional packed row -> the row of pred that holds its unconditional prediction, -1 = none (k = pc)
 // apg (N11, optional): the item coefficients {A, C} and the evaluation state of the projected combine
 // k_out_ring != 0 (N20, the steps driver under a multistep plan): a->k_out may be the buffer of one of the earlier slopes
-int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring = 0);
+// reuse (N21, optional; needs u_row, never with apg): the buffer of the kept guidance differences and the items' modes (HOST, kernel arguments)
+int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring = 0,
+                  const vv_reuse_stage_args* reuse = nullptr);
+// N21: the drift report -- which & 1: cfg_drift_reduce_kernel, which & 2: the item sums
+int vvk_cfg_drift_reduce(const vv_cfg_drift_args* a, int which, hipStream_t st, const char** err);
 // N20: the step report -- which & 1: ode_diff_reduce_kernel, which & 2: the item sums
 int vvk_ode_diff_reduce(const vv_ode_diff_args* a, int which, hipStream_t st, const char** err);
 // N11: apg_reduce_kernel (which & 1) and apg_coef_kernel (which & 2) of one evaluation

@@ -292,17 +292,40 @@ def check_cfg_interval(interval) -> Optional[Tuple[float, float]]:
     return lo, hi
 
 
-def guidance_mask(plan: OdePlan, interval, strengths) -> Optional[torch.Tensor]:
+def check_cfg_reuse(v) -> Optional[int]:
+    """N21 guidance reuse of one item: None, or an integer k >= 1 -- the unconditional branch runs at every k-th guided evaluation.  Returns
+    the integer (1 = off, as None); ValueError for a bool, a non-integer and k < 1."""
+    if v is None:
+        return None
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or int(v) < 1:
+        raise ValueError("cfg_reuse must be an integer >= 1 or None")
+    return int(v)
+
+
+def guidance_mask(plan: OdePlan, interval, strengths, reuse=None) -> Optional[torch.Tensor]:
     """N8 limited-interval guidance (Kynkaanniemi et al. 2024): uint8 [n_evals][B], row e = step * s + stage as in ``plan.t``,
     guided(b, e) = (interval is None or lo <= float(plan.t[e]) <= hi) and strengths[b] != 0 -- both edges inclusive, the fp32 time
     of the plan compared as a double.  ``interval``: None or one (lo, hi) for every item, or a sequence of B of them, one per item.
-    Returns None when every item is guided at every evaluation (the unmasked call)."""
+    Returns None when every item is guided at every evaluation (the unmasked call).
+
+    ``reuse`` (N21 guidance reuse): None, one integer k >= 1 for every item, or a sequence of B of them (check_cfg_reuse); None and 1 are
+    "off".  Off for every item: exactly the above.  Otherwise the mask has three values -- 0 = not guided, 1 = guided and the unconditional
+    prediction COMPUTED, 2 = guided and the stored guidance difference REUSED: the guided evaluations of item b, in ascending e, are
+    numbered j = 0, 1, 2, ... and evaluation j is computed when j % k_b == 0, reused otherwise.  The count runs over evaluations (the
+    stages of a Runge-Kutta step count one each) and simply continues across a gap of the interval, so the first guided evaluation of an
+    item is always computed."""
     g = [float(v) for v in strengths]
     B = len(g)
     one = interval is None or (len(interval) == 2 and all(isinstance(v, numbers.Real) for v in interval))
     ivals = [check_cfg_interval(interval)] * B if one else [check_cfg_interval(v) for v in interval]
     if len(ivals) != B:
         raise ValueError("guidance_mask: one interval per item")
+    if reuse is None or isinstance(reuse, (bool, numbers.Number, str)):
+        ks = [check_cfg_reuse(reuse)] * B
+    else:
+        ks = [check_cfg_reuse(v) for v in reuse]
+    if len(ks) != B:
+        raise ValueError("guidance_mask: one cfg_reuse per item")
     t = [float(v) for v in plan.t]
     mask = torch.zeros((len(t), B), dtype=torch.uint8)
     for b in range(B):
@@ -310,7 +333,16 @@ def guidance_mask(plan: OdePlan, interval, strengths) -> Optional[torch.Tensor]:
             continue
         for e, te in enumerate(t):
             mask[e, b] = 1 if ivals[b] is None or ivals[b][0] <= te <= ivals[b][1] else 0
-    return None if bool(mask.all()) else mask
+    if all(k is None or k == 1 for k in ks):
+        return None if bool(mask.all()) else mask
+    for b in range(B):
+        k = ks[b] or 1
+        j = 0
+        for e in range(len(t)):
+            if mask[e, b]:
+                mask[e, b] = 1 if j % k == 0 else 2
+                j += 1
+    return mask
 
 
 def check_apg(eta, norm) -> Optional[Tuple[float, Optional[float]]]:

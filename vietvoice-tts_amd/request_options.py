@@ -19,13 +19,14 @@ class RequestOptions:
     tempo: Optional[float] = None
     formants: Optional[str] = None                         # (N18)
     denoise: Optional[float] = None                        # (N19)
+    cfg_reuse: Optional[int] = None                        # the acoustic stage, per chunk (N21)
 
     @classmethod
     def checked(cls, cfg_strength=None, cfg_interval=None, apg_eta=None, apg_norm=None, loudness=None, limiter=None, pitch=None, tempo=None,
-                formants=None, denoise=None) -> "RequestOptions":
+                formants=None, denoise=None, cfg_reuse=None) -> "RequestOptions":
         """The validated, normalised record; ValueError in the words of the option's own check, the first in this order."""
         from .core.audio_processor import check_denoise, check_formants, check_limiter, check_loudness, check_prosody
-        from .model_spec import check_apg, check_cfg_interval
+        from .model_spec import check_apg, check_cfg_interval, check_cfg_reuse
         loudness, _pk = check_loudness(loudness)
         check_limiter(limiter)
         pitch, tempo = check_prosody(pitch, tempo)
@@ -38,12 +39,14 @@ class RequestOptions:
             cfg_strength = float(cfg_strength)
             if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
                 raise ValueError("cfg_strength must be a finite number or None")
-        return cls(cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise)
+        cfg_reuse = check_cfg_reuse(cfg_reuse)
+        return cls(cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise, cfg_reuse)
 
     def resolved(self, config) -> "RequestOptions":
         """Every None replaced by the engine's value: the one place that says "own value, else the engine's"."""
         mine = RequestOptions(config.cfg_strength, config.cfg_interval, config.apg_eta, config.apg_norm, config.output_loudness,
-                              config.output_limiter, config.output_pitch, config.output_tempo, config.output_formants, config.output_denoise)
+                              config.output_limiter, config.output_pitch, config.output_tempo, config.output_formants, config.output_denoise,
+                              getattr(config, "cfg_reuse", None))
         return replace(mine, **{name: v for name, v in vars(self).items() if v is not None})
 
     def wants_output_stage(self) -> bool:

@@ -130,6 +130,22 @@ class vv_ode_diff_args(C.Structure):
                 ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p), ("report", C.c_void_p)]
 
 
+class vv_reuse_args(C.Structure):
+    _fields_ = [("report", C.c_void_p), ("report_B", C.c_int32), ("report_evals", C.c_int32)]
+
+
+class vv_reuse_stage_args(C.Structure):
+    _fields_ = [("d_buf", C.c_void_p), ("item_mode_host", C.c_void_p), ("n_items", C.c_int32)]
+
+
+class vv_cfg_drift_args(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("ldp", C.c_int32), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("u_row", C.c_void_p),
+                ("d_buf", C.c_void_p), ("has_old_host", C.c_void_p), ("B", C.c_int32), ("n_tiles", C.c_int32),
+                ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p), ("report", C.c_void_p)]
+
+
+REUSE_LOAD, REUSE_STORE = 1, 2          # VV_REUSE_LOAD / VV_REUSE_STORE of include/vvtts.h: an item's mode in vv_ode_stage_reuse
+
 APG_TILE = 32                 # VV_APG_TILE of include/vvtts.h: frames per partial sum of the projected-guidance reduction
 
 EXPORTS = {
@@ -154,6 +170,10 @@ EXPORTS = {
     "vv_transformer_apg_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vv_apg_coef": (C.c_int, [C.c_void_p, C.POINTER(vv_apg_coef_args), C.c_void_p]),
     "vv_ode_stage_apg": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_apg_stage_args), C.c_void_p]),
+    "vv_transformer_steps_reuse": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.POINTER(vv_reuse_args), C.c_void_p]),
+    "vv_transformer_reuse_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "vv_ode_stage_reuse": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_reuse_stage_args), C.c_void_p]),
+    "vv_cfg_drift_reduce": (C.c_int, [C.c_void_p, C.POINTER(vv_cfg_drift_args), C.c_void_p]),
     "vv_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_preprocess_h": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -389,6 +409,8 @@ class HipSynth(PcmStage):
         self.ode_method = None           # the solver of the plan in force: a name of model_spec.ODE_METHODS / ODE_MULTISTEP or a custom tableau (a, b)
         self.ode_report = False          # N20: every transformer_steps call from step 0 leaves its step report (last_ode_report); needs a multistep plan
         self._ode_report = None          # the last call's report, float64 [n_steps, B, 2] on the device
+        self.cfg_reuse_report = False    # N21: every transformer_steps call with a mask leaves its drift report (last_cfg_reuse_report)
+        self._cfg_reuse_report = None    # the last such call's report, float64 [n_evals, B, 2] on the device
         self.set_nfe(nfe_step, ode_method)
         self.set_ode_report(ode_report)
 
@@ -467,6 +489,25 @@ class HipSynth(PcmStage):
             rep = self._ode_report
         return None if rep is None else rep.cpu().numpy()
 
+    def set_cfg_reuse_report(self, on: bool):
+        """N21: turn the drift report of guidance reuse on or off (ModelConfig.cfg_reuse_report).  On, every transformer_steps call with a
+        guidance mask leaves float64 [n_evals, B, 2] for last_cfg_reuse_report (two small launches per evaluation and lane); off (the
+        default) launches and allocates nothing."""
+        with self._lock:
+            self.cfg_reuse_report = bool(on)
+            if not on:
+                self._cfg_reuse_report = None
+
+    def last_cfg_reuse_report(self):
+        """N21: the drift report of the last transformer_steps call that had a mask, numpy float64 [n_evals, B, 2]: per evaluation e and
+        item b (E2, N2) = (sum (D_e - D_stored)^2, sum D_e^2) over the item's frames and the n_mel columns where b's unconditional
+        prediction is computed at e, D = p_c - p_u and D_stored the difference of b's previous computed evaluation of the call (E2 = 0
+        at the first); (0, 0) where b reuses or is not guided, and at evaluations outside the call.  sqrt(E2 / N2) is how far the
+        difference moved over the evaluations it was reused for.  One copy from the device; None when no call has left a report."""
+        with self._lock:
+            rep = self._cfg_reuse_report
+        return None if rep is None else rep.cpu().numpy()
+
     class _ReportScope:
         """The report buffer of one steps call: set in front of it, cleared behind it whatever happens (the library keeps no pointer to a
         tensor that may be freed)."""
@@ -523,10 +564,11 @@ class HipSynth(PcmStage):
         es = 2 if self.dt_torch == torch.bfloat16 else 4
         return ((1 << 31) - 1) // (2 * 3 * self.spec.dim * es)
 
-    def guidance_mask(self, interval, strengths) -> Optional[torch.Tensor]:
+    def guidance_mask(self, interval, strengths, reuse=None) -> Optional[torch.Tensor]:
         """model_spec.guidance_mask on the plan in force: the ``guide`` of transformer_steps for a guidance interval (one for every item
-        or one per item) and the B strengths (a None strength = the model's); None = every item guided everywhere."""
-        return guidance_mask(self.plan, interval, [self.spec.cfg_strength if v is None else v for v in strengths])
+        or one per item) and the B strengths (a None strength = the model's); None = every item guided everywhere.  reuse (N21): None,
+        one k or one per item -- the unconditional branch at every k-th guided evaluation of an item, a 2 in the mask in between."""
+        return guidance_mask(self.plan, interval, [self.spec.cfg_strength if v is None else v for v in strengths], reuse)
 
     def apg_tensors(self, etas, norms):
         """N11: the ``apg`` of transformer_steps from B host values each -- eta (None = 1) and the RMS cap (None = no cap), validated by
@@ -548,7 +590,8 @@ class HipSynth(PcmStage):
         values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
         cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's.
         guide (optional uint8 [n_evals, B] on the HOST, N8): guided(b, e) of every evaluation of the plan in force
-        (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere.
+        (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere.  A mask that holds a 2
+        (N21 guidance reuse), or any mask while the drift report is on, goes to vv_transformer_steps_reuse.
         apg (optional pair (eta, norm) of fp32 [B] device tensors, either None, N11): projected guidance per item
         (vv_transformer_steps_apg; apg_tensors builds it); None, or a pair of Nones = off: the existing entries."""
         B, N, M = x.shape
@@ -581,18 +624,28 @@ class HipSynth(PcmStage):
         """Bytes of a caller-owned workspace for a call with a guidance mask (vv_transformer_guided_ws_bytes; the same for every mask)."""
         return self._steps_ws_bytes(self.lib.vv_transformer_guided_ws_bytes, B, N, _host_lens(B, seq_len_host))
 
+    def reuse_ws_bytes(self, B: int, N: int, seq_len_host, report: bool = False) -> int:
+        """Bytes of a caller-owned workspace for a call that reuses guidance differences (vv_transformer_reuse_ws_bytes; the same for every
+        mask): the guided figure plus one difference buffer per lane, plus the drift report's partial sums when ``report``."""
+        nb = C.c_uint64()
+        with self._lock:
+            self._check(self.lib.vv_transformer_reuse_ws_bytes(self.ctx, int(B), int(N), _host_lens(B, seq_len_host), int(bool(report)), C.byref(nb)))
+        return int(nb.value)
+
     def apg_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
         """Bytes of a caller-owned workspace for a call with projected guidance (vv_transformer_apg_ws_bytes; the same with any mask)."""
         return self._steps_ws_bytes(self.lib.vv_transformer_apg_ws_bytes, B, N, _host_lens(B, seq_len_host))
 
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
                              cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                             guide: Optional[torch.Tensor] = None, apg=None) -> None:
+                             guide: Optional[torch.Tensor] = None, apg=None, reuse_entry: Optional[bool] = None) -> None:
         """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
         the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host).  guide: a contiguous uint8
         HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
         ld_guide >= B).  apg: None, or a pair (eta, norm) of fp32 [B] device tensors (either None), handed to
-        vv_transformer_steps_apg with the times of the plan in force."""
+        vv_transformer_steps_apg with the times of the plan in force.  reuse_entry (N21): True hands the mask to
+        vv_transformer_steps_reuse (with the drift report's buffer when set_cfg_reuse_report is on), False never; None = when the mask
+        holds a 2 or the report is on.  Never together with apg."""
         B, N, _ = x.shape
         if apg is not None:
             if len(apg) != 2 or any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
@@ -610,8 +663,20 @@ class HipSynth(PcmStage):
         if ws is not None:
             a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
         a.cfg_item = _ptr(cfg)
+        if reuse_entry is None:
+            reuse_entry = guide is not None and apg is None and (self.cfg_reuse_report or bool((guide[:, :B] == 2).any()))
+        if reuse_entry and (apg is not None or guide is None):
+            raise ValueError("guidance reuse needs a mask and is not combined with projected guidance (apg)")
+        if apg is not None and guide is not None and bool((guide[:, :B] == 2).any()):
+            raise ValueError("a mask that reuses guidance differences (a 2) is not combined with projected guidance (apg)")
         with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
-            if apg is not None:
+            if reuse_entry:
+                rep = torch.zeros((self.n_evals, B, 2), dtype=torch.float64, device=self.device) if self.cfg_reuse_report else None
+                r = vv_reuse_args(_ptr(rep), B, self.n_evals)
+                self._cfg_reuse_report = None
+                self._check(self.lib.vv_transformer_steps_reuse(self.ctx, C.byref(a), guide.data_ptr(), int(guide.shape[1]), C.byref(r), self._stream()))
+                self._cfg_reuse_report = rep
+            elif apg is not None:
                 q = vv_apg_args(_ptr(apg[0]), _ptr(apg[1]), C.cast(self._t_host, C.c_void_p))
                 self._check(self.lib.vv_transformer_steps_apg(self.ctx, C.byref(a), None if guide is None else guide.data_ptr(),
                                                               0 if guide is None else int(guide.shape[1]), C.byref(q), self._stream()))
