@@ -986,6 +986,44 @@ VV_API uint64_t vv_pcm_denoise_bias_ws_bytes(int64_t total_frames, int R);
 VV_API int vv_pcm_denoise_bias(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const double* window,
                                const double* twiddles, double* out, int64_t n_out, void* ws, uint64_t ws_bytes, void* stream);
 
+/* ---- N22 keyed audio watermark: a multiplicative spread-spectrum mark on the frames of N19 (N, H, window, transform and
+ * scale 1536 as above), embedded behind pitch and tempo and before the loudness step, and its detector.  The arithmetic is pinned by
+ * core/audio_processor.py (watermark_embed, watermark_cells, watermark_stats), which the kernels equal bit for bit.  A cell is (frame f, band
+ * bin k), LO <= k < LO + K; at alignment q its group is g = ((f + q) / G) % P, its bit index j = (k - LO + 7 g) % NB and its chip
+ * chips[g K + k - LO] (+1 or -1, made from a 64-bit key on the HOST by audio_processor.watermark_chips: the device hashes nothing).  The
+ * message is 24 bits, bit j = bit 23 - j of (payload << 8 | CRC-8 of the payload's two big-endian bytes, polynomial 0x07, initial value 0).
+ *     embed  per frame: forward transform; re and im of the band bins k and of their mirrors N - k times (chip > 0) == (bit j set) ? gp : gm
+ *            at q = 0, every other bin times 1.0; inverse transform, window, overlap-add, y = clamp(rint(acc / 1536)) as N19.  gp = 1 + a
+ *            and gm = 1 - a are made by the caller, 0 <= a <= 0.5; a = 0 gives the input back sample for sample (computed, not short-circuited)
+ *     detect m[f][k] = the band magnitudes of the F = M + 3 frames; r = 0.5 (m[max(f - G, 0)][k] + m[min(f + G, F - 1)][k]);
+ *            d = (int32) rint(32768 (m - r) / (m + r + 1.0)), float64, every operation rounded on its own; for every alignment q < P G and
+ *            bit j: num = sum of chip d, den = sum of d d over the cells of bit j (int64) -> stats [R][P G][NB]{num, den}
+ * The calls never synchronise and read nothing back; the decision (z = num / sqrt(den), the score, the CRC) is the host's.
+ *   rows       R x 4 int64 in device memory and the same rows in HOST memory (rows_host, checked by the call): {x_off, n, y_off, message}
+ *              for vv_pcm_watermark, {x_off, n, 0, 0} for vv_pcm_watermark_detect
+ *   chips      int8 [n_chips >= P K] on the device, 4-byte aligned;  window, twiddles: as for vv_pcm_denoise
+ *   y          int16 [n_y], must not overlap x; nothing outside the rows' outputs is written
+ *   stats      int64 [n_stats >= R P G NB 2];  cells_out: NULL, or int32 [n_cells] for a test: the K cell values of every frame, request after
+ *              request, M + 3 frames each
+ *   ws         ws_bytes >= vv_pcm_watermark_ws_bytes(R) / vv_pcm_watermark_detect_ws_bytes(sum of M + 3, R), 8-byte aligned
+ * -22, and nothing is launched, for no context, R < 1 or R > 65535, a null or misaligned pointer, a chips, ws, stats or cells_out that is too
+ * small, a negative field, n > 2^30 (detect: n > VV_WATERMARK_DETECT_MAX_N), a message above 2^24 - 1, gains outside 1 <= gp <= 1.5 and
+ * 0.5 <= gm <= 1 (a NaN included), a row outside n_x / n_y, rows that overlap on y, y overlapping x. */
+#define VV_WATERMARK_LO 22
+#define VV_WATERMARK_K 320
+#define VV_WATERMARK_G 4
+#define VV_WATERMARK_P 64
+#define VV_WATERMARK_NB 24
+#define VV_WATERMARK_DETECT_MAX_N 16777216
+VV_API uint64_t vv_pcm_watermark_ws_bytes(int R);
+VV_API int vv_pcm_watermark(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const int8_t* chips,
+                            int64_t n_chips, double gp, double gm, const double* window, const double* twiddles, int16_t* y, int64_t n_y, void* ws,
+                            uint64_t ws_bytes, void* stream);
+VV_API uint64_t vv_pcm_watermark_detect_ws_bytes(int64_t total_frames, int R);
+VV_API int vv_pcm_watermark_detect(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R,
+                                   const int8_t* chips, int64_t n_chips, const double* window, const double* twiddles, int64_t* stats,
+                                   int64_t n_stats, int32_t* cells_out, int64_t n_cells, void* ws, uint64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

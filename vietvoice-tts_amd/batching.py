@@ -86,7 +86,8 @@ class BatchingFrontend:
     def submit(self, text: str, speed: Optional[float] = None, serial: Optional[int] = None, cfg_strength: Optional[float] = None,
                cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
                loudness: Optional[float] = None, limiter: Optional[str] = None, pitch: Optional[float] = None, tempo: Optional[float] = None,
-               formants: Optional[str] = None, denoise: Optional[float] = None, cfg_reuse: Optional[int] = None, **voice) -> Future:
+               formants: Optional[str] = None, denoise: Optional[float] = None, cfg_reuse: Optional[int] = None, watermark_payload: Optional[int] = None,
+               **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
@@ -103,12 +104,15 @@ class BatchingFrontend:
         request alone, against the engine's bias profile.
         ``cfg_reuse``: this request's guidance reuse k (None = the engine's ``cfg_reuse``, 1 = off): its unconditional branch
         runs at every k-th guided evaluation only, per item beside the interval and the strength in one ragged batch.  Together with an
-        ``apg_eta`` / ``apg_norm`` that is not off (its own or the engine's) the request fails with a ValueError."""
+        ``apg_eta`` / ``apg_norm`` that is not off (its own or the engine's) the request fails with a ValueError.
+        ``watermark_payload``: this request's watermark payload, 0 ... 65535 (None = the engine's
+        ``output_watermark_payload``), embedded in this request alone under the engine's ``output_watermark_key``; on an engine without a
+        key the request fails with a ValueError."""
         fut: Future = Future()
         try:
             options = RequestOptions.checked(cfg_strength=cfg_strength, cfg_interval=cfg_interval, apg_eta=apg_eta, apg_norm=apg_norm,
                                              loudness=loudness, limiter=limiter, pitch=pitch, tempo=tempo, formants=formants, denoise=denoise,
-                                             cfg_reuse=cfg_reuse)
+                                             cfg_reuse=cfg_reuse, watermark_payload=watermark_payload)
             config = getattr(self.engine, "config", None)
             full = options if config is None else options.resolved(config)
             from .model_spec import check_apg

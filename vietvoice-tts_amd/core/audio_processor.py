@@ -1650,6 +1650,196 @@ def denoise_pcm(pcm, bias, strength, mags: bool = False):
     return (z, mag) if mags else z
 
 
+# ---------------------------------------------------------------------------- keyed audio watermark
+# A multiplicative spread-spectrum mark (Cox et al. 1997; for audio Kirovski & Malvar 2003) on the denoiser's frames: every cell (frame f,
+# band bin k) of the STFT is scaled by 1 + a or 1 - a as its keyed chip and its message bit agree or not, and a detector that knows the key
+# correlates the chips with a per-cell contrast of the magnitude against its neighbours in time, at each of 256 whole-hop alignments.  The
+# arithmetic below is the specification of vv_pcm_watermark and vv_pcm_watermark_detect (csrc/vv_watermark.hip), which equal it bit for
+# bit: the transform and the frames are denoise_fft's, every float64 operation is rounded on its own, and behind the cell value
+# everything is an integer.
+#     cell (f, k) at alignment q: group g = ((f + q) // G) % P, bit index j = (k - LO + 7 g) % NB, chip = table[g][k - LO]
+#     embed (q = 0)  : gain = chip (2 bit_j - 1) > 0 ? 1 + a : 1 - a on bins k and N - k of the band, 1.0 elsewhere; then as the denoiser
+#     detect         : m = magnitude; r = 0.5 (m[max(f - G, 0)] + m[min(f + G, F - 1)]); d = int(rint(32768 (m - r) / (m + r + 1.0)));
+#                      num[q][j] = sum chip d, den[q][j] = sum d d over the cells of bit j (int64)
+#     host           : z = num / sqrt(den) (0 where den = 0); score[q] = sqrt(mean_j z^2); the smallest q with the largest score
+WATERMARK_LO = 22                    # VV_WATERMARK_LO: first band bin (about 0.5 kHz at 24 kHz)
+WATERMARK_K = 320                    # VV_WATERMARK_K: band bins LO ... LO + K - 1 (to about 8 kHz)
+WATERMARK_G = 4                      # VV_WATERMARK_G: frames that share a chip
+WATERMARK_P = 64                     # VV_WATERMARK_P: groups in a pattern period (65 536 samples)
+WATERMARK_NB = 24                    # VV_WATERMARK_NB: message bits: 16 of payload, MSB first, then the CRC-8 of its two bytes, MSB first
+WATERMARK_Q = WATERMARK_P * WATERMARK_G                  # alignments searched (whole hops)
+WATERMARK_MAX_STRENGTH = 0.5
+WATERMARK_DETECT_MAX_N = 1 << 24     # the longest clip watermark_stats / vv_pcm_watermark_detect take
+WATERMARK_THRESHOLD = 2.6153          # 1.3 x 2.0118, the largest score of the null pool measured on this mirror (profiles/watermark/notes.md)
+_WATERMARK_CHIPS = {}
+
+
+def check_watermark_key(key):
+    """Validate ``output_watermark_key``: None = no watermark, else an integer 0 ... 2^64 - 1.  -> None or the int."""
+    if key is None:
+        return None
+    if isinstance(key, bool) or not isinstance(key, (int, np.integer)) or not 0 <= int(key) < 1 << 64:
+        raise ValueError("output_watermark_key must be None or an integer in 0 ... 2^64 - 1")
+    return int(key)
+
+
+def check_watermark_payload(payload):
+    """Validate a watermark payload: None stays None (the engine's), else an integer 0 ... 65535.  -> None or the int."""
+    if payload is None:
+        return None
+    if isinstance(payload, bool) or not isinstance(payload, (int, np.integer)) or not 0 <= int(payload) <= 0xFFFF:
+        raise ValueError("the watermark payload must be an integer in 0 ... 65535")
+    return int(payload)
+
+
+def check_watermark_strength(strength, zero: bool = False):
+    """Validate ``output_watermark_strength``: a number a with 0 < a <= 0.5 (``zero``: 0 as well, which returns the input).  -> the float."""
+    ok = not isinstance(strength, bool) and isinstance(strength, (int, float)) and 0.0 <= float(strength) <= WATERMARK_MAX_STRENGTH
+    if not ok or (float(strength) == 0.0 and not zero):
+        raise ValueError(f"output_watermark_strength must be a number in {'0 ... ' if zero else '(0, '}{WATERMARK_MAX_STRENGTH:g}{'' if zero else ']'}")
+    return float(strength)
+
+
+def watermark_message(payload: int) -> int:
+    """The 24 message bits as one integer: payload << 8 | CRC-8 of its two big-endian bytes; bit j of the message is bit 23 - j of it."""
+    p = check_watermark_payload(payload)
+    if p is None:
+        raise ValueError("the watermark payload must be an integer in 0 ... 65535")
+    return p << 8 | flac_crc8(bytes([p >> 8, p & 0xFF]))
+
+
+def watermark_words(key: int, count: int) -> List[int]:
+    """The first ``count`` outputs of SplitMix64 from the state ``key``."""
+    mask, s, out = (1 << 64) - 1, check_watermark_key(key), []
+    if s is None:
+        raise ValueError("a watermark key is needed")
+    for _ in range(count):
+        s = (s + 0x9E3779B97F4A7C15) & mask
+        z = s
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+        out.append(z ^ (z >> 31))
+    return out
+
+
+def watermark_chips(key: int) -> np.ndarray:
+    """The chip table of a key: int8 [P][K] of +-1; cell e = g K + (k - LO) takes bit e % 64 (LSB first) of word e // 64.  Made on the
+    host only: the device reads the table and hashes nothing."""
+    key = check_watermark_key(key)
+    if key not in _WATERMARK_CHIPS:
+        cells = WATERMARK_P * WATERMARK_K
+        words = np.array(watermark_words(key, cells // 64), dtype=np.uint64)
+        bits = (words[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+        table = (2 * bits.astype(np.int8) - 1).reshape(WATERMARK_P, WATERMARK_K)
+        table.setflags(write=False)
+        if len(_WATERMARK_CHIPS) >= 16:
+            _WATERMARK_CHIPS.clear()
+        _WATERMARK_CHIPS[key] = table
+    return _WATERMARK_CHIPS[key]
+
+
+def _watermark_starts(n: int) -> np.ndarray:
+    return (np.arange(-(-n // DENOISE_H) + 3, dtype=np.int64) - 3) * DENOISE_H
+
+
+def watermark_embed(pcm, key: int, payload: int, strength: float = 0.2) -> np.ndarray:
+    """The embedder: the host mirror of vv_pcm_watermark, bit for bit.  pcm int16 [n] -> int16 [n]: the denoiser's
+    loop with the gain (chip (2 bit_j - 1) > 0) ? gp : gm on the band bins and their mirrors at alignment 0, gp = 1.0 + a and
+    gm = 1.0 - a; a = 0 is computed like any other and gives the input back."""
+    x = _as_pcm16(pcm)
+    a = check_watermark_strength(strength, zero=True)
+    chips, msg = watermark_chips(key), watermark_message(payload)
+    N, H, LO, K = DENOISE_N, DENOISE_H, WATERMARK_LO, WATERMARK_K
+    gp, gm = np.float64(1.0) + np.float64(a), np.float64(1.0) - np.float64(a)
+    n = x.size
+    M = -(-n // H)
+    fr = _denoise_frames(x, _watermark_starts(n))
+    re, im = denoise_fft(fr, np.zeros_like(fr))
+    g = (np.arange(M + 3) // WATERMARK_G) % WATERMARK_P
+    j = (np.arange(K)[None, :] + 7 * g[:, None]) % WATERMARK_NB
+    sign = 2 * ((msg >> (WATERMARK_NB - 1 - j)) & 1) - 1
+    band = np.where(chips[g] * sign > 0, gp, gm)
+    gain = np.ones((M + 3, N), np.float64)
+    gain[:, LO: LO + K] = band
+    gain[:, N - LO - K + 1: N - LO + 1] = band[:, ::-1]                               # bin N - k carries the gain of bin k
+    re, _im = denoise_fft(re * gain, im * gain, inverse=True)
+    c = (re * denoise_tables()[0][None, :]).reshape(M + 3, 4, H)
+    acc = np.zeros((M, H), np.float64)
+    for q in range(4):
+        acc = acc + c[q: q + M, 3 - q]
+    return np.clip(np.rint(acc / DENOISE_SCALE), -32768.0, 32767.0).astype(np.int16).reshape(-1)[:n]
+
+
+def watermark_cells(pcm) -> np.ndarray:
+    """The detector's cell values (the mirror of vv_pcm_watermark_detect's second kernel): int32 [F][K], F = ceil(n / H) + 3."""
+    x = _as_pcm16(pcm)
+    if x.size > WATERMARK_DETECT_MAX_N:
+        raise ValueError(f"watermark_cells: at most {WATERMARK_DETECT_MAX_N} samples, got {x.size}")
+    fr = _denoise_frames(x, _watermark_starts(x.size))
+    re, im = denoise_fft(fr, np.zeros_like(fr))
+    re, im = re[:, WATERMARK_LO: WATERMARK_LO + WATERMARK_K], im[:, WATERMARK_LO: WATERMARK_LO + WATERMARK_K]
+    m = np.sqrt(re * re + im * im)
+    f = np.arange(m.shape[0])
+    r = 0.5 * (m[np.maximum(f - WATERMARK_G, 0)] + m[np.minimum(f + WATERMARK_G, m.shape[0] - 1)])
+    return np.rint(32768.0 * (m - r) / (m + r + 1.0)).astype(np.int32)
+
+
+def watermark_stats(pcm, key: int, cells: Optional[np.ndarray] = None) -> np.ndarray:
+    """The detector's integer statistic (the mirror of vv_pcm_watermark_detect): int64 [256][24][2] = {num, den} per alignment q and bit j.
+    Integers, so the order of the sums is free: the frames that share a group at alignment q = 4 a + b are summed first."""
+    d = (watermark_cells(pcm) if cells is None else np.asarray(cells)).astype(np.int64)
+    chips = watermark_chips(key).astype(np.int64)
+    F, K, G, P, NB = d.shape[0], WATERMARK_K, WATERMARK_G, WATERMARK_P, WATERMARK_NB
+    out = np.zeros((WATERMARK_Q, NB, 2), np.int64)
+    fold = lambda v: np.pad(v, ((0, 0), (0, -K % NB))).reshape(v.shape[0], -1, NB).sum(axis=1)  # noqa: E731  [T][K] -> [T][(k - LO) % NB]
+    jj = np.arange(NB)[None, :]
+    for b in range(G):
+        t = (np.arange(F) + b) // G                                                   # frame f lies in block t; its group is (t + a) % P
+        T = int(t[-1]) + 1
+        D, E = np.zeros((T, K), np.int64), np.zeros((T, K), np.int64)
+        np.add.at(D, t, d)
+        np.add.at(E, t, d * d)
+        E, rows = fold(E), np.arange(T)[:, None]
+        for a in range(P):
+            g = (np.arange(T) + a) % P
+            src = (jj - 7 * g[:, None]) % NB                                          # bit j of group g collects the bins with (k - LO) % NB = j - 7 g
+            out[G * a + b, :, 0] = fold(chips[g] * D)[rows, src].sum(axis=0)
+            out[G * a + b, :, 1] = E[rows, src].sum(axis=0)
+    return out
+
+
+class WatermarkResult(NamedTuple):
+    """What the detector says of one clip: ``payload`` is None unless ``crc_ok``; ``offset`` = the alignment q of the largest score."""
+    score: float
+    present: bool
+    offset: int
+    payload: Optional[int]
+    crc_ok: bool
+    z: Tuple[float, ...]
+
+
+def watermark_decide(stats) -> WatermarkResult:
+    """The host step behind the statistic: stats int64 [256][24][2] -> the result record."""
+    s = np.asarray(stats, dtype=np.int64).reshape(WATERMARK_Q, WATERMARK_NB, 2)
+    num, den = s[..., 0].astype(np.float64), s[..., 1].astype(np.float64)
+    z = np.zeros_like(num)
+    np.divide(num, np.sqrt(den), out=z, where=den > 0.0)
+    score = np.sqrt(np.mean(z * z, axis=1))
+    q = int(np.argmax(score))                                                         # the first of the largest
+    bits = 0
+    for v in z[q]:
+        bits = bits << 1 | int(v > 0.0)
+    payload = bits >> 8
+    crc_ok = watermark_message(payload) == bits
+    present = bool(score[q] >= WATERMARK_THRESHOLD)
+    return WatermarkResult(float(score[q]), present, q, payload if crc_ok else None, crc_ok, tuple(float(v) for v in z[q]))
+
+
+def watermark_detect(pcm, key: int) -> WatermarkResult:
+    """The detector on the host: watermark_decide(watermark_stats(pcm, key))."""
+    return watermark_decide(watermark_stats(pcm, key))
+
+
 class AudioProcessor:
     """Static helpers, same names and semantics as the reference class."""
 

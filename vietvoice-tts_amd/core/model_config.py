@@ -113,6 +113,12 @@ class ModelConfig:
     output_denoise_bias: Optional[Sequence[float]] = None      # the profile: 513 non-negative magnitudes (bins 0 ... 512 of a 1024-point Hann frame of
                                             # int16 samples).  None = the model's own: what its decoder emits for an empty mel (HipSynth.vocoder_bias),
                                             # which needs the HIP engine
+    output_watermark_key: Optional[int] = None      # the key of the audio watermark, 0 ... 2^64 - 1; None = no watermark.  With a key
+                                            # every utterance carries a 16-bit payload as a multiplicative spread-spectrum mark, embedded behind pitch and
+                                            # tempo and before the loudness step; TTSEngine.detect_watermark reads it back.  vv_pcm_watermark on the HIP
+                                            # engine, audio_processor.watermark_embed on the host.  Not available in synthesize_stream
+    output_watermark_payload: int = 0       # the payload, 0 ... 65535 (a request id); a request may bring its own (submit(watermark_payload=))
+    output_watermark_strength: float = 0.2  # the gain step a of the mark, 0 < a <= 0.5: a band cell is scaled by 1 + a or 1 - a
 
     def __post_init__(self):
         if not 0.1 <= self.speed <= 5.0:
@@ -160,6 +166,12 @@ class ModelConfig:
         self.output_denoise = check_denoise(self.output_denoise)
         bias = check_denoise_bias(self.output_denoise_bias)
         self.output_denoise_bias = None if bias is None else [float(v) for v in bias]      # a plain list: to_dict / JSON keep working
+        from .audio_processor import check_watermark_key, check_watermark_payload, check_watermark_strength
+        self.output_watermark_key = check_watermark_key(self.output_watermark_key)
+        if self.output_watermark_payload is None:
+            raise ValueError("the watermark payload must be an integer in 0 ... 65535")
+        self.output_watermark_payload = check_watermark_payload(self.output_watermark_payload)
+        self.output_watermark_strength = check_watermark_strength(self.output_watermark_strength)
         from ..model_spec import check_cfg_interval
         self.cfg_interval = check_cfg_interval(self.cfg_interval)      # (lo, hi) floats, 0 <= lo <= hi <= 1; a list (from_dict of JSON) becomes the tuple
         from ..model_spec import check_apg

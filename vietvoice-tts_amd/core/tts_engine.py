@@ -174,8 +174,8 @@ class TTSEngine:
 
     def _device_output(self, options=None) -> bool:
         """The chunks stay in HBM until the final bytes exist: asked for by ``output_stage="device"``, and taken on the HIP engine whenever a
-        rate, an encoding, a loudness target, a limiter, a pitch, a tempo or a denoiser strength is set: the engine's, or the own one of
-        a request of ``options`` (the batch's RequestOptions).  False = today's path: one copy per chunk group, the numpy join."""
+        rate, an encoding, a loudness target, a limiter, a pitch, a tempo, a denoiser strength or a watermark key is set: the engine's, or
+        the own one of a request of ``options`` (the batch's RequestOptions).  False = today's path: one copy per chunk group, the numpy join."""
         rate, enc = self._output_options()
         return self.model_session_manager.engine is not None and (
             self.config.output_stage == "device" or rate is not None or enc != "pcm16"
@@ -194,8 +194,8 @@ class TTSEngine:
 
     def _finish_host(self, waves, options: Optional[RequestOptions] = None) -> np.ndarray:
         """One request's chunks -> its final audio on the host: the reference's join, the denoiser's mirror directly behind it (N19), then
-        the host mirrors of pitch and tempo (N14, N18), the loudness normalisation (N12), the limiter (N13), the output rate and the
-        encoding.  ``options`` = the request's own values, None (or a None field) = the engine's."""
+        the host mirrors of pitch and tempo (N14, N18), the watermark (N22), the loudness normalisation (N12), the limiter (N13), the
+        output rate and the encoding.  ``options`` = the request's own values, None (or a None field) = the engine's."""
         from .audio_processor import encode_output, limit_peaks, normalize_loudness, resample_output, shift_prosody
         cfg, (o,) = self.config, self._resolved([options], 1)
         final = self.audio_processor.concatenate_with_crossfade_improved(waves, cfg.cross_fade_duration, cfg.sample_rate)
@@ -205,6 +205,9 @@ class TTSEngine:
             final = denoise_pcm(pcm16(final), self._denoise_bias_host(), o.denoise)
         if o.pitch is not None or o.tempo is not None:
             final = shift_prosody(pcm16(final), o.pitch, o.tempo, formants=o.formants)
+        if o.watermark_payload is not None:
+            from .audio_processor import watermark_embed
+            final = watermark_embed(pcm16(final), cfg.output_watermark_key, o.watermark_payload, cfg.output_watermark_strength)
         if o.loudness is not None:
             final = normalize_loudness(pcm16(final), cfg.sample_rate, o.loudness, cfg.output_peak_dbfs, limiter=o.limiter)
         elif o.limiter is not None:
@@ -216,7 +219,7 @@ class TTSEngine:
 
     def _finish_device(self, dev_pcm, counts, options: Optional[List[RequestOptions]] = None) -> List[np.ndarray]:
         """``_synthesize_device(.., device_out=True)``'s result and the number of chunks of each request -> the requests' final audio:
-        one HipSynth.finish_output call (join, denoiser, prosody, loudness, limiter, rate, encoding in HBM; one device-to-host copy).
+        one HipSynth.finish_output call (join, denoiser, prosody, watermark, loudness, limiter, rate, encoding in HBM; one device-to-host copy).
         ``options`` = per request its own values, None (or a None field) = the engine's.  finish_output reads a column that is None for
         every request as "off" and calls nothing for it."""
         pcm, spans = dev_pcm
@@ -227,9 +230,14 @@ class TTSEngine:
         cfg = self.config
         opts = self._resolved(options, len(counts))
         rate, enc = self._output_options()
+        mark = {}
+        if cfg.output_watermark_key is not None:          # N22: the column travels only with a key; without one the call is the one of ever
+            mark = dict(watermark=column(opts, "watermark_payload"), watermark_key=cfg.output_watermark_key,
+                        watermark_strength=cfg.output_watermark_strength)
         return self.model_session_manager.engine.finish_output(
             pcm, plans, cfg.cross_fade_duration, cfg.sample_rate, rate, enc, peak_dbfs=cfg.output_peak_dbfs, flac_lpc_order=cfg.flac_lpc_order,
-            denoise_bias=cfg.output_denoise_bias, **{name: column(opts, name) for name in ("loudness", "limiter", "pitch", "tempo", "formants", "denoise")})
+            denoise_bias=cfg.output_denoise_bias, **{name: column(opts, name) for name in ("loudness", "limiter", "pitch", "tempo", "formants", "denoise")},
+            **mark)
 
     def _set_ode_plan(self) -> None:
         """The solver and its step report as the config has them now (the report is off while the plan changes under it)."""
@@ -418,7 +426,11 @@ class TTSEngine:
         With ``output_loudness`` set the call raises ValueError at once (N12): an integrated loudness is a property of the WHOLE utterance.
         ``output_limiter`` alone streams (N13): a LimiterStream in front of the output rate / encoding holds back 2L + H samples.
         ``output_pitch`` / ``output_tempo`` raise ValueError at once as well (N14): every frame position depends on the whole past.
-        ``output_denoise`` (N19) raises ValueError at once too: there is no block-wise denoiser yet."""
+        ``output_denoise`` (N19) raises ValueError at once too: there is no block-wise denoiser yet.  So does ``output_watermark_key``
+        (N22): the mark is laid on the frames of the whole utterance."""
+        if self.config.output_watermark_key is not None:  # N22: the same frames as the denoiser's; there is no block-wise embedder
+            raise ValueError("synthesize_stream cannot honour output_watermark_key: the watermark is embedded in the whole utterance; use "
+                             "synthesize, or unset output_watermark_key")
         if self.config.output_denoise is not None:        # N19: frames reach 768 samples back; a block-wise DenoiseStream does not exist yet
             raise ValueError("synthesize_stream cannot honour output_denoise: the denoiser works on the whole joined utterance; use "
                              "synthesize, or unset output_denoise")
@@ -544,6 +556,42 @@ class TTSEngine:
             self.audio_processor.save_audio(wave, output_path, self.output_rate, cfg.output_encoding)
             logger.info("Audio saved to: %s", output_path)
         return wave, time.time() - start
+
+    def detect_watermark(self, audio, key: Optional[int] = None):
+        """Look for this engine's watermark in ``audio``: a path or the bytes of a WAV or FLAC file (any rate and channel
+        count, taken in like a reference clip: mono at ``config.sample_rate``), or an int16 array at that rate; a list of those is
+        answered with a list, from one device call for all clips.  ``key`` = None: the engine's ``output_watermark_key``.  On the HIP
+        engine the statistic is vv_pcm_watermark_detect's, else the host mirror's (equal, bit for bit).
+        -> audio_processor.WatermarkResult: score, present, offset (the alignment in hops), payload (None unless crc_ok), crc_ok, z."""
+        from .audio_processor import WATERMARK_DETECT_MAX_N, check_watermark_key, watermark_decide, watermark_stats
+        key = check_watermark_key(self.config.output_watermark_key if key is None else key)
+        if key is None:
+            raise ValueError("detect_watermark needs a key: give one, or set output_watermark_key")
+        many = isinstance(audio, (list, tuple))
+        clips = []
+        for a in (audio if many else [audio]):
+            if isinstance(a, (str, bytes, bytearray)):
+                a = self.audio_processor.load_audio(bytes(a) if isinstance(a, bytearray) else a, self.config.sample_rate)
+            a = np.ascontiguousarray(np.asarray(a).reshape(-1))
+            if a.dtype != np.int16 or a.size > WATERMARK_DETECT_MAX_N:
+                raise ValueError(f"detect_watermark: int16 PCM of at most {WATERMARK_DETECT_MAX_N} samples expected")
+            clips.append(a)
+        if not clips:
+            return []
+        eng = self.model_session_manager.engine
+        if eng is None:
+            out = [watermark_decide(watermark_stats(a, key)) for a in clips]
+        else:
+            import torch
+            from ..pcm_stage import _place
+            offs, end = _place([a.size for a in clips], 8)
+            flat = np.zeros(max(end, 8), np.int16)
+            for o, a in zip(offs, clips):
+                flat[o: o + a.size] = a
+            with self._lock:
+                stats = eng.pcm_watermark_detect(torch.from_numpy(flat).to(eng.device), [[o, a.size] for o, a in zip(offs, clips)], key).cpu().numpy()
+            out = [watermark_decide(s) for s in stats]
+        return out if many else out[0]
 
     def validate_configuration(self, reference_audio: Optional[str] = None) -> bool:
         if reference_audio is None:

@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.13 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.14 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -972,6 +972,86 @@ int vv_pcm_denoise_bias(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t*
     Prof p(c, VV_PROF_ELEMWISE, (double)total_frames * 10.0 * 512.0 * 10.0, (double)total_frames * (2.0 * VV_DENOISE_N + 16.0 * (VV_DENOISE_N / 2 + 1)), st);
     KCHK(c, vvk_pcm_denoise_bias(x, (long long)n_x, (const long long*)rows, R, (long long)total_frames, (long long)max_frames, window, twiddles, out,
                                  ws, st, &m__));
+    return 0;
+}
+
+// N22: the keyed audio watermark and its detector.  As with N12 ... N19 the rows come in host memory too: everything is checked before a launch.
+// Accounted under the class of the denoiser, whose loop the embedder is.
+uint64_t vv_pcm_watermark_ws_bytes(int R) { return vvk_pcm_watermark_ws_bytes(R); }
+
+int vv_pcm_watermark(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const int8_t* chips,
+                     int64_t n_chips, double gp, double gm, const double* window, const double* twiddles, int16_t* y, int64_t n_y, void* ws,
+                     uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0) return c->fail(-22, "vv_pcm_watermark: bad sizes (1 <= R <= 65535)");
+    if (int e = check_ptrs(c, "vv_pcm_watermark", {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host}, {"chips", chips, 4}, {"window", window, 8},
+                                                   {"twiddles", twiddles, 8}, {"y", y, 2}, {"ws", ws, 8}})) return e;
+    if (n_chips < (int64_t)VV_WATERMARK_P * VV_WATERMARK_K)
+        return c->fail(-22, "vv_pcm_watermark: chips of %lld entries, %d are needed", (long long)n_chips, VV_WATERMARK_P * VV_WATERMARK_K);
+    if (!(gp >= 1.0 && gp <= 1.5 && gm >= 0.5 && gm <= 1.0)) return c->fail(-22, "vv_pcm_watermark: gains 1 <= gp <= 1.5 and 0.5 <= gm <= 1 are needed");
+    if (spans_overlap(x, 2ull * n_x, y, 2ull * n_y))
+        return c->fail(-22, "vv_pcm_watermark: y overlaps x (a hop reads the input under its neighbours: not in place)");
+    std::vector<std::pair<int64_t, int64_t>> on_y;
+    int64_t total_frames = 0, max_hops = 1, total_hops = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 4 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "vv_pcm_watermark: row %d has a negative field", r);
+        if (q[3] >= ((int64_t)1 << VV_WATERMARK_NB)) return c->fail(-22, "vv_pcm_watermark: row %d: a message of %d bits is needed", r, VV_WATERMARK_NB);
+        if (!fits(q[0], q[1], n_x) || q[1] > ((int64_t)1 << 30))
+            return c->fail(-22, "vv_pcm_watermark: row %d does not fit the %lld samples of x", r, (long long)n_x);
+        if (!fits(q[2], q[1], n_y)) return c->fail(-22, "vv_pcm_watermark: row %d does not fit the %lld samples of y", r, (long long)n_y);
+        const int64_t M = (q[1] + VV_DENOISE_H - 1) / VV_DENOISE_H, hops = M > 0 ? M : 1;
+        if (q[1] > 0) on_y.emplace_back(q[2], q[2] + q[1]);
+        total_frames += M + 3;
+        total_hops += hops;
+        if (hops > max_hops) max_hops = hops;
+    }
+    std::sort(on_y.begin(), on_y.end());
+    for (size_t i = 1; i < on_y.size(); ++i)
+        if (on_y[i].first < on_y[i - 1].second) return c->fail(-22, "vv_pcm_watermark: rows overlap on y");
+    if (int e = check_ws(c, "vv_pcm_watermark", ws_bytes, vvk_pcm_watermark_ws_bytes(R))) return e;
+    Prof p(c, VV_PROF_ELEMWISE, (double)total_hops * 8.0 * 10.0 * 512.0 * 10.0, 16.0 * (double)total_hops * VV_DENOISE_H, st);
+    KCHK(c, vvk_pcm_watermark(x, (long long)n_x, (const long long*)rows, R, (long long)total_frames, (long long)max_hops, chips, gp, gm, window,
+                              twiddles, y, (long long)n_y, ws, st, &m__));
+    return 0;
+}
+
+uint64_t vv_pcm_watermark_detect_ws_bytes(int64_t total_frames, int R) { return vvk_pcm_watermark_detect_ws_bytes((long long)total_frames, R); }
+
+int vv_pcm_watermark_detect(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, const int8_t* chips,
+                            int64_t n_chips, const double* window, const double* twiddles, int64_t* stats, int64_t n_stats, int32_t* cells_out,
+                            int64_t n_cells, void* ws, uint64_t ws_bytes, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_stats < 0 || n_cells < 0) return c->fail(-22, "vv_pcm_watermark_detect: bad sizes (1 <= R <= 65535)");
+    if (int e = check_ptrs(c, "vv_pcm_watermark_detect", {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host}, {"chips", chips, 4},
+                                                          {"window", window, 8}, {"twiddles", twiddles, 8}, {"stats", stats, 8},
+                                                          {"cells_out", cells_out, 4, true}, {"ws", ws, 8}})) return e;
+    if (n_chips < (int64_t)VV_WATERMARK_P * VV_WATERMARK_K)
+        return c->fail(-22, "vv_pcm_watermark_detect: chips of %lld entries, %d are needed", (long long)n_chips, VV_WATERMARK_P * VV_WATERMARK_K);
+    int64_t total_frames = 0, max_frames = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 4 * (size_t)r;
+        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0) return c->fail(-22, "vv_pcm_watermark_detect: row %d has a negative field", r);
+        if (q[1] > VV_WATERMARK_DETECT_MAX_N || !fits(q[0], q[1], n_x))
+            return c->fail(-22, "vv_pcm_watermark_detect: row %d: a signal of at most %d samples inside the %lld samples of x is needed", r,
+                           VV_WATERMARK_DETECT_MAX_N, (long long)n_x);
+        const int64_t F = (q[1] + VV_DENOISE_H - 1) / VV_DENOISE_H + 3;
+        total_frames += F;
+        if (F > max_frames) max_frames = F;
+    }
+    const int64_t per_row = (int64_t)VV_WATERMARK_P * VV_WATERMARK_G * VV_WATERMARK_NB * 2;
+    if (n_stats / per_row < R)
+        return c->fail(-22, "vv_pcm_watermark_detect: stats of %lld entries, %lld are needed", (long long)n_stats, (long long)R * per_row);
+    if (cells_out && n_cells / VV_WATERMARK_K < total_frames)
+        return c->fail(-22, "vv_pcm_watermark_detect: cells_out of %lld entries, %lld are needed", (long long)n_cells,
+                       (long long)total_frames * VV_WATERMARK_K);
+    if (int e = check_ws(c, "vv_pcm_watermark_detect", ws_bytes, vvk_pcm_watermark_detect_ws_bytes((long long)total_frames, R))) return e;
+    Prof p(c, VV_PROF_ELEMWISE, (double)total_frames * (10.0 * 512.0 * 10.0 + 3.0 * VV_WATERMARK_K * VV_WATERMARK_P * VV_WATERMARK_G),
+           (double)total_frames * (2.0 * VV_DENOISE_H + 24.0 * VV_WATERMARK_K) + 8.0 * (double)R * per_row, st);
+    KCHK(c, vvk_pcm_watermark_detect(x, (long long)n_x, (const long long*)rows, R, (long long)total_frames, (long long)max_frames, chips, window,
+                                     twiddles, (long long*)stats, (int*)cells_out, ws, st, &m__));
     return 0;
 }
 

@@ -121,6 +121,18 @@ int vvk_pcm_denoise(const int16_t* x, long long n_x, const long long* rows, int 
 unsigned long long vvk_pcm_denoise_bias_ws_bytes(long long total_frames, int R);
 int vvk_pcm_denoise_bias(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_frames,
                          const double* window, const double* twiddles, double* out, void* ws, hipStream_t st, const char** err);
+// N22 keyed audio watermark (vv_watermark.hip): the denoiser's loop with a keyed gain of gp or gm per band cell; rows R x 4 {x_off, n, y_off,
+// message}; chips int8 [64][320].  total_frames = the sum of M + 3, max_hops = the largest max(M, 1)
+unsigned long long vvk_pcm_watermark_ws_bytes(int R);
+int vvk_pcm_watermark(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_hops, const int8_t* chips,
+                      double gp, double gm, const double* window, const double* twiddles, int16_t* y, long long n_y, void* ws, hipStream_t st,
+                      const char** err);
+// the detector: band magnitudes per frame, one int32 contrast per cell, {num, den} per alignment and bit -> stats [R][256][24][2]; rows R x 4
+// {x_off, n, 0, 0}; max_frames = the largest M + 3; cells_out NULL or int32 [total_frames][320]
+unsigned long long vvk_pcm_watermark_detect_ws_bytes(long long total_frames, int R);
+int vvk_pcm_watermark_detect(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_frames,
+                             const int8_t* chips, const double* window, const double* twiddles, long long* stats, int* cells_out, void* ws,
+                             hipStream_t st, const char** err);
 // N15 FLAC output (vv_flac.hip): per frame of 4096 samples the exhaustive fixed-predictor / Rice search, the frames' offsets, the bit packing;
 // rows R x 4 {src_off, n, frame0, last}
 unsigned long long vvk_flac_frame_bound(long long m);

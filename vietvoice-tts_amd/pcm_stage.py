@@ -1,4 +1,4 @@
-"""The PCM stage of HipSynth (DESIGN §8 N10 ... N19, layering described there): per call a pure plan_* function of host values (every
+"""The PCM stage of HipSynth (DESIGN §8 N10 ... N22, layering described there): per call a pure plan_* function of host values (every
 ValueError, the row table, the derived sizes; no GPU needed) and a launch method of PcmStage, which HipSynth inherits."""
 from typing import Optional
 
@@ -319,6 +319,56 @@ def plan_finish_denoise(R: int, denoise=None):
         return None
     vals = [check_denoise(v) for v in _per_request("finish_output", denoise, R, "denoise entry per request")]
     return None if all(v is None for v in vals) else vals
+
+
+def plan_watermark(rows, payloads, strength, n_x: int, out_n: Optional[int] = None, overlaps: bool = False):
+    """vv_pcm_watermark's rows {x_off, n, y_off} and one payload per row (or one for all), validated -> (4-entry rows {x_off, n, y_off,
+    message}, gp = 1.0 + a, gm = 1.0 - a, n_y); strength a in 0 ... 0.5 (0 gives the input back); out_n: _out_arg; overlaps: out shares
+    memory with x."""
+    from .core.audio_processor import check_watermark_strength, watermark_message
+    rows = _int_rows("pcm_watermark", rows, (3,), "3 entries {x_off, n, y_off}")
+    payloads = _per_request("pcm_watermark", payloads, len(rows), "payload per row")
+    a = check_watermark_strength(strength, zero=True)
+    spans, full = [], []
+    for r, p in zip(rows, payloads):
+        xo, n, yo = r
+        if min(xo, n, yo) < 0 or xo + n > n_x or n > 1 << 30:
+            raise ValueError(f"pcm_watermark: row {r} does not fit the buffers ({n_x} samples of x)")
+        if n:
+            spans.append((yo, yo + n))
+        full.append([xo, n, yo, watermark_message(p)])
+    if overlaps:
+        raise ValueError("pcm_watermark: out overlaps x (a hop reads the input under its neighbours: not in place)")
+    return full, 1.0 + a, 1.0 - a, _spans("pcm_watermark", spans, out_n)
+
+
+def plan_watermark_detect(rows, n_x: int):
+    """vv_pcm_watermark_detect's rows {x_off, n}, or {x_off, n, 0, 0}, validated -> (4-entry rows, frame offsets [R + 1]: request r's frames
+    0 ... M + 2 are frame_offs[r] ... frame_offs[r + 1] - 1)."""
+    from .core.audio_processor import DENOISE_H, WATERMARK_DETECT_MAX_N
+    rows = [r + [0] * (4 - len(r)) for r in _int_rows("pcm_watermark_detect", rows, (2, 4), "2 entries {x_off, n} or 4 {x_off, n, 0, 0}")]
+    frame_offs = [0]
+    for r in rows:
+        if min(r) < 0 or r[1] > WATERMARK_DETECT_MAX_N or r[0] + r[1] > n_x:
+            raise ValueError(f"pcm_watermark_detect: row {r}: a signal of at most {WATERMARK_DETECT_MAX_N} samples inside the {n_x} samples of x "
+                             f"is needed")
+        frame_offs.append(frame_offs[-1] + -(-r[1] // DENOISE_H) + 3)
+    return rows, frame_offs
+
+
+def plan_finish_watermark(R: int, watermark=None, key=None, strength=0.2):
+    """finish_output's ``watermark``: one payload for every request or a per-request list with None entries -> (key, the list, strength), or
+    None when no request has one (nothing new is then called).  A payload without a key is refused."""
+    from .core.audio_processor import check_watermark_key, check_watermark_payload, check_watermark_strength
+    if watermark is None:
+        return None
+    vals = [check_watermark_payload(v) for v in _per_request("finish_output", watermark, R, "watermark entry per request")]
+    if all(v is None for v in vals):
+        return None
+    key = check_watermark_key(key)
+    if key is None:
+        raise ValueError("finish_output: a watermark payload needs watermark_key")
+    return key, vals, check_watermark_strength(strength)
 
 
 def plan_flac(rows, n_x: int, sample_rate, lpc_order: int = 0):
@@ -697,6 +747,63 @@ class PcmStage:
         self.pcm_denoise(buf, rows, [s for i, s in enumerate(denoise) if s is not None and lens[i] > 0], bias, out=new)
         return new
 
+    # ------------------------------------------------------------------ keyed audio watermark (N22)
+    def _watermark_chips(self, key: int) -> torch.Tensor:
+        """The chip table of ``key`` (int8 [64][320], made on the host) on the device; the last key's table is kept."""
+        from .core.audio_processor import watermark_chips
+        have = self._tables.get("watermark")
+        if have is None or have[0] != key:
+            have = self._tables["watermark"] = (key, torch.from_numpy(watermark_chips(key).copy()).to(self.device))
+        return have[1]
+
+    def pcm_watermark(self, x: torch.Tensor, rows, key: int, payloads, strength: float = 0.2, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The keyed watermark on R requests in one call (vv_pcm_watermark), bit for bit core.audio_processor.watermark_embed.
+        x int16 flat on the device; rows = HOST rows (x_off, n, y_off); key = 0 ... 2^64 - 1; payloads = one value in 0 ... 65535 or one per
+        row; strength 0 ... 0.5 (0 gives the input back).  out = None: a new buffer, or a flat int16 device tensor that does not overlap x.
+        -> y.  The rows are validated here; the call never synchronises."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        n_x = x.numel()
+        shared = isinstance(out, torch.Tensor) and out.data_ptr() < x.data_ptr() + 2 * n_x and x.data_ptr() < out.data_ptr() + 2 * out.numel()
+        rows, gp, gm, n_y = plan_watermark(rows, payloads, strength, n_x, _out_arg(out)[0], shared)
+        chips = self._watermark_chips(key)
+        y, R = self._out(out, n_y), len(rows)
+        rows_d, rows_h = self._upload(rows)
+        window, tw = self._denoise_tables
+        ws = self._ws(self.lib.vv_pcm_watermark_ws_bytes(R))
+        self._call(self.lib.vv_pcm_watermark, x.data_ptr(), n_x, rows_d.data_ptr(), rows_h.data_ptr(), R, chips.data_ptr(), chips.numel(), gp, gm,
+                   window.data_ptr(), tw.data_ptr(), y.data_ptr(), y.numel(), ws.data_ptr(), ws.numel() * 8)
+        return y
+
+    def pcm_watermark_detect(self, x: torch.Tensor, rows, key: int, cells: bool = False):
+        """The detector's statistic of R clips in one call (vv_pcm_watermark_detect), equal to
+        core.audio_processor.watermark_stats: x int16 flat on the device, rows = HOST rows (x_off, n), n <= 2^24 -> stats, the int64 device
+        tensor [R][256][24][2] of {num, den} per alignment and bit (core.audio_processor.watermark_decide turns a clip's into the result
+        record); with ``cells`` (stats, cells, frame_offs): the int32 device tensor [frames][320] of the cell values, request r's frames
+        cells[frame_offs[r] : frame_offs[r + 1]].  The rows are validated here; the call never synchronises."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        from .core.audio_processor import WATERMARK_K, WATERMARK_NB, WATERMARK_Q
+        rows, frame_offs = plan_watermark_detect(rows, x.numel())
+        chips = self._watermark_chips(key)
+        (rows_d, rows_h), R = self._upload(rows), len(rows)
+        window, tw = self._denoise_tables
+        stats = torch.empty((R, WATERMARK_Q, WATERMARK_NB, 2), dtype=torch.int64, device=self.device)
+        cell = torch.empty((frame_offs[-1], WATERMARK_K), dtype=torch.int32, device=self.device) if cells else None
+        ws = self._ws(self.lib.vv_pcm_watermark_detect_ws_bytes(frame_offs[-1], R))
+        self._call(self.lib.vv_pcm_watermark_detect, x.data_ptr(), x.numel(), rows_d.data_ptr(), rows_h.data_ptr(), R, chips.data_ptr(), chips.numel(),
+                   window.data_ptr(), tw.data_ptr(), stats.data_ptr(), stats.numel(), _ptr(cell), 0 if cell is None else cell.numel(), ws.data_ptr(),
+                   ws.numel() * 8)
+        return (stats, cell, frame_offs) if cells else stats
+
+    def _watermark(self, buf: torch.Tensor, offs, lens, key: int, payloads, strength: float):
+        """The watermark step of finish_output: the requests with a payload go through pcm_watermark into a copy of the buffer, the others
+        stay as they are."""
+        sel = [i for i, p in enumerate(payloads) if p is not None and lens[i] > 0]
+        if not sel:
+            return buf
+        new = buf.clone()
+        self.pcm_watermark(buf, [[offs[i], lens[i], offs[i]] for i in sel], key, [payloads[i] for i in sel], strength, out=new)
+        return new
+
     # ------------------------------------------------------------------ FLAC output (N15, N16)
     def pcm_flac(self, x: torch.Tensor, rows, sample_rate: int, lpc_order: int = 0):
         """FLAC frames of R final signals in one call (vv_pcm_flac), byte for byte core.audio_processor.flac_encode_frames.
@@ -825,8 +932,8 @@ class PcmStage:
 
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
                       encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0,
-                      formants=None, denoise=None, denoise_bias=None):
-        """The whole output stage of R requests on the caller's stream: join (-> denoiser) (-> pitch and tempo) (-> loudness) (-> limiter) (-> output rate)
+                      formants=None, denoise=None, denoise_bias=None, watermark=None, watermark_key=None, watermark_strength: float = 0.2):
+        """The whole output stage of R requests on the caller's stream: join (-> denoiser) (-> pitch and tempo) (-> watermark) (-> loudness) (-> limiter) (-> output rate)
         (-> G.711), then ONE device-to-host copy of the final bytes.  pcm int16 on the device, plans = per request its chunks' (src_off, len)
         spans.  pitch (semitones) / tempo = one value for every request, or a per-request list with None entries (N14; all None = nothing
         new is called): core.audio_processor.prosody_plan turns them into a WSOLA stretch and a rate conversion on the joined signal, and
@@ -844,6 +951,10 @@ class PcmStage:
         denoise (N19) = one strength (0 < s <= 16) for every request, or a per-request list with None entries; None or all None = nothing
         new is called.  A request with a strength goes through pcm_denoise directly behind the join and before pitch and tempo, into a new
         buffer, against denoise_bias: 513 values or a float64 device tensor, None = the model's own (vocoder_bias).
+        watermark (N22) = one payload (0 ... 65535) for every request, or a per-request list with None entries; None or all None = nothing
+        new is called.  A request with a payload goes through pcm_watermark under watermark_key (0 ... 2^64 - 1; a payload without a key is
+        refused) at watermark_strength, directly behind pitch and tempo (and formants) and before the loudness step, into a new buffer: the
+        loudness gain, the peak ceiling and the limiter's promise hold for what is heard, and the detector does not mind a constant gain.
         -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
         from .core.audio_processor import check_flac_lpc_order, resample_len
         if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
@@ -858,6 +969,9 @@ class PcmStage:
             formants = [check_formants(f) for f in _per_request("finish_output", formants, len(lens), "formants entry per request")]
         if pitch is not None:
             buf, offs, lens = self._prosody(buf, offs, lens, pitch, tempo, formants)
+        watermark = plan_finish_watermark(len(lens), watermark, watermark_key, watermark_strength)
+        if watermark is not None:
+            buf = self._watermark(buf, offs, lens, *watermark)
         for mode, sel, tg in groups:       # in place on the joined buffer: the apply passes are elementwise
             rows, meas = [[offs[i], lens[i], offs[i]] for i in sel], None
             if mode is None:

@@ -1,5 +1,7 @@
 """What one request may ask for beside its text, speed and voice: one record from ``BatchingFrontend.submit`` to the stage that consumes
-each value.  A new per-request option is a field here, its check in ``checked``, and its use in that one stage."""
+each value.  A new per-request option is a field here, its check in ``checked``, and its use in that one stage.  The
+record of N21 -- eleven fields, ``cfg_reuse`` the last -- is what every request without a watermark payload carries, unchanged; a request
+with one carries ``MarkedRequestOptions``, the same record with that field behind the eleven."""
 from __future__ import annotations
 
 from dataclasses import dataclass, replace
@@ -8,7 +10,7 @@ from typing import List, Optional, Tuple
 
 @dataclass(frozen=True)
 class RequestOptions:
-    """None = the engine's value (``resolved``)."""
+    """None = the engine's value (``resolved``).  ``watermark_payload`` (N22) reads None here; MarkedRequestOptions carries one."""
     cfg_strength: Optional[float] = None                   # the acoustic stage, per chunk (N7)
     cfg_interval: Optional[Tuple[float, float]] = None     # (N8)
     apg_eta: Optional[float] = None                        # (N11)
@@ -20,12 +22,13 @@ class RequestOptions:
     formants: Optional[str] = None                         # (N18)
     denoise: Optional[float] = None                        # (N19)
     cfg_reuse: Optional[int] = None                        # the acoustic stage, per chunk (N21)
+    watermark_payload = None                               # no field: only MarkedRequestOptions has a payload (N22)
 
     @classmethod
     def checked(cls, cfg_strength=None, cfg_interval=None, apg_eta=None, apg_norm=None, loudness=None, limiter=None, pitch=None, tempo=None,
-                formants=None, denoise=None, cfg_reuse=None) -> "RequestOptions":
+                formants=None, denoise=None, cfg_reuse=None, watermark_payload=None) -> "RequestOptions":
         """The validated, normalised record; ValueError in the words of the option's own check, the first in this order."""
-        from .core.audio_processor import check_denoise, check_formants, check_limiter, check_loudness, check_prosody
+        from .core.audio_processor import check_denoise, check_formants, check_limiter, check_loudness, check_prosody, check_watermark_payload
         from .model_spec import check_apg, check_cfg_interval, check_cfg_reuse
         loudness, _pk = check_loudness(loudness)
         check_limiter(limiter)
@@ -40,18 +43,35 @@ class RequestOptions:
             if cfg_strength != cfg_strength or abs(cfg_strength) == float("inf"):
                 raise ValueError("cfg_strength must be a finite number or None")
         cfg_reuse = check_cfg_reuse(cfg_reuse)
-        return cls(cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise, cfg_reuse)
+        watermark_payload = check_watermark_payload(watermark_payload)
+        eleven = (cfg_strength, cfg_interval, apg_eta, apg_norm, loudness, limiter, pitch, tempo, formants, denoise, cfg_reuse)
+        return RequestOptions(*eleven) if watermark_payload is None else MarkedRequestOptions(*eleven, watermark_payload)
 
     def resolved(self, config) -> "RequestOptions":
-        """Every None replaced by the engine's value: the one place that says "own value, else the engine's"."""
+        """Every None replaced by the engine's value: the one place that says "own value, else the engine's".  The watermark payload is the
+        engine's only where the engine has a key (the result is then a MarkedRequestOptions); a payload of its own on an engine without
+        a key is refused."""
+        keyed = getattr(config, "output_watermark_key", None) is not None
+        payload = self.watermark_payload
+        if payload is not None and not keyed:
+            raise ValueError("watermark_payload needs an engine with output_watermark_key")
+        if payload is None and keyed:
+            payload = getattr(config, "output_watermark_payload", 0)
         mine = RequestOptions(config.cfg_strength, config.cfg_interval, config.apg_eta, config.apg_norm, config.output_loudness,
                               config.output_limiter, config.output_pitch, config.output_tempo, config.output_formants, config.output_denoise,
                               getattr(config, "cfg_reuse", None))
-        return replace(mine, **{name: v for name, v in vars(self).items() if v is not None})
+        full = replace(mine, **{name: v for name, v in vars(self).items() if v is not None and name != "watermark_payload"})
+        return full if payload is None else MarkedRequestOptions(**vars(full), watermark_payload=payload)
 
     def wants_output_stage(self) -> bool:
         """Some step behind the join is asked for: what ``TTSEngine._device_output`` asks of the requests."""
-        return any(v is not None for v in (self.loudness, self.limiter, self.pitch, self.tempo, self.denoise))
+        return any(v is not None for v in (self.loudness, self.limiter, self.pitch, self.tempo, self.denoise, self.watermark_payload))
+
+
+@dataclass(frozen=True)
+class MarkedRequestOptions(RequestOptions):
+    """A request's options with a watermark payload (N22): 0 ... 65535, embedded under the engine's ``output_watermark_key``."""
+    watermark_payload: Optional[int] = None
 
 
 def column(options: List[RequestOptions], name: str) -> Optional[list]:
