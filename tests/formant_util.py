@@ -110,6 +110,12 @@ DEVICE_CASES = (
     ("constant", "constant", 1500, -4, None), ("zeros", "zeros", 700, 4, 1.25),
 )
 
+# one sample less than, equal to and one more than an analysis frame of NA samples, in x (and at no tempo in y), and in y alone
+FRAME_EDGE_CASES = (
+    ("len1023", "speech", 1023, 4, None), ("len1024", "speech", 1024, -4, None), ("len1025", "speech", 1025, 12, None),
+    ("y1023", "speech", 767, 4, 0.75), ("y1024", "speech", 1280, -4, 1.25), ("y1025", "silence_then_signal", 1281, -12, 1.25),
+)
+
 
 def device_case(name, kind, n, pitch, tempo):
     """One case as the device call takes it, with the mirror's results: x, y = shift_prosody's result, tn / td, z, h, flat."""

@@ -321,3 +321,16 @@ def test_front_end_honours_a_per_request_strength(tiny):
     for a, o in zip(alone, outs):
         assert o.dtype == np.int16 and np.array_equal(a, o)                           # alone == in a batch with another strength and a plain request
     assert np.array_equal(outs[0], ap.denoise_pcm(plain, model_bias, 1.0)) and not np.array_equal(outs[0], plain)
+
+
+def test_rows_of_no_samples_and_of_exactly_a_frame_equal_the_mirror(eng, biases):
+    """The lengths tests/denoise_util.LENGTHS lacks, 0 and 1024, between the others around a hop and a frame, in one call."""
+    ap = _ap()
+    bias, bias_d = biases
+    lens = (0, 1, 255, 256, 257, 1023, 1024, 1025)
+    sigs = [du.speechlike(n, 300 + n) for n in lens]
+    rows_b = [k % 2 for k in range(len(sigs))]
+    for x, b, (z, mag) in zip(sigs, rows_b, _launch(eng, sigs, 1.0, rows_b, bias_d)):
+        want, want_mag = ap.denoise_pcm(x, bias[b], 1.0, mags=True)
+        assert mag.shape == want_mag.shape == (du.frames_of(x.size), du.N) and np.array_equal(mag, want_mag), x.size
+        assert z.dtype == np.int16 and np.array_equal(z, want), x.size

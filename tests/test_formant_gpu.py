@@ -324,3 +324,12 @@ def test_front_end_request_with_keep_alone_equals_itself_in_a_mixed_batch(tiny):
         assert o.dtype == np.int16 and np.array_equal(a, o)                           # alone == in a batch with a shifted and a plain request
     assert np.array_equal(outs[0], keep_formants(base[LONG], shifted, 1, 1))          # the output stage, given equal input: exact
     assert not np.array_equal(outs[0], shifted)
+
+
+def test_rows_at_the_edges_of_an_analysis_frame_equal_the_mirror(eng):
+    """x, and y alone, of one sample less than, equal to and one more than an analysis frame of NA samples, in one call."""
+    items = [fu.device_case(*c) for c in fu.FRAME_EDGE_CASES]
+    assert {1023, 1024, 1025} <= {c["x"].size for c in items} and {1023, 1024, 1025} <= {c["y"].size for c in items}
+    res = _launch(eng, items)
+    assert len(res) == len(items)
+    _same(res, items)

@@ -102,3 +102,35 @@ def test_polyphase_is_opt_in(hip_tiny):
     want = AudioProcessor.load_audio(wav, 24000, resampler="polyphase")
     assert got.shape == want.shape and int(np.abs(got.astype(np.int32) - want.astype(np.int32)).max()) <= 1
     assert not np.array_equal(got, NPZ[GOLD["cases"][9]["key"] + "_pcm"])                 # and it is NOT the reference's arithmetic
+
+
+def test_a_clip_past_the_grid_of_the_ingest_kernel(hip_tiny):
+    """4096 * 256 + 257 outputs from one clip: the grid stops at 4096 workgroups, so the kernel's loop takes a second trip."""
+    import torch
+    from vietvoice_tts_amd.core.audio_processor import ratecv
+    eng = hip_tiny["f32"]
+    n_out = 4096 * 256 + 257
+    rng = np.random.default_rng(11)
+    big = rng.integers(-20000, 20000, size=(n_out - 1) // 2 + 1).astype(np.int16)          # 12 kHz mono: I / O = 1 / 2
+    small = rng.integers(-20000, 20000, size=6).astype(np.int16)                           # 16 kHz stereo, 3 frames, behind it
+    pcm = torch.frombuffer(bytearray(big.tobytes() + b"\0" * (-2 * big.size % 4) + small.tobytes()), dtype=torch.uint8).cuda()
+    off2 = 2 * big.size + (-2 * big.size % 4)
+    desc = [[0, 2, 1, big.size, 1, 2, 0, n_out], [off2, 2, 2, 3, 2, 3, n_out, 4]]
+    y = eng.ingest_pcm(pcm, desc, n_out + 4).cpu().numpy()
+    assert np.array_equal(y[:n_out], ratecv(big, 12000, 24000).astype(np.float32))
+    mono = ((small[0::2].astype(np.int64) + small[1::2]) >> 1).astype(np.int16)
+    assert np.array_equal(y[n_out:], ratecv(mono, 16000, 24000).astype(np.float32))
+
+
+def test_normalize_a_zero_length_clip_between_two_others(hip_tiny):
+    """A clip of no samples inside a batch, first and last too: its neighbours' slots of the scratch (off / 8192 + clip) stay their own."""
+    import torch
+    from vietvoice_tts_amd.core import AudioProcessor
+    eng = hip_tiny["f32"]
+    rng = np.random.default_rng(5)
+    a, z, b = (rng.standard_normal(8193) * 3000).astype(np.float32), np.zeros(0, np.float32), (rng.standard_normal(8191) * 500 + 40).astype(np.float32)
+    for clips in ([a, z, b], [z, b, z], [a, z, z, b]):
+        off = np.concatenate([[0], np.cumsum([len(c) for c in clips])]).astype(np.int64)
+        out = eng.normalize_clips(torch.from_numpy(np.concatenate(clips)).cuda(), torch.from_numpy(off).cuda()).cpu().numpy()
+        for j, c in enumerate(clips):
+            assert np.array_equal(out[off[j]: off[j + 1]], AudioProcessor.normalize_to_int16(c) if len(c) else z.astype(np.int16)), j

@@ -297,3 +297,42 @@ def test_vocos_preset_lengths(tmp_path):
         e.cleanup()
     assert len(plan) > 1 and host.size > 0
     assert dev.shape == host.shape and np.array_equal(dev, host)      # hop * max(T - 1, 0) per chunk, from the host's own frame counts
+
+
+# ------------------------------------------------------------------ the edge rows of tools/output_host_check.py
+@pytest.mark.parametrize("n,sr,d", [(0, 8000, 0.0), (1, 8000, 1 / 8000 + 1e-9), (16, 8000, 0.002 + 1e-9), (100, 16000, 100 / 16000 + 1e-9),
+                                    (2400, 24000, 0.1)])
+def test_join_edge_sets_equal_the_host_mirror(eng, n, sr, d):
+    """Junction sizes 0, 1, exactly the ring and more; chunks of 1, 2, 7, 8, 9 samples, one shorter than n and one shorter than 2 n, single
+    chunks, a 32767 first and last in a chunk, and eight chunks that start 0 ... 7 samples past a 16-byte boundary."""
+    from tests.host_check_util import tool
+    from vietvoice_tts_amd.core import AudioProcessor
+    t = tool("output")
+    assert int(d * sr) == n
+    sets, residues = t.edge_sets(n, seed=n)
+    plane, reqs = t.pack(sets, residues)
+    assert [so % 8 for so, _n in reqs[4]] == list(range(8))                        # torch's allocations are 16-byte aligned and more
+    total = sum(max(sum(c.size for c in cs), 8) + 8 for cs in sets) + 2 * GUARD
+    out = torch.full((total,), SENTINEL, dtype=torch.int16, device=DEV)
+    pd = _dev(plane)
+    assert pd.data_ptr() % 16 == 0
+    _o, offs, lens = eng.join_chunks(pd, reqs, d, sr, out=out, out_base=GUARD)
+    host = out.cpu().numpy()
+    written = np.zeros(total, bool)
+    for cs, o, m in zip(sets, offs, lens):
+        written[o: o + m] = True
+        want = np.asarray(AudioProcessor.concatenate_with_crossfade_improved([c.copy() for c in cs], d, sr))
+        assert np.array_equal(host[o: o + m], want), (n, [c.size for c in cs])
+    assert (host[~written] == SENTINEL).all(), "a sample outside a request's slice was written"
+
+
+def test_join_with_a_junction_whose_pairwise_tree_is_seven_deep(eng):
+    """8191 samples: the deepest tree numpy's pairwise sum builds over one buffer (the fixture's 8192 and 8193 stay 6 deep)."""
+    from tests.host_check_util import tool
+    from vietvoice_tts_amd.core import AudioProcessor
+    t = tool("output")
+    n, sr, d = t.DEEP
+    sets = t.deep_tree_sets()
+    for cs, got in zip(sets, _join(eng, sets, d, sr)):
+        want = np.asarray(AudioProcessor.concatenate_with_crossfade_improved([c.copy() for c in cs], d, sr))
+        assert np.array_equal(got, want), [c.size for c in cs]

@@ -284,3 +284,33 @@ def test_engine_edit_speech(tmp_path):
     with pytest.raises(ValueError, match="max_chunk_duration"):
         e.edit_speech(clip, text, [(0.1 * dur, 0.1 * dur)], fix_duration=[8.5])
     e.cleanup()
+
+
+@pytest.mark.parametrize("n_rows", [257, 600])
+def test_splice_with_two_and_three_passes_of_descriptor_rows(hip_tiny, n_rows):
+    """More rows than the 256 the splice kernel stages in LDS per pass: the rows of tools/edit_host_check.py (one starts at output sample 0,
+    one ends at ld_out - 1, one reads src[n_src - 1], the items' rows shuffled over the passes), against numpy."""
+    from tests.host_check_util import tool
+    eng = hip_tiny["f32"]
+    for B, ld_out in ((1, 1000), (3, 1000), (3, 4)):
+        src, rows, want = tool("edit").splice_case(n_rows, B, ld_out, seed=n_rows + B)
+        out = eng.edit_splice(torch.from_numpy(src).to(DEV), rows, B, ld_out).cpu().numpy()
+        assert np.array_equal(out, want), (n_rows, B, ld_out)
+
+
+def test_restore_past_the_grid(hip_tiny, tiny_setup):
+    """B = 8, N = 4096, n_mel = 100: 819200 float4s against a grid of 2048 x 256 threads, so the kernel's loop takes a second trip."""
+    spec, _, _ = tiny_setup
+    eng = hip_tiny["f32"]
+    B, N, M, cd = 8, 4096, spec.n_mel, spec.cond_dim
+    assert M == 100 and B * N * (M // 4) > 2048 * 256
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn((B, N, M), generator=g)
+    cat = torch.randn((B, N, cd), generator=g)
+    keep = (torch.rand((B, N + 3), generator=g) < 0.5).to(torch.uint8)
+    keep[:, 0], keep[:, N - 1] = 1, 1
+    seq_len = torch.tensor([0, N, N - 1, 1, N, 2049, N, 4095], dtype=torch.int32)
+    got = eng.edit_restore(x.to(DEV), {"cat_mel_text": cat.to(DEV), "seq_len": seq_len.to(DEV)}, keep.to(DEV)).cpu()
+    m = (torch.arange(N)[None, :] < seq_len[:, None]) & (keep[:, :N] != 0)
+    want = torch.where(m[..., None], cat[..., :M], x)
+    assert torch.equal(got, want)

@@ -330,3 +330,20 @@ def test_edit_speech_honours_the_option(tiny):
     base = _call(e, lambda: e.edit_speech(clip, text, parts, fix_duration=fix, seed=11)[0], key=None)
     got = _call(e, lambda: e.edit_speech(clip, text, parts, fix_duration=fix, seed=11)[0])
     assert np.array_equal(got, ap.watermark_embed(base, wu.KEY, 0x1234, 0.2)) and not np.array_equal(got, base)
+
+
+def test_rows_of_no_samples_and_of_exactly_a_frame_equal_the_mirror(eng):
+    """The lengths tests/watermark_util.LENGTHS lacks, 0 and 1024, between the others around a hop and a frame: embedder and detector."""
+    ap = _ap()
+    lens = (0, 1, 255, 256, 257, 1023, 1024, 1025)
+    sigs = [wu.speechlike(n, 300 + n) for n in lens]
+    payloads = [(0x1234, 0xBEEF, 0)[k % 3] for k in range(len(sigs))]
+    marked = _embed(eng, sigs, payloads, 0.2)
+    for x, p, z in zip(sigs, payloads, marked):
+        assert z.dtype == np.int16 and np.array_equal(z, ap.watermark_embed(x, wu.KEY, p, 0.2)), x.size
+    plane, reqs = pack_requests([[s] for s in marked], gap=5)
+    stats, cells, frame_offs = eng.pcm_watermark_detect(_dev(plane), [[xo, n] for ((xo, n),) in reqs], wu.KEY, cells=True)
+    stats, cells = stats.cpu().numpy(), cells.cpu().numpy()
+    for k, x in enumerate(marked):
+        assert np.array_equal(cells[frame_offs[k]: frame_offs[k + 1]], ap.watermark_cells(x)), x.size
+        assert np.array_equal(stats[k], ap.watermark_stats(x, wu.KEY)), x.size

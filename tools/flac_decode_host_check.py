@@ -9,7 +9,7 @@ heap buffers) with  clang++ -std=c++20 -fsanitize=address,undefined  and feeds i
     must give the mirror's samples);
 the sanitizers must stay silent.  A stream the container parser refuses never reaches the kernels and is only counted.  Needs no GPU.
 
-    python tools/flac_decode_host_check.py [--cxx clang++] [--keep DIR] [--valid | --malformed]"""
+    python tools/flac_decode_host_check.py [--cxx clang++] [--keep DIR] [--valid | --malformed] [--san asan|tsan]"""
 import argparse
 import os
 import shutil
@@ -27,9 +27,13 @@ def find_cxx():
     return os.environ.get("CXX") or next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++")) if c and os.path.exists(c)), None)
 
 
-def build(cxx, work):
-    exe = os.path.join(work, "flac_decode_host_check")
-    subprocess.run([cxx, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-pthread", "-w",
+SANITIZERS = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}
+TIME_LIMIT = 600      # seconds for one run of the built program
+
+
+def build(cxx, work, san="asan"):
+    exe = os.path.join(work, "flac_decode_host_check" + ("" if san == "asan" else "_" + san))
+    subprocess.run([cxx, "-std=c++20", "-O1", "-g", *SANITIZERS[san], "-pthread", "-w",
                     os.path.join(ROOT, "tools", "flac_decode_host_check.cpp"), "-o", exe], check=True)
     return exe
 
@@ -61,7 +65,7 @@ def run(exe, work, streams):
     fin, fout = os.path.join(work, "in.bin"), os.path.join(work, "out.bin")
     with open(fin, "wb") as f:
         f.write(struct.pack("<2q", R, len(buf)) + np.array(rows, np.int64).tobytes() + buf)
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"), timeout=TIME_LIMIT)
     if r.returncode != 0 or r.stderr.strip():
         raise SystemExit(f"the host program failed (exit {r.returncode}):\n{r.stderr[-4000:]}")
     raw = open(fout, "rb").read()
@@ -81,17 +85,18 @@ def run(exe, work, streams):
     return R, skipped, bad
 
 
-def main():
+def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--cxx", default=find_cxx() or "clang++")
     p.add_argument("--keep", default="")
+    p.add_argument("--san", choices=("asan", "tsan"), default="asan", help="address + undefined behaviour, or thread")
     p.add_argument("--valid", action="store_true")
     p.add_argument("--malformed", action="store_true")
-    a = p.parse_args()
+    a = p.parse_args(argv)
     from tests.flac_decode_util import cases, malformed, malformed_corpus
     work = a.keep or tempfile.mkdtemp(prefix="flac_decode_host_")
     os.makedirs(work, exist_ok=True)
-    exe = build(a.cxx, work)
+    exe = build(a.cxx, work, a.san)
     ok = True
     if a.valid or not a.malformed:
         n, skipped, bad = run(exe, work, [(c[0], c[1]) for c in cases()])

@@ -8,7 +8,7 @@ output windows, the destination 2, 4 and 6 bytes past an 8-byte boundary, and a 
 equal the numpy mirror (stats ==, PCM array_equal), nothing outside a request's window may be written, and the sanitizers must stay
 silent.  Needs no GPU; takes a few minutes.
 
-    python tools/limiter_host_check.py [--cxx clang++] [--keep DIR] [--quick]"""
+    python tools/limiter_host_check.py [--cxx clang++] [--keep DIR] [--quick] [--san asan|tsan] [--reduced]"""
 import argparse
 import os
 import shutil
@@ -53,16 +53,22 @@ def _gpu_cases(L):
     return mod._cases(L)
 
 
-def main():
+SANITIZERS = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], "tsan": ["-fsanitize=thread"]}
+TIME_LIMIT = 600      # seconds for one run of the built program
+
+
+def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--cxx", default=os.environ.get("CXX") or next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++")) if c and os.path.exists(c)), "clang++"))
     p.add_argument("--keep", default="")
+    p.add_argument("--san", choices=("asan", "tsan"), default="asan", help="address + undefined behaviour, or thread")
     p.add_argument("--quick", action="store_true", help="L = 3 only")
-    a = p.parse_args()
+    p.add_argument("--reduced", action="store_true", help="L = 3: every request once, six at each destination offset, the windows in place")
+    a = p.parse_args(argv)
     work = a.keep or tempfile.mkdtemp(prefix="limit_host_")
     os.makedirs(work, exist_ok=True)
     exe = os.path.join(work, "limiter_host_check")
-    subprocess.run([a.cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    subprocess.run([a.cxx, "-std=c++20", "-O1", "-g", "-ffp-contract=off", *SANITIZERS[a.san],
                     "-pthread", "-w", os.path.join(ROOT, "tools", "limiter_host_check.cpp"), "-o", exe], check=True)
 
     def run(items, L, mode, order, gap, in_place=False, yoff=0, windows=None, meas=None, targets=None):
@@ -86,7 +92,7 @@ def main():
             for part in parts + [plane, y0]:
                 f.write(np.ascontiguousarray(part).tobytes())
         env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-        r = subprocess.run([exe, fin, fout] + (["inplace"] if in_place else []) + [f"yoff={yoff}"], capture_output=True, text=True, env=env)
+        r = subprocess.run([exe, fin, fout] + (["inplace"] if in_place else []) + [f"yoff={yoff}"], capture_output=True, text=True, env=env, timeout=TIME_LIMIT)
         if r.returncode != 0 or r.stderr.strip():
             raise SystemExit(f"the host program failed (exit {r.returncode}):\n{r.stderr[-4000:]}")
         raw = open(fout, "rb").read()
@@ -105,7 +111,7 @@ def main():
         return not bad
 
     ok = []
-    for L in ((3,) if a.quick else (3, 120, 1024)):
+    for L in ((3,) if a.quick or a.reduced else (3, 120, 1024)):
         cases = _gpu_cases(3 if L == 1024 else L)
         if L != 3:
             cases = [c for c in cases if c[1].size <= 6000][:6] + ([] if L == 1024 else cases[-1:])      # one thread per GPU thread is slow
@@ -115,6 +121,13 @@ def main():
                 y, st = ap.limit_peaks(x, SR, PEAK, mode, gain=g, L=L)
                 items.append((name, x, g, y, np.array([st["g"], st["e_max"], st["s_min"], st["n_limited"]])))
             every = list(range(len(items)))
+            if a.reduced:
+                W = 2 * L + ap.LIMIT_H
+                win = [(min(x.size, (0, 1, W, x.size // 2, 2047)[k % 5]), 0) for k, (_n, x, *_r) in enumerate(items)]
+                win = [(lo, (x.size - lo, max(0, min(x.size - lo, x.size // 3)), 0, min(x.size - lo, 1))[k % 4]) for k, ((lo, _z), (_n, x, *_r)) in enumerate(zip(win, items))]
+                ok += [run(items, L, mode, every, 3), run(items, L, mode, every, 3, windows=win, in_place=True)]
+                ok += [run(items, L, mode, [13, 9, 11, 6, 0, 12], 2, yoff=k, in_place=k == 2) for k in (1, 2, 3)]
+                continue
             ok += [run(items, L, mode, every, 3), run(items, L, mode, every, 3, in_place=True)]
             if L == 3:
                 ok += [run(items, L, mode, [13, 9, 11, 6, 0, 12], 2), run(items, L, mode, [13], 9)]
@@ -139,7 +152,8 @@ def main():
         g = ap.limiter_pregain(zbar, kept, peak, T) if t is not None else g0
         y, st = ap.limit_peaks(x, SR, PEAK, "true", gain=g, L=120)
         items.append((f"meas{len(items)}", x, g0, y, np.array([st["g"], st["e_max"], st["s_min"], st["n_limited"]])))
-    ok.append(run(items, 120, "true", [0, 1, 2], 3, meas=meas, targets=targets, in_place=True))
+    if not a.reduced:
+        ok.append(run(items, 120, "true", [0, 1, 2], 3, meas=meas, targets=targets, in_place=True))
     if not a.keep:
         shutil.rmtree(work, ignore_errors=True)
     if not all(ok):

@@ -17,8 +17,10 @@
 // tables w and twiddle are the host's (the device evaluates neither a cosine nor a sine).  LDS: element i of a frame lies at i + i / 4, so
 // the four-point groups of the first passes (strides of 4 and 16 doubles) fall on distinct banks.
 #pragma clang fp contract(off)
+#ifndef VV_DENOISE_HOST_CHECK         // tools/denoise_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 #include "vv_denoise_fft.h"      // two_stages, transform, load_frame (shared with vv_watermark.hip)
 
 namespace {
@@ -156,6 +158,7 @@ unsigned long long vvk_pcm_denoise_bias_ws_bytes(long long total_frames, int R) 
     return 16ull * (unsigned long long)(R > 0 ? R : 1) + (unsigned long long)(total_frames > 0 ? total_frames : 1) * (8ull * DB);
 }
 
+#ifndef VV_DENOISE_HOST_CHECK
 int vvk_pcm_denoise(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_hops, const double* strengths,
                     const double* bias, long long n_bias, const double* window, const double* twiddles, int16_t* y, long long n_y, double* mag_out,
                     void* ws, hipStream_t st, const char** err) {
@@ -188,3 +191,4 @@ int vvk_pcm_denoise_bias(const int16_t* x, long long n_x, const long long* rows,
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif

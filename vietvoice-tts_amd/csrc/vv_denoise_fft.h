@@ -2,7 +2,9 @@
 // time behind a bit reversal, in LDS, by a workgroup of 256 threads.  The arithmetic is core/audio_processor.py's denoise_fft, operation by
 // operation; the including file sets "#pragma clang fp contract(off)" in front of the include.  Internal: everything is in an unnamed namespace.
 #pragma once
+#ifndef VV_HIP_HOST_SHIM               // tools/hip_host_shim.h: the host checks bring their own stand-ins
 #include "vv_common.h"
+#endif
 
 namespace {
 

@@ -4,8 +4,10 @@
 //   splice  : [B][ld_out] int16 clips assembled from source clips in HBM by descriptor rows {item, src_off, dst_off, n}:
 //             copied where a row covers a sample, 0 elsewhere (the spans to regenerate, and everything past the clip)
 //   restore : after the last Euler step, x[b][t] = cat[b][t][0:n_mel] wherever keep[b][t] (the known frames, bit for bit)
+#ifndef VV_EDIT_HOST_CHECK            // tools/edit_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 
 namespace {
 
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(256) void edit_restore_kernel(float* __restrict__ x
 
 }  // namespace
 
+#ifndef VV_EDIT_HOST_CHECK
 int vvk_edit_splice(const int16_t* src, long long n_src, const long long* desc, int n_rows, int B, int16_t* out, int ld_out,
                     hipStream_t st, const char** err) {
     if (B < 1 || B > 65535 || n_rows < 0 || ld_out < 4 || ld_out % 4 || n_src < 0) { *err = "edit_splice: bad sizes"; return -22; }
@@ -83,3 +86,4 @@ int vvk_edit_restore(float* x, const float* cat, const uint8_t* keep, int ld_kee
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif

@@ -18,8 +18,10 @@
 //                ascending, every product rounded on its own; z[i] = clamp(rint(w[k + H] v_a + w[k] v_b)).
 // No atomics, no readback; the tables wa, g and w are the host's (the device evaluates neither a cosine nor a power):
 #pragma clang fp contract(off)
+#ifndef VV_FORMANT_HOST_CHECK         // tools/formant_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 
 namespace {
 
@@ -218,6 +220,7 @@ unsigned long long vvk_pcm_formant_ws_bytes(long long total_frames, int R) {
     return 16ull * (unsigned long long)(R > 0 ? R : 1) + F * (2ull * COEF * 8ull) + F * (8ull * FL);
 }
 
+#ifndef VV_FORMANT_HOST_CHECK
 int vvk_pcm_formant(const int16_t* x, long long n_x, const int16_t* y, long long n_y, const long long* rows, int R, long long total_frames,
                     long long max_frames, const double* wa, const double* g, const double* window, int16_t* z, long long n_z, double* h_out,
                     void* ws, hipStream_t st, const char** err) {
@@ -237,3 +240,4 @@ int vvk_pcm_formant(const int16_t* x, long long n_x, const int16_t* y, long long
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif

@@ -12,8 +12,10 @@
 //   chunk sums : one workgroup per 8192-sample buffer; 8 lanes per leaf = numpy's 8 accumulators; tree combined through LDS
 //   mean / peak / scale : streaming passes, clips batched on grid.y
 // The polyphase FIR resampler of rounds 2-4 (vv_resample_poly) stays as an explicit opt-in; it is NOT the reference's arithmetic.
+#ifndef VV_INGEST_HOST_CHECK          // tools/ingest_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 #include "vv_np_sum.h"
 
 namespace {
@@ -145,6 +147,7 @@ __global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict
 
 }  // namespace
 
+#ifndef VV_INGEST_HOST_CHECK
 int vvk_resample_poly(const float* x, int n_in, const double* h, int n_taps, int up, int down, int skip, float* y, int n_out,
                       hipStream_t st, const char** err) {
     if (n_in <= 0 || n_out <= 0 || n_taps <= 0 || up <= 0 || down <= 0 || skip < 0) { *err = "resample: bad shape"; return -22; }
@@ -163,11 +166,13 @@ int vvk_ingest_pcm(const void* pcm, const long long* desc, int n_clips, long lon
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif
 
 size_t vvk_normalize_scratch_bytes(int n_clips, long long total_len) {
     return sizeof(double) * 2 * (size_t)n_clips + sizeof(float) * (size_t)(total_len / NP_BUF + n_clips + 1);
 }
 
+#ifndef VV_INGEST_HOST_CHECK
 int vvk_normalize_clips(const float* x, const long long* off, int n_clips, long long max_len, void* scratch, int16_t* out,
                         hipStream_t st, const char** err) {
     if (n_clips <= 0 || max_len <= 0) { *err = "normalize_clips: empty"; return -22; }
@@ -186,3 +191,4 @@ int vvk_normalize_clips(const float* x, const long long* off, int n_clips, long 
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif

@@ -3,7 +3,9 @@
 // elements on 8 interleaved accumulators, split at (n / 2) & ~7) and accumulates the buffer sums in order.  ONE implementation of
 // that order: a workgroup of 256 threads sums one buffer, 8 lanes per leaf = numpy's 8 accumulators, the tree combined through LDS.
 #pragma once
+#ifndef VV_HIP_HOST_SHIM               // tools/hip_host_shim.h: the host checks bring their own stand-ins
 #include <hip/hip_runtime.h>
+#endif
 
 constexpr int NP_BUF = 8192;          // np.getbufsize(): add.reduce hands the inner loop one buffer at a time
 constexpr int NP_LEAF = 128;          // PW_BLOCKSIZE of numpy's pairwise sum

@@ -16,8 +16,10 @@
 //              integer code, eight samples packed per store where the destination allows.
 // Rounding matters in every line of the join: no fma may form where numpy rounds a product and a sum separately.
 #pragma clang fp contract(off)
+#ifndef VV_OUTPUT_HOST_CHECK          // tools/output_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 #include "vv_np_sum.h"
 
 namespace {
@@ -70,7 +72,11 @@ __global__ __launch_bounds__(256) void join_walk_kernel(const int16_t* __restric
                                                         const long long* __restrict__ reqs, const double* __restrict__ fade, long long n_fade,
                                                         const int* __restrict__ flags, float* __restrict__ gains, int16_t* __restrict__ out,
                                                         long long n_out, int C, int n_chunks) {
+#ifndef VV_OUTPUT_HOST_CHECK
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#else
+    unsigned char* const smem = vv_host::dynamic_lds();                         // the block of the size given at launch
+#endif
     float* v = (float*)smem;                                                     // 128 floats of the pairwise tree
     int16_t* S = (int16_t*)(smem + 512);                                         // S[p % C] = joined sample at position p, the last C positions
     const long long* rq = reqs + 4 * (long long)blockIdx.x;
@@ -257,14 +263,17 @@ __global__ __launch_bounds__(256) void pcm_encode_kernel(const int16_t* __restri
     }
 }
 
+#ifndef VV_OUTPUT_HOST_CHECK
 inline int launched(const char** err) {
     hipError_t he = hipGetLastError();
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif
 
 }  // namespace
 
+#ifndef VV_OUTPUT_HOST_CHECK
 int vvk_join_max_n() { return JOIN_MAX_N; }
 
 int vvk_join_chunks(const int16_t* pcm, long long n_pcm, const long long* chunk_rows, int n_chunks, const long long* req_rows, int R,
@@ -316,3 +325,4 @@ int vvk_pcm_encode(const int16_t* x, long long n_x, const long long* rows, int n
     else pcm_encode_kernel<2><<<grid, 256, 0, st>>>(x, n_x, rows, y, n_y);
     return launched(err);
 }
+#endif

@@ -12,8 +12,10 @@
 //              10 i: in a frame of group g its bins are k - LO = (j + 17 g) % 24 + 24 i (17 = -7 mod 24), so it sums into two registers
 //              and nothing is indexed at run time; then one 64-bit integer LDS add per thread and value.
 #pragma clang fp contract(off)
+#ifndef VV_WATERMARK_HOST_CHECK       // tools/watermark_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 #include "vv_denoise_fft.h"      // two_stages, transform, load_frame (shared with vv_denoise.hip)
 
 namespace {
@@ -189,6 +191,7 @@ unsigned long long vvk_pcm_watermark_detect_ws_bytes(long long total_frames, int
     return 16ull * (unsigned long long)(R > 0 ? R : 1) + (unsigned long long)(total_frames > 0 ? total_frames : 1) * (12ull * WK);
 }
 
+#ifndef VV_WATERMARK_HOST_CHECK
 int vvk_pcm_watermark(const int16_t* x, long long n_x, const long long* rows, int R, long long total_frames, long long max_hops, const int8_t* chips,
                       double gp, double gm, const double* window, const double* twiddles, int16_t* y, long long n_y, void* ws, hipStream_t st,
                       const char** err) {
@@ -225,3 +228,4 @@ int vvk_pcm_watermark_detect(const int16_t* x, long long n_x, const long long* r
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif
