@@ -524,6 +524,9 @@ VV_API int vv_grn(vv_ctx* ctx, int dtype, void* x, float* sumsq, const float* ga
  * [1, 64], pre_slope outside (0, 1], B < 1, T < 1, ld_pcm < T, in / w / pcm NULL, a row of 2 GiB or more. */
 VV_API int vv_conv_post(vv_ctx* ctx, const float* in, const float* w, float bias, int16_t* pcm, int ld_pcm, float* wave_f32,
                  int B, int C, int T, int KW, float pre_slope, const int32_t* len_in, void* stream);
+/* K1: mel [B][F_max][n_mel] f32 = log-mel of audio [B][ld_audio] int16; item b has audio_len[b] / hop + 1 frames, the frames behind them are
+ * zeros.  audio_len is a DEVICE array: a value outside [0, ld_audio] is clamped to the row (wrong audio for that call, never a read outside
+ * the row).  Refused with -22 (nothing launched): audio / audio_len / mel NULL, ld_audio < 1, B < 1 or above 65535, F_max < 1. */
 VV_API int vv_mel(vv_ctx* ctx, const int16_t* audio, int ld_audio, const int32_t* audio_len, float* mel, int B, int F_max,
            void* stream);
 /* K5 GroupNorm over channel-major [B][C][T] fp32 (G groups), optional per-channel affine and fused activation code */

@@ -143,3 +143,105 @@ def ref_solve_reuse(orc, pre, x, method, nfe_step, g, col, report=None):
             if plan.b[j] != 0.0:
                 x = x + (h * plan.b[j]) * k[j]
     return x
+
+
+# ------------------------------------------------------------------------------------------------ shared with tools/elementwise_host_check.py
+EDGE_LENS = (0, TILE - 1, TILE, TILE + 1, TILE + 13)      # an empty item, one frame short of a tile, a tile, one more, a second tile's part
+EDGE_TILES = -(-max(EDGE_LENS) // TILE) + 1               # one more than the longest item needs
+EDGE_COMPUTED = (1, 1, 0, 1, 1)                           # item 2 reuses at this evaluation: no unconditional rows, sums {0, 0}
+EDGE_HAS_OLD = (1, 0, 1, 1, 1)                            # item 1 has nothing stored yet: d_buf is not read for it, E2 = 0
+
+
+def edge_predictions(M, seed=23):
+    """-> (pc, pu, d_old) float32 [sum(EDGE_LENS)][M], the items back to back."""
+    rng = np.random.default_rng(seed + M)
+    R = sum(EDGE_LENS)
+    pc = rng.standard_normal((R, M)).astype(np.float32)
+    pu = rng.standard_normal((R, M)).astype(np.float32)
+    return pc, pu, (pc - pu + 0.25 * rng.standard_normal((R, M))).astype(np.float32)
+
+
+REUSE_LOAD, REUSE_STORE = 1, 2                            # include/vvtts.h: VV_REUSE_LOAD, VV_REUSE_STORE
+
+
+class ReuseStageCase:
+    """One launch of the reuse form of the stage kernel, the operands and the float64 reference of tests/test_cfg_reuse_gpu.py
+    (test_reuse_stage_against_float64) for any shape.  subset ``mixed``: item b computes and stores (b % 4 == 0), reuses (1), computes with
+    its LOAD bit set as well (2: a mapped row is computed whatever LOAD says), is not guided (3).  ``none``: no unconditional row at all,
+    even items reuse (item 0 with a STORE bit that stores nothing), odd ones are not guided.  ``plain``: every row computed, no store."""
+
+    def __init__(self, name, method, stage, lens, N, n_mel, ldp, subset, seed=0, g=2.0, h=0.07):
+        self.name, self.method, self.stage, self.lens, self.N, self.n_mel, self.ldp, self.subset = name, method, stage, tuple(lens), N, n_mel, ldp, subset
+        self.seed, self.g, self.h = seed, g, h
+
+    def ops(self):
+        import torch
+        from vietvoice_tts_amd.model_spec import ODE_METHODS
+        a_t, b_t = ODE_METHODS[self.method]
+        o = type("Ops", (), {})()
+        gen = torch.Generator().manual_seed(2200 + self.seed)
+        B, N, M, i = len(self.lens), self.N, self.n_mel, self.stage
+        o.last = i == len(b_t) - 1
+        o.coef = [np.float32(self.h * float(b_t[j] if o.last else a_t[i + 1][j])) for j in range(i + 1)]
+        o.row_src = torch.cat([b * N + torch.arange(n) for b, n in enumerate(self.lens)]).to(torch.int32)
+        o.item = torch.cat([torch.full((n,), b) for b, n in enumerate(self.lens)])
+        Rc = o.Rc = int(o.row_src.numel())
+        L, S = REUSE_LOAD, REUSE_STORE
+        if self.subset == "mixed":
+            o.modes = [(S, L, L, 0)[b % 4] for b in range(B)]
+            mapped = (o.item % 4 == 0) | (o.item % 4 == 2)
+        elif self.subset == "none":
+            o.modes = [((L | S) if b == 0 else L) if b % 2 == 0 else 0 for b in range(B)]
+            mapped = torch.zeros(Rc, dtype=torch.bool)
+        else:
+            o.modes = [0] * B
+            mapped = torch.ones(Rc, dtype=torch.bool)
+        o.Ru = int(mapped.sum())
+        o.u_row = torch.full((Rc,), -1, dtype=torch.int32)
+        o.u_row[mapped] = Rc + torch.arange(o.Ru, dtype=torch.int32)
+        o.x = torch.randn(B * N, M, generator=gen)
+        o.pred = torch.randn(Rc + o.Ru, self.ldp, generator=gen)
+        o.d_old = torch.randn(Rc, M, generator=gen)
+        o.k_prev = [torch.randn(Rc, M, generator=gen) for _ in range(i)]
+        return o
+
+    def ref(self, o):
+        """-> dict(k, K, acc, mag: float64; guided, has_u, stores: row masks; want_d: d_buf after the launch)."""
+        import torch
+        M, g, i = self.n_mel, self.g, self.stage
+        Rc = o.Rc
+        has_u = o.u_row >= 0
+        loads = (~has_u) & torch.tensor([bool(o.modes[int(b)] & REUSE_LOAD) for b in o.item], dtype=torch.bool)
+        stores = has_u & torch.tensor([bool(o.modes[int(b)] & REUSE_STORE) for b in o.item], dtype=torch.bool)
+        rs = o.row_src.long()
+        pc32 = o.pred[:Rc, :M]
+        pu32 = torch.zeros_like(pc32)
+        pu32[has_u] = o.pred[o.u_row[has_u].long(), :M]
+        pc = pc32.double()
+        D = torch.where(has_u[:, None], pc - pu32.double(), o.d_old.double())
+        guided = has_u | loads
+        k = torch.where(guided[:, None], pc + D * g, pc)
+        K = torch.where(guided[:, None], pc.abs() + abs(g) * D.abs(), pc.abs())
+        acc, mag = o.x[rs].double(), o.x[rs].double().abs()
+        for j in range(i):
+            if o.coef[j] != 0:
+                acc = acc + float(o.coef[j]) * o.k_prev[j].double()
+                mag = mag + abs(float(o.coef[j])) * o.k_prev[j].double().abs()
+        if o.coef[i] != 0:
+            acc = acc + float(o.coef[i]) * k
+            mag = mag + abs(float(o.coef[i])) * K
+        want_d = o.d_old.clone()
+        want_d[stores] = (pc32 - pu32)[stores]               # one fp32 subtraction, stored as it is
+        return dict(k=k, K=K, acc=acc, mag=mag, guided=guided, has_u=has_u, stores=stores, want_d=want_d, pc32=pc32)
+
+
+def reuse_stage_cases():
+    """n_mel 4 and 100, ldp tight and + 4, 1 / 3 / 86 rows, the three subsets, a first, a middle and a last stage."""
+    shapes = ((4, 4, (1,), 5), (4, 8, (1, 1, 1), 5), (100, 100, (1, 1, 1), 5), (100, 104, (40, 17, 29), 40), (4, 8, (40, 17, 29), 40))
+    cs, n = [], 0
+    for subset in ("mixed", "none", "plain"):
+        for method, stage in (("euler", 0), ("rk4", 1), ("rk4", 3), ("heun2", 1)):
+            M, ldp, lens, N = shapes[n % len(shapes)]
+            cs.append(ReuseStageCase(f"reuse/{subset}/{method}{stage}/M{M}_ld{ldp}_Rc{sum(lens)}", method, stage, lens, N, M, ldp, subset, seed=n))
+            n += 1
+    return cs

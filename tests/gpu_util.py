@@ -1611,6 +1611,13 @@ def ln_cases():
     return cs
 
 
+def ln_host_cases():
+    """For tools/elementwise_host_check.py alone: tail parts with tail_row0 == R, no row in the tail.  vvk_ln_mod refuses that launch
+    (test_layernorm_refusals_write_nothing: tail_row0_at_R), so the device never sees it; the kernel must still read no part buffer."""
+    return [LnCase(f"ln/{tag}/tail2_rowR_both", n_delta=2, tail_row0=5, tail_parts=(2, 2), out_bf16=b, delta_bf16=b, seed=170)
+            for tag, b in (("f32_f32", False), ("bf16_bf16", True))]
+
+
 # ---- GroupNorm (groupnorm_kernel)
 ACT_MISH = 4
 
@@ -1783,6 +1790,7 @@ def gn_cases():
             cs.append(GnCase(f"gn/{where}{k}", data=f"{where}{k}", seed=30 + k))
             cs.append(GnCase(f"gn/{where}{k}_n2400", B=1, C=8, T=600, G=2, data=f"{where}{k}", seed=31 + k))
             cs.append(GnCase(f"gn/{where}{k}_T301", T=301, data=f"{where}{k}", seed=32 + k))
+    cs.append(GnCase("gn/n200", B=1, C=4, T=100, G=2, seed=19))              # 50 float4s: the last wave sums nothing, the third a part
     assert len({c.name for c in cs}) == len(cs)
     return cs
 
@@ -1803,6 +1811,7 @@ class TeCase:
     vocab_rows: int = 5
     text_len: tuple = (4, 6)
     seed: int = 0
+    far_ids: bool = False               # ids of -5 and vocab_rows + 3 inside the text: clamped well beyond the table on both sides
     kernel = "text_embed_kernel"
 
     def ops(self):
@@ -1811,6 +1820,8 @@ class TeCase:
         # ids walk through vocab_rows - 3 .. vocab_rows + 1 and -2: id + 1 reaches the last row and is clamped beyond it on both sides
         o.ids = (torch.arange(self.B * self.ld_ids).view(self.B, self.ld_ids) % 6 + self.vocab_rows - 4).to(torch.int32)
         o.ids[:, 0] = -2
+        if self.far_ids:
+            o.ids[:, 0], o.ids[:, 1] = -5, self.vocab_rows + 3
         o.emb, o.pos = torch.randn(self.vocab_rows, self.Dt, generator=g), torch.randn(self.N, self.Dt, generator=g)
         o.text_len = torch.tensor(self.text_len, dtype=torch.int32)
         return o
@@ -1849,6 +1860,7 @@ def te_cases():
     cs.append(TeCase("te/N_lt_ld", N=4, text_len=(6, 2), seed=11))
     cs.append(TeCase("te/B1_Dt4", B=1, Dt=4, text_len=(5,), seed=12))
     cs.append(TeCase("te/Dt100_blocks", B=3, N=40, Dt=100, ld_ids=33, text_len=(33, 1, 17), seed=13))      # more than one workgroup
+    cs.append(TeCase("te/far_ids", text_len=(6, 2), far_ids=True, seed=14))
     return cs
 
 
@@ -1944,6 +1956,7 @@ def dw_cases():
     for name, lens in (("len0_1", (0, 1)), ("lenN_gtN", (40, 45)), ("len_null", None), ("len_neg", (-3, 39))):
         cs.append(DwCase(f"dw/{name}", lens=lens, seed=len(cs)))
     cs.append(DwCase("dw/B3_K31", KW=31, B=3, lens=(40, 15, 16), seed=len(cs)))
+    cs.append(DwCase("dw/K1", KW=1, lens=(40, 0), seed=len(cs)))
     return cs
 
 
@@ -2069,6 +2082,10 @@ def grn_cases():
             cs.append(GrnCase(f"grn/{tag}/{name}", lens=lens, bf16=bf, seed=50))
         cs.append(GrnCase(f"grn/{tag}/zero_channel", zero_channel=65, bf16=bf, seed=51))
         cs.append(GrnCase(f"grn/{tag}/C512_B1", C=512, B=1, lens=(33,), bf16=bf, seed=52))       # two channels per thread in the mean
+        cs.append(GrnCase(f"grn/{tag}/C320", C=320, bf16=bf, seed=53))                             # the second trip of the mean's loop: one wave of four
+        for N in (4, 5):
+            cs.append(GrnCase(f"grn/{tag}/N{N}", N=N, lens=(N, N + 5), bf16=bf, seed=54 + N))
+        cs.append(GrnCase(f"grn/{tag}/len0_N_gtN", B=3, lens=(0, 40, 45), bf16=bf, seed=60))
     return cs
 
 
@@ -2118,14 +2135,15 @@ def _mel_frames(a, L, spec, window, edge_repeat=False):
     """int16 clip a[:L] -> float64 frames [L // hop + 1][n_fft], centred, reflected without repeating the edge sample, windowed."""
     n_fft, hop = spec.n_fft, spec.hop_length
     pos = torch.arange(L // hop + 1)[:, None] * hop + torch.arange(n_fft)[None, :] - n_fft // 2
+    S = max(L, 1)                                         # an empty clip has one frame, of the row's first (padding) sample
     if edge_repeat:
         pos = torch.where(pos < 0, -pos - 1, pos)
-        pos = torch.where(pos >= L, 2 * L - 1 - pos, pos)
+        pos = torch.where(pos >= S, 2 * S - 1 - pos, pos)
     else:
         pos = torch.where(pos < 0, -pos, pos)
-        pos = torch.where(pos >= L, 2 * (L - 1) - pos, pos)
-    pos = pos.clamp(0, L - 1)
-    return a[:L].double()[pos] / 32768.0 * window.double()[None, :]
+        pos = torch.where(pos >= S, 2 * (S - 1) - pos, pos)
+    pos = pos.clamp(0, S - 1)
+    return a[:S].double()[pos] / 32768.0 * window.double()[None, :]
 
 
 def mel_eval(case, o, spec, mode, variant=None):
@@ -2197,7 +2215,7 @@ def mel_emulate(case, o, spec):
     out = torch.zeros(2, F_max, spec.n_mel)
     k = torch.arange(nb)
     for b, L in enumerate(case.lens):
-        fr = ((o.audio[b].float()[:L])[_mel_pos(L, spec)] * torch.tensor(1.0 / 32768.0)) * window[None, :]
+        fr = ((o.audio[b].float()[:max(L, 1)])[_mel_pos(L, spec)] * torch.tensor(1.0 / 32768.0)) * window[None, :]
         re, im = torch.zeros(fr.shape[0], nb), torch.zeros(fr.shape[0], nb)
         for n in range(n_fft):
             idx = (n * k) & (n_fft - 1)
@@ -2212,9 +2230,10 @@ def mel_emulate(case, o, spec):
 
 def _mel_pos(L, spec):
     pos = torch.arange(L // spec.hop_length + 1)[:, None] * spec.hop_length + torch.arange(spec.n_fft)[None, :] - spec.n_fft // 2
+    S = max(L, 1)
     pos = torch.where(pos < 0, -pos, pos)
-    pos = torch.where(pos >= L, 2 * (L - 1) - pos, pos)
-    return pos.clamp(0, L - 1)
+    pos = torch.where(pos >= S, 2 * (S - 1) - pos, pos)
+    return pos.clamp(0, S - 1)
 
 
 def mel_launch(eng, case, o, spec, *, padded):
@@ -2246,6 +2265,27 @@ def mel_cases(spec):
           MelCase("mel/square", (6 * h, 6 * h + 1), signal="square", seed=6),
           MelCase("mel/impulse", (6 * h, 6 * h - 1), signal="impulse", seed=7)]
     return cs
+
+
+def mel_short_cases(spec):
+    """Clips the fp32 oracle cannot frame (its reflection needs more than n_fft / 2 samples): no samples (one frame of the row's first
+    sample), one sample, n_fft / 2.  Checked against the counted bound alone (mel_ref_counted)."""
+    half = spec.n_fft // 2
+    return [MelCase("mel/short/0_1", (0, 1), seed=8), MelCase("mel/short/half_half_plus1", (half, half + 1), seed=9)]
+
+
+def mel_ref_counted(case, spec, o=None):
+    """mel_ref without the fp32 oracle: the bound is the count mel_c alone (no yardstick term), so it is never the wider one."""
+    o = case.ops() if o is None else o
+    r = _Ops()
+    r.ref, r.lin = mel_eval(case, o, spec, "f64")
+    _, A_lin = mel_eval(case, o, spec, "abs")
+    floor = float(torch.tensor(1e-5, dtype=torch.float32))
+    r.A = (A_lin / r.lin.clamp_min(floor)).clamp_min(1e-300)
+    r.allow = MEL_LOG_ALLOW * r.ref.abs()
+    r.f32, r.yard = r.ref.float(), 0.0
+    r.bound = mel_c(spec) * EPS24
+    return r
 
 
 def old_metric(got, ref32):

@@ -5,7 +5,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("output", "ingest", "edit", "formant", "denoise", "watermark")      # on tools/hip_host_shim.h
+NEW = ("output", "ingest", "edit", "formant", "denoise", "watermark", "elementwise", "mel", "noise")      # on tools/hip_host_shim.h
 OLD = ("flac", "flac_decode", "loudness", "limiter", "prosody")            # on their own stand-ins
 
 

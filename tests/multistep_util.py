@@ -128,3 +128,17 @@ def report_plain(f, f_prev):
     f = np.asarray(f, dtype=np.float64)
     d2 = 0.0 if f_prev is None else float(np.sum((f - np.asarray(f_prev, dtype=np.float64)) ** 2))
     return d2, float(np.sum(f * f))
+
+
+# the item lengths tools/elementwise_host_check.py and the device test share: an empty item, one frame short of a tile, a tile, one more, two
+# tiles' worth of a part; with EDGE_TILES partials per item, one more than the longest needs
+EDGE_LENS = (0, TILE - 1, TILE, TILE + 1, TILE + 13)
+EDGE_TILES = -(-max(EDGE_LENS) // TILE) + 1
+
+
+def edge_slopes(M, seed=22):
+    """-> (f, f_prev) float32 [sum(EDGE_LENS)][M], the items back to back."""
+    rng = np.random.default_rng(seed + M)
+    R = sum(EDGE_LENS)
+    f = rng.standard_normal((R, M)).astype(np.float32)
+    return f, (f + 0.25 * rng.standard_normal((R, M))).astype(np.float32)

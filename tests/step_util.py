@@ -440,6 +440,8 @@ class ApgCase:
     zero_d: bool = False        # x_e = 0 and t_e = 1: d == 0, S2 == 0
     rows: bool = True
     seed: int = 0
+    extra_tiles: int = 0        # n_tiles beyond what the longest item needs: partials nobody writes
+    overstate: int = 0          # the DEVICE len of the last item says this many rows more than the Rc rows hold: the kernels clamp it
 
     @property
     def B(self):
@@ -455,7 +457,11 @@ class ApgCase:
 
     @property
     def n_tiles(self):
-        return -(-max(self.lens) // APG_TILE)
+        return -(-max(self.lens) // APG_TILE) + self.extra_tiles
+
+    @property
+    def lens_dev(self):
+        return tuple(self.lens[:-1]) + (self.lens[-1] + self.overstate,)
 
     def ops(self):
         g = _gen(self.seed)
@@ -548,7 +554,7 @@ def apg_launch(eng, case, o):
     pw, dp = framed(o.pred)
     xw, dxe = framed(o.x_e)
     nan_x = int((~torch.isfinite(o.x_e[:, 0])).nonzero()[0]) if case.rows else 0
-    keep = [table(o.row_start, 0), table(torch.tensor(case.lens), 0), table(o.row_src, nan_x)]
+    keep = [table(o.row_start, 0), table(torch.tensor(case.lens_dev), 0), table(o.row_src, nan_x)]
     du = table(o.u_row, o.pred.shape[0])[1] if o.u_row is not None else None
     fl = [framed(v, 0, 4)[1] for v in (o.g_item, o.eta, o.norm)]
     parts_w, parts = _guarded((B, nt, 3), 6, FILL, init=torch.full((B, nt, 3), FILL, dtype=torch.float64), dtype=torch.float64)
@@ -575,6 +581,11 @@ def apg_cases():
         ApgCase("apg/eta_one_and_caps", (7, 9, 11), eta=(1.0, 0.0, 0.0), norm=(0.0, 0.05, 50.0), seed=4002),      # eta == 1; a cap that binds; one that does not
         ApgCase("apg/S2_zero", (3, T), t_e=1.0, zero_d=True, eta=(0.0, 0.5), seed=4003),
         ApgCase("apg/n_mel4_packed", (1, T + 1), n_mel=4, ldp=4, rows=False, eta=(0.0, 0.5), norm=(0.2, 0.0), seed=4004),
+        # an empty item among lengths round a tile, one item unguided, a tile of partials nobody owns, a device len that overstates Rc
+        ApgCase("apg/lens_0_31_32_33_45", (0, T - 1, T, T + 1, T + 13), guided=(True, True, False, True, True), eta=(0.0, 0.5, 0.0, 0.25, 0.5),
+                norm=(0.0, 0.3, 0.0, 0.0, 0.1), extra_tiles=1, overstate=7, seed=4005),
+        ApgCase("apg/lens_0_31_32_33_45_n_mel4", (0, T - 1, T, T + 1, T + 13), n_mel=4, ldp=8, eta=(0.0, 0.5, 0.0, 0.25, 0.5), extra_tiles=1, overstate=7,
+                seed=4006),
     ]
 
 

@@ -531,6 +531,52 @@ def test_drift_reduce_equals_the_mirror_bit_for_bit(hip_tiny):
     assert rc == 0 and np.array_equal(again, want)
 
 
+@pytest.mark.parametrize("M", [4, 100])
+def test_drift_reduce_at_the_host_check_edges(hip_tiny, M):
+    """The batch tools/elementwise_host_check.py runs on exact-size buffers (an empty item, 31, 32, 33 and 45 frames, one tile of partials
+    more than the longest needs, one item reusing, one with nothing stored yet, n_mel 4 and 100): the mirror's bits."""
+    eng = hip_tiny["f32"]
+    pc, pu, d_old = U.edge_predictions(M)
+    lens = list(U.EDGE_LENS)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    rc, got = _drift(eng, pc, pu, d_old, lens, list(U.EDGE_COMPUTED), list(U.EDGE_HAS_OLD), n_tiles=U.EDGE_TILES, M=M)
+    assert rc == 0, eng.lib.vv_last_error(eng.ctx).decode()
+    for b in range(len(lens)):
+        rows = slice(off[b], off[b + 1])
+        want = U.drift_mirror(pc[rows], pu[rows], d_old[rows] if U.EDGE_HAS_OLD[b] else None) if U.EDGE_COMPUTED[b] else (0.0, 0.0)
+        assert got[b].tolist() == list(want), (b, got[b], want)
+
+
+REUSE_STAGE = U.reuse_stage_cases()
+
+
+@pytest.mark.parametrize("case", REUSE_STAGE, ids=[c.name for c in REUSE_STAGE])
+def test_reuse_stage_at_the_host_check_shapes(hip_tiny, case):
+    """The launches tools/elementwise_host_check.py runs on exact-size buffers: n_mel 4 and 100, ldp tight and + 4, 1 / 3 / 86 rows, the
+    three subsets; the bounds and the exact parts of test_reuse_stage_against_float64 (cfg_reuse_util.ReuseStageCase.ref)."""
+    eng = hip_tiny["f32"]
+    o = case.ops()
+    r = case.ref(o)
+    Rc, M, i = o.Rc, case.n_mel, case.stage
+    dx, dp, dd = o.x.clone().to(DEV), o.pred.to(DEV), o.d_old.clone().to(DEV)
+    dk = [k.to(DEV) if o.coef[j] != 0 else None for j, k in enumerate(o.k_prev)]
+    k_out = torch.full((Rc, M), 7.0, device=DEV)
+    x_out = None if o.last else torch.full((Rc, M), 7.0, device=DEV)
+    rc = _stage(eng, dx, dp, case.ldp, Rc, M, i, dk, [float(c) for c in o.coef], k_out, x_out, case.g, case.N, o.row_src.to(DEV), o.u_row.to(DEV), dd, o.modes)
+    assert rc == 0, eng.lib.vv_last_error(eng.ctx).decode()
+    torch.cuda.synchronize()
+    eps = 2.0 ** -24
+    rs = o.row_src.long()
+    got = (dx.cpu()[rs] if o.last else x_out.cpu()).double()
+    assert float(((got - r["acc"]).abs() - 8 * eps * r["mag"]).max()) <= 0.0, case.name
+    assert float(((k_out.cpu().double() - r["k"]).abs() - 4 * eps * r["K"]).max()) <= 0.0, case.name
+    assert torch.equal(k_out.cpu()[~r["guided"]], r["pc32"][~r["guided"]])
+    assert torch.equal(dd.cpu(), r["want_d"]), case.name
+    mask = torch.ones(o.x.shape[0], dtype=torch.bool)
+    mask[rs] = False
+    assert torch.equal(dx.cpu()[mask], o.x[mask]) and (o.last or torch.equal(dx.cpu(), o.x))
+
+
 def _pred_offset(spec, R):
     """Byte offset of the DiT's output in a one-lane fp32 workspace: the lane's buffers in the order the plan takes them (packed
     conditioning, three activations, the residual stream, qkv, attention, the MLP's middle), each 256-byte aligned."""

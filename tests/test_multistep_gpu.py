@@ -311,6 +311,21 @@ def test_ode_diff_reduce_equals_the_mirror_bit_for_bit(hip_tiny):
     assert rc == 0 and np.array_equal(again, want)
 
 
+@pytest.mark.parametrize("M", [4, 100])
+def test_ode_diff_reduce_at_the_host_check_edges(hip_tiny, M):
+    """The lengths tools/elementwise_host_check.py runs on exact-size buffers (an empty item, 31, 32, 33 and 45 frames in one batch, one
+    tile of partials more than the longest needs, n_mel 4 and 100, with and without an earlier slope): the mirror's bits."""
+    eng = hip_tiny["f32"]
+    f, p = mu.edge_slopes(M)
+    lens = list(mu.EDGE_LENS)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    for prev in (p, None):
+        want = np.array([mu.report_mirror(f[off[b]: off[b + 1]], None if prev is None else prev[off[b]: off[b + 1]]) for b in range(len(lens))])
+        rc, got = _diff(eng, f, prev, lens, n_tiles=mu.EDGE_TILES, M=M)
+        assert rc == 0, eng.lib.vv_last_error(eng.ctx).decode()
+        assert np.array_equal(got, want), (got, want)
+
+
 # ------------------------------------------------------------------------------------------------ 5. the report in the pipeline
 def _pred_offset(spec, R):
     """Byte offset of the DiT's output in a one-lane fp32 workspace: the lane's buffers in the order the plan takes them (packed

@@ -84,6 +84,21 @@ def test_normal_mode_stays_inside_the_derived_bound(eng, capsys):
     assert worst <= NORMAL_BOUND, worst / 2.0 ** -24
 
 
+def test_the_host_check_cases_on_the_device(eng):
+    """tools/noise_host_check.py's list (n_mel 4 and 100, N 1 and 37, seq_len of -3, 0 and N + 5, all-ones key words), which the sanitizer
+    builds run on exact-size buffers: the device gives the reference's bits (uniform) and stays inside NORMAL_BOUND (normal)."""
+    from tests.host_check_util import tool
+    for n_mel, n, seq, keys in tool("noise").CASES:
+        k = _keys(keys)
+        got = _fill(eng, k, list(seq), n, n_mel, 1)
+        assert torch.equal(got, torch.from_numpy(pr.fill(k, list(seq), n, n_mel, 1).astype(np.float32))), (n_mel, n, seq)
+        got = _fill(eng, k, list(seq), n, n_mel, 0).double().numpy()
+        z, r = pr.fill(k, list(seq), n, n_mel, 0)
+        live = r > 0
+        assert np.isfinite(got).all() and (np.abs(got - z)[live] <= NORMAL_BOUND * r[live]).all(), (n_mel, n, seq)
+        assert not got[~live].any() and not np.signbit(got[~live]).any()
+
+
 def test_a_value_depends_on_its_key_frame_and_bin_alone(eng):
     key = (9527, (3 << 16) | 2)
     for kind in (0, 1):

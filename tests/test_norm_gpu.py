@@ -151,6 +151,94 @@ def test_mel_float64_parity(hip_tiny, tiny_setup):
     assert not misses, misses
 
 
+def test_mel_short_clips_float64_parity(hip_tiny, tiny_setup):
+    """Clips the fp32 oracle cannot frame: no samples (one frame of the row's first sample), one sample, n_fft / 2 and n_fft / 2 + 1,
+    against the count alone (gpu_util.mel_ref_counted); tools/mel_host_check.py runs the same lengths at a small transform."""
+    spec = tiny_setup[0]
+    eng = hip_tiny["f32"]
+    for case in gu.mel_short_cases(spec):
+        o = case.ops()
+        r = gu.mel_ref_counted(case, spec, o)
+        got = _four(lambda padded: gu.mel_launch(eng, case, o, spec, padded=padded))
+        for b, L in enumerate(case.lens):
+            assert bool((got[b, L // spec.hop_length + 1:] == 0.0).all()), f"{case.name}: frames behind item {b} are not exact zeros"
+        _parity(case, got, r, r.f32)
+
+
+def _mel_guarded(eng, audio, audio_len, F_max, guard_rows=3):
+    """vv_mel on audio [B][ld] that sits inside a larger allocation, guard rows of 32767 in front and behind -> (rc, mel [B][F_max][n_mel])."""
+    B, ld = audio.shape
+    whole = torch.full((guard_rows + B + guard_rows, ld), 32767, dtype=torch.int16)
+    whole[guard_rows:guard_rows + B] = audio
+    whole = whole.to(gu.DEV)
+    lens = torch.tensor(audio_len, dtype=torch.int32, device=gu.DEV)
+    mbuf, mel = gu._guarded((B, F_max, eng.spec.n_mel), gu.CONV_GUARD, gu.CONV_FILL)
+    mel.fill_(gu.CONV_FILL)
+    rc = eng.lib.vv_mel(eng.ctx, whole[guard_rows].data_ptr(), ld, lens.data_ptr(), mel.data_ptr(), B, F_max, gu.stream())
+    torch.cuda.synchronize()
+    gu._bands_intact(mbuf, gu.CONV_GUARD, gu.CONV_FILL, "mel")
+    return rc, mel.cpu()
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["first_item", "last_item"])
+def test_mel_device_length_beyond_the_row_is_clamped(hip_tiny, tiny_setup, which):
+    """A device audio_len of ld_audio + 5 (a stale tensor): the kernel clamps it to the row, so the result is that of the clip clamped to
+    ld_audio and the frames past it are zeros -- wrong audio for that call, never a read outside the row.  The rows sit between guard rows
+    of 32767 inside one allocation: nothing outside the test's own memory is read whatever the kernel does."""
+    spec, _, orc = tiny_setup
+    eng = hip_tiny["f32"]
+    h = spec.hop_length
+    lens = (6 * h + 1, 4 * h) if which == 0 else (4 * h, 6 * h + 1)
+    case = gu.MelCase(f"mel/over_long_{which}", lens, seed=40 + which)
+    o = case.ops()
+    r = gu.mel_ref(case, spec, orc, o)                                 # the longer clip fills its row: clamped to ld_audio it is the row
+    ld = max(lens)
+    F_ref = ld // h + 1
+    given = [n + 5 if n == ld else n for n in lens]
+    rc, got = _mel_guarded(eng, o.audio, given, F_ref + 2)
+    gu.check(eng, rc)
+    assert bool((got[:, F_ref:] == 0.0).all()), "frames past the clamped clip are not exact zeros"
+    for b, L in enumerate(lens):
+        assert bool((got[b, L // h + 1:] == 0.0).all()), f"frames behind item {b} are not exact zeros"
+    _parity(case, got[:, :F_ref].contiguous(), r, r.f32)
+    rc, same = _mel_guarded(eng, o.audio, list(lens), F_ref + 2)       # the honest length: the same bits
+    gu.check(eng, rc)
+    assert _same_bits(got, same)
+
+
+MEL_REFUSALS = {
+    "audio_null": (dict(audio=None), "mel: audio, audio_len, mel and the four tables are required"),
+    "audio_len_null": (dict(audio_len=None), "mel: audio, audio_len, mel and the four tables are required"),
+    "mel_null": (dict(mel=None), "mel: audio, audio_len, mel and the four tables are required"),
+    "ld_audio_zero": (dict(ld=0), "mel: ld_audio, hop and n_mel must be at least 1"),
+    "ld_audio_negative": (dict(ld=-8), "mel: ld_audio, hop and n_mel must be at least 1"),
+    "B_zero": (dict(B=0), "mel: empty"),
+    "F_max_zero": (dict(F_max=0), "mel: empty"),
+    "B_beyond_grid_y": (dict(B=65536), "mel: at most 65535 clips per launch"),
+}
+
+
+@pytest.mark.parametrize("what", sorted(MEL_REFUSALS))
+def test_mel_refusals_write_nothing(hip_tiny, what):
+    """vvk_mel refuses null buffers, ld_audio < 1 and a batch beyond grid.y with -22 and its own message before anything is launched (hop,
+    n_mel and n_fft come from the bound model and are checked by the same lines); the base launch is valid."""
+    eng = hip_tiny["f32"]
+    spec = eng.spec
+    B, ld = 2, spec.n_fft
+    F_max = ld // spec.hop_length + 1
+    audio = torch.full((B, ld), 1000, dtype=torch.int16, device=gu.DEV)
+    lens = torch.tensor([ld, ld // 2 + 1], dtype=torch.int32, device=gu.DEV)
+    mel = torch.full((B, F_max, spec.n_mel), gu.CONV_FILL, device=gu.DEV)
+    call = lambda **k: eng.lib.vv_mel(eng.ctx, k.get("audio", audio.data_ptr()), k.get("ld", ld), k.get("audio_len", lens.data_ptr()),
+                                      k.get("mel", mel.data_ptr()), k.get("B", B), k.get("F_max", F_max), gu.stream())
+    bad, message = MEL_REFUSALS[what]
+    _refused(eng, call(**bad), mel)
+    assert eng.lib.vv_last_error(eng.ctx).decode().startswith(message), eng.lib.vv_last_error(eng.ctx).decode()
+    gu.check(eng, call())
+    torch.cuda.synchronize()
+    assert not bool((mel == gu.CONV_FILL).any())
+
+
 # ------------------------------------------------------------------------------------ the text stack
 @pytest.mark.parametrize("case", TE, ids=_ids(TE))
 def test_text_embed_bit_exact(hip_tiny, case):

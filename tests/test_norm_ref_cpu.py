@@ -32,7 +32,7 @@ def test_case_lists_cover_what_they_claim():
     assert any(c.n < 256 for c in GN) and any(c.vec and (c.n // 4) % 256 and c.n // 4 > 256 for c in GN) and any(c.C // c.G == 1 for c in GN)
     assert any(c.G == 1 for c in GN) and any(c.G == c.C for c in GN) and {c.T % 4 for c in GN} >= {0, 1, 3}
     assert any(c.offset == 1 and c.T % 4 == 0 and not c.vec for c in GN)
-    assert {c.KW for c in DW} == {3, 7, 31} and {c.C for c in DW} == {4, 64, 100} and any(c.lens is None for c in DW)
+    assert {c.KW for c in DW} == {1, 3, 7, 31} and {c.C for c in DW} == {4, 64, 100} and any(c.lens is None for c in DW)
     assert {c.C for c in GRN} >= {64, 128, 192} and {c.N for c in GRN} >= {1, 15, 16, 17, 40} and {c.bf16 for c in GRN} == {False, True}
 
 
@@ -281,11 +281,11 @@ def test_dwconv_bound_rejects_mutations():
         def rec(name, y):
             muts[name].append((case.name, _err(y, r) / r.bound, gu.old_metric(y, r.f32) < 2e-3))
         assert float((conv(xz, w, case.KW // 2) - r.ref).abs().max()) < 1e-13
-        if max(o.lens) > 0:
+        if max(o.lens) > 0 and case.KW > 1:               # at KW = 1 both paddings are none and [C][KW] is [KW][C]: the two mutations are the identity
             rec("causal_padding", conv(xz, w, case.KW - 1))
         if any(0 < L < case.N for L in o.lens) or (any(L < case.N for L in o.lens) and case.N > 1):
             rec("mask_at_N_not_len", conv(x, w, case.KW // 2))
-        if max(o.lens) > 0:
+        if max(o.lens) > 0 and case.KW > 1:
             rec("weights_read_as_KW_by_C", conv(xz, w.reshape(case.KW, case.C).t().contiguous(), case.KW // 2))
     _table("dwconv_kernel", list(muts.items()))
 

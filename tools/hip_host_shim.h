@@ -1,4 +1,4 @@
-// Host stand-ins for the HIP names the PCM-stage, ingest and edit kernels use, for the tools/*_host_check.cpp programs: a .hip file's
+// Host stand-ins for the HIP names the PCM-stage, ingest, edit, elementwise, mel and noise kernels use, for the tools/*_host_check.cpp programs: a .hip file's
 // kernels are compiled for the CPU (its includes and launchers sit behind #ifndef VV_*_HOST_CHECK) and run one OS thread per GPU thread
 // of a workgroup, workgroups one after the other, so that -fsanitize=address,undefined sees an index past the end of an exact-size heap
 // block and -fsanitize=thread sees an LDS write and a read with no barrier between them.  Build with -std=c++20 -ffp-contract=off.
@@ -8,11 +8,14 @@
 //   exact_block<T>(n, byte_off)           n elements whose LAST byte is the allocation's last byte; the first sits byte_off bytes past
 //                                         a 16-byte boundary (destinations at +2, +4, +6); release with exact_free
 //
-// A thread that returns from the kernel leaves the barrier, so the others pass theirs (a kernel may return early per thread).
-// __shfl_xor and __syncthreads_or are WORKGROUP-WIDE exchanges here: write a slot, barrier, read, barrier.  That equals the wave
-// shuffle only where every thread of the workgroup reaches the call, which holds for every shuffle in the files checked with this
-// header: np_buffer_sum (vv_np_sum.h) is called by all 256 threads, and clip_peak_kernel (vv_ingest.hip) shuffles after a return that
-// is uniform over the workgroup.  A kernel that broke the rule would wait for ever: run every program under a time limit.
+// A thread that returns from the kernel leaves the workgroup's barrier and its wave's, so the others pass theirs (a kernel may return
+// early per thread, per wave, or with all lanes but a few).
+// __shfl_xor and __shfl are WAVE-SCOPED exchanges: threads threadIdx.x >> 6 form a wave of 64 lanes (blockDim.x % 64 in a short last
+// wave) with a barrier of its own; write a slot, wave barrier, read, wave barrier.  A wave barrier orders nothing between waves: what
+// crosses waves through LDS still needs the kernel's own __syncthreads, and the thread build reports it when that is missing.  A
+// shuffle that only part of a wave's live lanes reach would wait for ever: run every program under a time limit.  A lane that reads
+// the slot of a lane that has returned, or that lies past the wave, gets a stale or its own value, as on the device it gets an
+// undefined one.  __syncthreads_or is workgroup-wide.
 #pragma once
 #define VV_HIP_HOST_SHIM
 #include <algorithm>
@@ -33,6 +36,9 @@ struct dim3 { unsigned x = 1, y = 1, z = 1; dim3(unsigned a = 1, unsigned b = 1,
 struct alignas(8) uint2 { uint32_t x, y; };
 struct alignas(16) uint4 { uint32_t x, y, z, w; };
 struct alignas(16) float4 { float x, y, z, w; };
+struct alignas(8) float2 { float x, y; };
+static inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+static inline uint4 make_uint4(uint32_t x, uint32_t y, uint32_t z, uint32_t w) { return uint4{x, y, z, w}; }
 static thread_local dim3 threadIdx, blockIdx, gridDim, blockDim;
 #define __global__
 #define __device__
@@ -71,12 +77,14 @@ struct Barrier {
 struct Pool {
     const int n;
     Barrier work, wg, gate, done;                   // work: __syncthreads of the running workgroup (a returned thread has left it);
+    Barrier wave[16];                               // wave: the exchange of one wave's shuffles (a returned lane has left it);
     std::vector<std::thread> th;                    // wg: between workgroups; gate / done: the n workers and the launcher
     dim3 grid, block;
     const std::function<void()>* f = nullptr;
     bool quit = false;
     explicit Pool(int n_) : n(n_) {
         work.expected = wg.expected = n;
+        arm_waves();
         gate.expected = done.expected = n + 1;
         for (int t = 0; t < n; ++t) th.emplace_back([this, t] { run(t); });
     }
@@ -85,6 +93,7 @@ struct Pool {
         gate.wait();
         for (auto& x : th) x.join();
     }
+    void arm_waves() { for (int w = 0; w * 64 < n; ++w) wave[w].expected = std::min(64, n - w * 64); }
     void run(int t);
     void launch(dim3 g, dim3 b, const std::function<void()>& fn) {
         grid = g; block = b; f = &fn;
@@ -95,7 +104,7 @@ struct Pool {
 
 static Pool* g_pool = nullptr;                      // the pool of the running launch
 static unsigned char* g_lds = nullptr;              // its dynamic LDS
-static uint32_t g_slot[1024];                       // __shfl_xor
+static uint64_t g_slot[1024];                       // __shfl_xor, __shfl
 static int g_or = 0;                                // __syncthreads_or
 
 inline void Pool::run(int t) {
@@ -108,8 +117,9 @@ inline void Pool::run(int t) {
                     threadIdx = dim3((unsigned)t); blockIdx = dim3(bx, by, bz); gridDim = grid; blockDim = block;
                     (*f)();
                     work.leave();
+                    wave[t >> 6].leave();
                     wg.wait();                      // the workgroup is over: the next one reuses the static "shared" arrays
-                    if (t == 0) work.expected = n;
+                    if (t == 0) { work.expected = n; arm_waves(); }
                     wg.wait();
                 }
         done.wait();
@@ -158,15 +168,21 @@ static inline int __syncthreads_or(int pred) {
     __syncthreads();
     return r;
 }
-template <typename T> static inline T __shfl_xor(T v, int o) {
-    static_assert(sizeof(T) == 4, "32-bit values");
-    memcpy(&vv_host::g_slot[threadIdx.x], &v, 4);
-    __syncthreads();
-    T r;
-    memcpy(&r, &vv_host::g_slot[threadIdx.x ^ (unsigned)o], 4);
-    __syncthreads();
+namespace vv_host {
+template <typename T> inline T wave_exchange(T v, unsigned src_lane) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "32-bit and 64-bit values");
+    const unsigned t = threadIdx.x, w0 = t & ~63u;
+    Barrier& wb = g_pool->wave[t >> 6];
+    memcpy(&g_slot[t], &v, sizeof(T));
+    wb.wait();
+    T r = v;
+    if (src_lane < 64 && w0 + src_lane < blockDim.x) memcpy(&r, &g_slot[w0 + src_lane], sizeof(T));
+    wb.wait();
     return r;
 }
+}  // namespace vv_host
+template <typename T> static inline T __shfl_xor(T v, int o) { return vv_host::wave_exchange(v, (threadIdx.x & 63u) ^ (unsigned)o); }
+template <typename T> static inline T __shfl(T v, int src) { return vv_host::wave_exchange(v, (unsigned)src & 63u); }
 template <typename T> static inline T atomicAdd(T* p, T v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
 template <typename T> static inline T atomicMax(T* p, T v) {
     T old = __atomic_load_n(p, __ATOMIC_RELAXED);
@@ -180,3 +196,9 @@ static inline float __uint_as_float(unsigned u) { float f; memcpy(&f, &u, 4); re
 static inline double __dmul_rn(double a, double b) { return a * b; }
 static inline double __dadd_rn(double a, double b) { return a + b; }
 static inline double __ddiv_rn(double a, double b) { return a / b; }
+// Stand-ins, NOT the device's functions: a host result through one of these speaks for the indexing and the barriers of its path only.
+static inline float rsqrtf(float x) { return 1.0f / sqrtf(x); }
+static inline float cospif(float x) { return (float)cos(M_PI * (double)x); }     // in double, rounded once
+static inline float sinpif(float x) { return (float)sin(M_PI * (double)x); }
+static inline float vv_host_exp2f(float x) { return exp2f(x); }                   // act_apply's Mish branch (vv_common.h)
+static inline float vv_host_rcpf(float x) { return 1.0f / x; }

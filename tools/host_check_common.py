@@ -71,6 +71,89 @@ def check(label, good):
     return label, bool(good)
 
 
+FILL = 0xAA               # what an output holds before a launch; what no thread owns must still hold it afterwards
+
+
+def filled(shape, dtype):
+    """An output buffer before its launch: every byte 0xAA."""
+    import numpy as np
+    a = np.empty(shape, dtype)
+    a.view(np.uint8).reshape(-1)[:] = FILL
+    return a
+
+
+def still_filled(a):
+    """Every byte of ``a`` (a slice of an output that no thread owns) is still 0xAA."""
+    import numpy as np
+    return bool((np.ascontiguousarray(a).view(np.uint8) == FILL).all())
+
+
+class Alias:
+    """Argument: the block of argument ``k`` of the same launch once more."""
+    def __init__(self, k):
+        self.k = k
+
+
+class Off:
+    """Argument: a block whose first byte lies ``byte_off`` past a 16-byte boundary (its last byte still ends the allocation)."""
+    def __init__(self, a, byte_off):
+        self.a, self.byte_off = a, byte_off
+
+
+class Batch:
+    """The launches of one run of a program on tools/host_check_driver.h.  add() takes a kernel's arguments in order: a numpy array is an
+    exact-size block holding it (an output comes as filled()), None a null pointer, an int or a float a scalar; run() returns, per launch,
+    {argument index: the block after the launch, in the array's dtype and shape}."""
+
+    def __init__(self, exe, work, name):
+        self.exe, self.fin, self.fout = exe, os.path.join(work, f"{name}_in.bin"), os.path.join(work, f"{name}_out.bin")
+        self.parts, self.outs = [], []
+
+    def add(self, kernel, grid, block, args, shmem=0):
+        import struct
+        import numpy as np
+        g = tuple(grid) + (1,) * (3 - len(tuple(grid))) if not isinstance(grid, int) else (grid, 1, 1)
+        k = kernel.encode()
+        b = [struct.pack("<q", len(k)), k, struct.pack("<6q", *g, block, shmem, len(args))]
+        outs = {}
+        for i, a in enumerate(args):
+            off = 0
+            if isinstance(a, Off):
+                a, off = a.a, a.byte_off
+            if a is None:
+                b.append(struct.pack("<3q", 3, -1, 0))
+            elif isinstance(a, Alias):
+                b.append(struct.pack("<2q", 2, a.k))
+            elif isinstance(a, np.ndarray):
+                a = np.ascontiguousarray(a)
+                b += [struct.pack("<3q", 3, a.nbytes, off), a.tobytes()]
+                outs[i] = (a.dtype, a.shape, a.nbytes)
+            elif isinstance(a, (bool, int, np.integer)):
+                b.append(struct.pack("<2q", 0, int(a)))
+            else:
+                b.append(struct.pack("<qd", 1, float(a)))
+        self.parts.append(b"".join(b))
+        self.outs.append(outs)
+        return len(self.outs) - 1
+
+    def run(self, timeout=TIME_LIMIT):
+        import struct
+        import numpy as np
+        with open(self.fin, "wb") as f:
+            f.write(struct.pack("<q", len(self.parts)) + b"".join(self.parts))
+        run(self.exe, [self.fin, self.fout], timeout)
+        raw, pos, res = open(self.fout, "rb").read(), 0, []
+        for outs in self.outs:
+            d = {}
+            for i, (dt, shape, nb) in outs.items():
+                d[i] = np.frombuffer(raw, dt, nb // max(dt.itemsize, 1), pos).reshape(shape)
+                pos += nb
+            res.append(d)
+        assert pos == len(raw), "the program wrote another number of bytes than its blocks hold"
+        self.parts, self.outs = [], []
+        return res
+
+
 def pack_signals(sigs, gap=3):
     """int16 signals into one plane, the first at element 0, the last ending the plane, ``gap`` samples of 32767 junk between them (source
     offsets that are no multiple of a hop) -> (plane, offsets)"""

@@ -1,6 +1,8 @@
 // Shared device helpers for the gfx950 kernels (wave64, MFMA fragment types, LDS swizzles).
 #pragma once
+#ifndef VV_HIP_HOST_SHIM               // tools/hip_host_shim.h: the host checks bring their own stand-ins
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 typedef __bf16 bf16;
@@ -19,6 +21,7 @@ enum { VV_F32 = 0, VV_BF16 = 1 };
 // activation codes
 enum { VV_ACT_NONE = 0, VV_ACT_GELU_TANH = 1, VV_ACT_GELU_ERF = 2, VV_ACT_SILU = 3, VV_ACT_MISH = 4 };
 
+#ifndef VV_HIP_HOST_SHIM
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -27,6 +30,7 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 __device__ __forceinline__ void glds16(const void* g, void* lds_wave_base) {
     __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
 }
+#endif
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -55,9 +59,15 @@ __device__ __forceinline__ float act_apply(float x, int act) {
         case VV_ACT_MISH: {
             // x * tanh(softplus(x)) = x * t / (t + 2),  t = e^x (e^x + 2)   (one v_exp + one v_rcp)
             if (x > 20.0f) return x;
+#ifndef VV_HIP_HOST_SHIM
             const float n = __builtin_amdgcn_exp2f(1.4426950408889634f * x);
             const float t = n * (n + 2.0f);
             return x * t * __builtin_amdgcn_rcpf(t + 2.0f);
+#else
+            const float n = vv_host_exp2f(1.4426950408889634f * x);
+            const float t = n * (n + 2.0f);
+            return x * t * vv_host_rcpf(t + 2.0f);
+#endif
         }
         default: return x;
     }

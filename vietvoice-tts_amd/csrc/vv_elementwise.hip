@@ -2,8 +2,10 @@
 // K9 CFG+Euler, text-side embedding gather / depthwise conv / GRN, and the tiny time-grid helpers.
 // All are wave64-native: 16-byte vector loads, wave shuffles for row reductions, no LDS unless a
 // cross-wave reduction is needed.
+#ifndef VV_ELEMENTWISE_HOST_CHECK     // tools/elementwise_host_check.cpp compiles the kernels below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 #include <type_traits>
 
 namespace {
@@ -580,7 +582,11 @@ template <typename T>
 __global__ __launch_bounds__(256) void grn_apply_kernel(T* __restrict__ x, const float* __restrict__ sumsq,
                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
                                                         int N, int C, int rows_per_block) {
+#ifndef VV_ELEMENTWISE_HOST_CHECK
     extern __shared__ float sc[];      // [C] scale = gamma*nx + 1
+#else
+    float* sc = (float*)vv_host::dynamic_lds();
+#endif
     __shared__ float red[4];
     const int s = blockIdx.y;
     float part = 0.f;
@@ -817,10 +823,13 @@ __global__ __launch_bounds__(256) void rope_rows_kernel(const float* __restrict_
     *(float4*)(out + r * 64 + q * 4) = *(const float4*)(cs + (size_t)pos[r] * 64 + q * 4);
 }
 
+#ifndef VV_ELEMENTWISE_HOST_CHECK
 inline int grid_for(size_t total) { return (int)std::min<size_t>((total + 255) / 256, 256 * 8); }
+#endif
 
 }  // namespace
 
+#ifndef VV_ELEMENTWISE_HOST_CHECK
 #define VVK_CHECK_LAUNCH()                                               \
     do {                                                                 \
         hipError_t he__ = hipGetLastError();                             \
@@ -1122,3 +1131,4 @@ int vvk_rope_compact(const float* c, const float* s, float* out, int n, hipStrea
     VVK_CHECK_LAUNCH();
     return 0;
 }
+#endif

@@ -6,8 +6,10 @@
 //   normal  : Box-Muller on the word pairs (0, 1) and (2, 3): r = sqrtf(-2 logf(u0)), z0 = r cospif(2 u1), z1 = r sinpif(2 u1)
 //             (2 u is exact: no rounded 2 pi enters).  Precise libm forms only, as in the Vocos spectrum kernel: this file is built
 //             without fast-math and uses no __-prefixed intrinsic.
+#ifndef VV_NOISE_HOST_CHECK           // tools/noise_host_check.cpp compiles the kernel below for the host, on tools/hip_host_shim.h
 #include "vv_common.h"
 #include "vv_kernels.h"
+#endif
 
 namespace {
 
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(256) void noise_fill_kernel(float* __restrict__ x, 
 
 }  // namespace
 
+#ifndef VV_NOISE_HOST_CHECK
 int vvk_noise_fill(float* x, const int* seq_len, const unsigned long long* keys, int B, int N, int n_mel, int kind, hipStream_t st,
                    const char** err) {
     if (B < 1 || N < 1 || n_mel < 4 || n_mel % 4) { *err = "noise_fill: B, N >= 1 and n_mel a positive multiple of 4"; return -22; }
@@ -70,3 +73,4 @@ int vvk_noise_fill(float* x, const int* seq_len, const unsigned long long* keys,
     if (he != hipSuccess) { *err = hipGetErrorString(he); return -5; }
     return 0;
 }
+#endif
