@@ -289,6 +289,44 @@ VV_API int vv_transformer_steps_reuse(vv_ctx* ctx, const vv_steps_args* args, co
                                       void* stream);
 VV_API int vv_transformer_reuse_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes);
 
+/* N23 block caching: vv_transformer_steps_ex where a span [first, last) of the DiT blocks is skipped at chosen
+ * evaluations.  X_l is the fp32 residual stream at the entry of block l (X_depth: what the final norm reads), formed per element as the
+ * LayerNorm kernel forms it: (xres + (float)d_attn) + (float)d_mlp with the two pending deltas of block l - 1, fp32 adds in this order, or
+ * plain xres at l = 0.  modes_host is a HOST array of n_modes = [evaluations of the plan in force] uint8, row e = step * s + stage:
+ *   0 FULL           the evaluation of vv_transformer_steps_ex, launch for launch;
+ *   1 FULL + STORE   the same, bit for bit, plus two read-only launches per lane (or branch view): buf = X_first in front of block `first`,
+ *                    buf = X_last - buf (one fp32 subtraction) in front of block `last`, or of the final norm when last = depth;
+ *   2 LIGHT          blocks 0 ... first - 1 run, then xres = X_first + buf (one fp32 add, nothing pending behind it), then blocks last ...
+ *                    depth - 1 and the tail; blocks first ... last - 1 launch nothing.
+ * buf is one fp32 [R][D] plane per lane (R its packed rows of both CFG branches) of the call's workspace and does not outlive the call.
+ * report (optional): a caller-owned DEVICE array [report_evals][report_B][2][2] float64, report_evals the evaluations of the plan and
+ * report_B the call's B: at an evaluation of the call with mode 1, item b, branch c (0 conditional, 1 unconditional) it holds
+ * {sum (buf_new - buf_prev)^2, sum buf_new^2} over the item's valid frames and the D columns (the first sum 0 at the first store of the
+ * call), {0, 0} at every other evaluation of the call; rows of evaluations outside the call are not written.  float64, deterministic,
+ * independent of the item's place in the batch (vv_block_drift_reduce).  With a report the workspace holds a second plane (the stores
+ * alternate between the two) and the partial sums.
+ * Every mode 0 and no report: the call IS vv_transformer_steps_ex (same launches, same workspace).  Otherwise a caller-owned ws holds
+ * vv_transformer_cached_ws_bytes bytes: the vv_transformer_ws_bytes figure plus one plane per lane, plus the second plane and the partial
+ * sums when with_report != 0 -- the same figure whatever the schedule.  -22, nothing launched and the context left usable, for: a mode
+ * above 2; a 2 at an evaluation of the call with no 1 at an earlier evaluation of the same call; a 2 in a call with step0 != 0; first /
+ * last outside 0 <= first < last <= depth; n_modes other than the plan's evaluations; a report whose report_B / report_evals are not the
+ * call's B and the plan's evaluations; option "split_k_tail" (its tail rows keep fp32 parts instead of a delta); and whatever
+ * vv_transformer_steps_ex refuses.  There is no mask, no APG and no reuse argument on this entry: a guided subset moves the unconditional
+ * rows between evaluations, which the stored rows do not follow.  The schedule reaches the device as launches alone: with host lengths
+ * the call does not synchronise and can be captured into a hipGraph. */
+#define VV_BLOCK_FULL 0
+#define VV_BLOCK_STORE 1
+#define VV_BLOCK_LIGHT 2
+typedef struct vv_block_cache_args {
+    int32_t first, last;              /* the span [first, last) of blocks */
+    const uint8_t* modes_host;        /* host [n_modes] */
+    int32_t n_modes;
+    double* report;                   /* device [report_evals][report_B][2][2] float64, optional */
+    int32_t report_B, report_evals;
+} vv_block_cache_args;
+VV_API int vv_transformer_steps_cached(vv_ctx* ctx, const vv_steps_args* args, const vv_block_cache_args* cache, void* stream);
+VV_API int vv_transformer_cached_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes);
+
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
  * that needs more bytes (vv_ws_generation counts those moves); a launch sequence captured into a hipGraph
@@ -613,6 +651,31 @@ typedef struct vv_cfg_drift_args {
     double* partials; double* report;
 } vv_cfg_drift_args;
 VV_API int vv_cfg_drift_reduce(vv_ctx* ctx, const vv_cfg_drift_args* args, void* stream);
+/* N23 single-kernel entries (unit parity).  vv_block_span: one launch of the span kernel on contiguous [R][D] planes.  X = (x + (float)d1)
+ * + (float)d2 per element (fp32 adds in this order; d1 / d2 of delta_dtype, d2 NULL = one delta, d1 NULL = X is x); VV_SPAN_MARK: buf = X;
+ * VV_SPAN_DIFF: buf = X - buf; VV_SPAN_APPLY: x = X + buf.  Nothing else is written.  -22 for R < 1, D < 4 or not a multiple of 4, a null
+ * x or buf, d2 without d1, x / buf not 16-byte or a delta not 16-byte (f32) / 8-byte (bf16) aligned, or buf aliasing x.
+ * vv_block_drift_reduce: the sums of the block-cache report.  Sequence s of n_seq owns the rows [row_start[s], + len[s]) of d_new and
+ * d_prev ([R][D] fp32, 16-byte aligned; row_start, len: device [n_seq] int32, clamped into [0, R) and to VV_APG_TILE * n_tiles rows); it is
+ * branch branch0 + s / n_items of item s % n_items (n_seq = n_items, or 2 n_items with branch0 0).  report [n_items][2][2] float64 =
+ * {sum (d_new - d_prev)^2, sum d_new^2} at [item][branch]: vv_ode_diff_reduce's arithmetic, tiles and order.  d_prev NULL: the first sum is
+ * 0.  partials [n_seq][n_tiles][2] float64 scratch. */
+#define VV_SPAN_MARK 0
+#define VV_SPAN_DIFF 1
+#define VV_SPAN_APPLY 2
+typedef struct vv_block_span_args {
+    int32_t mode, delta_dtype;
+    float* x; const void* d1; const void* d2; float* buf;
+    int32_t R, D;
+} vv_block_span_args;
+VV_API int vv_block_span(vv_ctx* ctx, const vv_block_span_args* args, void* stream);
+typedef struct vv_block_drift_args {
+    const float* d_new; const float* d_prev; int32_t R, D;
+    int32_t n_seq, n_items, branch0, n_tiles;
+    const int32_t* row_start; const int32_t* len;
+    double* partials; double* report;
+} vv_block_drift_args;
+VV_API int vv_block_drift_reduce(vv_ctx* ctx, const vv_block_drift_args* args, void* stream);
 /* K9: x[r] += dt * (p_c + (p_c - p_u) * cfg) over n_mel columns, p_c = pred row r, p_u = pred row BN + r (ld ldp, fp32).  Refused with
  * -22 (nothing launched): n_mel or ldp not a multiple of 4, BN < 1, n_mel < 4, ldp < n_mel, x or pred NULL or not 16-byte aligned.
  * vv_cfg_euler_rows: the same update on packed rows -- x row row_src[r] (device [BN] int32, the caller keeps it inside x) takes pred rows r

@@ -47,6 +47,17 @@ template <bool G, bool A, bool R> static bool stage(const Launch& L) {
                                             VV_P(const float, 20), VV_I(21), VV_F(22), ru)));
 }
 
+template <typename Td, int M> static bool span(const Launch& L) {
+    return VV_GO((block_span_kernel<Td, M>(VV_P(float, 0), VV_P(const Td, 1), VV_P(const Td, 2), VV_P(float, 3), (size_t)L.i(4))));
+}
+
+template <typename Td> static bool span_of(const Launch& L, const std::string& m) {
+    if (m == "mark") return span<Td, VV_SPAN_MARK>(L);
+    if (m == "diff") return span<Td, VV_SPAN_DIFF>(L);
+    if (m == "apply") return span<Td, VV_SPAN_APPLY>(L);
+    return false;
+}
+
 template <typename T> static bool grn_stats(const Launch& L) {
     return VV_GO(grn_stats_kernel<T>(VV_P(const T, 0), VV_P(float, 1), VV_P(const int, 2), VV_I(3), VV_I(4), VV_I(5)));
 }
@@ -91,6 +102,14 @@ static bool run(const Launch& L) {
     if (n == "cfg_drift_reduce")
         return VV_GO(cfg_drift_reduce_kernel(VV_P(const float, 0), VV_I(1), VV_I(2), VV_I(3), VV_P(const int, 4), VV_P(const float, 5), flags_of(L, 6),
                                              VV_P(const int, 7), VV_P(const int, 8), VV_I(9), VV_P(double, 10)));
+    if (n.rfind("block_span<f32,", 0) == 0) return span_of<float>(L, n.substr(15, n.size() - 16));
+    if (n.rfind("block_span<bf16,", 0) == 0) return span_of<bf16>(L, n.substr(16, n.size() - 17));
+    if (n == "block_drift_reduce")
+        return VV_GO(block_drift_reduce_kernel(VV_P(const float, 0), VV_P(const float, 1), VV_I(2), VV_I(3), VV_P(const int, 4), VV_P(const int, 5), VV_I(6),
+                                               VV_P(double, 7)));
+    if (n == "block_drift_finish")
+        return VV_GO(block_drift_finish_kernel(VV_P(const double, 0), VV_I(1), VV_I(2), VV_P(const int, 3), VV_P(const int, 4), VV_I(5), VV_I(6),
+                                               VV_P(double, 7)));
     if (n == "text_embed")
         return VV_GO(text_embed_kernel(VV_P(const int, 0), VV_I(1), VV_P(const int, 2), VV_P(const float, 3), VV_P(const float, 4), VV_P(float, 5), VV_I(6), VV_I(7),
                                        VV_I(8), VV_I(9)));

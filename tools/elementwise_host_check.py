@@ -3,9 +3,9 @@
 
 Builds tools/elementwise_host_check.cpp (the kernel source on tools/hip_host_shim.h, exact-size heap buffers) twice, with
 -fsanitize=address,undefined and with -fsanitize=thread.  Cases, references and bounds are those of tests/gpu_util.py (ln_*, gn_*, te_*,
-dw_*, grn_*), tests/step_util.py (stage_*, apg_*, pack_*, table_cases, len_*, rope_*), tests/cfg_reuse_util.py and
+dw_*, grn_*), tests/step_util.py (stage_*, apg_*, pack_*, table_cases, len_*, rope_*), tests/cfg_reuse_util.py, tests/block_cache_util.py and
 tests/multistep_util.py; nothing is fitted here.  Exact kernels (pack, tables, lengths, rope, text_embed, build_cat, ode_diff_*,
-cfg_drift_*) are compared bit for bit; the others under the bound function of their device test (ln_bound, gn_bound, dw_bound, the
+cfg_drift_*, block_span, block_drift_*) are compared bit for bit; the others under the bound function of their device test (ln_bound, gn_bound, dw_bound, the
 GRN counts, the stage counts, the APG chain bound).  rsqrtf and the Mish branch of act_apply run on the shim's stand-ins (1 / sqrtf;
 exp2f and a division): those results speak for the indexing and the barriers of their paths, not for the device's functions.
 
@@ -21,7 +21,8 @@ Grids, restated from the launchers of csrc/vv_elementwise.hip (which stay outsid
   tables              `row_tables_kernel<<<B, 256>>>`, `guided_tables_kernel<<<B, 256>>>`
   lengths             `(B + 63) / 64` workgroups of 64
   rope                `(n * 32 + 255) / 256` and `(rows * 16 + 255) / 256`: the device's (no grid-stride loop)
-  the grid-stride kernels (pack, cfg_euler, ode_stage, text_embed, dwconv, build_cat): `grid_for(total)`, but at most 2 workgroups, so
+  block_drift         `dim3(a->n_tiles, a->n_seq)`, 256; the finishing kernel `a->n_seq` workgroups of 64
+  the grid-stride kernels (pack, cfg_euler, ode_stage, text_embed, dwconv, build_cat, block_span): `grid_for(total)`, but at most 2 workgroups, so
   that the loop takes further trips (this replaces the device's 21000-row wrap cases)
 
 The reduced list (tests/test_host_sanitizers_cpu.py) keeps every edge named in profiles/host_sanitizers/notes.md and drops repeats of
@@ -662,6 +663,89 @@ def finish_check(m, part, report):
 
 
 
+# ---------------------------------------------------------------------------------------------------- block caching (N23)
+def span_list(reduced):
+    """Every form of the span kernel: MARK / DIFF / APPLY, nothing pending / fp32 / bf16 deltas, D 128 and 1024, 1 / 3 / 86 rows.  Reduced:
+    every mode with every dtype at the largest shape (two workgroups, 43 trips of the loop) and once at the smallest."""
+    from tests import block_cache_util as bu
+    full = [(m, p, D, R) for m in (bu.MARK, bu.DIFF, bu.APPLY) for p in bu.SPAN_PENDING for D in bu.SPAN_DIMS for R in bu.SPAN_ROWS]
+    return [c for c in full if (c[2], c[3]) == (1024, 86) or (c[1] == "f32" and (c[2], c[3]) == (128, 1))] if reduced else full
+
+
+def span_add(bt, case):
+    from tests import block_cache_util as bu
+    mode, pending, D, R = case
+    G = bu.GUARD
+    x, d1, d2, buf = (a[G: G + R].copy() for a in bu.span_operands(R, D))
+    if pending == "none":
+        d1 = d2 = a1 = a2 = None
+    elif pending == "bf16":
+        d1, d2 = bu.bf16_round(d1), bu.bf16_round(d2)
+        a1, a2 = ((d.view(np.uint32) >> 16).astype(np.uint16) for d in (d1, d2))
+    else:
+        a1, a2 = d1, d2
+    name = f"block_span<{'bf16' if pending == 'bf16' else 'f32'},{('mark', 'diff', 'apply')[mode]}>"
+    n4 = R * D // 4
+    k = bt.add(name, grid2(n4), 256, [x, a1, a2, buf, n4])
+    return k, bu.span_expected(mode, x, d1, d2, buf), (a1, a2)
+
+
+def span_check(want, deltas, out):
+    ok = same_bytes(out[0], want[0]) and same_bytes(out[3], want[1])
+    ok = ok and all(a is None or same_bytes(out[i + 1], a) for i, a in enumerate(deltas))
+    return bool(ok), 0.0
+
+
+def bdrift_add(bt, D, with_prev, branch0):
+    """The report's reduction on block_cache_util's edge sequences (0, 31, 32, 33 and 45 rows, the last one's device length overstated,
+    one more sequence whose device row_start lies past the rows)."""
+    from tests import block_cache_util as bu
+    d_new, d_prev = bu.edge_planes(D)
+    rs, ln, R = _edge_tables(bu.EDGE_LENS)
+    S, nt = len(rs), bu.EDGE_TILES
+    args = [d_new, d_prev if with_prev else None, R, D, rs, ln, nt, H.filled((S, nt, 2), np.float64)]
+    want = [bu.report_mirror(d_new[rs[s]: rs[s] + n], d_prev[rs[s]: rs[s] + n] if with_prev else None) for s, n in enumerate(bu.EDGE_LENS)] + [(0.0, 0.0)]
+    return bt.add("block_drift_reduce", (nt, S), 256, args), dict(rs=rs, ln=ln, R=R, nt=nt, S=S, want=np.array(want), lens=bu.EDGE_LENS, branch0=branch0)
+
+
+def bfinish_add(bt, m, part, zero=False):
+    """The finishing kernel on one branch of S items; zero: over no tiles, the partials a null pointer."""
+    return bt.add("block_drift_finish", m["S"], 64, [None if zero else part, 0 if zero else m["nt"], m["R"], m["rs"], m["ln"], m["S"], m["branch0"],
+                                                     H.filled((m["S"], 2, 2), np.float64)])
+
+
+def bfinish_check(m, part, report, zero=False):
+    owned = np.zeros(part.shape[:2], bool)
+    for s, n in enumerate(m["lens"]):
+        owned[s, :-(-n // 32)] = True
+    c = m["branch0"]
+    want = np.zeros_like(m["want"]) if zero else m["want"]
+    return bool(H.still_filled(part[~owned]) and same_bytes(report[:, c], want) and H.still_filled(report[:, 1 - c]))
+
+
+def block_cache_cases(exe, work, reduced=False):
+    """The cases of the two N23 kernels alone (tests/test_block_cache_cpu.py runs these; cases() runs them among the others)."""
+    bt, spans, sums = H.Batch(exe, work, NAME), [], []
+    for case in span_list(reduced):
+        k, want, deltas = span_add(bt, case)
+        spans.append((k, want, deltas, f"block_span mode {case[0]} pending {case[1]} D {case[2]} R {case[3]}"))
+    for D in (128, 1024):
+        for with_prev, branch0 in ((True, 0), (False, 1)):
+            k, m = bdrift_add(bt, D, with_prev, branch0)
+            sums.append((k, m, f"block_drift D {D} d_prev {'given' if with_prev else 'null'} branch {branch0}"))
+    outs = bt.run()
+    for k, want, deltas, label in spans:
+        yield H.check(label, span_check(want, deltas, outs[k])[0])
+    second = []
+    for k, m, label in sums:
+        part = outs[k][7].copy()
+        second.append((bfinish_add(bt, m, part), m, part, label, False))
+    second.append((bfinish_add(bt, sums[0][1], None, zero=True), sums[0][1], outs[sums[0][0]][7].copy(), "block_drift over no tiles", True))
+    outs2 = bt.run()
+    for k, m, part, label, zero in second:
+        yield H.check(label, bfinish_check(m, part, outs2[k][7], zero))
+
+
 # ---------------------------------------------------------------------------------------------------- the lists
 def cases(exe, work, reduced=False):
     """Runs every case through exe; yields (label, equal to the mirror / inside the bound of the device test)."""
@@ -745,6 +829,7 @@ def cases(exe, work, reduced=False):
         yield H.check(f"{case.name} (partials err / bound {ratio:.3f})", good)
     for k, m, part, label in fourth:
         yield H.check(label, finish_check(m, part, outs2[k][5])[0])
+    yield from block_cache_cases(exe, work, reduced)
 
 
 if __name__ == "__main__":

@@ -107,7 +107,9 @@ class BatchingFrontend:
         ``apg_eta`` / ``apg_norm`` that is not off (its own or the engine's) the request fails with a ValueError.
         ``watermark_payload``: this request's watermark payload, 0 ... 65535 (None = the engine's
         ``output_watermark_payload``), embedded in this request alone under the engine's ``output_watermark_key``; on an engine without a
-        key the request fails with a ValueError."""
+        key the request fails with a ValueError.
+        On an engine with ``block_cache`` every batch caches blocks; a request that brings a ``cfg_interval``, a ``cfg_reuse``
+        above 1 or projected guidance fails with a ValueError."""
         fut: Future = Future()
         try:
             options = RequestOptions.checked(cfg_strength=cfg_strength, cfg_interval=cfg_interval, apg_eta=apg_eta, apg_norm=apg_norm,
@@ -118,6 +120,10 @@ class BatchingFrontend:
             from .model_spec import check_apg
             if (full.cfg_reuse or 1) > 1 and check_apg(full.apg_eta, full.apg_norm) is not None:
                 raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
+            if getattr(config, "block_cache", None) is not None and (full.cfg_interval is not None or (full.cfg_reuse or 1) > 1
+                                                                     or check_apg(full.apg_eta, full.apg_norm) is not None):
+                raise ValueError("this engine caches blocks (block_cache): a request cannot bring a cfg_interval, cfg_reuse > 1 or apg_eta / apg_norm "
+                                 "(a guided subset moves the unconditional rows between evaluations, which the stored rows do not follow)")
         except ValueError as e:
             fut.set_exception(e)
             return fut

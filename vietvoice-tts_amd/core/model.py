@@ -48,7 +48,8 @@ class HipSession:
     numpy in and out -- the reference's contract, including its host round trips)."""
 
     def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None,
-                 noise_keys=None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None, cfg_reuse: Optional[int] = None):
+                 noise_keys=None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None, cfg_reuse: Optional[int] = None,
+                 block_cache=None, block_cache_interval=None):
         self.engine, self.kind, self.noise_gen, self.fuse_nfe = engine, kind, noise_gen, max(1, int(fuse_nfe))
         # N9 (ModelConfig.noise_source == "device"): a callable -> the next run's Philox key row {seed, stream}; the preprocess session
         # then fills the noise in HBM (vv_noise_fill) and returns it, as the reference's graph returns its own.  None = the host generator.
@@ -57,6 +58,7 @@ class HipSession:
         self.cfg_interval = cfg_interval          # None = guidance at every evaluation (ModelConfig.cfg_interval)
         self.apg_eta, self.apg_norm = apg_eta, apg_norm      # both None = the plain combine (ModelConfig.apg_eta / apg_norm)
         self.cfg_reuse = cfg_reuse                # None or 1 = every guided evaluation computes both predictions (ModelConfig.cfg_reuse)
+        self.block_cache, self.block_cache_interval = block_cache, block_cache_interval      # None = every block at every evaluation (ModelConfig.block_cache)
         self._in, self._out = SESSION_IO[kind]
 
     def get_inputs(self):
@@ -105,21 +107,24 @@ class HipSession:
                                                      for i, k_ in enumerate(("rope_cos_q", "rope_sin_q", "rope_cos_k", "rope_sin_k")))
             step = int(np.asarray(vals[7]).reshape(-1)[0])
             k = min(self.fuse_nfe, eng.n_steps - step)          # ODE steps, whatever the solver: a step is never split between calls
-            if (self.cfg_reuse or 1) > 1:                       # N21: the stored guidance difference lives for one call, so the utterance's
+            if (self.cfg_reuse or 1) > 1 or self.block_cache is not None:     # N21 / N23: what is stored lives for one call, so the utterance's
                 k = eng.n_steps - step                          # steps are one call (from step 0); fuse_nfe keeps its meaning for everything else
             if k <= 0:                                          # ... and the runs the caller's loop still makes behind it have nothing to do
                 return [np.ascontiguousarray(vals[0], dtype=np.float32), np.array([step], dtype=np.int32)]
             cfg = None if self.cfg_strength is None else torch.full((1,), float(self.cfg_strength), dtype=torch.float32, device=dev)
             guide = eng.guidance_mask(self.cfg_interval, [self.cfg_strength], self.cfg_reuse)      # absolute evaluation rows: the split calls read one table
             apg = eng.apg_tensors([self.apg_eta], [self.apg_norm])                 # N11: stateless between the split calls (no momentum)
+            bc = dict(block_cache=self.block_cache, block_cache_interval=self.block_cache_interval)
+            if self.block_cache is not None:                    # N23: no mask on that entry; a strength of 0 travels as the strength it is
+                guide = None
             if same:
-                eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg)
+                eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg, **bc)
             else:
                 if not getattr(self, "_rope_warned", False):
                     logger.warning("transformer session: non-standard rope tables fed; the tables are read instead of computed")
                     self._rope_warned = True
                 with eng.reading_rope_tables():
-                    eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg)
+                    eng.transformer_steps(x, pre, step, k, cfg=cfg, guide=guide, apg=apg, **bc)
             return [x.cpu().numpy(), np.array([step + k], dtype=np.int32)]
         x = torch.from_numpy(np.ascontiguousarray(vals[0], dtype=np.float32)).to(dev)
         n = x.shape[1]
@@ -209,7 +214,8 @@ class ModelSessionManager:
                 on_device = self._session_key if self.config.noise_source == "device" else None
                 made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval,
                                       noise_keys=on_device if k == "preprocess" else None, apg_eta=self.config.apg_eta,
-                                      apg_norm=self.config.apg_norm, cfg_reuse=self.config.cfg_reuse) for k in SESSION_IO}
+                                      apg_norm=self.config.apg_norm, cfg_reuse=self.config.cfg_reuse, block_cache=self.config.block_cache,
+                                      block_cache_interval=self.config.block_cache_interval) for k in SESSION_IO}
             for name in ("preprocess", "transformer", "decode"):
                 sess = made[name]
                 self.sessions[name] = sess

@@ -80,6 +80,14 @@ class ModelConfig:
     cfg_reuse_report: bool = False          # N21, needs cfg_reuse > 1: per evaluation and item the sums (|D - D_stored|^2, |D|^2) of the guidance
                                             # difference at the computed evaluations, reduced on the device -- how far it moved while it was reused
                                             # (HipSynth.last_cfg_reuse_report, TTSEngine.last_cfg_reuse_report).  Off = nothing is launched or allocated
+    block_cache: Optional[Tuple[int, int, int]] = None      # block caching, (first, last, every): the DiT blocks [first, last) run at
+                                            # every ``every``-th evaluation only; in between their stored contribution to the residual stream is added
+                                            # back instead.  None, or every = 1 = off.  The span is checked against the model's depth when the engine is
+                                            # built.  Not combined with cfg_interval, cfg_reuse > 1 or apg_eta / apg_norm
+    block_cache_interval: Optional[Tuple[float, float]] = None   # ... only at the evaluations with lo <= t <= hi; None = everywhere.  Needs block_cache
+    block_cache_report: bool = False        # N23, needs block_cache: per evaluation, item and CFG branch the sums (|C - C_stored|^2, |C|^2) of the span's
+                                            # contribution at the full evaluations, reduced on the device -- how far it moved while it was reused
+                                            # (HipSynth.last_block_cache_report, TTSEngine.last_block_cache_report).  On, every full evaluation stores
     noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
                                             # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
     output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
@@ -185,6 +193,16 @@ class ModelConfig:
             raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
         if self.cfg_reuse_report and not (self.cfg_reuse or 1) > 1:
             raise ValueError("cfg_reuse_report needs cfg_reuse > 1: it reports the drift of the reused guidance difference")
+        from ..model_spec import check_block_cache
+        self.block_cache = check_block_cache(self.block_cache, 1 << 30)     # three integers; a list (from_dict of JSON) becomes the tuple
+        self.block_cache_interval = check_cfg_interval(self.block_cache_interval)
+        self.block_cache_report = bool(self.block_cache_report)
+        if self.block_cache is not None:
+            if self.cfg_interval is not None or (self.cfg_reuse or 1) > 1 or check_apg(self.apg_eta, self.apg_norm) is not None:
+                raise ValueError("block_cache cannot be combined with cfg_interval, cfg_reuse > 1 or apg_eta / apg_norm (a guided subset moves the "
+                                 "unconditional rows between evaluations, which the stored rows do not follow)")
+        elif self.block_cache_report or self.block_cache_interval is not None:
+            raise ValueError("block_cache_report and block_cache_interval need block_cache")
         self.validate_paths()
 
     @property

@@ -38,6 +38,13 @@ class TTSEngine:
         self.config = config or ModelConfig()
         self.model_session_manager = ModelSessionManager(self.config, session_factory=session_factory)
         self.model_session_manager.load_models()
+        if self.config.block_cache is not None and self.model_session_manager.spec is not None:      # N23: the span against this model's depth
+            from ..model_spec import check_block_cache
+            try:
+                check_block_cache(self.config.block_cache, self.model_session_manager.spec.depth)
+            except ValueError:
+                self.model_session_manager.cleanup()
+                raise
         if not self.model_session_manager.vocab_path:
             raise RuntimeError("Vocabulary file not found in model tar archive")
         self.text_processor = TextProcessor(self.model_session_manager.vocab_path)
@@ -51,6 +58,7 @@ class TTSEngine:
         self._decode_graphs = None               # DecodeGraphCache, created with the first captured decode (use_hip_graph)
         self._last_plan = []
         self.last_cfg_reuse_report = []          # N21 (config.cfg_reuse_report): the drift reports of the last synthesis, float64 [n_evals, B, 2] per GPU batch
+        self.last_block_cache_report = []        # N23 (config.block_cache_report): the reports of the last synthesis, float64 [n_evals, B, 2, 2] per GPU batch
         self.last_ode_report = []                # N20 (config.ode_report): the step reports of the last synthesis, float64 [n_steps, B, 2] per GPU batch
 
     def cleanup(self) -> None:
@@ -246,6 +254,7 @@ class TTSEngine:
         eng.set_nfe(self.config.nfe_step, self.config.ode_method)
         eng.set_ode_report(self.config.ode_report)
         eng.set_cfg_reuse_report(self.config.cfg_reuse_report)
+        eng.set_block_cache_report(self.config.block_cache_report)
 
     def _synthesize_device(self, inputs_list, noise_blocks=None, noise_keys=None, device_out: bool = False, options=None):
         """inputs_list items are (audio (1,1,S_i), text_ids (1,T_i), max_duration (1,), time_step); the reference
@@ -268,6 +277,7 @@ class TTSEngine:
         self._set_ode_plan()
         self.last_ode_report = []
         self.last_cfg_reuse_report = []
+        self.last_block_cache_report = []
         hop = self.config.hop_length
         opts = self._resolved(options, len(inputs_list))
         g_all, iv_all, eta_all, norm_all, reuse_all = ([getattr(o, name) for o in opts]
@@ -277,6 +287,11 @@ class TTSEngine:
         for k, on in zip(reuse_all, apg_on):
             if (k or 1) > 1 and on:
                 raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
+        # N23: the engine's block caching for every batch.  Its entry takes no mask: a request's strength travels per item (also a strength
+        # of 0, whose unconditional rows are then computed and weighted by 0), and a request with an interval, reuse or APG of its own is refused
+        bc = dict(block_cache=self.config.block_cache, block_cache_interval=self.config.block_cache_interval)
+        if self.config.block_cache is not None and (any(v is not None for v in iv_all) or any((k or 1) > 1 for k in reuse_all) or any(apg_on)):
+            raise ValueError("block_cache cannot be combined with a request's cfg_interval, cfg_reuse > 1 or apg_eta / apg_norm")
         from ..sharding import plan_batches
         n_items = len(inputs_list)
         seq_all = [int(g[2][0]) for g in inputs_list]
@@ -353,10 +368,12 @@ class TTSEngine:
                 cfg = torch.tensor([float(spec.cfg_strength) if g_all[j] is None else g_all[j] for j in idx], dtype=torch.float32).to(dev)
             guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx], [reuse_all[j] for j in idx])     # None: every item guided everywhere
             apg = eng.apg_tensors([eta_all[j] for j in idx], [norm_all[j] for j in idx])      # None: the plain combine for every item
+            if self.config.block_cache is not None:
+                guide = None
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
                 x = noise.to(dev) if keys is None else eng.noise(keys, pre["seq_len"], N)
-                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide, apg=apg)
+                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide, apg=apg, **bc)
                 if self._decode_graphs is None:
                     self._decode_graphs = DecodeGraphCache(eng, self.config.decode_graph_cache_entries, self.config.decode_graph_cache_bytes)
                 pcm, pcm_len = self._decode_graphs.get(B, N, t_gen)(x, pre["ref_signal_len"], pre["seq_len"])
@@ -364,11 +381,13 @@ class TTSEngine:
                 _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N,
                                                               None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
-                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg)
+                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg, **bc)
             if self.config.ode_report:
                 self.last_ode_report.append(eng.last_ode_report())
             if self.config.cfg_reuse_report:
                 self.last_cfg_reuse_report.append(eng.last_cfg_reuse_report())
+            if self.config.block_cache_report:
+                self.last_block_cache_report.append(eng.last_block_cache_report())
             if device_out:
                 pcm = pcm.clone() if self.config.use_hip_graph else pcm.contiguous()      # a captured graph's output buffer is replayed over
                 for i, j in enumerate(idx):
@@ -541,10 +560,12 @@ class TTSEngine:
                                                torch.tensor([ids.shape[1]], dtype=torch.int32, device=dev),
                                                torch.from_numpy(plan.keep.reshape(1, -1)).to(dev),
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
-                                               guide=eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength], cfg.cfg_reuse), noise_keys=keys,
-                                               apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]))
+                                               guide=None if cfg.block_cache is not None else eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength], cfg.cfg_reuse),
+                                               noise_keys=keys, apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]), block_cache=cfg.block_cache,
+                                               block_cache_interval=cfg.block_cache_interval)
                 self.last_ode_report = [eng.last_ode_report()] if cfg.ode_report else []
                 self.last_cfg_reuse_report = [eng.last_cfg_reuse_report()] if cfg.cfg_reuse_report else []
+                self.last_block_cache_report = [eng.last_block_cache_report()] if cfg.block_cache_report else []
                 if self._device_output():                         # N10: rate / encoding in HBM; the length from the host's own plan
                     n_host = min(plan.spliced_len, m.spec.pcm_samples(plan.n_frames))
                     wave = self._finish_device((pcm[0], [(0, n_host)]), [1])[0]      # one request of one span, the engine's options

@@ -1215,6 +1215,10 @@ struct Lane {
     // N21 (a call that reuses guidance differences): the lane's stored D = p_c - p_u, [Rc][n_mel] fp32; the drift report's partial sums [B][n_tiles][2]
     float* d_buf = nullptr;
     double* drift_part = nullptr;
+    // N23 (a call that caches a span of blocks): the stored contribution of the span, [R][D] fp32 (a second plane with a report: the stores
+    // alternate); the report's partial sums [2B][n_tiles][2]
+    float* bc_buf[2] = {};
+    double* bc_part = nullptr;
 };
 // N20: slots of the slope ring.  q - 1 without a report: the fresh slope takes the slot of the oldest one the step reads.  With a report
 // one more (two at the least), so that f_{n-1} outlives the stage launch of step n.
@@ -1235,7 +1239,8 @@ struct GuideState {
 // ws_form, named by a size query: the workspace of a plain call, with the tables of a mask's subsets on top (whatever the mask), or with
 // APG's on top of those (with or without a mask).  A call with a mask or with APG implies its form.
 // N21: WS_REUSE / WS_REUSE_REPORT = the guided form plus a D buffer per lane, and the drift report's partial sums.
-enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG, WS_REUSE, WS_REUSE_REPORT };
+// N23: WS_CACHED / WS_CACHED_REPORT = the plain form plus a plane per lane, and with a report a second plane and the partial sums.
+enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG, WS_REUSE, WS_REUSE_REPORT, WS_CACHED, WS_CACHED_REPORT };
 struct StepsCall {
     vv_steps_args a{};
     const uint8_t* guide = nullptr; int ld_guide = 0;
@@ -1250,6 +1255,10 @@ struct StepsCall {
     // call is stored" in front of evaluation e
     bool with_reuse = false, with_drift = false;
     std::vector<uint8_t> ru_mode, ru_old;
+    // N23 (vv_transformer_steps_cached): the span and the modes of the plan's evaluations; derived by transformer_steps: a plane is needed
+    // (a mode other than 0, or a report) / the report is on
+    const vv_block_cache_args* bc = nullptr;
+    bool with_cache = false, with_cache_report = false;
 };
 struct StepDims { int D, FF, M, CD, es, KP, MP; };
 
@@ -1299,7 +1308,7 @@ LanePlan lane_plan(const vv_ctx* c, const StepDims& d, const std::vector<int>& h
 
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg, bool reuse, bool drift) {
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg, bool reuse, bool drift, bool cache, bool cache_report) {
     const size_t R = L.R, es = d.es, D = d.D, FF = d.FF, M = d.M, KP = d.KP, MP = d.MP;
     L.xcat = a.take<char>(es * R * KP);
     L.h = a.take<char>(es * R * D); L.h2 = a.take<char>(es * R * D); L.h3 = a.take<char>(es * R * D);
@@ -1331,6 +1340,11 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, boo
     }
     if (reuse) L.d_buf = a.take<float>(L.Rc * M);  // N21: behind everything the guided form takes, so that form's offsets stay as they are
     if (drift) L.drift_part = a.take<double>((size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2);
+    if (cache) L.bc_buf[0] = a.take<float>(R * D);  // N23: behind everything the other forms take, so their offsets stay as they are
+    if (cache_report) {
+        L.bc_buf[1] = a.take<float>(R * D);
+        L.bc_part = a.take<double>(2 * (size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2);
+    }
 }
 
 // The launches of one call, lane by lane: every member fills the arguments of its kernels for the Lane (or view of one) it is given and
@@ -1559,6 +1573,31 @@ struct StepsRun : StepDims {
         }
         return 0;
     }
+    // N23: one launch of the span kernel on a lane (or view) in front of a block or of the tail -- `which` plane takes X (MARK), becomes the
+    // span's contribution (DIFF), or is added back (APPLY: x is rewritten and nothing is pending behind it)
+    int span(Lane& L, int mode, int which) const {
+        vv_block_span_args a{};
+        a.mode = mode; a.delta_dtype = c->dt; a.x = L.xres; a.d1 = L.pending ? L.h2 : nullptr; a.d2 = L.pending ? L.h3 : nullptr;
+        a.buf = L.bc_buf[which]; a.R = (int)L.R; a.D = D;
+        {
+            Prof p(c, VV_PROF_ELEMWISE, 0, (4.0 + (L.pending ? 2.0 * es : 0) + (mode == VV_SPAN_MARK ? 4.0 : 8.0)) * L.R * D, L.st);
+            KCHK(c, vvk_block_span(&a, L.st, &m__));
+        }
+        if (mode == VV_SPAN_APPLY) L.pending = false;
+        return 0;
+    }
+    // N23: the report rows of evaluation e for the sequences of a lane (both branches) or of branch view v: the sums of plane `which` against
+    // the other one (with_prev) behind a DIFF, zeros (which < 0) at an evaluation that stores nothing
+    int span_report(Lane& L, int v, int e, int which, bool with_prev) const {
+        vv_block_drift_args r{};
+        r.R = (int)L.R; r.D = D; r.n_seq = L.n_seq; r.n_items = L.B; r.branch0 = P.branch_lanes ? v : 0; r.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE;
+        r.row_start = L.row_start; r.len = L.kv_len; r.partials = L.bc_part; r.report = q.bc->report + ((size_t)e * q.a.B + L.b0) * 4;
+        if (which < 0) { Prof p(c, VV_PROF_ELEMWISE, 0, 16.0 * L.n_seq, L.st); KCHK(c, vvk_block_drift_reduce(&r, 4, L.st, &m__)); return 0; }
+        r.d_new = L.bc_buf[which]; r.d_prev = with_prev ? L.bc_buf[which ^ 1] : nullptr;
+        { Prof p(c, VV_PROF_ELEMWISE, 6.0 * L.R * D, (with_prev ? 8.0 : 4.0) * L.R * D, L.st); KCHK(c, vvk_block_drift_reduce(&r, 1, L.st, &m__)); }
+        { Prof p(c, VV_PROF_ELEMWISE, 0, 16.0 * L.n_seq * r.n_tiles, L.st); KCHK(c, vvk_block_drift_reduce(&r, 2, L.st, &m__)); }
+        return 0;
+    }
     // What the block-level kernels (step_head, block, step_tail) run on: views of the lanes' buffers, two at the most; -> their number.
     // The schedule gives each its stream.  Branch lanes: view v is the conditional (0) or the unconditional (1) half of the one lane's rows.
     Lane branch_view(const Lane& L, int v) const {
@@ -1568,6 +1607,8 @@ struct StepsRun : StepDims {
         V.xcat += r0 * KP * es; V.h += r0 * D * es; V.h2 += r0 * D * es; V.h3 += r0 * D * es; V.att += r0 * D * es;
         V.qkv += r0 * 3 * D * es; V.ffm += r0 * FF * es; V.xres += r0 * D; V.pred += r0 * MP;
         V.csq_rows += r0 * 64; V.csk_rows += r0 * 64;
+        for (float*& b : V.bc_buf) if (b) b += r0 * D;                 // N23: the view's half of the planes and of the partial sums
+        if (V.bc_part && v) V.bc_part += (size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2;
         // row_start / kv_len: the conditional branch's entries serve both views (same lengths, rows relative to the view's base);
         // row_pos: the first Rc entries (a row's position does not depend on its branch)
         return V;
@@ -1624,6 +1665,10 @@ int steps_schedule(const StepsRun& r, Lane* lanes, hipStream_t st) {
     };
     for (int li = 0; li < n_lanes; ++li) lanes[li].st = streams[li];
     int n_views = make_views(nullptr), rc = 0;
+    // N23: the span, the modes, and where the latest stored contribution lives (plane `cur`; under a report the stores alternate)
+    const vv_block_cache_args* bc = r.q.with_cache ? r.q.bc : nullptr;
+    const bool bc_report = bc && r.q.with_cache_report;
+    int bc_cur = 0; bool bc_stored = false;
     if (n_lanes > 1) rc = fork();
     for (int li = 0; li < n_lanes && !rc; ++li) rc = r.setup(lanes[li]);
     for (int s = step0; s < step0 + n_steps && !rc; ++s)
@@ -1635,9 +1680,24 @@ int steps_schedule(const StepsRun& r, Lane* lanes, hipStream_t st) {
             if (want_fork && !rc) rc = fork();
             const bool forked = want_fork && !rc;
             for (int v = 0; v < n_views && !rc; ++v) rc = r.step_head(views[v]);
-            for (int l = 0; l < r.g.depth && !rc; ++l)
-                for (int v = 0; v < n_views && !rc; ++v) rc = r.block(views[v], e, l);
-            for (int v = 0; v < n_views && !rc; ++v) rc = r.step_tail(views[v], e);
+            const int mode = bc ? bc->modes_host[e] : VV_BLOCK_FULL;
+            if (mode == VV_BLOCK_STORE && bc_report && bc_stored) bc_cur ^= 1;
+            for (int l = 0; l <= r.g.depth && !rc; ++l)   // l = depth: the tail
+                for (int v = 0; v < n_views && !rc; ++v) {
+                    Lane& V = views[v];
+                    if (mode == VV_BLOCK_LIGHT && l >= bc->first && l < bc->last) {     // the span: its first block's place takes the APPLY, the rest launch nothing
+                        if (l == bc->first) rc = r.span(V, VV_SPAN_APPLY, bc_cur);
+                        continue;
+                    }
+                    if (mode == VV_BLOCK_STORE && l == bc->first) rc = r.span(V, VV_SPAN_MARK, bc_cur);
+                    if (mode == VV_BLOCK_STORE && l == bc->last && !rc) {
+                        rc = r.span(V, VV_SPAN_DIFF, bc_cur);
+                        if (bc_report && !rc) rc = r.span_report(V, v, e, bc_cur, bc_stored);
+                    }
+                    if (bc_report && mode != VV_BLOCK_STORE && l == r.g.depth && !rc) rc = r.span_report(V, v, e, -1, false);
+                    if (!rc) rc = l < r.g.depth ? r.block(V, e, l) : r.step_tail(V, e);
+                }
+            if (mode == VV_BLOCK_STORE) bc_stored = true;
             if (forked) join();
             for (int li = 0; li < n_lanes && !rc; ++li) rc = r.combine(lanes[li], s, i);
         }
@@ -1652,7 +1712,7 @@ int steps_schedule(const StepsRun& r, Lane* lanes, hipStream_t st) {
 static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
     if (!c) return -22;
     const vv_steps_args& a = q.a;
-    q.with_apg = q.apg != nullptr || q.ws_form == WS_APG; q.guided = q.guide != nullptr || q.ws_form != WS_PLAIN || q.with_apg;
+    q.with_apg = q.apg != nullptr || q.ws_form == WS_APG; q.guided = q.guide != nullptr || (q.ws_form != WS_PLAIN && q.ws_form != WS_CACHED && q.ws_form != WS_CACHED_REPORT) || q.with_apg;
     q.rk = c->ode_s > 1 || c->ms_q > 0 || a.cfg_item != nullptr || q.guide != nullptr || q.apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     const int B = a.B, N = a.N;
     if (!c->finalized || !c->modtab) return c->fail(-1, "vv_transformer_steps: weights/time grid not ready");
@@ -1699,6 +1759,26 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
             }
         }
     }
+    q.with_cache_report = q.ws_form == WS_CACHED_REPORT || (q.bc && q.bc->report); q.with_cache = q.with_cache_report || q.ws_form == WS_CACHED || q.bc;
+    if (q.with_cache && c->split_k_tail) return c->fail(-22, "vv_transformer_steps_cached: block caching cannot be combined with option split_k_tail (its tail rows keep fp32 parts instead of a delta)");
+    if (q.bc) {                                           // N23: the span, the modes of the plan and what the call's own evaluations ask for
+        const vv_block_cache_args& k = *q.bc;
+        const int E = c->n_steps * c->ode_s, e0 = a.step0 * c->ode_s, e1 = (a.step0 + a.n_steps) * c->ode_s;
+        if (k.first < 0 || k.first >= k.last || k.last > c->cfg.depth) return c->fail(-22, "vv_transformer_steps_cached: the span [%d, %d) is not inside the %d blocks", k.first, k.last, c->cfg.depth);
+        if (!k.modes_host || k.n_modes != E) return c->fail(-22, "vv_transformer_steps_cached: one mode per evaluation of the plan (%d), got %d", E, k.n_modes);
+        if (k.report && ((uintptr_t)k.report % 8 || k.report_B != B || k.report_evals != E))
+            return c->fail(-22, "vv_transformer_steps_cached: the report is float64 [%d evaluations of the plan][%d items][2][2], got [%d][%d][2][2]", E, B, k.report_evals, k.report_B);
+        if (k.report && B > VVK_GUIDE_MAX_ITEMS) return c->fail(-22, "vv_transformer_steps_cached: at most %d items per call with a report", VVK_GUIDE_MAX_ITEMS);
+        for (int e = 0; e < E; ++e)
+            if (k.modes_host[e] > VV_BLOCK_LIGHT) return c->fail(-22, "vv_transformer_steps_cached: mode %d at evaluation %d (0 = full, 1 = full and store, 2 = light)", (int)k.modes_host[e], e);
+        bool stored = false;
+        for (int e = e0; e < e1; ++e) {
+            if (k.modes_host[e] == VV_BLOCK_LIGHT && a.step0 != 0)
+                return c->fail(-22, "vv_transformer_steps_cached: a call with a light evaluation starts at step 0 (the stored contribution lives for one call), got step0 = %d", a.step0);
+            if (k.modes_host[e] == VV_BLOCK_LIGHT && !stored) return c->fail(-22, "vv_transformer_steps_cached: evaluation %d is light with no storing evaluation before it in the call", e);
+            stored = stored || k.modes_host[e] == VV_BLOCK_STORE;
+        }
+    }
     hipStream_t st = enter(c, stream);
     const vv_model_cfg& g = c->cfg;
     const StepDims d{g.dim, g.dim * g.ff_mult, g.n_mel, g.n_mel + g.text_dim, c->esz(), pad_to(2 * g.n_mel + g.text_dim, 64), pad_to(g.n_mel, 128)};
@@ -1723,7 +1803,7 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
         return c->fail(-22, "vv_transformer_steps: %zu packed rows make a %zu-byte qkv buffer; kernels address it with 32-bit byte offsets "
                             "(< 2 GiB) -- synthesise fewer units per call", 2 * Rc_all, 2 * Rc_all * 3 * (size_t)d.D * d.es);
     LanePlan P = lane_plan(c, d, hlen, N);
-    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg, q.with_reuse, q.with_drift); };
+    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg, q.with_reuse, q.with_drift, q.with_cache, q.with_cache_report); };
     if (q.ws_only) { *q.ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
     if (int r = plan_ws(c, a.ws, (size_t)a.ws_bytes, bufs)) return r;
     for (int li = 0; li < P.n_lanes; ++li) {              // each lane's slice of the call's arrays
@@ -1829,6 +1909,26 @@ int vv_transformer_steps_reuse(vv_ctx* c, const vv_steps_args* a, const uint8_t*
 
 int vv_transformer_reuse_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes) {
     return steps_ws_query(c, "vv_transformer_reuse_ws_bytes", with_report ? WS_REUSE_REPORT : WS_REUSE, B, N, seq_len_host, bytes);
+}
+
+// N23: block caching on top of vv_transformer_steps_ex (include/vvtts.h)
+int vv_transformer_steps_cached(vv_ctx* c, const vv_steps_args* a, const vv_block_cache_args* cache, void* stream) {
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_cached: null arguments");
+    if (!cache) return vv_transformer_steps_ex(c, a, stream);
+    bool any = cache->report != nullptr;
+    if (cache->modes_host && cache->n_modes == c->n_steps * c->ode_s && cache->first >= 0 && cache->first < cache->last && cache->last <= c->cfg.depth) {
+        for (int e = 0; e < cache->n_modes; ++e) any = any || cache->modes_host[e] != VV_BLOCK_FULL;
+        if (!any) return vv_transformer_steps_ex(c, a, stream);     // every evaluation full, no report: the plain call, launches and workspace
+    }
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_cached: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_cached: cfg_item must be a float array");
+    StepsCall q; q.a = *a; q.bc = cache;
+    return transformer_steps(c, q, stream);
+}
+
+int vv_transformer_cached_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes) {
+    return steps_ws_query(c, "vv_transformer_cached_ws_bytes", with_report ? WS_CACHED_REPORT : WS_CACHED, B, N, seq_len_host, bytes);
 }
 
 // --------------------------------------------------------------------------------------- decode
@@ -2215,6 +2315,14 @@ int vv_ode_stage_reuse(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_r
     if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_reuse: null arguments") : -22;
     if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_reuse: u_row must be an int32 array");
     SINGLE(c, vvk_ode_stage(a, u_row, nullptr, (hipStream_t)st, &m__, 0, reuse));
+}
+int vv_block_span(vv_ctx* c, const vv_block_span_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_block_span: null arguments") : -22;
+    SINGLE(c, vvk_block_span(a, (hipStream_t)st, &m__));
+}
+int vv_block_drift_reduce(vv_ctx* c, const vv_block_drift_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_block_drift_reduce: null arguments") : -22;
+    SINGLE(c, vvk_block_drift_reduce(a, 3, (hipStream_t)st, &m__));
 }
 int vv_cfg_drift_reduce(vv_ctx* c, const vv_cfg_drift_args* a, void* st) {
     if (!c || !a) return c ? c->fail(-22, "vv_cfg_drift_reduce: null arguments") : -22;

@@ -507,6 +507,107 @@ __global__ __launch_bounds__(256) void cfg_drift_reduce_kernel(const float* __re
     if (threadIdx.x < 2) partials[((size_t)b * n_tiles + tile) * 2 + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// ---------------------------------------------------------------- N23: block caching, the span kernels
+// X = the fp32 residual stream at a block boundary, formed per element as ln_mod_kernel forms it: (x + (float)d1) + (float)d2 with the two
+// pending deltas of the block in front (fp32 adds, in this order), or plain x when nothing is pending (d1 NULL).  Over n4 float4s of the
+// contiguous [R][D] planes:
+//   MARK   buf = X                (x and the deltas are read only)
+//   DIFF   buf = X - buf          (one fp32 subtraction: the span's contribution, X at its end less X at its start)
+//   APPLY  x   = X + buf          (one fp32 add: the stored contribution in place of the span's blocks; buf is read only)
+// Flat, float4, grid-stride with size_t indices: every element is read and written by one thread.  The planes are far larger than the
+// caches and each is touched once per evaluation: non-temporal loads and stores, as ln_mod_kernel's.  No LDS, no atomics.
+template <typename Td, int MODE>
+__global__ __launch_bounds__(256) void block_span_kernel(float* x, const Td* __restrict__ d1, const Td* __restrict__ d2, float* buf, size_t n4) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < n4; q += stride) {
+        float4 v = load4_nt<float>(x + q * 4);
+        if (d1) {
+            const float4 a = load4_nt<Td>(d1 + q * 4);
+            v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+            if (d2) {
+                const float4 b = load4_nt<Td>(d2 + q * 4);
+                v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
+            }
+        }
+        if (MODE == VV_SPAN_MARK) {
+            store4_nt<float>(buf + q * 4, v.x, v.y, v.z, v.w);
+        } else {
+            const float4 s = load4_nt<float>(buf + q * 4);
+            if (MODE == VV_SPAN_DIFF) store4_nt<float>(buf + q * 4, v.x - s.x, v.y - s.y, v.z - s.z, v.w - s.w);
+            else store4_nt<float>(x + q * 4, v.x + s.x, v.y + s.y, v.z + s.z, v.w + s.w);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- N23: the drift report of block caching, the per-sequence reduction
+// Partial sums of one (frame tile, sequence): E2 = sum (d_new - d_prev)^2 and N2 = sum d_new^2 over the tile's valid frames and the D columns
+// of two stored contributions ([R][D] fp32).  Sequence s owns the rows [row_start[s], + len[s]) -- one CFG branch of one item.  d_prev NULL
+// (the first store of a call): E2 = 0.  Differences, squares and sums in float64 and NOT contracted.  cfg_drift_reduce_kernel's determinism
+// contract: tiles of VV_APG_TILE frames counted from the SEQUENCE's frame 0, float4 q of the tile to thread q % 256 with its four elements in
+// order, one fixed LDS tree -- a sequence's partials are a function of its own rows alone.  grid (n_tiles, n_seq); a tile past the length
+// writes nothing.
+__global__ __launch_bounds__(256) void block_drift_reduce_kernel(const float* __restrict__ d_new, const float* __restrict__ d_prev, int R, int D,
+                                                                 const int* __restrict__ row_start, const int* __restrict__ len, int n_tiles,
+                                                                 double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double red[2][256];
+    const int s = blockIdx.y, tile = blockIdx.x;
+    const int r0 = min(max(row_start[s], 0), R);
+    const int n = min(min(max(len[s], 0), R - r0), n_tiles * VV_APG_TILE);    // inside the R rows and the sequence's n_tiles partials, whatever the tables say
+    const int f0 = tile * VV_APG_TILE;
+    if (f0 >= n) return;
+    const int c4 = D >> 2;
+    const int total = min(VV_APG_TILE, n - f0) * c4;
+    double s1 = 0.0, s2 = 0.0;
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const size_t at = ((size_t)r0 + f0 + q / c4) * D + (q % c4) * 4;
+        const float4 a = load4_nt<float>(d_new + at);
+        const float av[4] = {a.x, a.y, a.z, a.w};
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (d_prev) {
+            const float4 p = load4_nt<float>(d_prev + at);
+            pv[0] = p.x; pv[1] = p.y; pv[2] = p.z; pv[3] = p.w;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double v = (double)av[j];
+            if (d_prev) {
+                const double d = v - (double)pv[j];
+                const double dd = d * d;
+                s1 = s1 + dd;
+            }
+            const double vv = v * v;
+            s2 = s2 + vv;
+        }
+    }
+    red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) partials[((size_t)s * n_tiles + tile) * 2 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// One wave per sequence: lane j < 2 adds the sequence's partials in ascending tile order from 0.0 and stores them at the report's
+// [item][branch][2] place: item = s % n_items, branch = branch0 + s / n_items.  {0, 0} for a sequence without rows, and for every sequence
+// when n_tiles is 0 (an evaluation that stores nothing: the partials are not read).
+__global__ __launch_bounds__(64) void block_drift_finish_kernel(const double* __restrict__ partials, int n_tiles, int R,
+                                                                const int* __restrict__ row_start, const int* __restrict__ len, int n_items,
+                                                                int branch0, double* __restrict__ report) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    if (lane >= 2) return;
+    const int r0 = min(max(row_start[s], 0), R);
+    const int n = min(min(max(len[s], 0), R - r0), n_tiles * VV_APG_TILE);
+    const int nt = (n + VV_APG_TILE - 1) / VV_APG_TILE;
+    double sum = 0.0;
+    for (int t = 0; t < nt; ++t) sum += partials[((size_t)s * n_tiles + t) * 2 + lane];
+    report[((size_t)(s % n_items) * 2 + (branch0 + s / n_items)) * 2 + lane] = sum;
+}
+
 // ---------------------------------------------------------------- text: embed gather + position table
 // Sequence s in [0, 2B): b = s % B, drop branch when s >= B (all filler ids).  Token t of the
 // text is id+1; beyond the text (or the sequence) the filler id 0.
@@ -1003,6 +1104,55 @@ int vvk_cfg_drift_reduce(const vv_cfg_drift_args* a, int which, hipStream_t st, 
     }
     if (which & 2) {
         ode_diff_finish_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->row_start, a->len, a->report);
+        VVK_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// N23: one MARK, DIFF or APPLY launch of block_span_kernel
+int vvk_block_span(const vv_block_span_args* a, hipStream_t st, const char** err) {
+    if (a->mode < VV_SPAN_MARK || a->mode > VV_SPAN_APPLY) { *err = "block_span: mode is VV_SPAN_MARK, VV_SPAN_DIFF or VV_SPAN_APPLY"; return -22; }
+    if (a->R < 1 || a->D < 4 || a->D % 4) { *err = "block_span: R >= 1, D a multiple of 4"; return -22; }
+    if (!a->x || !a->buf || (a->d2 && !a->d1)) { *err = "block_span: x and buf are required, d2 needs d1"; return -22; }
+    const bool db = a->delta_dtype == VV_BF16;
+    if (((uintptr_t)a->x | (uintptr_t)a->buf) % 16 || ((uintptr_t)a->d1 | (uintptr_t)a->d2) % (db ? 8 : 16)) {
+        *err = "block_span: x and buf must be 16-byte aligned, the deltas 16-byte (f32) or 8-byte (bf16)"; return -22;
+    }
+    const size_t n4 = (size_t)a->R * a->D / 4;
+    if ((uintptr_t)a->x < (uintptr_t)a->buf + n4 * 16 && (uintptr_t)a->buf < (uintptr_t)a->x + n4 * 16) { *err = "block_span: buf must be a plane of its own"; return -22; }
+    const int grid = grid_for(n4);
+#define SPAN_GO(Td, M) block_span_kernel<Td, M><<<grid, 256, 0, st>>>(a->x, (const Td*)a->d1, (const Td*)a->d2, a->buf, n4)
+#define SPAN_DT(M) do { if (db) SPAN_GO(bf16, M); else SPAN_GO(float, M); } while (0)
+    if (a->mode == VV_SPAN_MARK) SPAN_DT(VV_SPAN_MARK);
+    else if (a->mode == VV_SPAN_DIFF) SPAN_DT(VV_SPAN_DIFF);
+    else SPAN_DT(VV_SPAN_APPLY);
+#undef SPAN_DT
+#undef SPAN_GO
+    VVK_CHECK_LAUNCH();
+    return 0;
+}
+
+// N23: the two kernels behind vv_block_drift_reduce.  which & 1: the reduction, which & 2: the sequence sums at their [item][branch] place;
+// which == 4: zeros at those places (the finishing kernel over no tiles: nothing but the tables is read).
+int vvk_block_drift_reduce(const vv_block_drift_args* a, int which, hipStream_t st, const char** err) {
+    if (a->D < 4 || a->D % 4 || a->R < 1) { *err = "block_drift_reduce: D must be a multiple of 4, R >= 1"; return -22; }
+    if (!a->row_start || !a->len || !a->report || (which != 4 && (!a->d_new || !a->partials))) { *err = "block_drift_reduce: d_new, row_start, len, partials and report are required"; return -22; }
+    if (a->n_items < 1 || a->n_items > VVK_GUIDE_MAX_ITEMS || a->n_tiles < 1) { *err = "block_drift_reduce: 1..1024 items, n_tiles >= 1"; return -22; }
+    if (!((a->n_seq == a->n_items && (a->branch0 == 0 || a->branch0 == 1)) || (a->n_seq == 2 * a->n_items && a->branch0 == 0))) {
+        *err = "block_drift_reduce: n_seq is n_items (one branch, branch0 0 or 1) or 2 n_items (both, branch0 0)"; return -22;
+    }
+    if (((uintptr_t)a->d_new | (uintptr_t)a->d_prev) % 16 || ((uintptr_t)a->partials | (uintptr_t)a->report) % 8) { *err = "block_drift_reduce: d_new and d_prev 16-byte, partials and report 8-byte aligned"; return -22; }
+    if (which == 4) {
+        block_drift_finish_kernel<<<a->n_seq, 64, 0, st>>>(a->partials, 0, a->R, a->row_start, a->len, a->n_items, a->branch0, a->report);
+        VVK_CHECK_LAUNCH();
+        return 0;
+    }
+    if (which & 1) {
+        block_drift_reduce_kernel<<<dim3(a->n_tiles, a->n_seq), 256, 0, st>>>(a->d_new, a->d_prev, a->R, a->D, a->row_start, a->len, a->n_tiles, a->partials);
+        VVK_CHECK_LAUNCH();
+    }
+    if (which & 2) {
+        block_drift_finish_kernel<<<a->n_seq, 64, 0, st>>>(a->partials, a->n_tiles, a->R, a->row_start, a->len, a->n_items, a->branch0, a->report);
         VVK_CHECK_LAUNCH();
     }
     return 0;

@@ -37,6 +37,10 @@ int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_sta
                   const vv_reuse_stage_args* reuse = nullptr);
 // N21: the drift report -- which & 1: cfg_drift_reduce_kernel, which & 2: the item sums
 int vvk_cfg_drift_reduce(const vv_cfg_drift_args* a, int which, hipStream_t st, const char** err);
+// N23 block caching: one MARK / DIFF / APPLY launch of the span kernel; the report -- which & 1: block_drift_reduce_kernel, which & 2: the
+// sequence sums, which == 4: zeros in their place
+int vvk_block_span(const vv_block_span_args* a, hipStream_t st, const char** err);
+int vvk_block_drift_reduce(const vv_block_drift_args* a, int which, hipStream_t st, const char** err);
 // N20: the step report -- which & 1: ode_diff_reduce_kernel, which & 2: the item sums
 int vvk_ode_diff_reduce(const vv_ode_diff_args* a, int which, hipStream_t st, const char** err);
 // N11: apg_reduce_kernel (which & 1) and apg_coef_kernel (which & 2) of one evaluation

@@ -345,6 +345,54 @@ def guidance_mask(plan: OdePlan, interval, strengths, reuse=None) -> Optional[to
     return mask
 
 
+def check_block_cache(value, depth: int) -> Optional[Tuple[int, int, int]]:
+    """N23 block caching: None, or (first, last, every) -- the span [first, last) of the ``depth`` DiT blocks and the period of the full
+    evaluations -- as three integers with 0 <= first < last <= depth and every >= 1 (1 = no block is ever skipped).  A list (from JSON)
+    becomes the tuple.  ValueError for anything else."""
+    if value is None:
+        return None
+    try:
+        vals = tuple(value)
+    except TypeError:
+        raise ValueError("block_cache must be None or (first, last, every)") from None
+    if len(vals) != 3 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) for v in vals):
+        raise ValueError("block_cache must be None or three integers (first, last, every)")
+    first, last, every = (int(v) for v in vals)
+    if not 0 <= first < last <= int(depth):
+        raise ValueError(f"block_cache: the span must satisfy 0 <= first < last <= depth = {int(depth)}, got [{first}, {last})")
+    if every < 1:
+        raise ValueError("block_cache: every must be >= 1")
+    return first, last, every
+
+
+BLOCK_FULL, BLOCK_STORE, BLOCK_LIGHT = 0, 1, 2      # VV_BLOCK_* of include/vvtts.h: an evaluation's mode under block caching (N23)
+
+
+def block_cache_schedule(plan: OdePlan, every: int, interval=None, report: bool = False) -> torch.Tensor:
+    """N23: the mode of every evaluation of ``plan`` under block caching, uint8 [n_evals], row e = step * s + stage as in ``plan.t``.
+    Evaluation e is a candidate when ``interval`` is None or lo <= float(plan.t[e]) <= hi (both edges inclusive, the fp32 time compared
+    as a double, as guidance_mask does); candidate number j (in ascending e) is LIGHT (2) iff every > 1 and j % every != 0; every other
+    evaluation is FULL, and a FULL evaluation STOREs (1) iff the next evaluation is LIGHT or ``report`` is on.  The first candidate is
+    always full, so a LIGHT evaluation always has a store in front of it; every = 1 skips nothing."""
+    if isinstance(every, bool) or not isinstance(every, numbers.Integral) or int(every) < 1:
+        raise ValueError("block_cache_schedule: every must be an integer >= 1")
+    every = int(every)
+    iv = check_cfg_interval(interval)
+    t = [float(v) for v in plan.t]
+    assert all(t[e] <= t[e + 1] for e in range(len(t) - 1)), "the evaluation times of a plan do not decrease: the candidates are contiguous"
+    modes = torch.zeros((len(t),), dtype=torch.uint8)
+    j = 0
+    for e, te in enumerate(t):
+        if iv is None or iv[0] <= te <= iv[1]:
+            if every > 1 and j % every != 0:
+                modes[e] = BLOCK_LIGHT
+            j += 1
+    for e in range(len(t)):
+        if modes[e] == BLOCK_FULL and (report or (e + 1 < len(t) and modes[e + 1] == BLOCK_LIGHT)):
+            modes[e] = BLOCK_STORE
+    return modes
+
+
 def check_apg(eta, norm) -> Optional[Tuple[float, Optional[float]]]:
     """N11 projected guidance (Sadat et al. 2025) of one item: ``eta`` scales the part of the guidance difference parallel to the
     conditional data estimate (None = 1, plain CFG's), ``norm`` caps the RMS of the data-space difference (None = no cap).  Returns

@@ -16,7 +16,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ODE_MAX_EVALS, ODE_MULTISTEP, ModelSpec, check_apg, guidance_mask, ode_plan
+from .model_spec import ODE_MAX_EVALS, ODE_MULTISTEP, ModelSpec, block_cache_schedule, check_apg, check_block_cache, guidance_mask, ode_plan
 from .pcm_stage import JOIN_MAX_N, LOUD_RUN, PcmStage, _ptr, plan_join  # noqa: F401  (the constants and plan_join stay importable from here)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -144,6 +144,24 @@ class vv_cfg_drift_args(C.Structure):
                 ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p), ("report", C.c_void_p)]
 
 
+class vv_block_cache_args(C.Structure):
+    _fields_ = [("first", C.c_int32), ("last", C.c_int32), ("modes_host", C.c_void_p), ("n_modes", C.c_int32), ("report", C.c_void_p),
+                ("report_B", C.c_int32), ("report_evals", C.c_int32)]
+
+
+class vv_block_span_args(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("delta_dtype", C.c_int32), ("x", C.c_void_p), ("d1", C.c_void_p), ("d2", C.c_void_p), ("buf", C.c_void_p),
+                ("R", C.c_int32), ("D", C.c_int32)]
+
+
+class vv_block_drift_args(C.Structure):
+    _fields_ = [("d_new", C.c_void_p), ("d_prev", C.c_void_p), ("R", C.c_int32), ("D", C.c_int32), ("n_seq", C.c_int32), ("n_items", C.c_int32),
+                ("branch0", C.c_int32), ("n_tiles", C.c_int32), ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p),
+                ("report", C.c_void_p)]
+
+
+SPAN_MARK, SPAN_DIFF, SPAN_APPLY = 0, 1, 2      # VV_SPAN_* of include/vvtts.h: the form of one vv_block_span launch (N23)
+
 REUSE_LOAD, REUSE_STORE = 1, 2          # VV_REUSE_LOAD / VV_REUSE_STORE of include/vvtts.h: an item's mode in vv_ode_stage_reuse
 
 APG_TILE = 32                 # VV_APG_TILE of include/vvtts.h: frames per partial sum of the projected-guidance reduction
@@ -174,6 +192,10 @@ EXPORTS = {
     "vv_transformer_reuse_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "vv_ode_stage_reuse": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_reuse_stage_args), C.c_void_p]),
     "vv_cfg_drift_reduce": (C.c_int, [C.c_void_p, C.POINTER(vv_cfg_drift_args), C.c_void_p]),
+    "vv_transformer_steps_cached": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.POINTER(vv_block_cache_args), C.c_void_p]),
+    "vv_transformer_cached_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
+    "vv_block_span": (C.c_int, [C.c_void_p, C.POINTER(vv_block_span_args), C.c_void_p]),
+    "vv_block_drift_reduce": (C.c_int, [C.c_void_p, C.POINTER(vv_block_drift_args), C.c_void_p]),
     "vv_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_preprocess_h": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -417,6 +439,8 @@ class HipSynth(PcmStage):
         self._ode_report = None          # the last call's report, float64 [n_steps, B, 2] on the device
         self.cfg_reuse_report = False    # N21: every transformer_steps call with a mask leaves its drift report (last_cfg_reuse_report)
         self._cfg_reuse_report = None    # the last such call's report, float64 [n_evals, B, 2] on the device
+        self.block_cache_report = False  # N23: every transformer_steps call with a block cache leaves its report (last_block_cache_report)
+        self._block_cache_report = None  # the last such call's report, float64 [n_evals, B, 2, 2] on the device
         self.set_nfe(nfe_step, ode_method)
         self.set_ode_report(ode_report)
 
@@ -514,6 +538,43 @@ class HipSynth(PcmStage):
             rep = self._cfg_reuse_report
         return None if rep is None else rep.cpu().numpy()
 
+    def set_block_cache_report(self, on: bool):
+        """N23: turn the report of block caching on or off (ModelConfig.block_cache_report).  On, every transformer_steps call with a
+        block cache stores at each full evaluation and leaves float64 [n_evals, B, 2, 2] for last_block_cache_report; off (the default)
+        launches and allocates nothing for it."""
+        with self._lock:
+            self.block_cache_report = bool(on)
+            if not on:
+                self._block_cache_report = None
+
+    def last_block_cache_report(self):
+        """N23: the report of the last transformer_steps call that cached blocks, numpy float64 [n_evals, B, 2, 2]: per evaluation e, item
+        b and CFG branch (0 conditional, 1 unconditional) (E2, N2) = (sum (C_e - C_stored)^2, sum C_e^2) over the item's frames and the
+        model's columns, C the contribution of the span of blocks to the residual stream at a full evaluation and C_stored the one of
+        the previous full evaluation of the call (E2 = 0 at the first); (0, 0) at a light evaluation and outside the call.
+        sqrt(E2 / N2) is how far the contribution moved between two full evaluations.  One copy from the device; None when no call has
+        left a report."""
+        with self._lock:
+            rep = self._block_cache_report
+        return None if rep is None else rep.cpu().numpy()
+
+    def block_cache_modes(self, block_cache, interval=None) -> Optional[torch.Tensor]:
+        """N23: the ``block_modes`` of transformer_steps_ex for ``block_cache`` = (first, last, every) on the plan in force
+        (model_spec.block_cache_schedule, with this engine's report switch) -> (first, last, uint8 host tensor [n_evals]); None for None."""
+        bc = check_block_cache(block_cache, self.spec.depth)
+        if bc is None:
+            return None
+        return bc[0], bc[1], block_cache_schedule(self.plan, bc[2], interval, self.block_cache_report)
+
+    def cached_ws_bytes(self, B: int, N: int, seq_len_host, report: bool = False) -> int:
+        """Bytes of a caller-owned workspace for a call that caches blocks (vv_transformer_cached_ws_bytes; the same for every schedule):
+        the plain figure plus one fp32 plane of the lane's rows x the model's width per lane, plus a second plane and the partial sums
+        when ``report``."""
+        nb = C.c_uint64()
+        with self._lock:
+            self._check(self.lib.vv_transformer_cached_ws_bytes(self.ctx, int(B), int(N), _host_lens(B, seq_len_host), int(bool(report)), C.byref(nb)))
+        return int(nb.value)
+
     class _ReportScope:
         """The report buffer of one steps call: set in front of it, cleared behind it whatever happens (the library keeps no pointer to a
         tensor that may be freed)."""
@@ -591,7 +652,8 @@ class HipSynth(PcmStage):
         return eta, norm
 
     def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None,
-                          cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, apg=None) -> torch.Tensor:
+                          cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, apg=None, block_cache=None,
+                          block_cache_interval=None) -> torch.Tensor:
         """x fp32 [B,N,n_mel] updated in place on the device.  seq_len_host (optional list / array of the B lengths, the same
         values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
         cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's.
@@ -599,17 +661,21 @@ class HipSynth(PcmStage):
         (vv_transformer_steps_guided; model_spec.guidance_mask builds it); None = every item guided everywhere.  A mask that holds a 2
         (N21 guidance reuse), or any mask while the drift report is on, goes to vv_transformer_steps_reuse.
         apg (optional pair (eta, norm) of fp32 [B] device tensors, either None, N11): projected guidance per item
-        (vv_transformer_steps_apg; apg_tensors builds it); None, or a pair of Nones = off: the existing entries."""
+        (vv_transformer_steps_apg; apg_tensors builds it); None, or a pair of Nones = off: the existing entries.
+        block_cache (optional (first, last, every), N23): the blocks [first, last) are skipped at every evaluation inside
+        block_cache_interval (None = everywhere) whose count is not a multiple of ``every`` (vv_transformer_steps_cached;
+        model_spec.block_cache_schedule builds the modes); never with a mask or apg.  None = the existing entries."""
         B, N, M = x.shape
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
         if seq_len_host is None:
             seq_len_host = pre.get("seq_len_host")
         if apg is not None and apg[0] is None and apg[1] is None:
             apg = None
-        if cfg is not None or guide is not None or apg is not None:
+        modes = self.block_cache_modes(block_cache, block_cache_interval)
+        if cfg is not None or guide is not None or apg is not None or modes is not None:
             assert cfg is None or (cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,)), "cfg: fp32 [B] on the device"
             host = None if seq_len_host is None else _host_lens(B, seq_len_host)
-            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg)
+            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg, block_modes=modes)
             return x
         with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
             tail = _pre_ptrs(pre) + (step0, n_steps, self._stream())
@@ -644,15 +710,23 @@ class HipSynth(PcmStage):
 
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
                              cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                             guide: Optional[torch.Tensor] = None, apg=None, reuse_entry: Optional[bool] = None) -> None:
+                             guide: Optional[torch.Tensor] = None, apg=None, reuse_entry: Optional[bool] = None, block_modes=None) -> None:
         """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
         the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host).  guide: a contiguous uint8
         HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
         ld_guide >= B).  apg: None, or a pair (eta, norm) of fp32 [B] device tensors (either None), handed to
         vv_transformer_steps_apg with the times of the plan in force.  reuse_entry (N21): True hands the mask to
         vv_transformer_steps_reuse (with the drift report's buffer when set_cfg_reuse_report is on), False never; None = when the mask
-        holds a 2 or the report is on.  Never together with apg."""
+        holds a 2 or the report is on.  Never together with apg.  block_modes (N23): None, or (first, last, modes) with modes a
+        contiguous uint8 HOST tensor [n_modes], handed to vv_transformer_steps_cached as they are (with the report's buffer when
+        set_block_cache_report is on); never together with guide or apg."""
         B, N, _ = x.shape
+        if block_modes is not None:
+            if guide is not None or apg is not None:
+                raise ValueError("block caching takes no guidance mask and no projected guidance (a guided subset moves the rows the cache stores)")
+            first, last, modes = block_modes
+            if not (isinstance(modes, torch.Tensor) and modes.device.type == "cpu" and modes.dtype == torch.uint8 and modes.dim() == 1 and modes.is_contiguous()):
+                raise ValueError("block_modes is (first, last, a contiguous uint8 host tensor of one mode per evaluation)")
         if apg is not None:
             if len(apg) != 2 or any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
                                                            and t.is_contiguous() and t.shape == (B,)) for t in apg):
@@ -676,7 +750,13 @@ class HipSynth(PcmStage):
         if apg is not None and guide is not None and bool((guide[:, :B] == 2).any()):
             raise ValueError("a mask that reuses guidance differences (a 2) is not combined with projected guidance (apg)")
         with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
-            if reuse_entry:
+            if block_modes is not None:
+                rep = torch.zeros((self.n_evals, B, 2, 2), dtype=torch.float64, device=self.device) if self.block_cache_report else None
+                k = vv_block_cache_args(int(first), int(last), modes.data_ptr(), int(modes.numel()), _ptr(rep), B, self.n_evals)
+                self._block_cache_report = None
+                self._check(self.lib.vv_transformer_steps_cached(self.ctx, C.byref(a), C.byref(k), self._stream()))
+                self._block_cache_report = rep
+            elif reuse_entry:
                 rep = torch.zeros((self.n_evals, B, 2), dtype=torch.float64, device=self.device) if self.cfg_reuse_report else None
                 r = vv_reuse_args(_ptr(rep), B, self.n_evals)
                 self._cfg_reuse_report = None
@@ -781,19 +861,21 @@ class HipSynth(PcmStage):
     def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: Optional[torch.Tensor], t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
                          audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, noise_keys=None,
-                         apg=None):
+                         apg=None, block_cache=None, block_cache_interval=None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
         noise fp32 [B, N, n_mel] on the device, or None with noise_keys = (model_spec.noise_keys rows): the noise is then drawn on the
         device (``noise``) and nothing of it crosses PCIe.  Exactly one of the two.
         gen_frames (host list, optional): per-item generated frames; lets the vocoder run in length buckets on ragged batches.
         seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
         cfg (optional fp32 [B] on the device): per-item guidance strength.  guide (optional uint8 [n_evals, B] on the host): the
-        guidance mask of transformer_steps.  apg (optional pair of fp32 [B] device tensors): its projected guidance."""
+        guidance mask of transformer_steps.  apg (optional pair of fp32 [B] device tensors): its projected guidance.  block_cache /
+        block_cache_interval (N23): its block caching."""
         self._one_noise(noise, noise_keys)
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, seq_len, N)
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg, block_cache=block_cache,
+                               block_cache_interval=block_cache_interval)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
             if pcm.shape[1] < t_gen_max * self.spec.hop_length:
@@ -861,7 +943,7 @@ class HipSynth(PcmStage):
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
                    noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
-                   guide: Optional[torch.Tensor] = None, noise_keys=None, apg=None):
+                   guide: Optional[torch.Tensor] = None, noise_keys=None, apg=None, block_cache=None, block_cache_interval=None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
@@ -882,7 +964,8 @@ class HipSynth(PcmStage):
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=self.device)
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, pre["seq_len"], N)
-        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg)
+        self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg, block_cache=block_cache,
+                               block_cache_interval=block_cache_interval)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
