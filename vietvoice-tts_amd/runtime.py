@@ -571,7 +571,7 @@ class HipSynth(PcmStage):
         the plain figure plus one fp32 plane of the lane's rows x the model's width per lane, plus a second plane and the partial sums
         when ``report``."""
         nb = C.c_uint64()
-        with self._lock:
+        with self._lock, self._SizedAsTheCall(self, B):
             self._check(self.lib.vv_transformer_cached_ws_bytes(self.ctx, int(B), int(N), _host_lens(B, seq_len_host), int(bool(report)), C.byref(nb)))
         return int(nb.value)
 
@@ -685,10 +685,29 @@ class HipSynth(PcmStage):
                 self._check(self.lib.vv_transformer_steps(self.ctx, B, N, pre["seq_len"].data_ptr(), x.data_ptr(), *tail))
         return x
 
+    class _SizedAsTheCall:
+        """A size query sees the context as the next steps call will: under the step report (N20) the library keeps one more slope and the
+        report's partial sums, and it knows of the report only while a buffer is set (_ReportScope sets one around every call).  Without
+        this the bytes a query names were too few for a call under set_ode_report(True)."""
+        def __init__(self, eng, B):
+            self.eng, self.buf = eng, None
+            if eng.ode_report:
+                self.buf = torch.zeros((eng.n_steps, int(B), 2), dtype=torch.float64, device=eng.device)
+
+        def __enter__(self):
+            if self.buf is not None:
+                self.eng._check(self.eng.lib.vv_set_ode_report(self.eng.ctx, self.buf.data_ptr(), self.eng.n_steps, int(self.buf.shape[1])))
+            return self
+
+        def __exit__(self, et, ev, tb):
+            if self.buf is not None:
+                self.eng.lib.vv_set_ode_report(self.eng.ctx, None, 0, 0)
+            return False
+
     def _steps_ws_bytes(self, entry, B: int, N: int, host) -> int:
         """One of the three size queries of the transformer stage (``entry``) for the B host lengths ``host`` (a ctypes int32 array)."""
         nb = C.c_uint64()
-        with self._lock:
+        with self._lock, self._SizedAsTheCall(self, B):
             self._check(entry(self.ctx, int(B), int(N), host, C.byref(nb)))
         return int(nb.value)
 
@@ -700,7 +719,7 @@ class HipSynth(PcmStage):
         """Bytes of a caller-owned workspace for a call that reuses guidance differences (vv_transformer_reuse_ws_bytes; the same for every
         mask): the guided figure plus one difference buffer per lane, plus the drift report's partial sums when ``report``."""
         nb = C.c_uint64()
-        with self._lock:
+        with self._lock, self._SizedAsTheCall(self, B):
             self._check(self.lib.vv_transformer_reuse_ws_bytes(self.ctx, int(B), int(N), _host_lens(B, seq_len_host), int(bool(report)), C.byref(nb)))
         return int(nb.value)
 
