@@ -327,6 +327,30 @@ typedef struct vv_block_cache_args {
 VV_API int vv_transformer_steps_cached(vv_ctx* ctx, const vv_steps_args* args, const vv_block_cache_args* cache, void* stream);
 VV_API int vv_transformer_cached_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, int with_report, uint64_t* bytes);
 
+/* N24 CFG-Zero* and guidance rescale: vv_transformer_steps_guided where the two predictions of a guided item are
+ * combined as k = f_b (p_c + (p_c - s_b p_u) g_b).  Over the item's valid frames and the n_mel columns of the fp32 predictions:
+ * S_cu = sum p_c p_u, S_uu = sum p_u^2, S_cc = sum p_c^2, S_c = sum p_c, S_u = sum p_u, n = frames * n_mel.  s_b = S_cu / S_uu where
+ * star[b] != 0 and S_uu != 0, else 1 (Fan et al. 2025: the unconditional velocity projected onto the conditional one), rounded to fp32
+ * once.  With a = 1 + g_b, c = -g_b s_b, V_xy = S_xy / n - (S_x / n)(S_y / n) and var_k = a^2 V_cc + 2 a c V_cu + c^2 V_uu:
+ * rho = sqrt(V_cc / var_k) (1 unless both are > 0), f_b = phi_b rho + (1 - phi_b) with phi_b = rescale[b], exactly 1 where that is 0,
+ * rounded to fp32 once (Lin et al. 2024, applied to the guided VELOCITY, not to an x_0 prediction).  star / rescale: device [B] fp32,
+ * NULL = off for every item; an item with s = 1 and f = 1 gets the bits of the plain rule, an item that is not guided at an evaluation
+ * has k = p_c and nothing is reduced for it.  report (optional): a caller-owned DEVICE array [evaluations of the plan in force][B][2] fp32
+ * that receives the (s, f) used at every evaluation of the call, {1, 1} where the item is not guided; rows of evaluations outside the call
+ * are not written.  The sums are float64 (a product and an add each, never fused), deterministic and independent of the item's place in
+ * the batch (no atomics; vv_cfg_norm_coef); every evaluation adds two small launches to the stage kernel's.  norm NULL: the call IS
+ * vv_transformer_steps_guided.  guide_host NULL: every item guided everywhere.  A caller-owned ws holds vv_transformer_norm_ws_bytes bytes
+ * (the same figure whatever the mask).  -22 for what vv_transformer_steps_guided refuses and for a mask that holds a 2 (guidance reuse:
+ * the item has no p_u to measure); a refused call launches nothing and leaves the context usable; no readback, no synchronisation. */
+typedef struct vv_cfg_norm_args {
+    const float* star;       /* device [B], optional: != 0 = the optimised scale for item b */
+    const float* rescale;    /* device [B], optional: phi of item b */
+    float* report;           /* device [evaluations][B][2], optional */
+} vv_cfg_norm_args;
+VV_API int vv_transformer_steps_norm(vv_ctx* ctx, const vv_steps_args* args, const uint8_t* guide_host, int ld_guide, const vv_cfg_norm_args* norm,
+                                     void* stream);
+VV_API int vv_transformer_norm_ws_bytes(vv_ctx* ctx, int B, int N, const int32_t* seq_len_host, uint64_t* bytes);
+
 /* The same decode stage with every intermediate carved from a CALLER-OWNED device block `ws` (256-byte aligned,
  * >= vv_decode_ws_bytes bytes) instead of the context arena.  The context arena may be reallocated by any later call
  * that needs more bytes (vv_ws_generation counts those moves); a launch sequence captured into a hipGraph
@@ -651,6 +675,25 @@ typedef struct vv_cfg_drift_args {
     double* partials; double* report;
 } vv_cfg_drift_args;
 VV_API int vv_cfg_drift_reduce(vv_ctx* ctx, const vv_cfg_drift_args* args, void* stream);
+/* N24 single-kernel entries (unit parity).  vv_cfg_norm_coef: the Gram sums and the coefficients of one evaluation.  Item b owns the packed
+ * conditional rows [row_start[b], + len[b]) of pred (as vv_apg_coef); p_u of row r is pred row Rc + r, or u_row[r] when u_row is given
+ * (< 0: not guided); columns >= n_mel of a row are never read.  partials [B][n_tiles][5] float64 = {S_cu, S_uu, S_cc, S_c, S_u} per tile
+ * (scratch: the entries of an item's tiles are written, the rest untouched), coef [B][2] fp32 = {s, f}; {1, 1} for an item without rows
+ * or not guided.  g_item / star / rescale: device [B], optional (g, off, off).  report: optional second copy of coef.
+ * vv_ode_stage_norm: vv_ode_stage_guided where row r's slope is coef[item][1] * (p_c + (p_c - coef[item][0] * p_u) * g), item =
+ * row_src[r] / seq_n (or r / seq_n); u_row is required.  coef = {1, 1} everywhere is vv_ode_stage_guided bit for bit.  coef NULL: the
+ * call IS vv_ode_stage_guided. */
+typedef struct vv_cfg_norm_coef_args {
+    const float* pred; int32_t ldp, Rc, n_mel;
+    const int32_t* u_row;
+    int32_t B, n_tiles;
+    const int32_t* row_start; const int32_t* len;
+    float g;
+    const float* g_item; const float* star; const float* rescale;
+    double* partials; float* coef; float* report;
+} vv_cfg_norm_coef_args;
+VV_API int vv_cfg_norm_coef(vv_ctx* ctx, const vv_cfg_norm_coef_args* args, void* stream);
+VV_API int vv_ode_stage_norm(vv_ctx* ctx, const vv_ode_stage_args* args, const int32_t* u_row, const float* coef, void* stream);
 /* N23 single-kernel entries (unit parity).  vv_block_span: one launch of the span kernel on contiguous [R][D] planes.  X = (x + (float)d1)
  * + (float)d2 per element (fp32 adds in this order; d1 / d2 of delta_dtype, d2 NULL = one delta, d1 NULL = X is x); VV_SPAN_MARK: buf = X;
  * VV_SPAN_DIFF: buf = X - buf; VV_SPAN_APPLY: x = X + buf.  Nothing else is written.  -22 for R < 1, D < 4 or not a multiple of 4, a null

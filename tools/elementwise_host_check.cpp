@@ -37,12 +37,12 @@ template <typename T> static bool pack_guided(const Launch& L) {
                                            VV_I(9), VV_I(10), VV_I(11), VV_P(const int, 12), VV_P(const int, 13), VV_P(const int, 14)));
 }
 
-template <bool G, bool A, bool R> static bool stage(const Launch& L) {
+template <bool G, bool A, bool R, bool Nm = false> static bool stage(const Launch& L) {
     OdeStagePrev pv{};
     for (int j = 0; j < 3; ++j) { pv.k[j] = VV_P(const float, 9 + j); pv.c[j] = VV_F(12 + j); }
     std::conditional_t<R, OdeStageReuse, OdeStageNoReuse> ru{};
     if constexpr (R) { ru.d_buf = VV_P(float, 23); ru.load = flags_of(L, 24); ru.store = flags_of(L, 25); }
-    return VV_GO((ode_stage_kernel<G, A, R>(VV_P(float, 0), VV_P(const float, 1), VV_I(2), VV_I(3), VV_I(4), VV_F(5), VV_P(const float, 6), VV_I(7),
+    return VV_GO((ode_stage_kernel<G, A, R, Nm>(VV_P(float, 0), VV_P(const float, 1), VV_I(2), VV_I(3), VV_I(4), VV_F(5), VV_P(const float, 6), VV_I(7),
                                             VV_P(const int, 8), pv, VV_F(15), VV_P(float, 16), VV_P(float, 17), VV_P(const int, 18), VV_P(const float, 19),
                                             VV_P(const float, 20), VV_I(21), VV_F(22), ru)));
 }
@@ -88,6 +88,13 @@ static bool run(const Launch& L) {
     if (n == "ode_stage<apg>") return stage<false, true, false>(L);
     if (n == "ode_stage<apg_guided>") return stage<true, true, false>(L);
     if (n == "ode_stage<reuse>") return stage<true, false, true>(L);
+    if (n == "ode_stage<norm>") return stage<true, false, false, true>(L);
+    if (n == "cfg_gram_reduce")
+        return VV_GO(cfg_gram_reduce_kernel(VV_P(const float, 0), VV_I(1), VV_I(2), VV_I(3), VV_P(const int, 4), VV_P(const int, 5), VV_P(const int, 6), VV_I(7),
+                                            VV_P(double, 8)));
+    if (n == "cfg_norm_coef")
+        return VV_GO(cfg_norm_coef_kernel(VV_P(const double, 0), VV_I(1), VV_I(2), VV_I(3), VV_P(const int, 4), VV_P(const int, 5), VV_P(const int, 6), VV_F(7),
+                                          VV_P(const float, 8), VV_P(const float, 9), VV_P(const float, 10), VV_P(float, 11), VV_P(float, 12)));
     if (n == "apg_reduce")
         return VV_GO(apg_reduce_kernel(VV_P(const float, 0), VV_I(1), VV_I(2), VV_I(3), VV_P(const int, 4), VV_P(const float, 5), VV_P(const int, 6),
                                        VV_P(const int, 7), VV_P(const int, 8), VV_I(9), VV_D(10), VV_P(double, 11)));

@@ -3,8 +3,8 @@
 
 Builds tools/elementwise_host_check.cpp (the kernel source on tools/hip_host_shim.h, exact-size heap buffers) twice, with
 -fsanitize=address,undefined and with -fsanitize=thread.  Cases, references and bounds are those of tests/gpu_util.py (ln_*, gn_*, te_*,
-dw_*, grn_*), tests/step_util.py (stage_*, apg_*, pack_*, table_cases, len_*, rope_*), tests/cfg_reuse_util.py, tests/block_cache_util.py and
-tests/multistep_util.py; nothing is fitted here.  Exact kernels (pack, tables, lengths, rope, text_embed, build_cat, ode_diff_*,
+dw_*, grn_*), tests/step_util.py (stage_*, apg_*, pack_*, table_cases, len_*, rope_*), tests/cfg_reuse_util.py, tests/block_cache_util.py,
+tests/cfg_norm_util.py and tests/multistep_util.py; nothing is fitted here.  Exact kernels (pack, tables, lengths, rope, text_embed, build_cat, ode_diff_*,
 cfg_drift_*, block_span, block_drift_*) are compared bit for bit; the others under the bound function of their device test (ln_bound, gn_bound, dw_bound, the
 GRN counts, the stage counts, the APG chain bound).  rsqrtf and the Mish branch of act_apply run on the shim's stand-ins (1 / sqrtf;
 exp2f and a division): those results speak for the indexing and the barriers of their paths, not for the device's functions.
@@ -17,7 +17,7 @@ Grids, restated from the launchers of csrc/vv_elementwise.hip (which stay outsid
   ln_mod              vvk_ln_mod: `grid = (a->R + 3) / 4`, 256 threads; tail_row0 = R and tp = 0 without a tail
   groupnorm           vvk_groupnorm: `dim3 grid(G, B)`, 256
   grn                 vvk_grn: `dim3 g1(C / 64, n_seq)`, `rpb = 16`, `dim3 g2((N + rpb - 1) / rpb, n_seq)`, LDS `C * sizeof(float)`
-  apg / diff / drift  `dim3(a->n_tiles, a->B)`, 256; the finishing kernels `a->B` workgroups of 64
+  apg / diff / drift / cfg_gram  `dim3(a->n_tiles, a->B)`, 256; the finishing kernels (cfg_norm_coef among them) `a->B` workgroups of 64
   tables              `row_tables_kernel<<<B, 256>>>`, `guided_tables_kernel<<<B, 256>>>`
   lengths             `(B + 63) / 64` workgroups of 64
   rope                `(n * 32 + 255) / 256` and `(rows * 16 + 255) / 256`: the device's (no grid-stride loop)
@@ -746,6 +746,86 @@ def block_cache_cases(exe, work, reduced=False):
         yield H.check(label, bfinish_check(m, part, outs2[k][7], zero))
 
 
+# ---------------------------------------------------------------------------------------------------- CFG-Zero* / rescale (N24)
+def cfg_norm_cases(exe, work, reduced=False):
+    """The three N24 kernels: cfg_gram_reduce on cfg_norm_util's items of 1, 31, 32, 33, 97 and 0 rows (permuted places, one item
+    unguided, a tile of partials nobody owns, pad columns that end the block behind the last row), bit for bit against gram_mirror;
+    cfg_norm_coef on those partials under coef_exact's bound; ode_stage<norm> on the stage cases of the device test under its counted bound.
+    Reduced: one width of each and the stage cases that bring a new shape, row count, map or stage form."""
+    torch, gu, su = _mods()
+    from tests import cfg_norm_util as nu
+    bt, grams, stages = H.Batch(exe, work, NAME), [], []
+    nt = -(-max(nu.LENS) // nu.TILE) + 1
+    B = len(nu.LENS)
+    for M, ldp in (((100, 104),) if reduced else ((4, 4), (4, 8), (100, 100), (100, 104), (100, 128))):
+        o = nu.coef_ops(M, ldp)
+        pred = plane(npy(o["pred"][:, :M]), ldp, NANF)
+        h = dict(pred=pred, u_row=npy(o["u_row"]), row_start=np.array(o["start"], np.int32), len=np.array(o["lens"], np.int32))
+        k = bt.add("cfg_gram_reduce", (nt, B), 256, [pred, ldp, o["Rc"], M, h["u_row"], h["row_start"], h["len"], nt, H.filled((B, nt, 5), np.float64)])
+        grams.append((k, o, h, f"cfg_gram M {M} ldp {ldp}"))
+    cs = nu.stage_cases()
+    if reduced:
+        cs = cover([c for c in cs if c.n_mel in (4, 100)], lambda c: [("M", c.n_mel, c.ldp - c.n_mel in (0, 4) and c.ldp - c.n_mel), ("Rc", c.Rc), ("last", c.last),
+                                                                    ("u", c.u_map), ("item", c.per_item), ("stage", c.stage)])
+    for case in cs:
+        o = case.ops()
+        g = torch.Generator().manual_seed(case.seed)
+        coef = torch.stack([0.7 + 0.3 * torch.rand(case.B, generator=g), 0.5 + 0.4 * torch.rand(case.B, generator=g)], dim=1).contiguous()
+        Rc, M = case.Rc, case.n_mel
+        cf = [float(c) for c in case.coef]
+        kp = [npy(o.k_prev[j]) if j < case.stage and cf[j] != 0 else None for j in range(3)]
+        cc = [cf[j] if kp[j] is not None else 0.0 for j in range(3)]
+        args = [npy(o.x), pred_plane(o, M, case.ldp)[0], case.ldp, Rc, M, case.g, None if o.g_item is None else npy(o.g_item), case.N, npy(o.row_src),
+                kp[0], kp[1], kp[2], cc[0], cc[1], cc[2], cf[case.stage], H.filled((Rc, M), np.float32), None if case.last else H.filled((Rc, M), np.float32),
+                npy(o.u_row), npy(coef).reshape(-1), None, 0, 0.0]
+        stages.append((bt.add("ode_stage<norm>", grid2(Rc * M // 4), 256, args), case, o, coef))
+    outs = bt.run()
+    second = []
+    for k, o, h, label in grams:
+        part = outs[k][8]
+        pred2 = npy(o["pred"])
+        M = o["n_mel"]
+        ok = True
+        for b, n in enumerate(nu.LENS):
+            own = -(-n // nu.TILE)
+            rows = np.arange(o["start"][b], o["start"][b] + n)
+            ok = ok and H.still_filled(part[b, own:])
+            if n and nu.GUIDED[b]:
+                want, _ = nu.gram_mirror(pred2[rows, :M], pred2[h["u_row"][rows], :M])
+                ok = ok and same_bytes(part[b, :own], want)
+            elif n:
+                ok = ok and not part[b, :own].any()
+        yield H.check(label + " (partials equal the mirror)", bool(ok))
+        args = [part.copy(), nt, o["Rc"], M, h["u_row"], h["row_start"], h["len"], 9.0, np.array(nu.G_ITEM, np.float32), np.array(nu.STAR, np.float32),
+                np.array(nu.RESC, np.float32), H.filled((B, 2), np.float32), H.filled((B, 2), np.float32)]
+        second.append((bt.add("cfg_norm_coef", B, 64, args), o, h, label))
+    for k, case, o, coef in stages:
+        ref = nu.stage_ref(case, o, coef)
+        out = outs[k]
+        x = tor(out[0])
+        state = x[o.xr] if case.last else tor(out[17])
+        ek = gu.parity_err(tor(out[16]), ref["k"], ref["K"].clamp_min(1e-300))[0]
+        ea = gu.parity_err(state, ref["acc"], ref["mag"].clamp_min(1e-300))[0]
+        good = ek <= nu.NORM_SLOPE_C * gu.EPS24 and ea <= su.STATE_C * gu.EPS24
+        if not case.last:
+            good = good and su.same_bits(x, o.x)
+        yield H.check(f"{case.name} (slope err / bound {ek / (nu.NORM_SLOPE_C * gu.EPS24):.3f})", bool(good))
+    outs2 = bt.run()
+    for k, o, h, label in second:
+        coef, rep_ = outs2[k][11], outs2[k][12]
+        pred2 = npy(o["pred"])
+        M = o["n_mel"]
+        ok = same_bytes(coef, rep_)
+        for b, n in enumerate(nu.LENS):
+            rows = np.arange(o["start"][b], o["start"][b] + n)
+            if not n or not nu.GUIDED[b]:
+                ok = ok and coef[b].tolist() == [1.0, 1.0]
+                continue
+            s, f, bs, bf = nu.coef_exact(pred2[rows, :M], pred2[h["u_row"][rows], :M], nu.G_ITEM[b], nu.STAR[b] != 0, nu.RESC[b])
+            ok = ok and abs(float(coef[b, 0]) - float(s)) <= bs and abs(float(coef[b, 1]) - float(f)) <= bf
+        yield H.check(label.replace("cfg_gram", "cfg_norm_coef") + " (inside the derived bound)", bool(ok))
+
+
 # ---------------------------------------------------------------------------------------------------- the lists
 def cases(exe, work, reduced=False):
     """Runs every case through exe; yields (label, equal to the mirror / inside the bound of the device test)."""
@@ -830,6 +910,7 @@ def cases(exe, work, reduced=False):
     for k, m, part, label in fourth:
         yield H.check(label, finish_check(m, part, outs2[k][5])[0])
     yield from block_cache_cases(exe, work, reduced)
+    yield from cfg_norm_cases(exe, work, reduced)
 
 
 if __name__ == "__main__":

@@ -3,7 +3,11 @@
 shape (B = 32, 256 tokens, N = 1600 frames per item) and of B = 1 under four configurations -- (a) unmasked, the path without a
 mask; (b) an all-ones mask (the same rows through the masked path); (c) an all-zero mask (no unconditional row anywhere); (d) the
 interval (0.25, 0.75); and guidance reuse -- (e) reuse k = 2, 3, 4 over the whole grid, the unconditional branch at every
-k-th evaluation; (f) k = 2 inside the interval (0.25, 0.75).  (a) is run first AND last: the two bracket what the run itself drifts by.  Per configuration: ms per batch,
+k-th evaluation; (f) k = 2 inside the interval (0.25, 0.75); and CFG-Zero* / guidance rescale / zero-init
+ -- (g) the optimised scale, the rescale at phi = 0.7 and both for every item (two small launches per evaluation in front of
+the combine: the row also gives the time over the all-ones mask of the same run, the plain guided call, and the bytes the two launches
+read per evaluation, 2 Rc n_mel 4); (h) cfg_zero_init = 1 and 2 (the plan without its first K steps: the row also gives the expected
+(n - 1 - K) / (n - 1) and the deviation from it), closed by one more unmasked run.  (a) is run first AND last: the two bracket what the run itself drifts by.  Per configuration: ms per batch,
 ms per evaluation, the rows launched over the unmasked rows, and the time over the first (a).  Host clock around calls that end in
 a device synchronise; one warm-up call, then median (and min / max) of --reps.
 
@@ -28,7 +32,11 @@ from vietvoice_tts_amd.runtime import HipSynth  # noqa: E402
 
 SEED, REF_S, TOK, FRAMES = 9527, 6.0, 256, 1600            # the headline unit of bench.py: 6 s reference clip, 256 tokens, N = 1600 frames
 INTERVAL = (0.25, 0.75)
-CONFIGS = ["unmasked", "ones", "zeros", "interval", "reuse2", "reuse3", "reuse4", "interval_reuse2", "unmasked"]
+CONFIGS = ["unmasked", "ones", "zeros", "interval", "reuse2", "reuse3", "reuse4", "interval_reuse2", "unmasked",
+           "zero_star", "rescale", "zero_star_rescale", "zero_init1", "zero_init2", "unmasked"]
+RESCALE = 0.7
+NORMS = {"zero_star": (True, None), "rescale": (False, RESCALE), "zero_star_rescale": (True, RESCALE)}      # N24: (cfg_zero_star, cfg_rescale) of every item
+ZERO_INIT = {"zero_init1": 1, "zero_init2": 2}
 
 
 def timed(fn, reps):
@@ -49,7 +57,7 @@ def main():
     ap.add_argument("--batches", default="32,1")
     ap.add_argument("--frames", type=int, default=FRAMES)
     ap.add_argument("--nfe", type=int, default=32)
-    ap.add_argument("--configs", default="", help="unmasked,ones,zeros,interval,reuse2,reuse3,reuse4,interval_reuse2 in any order instead of the default list (start with unmasked)")
+    ap.add_argument("--configs", default="", help="unmasked,ones,zeros,interval,reuse2,reuse3,reuse4,interval_reuse2,zero_star,rescale,zero_star_rescale,zero_init1,zero_init2 in any order instead of the default list (start with unmasked)")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "guidance_bench times the GPU path; there is nothing to measure without a HIP device"
@@ -73,13 +81,17 @@ def main():
                  "interval": eng.guidance_mask(INTERVAL, [None] * B), "reuse2": eng.guidance_mask(None, [None] * B, 2),
                  "reuse3": eng.guidance_mask(None, [None] * B, 3), "reuse4": eng.guidance_mask(None, [None] * B, 4),
                  "interval_reuse2": eng.guidance_mask(INTERVAL, [None] * B, 2)}
-        rows, base = [], None
+        rows, base, ones_ms = [], None, None
+        full_evals = eng.n_evals
         for name in configs:
-            guide = masks[name]
+            guide = masks.get(name)
+            norm = eng.cfg_norm_tensors([NORMS[name][0]] * B, [NORMS[name][1]] * B) if name in NORMS else None
+            if name in ZERO_INIT:                       # N24 zero-init: the plan without its first K steps (no mask: the unmasked path)
+                eng.set_nfe(a.nfe, "euler", ZERO_INIT[name])
 
             def run():
                 x.copy_(noise)
-                eng.transformer_steps(x, pre, 0, eng.n_steps, guide=guide)
+                eng.transformer_steps(x, pre, 0, eng.n_steps, guide=guide, cfg_norm=norm)
             ts = timed(run, a.reps)
             med = float(np.median(ts))
             guided = eng.n_evals if guide is None else int((guide[:, 0] == 1).sum())      # evaluations with unconditional rows (a 2 reuses: none)
@@ -91,6 +103,17 @@ def main():
             if base is None:
                 base = med
             row["over_unmasked"] = round(med / base, 4)
+            if name == "ones":
+                ones_ms = med
+            if name in NORMS:                           # N24: against the plain guided call of the same run; what the two launches read
+                row["over_guided"] = None if ones_ms is None else round(med / ones_ms, 4)
+                row["norm_read_bytes_per_eval"] = 2 * B * N * spec.n_mel * 4
+                row["norm_extra_ms_per_eval"] = None if ones_ms is None else round((med - ones_ms) / eng.n_evals, 4)
+            if name in ZERO_INIT:
+                want = eng.n_evals / full_evals
+                row["zero_init"], row["expected_over_unmasked"] = ZERO_INIT[name], round(want, 4)
+                row["deviation"] = round(med / base - want, 4)
+                eng.set_nfe(a.nfe, "euler")
             rows.append(row)
             print(f"B={B} {name}: {row['ms']} ms, {row['ms_per_eval']} ms per evaluation, {row['over_unmasked']} of unmasked", file=sys.stderr, flush=True)
         res[f"b{B}"] = rows

@@ -87,7 +87,7 @@ class BatchingFrontend:
                cfg_interval: Optional[Tuple[float, float]] = None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None,
                loudness: Optional[float] = None, limiter: Optional[str] = None, pitch: Optional[float] = None, tempo: Optional[float] = None,
                formants: Optional[str] = None, denoise: Optional[float] = None, cfg_reuse: Optional[int] = None, watermark_payload: Optional[int] = None,
-               **voice) -> Future:
+               cfg_zero_star: Optional[bool] = None, cfg_rescale: Optional[float] = None, **voice) -> Future:
         """voice: gender / group / area / emotion / sample_iteration / reference_audio / reference_text.
         ``serial`` fixes the request's noise stream (default: arrival counter).  ``cfg_strength``: this request's guidance strength
         (None = the engine's), carried per item into the batch -- the audio does not depend on the strengths of its batch neighbours.
@@ -109,15 +109,22 @@ class BatchingFrontend:
         ``output_watermark_payload``), embedded in this request alone under the engine's ``output_watermark_key``; on an engine without a
         key the request fails with a ValueError.
         On an engine with ``block_cache`` every batch caches blocks; a request that brings a ``cfg_interval``, a ``cfg_reuse``
-        above 1 or projected guidance fails with a ValueError."""
+        above 1 or projected guidance fails with a ValueError.
+        ``cfg_zero_star`` / ``cfg_rescale``: this request's CFG-Zero* optimised scale (True / False) and guidance rescale phi, 0 < phi <= 1
+        (None = the engine's ``cfg_zero_star`` / ``cfg_rescale``), per item beside the strength and the interval in one ragged
+        batch.  Together with projected guidance, with a ``cfg_reuse`` above 1 or on an engine with ``block_cache`` the request fails with a
+        ValueError (zero-init, ``cfg_zero_init``, is the engine's alone, as ``ode_method`` is)."""
         fut: Future = Future()
         try:
             options = RequestOptions.checked(cfg_strength=cfg_strength, cfg_interval=cfg_interval, apg_eta=apg_eta, apg_norm=apg_norm,
                                              loudness=loudness, limiter=limiter, pitch=pitch, tempo=tempo, formants=formants, denoise=denoise,
-                                             cfg_reuse=cfg_reuse, watermark_payload=watermark_payload)
+                                             cfg_reuse=cfg_reuse, watermark_payload=watermark_payload, cfg_zero_star=cfg_zero_star,
+                                             cfg_rescale=cfg_rescale)
             config = getattr(self.engine, "config", None)
             full = options if config is None else options.resolved(config)
-            from .model_spec import check_apg
+            from .model_spec import check_apg, check_cfg_norm_combination
+            check_cfg_norm_combination(full.cfg_zero_star, full.cfg_rescale, full.apg_eta, full.apg_norm, full.cfg_reuse,
+                                       getattr(config, "block_cache", None))
             if (full.cfg_reuse or 1) > 1 and check_apg(full.apg_eta, full.apg_norm) is not None:
                 raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
             if getattr(config, "block_cache", None) is not None and (full.cfg_interval is not None or (full.cfg_reuse or 1) > 1

@@ -49,7 +49,7 @@ class HipSession:
 
     def __init__(self, engine, kind: str, noise_gen, fuse_nfe: int = 1, cfg_strength: Optional[float] = None, cfg_interval=None,
                  noise_keys=None, apg_eta: Optional[float] = None, apg_norm: Optional[float] = None, cfg_reuse: Optional[int] = None,
-                 block_cache=None, block_cache_interval=None):
+                 block_cache=None, block_cache_interval=None, cfg_zero_star: bool = False, cfg_rescale: Optional[float] = None):
         self.engine, self.kind, self.noise_gen, self.fuse_nfe = engine, kind, noise_gen, max(1, int(fuse_nfe))
         # N9 (ModelConfig.noise_source == "device"): a callable -> the next run's Philox key row {seed, stream}; the preprocess session
         # then fills the noise in HBM (vv_noise_fill) and returns it, as the reference's graph returns its own.  None = the host generator.
@@ -59,6 +59,7 @@ class HipSession:
         self.apg_eta, self.apg_norm = apg_eta, apg_norm      # both None = the plain combine (ModelConfig.apg_eta / apg_norm)
         self.cfg_reuse = cfg_reuse                # None or 1 = every guided evaluation computes both predictions (ModelConfig.cfg_reuse)
         self.block_cache, self.block_cache_interval = block_cache, block_cache_interval      # None = every block at every evaluation (ModelConfig.block_cache)
+        self.cfg_zero_star, self.cfg_rescale = cfg_zero_star, cfg_rescale      # False / None = the plain combine (ModelConfig.cfg_zero_star / cfg_rescale)
         self._in, self._out = SESSION_IO[kind]
 
     def get_inputs(self):
@@ -114,7 +115,8 @@ class HipSession:
             cfg = None if self.cfg_strength is None else torch.full((1,), float(self.cfg_strength), dtype=torch.float32, device=dev)
             guide = eng.guidance_mask(self.cfg_interval, [self.cfg_strength], self.cfg_reuse)      # absolute evaluation rows: the split calls read one table
             apg = eng.apg_tensors([self.apg_eta], [self.apg_norm])                 # N11: stateless between the split calls (no momentum)
-            bc = dict(block_cache=self.block_cache, block_cache_interval=self.block_cache_interval)
+            bc = dict(block_cache=self.block_cache, block_cache_interval=self.block_cache_interval,
+                      cfg_norm=eng.cfg_norm_tensors([self.cfg_zero_star], [self.cfg_rescale]))      # N24: stateless between the split calls
             if self.block_cache is not None:                    # N23: no mask on that entry; a strength of 0 travels as the strength it is
                 guide = None
             if same:
@@ -210,12 +212,13 @@ class ModelSessionManager:
                 from ..runtime import HipSynth
                 self.engine = HipSynth(spec, weights, device=self.config.device, acoustic_dtype=self.config.acoustic_dtype,
                                        nfe_step=self.config.nfe_step, ode_method=self.config.ode_method,
-                                       ode_report=self.config.ode_report)
+                                       ode_report=self.config.ode_report, cfg_zero_init=self.config.cfg_zero_init)
                 on_device = self._session_key if self.config.noise_source == "device" else None
                 made = {k: HipSession(self.engine, k, self.noise_gen, self.config.fuse_nfe, self.config.cfg_strength, self.config.cfg_interval,
                                       noise_keys=on_device if k == "preprocess" else None, apg_eta=self.config.apg_eta,
                                       apg_norm=self.config.apg_norm, cfg_reuse=self.config.cfg_reuse, block_cache=self.config.block_cache,
-                                      block_cache_interval=self.config.block_cache_interval) for k in SESSION_IO}
+                                      block_cache_interval=self.config.block_cache_interval, cfg_zero_star=self.config.cfg_zero_star,
+                                      cfg_rescale=self.config.cfg_rescale) for k in SESSION_IO}
             for name in ("preprocess", "transformer", "decode"):
                 sess = made[name]
                 self.sessions[name] = sess

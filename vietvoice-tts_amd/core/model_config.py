@@ -88,6 +88,14 @@ class ModelConfig:
     block_cache_report: bool = False        # N23, needs block_cache: per evaluation, item and CFG branch the sums (|C - C_stored|^2, |C|^2) of the span's
                                             # contribution at the full evaluations, reduced on the device -- how far it moved while it was reused
                                             # (HipSynth.last_block_cache_report, TTSEngine.last_block_cache_report).  On, every full evaluation stores
+    cfg_zero_star: bool = False             # CFG-Zero* (Fan et al. 2025): a guided item's unconditional velocity is scaled by the per-item
+                                            # s* = <p_c, p_u> / <p_u, p_u> before the combine.  Not combined with apg_eta / apg_norm, cfg_reuse > 1 or block_cache
+    cfg_rescale: Optional[float] = None     # guidance rescale phi, 0 < phi <= 1 (N24; Lin et al. 2024, on the guided velocity): the guided slope is scaled
+                                            # by phi std(p_c) / std(k) + 1 - phi per item.  None = off.  Same refusals as cfg_zero_star
+    cfg_zero_init: int = 0                  # zero-init (N24): the first K ODE steps are skipped -- the state stays the start noise up to t_K and their
+                                            # DiT evaluations are not run.  0 <= K <= nfe_step - 2; engine-wide, as ode_method
+    cfg_norm_report: bool = False           # N24, needs cfg_zero_star or cfg_rescale: the (s, f) every evaluation used, per item
+                                            # (HipSynth.last_cfg_norm_report, TTSEngine.last_cfg_norm_report).  Off = nothing is allocated for it
     noise_source: str = "host"              # where the flow ODE's start noise is drawn: "host" = torch.randn from seeded generators, uploaded;
                                             # "device" = Philox4x32-10 in HBM keyed by (random_seed, call serial, chunk) -- model_spec.noise_keys
     output_stage: str = "host"              # where the chunks of a text are joined: "host" = numpy after one copy per chunk group (the reference's
@@ -203,6 +211,16 @@ class ModelConfig:
                                  "unconditional rows between evaluations, which the stored rows do not follow)")
         elif self.block_cache_report or self.block_cache_interval is not None:
             raise ValueError("block_cache_report and block_cache_interval need block_cache")
+        from ..model_spec import check_cfg_norm, check_cfg_norm_combination, check_cfg_zero_init
+        if not isinstance(self.cfg_zero_star, bool):
+            raise ValueError("cfg_zero_star must be a bool")
+        check_cfg_norm(self.cfg_zero_star, self.cfg_rescale)             # phi a finite number in (0, 1], or None
+        self.cfg_rescale = None if self.cfg_rescale is None else float(self.cfg_rescale)
+        check_cfg_norm_combination(self.cfg_zero_star, self.cfg_rescale, self.apg_eta, self.apg_norm, self.cfg_reuse, self.block_cache)
+        self.cfg_zero_init = check_cfg_zero_init(self.cfg_zero_init, self.nfe_step)
+        self.cfg_norm_report = bool(self.cfg_norm_report)
+        if self.cfg_norm_report and check_cfg_norm(self.cfg_zero_star, self.cfg_rescale) is None:
+            raise ValueError("cfg_norm_report needs cfg_zero_star or cfg_rescale: it reports their coefficients")
         self.validate_paths()
 
     @property

@@ -59,6 +59,7 @@ class TTSEngine:
         self._last_plan = []
         self.last_cfg_reuse_report = []          # N21 (config.cfg_reuse_report): the drift reports of the last synthesis, float64 [n_evals, B, 2] per GPU batch
         self.last_block_cache_report = []        # N23 (config.block_cache_report): the reports of the last synthesis, float64 [n_evals, B, 2, 2] per GPU batch
+        self.last_cfg_norm_report = []           # N24 (config.cfg_norm_report): the (s, f) of the last synthesis, float32 [n_evals, B, 2] per GPU batch
         self.last_ode_report = []                # N20 (config.ode_report): the step reports of the last synthesis, float64 [n_steps, B, 2] per GPU batch
 
     def cleanup(self) -> None:
@@ -251,8 +252,9 @@ class TTSEngine:
         """The solver and its step report as the config has them now (the report is off while the plan changes under it)."""
         eng = self.model_session_manager.engine
         eng.set_ode_report(False)
-        eng.set_nfe(self.config.nfe_step, self.config.ode_method)
+        eng.set_nfe(self.config.nfe_step, self.config.ode_method, self.config.cfg_zero_init)
         eng.set_ode_report(self.config.ode_report)
+        eng.set_cfg_norm_report(self.config.cfg_norm_report)
         eng.set_cfg_reuse_report(self.config.cfg_reuse_report)
         eng.set_block_cache_report(self.config.block_cache_report)
 
@@ -267,7 +269,8 @@ class TTSEngine:
         options: optional RequestOptions per item (None, a None entry or a None field = the engine's value), read for the acoustic stage:
         ``cfg_strength`` (None in the config as well leaves it to the model); ``cfg_interval`` (lo, hi): an item is guided at the evaluations
         inside its interval, and never when its strength is 0: elsewhere its unconditional branch is not computed; ``apg_eta`` /
-        ``apg_norm``: items with neither keep the plain combine, in the same batch.
+        ``apg_norm``: items with neither keep the plain combine, in the same batch; ``cfg_zero_star`` / ``cfg_rescale`` (N24): the call goes to
+        vv_transformer_steps_norm only when some item of it has either, and items with neither keep the plain combine there.
         device_out (N10): nothing is copied to the host; returns (int16 device tensor, [(offset, samples) per item]) -- the planes of the
         chunk groups back to back and each item's span in them, the lengths from the host's own frame counts (no readback)."""
         import torch
@@ -278,12 +281,17 @@ class TTSEngine:
         self.last_ode_report = []
         self.last_cfg_reuse_report = []
         self.last_block_cache_report = []
+        self.last_cfg_norm_report = []
         hop = self.config.hop_length
         opts = self._resolved(options, len(inputs_list))
+        star_all, resc_all = ([getattr(o, name) for o in opts] for name in ("cfg_zero_star", "cfg_rescale"))
         g_all, iv_all, eta_all, norm_all, reuse_all = ([getattr(o, name) for o in opts]
                                                        for name in ("cfg_strength", "cfg_interval", "apg_eta", "apg_norm", "cfg_reuse"))
-        from ..model_spec import check_apg
+        from ..model_spec import check_apg, check_cfg_norm, check_cfg_norm_combination
         apg_on = [check_apg(e, r) is not None for e, r in zip(eta_all, norm_all)]
+        norm_on = [check_cfg_norm(z, r) is not None for z, r in zip(star_all, resc_all)]
+        for j in range(len(opts)):                           # N24: never with APG, reuse or the block-cache entry, each in its own words
+            check_cfg_norm_combination(star_all[j], resc_all[j], eta_all[j], norm_all[j], reuse_all[j], self.config.block_cache)
         for k, on in zip(reuse_all, apg_on):
             if (k or 1) > 1 and on:
                 raise ValueError("cfg_reuse > 1 cannot be combined with apg_eta / apg_norm (projected guidance needs both predictions at every evaluation)")
@@ -324,6 +332,10 @@ class TTSEngine:
         groups = [part for idx in groups
                   for part in (([[i for i in idx if (reuse_all[i] or 1) > 1], [i for i in idx if not (reuse_all[i] or 1) > 1]]
                                 if any(apg_on[i] for i in idx) and any((reuse_all[i] or 1) > 1 for i in idx) else [idx])) if part]
+        # N24: a call with CFG-Zero* / rescale takes neither APG nor reuse: such items of one group run as a call of their own
+        groups = [part for idx in groups
+                  for part in (([[i for i in idx if norm_on[i]], [i for i in idx if not norm_on[i]]]
+                                if any(norm_on[i] for i in idx) and any(apg_on[i] or (reuse_all[i] or 1) > 1 for i in idx) else [idx])) if part]
         for idx in groups:
             group = [inputs_list[i] for i in idx]
             B = len(group)
@@ -368,12 +380,13 @@ class TTSEngine:
                 cfg = torch.tensor([float(spec.cfg_strength) if g_all[j] is None else g_all[j] for j in idx], dtype=torch.float32).to(dev)
             guide = eng.guidance_mask([iv_all[j] for j in idx], [g_all[j] for j in idx], [reuse_all[j] for j in idx])     # None: every item guided everywhere
             apg = eng.apg_tensors([eta_all[j] for j in idx], [norm_all[j] for j in idx])      # None: the plain combine for every item
+            cfg_norm = eng.cfg_norm_tensors([star_all[j] for j in idx], [resc_all[j] for j in idx])      # None: no item of the call has either
             if self.config.block_cache is not None:
                 guide = None
             if self.config.use_hip_graph:
                 pre = eng.preprocess(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N, seq_len_host=seq, audio_len_host=lens_a)
                 x = noise.to(dev) if keys is None else eng.noise(keys, pre["seq_len"], N)
-                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide, apg=apg, **bc)
+                eng.transformer_steps(x, pre, 0, eng.n_steps, cfg=cfg, guide=guide, apg=apg, cfg_norm=cfg_norm, **bc)
                 if self._decode_graphs is None:
                     self._decode_graphs = DecodeGraphCache(eng, self.config.decode_graph_cache_entries, self.config.decode_graph_cache_bytes)
                 pcm, pcm_len = self._decode_graphs.get(B, N, t_gen)(x, pre["ref_signal_len"], pre["seq_len"])
@@ -381,7 +394,9 @@ class TTSEngine:
                 _x, pcm, pcm_len, _pre = eng.synthesize_batch(audio, t32(lens_a), t32(ids), t32(lens_t), t32(seq), N,
                                                               None if noise is None else noise.to(dev), t_gen,
                                                               gen_frames=[int(v) for v in (seq - ref_frames)], seq_len_host=seq,
-                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg, **bc)
+                                                              audio_len_host=lens_a, cfg=cfg, guide=guide, noise_keys=keys, apg=apg, cfg_norm=cfg_norm, **bc)
+            if self.config.cfg_norm_report and cfg_norm is not None:
+                self.last_cfg_norm_report.append(eng.last_cfg_norm_report())
             if self.config.ode_report:
                 self.last_ode_report.append(eng.last_ode_report())
             if self.config.cfg_reuse_report:
@@ -562,7 +577,9 @@ class TTSEngine:
                                                None if noise is None else noise.unsqueeze(0).to(dev), cfg=g_item,
                                                guide=None if cfg.block_cache is not None else eng.guidance_mask(cfg.cfg_interval, [cfg.cfg_strength], cfg.cfg_reuse),
                                                noise_keys=keys, apg=eng.apg_tensors([cfg.apg_eta], [cfg.apg_norm]), block_cache=cfg.block_cache,
-                                               block_cache_interval=cfg.block_cache_interval)
+                                               block_cache_interval=cfg.block_cache_interval,
+                                               cfg_norm=eng.cfg_norm_tensors([cfg.cfg_zero_star], [cfg.cfg_rescale]))
+                self.last_cfg_norm_report = [eng.last_cfg_norm_report()] if cfg.cfg_norm_report else []
                 self.last_ode_report = [eng.last_ode_report()] if cfg.ode_report else []
                 self.last_cfg_reuse_report = [eng.last_cfg_reuse_report()] if cfg.cfg_reuse_report else []
                 self.last_block_cache_report = [eng.last_block_cache_report()] if cfg.block_cache_report else []

@@ -1219,6 +1219,9 @@ struct Lane {
     // alternate); the report's partial sums [2B][n_tiles][2]
     float* bc_buf[2] = {};
     double* bc_part = nullptr;
+    // N24 (a call with CFG-Zero* / rescale): the Gram sums [B][n_tiles][5] and the coefficients [B][2] of the evaluation in hand
+    double* cn_part = nullptr;
+    float* cn_coef = nullptr;
 };
 // N20: slots of the slope ring.  q - 1 without a report: the fresh slope takes the slot of the oldest one the step reads.  With a report
 // one more (two at the least), so that f_{n-1} outlives the stage launch of step n.
@@ -1240,7 +1243,8 @@ struct GuideState {
 // APG's on top of those (with or without a mask).  A call with a mask or with APG implies its form.
 // N21: WS_REUSE / WS_REUSE_REPORT = the guided form plus a D buffer per lane, and the drift report's partial sums.
 // N23: WS_CACHED / WS_CACHED_REPORT = the plain form plus a plane per lane, and with a report a second plane and the partial sums.
-enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG, WS_REUSE, WS_REUSE_REPORT, WS_CACHED, WS_CACHED_REPORT };
+// N24: WS_NORM = the guided form plus the Gram sums and the coefficients per lane.
+enum WsForm { WS_PLAIN, WS_GUIDED, WS_APG, WS_REUSE, WS_REUSE_REPORT, WS_CACHED, WS_CACHED_REPORT, WS_NORM };
 struct StepsCall {
     vv_steps_args a{};
     const uint8_t* guide = nullptr; int ld_guide = 0;
@@ -1259,6 +1263,11 @@ struct StepsCall {
     // (a mode other than 0, or a report) / the report is on
     const vv_block_cache_args* bc = nullptr;
     bool with_cache = false, with_cache_report = false;
+    // N24 (vv_transformer_steps_norm): the optimised scale and the rescale per item; a call without a mask runs on one of ones (every item
+    // guided everywhere: the guided form's tables give the stage kernel its u_row)
+    const vv_cfg_norm_args* norm = nullptr;
+    bool with_norm = false;
+    std::vector<uint8_t> all_guided;
 };
 struct StepDims { int D, FF, M, CD, es, KP, MP; };
 
@@ -1308,7 +1317,8 @@ LanePlan lane_plan(const vv_ctx* c, const StepDims& d, const std::vector<int>& h
 
 // workspace of one lane (its B, Rc, R, n_tab and tail plan are set): buffers that only an option uses (csq_rows / csk_rows) and the
 // zero-length tails are taken all the same, so the bytes depend on the shapes, the tail plan and the ODE plan alone
-void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg, bool reuse, bool drift, bool cache, bool cache_report) {
+void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, bool guided, bool apg, bool reuse, bool drift, bool cache, bool cache_report,
+               bool norm) {
     const size_t R = L.R, es = d.es, D = d.D, FF = d.FF, M = d.M, KP = d.KP, MP = d.MP;
     L.xcat = a.take<char>(es * R * KP);
     L.h = a.take<char>(es * R * D); L.h2 = a.take<char>(es * R * D); L.h3 = a.take<char>(es * R * D);
@@ -1344,6 +1354,10 @@ void lane_bufs(Arena& a, Lane& L, const vv_ctx* c, const StepDims& d, int N, boo
     if (cache_report) {
         L.bc_buf[1] = a.take<float>(R * D);
         L.bc_part = a.take<double>(2 * (size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 2);
+    }
+    if (norm) {                                    // N24: behind everything the other forms take, so their offsets stay as they are
+        L.cn_part = a.take<double>((size_t)L.B * ((N + VV_APG_TILE - 1) / VV_APG_TILE) * 5);
+        L.cn_coef = a.take<float>(2 * (size_t)L.B);
     }
 }
 
@@ -1561,8 +1575,19 @@ struct StepsRun : StepDims {
                 { Prof p2(c, VV_PROF_ELEMWISE, 0, 16.0 * L.B * r.n_tiles, L.st); KCHK(c, vvk_cfg_drift_reduce(&r, 2, L.st, &m__)); }
             }
         }
+        if (q.norm) {                                    // N24: the Gram sums of this evaluation, then the items' {s, f}
+            vv_cfg_norm_coef_args k{};
+            k.pred = L.pred; k.ldp = MP; k.Rc = (int)L.Rc; k.n_mel = M; k.u_row = u_row;
+            k.B = L.B; k.n_tiles = (N + VV_APG_TILE - 1) / VV_APG_TILE; k.row_start = L.row_start; k.len = L.kv_len;
+            k.g = a.g; k.g_item = a.g_item;
+            k.star = q.norm->star ? q.norm->star + L.b0 : nullptr; k.rescale = q.norm->rescale ? q.norm->rescale + L.b0 : nullptr;
+            k.partials = L.cn_part; k.coef = L.cn_coef;
+            k.report = q.norm->report ? q.norm->report + ((size_t)(s * ns + i) * q.a.B + L.b0) * 2 : nullptr;
+            { Prof p2(c, VV_PROF_ELEMWISE, 10.0 * L.Rc * M, 8.0 * L.Rc * M, L.st); KCHK(c, vvk_cfg_norm_coef(&k, 1, L.st, &m__)); }
+            { Prof p2(c, VV_PROF_ELEMWISE, 0, 40.0 * L.B * k.n_tiles, L.st); KCHK(c, vvk_cfg_norm_coef(&k, 2, L.st, &m__)); }
+        }
         Prof p(c, VV_PROF_ELEMWISE, 0, 4.0 * L.Rc * M * (4 + n_read + (a.k_out ? 1 : 0) + (apg ? 1 : 0) + (q.with_reuse ? 1 : 0)), L.st);
-        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__, c->ms_q ? 1 : 0, q.with_reuse ? &ra : nullptr));
+        KCHK(c, vvk_ode_stage(&a, u_row, apg ? &sa : nullptr, L.st, &m__, c->ms_q ? 1 : 0, q.with_reuse ? &ra : nullptr, q.norm ? L.cn_coef : nullptr));
         if (c->ms_q && c->ode_report) {                  // N20: the step report, from the slope just stored and the one before it
             vv_ode_diff_args r{};
             r.f = L.hist[s % ring]; r.f_prev = s ? L.hist[(s - 1) % ring] : nullptr; r.Rc = (int)L.Rc; r.n_mel = M;
@@ -1712,6 +1737,16 @@ int steps_schedule(const StepsRun& r, Lane* lanes, hipStream_t st) {
 static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
     if (!c) return -22;
     const vv_steps_args& a = q.a;
+    q.with_norm = q.norm != nullptr || q.ws_form == WS_NORM;
+    if (q.norm && !q.ws_only && a.B > 0) {                // N24: no 2 in the mask (a reused item has no p_u to measure); no mask = one of ones
+        const size_t E = (size_t)c->n_steps * c->ode_s;
+        if (q.guide && q.ld_guide >= a.B)
+            for (size_t e = 0; e < E; ++e)
+                for (int b = 0; b < a.B; ++b)
+                    if (q.guide[e * q.ld_guide + b] == 2)
+                        return c->fail(-22, "vv_transformer_steps_norm: mask value 2 (guidance reuse) at evaluation %d, item %d: the item has no unconditional prediction to measure", (int)e, b);
+        if (!q.guide) { q.all_guided.assign(E * a.B, 1); q.guide = q.all_guided.data(); q.ld_guide = a.B; }
+    }
     q.with_apg = q.apg != nullptr || q.ws_form == WS_APG; q.guided = q.guide != nullptr || (q.ws_form != WS_PLAIN && q.ws_form != WS_CACHED && q.ws_form != WS_CACHED_REPORT) || q.with_apg;
     q.rk = c->ode_s > 1 || c->ms_q > 0 || a.cfg_item != nullptr || q.guide != nullptr || q.apg != nullptr;   // false: exactly the Euler launches (vvk_cfg_euler) and workspace of the s = 1 plan
     const int B = a.B, N = a.N;
@@ -1803,7 +1838,7 @@ static int transformer_steps(vv_ctx* c, StepsCall q, void* stream) {
         return c->fail(-22, "vv_transformer_steps: %zu packed rows make a %zu-byte qkv buffer; kernels address it with 32-bit byte offsets "
                             "(< 2 GiB) -- synthesise fewer units per call", 2 * Rc_all, 2 * Rc_all * 3 * (size_t)d.D * d.es);
     LanePlan P = lane_plan(c, d, hlen, N);
-    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg, q.with_reuse, q.with_drift, q.with_cache, q.with_cache_report); };
+    auto bufs = [&](Arena& ar) { for (int li = 0; li < P.n_lanes; ++li) lane_bufs(ar, P.lanes[li], c, d, N, q.guided, q.with_apg, q.with_reuse, q.with_drift, q.with_cache, q.with_cache_report, q.with_norm); };
     if (q.ws_only) { *q.ws_only = (uint64_t)align_up(plan_bytes(bufs), 256); return 0; }
     if (int r = plan_ws(c, a.ws, (size_t)a.ws_bytes, bufs)) return r;
     for (int li = 0; li < P.n_lanes; ++li) {              // each lane's slice of the call's arrays
@@ -1894,6 +1929,22 @@ int vv_transformer_steps_apg(vv_ctx* c, const vv_steps_args* a, const uint8_t* g
 
 int vv_transformer_apg_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
     return steps_ws_query(c, "vv_transformer_apg_ws_bytes", WS_APG, B, N, seq_len_host, bytes);
+}
+
+// N24: CFG-Zero* and guidance rescale on top of vv_transformer_steps_guided (include/vvtts.h)
+int vv_transformer_steps_norm(vv_ctx* c, const vv_steps_args* a, const uint8_t* guide_host, int ld_guide, const vv_cfg_norm_args* norm, void* stream) {
+    if (!norm) return vv_transformer_steps_guided(c, a, guide_host, ld_guide, stream);
+    if (!c) return -22;
+    if (!a) return c->fail(-22, "vv_transformer_steps_norm: null arguments");
+    if (a->ws && !a->seq_len_host) return c->fail(-22, "vv_transformer_steps_norm: a workspace block needs the host lengths");
+    if (a->cfg_item && (uintptr_t)a->cfg_item % 4) return c->fail(-22, "vv_transformer_steps_norm: cfg_item must be a float array");
+    if (((uintptr_t)norm->star | (uintptr_t)norm->rescale) % 4 || (uintptr_t)norm->report % 8) return c->fail(-22, "vv_transformer_steps_norm: star and rescale must be float arrays, the report 8-byte aligned");
+    StepsCall q; q.a = *a; q.guide = guide_host; q.ld_guide = ld_guide; q.norm = norm;
+    return transformer_steps(c, q, stream);
+}
+
+int vv_transformer_norm_ws_bytes(vv_ctx* c, int B, int N, const int32_t* seq_len_host, uint64_t* bytes) {
+    return steps_ws_query(c, "vv_transformer_norm_ws_bytes", WS_NORM, B, N, seq_len_host, bytes);
 }
 
 // N21: a third mask value on top of vv_transformer_steps_guided (include/vvtts.h)
@@ -2340,6 +2391,18 @@ int vv_apg_coef(vv_ctx* c, const vv_apg_coef_args* a, void* st) {
          (uintptr_t)a->norm_rms) % 4)
         return c->fail(-22, "vv_apg_coef: the index and item arrays must be 4-byte aligned");
     SINGLE(c, vvk_apg_coef(a, 3, (hipStream_t)st, &m__));
+}
+int vv_cfg_norm_coef(vv_ctx* c, const vv_cfg_norm_coef_args* a, void* st) {
+    if (!c || !a) return c ? c->fail(-22, "vv_cfg_norm_coef: null arguments") : -22;
+    if (((uintptr_t)a->u_row | (uintptr_t)a->row_start | (uintptr_t)a->len | (uintptr_t)a->g_item | (uintptr_t)a->star | (uintptr_t)a->rescale) % 4)
+        return c->fail(-22, "vv_cfg_norm_coef: the index and item arrays must be 4-byte aligned");
+    SINGLE(c, vvk_cfg_norm_coef(a, 3, (hipStream_t)st, &m__));
+}
+int vv_ode_stage_norm(vv_ctx* c, const vv_ode_stage_args* a, const int32_t* u_row, const float* coef, void* st) {
+    if (!coef) return vv_ode_stage_guided(c, a, u_row, st);
+    if (!c || !a) return c ? c->fail(-22, "vv_ode_stage_norm: null arguments") : -22;
+    if ((uintptr_t)u_row % 4) return c->fail(-22, "vv_ode_stage_norm: u_row must be an int32 array");
+    SINGLE(c, vvk_ode_stage(a, u_row, nullptr, (hipStream_t)st, &m__, 0, nullptr, coef));
 }
 // single-kernel entries (unit parity) of the text stack: the checks live here, the stages call the launchers with operands they own
 int vv_text_embed(vv_ctx* c, const int32_t* ids, int ld_ids, const int32_t* text_len, const float* emb, const float* pos, int vocab_rows,

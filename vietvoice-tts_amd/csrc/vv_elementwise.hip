@@ -225,11 +225,15 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ x, c
 // k_i = pc + D g with D read from d_buf; bit `store` -- the item's D, formed from pred, is also written to d_buf because a later evaluation
 // of the call reads it.  A row with u_row >= 0 is computed whatever `load` says; a row with u_row < 0 and no `load` bit is not guided, k_i =
 // pc.  One body and one combine expression, so a computed row runs the very arithmetic of ode_stage_kernel<true, false>.
+// NORM (N24, on top of GUIDED, never with APG or REUSE): coef[b] = {s, f} of cfg_norm_coef_kernel arrives where APG's coefficients do; a
+// guided row's slope is k = f (pc + (pc - s pu) g) -- the plain combine with s pu in place of pu, then one multiplication.  s = 1 and f = 1
+// are exact multiplications, fused or not: such an item runs the arithmetic of ode_stage_kernel<true, false>.  A row with u_row < 0 has
+// k = pc and reads no coefficient.
 struct OdeStagePrev { const float* k[3]; float c[3]; };
 struct GuideFlags { unsigned w[VVK_GUIDE_MAX_ITEMS / 32]; };     // one bit per item of a launch, a kernel argument (N8; N21)
 struct OdeStageReuse { float* d_buf; GuideFlags load, store; };
 struct OdeStageNoReuse {};
-template <bool GUIDED, bool APG, bool REUSE = false>
+template <bool GUIDED, bool APG, bool REUSE = false, bool NORM = false>
 __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* __restrict__ pred, int ldp, int BN, int n_mel, float g,
                                                         const float* __restrict__ g_item, int seq_n, const int* __restrict__ row_src,
                                                         OdeStagePrev pv, float c_new, float* k_out, float* __restrict__ x_out,
@@ -237,6 +241,7 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
                                                         const float* x_e, int xe_packed, float omt,
                                                         std::conditional_t<REUSE, OdeStageReuse, OdeStageNoReuse> ru) {
     static_assert(!REUSE || (GUIDED && !APG), "the reuse form sits on the guided kernel and is never combined with APG");
+    static_assert(!NORM || (GUIDED && !APG && !REUSE), "the CFG-Zero* / rescale form sits on the guided kernel and is never combined with APG or reuse");
     const int c4 = n_mel >> 2;
     const size_t total = (size_t)BN * c4;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -264,14 +269,21 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(float* x, const float* _
             if constexpr (REUSE) {
                 if (ru_load) D = *(const float4*)(ru.d_buf + row * n_mel + c);
             }
+            float2 sf = {1.f, 1.f};
+            if constexpr (NORM) sf = *(const float2*)(apg_coef + 2 * (xr / (size_t)seq_n));
             if (!ru_load) {
                 const float4 pu = *(const float4*)(pred + (GUIDED ? (size_t)ur : row + BN) * ldp + c);
-                D.x = pc.x - pu.x; D.y = pc.y - pu.y; D.z = pc.z - pu.z; D.w = pc.w - pu.w;
+                if constexpr (NORM) {
+                    D.x = pc.x - sf.x * pu.x; D.y = pc.y - sf.x * pu.y; D.z = pc.z - sf.x * pu.z; D.w = pc.w - sf.x * pu.w;
+                } else {
+                    D.x = pc.x - pu.x; D.y = pc.y - pu.y; D.z = pc.z - pu.z; D.w = pc.w - pu.w;
+                }
             }
             k.x = pc.x + D.x * cfg;
             k.y = pc.y + D.y * cfg;
             k.z = pc.z + D.z * cfg;
             k.w = pc.w + D.w * cfg;
+            if constexpr (NORM) { k.x *= sf.y; k.y *= sf.y; k.z *= sf.y; k.w *= sf.y; }
             if constexpr (REUSE) {
                 if (ru_store) *(float4*)(ru.d_buf + row * n_mel + c) = D;
             }
@@ -377,6 +389,93 @@ __global__ __launch_bounds__(64) void apg_coef_kernel(const double* __restrict__
         Cc = (e == 1.0 || S2 == 0.0) ? 0.f : (float)(gb * sc * (e - 1.0) * S1 / S2);
     }
     coef[2 * b] = A; coef[2 * b + 1] = Cc;
+}
+
+// ---------------------------------------------------------------- N24: CFG-Zero* and guidance rescale, the per-item Gram sums
+// Partial sums of one (frame tile, item) over the tile's valid frames and the n_mel columns of the fp32 predictions, in this order:
+// S_cu = sum pc pu, S_uu = sum pu pu, S_cc = sum pc pc, S_c = sum pc, S_u = sum pu.  Products and sums in float64 and NOT contracted (a
+// product, then an add: what a host mirror does with numpy alone).  apg_reduce_kernel's determinism contract: tiles of VV_APG_TILE frames
+// counted from the ITEM's frame 0, float4 q of the tile to thread q % 256 with its four elements in order, one fixed LDS tree -- an item's
+// partials are a function of its own rows alone.  A row whose u_row is < 0 contributes nothing (the coefficient kernel writes {1, 1} for
+// such an item); columns >= n_mel of an ldp-wide row are never read.  grid (n_tiles, B); a tile past the item's length writes nothing.
+__global__ __launch_bounds__(256) void cfg_gram_reduce_kernel(const float* __restrict__ pred, int ldp, int Rc, int n_mel,
+                                                              const int* __restrict__ u_row, const int* __restrict__ row_start,
+                                                              const int* __restrict__ len, int n_tiles, double* __restrict__ partials) {
+#pragma clang fp contract(off)
+    __shared__ double red[5][256];
+    const int b = blockIdx.y, tile = blockIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);   // inside the Rc conditional rows and the item's n_tiles partials, whatever the tables say
+    const int f0 = tile * VV_APG_TILE;
+    if (f0 >= n) return;
+    const int c4 = n_mel >> 2;
+    const int total = min(VV_APG_TILE, n - f0) * c4;
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int q = threadIdx.x; q < total; q += 256) {
+        const int c = (q % c4) * 4;
+        const size_t row = (size_t)r0 + f0 + q / c4;
+        const int ur = u_row ? u_row[row] : (int)row + Rc;
+        if (ur < 0) continue;
+        const float4 pc = *(const float4*)(pred + row * ldp + c);
+        const float4 pu = *(const float4*)(pred + (size_t)ur * ldp + c);
+        const float pcv[4] = {pc.x, pc.y, pc.z, pc.w}, puv[4] = {pu.x, pu.y, pu.z, pu.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double vc = (double)pcv[j], vu = (double)puv[j];
+            const double cu = vc * vu, uu = vu * vu, cc = vc * vc;
+            s[0] = s[0] + cu; s[1] = s[1] + uu; s[2] = s[2] + cc; s[3] = s[3] + vc; s[4] = s[4] + vu;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 5; ++j) red[j][threadIdx.x] = s[j];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 5) partials[((size_t)b * n_tiles + tile) * 5 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// One wave per item: lane j < 5 adds the item's partials in ascending tile order from 0.0, lane 0 turns them into coef[b] = {s, f} (float64,
+// not contracted, one fp32 rounding each):  s = S_cu / S_uu where star[b] != 0 and S_uu != 0, else 1;  with a = 1 + g, c = -g s (s the fp32
+// value), V_xy = S_xy / n - (S_x / n)(S_y / n), var_k = a a V_cc + 2 a c V_cu + c c V_uu:  rho = sqrt(V_cc / var_k), 1 unless both are
+// > 0;  f = phi rho + (1 - phi), exactly 1 where phi = rescale[b] is 0.  {1, 1} for an item without rows or whose first row is not guided
+// (u_row < 0).  report (optional): the same pair once more, the caller's [B][2] row of this evaluation.
+__global__ __launch_bounds__(64) void cfg_norm_coef_kernel(const double* __restrict__ partials, int n_tiles, int Rc, int n_mel,
+                                                           const int* __restrict__ u_row, const int* __restrict__ row_start,
+                                                           const int* __restrict__ len, float g, const float* __restrict__ g_item,
+                                                           const float* __restrict__ star, const float* __restrict__ rescale,
+                                                           float* __restrict__ coef, float* __restrict__ report) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int r0 = min(max(row_start[b], 0), Rc);
+    const int n = min(min(max(len[b], 0), Rc - r0), n_tiles * VV_APG_TILE);
+    const bool guided = n > 0 && (!u_row || u_row[r0] >= 0);
+    double acc = 0.0;
+    if (guided && lane < 5) {
+        const int nt = (n + VV_APG_TILE - 1) / VV_APG_TILE;
+        for (int t = 0; t < nt; ++t) acc += partials[((size_t)b * n_tiles + t) * 5 + lane];
+    }
+    const double Scu = __shfl(acc, 0), Suu = __shfl(acc, 1), Scc = __shfl(acc, 2), Sc = __shfl(acc, 3), Su = __shfl(acc, 4);
+    if (lane != 0) return;
+    float s = 1.f, f = 1.f;
+    if (guided) {
+        if (star && star[b] != 0.f && Suu != 0.0) s = (float)(Scu / Suu);
+        const double phi = rescale ? (double)rescale[b] : 0.0;
+        if (phi != 0.0) {
+            const double gb = (double)(g_item ? g_item[b] : g), a = 1.0 + gb, c = -gb * (double)s;
+            const double cnt = (double)n * (double)n_mel, mc = Sc / cnt, mu = Su / cnt;
+            const double Vcc = Scc / cnt - mc * mc, Vcu = Scu / cnt - mc * mu, Vuu = Suu / cnt - mu * mu;
+            const double var_k = (a * a) * Vcc + (2.0 * a * c) * Vcu + (c * c) * Vuu;
+            const double rho = (var_k > 0.0 && Vcc > 0.0) ? sqrt(Vcc / var_k) : 1.0;
+            f = (float)(phi * rho + (1.0 - phi));
+        }
+    }
+    coef[2 * b] = s; coef[2 * b + 1] = f;
+    if (report) { report[2 * b] = s; report[2 * b + 1] = f; }
 }
 
 // ---------------------------------------------------------------- N20: the step report of a multistep plan, the per-item reduction
@@ -993,7 +1092,7 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
 }
 
 int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring,
-                  const vv_reuse_stage_args* reuse) {
+                  const vv_reuse_stage_args* reuse, const float* norm_coef) {
     if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "ode_stage: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
     if (!a->x || !a->pred || a->n_prev < 0 || a->n_prev > 3) { *err = "ode_stage: x, pred and 0..3 earlier slopes"; return -22; }
     if (a->g_item && a->seq_n < 1) { *err = "ode_stage: g_item needs the padded sequence length seq_n"; return -22; }
@@ -1018,6 +1117,14 @@ int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_sta
     }
     const int grid = grid_for((size_t)a->Rc * a->n_mel / 4);
     const float omt = apg ? 1.0f - apg->t_e : 0.f;
+    if (norm_coef) {                                     // N24
+        if (apg || reuse || !u_row) { *err = "ode_stage: the CFG-Zero* / rescale form needs u_row and is not combined with APG or reuse"; return -22; }
+        if ((uintptr_t)norm_coef % 8 || a->seq_n < 1) { *err = "ode_stage: the CFG-Zero* / rescale form needs 8-byte aligned coefficients and the padded sequence length seq_n"; return -22; }
+        ode_stage_kernel<true, false, false, true><<<grid, 256, 0, st>>>(a->x, a->pred, a->ldp, a->Rc, a->n_mel, a->g, a->g_item, a->seq_n, a->row_src, pv,
+                                                                          a->coef[a->n_prev], a->k_out, a->x_out, u_row, norm_coef, nullptr, 0, omt, OdeStageNoReuse{});
+        VVK_CHECK_LAUNCH();
+        return 0;
+    }
     if (reuse) {                                         // N21
         if (apg || !u_row) { *err = "ode_stage: the reuse form needs u_row and is not combined with APG"; return -22; }
         if (!reuse->d_buf || (uintptr_t)reuse->d_buf % 16 || !reuse->item_mode_host) { *err = "ode_stage: d_buf (16-byte aligned) and the item modes are required"; return -22; }
@@ -1063,6 +1170,25 @@ int vvk_apg_coef(const vv_apg_coef_args* a, int which, hipStream_t st, const cha
     if (which & 2) {
         apg_coef_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->n_mel, a->u_row, a->row_start, a->len, omt, a->g, a->g_item,
                                              a->eta, a->norm_rms, a->coef);
+        VVK_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// N24: the two kernels behind vv_cfg_norm_coef.  which & 1: the Gram sums, which & 2: the coefficients.
+int vvk_cfg_norm_coef(const vv_cfg_norm_coef_args* a, int which, hipStream_t st, const char** err) {
+    if (a->n_mel < 4 || a->n_mel % 4 || a->ldp % 4 || a->ldp < a->n_mel || a->Rc < 1) { *err = "cfg_norm_coef: widths must be multiples of 4, ldp >= n_mel, Rc >= 1"; return -22; }
+    if (!a->pred || !a->row_start || !a->len || !a->partials || !a->coef) { *err = "cfg_norm_coef: pred, row_start, len, partials and coef are required"; return -22; }
+    if (a->B < 1 || a->B > VVK_GUIDE_MAX_ITEMS || a->n_tiles < 1) { *err = "cfg_norm_coef: 1..1024 items, n_tiles >= 1"; return -22; }
+    if ((uintptr_t)a->pred % 16 || (uintptr_t)a->partials % 8 || (uintptr_t)a->coef % 8 || (uintptr_t)a->report % 8) { *err = "cfg_norm_coef: pred 16-byte, partials, coef and report 8-byte aligned"; return -22; }
+    if (!(a->g == a->g)) { *err = "cfg_norm_coef: NaN strength"; return -22; }
+    if (which & 1) {
+        cfg_gram_reduce_kernel<<<dim3(a->n_tiles, a->B), 256, 0, st>>>(a->pred, a->ldp, a->Rc, a->n_mel, a->u_row, a->row_start, a->len, a->n_tiles, a->partials);
+        VVK_CHECK_LAUNCH();
+    }
+    if (which & 2) {
+        cfg_norm_coef_kernel<<<a->B, 64, 0, st>>>(a->partials, a->n_tiles, a->Rc, a->n_mel, a->u_row, a->row_start, a->len, a->g, a->g_item, a->star, a->rescale,
+                                                  a->coef, a->report);
         VVK_CHECK_LAUNCH();
     }
     return 0;

@@ -33,8 +33,11 @@ int vvk_cfg_euler(float* x, const float* pred, int ldp, int BN, int n_mel, float
 // apg (N11, optional): the item coefficients {A, C} and the evaluation state of the projected combine
 // k_out_ring != 0 (N20, the steps driver under a multistep plan): a->k_out may be the buffer of one of the earlier slopes
 // reuse (N21, optional; needs u_row, never with apg): the buffer of the kept guidance differences and the items' modes (HOST, kernel arguments)
+// norm_coef (N24, optional; needs u_row, never with apg or reuse): the items' {s, f} of cfg_norm_coef_kernel, device [items][2] fp32
 int vvk_ode_stage(const vv_ode_stage_args* a, const int* u_row, const vv_apg_stage_args* apg, hipStream_t st, const char** err, int k_out_ring = 0,
-                  const vv_reuse_stage_args* reuse = nullptr);
+                  const vv_reuse_stage_args* reuse = nullptr, const float* norm_coef = nullptr);
+// N24: cfg_gram_reduce_kernel (which & 1) and cfg_norm_coef_kernel (which & 2) of one evaluation
+int vvk_cfg_norm_coef(const vv_cfg_norm_coef_args* a, int which, hipStream_t st, const char** err);
 // N21: the drift report -- which & 1: cfg_drift_reduce_kernel, which & 2: the item sums
 int vvk_cfg_drift_reduce(const vv_cfg_drift_args* a, int which, hipStream_t st, const char** err);
 // N23 block caching: one MARK / DIFF / APPLY launch of the span kernel; the report -- which & 1: block_drift_reduce_kernel, which & 2: the

@@ -255,7 +255,17 @@ def multistep_weights(t64, q: int) -> Tuple[Tuple[float, ...], ...]:
     return tuple(rows)
 
 
-def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
+def check_cfg_zero_init(k, nfe_step: int) -> int:
+    """N24 zero-init (Fan et al. 2025): the number K of leading ODE steps that are skipped -- the state stays the start noise up to t_K.  An
+    integer with 0 <= K <= nfe_step - 2 (one step at least is left); ValueError for a bool, a non-integer and a K outside that range."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral):
+        raise ValueError("cfg_zero_init must be an integer >= 0")
+    if int(k) != 0 and not 0 <= int(k) <= int(nfe_step) - 2:            # 0 is "off" on any grid
+        raise ValueError(f"cfg_zero_init must satisfy 0 <= K <= nfe_step - 2 = {int(nfe_step) - 2}, got {int(k)}")
+    return int(k)
+
+
+def ode_plan(nfe_step: int, sway_coef: float, method="euler", skip: int = 0) -> OdePlan:
     """The sampler's plan on time_grid's grid: ``nfe_step`` points, ``nfe_step - 1`` ODE steps of ``s`` evaluations each at
     t_n + c_i h_n (float64, clamped to [0, 1], then fp32 -- like time_grid).  ``ode_plan(n, sway, "euler")`` is time_grid bit for bit.
 
@@ -263,10 +273,15 @@ def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
     Euler's bit for bit (one evaluation per step, at t_n), and ``beta`` holds multistep_weights' rows on the float64 grid.  No start-up
     step with extra evaluations is built: step 0 is an Euler step and step 1 of "ab3" an AB2 step.  With that start "ab3" has global
     order 3 on the model's own sway grid (coefficient -1: the first step is O(n^-2) long, so its O(h_0^2) error is O(n^-4)) and order
-    2 on a uniform grid; "ab2" has order 2 on both."""
+    2 on a uniform grid; "ab2" has order 2 on both.
+
+    ``skip`` = K (N24 zero-init, check_cfg_zero_init): the plan of the steps K ... nfe_step - 2 of the same grid -- the state stays the start
+    noise up to t_K.  ``t``, ``dt`` are the rows of the full plan from step K on, and ``beta`` the variable-step weights of the grid points
+    from K on, so the order ramp starts at the first step that exists.  skip = 0 is the full plan bit for bit."""
+    skip = check_cfg_zero_init(skip, nfe_step)
     if isinstance(method, str) and method in ODE_MULTISTEP:
-        e = ode_plan(nfe_step, sway_coef, "euler")
-        return e._replace(beta=multistep_weights(_grid64(nfe_step, sway_coef), ODE_MULTISTEP[method]))
+        e = ode_plan(nfe_step, sway_coef, "euler", skip)
+        return e._replace(beta=multistep_weights(_grid64(nfe_step, sway_coef)[skip:], ODE_MULTISTEP[method]))
     a, b = ode_tableau(method)
     s = len(b)
     t = torch.linspace(0.0, 1.0, nfe_step, dtype=torch.float64)
@@ -276,7 +291,7 @@ def ode_plan(nfe_step: int, sway_coef: float, method="euler") -> OdePlan:
     te = t[:-1, None] + c[None, :] * dt[:, None]
     if s > 1:
         te = te.clamp(0.0, 1.0)
-    return OdePlan(te.reshape(-1).to(torch.float32), dt.to(torch.float32), a, b, s)
+    return OdePlan(te[skip:].reshape(-1).to(torch.float32), dt[skip:].to(torch.float32), a, b, s)
 
 
 def check_cfg_interval(interval) -> Optional[Tuple[float, float]]:
@@ -409,6 +424,36 @@ def check_apg(eta, norm) -> Optional[Tuple[float, Optional[float]]]:
     if r is not None and not (math.isfinite(r) and r > 0.0):
         raise ValueError("apg_norm must be finite and > 0, or None")
     return None if (e == 1.0 and r is None) else (e, r)
+
+
+def check_cfg_norm(zero_star, rescale) -> Optional[Tuple[bool, float]]:
+    """N24 of one item: ``zero_star`` turns on the optimised scale s* = <p_c, p_u> / <p_u, p_u> of CFG-Zero* (Fan et al. 2025; None or False
+    = off), ``rescale`` is the guidance rescale phi of Lin et al. 2024 applied to the guided velocity (None = off, else 0 < phi <= 1).
+    Returns (zero_star, phi) with phi = 0.0 for "no rescale", or None when both are off (the plain rule).  ValueError for a zero_star that is
+    not a bool and a rescale that is not a finite number in (0, 1]."""
+    if zero_star is not None and not isinstance(zero_star, bool):
+        raise ValueError("cfg_zero_star must be a bool or None")
+    phi = 0.0
+    if rescale is not None:
+        if isinstance(rescale, bool) or not isinstance(rescale, numbers.Real):
+            raise ValueError("cfg_rescale must be a number or None")
+        phi = float(rescale)
+        if not (math.isfinite(phi) and 0.0 < phi <= 1.0):
+            raise ValueError("cfg_rescale must satisfy 0 < phi <= 1, or be None")
+    return None if (not zero_star and phi == 0.0) else (bool(zero_star), phi)
+
+
+def check_cfg_norm_combination(zero_star, rescale, apg_eta, apg_norm, cfg_reuse, block_cache) -> None:
+    """N24: what one item's CFG-Zero* / rescale is never combined with, each refusal a sentence of its own (ModelConfig, submit and the
+    engine all raise these): projected guidance, guidance reuse, block caching.  Nothing is raised for an item with both options off."""
+    if check_cfg_norm(zero_star, rescale) is None:
+        return
+    if check_apg(apg_eta, apg_norm) is not None:
+        raise ValueError("cfg_zero_star / cfg_rescale cannot be combined with apg_eta / apg_norm (both rewrite the guided slope from the same two predictions)")
+    if (cfg_reuse or 1) > 1:
+        raise ValueError("cfg_zero_star / cfg_rescale cannot be combined with cfg_reuse > 1 (a reused evaluation has no unconditional prediction to measure)")
+    if block_cache is not None:
+        raise ValueError("cfg_zero_star / cfg_rescale cannot be combined with block_cache (the block-cache entry has no guided form)")
 
 
 NOISE_SOURCES = ("host", "device")      # ModelConfig.noise_source: torch.randn on the host (default) | vv_noise_fill on the device (N9)

@@ -16,7 +16,8 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import pack
-from .model_spec import ODE_MAX_EVALS, ODE_MULTISTEP, ModelSpec, block_cache_schedule, check_apg, check_block_cache, guidance_mask, ode_plan
+from .model_spec import (ODE_MAX_EVALS, ODE_MULTISTEP, ModelSpec, block_cache_schedule, check_apg, check_block_cache, check_cfg_norm, guidance_mask,
+                         ode_plan)
 from .pcm_stage import JOIN_MAX_N, LOUD_RUN, PcmStage, _ptr, plan_join  # noqa: F401  (the constants and plan_join stay importable from here)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -125,6 +126,17 @@ class vv_apg_stage_args(C.Structure):
     _fields_ = [("coef", C.c_void_p), ("x_e", C.c_void_p), ("x_e_packed", C.c_int32), ("t_e", C.c_float)]
 
 
+class vv_cfg_norm_args(C.Structure):
+    _fields_ = [("star", C.c_void_p), ("rescale", C.c_void_p), ("report", C.c_void_p)]
+
+
+class vv_cfg_norm_coef_args(C.Structure):
+    _fields_ = [("pred", C.c_void_p), ("ldp", C.c_int32), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("u_row", C.c_void_p),
+                ("B", C.c_int32), ("n_tiles", C.c_int32), ("row_start", C.c_void_p), ("len", C.c_void_p), ("g", C.c_float),
+                ("g_item", C.c_void_p), ("star", C.c_void_p), ("rescale", C.c_void_p), ("partials", C.c_void_p), ("coef", C.c_void_p),
+                ("report", C.c_void_p)]
+
+
 class vv_ode_diff_args(C.Structure):
     _fields_ = [("f", C.c_void_p), ("f_prev", C.c_void_p), ("Rc", C.c_int32), ("n_mel", C.c_int32), ("B", C.c_int32), ("n_tiles", C.c_int32),
                 ("row_start", C.c_void_p), ("len", C.c_void_p), ("partials", C.c_void_p), ("report", C.c_void_p)]
@@ -188,6 +200,10 @@ EXPORTS = {
     "vv_transformer_apg_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
     "vv_apg_coef": (C.c_int, [C.c_void_p, C.POINTER(vv_apg_coef_args), C.c_void_p]),
     "vv_ode_stage_apg": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_apg_stage_args), C.c_void_p]),
+    "vv_transformer_steps_norm": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.POINTER(vv_cfg_norm_args), C.c_void_p]),
+    "vv_transformer_norm_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "vv_cfg_norm_coef": (C.c_int, [C.c_void_p, C.POINTER(vv_cfg_norm_coef_args), C.c_void_p]),
+    "vv_ode_stage_norm": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.c_void_p, C.c_void_p]),
     "vv_transformer_steps_reuse": (C.c_int, [C.c_void_p, C.POINTER(vv_steps_args), C.c_void_p, C.c_int, C.POINTER(vv_reuse_args), C.c_void_p]),
     "vv_transformer_reuse_ws_bytes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]),
     "vv_ode_stage_reuse": (C.c_int, [C.c_void_p, C.POINTER(vv_ode_stage_args), C.c_void_p, C.POINTER(vv_reuse_stage_args), C.c_void_p]),
@@ -396,7 +412,7 @@ class HipSynth(PcmStage):
 
     def __init__(self, spec: ModelSpec, weights: Optional[Dict[str, torch.Tensor]] = None, device: str = "cuda:0",
                  acoustic_dtype="bf16", nfe_step: int = 32, flat_weights: Optional[torch.Tensor] = None, ode_method="euler",
-                 ode_report: bool = False):
+                 ode_report: bool = False, cfg_zero_init: int = 0):
         super().__init__()
         self.lib = load_library()
         if not torch.cuda.is_available():
@@ -441,7 +457,10 @@ class HipSynth(PcmStage):
         self._cfg_reuse_report = None    # the last such call's report, float64 [n_evals, B, 2] on the device
         self.block_cache_report = False  # N23: every transformer_steps call with a block cache leaves its report (last_block_cache_report)
         self._block_cache_report = None  # the last such call's report, float64 [n_evals, B, 2, 2] on the device
-        self.set_nfe(nfe_step, ode_method)
+        self.cfg_norm_report = False     # N24: every transformer_steps call with CFG-Zero* / rescale leaves its (s, f) (last_cfg_norm_report)
+        self._cfg_norm_report = None     # the last such call's report, fp32 [n_evals, B, 2] on the device
+        self.cfg_zero_init = None        # N24 zero-init: the leading steps the plan in force leaves out
+        self.set_nfe(nfe_step, ode_method, cfg_zero_init)
         self.set_ode_report(ode_report)
 
     # ------------------------------------------------------------------ plumbing
@@ -463,20 +482,21 @@ class HipSynth(PcmStage):
         except Exception:
             pass
 
-    def set_nfe(self, nfe_step: int, ode_method="euler"):
+    def set_nfe(self, nfe_step: int, ode_method="euler", cfg_zero_init: int = 0):
         """The sampler's plan (N7): ``nfe_step`` grid points = ``nfe_step - 1`` ODE steps of the explicit Runge-Kutta method
         ``ode_method`` (a name of model_spec.ODE_METHODS, or a tableau (a, b)); ``n_evals`` = stages x steps DiT evaluations.  Or (N20) a
         name of model_spec.ODE_MULTISTEP: Adams-Bashforth on the slopes kept from the steps before, one evaluation per step
-        (vv_set_ode_multistep); a transformer_steps call then starts at step 0."""
+        (vv_set_ode_multistep); a transformer_steps call then starts at step 0.  ``cfg_zero_init`` = K (N24): the plan of the grid's steps
+        K ... nfe_step - 2 alone (model_spec.ode_plan(skip=K)); steps, evaluations, masks and reports are then those of that plan."""
         if not isinstance(ode_method, str):
             ode_method = (tuple(tuple(r) for r in ode_method[0]), tuple(ode_method[1]))
-        if (nfe_step, ode_method) == (self.nfe_step, self.ode_method):
+        if (nfe_step, ode_method, cfg_zero_init) == (self.nfe_step, self.ode_method, self.cfg_zero_init):
             return
         if nfe_step < 2:
             raise ValueError("nfe_step must be >= 2")
         if self.ode_report and not (isinstance(ode_method, str) and ode_method in ODE_MULTISTEP):
             raise ValueError("ode_report is on: it needs a multistep ode_method (set_ode_report(False) first)")
-        plan = ode_plan(nfe_step, self.spec.sway_coef, ode_method)
+        plan = ode_plan(nfe_step, self.spec.sway_coef, ode_method, cfg_zero_init)
         n_steps = int(plan.dt.numel())
         if n_steps * plan.s > ODE_MAX_EVALS:
             raise ValueError(f"{n_steps} ODE steps of {plan.s} stages exceed {ODE_MAX_EVALS} evaluations")
@@ -493,6 +513,7 @@ class HipSynth(PcmStage):
                 self._check(self.lib.vv_set_ode_plan(self.ctx, sinus.data_ptr(), dtc.data_ptr(), n_steps, plan.s, a, b, self._stream()))
             self.nfe_step = nfe_step
             self.ode_method = ode_method
+            self.cfg_zero_init = int(cfg_zero_init)
             self.n_steps = n_steps
             self.n_evals = n_steps * plan.s
             self.plan = plan             # the evaluation times a guidance interval is compared with (guidance_mask)
@@ -651,9 +672,43 @@ class HipSynth(PcmStage):
         norm = torch.tensor([0.0 if p is None or p[1] is None else p[1] for p in pairs], dtype=torch.float32).to(self.device)
         return eta, norm
 
+    def cfg_norm_tensors(self, stars, rescales):
+        """N24: the ``cfg_norm`` of transformer_steps from B host values each -- the CFG-Zero* switch (None / False = off) and the rescale phi
+        (None = off), validated by model_spec.check_cfg_norm.  None when both are off for every item (the call then goes to the existing
+        entries), else (star, rescale) fp32 [B] on the device, 0 standing for "off"."""
+        stars, rescales = list(stars), list(rescales)
+        if len(stars) != len(rescales):
+            raise ValueError("cfg_norm_tensors: one cfg_zero_star and one cfg_rescale per item")
+        pairs = [check_cfg_norm(z, r) for z, r in zip(stars, rescales)]
+        if all(p is None for p in pairs):
+            return None
+        star = torch.tensor([0.0 if p is None or not p[0] else 1.0 for p in pairs], dtype=torch.float32).to(self.device)
+        resc = torch.tensor([0.0 if p is None else p[1] for p in pairs], dtype=torch.float32).to(self.device)
+        return star, resc
+
+    def set_cfg_norm_report(self, on: bool):
+        """N24: on, every transformer_steps call with cfg_norm leaves fp32 [n_evals, B, 2] for last_cfg_norm_report (the coefficient kernel
+        writes its pair twice: no further launch); off (the default) allocates nothing."""
+        with self._lock:
+            self.cfg_norm_report = bool(on)
+            if not on:
+                self._cfg_norm_report = None
+
+    def last_cfg_norm_report(self):
+        """N24: the (s, f) of the last transformer_steps call with cfg_norm, numpy float32 [n_evals, B, 2]: per evaluation e of the plan in
+        force and item b the optimised scale and the rescale factor the stage kernel used, (1, 1) where b is not guided, and zeros at
+        evaluations outside the call.  One copy from the device; None when no call has left a report."""
+        with self._lock:
+            rep = self._cfg_norm_report
+            return None if rep is None else rep.cpu().numpy()
+
+    def norm_ws_bytes(self, B: int, N: int, seq_len_host) -> int:
+        """Bytes of a caller-owned workspace for a call with CFG-Zero* / rescale (vv_transformer_norm_ws_bytes; the same with any mask)."""
+        return self._steps_ws_bytes(self.lib.vv_transformer_norm_ws_bytes, B, N, _host_lens(B, seq_len_host))
+
     def transformer_steps(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, seq_len_host=None,
                           cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, apg=None, block_cache=None,
-                          block_cache_interval=None) -> torch.Tensor:
+                          block_cache_interval=None, cfg_norm=None) -> torch.Tensor:
         """x fp32 [B,N,n_mel] updated in place on the device.  seq_len_host (optional list / array of the B lengths, the same
         values as pre["seq_len"]): the call then needs no read-back and no stream synchronisation (vv_transformer_steps_h).
         cfg (optional fp32 [B] on the device): the guidance strength of each item (vv_transformer_steps_ex); None = the model's.
@@ -664,18 +719,22 @@ class HipSynth(PcmStage):
         (vv_transformer_steps_apg; apg_tensors builds it); None, or a pair of Nones = off: the existing entries.
         block_cache (optional (first, last, every), N23): the blocks [first, last) are skipped at every evaluation inside
         block_cache_interval (None = everywhere) whose count is not a multiple of ``every`` (vv_transformer_steps_cached;
-        model_spec.block_cache_schedule builds the modes); never with a mask or apg.  None = the existing entries."""
+        model_spec.block_cache_schedule builds the modes); never with a mask or apg.  None = the existing entries.
+        cfg_norm (optional pair (star, rescale) of fp32 [B] device tensors, either None, N24): CFG-Zero*'s optimised scale and the guidance
+        rescale per item (vv_transformer_steps_norm; cfg_norm_tensors builds it); never with apg, block_cache or a mask that holds a 2."""
         B, N, M = x.shape
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and M == self.spec.n_mel
         if seq_len_host is None:
             seq_len_host = pre.get("seq_len_host")
         if apg is not None and apg[0] is None and apg[1] is None:
             apg = None
+        if cfg_norm is not None and cfg_norm[0] is None and cfg_norm[1] is None:
+            cfg_norm = None
         modes = self.block_cache_modes(block_cache, block_cache_interval)
-        if cfg is not None or guide is not None or apg is not None or modes is not None:
+        if cfg is not None or guide is not None or apg is not None or modes is not None or cfg_norm is not None:
             assert cfg is None or (cfg.is_cuda and cfg.dtype == torch.float32 and cfg.is_contiguous() and cfg.shape == (B,)), "cfg: fp32 [B] on the device"
             host = None if seq_len_host is None else _host_lens(B, seq_len_host)
-            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg, block_modes=modes)
+            self.transformer_steps_ex(x, pre, step0, n_steps, host, cfg, guide=guide, apg=apg, block_modes=modes, cfg_norm=cfg_norm)
             return x
         with self._lock, torch.cuda.device(self.device), self._ReportScope(self, B, step0):
             tail = _pre_ptrs(pre) + (step0, n_steps, self._stream())
@@ -729,7 +788,8 @@ class HipSynth(PcmStage):
 
     def transformer_steps_ex(self, x: torch.Tensor, pre: Dict[str, torch.Tensor], step0: int, n_steps: int, host=None,
                              cfg: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
-                             guide: Optional[torch.Tensor] = None, apg=None, reuse_entry: Optional[bool] = None, block_modes=None) -> None:
+                             guide: Optional[torch.Tensor] = None, apg=None, reuse_entry: Optional[bool] = None, block_modes=None,
+                             cfg_norm=None) -> None:
         """The struct-argument entry as it is (vv_transformer_steps_ex); raises on a non-zero code.  host: a ctypes int32 array of
         the B lengths or None (read back); ws: an optional caller-owned uint8 workspace (needs host).  guide: a contiguous uint8
         HOST tensor [n_evals of the plan in force, ld_guide], handed to vv_transformer_steps_guided as it is (the library checks
@@ -738,8 +798,21 @@ class HipSynth(PcmStage):
         vv_transformer_steps_reuse (with the drift report's buffer when set_cfg_reuse_report is on), False never; None = when the mask
         holds a 2 or the report is on.  Never together with apg.  block_modes (N23): None, or (first, last, modes) with modes a
         contiguous uint8 HOST tensor [n_modes], handed to vv_transformer_steps_cached as they are (with the report's buffer when
-        set_block_cache_report is on); never together with guide or apg."""
+        set_block_cache_report is on); never together with guide or apg.  cfg_norm (N24): None, or a pair (star, rescale) of fp32 [B]
+        device tensors (either None), handed to vv_transformer_steps_norm (with the report's buffer when set_cfg_norm_report is on); never
+        together with apg, block_modes or a mask that holds a 2."""
         B, N, _ = x.shape
+        if cfg_norm is not None:
+            if len(cfg_norm) != 2 or any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32
+                                                                and t.is_contiguous() and t.shape == (B,)) for t in cfg_norm):
+                raise ValueError("cfg_norm must be a pair (star, rescale) of fp32 [B] device tensors or Nones")
+            if apg is not None:
+                raise ValueError("CFG-Zero* / guidance rescale is not combined with projected guidance (apg): both rewrite the guided slope")
+            if block_modes is not None:
+                raise ValueError("CFG-Zero* / guidance rescale is not combined with block caching (that entry has no guided form)")
+            if reuse_entry or (guide is not None and bool((guide[:, :B] == 2).any())):
+                raise ValueError("CFG-Zero* / guidance rescale is not combined with guidance reuse (a reused item has no unconditional prediction to measure)")
+            reuse_entry = False
         if block_modes is not None:
             if guide is not None or apg is not None:
                 raise ValueError("block caching takes no guidance mask and no projected guidance (a guided subset moves the rows the cache stores)")
@@ -775,6 +848,13 @@ class HipSynth(PcmStage):
                 self._block_cache_report = None
                 self._check(self.lib.vv_transformer_steps_cached(self.ctx, C.byref(a), C.byref(k), self._stream()))
                 self._block_cache_report = rep
+            elif cfg_norm is not None:
+                rep = torch.zeros((self.n_evals, B, 2), dtype=torch.float32, device=self.device) if self.cfg_norm_report else None
+                q = vv_cfg_norm_args(_ptr(cfg_norm[0]), _ptr(cfg_norm[1]), _ptr(rep))
+                self._cfg_norm_report = None
+                self._check(self.lib.vv_transformer_steps_norm(self.ctx, C.byref(a), None if guide is None else guide.data_ptr(),
+                                                               0 if guide is None else int(guide.shape[1]), C.byref(q), self._stream()))
+                self._cfg_norm_report = rep
             elif reuse_entry:
                 rep = torch.zeros((self.n_evals, B, 2), dtype=torch.float64, device=self.device) if self.cfg_reuse_report else None
                 r = vv_reuse_args(_ptr(rep), B, self.n_evals)
@@ -880,7 +960,7 @@ class HipSynth(PcmStage):
     def synthesize_batch(self, audio, audio_len, text_ids, text_len, seq_len, N: int, noise: Optional[torch.Tensor], t_gen_max: int,
                          n_steps: Optional[int] = None, max_audio_len: Optional[int] = None, gen_frames=None, seq_len_host=None,
                          audio_len_host=None, cfg: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None, noise_keys=None,
-                         apg=None, block_cache=None, block_cache_interval=None):
+                         apg=None, block_cache=None, block_cache_interval=None, cfg_norm=None):
         """Whole hot path for a batch, state resident in HBM: preprocess -> ODE steps -> vocoder.
         noise fp32 [B, N, n_mel] on the device, or None with noise_keys = (model_spec.noise_keys rows): the noise is then drawn on the
         device (``noise``) and nothing of it crosses PCIe.  Exactly one of the two.
@@ -888,13 +968,13 @@ class HipSynth(PcmStage):
         seq_len_host (optional): the lengths on the host too -- the Euler-step call then runs without any stream synchronisation.
         cfg (optional fp32 [B] on the device): per-item guidance strength.  guide (optional uint8 [n_evals, B] on the host): the
         guidance mask of transformer_steps.  apg (optional pair of fp32 [B] device tensors): its projected guidance.  block_cache /
-        block_cache_interval (N23): its block caching."""
+        block_cache_interval (N23): its block caching.  cfg_norm (N24): its CFG-Zero* / rescale pair."""
         self._one_noise(noise, noise_keys)
         pre = self.preprocess(audio, audio_len, text_ids, text_len, seq_len, N, max_audio_len, seq_len_host=seq_len_host,
                               audio_len_host=audio_len_host)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, seq_len, N)
         self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg, block_cache=block_cache,
-                               block_cache_interval=block_cache_interval)
+                               block_cache_interval=block_cache_interval, cfg_norm=cfg_norm)
         if gen_frames is not None and len(gen_frames) == x.shape[0]:
             pcm, pcm_len = self.decode_bucketed(x, pre, gen_frames)
             if pcm.shape[1] < t_gen_max * self.spec.hop_length:
@@ -962,12 +1042,13 @@ class HipSynth(PcmStage):
 
     def edit_batch(self, src: torch.Tensor, rows, spliced_len, text_ids: torch.Tensor, text_len: torch.Tensor, keep: torch.Tensor,
                    noise: Optional[torch.Tensor] = None, n_steps: Optional[int] = None, cfg: Optional[torch.Tensor] = None,
-                   guide: Optional[torch.Tensor] = None, noise_keys=None, apg=None, block_cache=None, block_cache_interval=None):
+                   guide: Optional[torch.Tensor] = None, noise_keys=None, apg=None, block_cache=None, block_cache_interval=None,
+                   cfg_norm=None):
         """B speech edits in one batch: splice -> masked preprocess -> Euler steps -> restore -> vocoder over every frame.
         src int16 [n] (device, the source clips back to back), rows = host splice rows {item, src_off, dst_off, n}, spliced_len = host
         list of the B spliced clip lengths L_b (frames N_b = L_b // hop + 1), text_ids / text_len int32 on the device (the new full
         transcripts), keep uint8 [B, >= max N_b] (device), noise fp32 [B, max N_b, n_mel] (device) or, in its place, noise_keys =
-        model_spec.noise_keys rows (drawn on the device; exactly one of the two).  cfg / guide / apg: as transformer_steps.
+        model_spec.noise_keys rows (drawn on the device; exactly one of the two).  cfg / guide / apg / cfg_norm: as transformer_steps.
         Returns (x, pcm, pcm_len): pcm int16 [B, N * hop] holds the edited clip b in its first pcm_len[b] = min(L_b, the vocoder's
         output of N_b frames) samples -- L_b with the HiFi-GAN (hop * N_b >= L_b), hop * (N_b - 1) with Vocos (the rest is zeros)."""
         s = self.spec
@@ -984,7 +1065,7 @@ class HipSynth(PcmStage):
         pre = self.preprocess_edit(audio, i32(L), text_ids, text_len, i32(frames), N, keep, L, max_audio_len=mal, seq_len_host=frames)
         x = noise.clone() if noise_keys is None else self.noise(noise_keys, pre["seq_len"], N)
         self.transformer_steps(x, pre, 0, self.n_steps if n_steps is None else n_steps, cfg=cfg, guide=guide, apg=apg, block_cache=block_cache,
-                               block_cache_interval=block_cache_interval)
+                               block_cache_interval=block_cache_interval, cfg_norm=cfg_norm)
         self.edit_restore(x, pre, keep)
         pcm, _ = self.decode(x, pre, N)
         return x, pcm, i32([min(v, s.pcm_samples(f)) for v, f in zip(L, frames)])
