@@ -1024,6 +1024,39 @@ VV_API int vv_flac_decode(vv_ctx* ctx, const uint8_t* data, int64_t n_bytes, con
                           const int64_t* lay_host, const void* ws, uint64_t ws_bytes, uint8_t* pcm, int64_t n_pcm, int64_t* info2, void* ws2,
                           uint64_t ws2_bytes, void* stream);
 
+/* ---- N25 IMA ADPCM output, and IMA ADPCM / G.711 reference clips.  The arithmetic is the Intel/DVI coder of CPython's
+ * Modules/audioop.c (lin2adpcm, adpcm2lin, ulaw2lin, alaw2lin), restated by core/audio_processor.py (adpcm_encode_blocks,
+ * adpcm_decode_frames, ulaw2lin, alaw2lin), which the kernels equal byte for byte and sample for sample.  Integers only.
+ * vv_pcm_adpcm: the blocks of a mono WAVE file with format tag 0x11 for R final signals.
+ *   samples_per_block   spb = 8 k + 1 in 9 ... 8185; a block is {int16 first sample, uint8 step index, uint8 0} and (spb - 1) / 2 bytes of
+ *            codes, low nibble first: (spb - 1) / 2 + 4 <= VV_ADPCM_MAX_BLOCK_ALIGN bytes
+ *   rows     R x 3 int64 on the device, rows_host the same on the host (checked before a launch): {src_off, n >= 1, dst_off in bytes,
+ *            a multiple of 4}: x[src_off, +n) becomes ceil(n / spb) blocks at y + dst_off, the last one padded with its last sample;
+ *            the rows' blocks lie in ascending order on y, disjoint
+ *   search   the header's step index is free: each block tries all 89 and keeps the one with the smallest sum of (x - decoded)^2 over its
+ *            real samples, the smallest index of equals.  Blocks are independent: a request alone equals itself in a batch, and a stream
+ *            cut at block boundaries equals the whole signal
+ *   y        n_y bytes, 8-byte aligned, must not overlap x; the size is known on the host, so nothing is read back but the bytes
+ * vv_wav_decode: the coded data chunks of R WAVE clips -> the interleaved int16 frames vv_ingest_pcm reads at width 2.
+ *   data     the clips' data chunks, each at a 16-byte aligned offset; 16-byte aligned
+ *   rows     R x 8 int64 (device, and rows_host): {data byte offset, n_bytes, format tag (6 A-law, 7 mu-law, 0x11 IMA ADPCM), channels,
+ *            nBlockAlign (ADPCM: a multiple of 4 x channels, >= 8 x channels; 1 or 2 channels), frames to write (at most what the bytes
+ *            hold: a fact chunk may state fewer), pcm byte offset (16-byte aligned, ascending), 0}
+ *   ADPCM    per channel a 4-byte header, then rounds of 4 bytes (8 samples) per channel; a trailing part of a block decodes the codes
+ *            it holds; one lane per (block, channel)
+ *   status   R x 2 int64 (device): {0, 0}, or {VV_WAV_STEP_INDEX, the byte of the first header step index above 88, from the clip's first
+ *            data byte}.  Such a clip's PCM is undefined inside its own frames; nothing outside them is written, other clips are intact
+ * -22 and nothing launched: null or misaligned pointers, rows outside the buffers, R outside 1 ... 65535, overlapping buffers. */
+#define VV_ADPCM_MAX_BLOCK_ALIGN 4096
+#define VV_WAVE_TAG_ALAW 6
+#define VV_WAVE_TAG_ULAW 7
+#define VV_WAVE_TAG_ADPCM 17
+enum { VV_WAV_OK = 0, VV_WAV_STEP_INDEX = 1, VV_WAV_BLOCK_ALIGN = 2, VV_WAV_BITS = 3, VV_WAV_CHANNELS = 4 };
+VV_API int vv_pcm_adpcm(vv_ctx* ctx, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int samples_per_block,
+                        uint8_t* y, int64_t n_y, void* stream);
+VV_API int vv_wav_decode(vv_ctx* ctx, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, uint8_t* pcm,
+                         int64_t n_pcm, int64_t* status, void* stream);
+
 /* ---- N18 formant-preserving pitch shift: the envelope correction behind the rate conversion that makes the pitch.  x is a
  * request's joined signal (n samples), y what the prosody step made of it (n_f = ceil(n td / tn) samples, tn / td the tempo fraction), z the
  * result: y filtered so that its LPC envelope is x's again.  The arithmetic is pinned by core/audio_processor.py (formant_filters,

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libvvtts_hip.so")
 SOURCES = ["vv_gemm", "vv_attention", "vv_elementwise", "vv_posconv", "vv_vocoder", "vv_vocoder_x3", "vv_mel", "vv_ingest", "vv_edit", "vv_vocos", "vv_noise",
-           "vv_output", "vv_loudness", "vv_limiter", "vv_prosody", "vv_formant", "vv_denoise", "vv_watermark", "vv_flac", "vv_flac_decode", "vv_api"]
+           "vv_output", "vv_loudness", "vv_limiter", "vv_prosody", "vv_formant", "vv_denoise", "vv_watermark", "vv_flac", "vv_flac_decode", "vv_adpcm", "vv_api"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-fvisibility=hidden", "-std=c++17", "-Wno-unused-value", "-Wno-unused-result",
          "-Werror=extra-tokens"]      # `#endif code;` silently drops the code (round 4: an uninitialised epilogue flag)
 EXTRA_FLAGS = {}      # per-file extras (none needed at present)

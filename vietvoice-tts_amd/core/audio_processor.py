@@ -40,27 +40,75 @@ _PCM_GUID = bytes.fromhex("0100000000001000800000aa00389b71")
 _INT_OF_WIDTH = {1: np.int8, 2: np.int16, 4: np.int32}
 
 
-def _decode_wav(data: bytes) -> Tuple[np.ndarray, int, int]:
-    """RIFF/WAVE bytes -> (frames (n_frames, channels) of int8 / int16 / int32, sample width in bytes, rate): the
-    samples pydub's AudioSegment holds after ``from_file`` (see the module docstring for the 8- / 24-bit / float glue)."""
+class WavStatus:
+    """Reason codes of a refused G.711 / IMA ADPCM WAVE clip (N25): one enum for this mirror and csrc/vv_adpcm.hip (VV_WAV_* in include/vvtts.h)."""
+    OK, STEP_INDEX, BLOCK_ALIGN, BITS, CHANNELS = range(5)
+    NAMES = ("ok", "step index above 88", "block alignment", "bits per sample", "more than 2 ADPCM channels")
+
+
+class WavError(ValueError):
+    """``malformed WAVE: <reason> at byte <position>``; ``code`` is a WavStatus, ``position`` a byte offset into the data given."""
+
+    def __init__(self, code: int, position: int, detail: str = ""):
+        self.code, self.position = int(code), int(position)
+        super().__init__(f"malformed WAVE: {detail or WavStatus.NAMES[self.code]} at byte {self.position}")
+
+
+class WavInfo(NamedTuple):
+    tag: int                         # after WAVE_FORMAT_EXTENSIBLE is resolved
+    channels: int
+    rate: int
+    block_align: int
+    bits: int
+    fact: Optional[int]              # frames the fact chunk states, None without one
+    fmt_at: int                      # the byte at which the fmt chunk's body starts
+    data_at: int                     # the byte at which the data chunk's body starts
+    data: bytes
+
+
+def wav_container(data: bytes) -> WavInfo:
+    """Byte parsing only: the RIFF chunks, the fields of ``fmt `` and, for the coded tags 6 / 7 / 0x11 (N25), the refusals that the header
+    alone decides (position = the byte of the offending fmt field)."""
     if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
         raise ValueError("unsupported audio container: only RIFF/WAVE can be decoded in this build (no ffmpeg)")
-    pos, fmt, pcm = 12, None, None
+    pos, fmt, pcm, fact, fmt_at, data_at = 12, None, None, None, 0, 0
     while pos + 8 <= len(data):
         cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
         body = data[pos + 8: pos + 8 + size]
         if cid == b"fmt ":
-            fmt = body
+            fmt, fmt_at = body, pos + 8
         elif cid == b"data":
-            pcm = body
+            pcm, data_at = body, pos + 8
+        elif cid == b"fact" and len(body) >= 4:
+            fact = struct.unpack("<I", body[:4])[0]
         pos += 8 + size + (size & 1)
     if fmt is None or pcm is None or len(fmt) < 16:
         raise ValueError("malformed WAVE file: missing fmt or data chunk")
-    tag, ch, rate, _br, _ba, bits = struct.unpack("<HHIIHH", fmt[:16])
+    tag, ch, rate, _br, align, bits = struct.unpack("<HHIIHH", fmt[:16])
     if tag == 0xFFFE and len(fmt) >= 26:
         tag = struct.unpack("<H", fmt[24:26])[0]
     if ch < 1 or rate < 1:
         raise ValueError("malformed WAVE file: zero channels or rate")
+    if tag in (6, 7) and bits != 8:
+        raise WavError(WavStatus.BITS, fmt_at + 14, f"{bits} bits per sample, G.711 has 8")
+    if tag == 0x11:
+        if bits != 4:
+            raise WavError(WavStatus.BITS, fmt_at + 14, f"{bits} bits per sample, IMA ADPCM has 4")
+        if ch > 2:
+            raise WavError(WavStatus.CHANNELS, fmt_at + 2)
+        if align < 8 * ch or align % (4 * ch):
+            raise WavError(WavStatus.BLOCK_ALIGN, fmt_at + 12, f"block alignment {align}: a multiple of {4 * ch}, at least {8 * ch}")
+    return WavInfo(tag, ch, int(rate), align, bits, fact, fmt_at, data_at, pcm)
+
+
+def _decode_wav(data: bytes) -> Tuple[np.ndarray, int, int]:
+    """RIFF/WAVE bytes -> (frames (n_frames, channels) of int8 / int16 / int32, sample width in bytes, rate): the
+    samples pydub's AudioSegment holds after ``from_file`` (see the module docstring for the 8- / 24-bit / float glue).  Tags 6, 7
+    (G.711) and 0x11 (IMA ADPCM) decode to int16 by audioop's arithmetic (N25, below); pydub hands these to ffmpeg: parity unpinned."""
+    info = wav_container(data)
+    tag, ch, rate, bits, pcm = info.tag, info.channels, info.rate, info.bits, info.data
+    if tag in (6, 7, 0x11):
+        return wav_coded_frames(info), 2, rate
     if tag == 1:
         if bits == 8:
             x, width = (np.frombuffer(pcm, dtype=np.uint8) ^ 0x80).view(np.int8), 1          # audioop.bias(data, 1, -128)
@@ -136,8 +184,9 @@ def _resample_polyphase(x: np.ndarray, src: int, dst: int) -> np.ndarray:
     return resample_poly(x.astype(np.float64), dst // g, src // g).astype(np.float32)
 
 
-OUTPUT_ENCODINGS = ("pcm16", "ulaw", "alaw", "flac")      # ModelConfig.output_encoding; G.711 = WAVE format tags 7 (mu-law) / 6 (A-law);
-                                                          # "flac" = a complete FLAC file, lossless (N15)
+OUTPUT_ENCODINGS = ("pcm16", "ulaw", "alaw", "flac", "adpcm")     # ModelConfig.output_encoding; G.711 = WAVE format tags 7 (mu-law) / 6 (A-law);
+                                                          # "flac" = a complete FLAC file, lossless (N15); "adpcm" = a complete IMA ADPCM WAVE
+                                                          # file, format tag 0x11, 4 bits per sample (N25)
 _WAVE_TAG = {"pcm16": 1, "alaw": 6, "ulaw": 7}
 _DESIGNS = {}
 
@@ -232,7 +281,236 @@ def encode_output(x: np.ndarray, encoding: str, sample_rate: int = 24000, lpc_or
             return np.frombuffer(flac_stream_header(sample_rate, 0), np.uint8).copy()
         frames, lo, hi = flac_encode_frames(pcm, sample_rate, lpc_order=lpc_order)
         return np.concatenate([np.frombuffer(flac_stream_header(sample_rate, pcm.size, lo, hi), np.uint8), frames])
+    if encoding == "adpcm":
+        pcm = _adpcm_pcm(x)
+        return adpcm_wav(adpcm_encode_blocks(pcm, adpcm_samples_per_block(adpcm_block_align(sample_rate))), sample_rate, pcm.size)
     raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
+
+
+# ---------------------------------------------------------------------- N25: IMA ADPCM output; IMA ADPCM and G.711 reference clips
+# The arithmetic IS the specification: the quantiser and predictor of CPython's Modules/audioop.c (lin2adpcm / adpcm2lin,
+# the Intel/DVI reference coder behind the IMA Digital Audio Focus Group's 1992 recommendation), in integers throughout, so this mirror,
+# stdlib audioop and csrc/vv_adpcm.hip agree byte for byte.  Per sample, with the predictor p, the step s = ADPCM_STEPS[index]:
+#     d = x - p; sign = d < 0; d = |d|; vp = s >> 3
+#     d >= s      -> code |= 4, d -= s,      vp += s
+#     d >= s >> 1 -> code |= 2, d -= s >> 1, vp += s >> 1
+#     d >= s >> 2 -> code |= 1,              vp += s >> 2
+#     p = clamp(p -/+ vp, int16); index = clamp(index + ADPCM_INDEX[code], 0, 88)
+# A WAVE block (format tag 0x11, mono) is {int16 first sample, uint8 step index, uint8 0} and the codes of the samples behind the first, LOW
+# nibble first (audioop packs the first code high).  The block header restarts the predictor, so blocks are independent -- and the step
+# index of the header is free: every block tries all 89 and keeps the one with the smallest sum of (x - p)^2 over its real samples (p is what
+# a decoder reconstructs; the padding of the last block, which repeats the last real sample, does not count), the smallest index of equals.
+# The index a conventional encoder would carry over from the block before is one of the 89, so no block is worse than under that encoder.
+ADPCM_STEPS = np.array([7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143,
+                        157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411,
+                        1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493,
+                        10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767], np.int64)
+ADPCM_INDEX = np.array([-1, -1, -1, -1, 2, 4, 6, 8] * 2, np.int64)
+ADPCM_WAVE_TAG = 0x11
+ADPCM_MAX_BLOCK_ALIGN = 4096         # VV_ADPCM_MAX_BLOCK_ALIGN: bytes of the largest block the encoder writes and the decoder follows (8185 samples)
+ADPCM_HEADER_BYTES = 60              # RIFF 12, fmt 8 + 20, fact 8 + 4, data 8
+
+
+def adpcm_block_align(sample_rate: int) -> int:
+    """nBlockAlign of the output: 256 bytes per 11025 Hz of rate (256 at 8 / 16 kHz, 512 at 22.05 / 24 kHz, 1024 at 44.1 / 48 kHz)."""
+    if isinstance(sample_rate, bool) or int(sample_rate) != sample_rate or int(sample_rate) < 1:
+        raise ValueError("ADPCM: a positive integer sample rate is needed")
+    align = 256 * max(1, int(sample_rate) // 11025)
+    if align > ADPCM_MAX_BLOCK_ALIGN:
+        raise ValueError(f"ADPCM: the rate {sample_rate} Hz needs blocks of {align} bytes, more than {ADPCM_MAX_BLOCK_ALIGN}")
+    return align
+
+
+def adpcm_samples_per_block(block_align: int, channels: int = 1) -> int:
+    """wSamplesPerBlock: the header's sample and two per byte behind the headers, per channel."""
+    return (int(block_align) // int(channels) - 4) * 2 + 1
+
+
+def check_adpcm_block(samples_per_block) -> int:
+    """Samples of a mono block the encoder writes: 8 k + 1 (whole 4-byte groups behind the header), 9 ... 8185."""
+    spb = int(samples_per_block)
+    if isinstance(samples_per_block, bool) or spb != samples_per_block or spb < 9 or (spb - 1) % 8 or (spb - 1) // 2 + 4 > ADPCM_MAX_BLOCK_ALIGN:
+        raise ValueError(f"ADPCM: samples_per_block must be 8 k + 1 in 9 ... {(ADPCM_MAX_BLOCK_ALIGN - 4) * 2 + 1}")
+    return spb
+
+
+def _adpcm_pcm(pcm) -> np.ndarray:
+    x = np.asarray(pcm).reshape(-1)
+    if x.dtype != np.int16:
+        raise ValueError("ADPCM: int16 PCM expected")
+    return x
+
+
+def _adpcm_quantise(x: np.ndarray, s0: np.ndarray, index: np.ndarray, n_real: np.ndarray, keep: bool):
+    """lin2adpcm over the last axis of ``x`` [B][T] from the states (s0 [B][1], index [B][K]), all K candidates of all B blocks at once ->
+    (sum of (x - p)^2 over each block's first n_real [B][1] samples as int64 [B][K], the codes uint8 [B][K][T] or None)."""
+    T = x.shape[1]
+    index = index.astype(np.int64)
+    pred = np.broadcast_to(s0.astype(np.int64), index.shape)
+    err = np.zeros(index.shape, np.int64)
+    codes = np.empty(index.shape + (T,), np.uint8) if keep else None
+    for t in range(T):
+        step = ADPCM_STEPS[index]
+        xt = x[:, t:t + 1]
+        d = xt - pred
+        sign = d < 0
+        d = np.abs(d)
+        b2 = d >= step
+        d = d - b2 * step
+        b1 = d >= step >> 1
+        d = d - b1 * (step >> 1)
+        b0 = d >= step >> 2
+        vp = (step >> 3) + b2 * step + b1 * (step >> 1) + b0 * (step >> 2)
+        pred = np.clip(np.where(sign, pred - vp, pred + vp), -32768, 32767)
+        code = b2 * 4 + b1 * 2 + b0 * 1 + sign * 8
+        index = np.clip(index + ADPCM_INDEX[code], 0, 88)
+        err = err + (t < n_real) * (xt - pred) ** 2
+        if keep:
+            codes[..., t] = code
+    return err, codes
+
+
+def adpcm_choose(x, samples_per_block: int):
+    """-> (blocks [B][spb] int64 with the padding, the step index of every block's header [B], its error [B])."""
+    x, spb = _adpcm_pcm(x), check_adpcm_block(samples_per_block)
+    nb = -(-x.size // spb)
+    blocks = np.concatenate([x, np.full(nb * spb - x.size, x[-1] if x.size else 0, np.int16)]).reshape(nb, spb).astype(np.int64)
+    n_real = np.clip(x.size - np.arange(nb) * spb - 1, 0, spb - 1)[:, None]
+    best, best_err = np.zeros(nb, np.int64), np.zeros(nb, np.int64)
+    for lo in range(0, nb, 512):                           # 512 blocks x 89 candidates at a time
+        b = blocks[lo: lo + 512]
+        err = _adpcm_quantise(b[:, 1:], b[:, :1], np.broadcast_to(np.arange(89), (b.shape[0], 89)), n_real[lo: lo + 512], False)[0]
+        best[lo: lo + 512] = err.argmin(axis=1)            # the first of equals = the smallest index
+        best_err[lo: lo + 512] = err.min(axis=1)
+    return blocks, best, best_err
+
+
+def adpcm_encode_blocks(x, samples_per_block: int) -> np.ndarray:
+    """int16 mono PCM -> the uint8 bytes of ceil(n / samples_per_block) blocks of (samples_per_block - 1) / 2 + 4 bytes each (nothing for
+    n = 0): the ``data`` chunk of the WAVE file.  The last block is padded with its last real sample."""
+    blocks, best, _err = adpcm_choose(x, samples_per_block)
+    nb, spb = blocks.shape
+    if nb == 0:
+        return np.zeros(0, np.uint8)
+    codes = _adpcm_quantise(blocks[:, 1:], blocks[:, :1], best[:, None], np.zeros((nb, 1), np.int64), True)[1][:, 0, :]
+    out = np.zeros((nb, (spb - 1) // 2 + 4), np.uint8)
+    out[:, :2] = blocks[:, 0].astype("<i2").view(np.uint8).reshape(nb, 2)
+    out[:, 2] = best
+    out[:, 4:] = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    return out.reshape(-1)
+
+
+def _adpcm_expand(codes: np.ndarray, s0: np.ndarray, index: np.ndarray) -> np.ndarray:
+    """adpcm2lin over the last axis of the 4-bit ``codes`` [S][T] from the states (s0 [S], index [S]) -> int16 [S][T]."""
+    pred, index = s0.astype(np.int64), index.astype(np.int64)
+    out = np.empty(codes.shape, np.int16)
+    for t in range(codes.shape[1]):
+        step, c = ADPCM_STEPS[index], codes[:, t].astype(np.int64)
+        vp = (step >> 3) + ((c >> 2) & 1) * step + ((c >> 1) & 1) * (step >> 1) + (c & 1) * (step >> 2)
+        pred = np.clip(np.where(c & 8, pred - vp, pred + vp), -32768, 32767)
+        index = np.clip(index + ADPCM_INDEX[c], 0, 88)
+        out[:, t] = pred
+    return out
+
+
+def adpcm_block_frames(n_bytes: int, channels: int) -> int:
+    """Frames the first n_bytes of a block hold: the header's, 8 per whole round of 4-byte groups, and what the LAST channel's group of
+    a cut round still holds; 0 when the headers are not whole."""
+    ch = int(channels)
+    if n_bytes < 4 * ch:
+        return 0
+    q, rem = divmod(int(n_bytes) - 4 * ch, 4 * ch)
+    return 1 + 8 * q + 2 * max(0, rem - 4 * (ch - 1))
+
+
+def adpcm_frame_count(n_bytes: int, channels: int, block_align: int, fact: Optional[int] = None) -> int:
+    """Frames of a data chunk of n_bytes: whole blocks, the trailing part of one, at most what a fact chunk states."""
+    full, rem = divmod(int(n_bytes), int(block_align))
+    n = full * adpcm_samples_per_block(block_align, channels) + adpcm_block_frames(rem, channels)
+    return n if fact is None else min(n, int(fact))
+
+
+def adpcm_decode_frames(data: bytes, channels: int, block_align: int, fact: Optional[int] = None, data_at: int = 0) -> np.ndarray:
+    """The ``data`` bytes of an IMA ADPCM WAVE file -> int16 frames [n][channels], audioop.adpcm2lin per block and channel from the header
+    state.  Stereo: one 4-byte header per channel, then groups of 4 bytes (8 samples) alternating left and right.  A step index above 88 in
+    any block whose headers are whole is refused, the first one in file order (position = data_at + the byte of that index)."""
+    ch, ba = int(channels), int(block_align)
+    raw = np.frombuffer(bytes(data), np.uint8)
+    full, rem = divmod(raw.size, ba)
+    nb = full + (rem >= 4 * ch)
+    n = adpcm_frame_count(raw.size, ch, ba, fact)
+    if nb == 0:
+        return np.zeros((0, ch), np.int16)
+    blocks = np.zeros((nb, ba), np.uint8)
+    blocks.reshape(-1)[: min(raw.size, nb * ba)] = raw[: nb * ba]
+    head = blocks[:, : 4 * ch].reshape(nb, ch, 4)
+    bad = np.argwhere(head[:, :, 2] > 88)
+    if bad.size:
+        b, c = (int(v) for v in bad[0])
+        raise WavError(WavStatus.STEP_INDEX, data_at + b * ba + 4 * c + 2)
+    s0 = np.ascontiguousarray(head[:, :, :2]).view("<i2").reshape(nb * ch)
+    body = blocks[:, 4 * ch:].reshape(nb, -1, ch, 4).transpose(0, 2, 1, 3).reshape(nb * ch, -1)
+    codes = np.stack([body & 15, body >> 4], axis=-1).reshape(nb * ch, -1)                    # low nibble first
+    pcm = np.concatenate([s0[:, None].astype(np.int16), _adpcm_expand(codes, s0, head[:, :, 2].reshape(-1))], axis=1)
+    return np.ascontiguousarray(pcm.reshape(nb, ch, -1).transpose(0, 2, 1).reshape(-1, ch)[:n])
+
+
+def adpcm_decode_blocks(data, samples_per_block: int, n: Optional[int] = None) -> np.ndarray:
+    """The inverse of adpcm_encode_blocks: mono blocks -> int16, the first n samples of them (None = all, padding included)."""
+    spb = check_adpcm_block(samples_per_block)
+    return adpcm_decode_frames(np.asarray(data, np.uint8).tobytes(), 1, (spb - 1) // 2 + 4, n)[:, 0]
+
+
+def adpcm_wav(blocks, sample_rate: int, n_samples: Optional[int] = None) -> np.ndarray:
+    """The blocks of adpcm_encode_blocks at ``sample_rate`` -> the uint8 bytes of the complete mono WAVE file: format tag 0x11, 4 bits,
+    nBlockAlign = adpcm_block_align(rate), cbSize 2 and wSamplesPerBlock, a fact chunk with the true sample count (None = the blocks' own,
+    padding included: what a collected stream knows), the data chunk."""
+    payload = np.asarray(blocks, np.uint8).reshape(-1).tobytes()
+    ba = adpcm_block_align(sample_rate)
+    spb = adpcm_samples_per_block(ba)
+    if len(payload) % ba:
+        raise ValueError(f"ADPCM: whole blocks of {ba} bytes are needed at {sample_rate} Hz")
+    n = len(payload) // ba * spb if n_samples is None else int(n_samples)
+    if not len(payload) // ba * spb - spb < n <= len(payload) // ba * spb and not (n == 0 and not payload):
+        raise ValueError("ADPCM: the sample count does not end in the last block")
+    fmt = struct.pack("<HHIIHHHH", ADPCM_WAVE_TAG, 1, int(sample_rate), int(sample_rate) * ba // spb, ba, 4, 2, spb)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"fact" + struct.pack("<II", 4, n) + b"data" + struct.pack("<I", len(payload)) + payload
+    return np.frombuffer(b"RIFF" + struct.pack("<I", len(body)) + body, np.uint8).copy()
+
+
+def ulaw2lin(codes) -> np.ndarray:
+    """uint8 G.711 mu-law -> int16, audioop.ulaw2lin(data, 2) in closed form for all 256 codes."""
+    u = ~np.asarray(codes, np.uint8).astype(np.int32) & 0xFF
+    t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4)
+    return np.where(u & 0x80, 0x84 - t, t - 0x84).astype(np.int16)
+
+
+def alaw2lin(codes) -> np.ndarray:
+    """uint8 G.711 A-law -> int16, audioop.alaw2lin(data, 2) in closed form for all 256 codes."""
+    a = np.asarray(codes, np.uint8).astype(np.int32) ^ 0x55
+    seg = (a & 0x70) >> 4
+    t = ((a & 0x0F) << 4) + np.where(seg == 0, 8, 0x108)
+    t = np.where(seg > 1, t << np.maximum(seg - 1, 0), t)
+    return np.where(a & 0x80, t, -t).astype(np.int16)
+
+
+def wav_coded_frame_count(info: "WavInfo") -> int:
+    """Frames a coded clip (tag 6, 7 or 0x11) decodes to: what its bytes hold, at most what a fact chunk states."""
+    if info.tag == ADPCM_WAVE_TAG:
+        return adpcm_frame_count(len(info.data), info.channels, info.block_align, info.fact)
+    n = len(info.data) // info.channels
+    return n if info.fact is None else min(n, info.fact)
+
+
+def wav_coded_frames(info: "WavInfo") -> np.ndarray:
+    """The int16 frames [n][channels] of a WAVE clip with tag 7 (mu-law), 6 (A-law) or 0x11 (IMA ADPCM): what csrc/vv_adpcm.hip
+    (vv_wav_decode) writes on the device.  G.711 has one code per sample; a fact chunk that states fewer frames cuts either."""
+    ch = info.channels
+    if info.tag == ADPCM_WAVE_TAG:
+        return adpcm_decode_frames(info.data, ch, info.block_align, info.fact, info.data_at)
+    codes = np.frombuffer(info.data, np.uint8)
+    n = codes.size // ch if info.fact is None else min(codes.size // ch, info.fact)
+    return np.ascontiguousarray((ulaw2lin if info.tag == 7 else alaw2lin)(codes[: n * ch]).reshape(n, ch))
 
 
 # ---------------------------------------------------------------------- N15: FLAC output (RFC 9639), fixed predictors, mono, 16 bits
@@ -1922,6 +2200,13 @@ class AudioProcessor:
         return flat.tobytes()
 
     @staticmethod
+    def _adpcm_bytes(flat: np.ndarray) -> bytes:
+        """The complete IMA ADPCM WAVE file the output stage made (N25), as it is; raw blocks (a collected stream) need adpcm_wav first."""
+        if flat.dtype != np.uint8 or flat.size < ADPCM_HEADER_BYTES or flat[:4].tobytes() != b"RIFF":
+            raise ValueError("adpcm audio must be the uint8 bytes of an IMA ADPCM WAVE file (encode_output(x, 'adpcm', rate), or adpcm_wav of a stream's blocks)")
+        return flat.tobytes()
+
+    @staticmethod
     def save_audio(audio: np.ndarray, file_path: str, sample_rate: int, encoding: str = "pcm16") -> None:
         if audio.size == 0:
             raise ValueError("Cannot save empty audio.")
@@ -1929,9 +2214,9 @@ class AudioProcessor:
             raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
         Path(file_path).parent.mkdir(parents=True, exist_ok=True)
         flat = np.asarray(audio).reshape(-1)
-        if encoding == "flac":                       # already a complete file (N15): written as it is
+        if encoding in ("flac", "adpcm"):            # already a complete file (N15, N25): written as it is
             with open(file_path, "wb") as fh:
-                fh.write(AudioProcessor._flac_bytes(flat))
+                fh.write(AudioProcessor._flac_bytes(flat) if encoding == "flac" else AudioProcessor._adpcm_bytes(flat))
             return
         if encoding != "pcm16":                      # already companded (uint8) by the output stage
             if flat.dtype != np.uint8:
@@ -1957,6 +2242,8 @@ class AudioProcessor:
                 raise ValueError(f"output_encoding must be one of {list(OUTPUT_ENCODINGS)}")
             if encoding == "flac":                   # not a WAVE file: the FLAC file the output stage made, as it is
                 return AudioProcessor._flac_bytes(np.asarray(audio).reshape(-1))
+            if encoding == "adpcm":                  # the IMA ADPCM WAVE file the output stage made (N25), as it is
+                return AudioProcessor._adpcm_bytes(np.asarray(audio).reshape(-1))
             return AudioProcessor._g711_wav(np.asarray(audio).reshape(-1), sample_rate, encoding)
         buf = io.BytesIO()
         flat = np.asarray(audio).reshape(-1).astype("<i2")
@@ -2072,6 +2359,8 @@ class OutputStream:
     def __init__(self, src: int, dst, encoding: str = "pcm16", resample=None, encode=None):
         if encoding == "flac":
             raise ValueError("OutputStream: FLAC frames span blocks; put a FlacStream behind an OutputStream with encoding 'pcm16'")
+        if encoding == "adpcm":
+            raise ValueError("OutputStream: ADPCM blocks span blocks; put an AdpcmStream behind an OutputStream with encoding 'pcm16'")
         self.rate = None if dst is None or int(dst) == int(src) else int(dst)
         self.encoding = encoding
         if self.rate is not None:
@@ -2152,6 +2441,33 @@ class FlacStream:
     def flush(self) -> np.ndarray:
         rest, self.left = self.left, np.zeros(0, np.int16)
         return self._out(rest, True)
+
+
+class AdpcmStream:
+    """IMA ADPCM for a STREAM of final int16 blocks at the output rate (``synthesize_stream``), behind the OutputStream.
+    Blocks are independent, so it carries only the samples that do not fill a block yet: ``push`` returns the bytes of every complete
+    block, ``flush`` pads the rest and returns the last one.  The blocks come raw, as uint8 without a RIFF header (as the G.711 stream's
+    codes do): their concatenation equals the ``data`` chunk of the file ``synthesize`` returns, byte for byte, and ``adpcm_wav`` puts a
+    header in front of them.  ``encode(pcm)`` returns the blocks' bytes: the host mirror, or the device kernel
+    (HipSynth.output_stream_backends)."""
+
+    def __init__(self, sample_rate: int, encode=None):
+        self.spb = adpcm_samples_per_block(adpcm_block_align(sample_rate))
+        self._encode = encode or (lambda pcm: adpcm_encode_blocks(pcm, self.spb))
+        self.left = np.zeros(0, np.int16)
+
+    def _out(self, pcm: np.ndarray) -> np.ndarray:
+        return np.asarray(self._encode(pcm), np.uint8).reshape(-1) if pcm.size else np.zeros(0, np.uint8)
+
+    def push(self, block: np.ndarray) -> np.ndarray:
+        have = np.concatenate([self.left, _adpcm_pcm(block)])
+        whole = have.size - have.size % self.spb
+        self.left = have[whole:]
+        return self._out(have[:whole])
+
+    def flush(self) -> np.ndarray:
+        rest, self.left = self.left, np.zeros(0, np.int16)
+        return self._out(rest)
 
 
 class LimiterStream:

@@ -102,7 +102,9 @@ class ModelConfig:
                                             # function); "device" = vv_join_chunks in HBM, bit for bit the same samples, one copy of the final bytes
     output_sample_rate: Optional[int] = None   # None = sample_rate; else the output is rate-converted (band-limited polyphase FIR, vv_pcm_resample)
     output_encoding: str = "pcm16"          # "pcm16" | "ulaw" | "alaw" (G.711, uint8 codes, vv_pcm_encode) | "flac" (a FLAC file, lossless, vv_pcm_flac: N15).  A rate or an encoding runs on the
-                                            # device on the HIP engine, through the host mirrors on injected sessions
+                                            # device on the HIP engine, through the host mirrors on injected sessions.
+                                            # "adpcm" (N25, vv_pcm_adpcm): an IMA ADPCM WAVE file, format tag 0x11, 4 bits per sample, blocks of 256 bytes per
+                                            # 11025 Hz of the output rate; synthesize_stream yields the raw blocks (adpcm_wav makes a file of them)
     flac_lpc_order: int = 0                 # highest LPC order the FLAC encoder tries per frame, 1 ... 12 (vv_pcm_flac_lpc): smaller files on
                                             # tonal material, the same samples back.  0 = fixed predictors only, the encoder of N15 byte for byte.  Needs
                                             # output_encoding "flac"

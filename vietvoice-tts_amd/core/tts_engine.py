@@ -451,7 +451,7 @@ class TTSEngine:
     def synthesize_stream(self, text: str, gender: Optional[str] = None, group: Optional[str] = None, area: Optional[str] = None,
                           emotion: Optional[str] = None, sample_iteration: Optional[int] = None,
                           reference_audio: Optional[str] = None, reference_text: Optional[str] = None, chunks_per_step: int = 1):
-        """Generator of PCM blocks (int16 at the output rate, uint8 G.711 codes, or the bytes of a FLAC stream: N15): audio is emitted as soon as a group of ``chunks_per_step``
+        """Generator of PCM blocks (int16 at the output rate, uint8 G.711 codes, the bytes of a FLAC stream: N15, or raw IMA ADPCM blocks: N25): audio is emitted as soon as a group of ``chunks_per_step``
         chunks is synthesised instead of after the whole text (the reference buffers everything, api/app.py:59-65).
         Overlap-save: the improved cross-fade only rewrites the last ``cross_fade_duration`` of what has been joined
         so far (audio_processor.py:122-192), so everything before that tail is final and can be yielded.  The joiner
@@ -487,7 +487,7 @@ class TTSEngine:
                 # device noise: ONE call serial for the whole stream, chunk c under it whatever group it is synthesised in
                 keys = self.model_session_manager.take_noise_keys(len(inputs_list)) if self._device_noise() else None
             self._last_plan = [int(i[2][0]) for i in inputs_list]
-            from .audio_processor import CrossfadeStream, FlacStream, LimiterStream, OutputStream
+            from .audio_processor import AdpcmStream, CrossfadeStream, FlacStream, LimiterStream, OutputStream
             cfg, eng = self.config, self.model_session_manager.engine
             joiner = CrossfadeStream(len(inputs_list), cfg.cross_fade_duration, cfg.sample_rate)
             # The stages behind the join, in order; each carries the state it needs (on the HIP engine its back end is the device kernel,
@@ -499,12 +499,13 @@ class TTSEngine:
                 stages.append(LimiterStream(cfg.sample_rate, cfg.output_peak_dbfs, cfg.output_limiter, backend))
             if rate is not None or enc != "pcm16":             # N10: the filter's position and history
                 resample, encode = eng.output_stream_backends(cfg.sample_rate, rate, enc) if eng is not None else (None, None)
-                if enc != "flac":
+                if enc not in ("flac", "adpcm"):
                     stages.append(OutputStream(cfg.sample_rate, rate, enc, resample, encode))
-                else:                                          # N15: frames are independent -- a FlacStream behind the rate conversion
+                else:                                          # N15, N25: frames / blocks are independent -- their stream behind the rate conversion
                     if rate is not None:
                         stages.append(OutputStream(cfg.sample_rate, rate, "pcm16", resample, None))
-                    stages.append(FlacStream(self.output_rate, encode, lpc_order=cfg.flac_lpc_order))
+                    stages.append(FlacStream(self.output_rate, encode, lpc_order=cfg.flac_lpc_order) if enc == "flac" else
+                                  AdpcmStream(self.output_rate, encode))
 
             def through(block, stages):                        # handed over as contiguous int16, which PCM blocks are already
                 for stage in stages:

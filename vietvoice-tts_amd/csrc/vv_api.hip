@@ -13,7 +13,7 @@
 #include <vector>
 #include "vv_kernels.h"
 
-#define VV_VERSION_STR "vvtts-hip 0.14 (gfx950)"
+#define VV_VERSION_STR "vvtts-hip 0.15 (gfx950)"
 
 namespace {
 std::string g_create_error;
@@ -1170,6 +1170,81 @@ int vv_flac_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_
     Prof p(c, VV_PROF_ELEMWISE, 40.0 * (double)P, 2.0 * (double)n_bytes + 8.0 * (double)P + (double)n_pcm, st);
     KCHK(c, vvk_flac_decode(data, (long long)n_bytes, (const long long*)rows, R, (const long long*)lay, (long long)F, (long long)S, (long long)P, maxch,
                             (void*)ws, pcm, (long long)n_pcm, (long long*)info2, ws2, st, &m__));
+    return 0;
+}
+
+// N25: IMA ADPCM blocks of the final PCM; IMA ADPCM and G.711 clips into the PCM vv_ingest_pcm reads.  The rows come in host memory too.
+int vv_pcm_adpcm(vv_ctx* c, const int16_t* x, int64_t n_x, const int64_t* rows, const int64_t* rows_host, int R, int spb, uint8_t* y, int64_t n_y,
+                 void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_x < 0 || n_y < 0) return c->fail(-22, "vv_pcm_adpcm: bad sizes (1 <= R <= 65535)");
+    if (spb < 9 || (spb - 1) % 8 || (spb - 1) / 2 + 4 > VV_ADPCM_MAX_BLOCK_ALIGN)
+        return c->fail(-22, "vv_pcm_adpcm: samples_per_block is 8 k + 1 in 9 ... %d", (VV_ADPCM_MAX_BLOCK_ALIGN - 4) * 2 + 1);
+    if (int e = check_ptrs(c, "vv_pcm_adpcm", {{"x", x, 2}, {"rows", rows, 8}, {"rows_host", rows_host, 8}, {"y", y, 8}})) return e;
+    if (spans_overlap(x, 2ull * n_x, y, (uint64_t)n_y)) return c->fail(-22, "vv_pcm_adpcm: y overlaps x");
+    const int64_t ba = (spb - 1) / 2 + 4;
+    int64_t max_blocks = 0, total = 0, at = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 3 * (size_t)r;
+        if (q[1] < 1 || !fits(q[0], q[1], n_x)) return c->fail(-22, "vv_pcm_adpcm: row %d does not fit the %lld samples of x (n >= 1)", r, (long long)n_x);
+        const int64_t blocks = (q[1] + spb - 1) / spb;
+        if (q[2] < 0 || q[2] % 4 || q[2] > n_y || blocks > (n_y - q[2]) / ba)
+            return c->fail(-22, "vv_pcm_adpcm: row %d: %lld blocks of %lld bytes at dst_off %lld (a multiple of 4) do not fit the %lld bytes of y", r,
+                           (long long)blocks, (long long)ba, (long long)q[2], (long long)n_y);
+        if (q[2] < at) return c->fail(-22, "vv_pcm_adpcm: row %d: the rows' blocks lie in ascending order on y, disjoint", r);
+        at = q[2] + blocks * ba;
+        if (blocks > max_blocks) max_blocks = blocks;
+        total += q[1];
+    }
+    Prof p(c, VV_PROF_ELEMWISE, 40.0 * 90.0 * (double)total, 2.5 * (double)total, st);
+    KCHK(c, vvk_pcm_adpcm(x, (long long)n_x, (const long long*)rows, R, spb, (long long)max_blocks, y, (long long)n_y, st, &m__));
+    return 0;
+}
+
+int vv_wav_decode(vv_ctx* c, const uint8_t* data, int64_t n_bytes, const int64_t* rows, const int64_t* rows_host, int R, uint8_t* pcm, int64_t n_pcm,
+                  int64_t* status, void* stream) {
+    if (!c) return -22;
+    hipStream_t st = enter(c, stream);
+    if (R < 1 || R > 65535 || n_bytes < 0 || n_pcm < 0) return c->fail(-22, "vv_wav_decode: bad sizes (1 <= R <= 65535)");
+    if (int e = check_ptrs(c, "vv_wav_decode", {{"data", data, 16}, {"rows", rows, 8}, {"rows_host", rows_host, 8}, {"pcm", pcm, 16}, {"status", status, 8}}))
+        return e;
+    int64_t at = 0, max_heads = 0, max_codes = 0, samples = 0;
+    for (int r = 0; r < R; ++r) {
+        const int64_t* q = rows_host + 8 * (size_t)r;
+        const int64_t tag = q[2], ch = q[3], ba = q[4], frames = q[5];
+        if (q[0] % 16 || !fits(q[0], q[1], n_bytes)) return c->fail(-22, "vv_wav_decode: row %d: a clip at a 16-byte aligned offset inside data is needed", r);
+        if (ch < 1 || ch > 65535 || frames < 0) return c->fail(-22, "vv_wav_decode: row %d: channels in 1 ... 65535 and frames >= 0 are needed", r);
+        int64_t holds = 0;
+        if (tag == VV_WAVE_TAG_ADPCM) {
+            if (ch > 2 || ba < 8 * ch || ba % (4 * ch) || ba > 65535)
+                return c->fail(-22, "vv_wav_decode: row %d: IMA ADPCM has 1 or 2 channels and a block alignment that is a multiple of 4 x channels, at least 8 x channels", r);
+            const int64_t rem = q[1] % ba;
+            if (rem >= 4 * ch) {
+                const int64_t m = (rem - 4 * ch) % (4 * ch) - 4 * (ch - 1);
+                holds = 1 + 8 * ((rem - 4 * ch) / (4 * ch)) + 2 * (m > 0 ? m : 0);
+            }
+            holds += q[1] / ba * ((ba / ch - 4) * 2 + 1);
+            const int64_t heads = (q[1] / ba + (rem >= 4 * ch ? 1 : 0)) * ch;
+            if (heads > max_heads) max_heads = heads;
+        } else if (tag == VV_WAVE_TAG_ALAW || tag == VV_WAVE_TAG_ULAW) {
+            holds = q[1] / ch;
+            if (frames * ch > max_codes) max_codes = frames * ch;
+        } else {
+            return c->fail(-22, "vv_wav_decode: row %d: format tag %lld (6, 7 and 17 are decoded)", r, (long long)tag);
+        }
+        if (frames > holds) return c->fail(-22, "vv_wav_decode: row %d: %lld frames, the bytes hold %lld", r, (long long)frames, (long long)holds);
+        if (q[6] < at || q[6] % 16 || q[6] > n_pcm || frames > (n_pcm - q[6]) / (2 * ch))
+            return c->fail(-22, "vv_wav_decode: row %d does not fit the %lld bytes of pcm, 16-byte aligned, in ascending order", r, (long long)n_pcm);
+        at = q[6] + frames * ch * 2;
+        samples += frames * ch;
+    }
+    if (spans_overlap(data, (uint64_t)n_bytes, pcm, (uint64_t)n_pcm) || spans_overlap(status, 16ull * R, pcm, (uint64_t)n_pcm) ||
+        spans_overlap(status, 16ull * R, data, (uint64_t)n_bytes))
+        return c->fail(-22, "vv_wav_decode: data, pcm and status overlap");
+    Prof p(c, VV_PROF_ELEMWISE, 20.0 * (double)samples, (double)n_bytes + 2.0 * (double)samples, st);
+    KCHK(c, vvk_wav_decode(data, (long long)n_bytes, (const long long*)rows, R, (long long)max_heads, (long long)max_codes, pcm, (long long)n_pcm,
+                           (long long*)status, st, &m__));
     return 0;
 }
 

@@ -158,6 +158,13 @@ int vvk_flac_index(const uint8_t* data, long long n_bytes, const long long* rows
 int vvk_flac_decode(const uint8_t* data, long long n_bytes, const long long* rows, int R, const long long* lay, long long total_frames,
                     long long total_samples, long long n_plane, int max_channels, void* ws, uint8_t* pcm, long long n_pcm, long long* info2, void* ws2,
                     hipStream_t st, const char** err);
+// N25 IMA ADPCM output and ADPCM / G.711 input (vv_adpcm.hip).  Encoder rows R x 3 {src_off, n, dst_off in bytes}, max_blocks = the largest
+// ceil(n / spb).  Decoder rows R x 8 {data byte offset, n_bytes, tag, channels, block align, frames, pcm byte offset, 0}; max_heads = the
+// largest blocks x channels of an ADPCM clip, max_codes = the largest frames x channels of a G.711 clip (0 = none of that kind)
+int vvk_pcm_adpcm(const int16_t* x, long long n_x, const long long* rows, int R, int spb, long long max_blocks, uint8_t* y, long long n_y,
+                  hipStream_t st, const char** err);
+int vvk_wav_decode(const uint8_t* data, long long n_data, const long long* rows, int R, long long max_heads, long long max_codes, uint8_t* pcm,
+                   long long n_pcm, long long* status, hipStream_t st, const char** err);
 // N6 Vocos decoder (vv_vocos.hip): generated-frame counts, the embed conv's im2col operand, the ISTFT spectrum and overlap-add
 int vvk_vocos_lens(const int* seq_len, const int* ref_len, int* lens, int B, int N, int T_max, hipStream_t st, const char** err);
 int vvk_vocos_im2col(const float* x, int B, int N, int M, const int* ref_len, const int* seq_len, int T_max, int k, float* out, int ld_out,

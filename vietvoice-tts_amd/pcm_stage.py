@@ -421,6 +421,48 @@ def plan_flac_decode(lay, clips, n_pcm: int):
     return full, F, P
 
 
+def plan_adpcm(rows, n_x: int, samples_per_block, n_y: Optional[int] = None):
+    """vv_pcm_adpcm's rows (src_off, n, dst_off in bytes), ascending and disjoint on y -> (samples_per_block, rows, n_y: None = what the
+    rows need, the largest number of blocks of a row)."""
+    from .core.audio_processor import check_adpcm_block
+    spb = check_adpcm_block(samples_per_block)
+    ba = (spb - 1) // 2 + 4
+    rows = _int_rows("pcm_adpcm", rows, (3,), "3 entries {src_off, n, dst_off}")
+    at, most = 0, 0
+    for so, n, do in rows:
+        blocks = -(-n // spb)
+        if so < 0 or n < 1 or so + n > n_x or do < at or do % 4:
+            raise ValueError(f"pcm_adpcm: row {[so, n, do]} does not fit the {n_x} samples of x (n >= 1), or its blocks do not lie in ascending "
+                             f"order on y at a multiple of 4 bytes")
+        at, most = do + blocks * ba, max(most, blocks)
+    if n_y is not None and at > n_y:
+        raise ValueError(f"pcm_adpcm: y holds {n_y} bytes, {at} are needed")
+    return spb, rows, at if n_y is None else int(n_y), most
+
+
+def plan_wav_decode(rows, n_bytes: int, n_pcm: int):
+    """vv_wav_decode's rows {data byte offset, n_bytes, tag, channels, block align, frames, pcm byte offset}, validated -> 8-entry rows."""
+    from .core.audio_processor import ADPCM_WAVE_TAG, adpcm_frame_count
+    rows = _int_rows("wav_decode", rows, (7,), "7 entries {data byte offset, n_bytes, tag, channels, block align, frames, pcm byte offset}")
+    at = 0
+    for r in rows:
+        off, n, tag, ch, ba, frames, po = r
+        if off < 0 or off % 16 or n < 0 or off + n > n_bytes or not 1 <= ch <= 65535 or frames < 0:
+            raise ValueError(f"wav_decode: row {r} does not fit the {n_bytes} bytes of data (16-byte aligned clips)")
+        if tag == ADPCM_WAVE_TAG:
+            if ch > 2 or ba < 8 * ch or ba % (4 * ch) or ba > 65535:
+                raise ValueError(f"wav_decode: row {r}: IMA ADPCM has 1 or 2 channels and a block alignment that is a multiple of 4 x channels")
+            holds = adpcm_frame_count(n, ch, ba)
+        elif tag in (6, 7):
+            holds = n // ch
+        else:
+            raise ValueError(f"wav_decode: row {r}: format tag 6, 7 or 17")
+        if frames > holds or po < at or po % 16 or po + frames * ch * 2 > n_pcm:
+            raise ValueError(f"wav_decode: row {r}: {frames} frames do not fit its bytes ({holds}) or the {n_pcm} bytes of pcm (16-byte aligned, ascending)")
+        at = po + frames * ch * 2
+    return [r + [0] for r in rows]
+
+
 def plan_finish(R: int, loudness=None, limiter=None, pitch=None, tempo=None):
     """finish_output's options, each one value or one per request, normalised once -> (pitch list, tempo list: both None when no request
     has either; groups [(limiter mode or None, requests, their loudness targets)] in calling order: None = one pcm_loudness call)."""
@@ -930,6 +972,75 @@ class PcmStage:
             out.append(np.concatenate([np.frombuffer(flac_stream_header(sample_rate, n, lo, hi), np.uint8), data]))
         return out
 
+    # ------------------------------------------------------------------ IMA ADPCM output, ADPCM / G.711 input (N25)
+    def pcm_adpcm(self, x: torch.Tensor, rows, samples_per_block: int, n_y: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """IMA ADPCM blocks of R final signals in one call (vv_pcm_adpcm), byte for byte
+        core.audio_processor.adpcm_encode_blocks.  x int16 flat on the device; rows = HOST rows (src_off, n, dst_off in bytes, a multiple of
+        4, ascending): x[src_off, +n) becomes ceil(n / samples_per_block) blocks of (samples_per_block - 1) / 2 + 4 bytes at dst_off.
+        -> y, the uint8 device buffer [n_y] (out = an existing one).  The size is the host's to know: nothing is read back.  The rows are
+        validated here; the call never synchronises."""
+        assert x.is_cuda and x.dtype == torch.int16 and x.is_contiguous() and x.dim() == 1
+        spb, rows, n_y, _most = plan_adpcm(rows, x.numel(), samples_per_block, n_y if out is None else out.numel())
+        y = self._out(out, n_y, torch.uint8, floor=8)
+        rows_d, rows_h = self._upload(rows)
+        self._call(self.lib.vv_pcm_adpcm, x.data_ptr(), x.numel(), rows_d.data_ptr(), rows_h.data_ptr(), len(rows), spb, y.data_ptr(), y.numel())
+        return y[:n_y]
+
+    def wav_decode(self, data: torch.Tensor, rows, pcm: torch.Tensor) -> torch.Tensor:
+        """vv_wav_decode: the coded data chunks of R G.711 / IMA ADPCM WAVE clips in ``data`` (uint8 on the device, each clip
+        16-byte aligned) into ``pcm`` (uint8 on the device) as the interleaved int16 frames vv_ingest_pcm reads, sample for sample
+        core.audio_processor.wav_coded_frames.  rows = HOST rows {data byte offset, n_bytes, tag, channels, block align, frames, pcm byte
+        offset}.  -> status R x 2 int64 on the device {reason, byte inside the clip's data}.  The rows are validated here; the call never
+        synchronises."""
+        assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
+        assert pcm.is_cuda and pcm.dtype == torch.uint8 and pcm.is_contiguous() and pcm.dim() == 1
+        rows = plan_wav_decode(rows, data.numel(), pcm.numel())
+        rows_d, rows_h = self._upload(rows)
+        status = torch.empty((len(rows), 2), dtype=torch.int64, device=self.device)
+        self._call(self.lib.vv_wav_decode, data.data_ptr(), data.numel(), rows_d.data_ptr(), rows_h.data_ptr(), len(rows), pcm.data_ptr(), pcm.numel(),
+                   status.data_ptr())
+        return status
+
+    def wav_clips(self, infos, pcm_offsets=None):
+        """The coded WAVE clips ``infos`` (core.audio_processor.WavInfo of tag 6, 7 or 0x11) -> their PCM on the device, without a decoded
+        sample crossing the bus: one upload of the data chunks, vv_wav_decode, one small readback of the status (16 R bytes).
+        -> (pcm uint8 on the device, [per clip: (byte offset, frames, 2, rate, channels) or the WavError the mirror would raise]).  A
+        refused clip does not disturb the others.  ``pcm_offsets(sizes) -> (buffer, offsets)`` lets the caller place the clips (16-byte
+        aligned) in a buffer it shares with other PCM."""
+        from .core.audio_processor import WavError, wav_coded_frame_count
+        parts, rows, pos = [], [], 0
+        for fi in infos:
+            n = len(fi.data)
+            rows.append([pos, n, fi.tag, fi.channels, fi.block_align, wav_coded_frame_count(fi), 0])
+            parts.append(fi.data + b"\0" * (-n % 16))
+            pos += len(parts[-1])
+        sizes = [r[5] * r[3] * 2 for r in rows]
+        if pcm_offsets is None:
+            offs, end = _place(sizes, 16)
+            pcm = torch.empty((max(-(-end // 16) * 16, 16),), dtype=torch.uint8, device=self.device)
+        else:
+            pcm, offs = pcm_offsets(sizes)
+        for r, o in zip(rows, offs):
+            r[6] = o
+        buf = torch.frombuffer(bytearray(b"".join(parts) + b"\0" * 16), dtype=torch.uint8).to(self.device)
+        status = self.wav_decode(buf, rows, pcm).cpu().tolist()
+        out = [WavError(code, fi.data_at + byte) if code else (r[6], r[5], 2, fi.rate, fi.channels) for (code, byte), fi, r in zip(status, infos, rows)]
+        return pcm, out
+
+    def _adpcm_files(self, buf: torch.Tensor, offs, lens, sample_rate: int):
+        """The last step of finish_output with encoding "adpcm": one vv_pcm_adpcm call over the requests and ONE copy of the blocks -- their
+        sizes are the host's to know; it puts each request's RIFF header in front, with the true sample count.  An empty request is a
+        header alone."""
+        import numpy as np
+        from .core.audio_processor import adpcm_block_align, adpcm_samples_per_block, adpcm_wav
+        ba = adpcm_block_align(sample_rate)
+        spb = adpcm_samples_per_block(ba)
+        sizes = [-(-n // spb) * ba for n in lens]
+        out_offs, end = _place(sizes)
+        rows = [[o, n, do] for o, n, do in zip(offs, lens, out_offs) if n > 0]
+        host = self.pcm_adpcm(buf, rows, spb, n_y=end).cpu().numpy() if rows else np.zeros(0, np.uint8)
+        return [adpcm_wav(host[do: do + nb], sample_rate, n) for do, nb, n in zip(out_offs, sizes, lens)]
+
     def finish_output(self, pcm: torch.Tensor, plans, cross_fade_duration: float, sample_rate: int, rate: Optional[int] = None,
                       encoding: str = "pcm16", loudness=None, peak_dbfs: float = -1.0, limiter=None, pitch=None, tempo=None, flac_lpc_order: int = 0,
                       formants=None, denoise=None, denoise_bias=None, watermark=None, watermark_key=None, watermark_strength: float = 0.2):
@@ -955,7 +1066,9 @@ class PcmStage:
         new is called.  A request with a payload goes through pcm_watermark under watermark_key (0 ... 2^64 - 1; a payload without a key is
         refused) at watermark_strength, directly behind pitch and tempo (and formants) and before the loudness step, into a new buffer: the
         loudness gain, the peak ceiling and the limiter's promise hold for what is heard, and the detector does not mind a constant gain.
-        -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC file."""
+        encoding "adpcm" (N25): the final PCM goes through pcm_adpcm; the blocks' sizes follow from the lengths, so there is no size
+        readback, and each request comes back as a complete IMA ADPCM WAVE file (60 header bytes made on the host, then the blocks).
+        -> a list of R numpy arrays: int16 at ``rate`` (None = sample_rate), uint8 G.711 codes, or the uint8 bytes of a FLAC or ADPCM file."""
         from .core.audio_processor import check_flac_lpc_order, resample_len
         if check_flac_lpc_order(flac_lpc_order) and encoding != "flac":
             raise ValueError("finish_output: flac_lpc_order belongs to the encoding 'flac'")
@@ -988,6 +1101,8 @@ class PcmStage:
             buf, offs, lens = (self.pcm_resample(buf, rows, sample_rate, rate, n_y=end) if end else buf[:0]), out_offs, out_lens
         if encoding == "flac":             # N15: variable-length output -- the frames' total comes back first, then exactly that many bytes
             return self._flac_files(buf, offs, lens, int(sample_rate) if rate is None else int(rate), flac_lpc_order)
+        if encoding == "adpcm":            # N25: blocks of a size the host knows -- one copy, then each request's RIFF header in front
+            return self._adpcm_files(buf, offs, lens, int(sample_rate) if rate is None else int(rate))
         if encoding != "pcm16":
             out_offs, end = _place(lens)
             rows = [[o, n, do] for o, n, do in zip(offs, lens, out_offs)]
@@ -1000,7 +1115,7 @@ class PcmStage:
         """(resample, encode) callables for core.audio_processor.OutputStream on this device: host blocks go up in pieces of at most
         ``max_upload`` samples (0.5 MB), through vv_pcm_resample / vv_pcm_encode, and come back.  With encoding "flac" the second one is
         the ``encode(pcm, frame0, last[, lpc_order])`` of core.audio_processor.FlacStream (vv_pcm_flac, vv_pcm_flac_lpc), which sits behind
-        the OutputStream."""
+        the OutputStream; with "adpcm" it is the ``encode(pcm)`` of core.audio_processor.AdpcmStream (vv_pcm_adpcm), in the same place."""
         import numpy as np
 
         def up_(x):
@@ -1027,5 +1142,13 @@ class PcmStage:
             y, info = self.pcm_flac(up_(pcm), [[0, pcm.size, int(frame0), 1 if last else 0]], sample_rate if rate is None else rate, lpc_order)
             return y[: int(info[1, 0])].cpu().numpy()
 
+        def adpcm(pcm):                                # AdpcmStream's back end (N25): whole blocks, or the final one to be padded
+            from .core.audio_processor import adpcm_block_align, adpcm_samples_per_block
+            pcm = np.asarray(pcm, dtype=np.int16).reshape(-1)
+            if pcm.size == 0:
+                return np.zeros(0, np.uint8)
+            spb = adpcm_samples_per_block(adpcm_block_align(sample_rate if rate is None else rate))
+            return self.pcm_adpcm(up_(pcm), [[0, pcm.size, 0]], spb).cpu().numpy()
+
         return (resample if rate is not None and int(rate) != int(sample_rate) else None), \
-            (flac if encoding == "flac" else encode if encoding != "pcm16" else None)
+            (flac if encoding == "flac" else adpcm if encoding == "adpcm" else encode if encoding != "pcm16" else None)

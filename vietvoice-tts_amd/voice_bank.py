@@ -8,6 +8,7 @@ The reference re-opens the model tar, re-decodes and re-normalises the clip on e
 
   host   : RIFF/WAVE and FLAC container parsing (no arithmetic on samples), one descriptor row per clip
   device : vv_flac_index + vv_flac_decode = a FLAC clip's frames -> the same interleaved PCM bytes a WAV clip uploads (N17, RFC 9639)
+  device : vv_wav_decode = a G.711 or IMA ADPCM WAVE clip's data chunk -> interleaved int16 frames in that same buffer (N25, audioop's arithmetic)
   device : vv_ingest_pcm  = pydub set_channels(1) / set_frame_rate = audioop.tomono + audioop.ratecv, -> float32
            vv_normalize_clips = numpy-ordered float32 mean / peak / scale / int16 truncation
            -- bit-exact to AudioProcessor.load_audio (tests/test_ingest_gpu.py); clips of one ``ingest_many`` call batched on grid.y
@@ -26,7 +27,7 @@ from typing import Dict, List, Tuple, Union
 
 import numpy as np
 
-from .core.audio_processor import AudioProcessor, is_flac, ratecv_len, tomono
+from .core.audio_processor import AudioProcessor, WavError, is_flac, ratecv_len, tomono, wav_coded_frame_count, wav_container
 
 
 def resample_design(src: int, dst: int) -> Tuple[np.ndarray, int, int, int]:
@@ -41,6 +42,20 @@ def resample_design(src: int, dst: int) -> Tuple[np.ndarray, int, int, int]:
     n_pre_pad = down - half_len % down
     skip = (half_len + n_pre_pad) // down
     return np.concatenate([np.zeros(n_pre_pad), h]).astype(np.float64), up, down, skip
+
+
+def _coded_wav(data: bytes):
+    """The WavInfo of a RIFF/WAVE file whose format tag (WAVE_FORMAT_EXTENSIBLE resolved) is 6, 7 or 0x11 (N25), else None; what is
+    malformed is AudioProcessor.decode's to refuse, with the same error."""
+    if data[:4] != b"RIFF":
+        return None
+    try:
+        info = wav_container(data)
+    except WavError:
+        raise
+    except ValueError:
+        return None
+    return info if info.tag in (6, 7, 0x11) else None
 
 
 class VoiceEntry:
@@ -102,12 +117,17 @@ class VoiceBank:
             if flac and self.resampler != "ratecv":                                 # opt-in path: device-decoded frames come back
                 back = self._flac_frames(list(flac.values()))
                 flac = dict(zip(flac, back))
-            decoded = [flac[j] if j in flac and self.resampler != "ratecv" else None if j in flac else AudioProcessor.decode(d)
+            coded = {j: fi for j, fi in enumerate(_coded_wav(d) for d in raw) if fi is not None}      # N25: G.711 / IMA ADPCM, decoded on the device
+            if coded and self.resampler != "ratecv":
+                back = self._wav_frames(list(coded.values()))
+                coded = dict(zip(coded, back))
+            on_dev = {**flac, **coded}
+            decoded = [on_dev[j] if j in on_dev and self.resampler != "ratecv" else None if j in on_dev else AudioProcessor.decode(d)
                        for j, d in enumerate(raw)]                                   # host: container parsing only
             if any(d is not None and d[0].shape[0] == 0 for d in decoded):
                 raise ValueError("empty audio clip")
             if self.resampler == "ratecv":
-                x, lens = self._ingest_ratecv(decoded, dev, flac)
+                x, lens = self._ingest_ratecv(decoded, dev, flac, coded)
             else:
                 x, lens = self._ingest_polyphase(decoded, dev)
             off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -139,10 +159,22 @@ class VoiceBank:
             out.append((host[off: off + n * ch * width].view({1: np.int8, 2: np.int16, 4: np.int32}[width]).reshape(n, ch).copy(), width, rate))
         return out
 
-    def _ingest_ratecv(self, decoded, dev, flac=None):
+    def _wav_frames(self, infos):
+        """Coded WAVE clips (N25) -> [(frames (n, channels), 2, rate)] through the device decoder, copied back (the opt-in polyphase path)."""
+        pcm, res = self.synth.wav_clips(infos)
+        host, out = pcm.cpu().numpy(), []
+        for r in res:
+            if isinstance(r, Exception):
+                raise r
+            off, n, _width, rate, ch = r
+            out.append((host[off: off + n * ch * 2].view(np.int16).reshape(n, ch).copy(), 2, rate))
+        return out
+
+    def _ingest_ratecv(self, decoded, dev, flac=None, coded=None):
         """One vv_ingest_pcm launch for all clips: interleaved PCM bytes back to back (4-byte aligned) + descriptor rows.  A FLAC clip
         (``decoded[j] is None``, its file in ``flac[j]``) is decoded on the device (vv_flac_index / vv_flac_decode) into the same byte
-        buffer, behind the uploaded WAV clips: no decoded sample crosses the bus."""
+        buffer, behind the uploaded WAV clips: no decoded sample crosses the bus.  So is a G.711 or IMA ADPCM WAVE clip (its WavInfo in
+        ``coded[j]``; vv_wav_decode, N25): its size is the host's to know, so it lies between the two, on 16-byte boundaries."""
         import torch
         parts, clips, pos = [], {}, 0
         for j, d in enumerate(decoded):
@@ -156,16 +188,26 @@ class VoiceBank:
             pad = -len(raw) % 4
             parts.append(raw + b"\0" * pad)
             pos += len(raw) + pad
+        coded = coded or {}
+        c_offs, base = [], pos                            # the coded clips' places; ``base`` = where FLAC clips may start
+        for j in sorted(coded):
+            base = -(-base // 16) * 16
+            c_offs.append(base)
+            base += wav_coded_frame_count(coded[j]) * coded[j].channels * 2
+        base = -(-base // 4) * 4
+
+        def alloc(end):
+            buf = torch.empty((max(end, 16),), dtype=torch.uint8, device=dev)
+            if pos:
+                buf[:pos] = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
+            return buf
         if flac:
             def place(sizes):
-                offs, at = [], pos
+                offs, at = [], base
                 for n in sizes:
                     offs.append(at)
                     at += n + (-n % 4)
-                buf = torch.empty((max(at, 8),), dtype=torch.uint8, device=dev)
-                if pos:
-                    buf[:pos] = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
-                return buf, offs
+                return alloc(at), offs
             buf, res = self.synth.flac_clips([flac[j] for j in sorted(flac)], pcm_offsets=place)
             for j, r in zip(sorted(flac), res):
                 if isinstance(r, Exception):
@@ -176,8 +218,21 @@ class VoiceBank:
                 if ch > 2:                        # the same range check, on a copy of this clip alone
                     tomono(buf[off: off + n * ch * width].cpu().numpy().view({1: np.int8, 2: np.int16, 4: np.int32}[width]).reshape(n, ch))
                 clips[j] = (off, width, ch, n, rate)
+        elif coded:
+            buf = alloc(base)
         else:
             buf = torch.frombuffer(bytearray(b"".join(parts)), dtype=torch.uint8).to(dev)
+        if coded:
+            _pcm, res = self.synth.wav_clips([coded[j] for j in sorted(coded)], pcm_offsets=lambda sizes: (buf, c_offs))
+            for j, r in zip(sorted(coded), res):
+                if isinstance(r, Exception):
+                    raise r
+                off, n, width, rate, ch = r
+                if n == 0:
+                    raise ValueError("empty audio clip")
+                if ch > 2:                        # G.711 with more than two channels: the same range check, on a copy of this clip alone
+                    tomono(buf[off: off + n * ch * 2].cpu().numpy().view(np.int16).reshape(n, ch))
+                clips[j] = (off, width, ch, n, rate)
         desc, out_pos = [], 0
         for j in range(len(decoded)):
             off, width, ch, n, rate = clips[j]
